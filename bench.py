@@ -20,11 +20,12 @@ over RCCL inside the CG).
 
 Prints ONE JSON line (rank 0): metric DOF/s = nDOF * K / t, plus
   roofline     achieved HBM GB/s of the dominant kernel (the BSELL-64 SpMV), from HIP events
-               around every SpMV launch of the timed solves, against 8 TB/s -- and against what a read-only
+               around every SpMV launch of the timed solves, against 8 TB/s -- and (--full) against what a read-only
                sweep of K's resident values reaches on THIS box (stream_GBs, frac_of_stream);
-  cpu_baseline the CPU oracle (a port of the reference algorithm) on a bounded sample;
-  secondary    (N = 1, default workload) BASELINE.json's other single-GPU configs, 100^3 ... 400^3, as child processes
+  cpu_baseline (--full) the CPU oracle (a port of the reference algorithm) on a bounded sample;
+  secondary    (--full, N = 1, default workload) BASELINE.json's other single-GPU configs, 100^3 ... 400^3, as child processes
                BEHIND the measured line: a signal or a stall there prints the line as measured (bench_legs.py).
+A plain run only sets up, warms up, times the steps, writes --dump-outputs DIR and prints the line; --full adds the rest.
 The merit-function stop of ALGLIB's lincg (termination type 7) is switched OFF here and in
 the CPU baseline: with it the reference algorithm gives up near 1e-7 on cubes of this size
 and would never reach the 1e-8 the metric names.
@@ -80,6 +81,9 @@ def build_parser():
     A("--no-secondary", action="store_true",
       help="N = 1, default workload: skip the `secondary` legs (100^3, 200^3, FIXED-48, console driver, PMC traffic, k_recover, 400^3)")
     A("--secondary-budget", type=float, default=600.0, help="seconds all secondary legs may take together")
+    A("--full", action="store_true", help="also what the headline does not need: CPU baseline, stream yardstick, transport "
+                                          "probe (N > 1), secondary legs (N = 1); a plain run sets up, warms up, times, reports")
+    A("--dump-outputs", metavar="DIR", help="write what the last timed step computed (U sample, U norms, CG report) as DIR/*.npy")
     return ap
 
 
@@ -266,10 +270,12 @@ def measure(R, dog):
         dist.all_gather(allb, buf)
         rank_devices = [json.loads(bytes(b.cpu().tolist()).rstrip(b"\0").decode()) for b in allb]
     dog.touch("report")
+    R.last_rep = rep   # (what the last timed step returned, next to its U in R.d_U: --dump-outputs)
     ok = rep["terminationtype"] == 1 and rep["rel_residual"] <= args.eps
     if rank != 0:
         return None, ok
-    stream = R.stream_probe()     # outside the timed region: what a read-only sweep of K's values reaches on THIS box
+    # --full: outside the timed region, what a read-only sweep of K's values reaches on THIS box
+    stream = R.stream_probe() if args.full else None
     avg_ms = spmv_ms / max(spmv_n, 1)
     # HBM traffic per launch: the committed PMC passes of this workload (tools/pmc_run.sh) unless this run's own
     # secondary leg measures it (main) -- counters cannot be read from inside the measured process
@@ -398,7 +404,7 @@ def main():
         time.sleep(3600)
     out, ok = measure(R, dog)
     if rank == 0:
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             dog.stop()   # the CPU sample is bounded by its size, not by the watchdog
             out["cpu_baseline"], out["cpu_baseline_all_cores"] = LEGS.cpu_baseline(args.cpu_n, args.eps)
             if args.watchdog > 0:
@@ -408,7 +414,7 @@ def main():
         # the CPU port on the WORKLOAD itself (not the in-run sample): a committed run of tests/golden/
         # make_bench_mode_golden.py on a GPU box's host (8 min at 148^3: --cpu-n 148 repeats it here).  When ONE
         # speed-up is quoted, quote value / cpu_baseline.value: that one is of this run.
-        at_wl = LEGS.cpu_at_workload(args.n) if args.knockout == 0 and args.etype == 2 else None
+        at_wl = LEGS.cpu_at_workload(args.n) if args.full and args.knockout == 0 and args.etype == 2 else None
         if at_wl and ok:
             out["cpu_baseline_at_workload"] = at_wl
             out["speedup_vs_cpu_at_workload"] = out["value"] / at_wl["value"]
@@ -422,11 +428,13 @@ def main():
         if not ok2:
             out["then_fixed48"]["error"] = out2.get("error")
         args.fixed48, R.prec = False, R.hip.PREC_FP64
+    if args.dump_outputs and rank == 0:   # (every rank holds the whole U after the solve's final gather)
+        BL.dump_outputs(args.dump_outputs, R.d_U.cpu().numpy(), R.last_rep)
     line = json.dumps(out) if rank == 0 else None
     # From here on everything is OPTIONAL work behind a finished measurement, in child processes: whatever happens in there
     # (a stall, a GPU fault, an abort inside RCCL or an IPC mapping, an outer timeout's SIGTERM), the line measured above is
     # printed and the exit code is 0 (bench_launch.hold_line).
-    if world > 1 and not args.no_p2p_probe and not args.p2p and ok:
+    if args.full and world > 1 and not args.no_p2p_probe and not args.p2p and ok:
         BL.hold_line(dog, line)
         dog.optional = True
         dog.bound = float(args.probe_watchdog) * (len(BL.PROBE_LEGS) + 1) + 300.0   # (the children carry the real bound)
@@ -443,7 +451,7 @@ def main():
             line = json.dumps(out)
         BL.hold_line(dog, line)
     # N = 1, the default workload: BASELINE.json's other single-GPU configurations behind the headline (child processes)
-    if (world == 1 and rank == 0 and ok and not args.no_secondary and args.n == 148 and args.etype == 2 and args.knockout == 0
+    if (args.full and world == 1 and rank == 0 and ok and not args.no_secondary and args.n == 148 and args.etype == 2 and args.knockout == 0
             and not args.mixed and not args.fixed48 and not args.then_fixed48 and args.max_its == 0):
         BL.hold_line(dog, line)
         dog.optional = True

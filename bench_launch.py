@@ -1,8 +1,8 @@
 """bench_launch.py -- what surrounds bench.py's measurement when more than one GPU is involved (and what keeps a run from
 hanging): the progress watchdog, the self-launcher of `python bench.py --gpus N`, the one-process form
 (stan_hip_init_multi), and the transport probe {classic, single-reduction} x {RCCL, peer to peer} that runs in child
-processes behind a multi-rank measurement.  bench.py holds the N = 1 path and the JSON line; bench_legs.py the CPU
-baseline and the secondary single-GPU legs.  Nothing here is timed as part of `value`."""
+processes behind a multi-rank measurement (--full), and what --dump-outputs writes.  bench.py holds the N = 1 path and
+the JSON line; bench_legs.py the CPU baseline and the secondary single-GPU legs.  Nothing here is timed as part of `value`."""
 import json
 import os
 import sys
@@ -87,6 +87,29 @@ def error_line(args, world, msg, **extra):
     line.update(extra)
     return json.dumps(line)
 
+
+DUMP_ROWS = 1 << 21   # rows of U that --dump-outputs writes when U is longer (16 MB of fp64, the same again for their indices)
+
+
+def dump_outputs(path, U, rep):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step, as float64 .npy files (< 64 MB):
+      U_sample.npy       U at the rows of U_sample_rows.npy: all rows up to DUMP_ROWS, else DUMP_ROWS rows drawn with a
+                         fixed seed (the same rows for the same workload, run after run)
+      U_sample_rows.npy  those row indices (exact in float64)
+      U_norms.npy        sum, sum |U|, ||U||_2, max |U| over ALL of U
+      cg_report.npy      termination type, iterations, rel_residual"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    U = np.asarray(U, dtype=np.float64).ravel()
+    rows = (np.arange(U.size) if U.size <= DUMP_ROWS else
+            np.sort(np.random.default_rng(148).choice(U.size, DUMP_ROWS, replace=False)))
+    a = np.abs(U)
+    out = {"U_sample": U[rows], "U_sample_rows": rows.astype(np.float64),
+           "U_norms": np.array([U.sum(), a.sum(), np.linalg.norm(U), a.max() if U.size else 0.0]),
+           "cg_report": np.array([rep["terminationtype"], rep["iterations"], rep["rel_residual"]], dtype=np.float64)}
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
 def hold_line(dog, line):
     """once the headline is measured, optional work behind it (secondary legs, the transport probe)
     must not be able to cost it.  The finished line is (1) what the watchdog prints if that work stalls (`dog.held_line`),
@@ -155,6 +178,8 @@ def launch_ranks(args, argv):
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
+    if args.dump_outputs:   # (the ranks run in ROOT: the caller's relative DIR, made absolute; the last one given counts)
+        argv = list(argv) + ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), BENCH] + list(argv)
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
@@ -286,6 +311,8 @@ def run_one_process(args):
     if not ok:
         out["error"] = "CG ended with type %d at %.3e (> eps %.0e): no DOF/s reported" % (
             rep["terminationtype"], rep["rel_residual"], args.eps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, U, rep)
     print(json.dumps(out), flush=True)
     dog.stop()
     ctx.close()

@@ -125,7 +125,7 @@ def _leg_summary(d):
 
 
 def _bench_leg(extra, timeout, steps=2, warmup=1):
-    d, why = _child_json([sys.executable, BENCH, "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--no-cpu",
+    d, why = _child_json([sys.executable, BENCH, "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-cpu",
                           "--no-secondary"] + extra, timeout)
     return _leg_summary(d) if d is not None else {"error": why}
 
@@ -150,7 +150,7 @@ def _n400_leg(timeout):
     avail_gb = _host_mem_available_gb()
     if avail_gb < 48:   # (the child's mesh, DOF tables and incidence lists take ~20 GB of host memory: never drive a box out of memory)
         return [{"leg": "config 5's size: 400^3", "error": "skipped: %.0f GB of host memory available, the 400^3 set-up wants 48" % avail_gb}]
-    d, why = _child_json([sys.executable, BENCH, "--gpus", "1", "--size", "400", "--steps", "1", "--warmup", "0", "--no-cpu",
+    d, why = _child_json([sys.executable, BENCH, "--gpus", "1", "--size", "400", "--steps", "1", "--warmup", "0", "--full", "--no-cpu",
                           "--no-secondary", "--then-fixed48", "--watchdog", str(int(timeout))], timeout)
     if d is None:
         return [{"leg": "config 5's size: 400^3 fp64", "error": why}]

@@ -179,3 +179,63 @@ time.sleep(60)
     out, err = p.communicate(timeout=20)
     assert p.returncode == 0 and json.loads(out.strip().splitlines()[-1])["secondary"] == [1]
     assert "the measured line stands" in err
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_u_in_float64(tmp_path):
+    """--dump-outputs DIR: U of the last timed step (all of it when short, else a fixed seeded sample of rows with their
+    indices), U's norms over all rows and the CG report, as float64 .npy files, 64 MB at most for the headline's U."""
+    import numpy as np
+    import bench_launch as BL
+    rep = {"terminationtype": 1, "iterations": 1335, "rel_residual": 9.7e-9}
+    U = np.random.default_rng(1).standard_normal(9923847 - 3 * 149 * 149)     # the 148^3 workload's reduced system
+    for d in ("a", "b"):
+        BL.dump_outputs(str(tmp_path / d), U, rep)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["U_norms.npy", "U_sample.npy", "U_sample_rows.npy", "cg_report.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    got = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert all(np.array_equal(a, np.load(tmp_path / "b" / f)) for f, a in got.items())    # the same rows, run after run
+    rows = got["U_sample_rows.npy"].astype(np.int64)
+    assert len(rows) == BL.DUMP_ROWS and np.all(np.diff(rows) > 0) and rows[-1] < len(U)
+    assert np.array_equal(got["U_sample.npy"], U[rows])
+    assert np.allclose(got["U_norms.npy"], [U.sum(), np.abs(U).sum(), np.linalg.norm(U), np.abs(U).max()], rtol=1e-12)
+    assert list(got["cg_report.npy"]) == [1.0, 1335.0, 9.7e-9]
+    BL.dump_outputs(str(tmp_path / "c"), U[:1000], rep)                        # short: every row
+    assert np.array_equal(np.load(tmp_path / "c" / "U_sample.npy"), U[:1000])
+
+
+def test_a_plain_run_leaves_the_extras_to_full():
+    """A plain bench.py run does only what its headline needs; the CPU figures, the stream yardstick, the transport probe
+    and the secondary legs are behind --full (off by default)."""
+    import bench
+    a = bench.build_parser().parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not a.full and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    assert bench.build_parser().parse_args(["--full", "--dump-outputs", "d"]).full
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_dumps_what_its_last_step_computed(built_libs, oracle, tmp_path):
+    """python bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR on a small cube: exactly the timed steps, the line
+    with ms_per_step and none of the --full extras, and DIR holds U of the last step -- the oracle's answer."""
+    import numpy as np
+    from stan_amd import problem
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--size", "8", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, cwd=ROOT, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["config"]["converged"]
+    import bench_launch
+    assert (d["metric"], d["unit"], d["higher_is_better"], d["dtype"]) == (bench_launch.METRIC, "DOF/s", True, "f64")
+    assert d["cpu_baseline"] is None and "secondary" not in d and d["roofline"]["stream_GBs"] is None
+    job = problem.cube_job(8)
+    U = np.load(tmp_path / "U_sample.npy")
+    assert np.array_equal(np.load(tmp_path / "U_sample_rows.npy"), np.arange(job.n_red, dtype=np.float64))
+    rep = np.load(tmp_path / "cg_report.npy")
+    assert rep[0] == 1 and rep[1] == d["config"]["cg_iterations"] and rep[2] == d["config"]["rel_residual"]
+    rc, A = oracle.assemble(job.xyz, job.node_dof, job.conn, job.elem_mat, job.elem_type, job.mat_E_nu, job.red)
+    assert rc == 0
+    Uo, _ = oracle.cg(A, job.F, 1e-8, merit_stop=False)
+    assert np.abs(U - Uo).max() <= 1e-6 * np.abs(Uo).max()

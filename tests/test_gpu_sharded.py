@@ -297,7 +297,7 @@ def test_bench_gpus_2_without_a_launcher(built_libs):
     """`python bench.py --gpus 2` with WORLD_SIZE unset starts its two rank processes itself
     (fresh children, the parent never touches the GPU), relays ONE JSON line and the exit code; the line carries the
     capped comparison of the two transports and says which one it would select."""
-    out = _bench_no_launcher(["--gpus", "2", "--steps", "1", "--warmup", "1", "--size", "16", "--no-cpu",
+    out = _bench_no_launcher(["--gpus", "2", "--steps", "1", "--warmup", "1", "--size", "16", "--full", "--no-cpu",
                               "--probe-its", "40"], {})
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -326,7 +326,7 @@ def test_bench_probe_that_crashes_leaves_the_line_alone(built_libs):
     """a HARD failure inside the probe -- here rank 1's probe process aborts (test hook) in front of its
     first peer-to-peer leg, as a GPU fault or an abort inside RCCL / an IPC mapping would -- must not cost the measurement:
     the probe runs in child processes, the measured ranks print their line unchanged and end with code 0."""
-    out = _bench_no_launcher(["--gpus", "2", "--steps", "1", "--warmup", "1", "--size", "12", "--no-cpu",
+    out = _bench_no_launcher(["--gpus", "2", "--steps", "1", "--warmup", "1", "--size", "12", "--full", "--no-cpu",
                               "--probe-its", "20", "--probe-watchdog", "10"], {"STAN_BENCH_TEST_CRASH_PROBE": "1"})
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -343,7 +343,7 @@ def test_bench_probe_that_stalls_leaves_the_line_alone(built_libs):
     """The transport probe is an optional extra behind the measurement: rank 1 never enters its peer-to-peer leg
     (test hook), rank 0 blocks in the collective set-up; the probe's own watchdog prints the measured line
     unchanged and the job ends with code 0."""
-    out = _bench_no_launcher(["--gpus", "2", "--steps", "1", "--warmup", "1", "--size", "12", "--no-cpu",
+    out = _bench_no_launcher(["--gpus", "2", "--steps", "1", "--warmup", "1", "--size", "12", "--full", "--no-cpu",
                               "--probe-its", "20", "--probe-watchdog", "8"], {"STAN_BENCH_TEST_HANG_PROBE": "1"})
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -186,44 +186,63 @@ def test_replacement_methods_call_only_declared_imports_with_declared_arity():
     assert re.search(r"e\.dS\[a\]\.SetFast\(c, 0, stress\[48 \* i \+ 6 \* a \+ c\]\)", t)
 
 
-REF = "/root/reference/src"
+# What the reference's sources say, recorded by tests/golden/make_reference_facts.py from a checkout of the reference
+# (regenerate it there with the path to the checkout's src/): for every (file, pattern) of REF_DECLS whether the pattern
+# matches, for every (file, text) of REF_CALL_SITES the lines that hold the text, and a digest of the Console.Write*
+# literals of every method of CONSOLE_REF.  Names, line numbers and digests only: no source text of the reference.
+REF_FACTS = os.path.join(ROOT, "tests", "golden", "reference_facts.json")
+REF_DECLS = [
+    ("STAN_Database/Node.cs", p) for p in (
+        r"public\s+int\s+ID\b", r"public\s+double\s+X\b", r"public\s+double\s+Y\b", r"public\s+double\s+Z\b",
+        r"public\s+int\[\]\s+DOF\b", r"public\s+double\[\]\s+dU_buffer\b")] + [
+    ("STAN_Database/Element.cs", p) for p in (
+        r"public\s+int\s+ID\b", r"public\s+string\s+Type\b", r"public\s+int\s+MatID\b", r"public\s+List<int>\s+NList\b",
+        r"public\s+MatrixST\[\]\s+dE\b", r"public\s+MatrixST\[\]\s+dS\b", r"public\s+void\s+Update_StrainStress\(int\s+\w+\)",
+        r"public\s+void\s+Initialize_Increment\(int\s+\w+\)")] + [
+    ("STAN_Database/Material.cs", p) for p in (
+        r"public\s+int\s+ID\b", r"public\s+double\s+E\b", r"public\s+double\s+Poisson\b")] + [
+    ("STAN_Database/Database.cs", p) for p in (
+        r"public\s+Dictionary<int,\s*Node>\s+NodeLib\b", r"public\s+Dictionary<int,\s*Element>\s+ElemLib\b",
+        r"public\s+Dictionary<int,\s*Material>\s+MatLib\b", r"public\s+int\s+nDOF\b", r"public\s+Analysis\s+AnalysisLib\b")] + [
+    ("STAN_Database/Analysis.cs", p) for p in (
+        r"public\s+double\s+GetLinSolverTolerance\(\)", r"public\s+int\s+GetLinSolverMaxIter\(\)",
+        r"public\s+string\s+GetLinSolver\(\)")] + [
+    ("STAN_Database/MatrixST.cs", r"public\s+void\s+SetFast\(int\s+\w+,\s*int\s+\w+,\s*double\s+\w+\)")]
+# the call sites the shim replaces, at the (1-based) lines INTEGRATION.md gives
+REF_CALL_SITES = [
+    ("STAN_Solver/Solver.cs", "Fun.ParallelAssembly_K(DB, nDOF_reduction, inc", 156),
+    ("STAN_Solver/Solver.cs", "Fun.LinearSolver_CG(K, F, DB.AnalysisLib)", 162),
+    ("STAN_Solver/Solver.cs", "Elem.Recovery_Stress(DB)", 186),
+    ("STAN_Solver/Solver.cs", "E.Update_StrainStress(inc)", 209),
+    ("STAN_Solver/SolverFunctions.cs", "ParallelAssembly_K(", 117),
+    ("STAN_Solver/SolverFunctions.cs", "LinearSolver_CG(", 270),
+]
+
+
+def ref_key(*parts):
+    return " :: ".join(str(p) for p in parts)
+
+
+def literals_digest(literals):
+    import hashlib
+    import json
+    return hashlib.sha256(json.dumps(literals).encode()).hexdigest()
+
+
+def _ref_facts():
+    import json
+    return json.load(open(REF_FACTS))
 
 
 def test_shim_uses_only_members_the_reference_declares():
     """integration/SolverFunctions.Hip.cs is written against the reference's object model without a compiler to check
-    it: every member it touches must exist, public, in the reference's sources (checked HERE, where the checkout is
-    present; the GPU box has none and skips).  Reads the reference, copies nothing."""
-    import pytest
-    if not os.path.isdir(REF):
-        pytest.skip("no reference checkout on this machine")
-
-    def src(rel):
-        return open(os.path.join(REF, rel), encoding="utf-8-sig").read()
-    node, elem, mat = src("STAN_Database/Node.cs"), src("STAN_Database/Element.cs"), src("STAN_Database/Material.cs")
-    db, ana, mst = src("STAN_Database/Database.cs"), src("STAN_Database/Analysis.cs"), src("STAN_Database/MatrixST.cs")
-    need = [
-        (node, r"public\s+int\s+ID\b"), (node, r"public\s+double\s+X\b"), (node, r"public\s+double\s+Y\b"),
-        (node, r"public\s+double\s+Z\b"), (node, r"public\s+int\[\]\s+DOF\b"), (node, r"public\s+double\[\]\s+dU_buffer\b"),
-        (elem, r"public\s+int\s+ID\b"), (elem, r"public\s+string\s+Type\b"), (elem, r"public\s+int\s+MatID\b"),
-        (elem, r"public\s+List<int>\s+NList\b"), (elem, r"public\s+MatrixST\[\]\s+dE\b"), (elem, r"public\s+MatrixST\[\]\s+dS\b"),
-        (elem, r"public\s+void\s+Update_StrainStress\(int\s+\w+\)"), (elem, r"public\s+void\s+Initialize_Increment\(int\s+\w+\)"),
-        (mat, r"public\s+int\s+ID\b"), (mat, r"public\s+double\s+E\b"), (mat, r"public\s+double\s+Poisson\b"),
-        (db, r"public\s+Dictionary<int,\s*Node>\s+NodeLib\b"), (db, r"public\s+Dictionary<int,\s*Element>\s+ElemLib\b"),
-        (db, r"public\s+Dictionary<int,\s*Material>\s+MatLib\b"), (db, r"public\s+int\s+nDOF\b"),
-        (db, r"public\s+Analysis\s+AnalysisLib\b"),
-        (ana, r"public\s+double\s+GetLinSolverTolerance\(\)"), (ana, r"public\s+int\s+GetLinSolverMaxIter\(\)"),
-        (ana, r"public\s+string\s+GetLinSolver\(\)"),
-        (mst, r"public\s+void\s+SetFast\(int\s+\w+,\s*int\s+\w+,\s*double\s+\w+\)"),
-    ]
-    for text, pat in need:
-        assert re.search(pat, text), pat
+    it: every member it touches must exist, public, in the reference's sources (as recorded in REF_FACTS)."""
+    facts = _ref_facts()
+    for rel, pat in REF_DECLS:
+        assert facts["declarations"][ref_key(rel, pat)] is True, (rel, pat)
     # the call sites the shim replaces are where INTEGRATION.md says they are
-    solver = src("STAN_Solver/Solver.cs").split("\n")
-    assert "Fun.ParallelAssembly_K(DB, nDOF_reduction, inc" in solver[155]            # Solver.cs:156
-    assert "Fun.LinearSolver_CG(K, F, DB.AnalysisLib)" in solver[161]                 # Solver.cs:162
-    assert "Elem.Recovery_Stress(DB)" in solver[185] and "E.Update_StrainStress(inc)" in solver[208]
-    fun = src("STAN_Solver/SolverFunctions.cs").split("\n")
-    assert "ParallelAssembly_K(" in fun[116] and "LinearSolver_CG(" in fun[269]       # SolverFunctions.cs:117, :270
+    for rel, text, line in REF_CALL_SITES:
+        assert line in facts["call_sites"][ref_key(rel, text)], (rel, text, line)
     # and every member access of the shim on those objects is in the list above
     shim = _strip_c_comments(open(SHIM2).read())
     for m in set(re.findall(r"\b(?:n|e|m)\.(\w+)", shim)):
@@ -266,15 +285,13 @@ CONSOLE_REF = {
 def test_the_shim_prints_the_reference_console_lines_literal_by_literal():
     """`integration/SolverFunctions.Hip.cs` printed " (type N, M iterations)" where the reference
     prints " (type N)" (SolverFunctions.cs:325).  Every Console.Write* literal of the two replaced methods is compared
-    with the reference's -- against the list above everywhere, and against the reference's own source where the
-    checkout is present (this container; the GPU box has none)."""
+    with the reference's -- against the list above, and the list above against the digest of the reference's own
+    literals (REF_FACTS)."""
     shim = _strip_c_comments(open(SHIM2).read())
+    facts = _ref_facts()
     for name, want in CONSOLE_REF.items():
         assert _console_literals(_method_body(shim, name)) == want, name
-    if os.path.isdir(REF):
-        ref = _strip_c_comments(open(os.path.join(REF, "STAN_Solver", "SolverFunctions.cs"), encoding="utf-8-sig").read())
-        for name, want in CONSOLE_REF.items():
-            assert _console_literals(_method_body(ref, name)) == want, name
+        assert facts["console_literals_sha256"][name] == literals_digest(want), name
     # the native console driver (stan_amd/host/solver_functions.cpp) prints the same text through printf
     cpp = open(os.path.join(ROOT, "stan_amd", "host", "solver_functions.cpp")).read()
     for lit in ('"   K Matrix assembly: "', '"          Done in %.2fs\\n"', '"   Solving linear system...   "',

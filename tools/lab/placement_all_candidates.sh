@@ -5,7 +5,7 @@
 N=${1:-5}
 for i in $(seq 1 $N); do
   echo "== process $i"
-  STAN_PLACEMENT_TRACE=all python bench.py --steps 3 --warmup 1 --no-cpu --no-secondary 2> /tmp/pl_$i.err | python -c "
+  STAN_PLACEMENT_TRACE=all python bench.py --steps 3 --warmup 1 --full --no-cpu --no-secondary 2> /tmp/pl_$i.err | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; c=d['config']
 print('   value %.4e  spmv %.4f ms  frac %.3f  of stream %.3f  search %s' % (d['value'], r['avg_launch_ms'], r['frac'], r['frac_of_stream'], c['placement_search']))"

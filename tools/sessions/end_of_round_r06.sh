@@ -11,7 +11,7 @@ cd $R
 python3 __graft_entry__.py smoke > $OUT/smoke.txt 2>&1; echo "smoke rc=$?"; tail -1 $OUT/smoke.txt
 timeout 3000 python3 -m pytest tests -m gpu -q --durations=20 > $OUT/pytest_gpu.txt 2>&1
 echo "pytest rc=$?"; tail -4 $OUT/pytest_gpu.txt | cut -c1-300
-timeout 1500 python3 bench.py > $OUT/bench_default_flags.json 2> $OUT/bench_err.txt
+timeout 1500 python3 bench.py --full > $OUT/bench_default_flags.json 2> $OUT/bench_err.txt
 cut -c1-300 $OUT/bench_default_flags.json
 timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-secondary > $OUT/bench_driver_command_steps20_warmup5.json 2>> $OUT/bench_err.txt
 cut -c1-200 $OUT/bench_driver_command_steps20_warmup5.json
@@ -29,6 +29,6 @@ grep -E "k_numeric|k_spmv<|k_spmv2|k_update|k_step|k_value_stream" $OUT/pmc_fetc
 python3 tools/pmc_spmv_json.py $OUT/pmc_fetch_write_n148.txt $OUT/pmc_spmv.json 148 6698765463 "round 6, tools/sessions/end_of_round_r06.sh: two rocprofv3 --pmc passes over one step of bench.py's default workload" >> $OUT/bench_err.txt 2>&1
 rm -rf $OUT/pmc/FETCH_SIZE $OUT/pmc/WRITE_SIZE
 export STAN_RCCL_LIB=$R/tests/fake_rccl/libfake_rccl.so STAN_BENCH_BACKEND=gloo STAN_BENCH_DEVICE=0 GPU_MAX_HW_QUEUES=20 FAKE_RCCL_ASYNC=1
-timeout 900 python3 bench.py --gpus 2 --steps 1 --warmup 1 --no-cpu > $OUT/bench_gpus2_dry_run_on_one_gpu_async_stand_in.json 2> $OUT/bench_gpus2.err
-timeout 1200 python3 bench.py --gpus 8 --steps 1 --warmup 1 --no-cpu --size 100 > $OUT/bench_gpus8_n100_dry_run_on_one_gpu_async_stand_in.json 2> $OUT/bench_gpus8.err
+timeout 900 python3 bench.py --gpus 2 --steps 1 --warmup 1 --full --no-cpu > $OUT/bench_gpus2_dry_run_on_one_gpu_async_stand_in.json 2> $OUT/bench_gpus2.err
+timeout 1200 python3 bench.py --gpus 8 --steps 1 --warmup 1 --full --no-cpu --size 100 > $OUT/bench_gpus8_n100_dry_run_on_one_gpu_async_stand_in.json 2> $OUT/bench_gpus8.err
 echo done > $OUT/done.txt
