@@ -21,6 +21,7 @@
 #include <chrono>
 #include <cmath>
 #include <thread>
+#include <type_traits>
 
 #include "internal.h"
 #include "p2p_device.h"
@@ -242,114 +243,138 @@ inline colstream fold_cols_of(const stan_ctx *ctx, const stan_matrix *K) {
     return ctx->cols16 && K->d_fold_cols16 ? make_colstream(K->d_fold_cols16, K->d_fold_colbase, K->d_fold_pair_ptr, K->d_fold_packed, K->nfslots)
                                            : NO_COLSTREAM;
 }
+inline colstream colstream_of(const stan_ctx *ctx, const stan_matrix *K) {
+    return ctx->cols16 && K->d_cols16 ? make_colstream(K->d_cols16, K->d_colbase, K->d_pair_ptr, K->d_slice_packed, K->nslots) : NO_COLSTREAM;
+}
+// length of a gather vector of K (NOTE on the halo layout, below): the owned rows padded to whole slices, or the owned
+// rows and the halo columns behind them, whichever is longer
+inline int64_t gather_len(const stan_matrix *K) {
+    const int64_t npad = (int64_t)K->nslices * 64;
+    return 3 * (npad > K->nloc + K->nhalo ? npad : K->nloc + K->nhalo);
+}
+// status words for kernels launched outside a solve: never stopped
+int alloc_never_stopped(stan_ctx *ctx, dev_bufs &b, int64_t **stt, hipStream_t s) {
+    STANCHK(alloc(ctx, b, stt, (size_t)T_NSTAT));
+    const int64_t init[T_NSTAT] = {0x7fffffffffffffffLL, 0x7fffffffffffffffLL, 0, 0, 0, 0, 0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(*stt, init, sizeof(init), hipMemcpyHostToDevice, s));
+    return STAN_OK;
+}
+
+// One product, as it is enqueued: y = A x with `dot` sums (k_spmv's DOT), or -- x2 given, dot = 1 -- y = A x and
+// y2 = A x2 in one pass over the matrix.
+struct product_args {
+    const double *x;
+    double *y;
+    const double *x2;
+    double *y2;
+    int dot;
+    double *partial;
+    const int64_t *st;
+    int64_t k;
+    int kind;           // the value stream (STAN_PREC_*)
+    const void *vals;   // nullptr: K's own stream of that kind
+    bool first;         // the first product of an unscaled fp64 matrix scales it on the way (k_spmv_first)
+};
+// the run-time choices of a product -- value stream and DOT -- as the types of f's arguments
+template <typename F>
+void with_product_types(const stan_matrix *K, const product_args &a, F f) {
+    auto by_dot = [&](auto *vals) {
+        if (a.dot == 2) f(vals, std::integral_constant<int, 2>());
+        else if (a.dot == 1) f(vals, std::integral_constant<int, 1>());
+        else f(vals, std::integral_constant<int, 0>());
+    };
+    if (a.kind == STAN_PREC_MIXED) by_dot(a.vals ? (const float *)a.vals : K->d_vals32);
+    else if (a.kind == STAN_PREC_FIXED48) by_dot(a.vals ? (const uint32_t *)a.vals : K->d_vals48);
+    else by_dot(a.vals ? (const double *)a.vals : K->d_vals);
+}
 // which: 0 = all slices, 1 = interior list, 2 = boundary list (partials offset by the
 // interior launch's block count).  Returns the number of partial slots this launch writes.
 // `fold`: counter/out of the folded reduction (counter == nullptr: partials only); nblocks and np
 // are filled in here (np = this launch's slots + poff: the boundary launch of a split product
 // also adds up what the interior launch left).
-template <typename VT, int DOT>
-unsigned launch_spmv(stan_ctx *ctx, stan_matrix *K, const VT *vals, const double *x, double *y,
-                     double *partial, const int64_t *st, int64_t k, int which = 0,
-                     hipStream_t stream = nullptr, fold_args fold = NO_FOLD) {
+unsigned launch_product(stan_ctx *ctx, stan_matrix *K, const product_args &a, int which = 0, hipStream_t stream = nullptr,
+                        fold_args fold = NO_FOLD) {
     if (!stream) stream = ctx->stream;
     const int32_t *slist = which == 1 ? K->d_sl_int : which == 2 ? K->d_sl_bnd : nullptr;
     const int32_t nlist = which == 1 ? K->n_sl_int : which == 2 ? K->n_sl_bnd : K->nslices;
-    const colstream cs = ctx->cols16 && K->d_cols16 ? make_colstream(K->d_cols16, K->d_colbase, K->d_pair_ptr, K->d_slice_packed, K->nslots)
-                                                    : NO_COLSTREAM;
-    if (stan_small_system(ctx, K)) {   // one workgroup per slice (k_spmv_small); partials per slice
-        const int32_t poff_s = which == 2 ? K->n_sl_int : 0;
-        const unsigned grid_s = (unsigned)nlist;
-        if (grid_s == 0) return 0;
-        fold.nblocks = grid_s;
-        fold.np = (int)grid_s + poff_s;
-        hipLaunchKernelGGL((k_spmv_small<VT, DOT>), dim3(grid_s), dim3(256), 0, stream, K->nslices, K->nloc,
-                           K->d_slot_ptr, K->d_rowof, K->d_cols, vals, x, y, partial, st, k, slist, nlist, poff_s, fold, cs);
-        return grid_s;
-    }
-    if (stan_pair_kernel(ctx)) {   // two wavefronts per slice, two slices per workgroup (k_spmv_pair; STAN_OPT_SPMV_VARIANT 20)
-        const int32_t poff_p = which == 2 ? (int32_t)nblk(K->n_sl_int, 2) : 0;
-        const unsigned grid_p = nblk(nlist, 2);
-        if (grid_p == 0) return 0;
-        fold.nblocks = grid_p;
-        fold.np = (int)grid_p + poff_p;
-        hipLaunchKernelGGL((k_spmv_pair<VT, DOT, true>), dim3(grid_p), dim3(256), 0, stream, K->nslices, K->nloc,
-                           K->d_slot_ptr, K->d_rowof, K->d_cols, vals, x, y, partial, st, k, slist, nlist, poff_p, fold, cs);
-        return grid_p;
-    }
-    const int32_t poff = which == 2 ? (int32_t)nblk(K->n_sl_int, 4) : 0;
-    const unsigned grid = nblk(nlist, 4);
+    // slices per workgroup: one (k_spmv_small) or two (k_spmv_pair; STAN_OPT_SPMV_VARIANT 20) for a single product
+    // that is not a matrix's first, four for every other kernel
+    const bool plain = !a.x2 && !a.first, small = plain && stan_small_system(ctx, K), pair = plain && !small && stan_pair_kernel(ctx);
+    const int spb = small ? 1 : pair ? 2 : 4;
+    const int32_t poff = which == 2 ? (int32_t)nblk(K->n_sl_int, spb) : 0;
+    const unsigned grid = nblk(nlist, spb);
     if (grid == 0) return 0;
     fold.nblocks = grid;
     fold.np = (int)grid + poff;
-    if (const VT *fv = fold_vals<VT>(ctx, K, vals)) {
-        hipLaunchKernelGGL((k_spmv_fold<VT, DOT, 1>), dim3(grid), dim3(256), 0, stream, K->nslices, K->nloc, K->d_fold_ptr,
-                           K->d_rowof, K->d_fold_meta, K->d_fold_cols, fv, x, (const double *)nullptr, y, (double *)nullptr,
-                           partial, st, k, slist, nlist, poff, fold, fold_cols_of(ctx, K));
-        return grid;
-    }
-#define SPMV_CASE(V)                                                                          \
-    case V:                                                                                   \
-        hipLaunchKernelGGL((k_spmv<VT, DOT, V>), dim3(grid), dim3(256), 0, stream, K->nslices, \
-                           K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols, vals, x, y, partial, st, k, \
-                           slist, nlist, poff, fold, cs);                                     \
+    const colstream cs = colstream_of(ctx, K);
+    with_product_types(K, a, [&](auto *vals, auto dot_tag) {
+        using VT = std::remove_cv_t<std::remove_pointer_t<decltype(vals)>>;
+        constexpr int DOT = decltype(dot_tag)::value;
+        const dim3 g(grid), b(256);
+        const VT *fv = small || pair || a.first ? nullptr : fold_vals<VT>(ctx, K, vals);
+        if constexpr (std::is_same_v<VT, double>)
+            if (a.first) {
+                hipLaunchKernelGGL(k_spmv_first<DOT>, g, b, 0, stream, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols,
+                                   K->d_vals, K->d_scale, a.x, a.y, a.partial, a.st, a.k, fold, cs);
+                return;
+            }
+        if constexpr (DOT == 1)
+            if (a.x2) {
+                if (fv)
+                    hipLaunchKernelGGL((k_spmv_fold<VT, 1, 2>), g, b, 0, stream, K->nslices, K->nloc, K->d_fold_ptr, K->d_rowof,
+                                       K->d_fold_meta, K->d_fold_cols, fv, a.x, a.x2, a.y, a.y2, a.partial, a.st, a.k, slist, nlist,
+                                       poff, fold, fold_cols_of(ctx, K));
+                else
+                    hipLaunchKernelGGL((k_spmv2<VT>), g, b, 0, stream, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols,
+                                       vals, a.x, a.x2, a.y, a.y2, a.partial, a.st, a.k, slist, nlist, poff, fold, cs);
+                return;
+            }
+        if (small) {   // one workgroup per slice; partials per slice
+            hipLaunchKernelGGL((k_spmv_small<VT, DOT>), g, b, 0, stream, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof,
+                               K->d_cols, vals, a.x, a.y, a.partial, a.st, a.k, slist, nlist, poff, fold, cs);
+            return;
+        }
+        if (pair) {   // two wavefronts per slice, two slices per workgroup
+            hipLaunchKernelGGL((k_spmv_pair<VT, DOT, true>), g, b, 0, stream, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof,
+                               K->d_cols, vals, a.x, a.y, a.partial, a.st, a.k, slist, nlist, poff, fold, cs);
+            return;
+        }
+        if (fv) {
+            hipLaunchKernelGGL((k_spmv_fold<VT, DOT, 1>), g, b, 0, stream, K->nslices, K->nloc, K->d_fold_ptr, K->d_rowof,
+                               K->d_fold_meta, K->d_fold_cols, fv, a.x, (const double *)nullptr, a.y, (double *)nullptr, a.partial,
+                               a.st, a.k, slist, nlist, poff, fold, fold_cols_of(ctx, K));
+            return;
+        }
+#define SPMV_CASE(V)                                                                                                          \
+    case V:                                                                                                                   \
+        hipLaunchKernelGGL((k_spmv<VT, DOT, V>), g, b, 0, stream, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols, \
+                           vals, a.x, a.y, a.partial, a.st, a.k, slist, nlist, poff, fold, cs);                               \
         break;
-    // auto (-1): non-temporal matrix stream + XCD-chunked workgroup mapping (variant 9), with the
-    // loop unrolled by 4 for the FIXED-48 stream, whose iterations carry 21 % fewer bytes in
-    // flight (variant 12).  One process, one box (tools/fx48_variants.py, min of 3 x 20 launches):
-    // fp64 plain 1.181 / nt 1.102 / nt+chunk 1.100 ms; FIXED-48 1.003 / 0.955 / nt+unroll4 0.925;
-    // fp32 0.636 / 0.583 / 0.580.
-    const int variant = ctx->spmv_variant >= 0 ? ctx->spmv_variant : vstream<VT>::FX ? 12 : 9;
-    switch (variant) {
-        SPMV_CASE(9) SPMV_CASE(12)
-        default:
-        SPMV_CASE(0)
-    }
+        // auto (-1): non-temporal matrix stream + XCD-chunked workgroup mapping (variant 9), with the
+        // loop unrolled by 4 for the FIXED-48 stream, whose iterations carry 21 % fewer bytes in
+        // flight (variant 12).  One process, one box (tools/fx48_variants.py, min of 3 x 20 launches):
+        // fp64 plain 1.181 / nt 1.102 / nt+chunk 1.100 ms; FIXED-48 1.003 / 0.955 / nt+unroll4 0.925;
+        // fp32 0.636 / 0.583 / 0.580.
+        const int variant = ctx->spmv_variant >= 0 ? ctx->spmv_variant : vstream<VT>::FX ? 12 : 9;
+        switch (variant) {
+            SPMV_CASE(9) SPMV_CASE(12)
+            default:
+            SPMV_CASE(0)
+        }
 #undef SPMV_CASE
+    });
     return grid;
 }
-
-template <typename VT>
-unsigned launch_spmv2(stan_ctx *ctx, stan_matrix *K, const VT *vals, const double *x, const double *x2,
-                      double *y, double *y2, double *partial, const int64_t *st, int64_t k, int which,
-                      hipStream_t stream, fold_args fold) {
-    const int32_t *slist = which == 1 ? K->d_sl_int : which == 2 ? K->d_sl_bnd : nullptr;
-    const int32_t nlist = which == 1 ? K->n_sl_int : which == 2 ? K->n_sl_bnd : K->nslices;
-    const int32_t poff = which == 2 ? (int32_t)nblk(K->n_sl_int, 4) : 0;
-    const unsigned grid = nblk(nlist, 4);
-    if (grid == 0) return 0;
-    fold.nblocks = grid;
-    fold.np = (int)grid + poff;
-    if (const VT *fv = fold_vals<VT>(ctx, K, vals)) {
-        hipLaunchKernelGGL((k_spmv_fold<VT, 1, 2>), dim3(grid), dim3(256), 0, stream, K->nslices, K->nloc, K->d_fold_ptr,
-                           K->d_rowof, K->d_fold_meta, K->d_fold_cols, fv, x, x2, y, y2, partial, st, k, slist, nlist, poff, fold,
-                           fold_cols_of(ctx, K));
-        return grid;
-    }
-    const colstream cs = ctx->cols16 && K->d_cols16 ? make_colstream(K->d_cols16, K->d_colbase, K->d_pair_ptr, K->d_slice_packed, K->nslots)
-                                                    : NO_COLSTREAM;
-    hipLaunchKernelGGL((k_spmv2<VT>), dim3(grid), dim3(256), 0, stream, K->nslices, K->nloc, K->d_slot_ptr,
-                       K->d_rowof, K->d_cols, vals, x, x2, y, y2, partial, st, k, slist, nlist, poff, fold, cs);
-    return grid;
-}
-
-// value-stream dispatch of one product (DOT as in k_spmv)
-template <int DOT>
-unsigned launch_spmv_any(stan_ctx *ctx, stan_matrix *K, int stream_kind, const double *x, double *y,
-                         double *partial, const int64_t *st, int64_t k, int which, hipStream_t s,
-                         fold_args fold) {
-    if (stream_kind == STAN_PREC_MIXED)
-        return launch_spmv<float, DOT>(ctx, K, K->d_vals32, x, y, partial, st, k, which, s, fold);
-    if (stream_kind == STAN_PREC_FIXED48)
-        return launch_spmv<uint32_t, DOT>(ctx, K, K->d_vals48, x, y, partial, st, k, which, s, fold);
-    return launch_spmv<double, DOT>(ctx, K, K->d_vals, x, y, partial, st, k, which, s, fold);
+// y = A x with K's fp64 values, no sums: the products outside a solve
+unsigned launch_plain_product(stan_ctx *ctx, stan_matrix *K, const double *x, double *y, const int64_t *st, int which = 0) {
+    return launch_product(ctx, K, product_args{x, y, nullptr, nullptr, 0, nullptr, st, 1, STAN_PREC_FP64, nullptr, false}, which);
 }
 
 }  // namespace
 
 // Vectors of the CG for a matrix of K's sizes, owned by the context (see stan_cg_ws).
 int stan_cg_workspace(stan_ctx *ctx, const stan_matrix *K) {
-    const int64_t npad = (int64_t)K->nslices * 64;
-    const int64_t ng = 3 * ((npad > K->nloc + K->nhalo ? npad : K->nloc + K->nhalo));
+    const int64_t ng = gather_len(K);
     const int64_t n3 = 3 * K->nloc > 0 ? 3 * K->nloc : 1;
     stan_cg_ws &ws = ctx->ws;
     if (ws.p && ws.ng >= ng && ws.n3 >= n3 && ws.ng <= ng + ng / 2 + 64) return STAN_OK;
@@ -721,34 +746,25 @@ struct cg_run {
         return rc_;
     }
 
-    // y = A^ x (x gets its halo filled first when sharded) with `dot` sums (k_spmv's DOT) reduced into out[0..dot):
-    // folded into the last launch of the product, or by k_reduce.  kind: the value stream (the loop's own, or
-    // STAN_PREC_FP64 for the check / refresh products of a reduced-precision solve).
-    int spmv(double *x, double *y, int dot, double *out, int64_t k, p2p_out po, int kind, bool extra = false) {
-        const bool own = !extra;   // extra: an fp64 product inside a reduced-precision solve (check, refresh): timed apart
+    // y = A^ x with `dot` sums (k_spmv's DOT) reduced into out[0..dot) -- or, x2 given and dot = 1, y = A^ x and w = A^ x2
+    // in one matrix pass (the fused residual refresh).  x and x2 get their halos filled first when sharded; the sums are
+    // folded into the last launch of the product, or formed by k_reduce.  kind: the value stream (the loop's own, or
+    // STAN_PREC_FP64 for the check / refresh products of a reduced-precision solve, `extra`: timed apart).
+    int product(double *x, double *x2, double *y, int dot, double *out, int64_t k, p2p_out po, int kind, bool extra = false) {
+        std::vector<hipEvent_t> &ev = extra ? spmv64_ev : x2 ? spmv2_ev : spmv_ev;
         if (ctx->profiling) {
             hipEvent_t a = events.make(), b = events.make();
             hipEventRecord(a, st_);
-            if (own) { spmv_ev.push_back(a); spmv_ev.push_back(b); spmv_k.push_back(k); }
-            else { spmv64_ev.push_back(a); spmv64_ev.push_back(b); }
+            ev.push_back(a); ev.push_back(b);
+            if (!extra) (x2 ? spmv2_k : spmv_k).push_back(k);
         }
         auto go = [&](int which, hipStream_t s, bool last) -> unsigned {
-            fold_args f = (dot && last) ? fold_to(0, out, po) : NO_FOLD;
             n_launch++;
-            if (lazy_scale) {   // the first product of this matrix (one rank, fp64 stream, all slices): scale on the way
-                lazy_scale = false;
-                const unsigned grid = nblk(K->nslices, 4);
-                f.nblocks = grid; f.np = (int)grid;
-                const colstream cs = ctx->cols16 && K->d_cols16 ? make_colstream(K->d_cols16, K->d_colbase, K->d_pair_ptr, K->d_slice_packed, K->nslots) : NO_COLSTREAM;
-                if (dot == 2) hipLaunchKernelGGL(k_spmv_first<2>, dim3(grid), dim3(256), 0, s, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols, K->d_vals, K->d_scale, x, y, partial, stt, k, f, cs);
-                else if (dot == 1) hipLaunchKernelGGL(k_spmv_first<1>, dim3(grid), dim3(256), 0, s, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols, K->d_vals, K->d_scale, x, y, partial, stt, k, f, cs);
-                else hipLaunchKernelGGL(k_spmv_first<0>, dim3(grid), dim3(256), 0, s, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols, K->d_vals, K->d_scale, x, y, partial, stt, k, f, cs);
-                mark_scaled(ctx, K);
-                return grid;
-            }
-            return dot == 2 ? launch_spmv_any<2>(ctx, K, kind, x, y, partial, stt, k, which, s, f)
-                 : dot == 1 ? launch_spmv_any<1>(ctx, K, kind, x, y, partial, stt, k, which, s, f)
-                            : launch_spmv_any<0>(ctx, K, kind, x, y, partial, stt, k, which, s, f);
+            // lazy_scale: the first product of this matrix (one rank, fp64 stream, all slices) scales it on the way
+            const product_args a{x, y, x2, x2 ? w : nullptr, dot, partial, stt, k, kind, nullptr, lazy_scale};
+            const unsigned blocks = launch_product(ctx, K, a, which, s, (dot && last) ? fold_to(0, out, po) : NO_FOLD);
+            if (lazy_scale) { lazy_scale = false; mark_scaled(ctx, K); }
+            return blocks;
         };
         unsigned parts = 0;
         bool folded = foldr;
@@ -758,12 +774,13 @@ struct cg_run {
             parts = go(1, ctx->side, false);
             HIPCHK(ctx, hipEventRecord(ctx->ev_b, ctx->side));
             STANCHK(halo(x));
+            if (x2) STANCHK(halo(x2));
             HIPCHK(ctx, hipStreamWaitEvent(st_, ctx->ev_b, 0));
             const unsigned pb = go(2, st_, true);   // adds up the interior launch's partials too
             if (pb == 0) folded = false;            // no boundary slices on this rank: nobody folded
             parts += pb;
         } else {
-            if (dist) STANCHK(halo(x));
+            if (dist) { STANCHK(halo(x)); if (x2) STANCHK(halo(x2)); }
             parts = go(0, st_, true);
             if (parts == 0) folded = false;
         }
@@ -775,48 +792,7 @@ struct cg_run {
                 n_launch++;
             } else HIPCHK(ctx, hipMemsetAsync(out, 0, 8 * dot, st_));   // a rank that owns no rows
         }
-        if (ctx->profiling) hipEventRecord(own ? spmv_ev.back() : spmv64_ev.back(), st_);
-        return STAN_OK;
-    }
-
-    // v = A^ x and w = A^ x2 in one matrix pass (fused residual refresh), x.v -> out
-    int spmv2(double *x, double *x2, double *out, int64_t k, p2p_out po) {
-        if (ctx->profiling) {
-            hipEvent_t a = events.make(), b = events.make();
-            hipEventRecord(a, st_);
-            spmv2_ev.push_back(a); spmv2_ev.push_back(b);
-            spmv2_k.push_back(k);
-        }
-        auto go = [&](int which, hipStream_t s, bool last) -> unsigned {
-            const fold_args f = last ? fold_to(0, out, po) : NO_FOLD;
-            n_launch++;
-            if (vs == STAN_PREC_FIXED48) return launch_spmv2<uint32_t>(ctx, K, K->d_vals48, x, x2, v, w, partial, stt, k, which, s, f);
-            return vs == STAN_PREC_MIXED ? launch_spmv2<float>(ctx, K, K->d_vals32, x, x2, v, w, partial, stt, k, which, s, f)
-                                         : launch_spmv2<double>(ctx, K, K->d_vals, x, x2, v, w, partial, stt, k, which, s, f);
-        };
-        unsigned parts = 0;
-        bool folded = foldr;
-        if (split) {
-            HIPCHK(ctx, hipEventRecord(ctx->ev_a, st_));
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_a, 0));
-            parts = go(1, ctx->side, false);
-            HIPCHK(ctx, hipEventRecord(ctx->ev_b, ctx->side));
-            STANCHK(halo(x));
-            STANCHK(halo(x2));
-            HIPCHK(ctx, hipStreamWaitEvent(st_, ctx->ev_b, 0));
-            const unsigned pb = go(2, st_, true);
-            if (pb == 0) folded = false;
-            parts += pb;
-        } else {
-            if (dist) { STANCHK(halo(x)); STANCHK(halo(x2)); }
-            parts = go(0, st_, true);
-            if (parts == 0) folded = false;
-        }
-        if (!folded) {
-            if (parts > 0 || po.pp) { hipLaunchKernelGGL(k_reduce<1>, dim3(1), dim3(256), 0, st_, partial, (int)parts, out, po, (const int64_t *)stt, k); n_launch++; }
-            else HIPCHK(ctx, hipMemsetAsync(out, 0, 8, st_));
-        }
-        if (ctx->profiling) hipEventRecord(spmv2_ev.back(), st_);
+        if (ctx->profiling) hipEventRecord(ev.back(), st_);
         return STAN_OK;
     }
 
@@ -888,7 +864,7 @@ int cg_run::setup() {
 
     n3 = 3 * K->nloc;
     npad = (int64_t)K->nslices * 64;
-    ng = 3 * ((npad > K->nloc + K->nhalo ? npad : K->nloc + K->nhalo));
+    ng = gather_len(K);
     dof0 = 3 * K->r0;
     xb[0] = ctx->ws.xb[0]; xb[1] = ctx->ws.xb[1]; p = ctx->ws.p; r = ctx->ws.r;
     v = ctx->ws.v; w = ctx->ws.w; bh = ctx->ws.bh;
@@ -972,7 +948,7 @@ int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
     if (sr) {   // w_0 = A r_0 with gamma_0, delta_0 (merit_0 = 0 sits in the zeroed scalars)
         if (p2p)         // ... or, peer to peer, is sent as this rank's zero into the slot of the first reduction
             hipLaunchKernelGGL(k_reduce<1>, dim3(1), dim3(256), 0, st_, partial, 0, sc + S_SR_MERIT, p2p_to(2, false), (const int64_t *)nullptr, (int64_t)0);
-        rc = spmv(r, w, 2, sc + S_SR_GAMMA, 0, p2p_to(0, true), vs);
+        rc = product(r, nullptr, w, 2, sc + S_SR_GAMMA, 0, p2p_to(0, true), vs);
         if (rc == STAN_OK) rc = exchange_sums(sc + S_SR_GAMMA, 3, &rs_sr);
     }
     // a sharded loop polls more often: what runs ahead of the stop are exchanges nobody can cut short
@@ -995,22 +971,21 @@ int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
                 n_launch++;
                 if (!refresh) reduce_if_unfolded((int)vg, 1, sc + S_SR_MERIT, p2p_to(2, false), k);
                 else {   // r' = b^ - A^ x' (ALGLIB's periodic residual recomputation), then as usual
-                    rc = spmv(xb[k & 1], v, 0, nullptr, k, NO_P2P, kind_refresh, refresh64);
+                    rc = product(xb[k & 1], nullptr, v, 0, nullptr, k, NO_P2P, kind_refresh, refresh64);
                     if (rc) break;
                     hipLaunchKernelGGL(k_refresh, dim3(vg), dim3(VEC_T), 0, st_, n3, k, (const int64_t *)stt,
                                        bh, v, xb[k & 1], r, partial, vec_fold(sc + S_SR_DELTA, p2p_to(1, false)));
                     n_launch++;
                     reduce_if_unfolded((int)vg, 2, sc + S_SR_DELTA, p2p_to(1, false), k);   // [r.r (rewritten below), merit]
                 }
-                rc = spmv(r, w, 2, sc + S_SR_GAMMA, k, p2p_to(0, true), vs);
+                rc = product(r, nullptr, w, 2, sc + S_SR_GAMMA, k, p2p_to(0, true), vs);
                 if (rc) break;
                 rc = exchange_sums(sc + S_SR_GAMMA, 3, &rs_sr);
                 if (rc) break;
                 continue;
             }
             const bool fused = refresh && ctx->cg_fused_refresh && !refresh64;
-            rc = fused ? spmv2(p, xb[(k - 1) & 1], sc + S_VMV, k, p2p_to(0, true))
-                       : spmv(p, v, 1, sc + S_VMV, k, p2p_to(0, true), vs);
+            rc = product(p, fused ? xb[(k - 1) & 1] : nullptr, v, 1, sc + S_VMV, k, p2p_to(0, true), vs);
             if (rc) break;
             rc = exchange_sums(sc + S_VMV, 1, &rs_vmv);
             if (rc) break;
@@ -1031,7 +1006,7 @@ int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
             n_launch++;
             if (a.refresh == 1) {
                 // a -5/-4 stop of this iteration is caught by k_refresh/k_update (ITER_B <= k)
-                rc = spmv(xb[k & 1], v, 0, nullptr, k, NO_P2P, kind_refresh, refresh64);
+                rc = product(xb[k & 1], nullptr, v, 0, nullptr, k, NO_P2P, kind_refresh, refresh64);
                 if (rc) break;
                 hipLaunchKernelGGL(k_refresh, dim3(vg), dim3(VEC_T), 0, st_, n3, k,
                                    (const int64_t *)stt, bh, v, xb[k & 1], r, partial, vec_fold(sc + S_R2NEW, po_r));
@@ -1127,7 +1102,7 @@ void cg_run::account_pass() {
 // r_t = b - A^64 xg with the fp64 values of the scaled matrix (xg: a gather vector -- one of the vectors the peers know,
 // cg_run::setup -- holding the iterate on the owned rows); r_t stays in r, *r2_out = ||r_t||^2 over all ranks.
 int cg_run::fp64_check(double *xg, const double *b, double *r2_out) {
-    STANCHK(spmv(xg, v, 0, nullptr, 0, NO_P2P, STAN_PREC_FP64, true));
+    STANCHK(product(xg, nullptr, v, 0, nullptr, 0, NO_P2P, STAN_PREC_FP64, true));
     const p2p_out po = p2p_to(0, true);
     hipLaunchKernelGGL(k_refresh, dim3(vg), dim3(VEC_T), 0, st_, n3, (int64_t)0, (const int64_t *)stt, b, v,
                        (const double *)xg, r, partial, vec_fold(sc + S_CHK_R2, po));
@@ -1311,15 +1286,13 @@ int stan_spmv_reduced(stan_ctx *ctx, stan_matrix *K, const double *d_x, double *
     double *xf, *yf; int64_t *stt;
     STANCHK(alloc(ctx, bufs, &xf, (size_t)npad3));
     STANCHK(alloc(ctx, bufs, &yf, (size_t)npad3));
-    STANCHK(alloc(ctx, bufs, &stt, (size_t)T_NSTAT));
-    int64_t init[T_NSTAT] = {0x7fffffffffffffffLL, 0x7fffffffffffffffLL, 0, 0, 0, 0, 0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(stt, init, sizeof(init), hipMemcpyHostToDevice, st_));
+    STANCHK(alloc_never_stopped(ctx, bufs, &stt, st_));
     HIPCHK(ctx, hipMemsetAsync(xf, 0, (size_t)npad3 * 8, st_));
     const double *sdiv = K->scaled ? K->d_scale : nullptr;
     // K x = S^-1 (A^ (S^-1 x)) when the matrix already carries its scaling
     hipLaunchKernelGGL(k_expand, dim3(vec_grid(n3)), dim3(VEC_T), 0, st_, n3, (int64_t)0, K->d_red,
                        d_x, sdiv, xf);
-    launch_spmv<double, 0>(ctx, K, K->d_vals, xf, yf, nullptr, stt, 1);
+    launch_plain_product(ctx, K, xf, yf, stt);
     // compress (and undo the row scaling)
     hipLaunchKernelGGL(k_compress_div, dim3(vec_grid(n3)), dim3(VEC_T), 0, st_, n3, K->d_red, sdiv, yf, d_y);
     HIPCHK(ctx, hipGetLastError());
@@ -1348,54 +1321,61 @@ int stan_matrix_diagonal(stan_ctx *ctx, stan_matrix *K, double *d_diag) {
 int stan_spmv_local(stan_ctx *ctx, stan_matrix *K, const double *d_x, double *d_y) {
     dev_bufs bufs;
     int64_t *stt;
-    STANCHK(alloc(ctx, bufs, &stt, (size_t)T_NSTAT));
-    int64_t init[T_NSTAT] = {0x7fffffffffffffffLL, 0x7fffffffffffffffLL, 0, 0, 0, 0, 0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(stt, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
+    STANCHK(alloc_never_stopped(ctx, bufs, &stt, ctx->stream));
     if (K->d_sl_bnd) {  // sharded: interior + boundary lists must cover every slice exactly once
         HIPCHK(ctx, hipMemsetAsync(d_y, 0xff, (size_t)(3 * K->nloc) * 8, ctx->stream));  // NaN
-        launch_spmv<double, 0>(ctx, K, K->d_vals, d_x, d_y, nullptr, stt, 1, 1);
-        launch_spmv<double, 0>(ctx, K, K->d_vals, d_x, d_y, nullptr, stt, 1, 2);
+        launch_plain_product(ctx, K, d_x, d_y, stt, 1);
+        launch_plain_product(ctx, K, d_x, d_y, stt, 2);
     } else
-        launch_spmv<double, 0>(ctx, K, K->d_vals, d_x, d_y, nullptr, stt, 1);
+        launch_plain_product(ctx, K, d_x, d_y, stt);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return STAN_OK;
+}
+
+// What stan_spmv_bench_device and stan_spmv_probe time: the product with its p.Ap sum, of the value stream `vals` (nullptr:
+// K's own of that precision), on the CG's own gather vector and product buffer -- the pair (value block, vector blocks)
+// that is timed is the pair the solve will run on -- or, self_block given, on vectors carved out of the front of that
+// block (a.x stays nullptr when they do not fit).  The gather vector is filled with ones.
+struct timed_product {
+    dev_bufs bufs;
+    product_args a{};
+};
+static int timed_product_setup(stan_ctx *ctx, stan_matrix *K, int32_t precision, const void *vals, void *self_block,
+                               size_t self_bytes, timed_product &t) {
+    hipStream_t st_ = ctx->stream;
+    const int64_t ng = gather_len(K), ngpad = (ng + 511) & ~(int64_t)511;
+    STANCHK(stan_cg_workspace(ctx, K));
+    double *x = ctx->ws.p, *y = ctx->ws.v, *partial;
+    int64_t *stt;
+    if (self_block) {
+        if ((size_t)(ngpad + 3 * K->nloc) * 8 > self_bytes) return STAN_OK;
+        x = (double *)self_block;
+        y = x + ngpad;
+    }
+    STANCHK(alloc(ctx, t.bufs, &partial, 2 * (size_t)K->nslices + 2));   // k_spmv_small leaves one partial per slice
+    STANCHK(alloc_never_stopped(ctx, t.bufs, &stt, st_));
+    hipLaunchKernelGGL(k_fill, dim3(vec_grid(ng)), dim3(VEC_T), 0, st_, x, ng, 1.0);
+    t.a = product_args{x, y, nullptr, nullptr, 1, partial, stt, 1, precision, vals, false};
     return STAN_OK;
 }
 
 int stan_spmv_bench_device(stan_ctx *ctx, stan_matrix *K, int32_t precision_mode, int32_t reps,
                            double *avg_ms) {
     hipStream_t st_ = ctx->stream;
-    const bool mixed = precision_mode == STAN_PREC_MIXED;
-    if (mixed) STANCHK(stan_matrix_make_fp32(ctx, K));
+    if (precision_mode == STAN_PREC_MIXED) STANCHK(stan_matrix_make_fp32(ctx, K));
     if (precision_mode == STAN_PREC_FIXED48) {
         STANCHK(ensure_scaled(ctx, K));
         STANCHK(stan_matrix_make_fx48(ctx, K));
         if (!K->d_vals48) { ctx->err = "spmv_bench: matrix not representable in FIXED48"; return STAN_E_UNSUPPORTED; }
     }
-    const bool fx = precision_mode == STAN_PREC_FIXED48;
-    const int64_t npad = (int64_t)K->nslices * 64;
-    const int64_t ng = 3 * ((npad > K->nloc + K->nhalo ? npad : K->nloc + K->nhalo));
-    dev_bufs bufs;
-    double *x, *y, *partial; int64_t *stt;
-    // the CG's own gather vector and product buffer: the pair (value block, vector blocks) that is
-    // timed here is the pair the solve will run on
-    STANCHK(stan_cg_workspace(ctx, K));
-    x = ctx->ws.p; y = ctx->ws.v;
-    STANCHK(alloc(ctx, bufs, &partial, 2 * (size_t)K->nslices + 2));   // k_spmv_small leaves one partial per slice
-    STANCHK(alloc(ctx, bufs, &stt, (size_t)T_NSTAT));
-    int64_t init[T_NSTAT] = {0x7fffffffffffffffLL, 0x7fffffffffffffffLL, 0, 0, 0, 0, 0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(stt, init, sizeof(init), hipMemcpyHostToDevice, st_));
-    hipLaunchKernelGGL(k_fill, dim3(vec_grid(ng)), dim3(VEC_T), 0, st_, x, ng, 1.0);
+    timed_product t;
+    STANCHK(timed_product_setup(ctx, K, precision_mode, nullptr, nullptr, 0, t));
     event_bag events;
     hipEvent_t a = events.make(), b = events.make();
-    auto one = [&]() {
-        if (mixed) launch_spmv<float, 1>(ctx, K, K->d_vals32, x, y, partial, stt, 1);
-        else if (fx) launch_spmv<uint32_t, 1>(ctx, K, K->d_vals48, x, y, partial, stt, 1);
-        else launch_spmv<double, 1>(ctx, K, K->d_vals, x, y, partial, stt, 1);
-    };
-    for (int i = 0; i < 3; i++) one();
+    for (int i = 0; i < 3; i++) launch_product(ctx, K, t.a);
     hipEventRecord(a, st_);
-    for (int i = 0; i < reps; i++) one();
+    for (int i = 0; i < reps; i++) launch_product(ctx, K, t.a);
     hipEventRecord(b, st_);
     HIPCHK(ctx, hipEventSynchronize(b));
     float ms = 0;
@@ -1441,39 +1421,17 @@ int stan_spmv_probe(stan_ctx *ctx, stan_matrix *K, const void *vals, size_t byte
     hipStream_t st_ = ctx->stream;
     *ms_out = 0;
     if (K->nslices <= 0) return STAN_OK;
-    const int64_t npad = (int64_t)K->nslices * 64;
-    const int64_t ng = 3 * ((npad > K->nloc + K->nhalo ? npad : K->nloc + K->nhalo));
-    dev_bufs bufs;
-    double *x, *y, *partial; int64_t *stt;
-    // the CG's own gather vector and product buffer: the pair (value block, vector blocks) that is
-    // timed here is the pair the solve will run on
-    STANCHK(stan_cg_workspace(ctx, K));
-    x = ctx->ws.p; y = ctx->ws.v;
-    if (self_pair) {   // the block holds no values yet (only addresses matter to the timing)
-        // the gather vector and the product must fit into the candidate: a stream with few slots per
-        // slice (or a large halo) has no self-paired reference -- *ms_out stays 0, the search then
-        // keeps the fastest real pairing (placement.hip)
-        if ((size_t)(((ng + 511) & ~(int64_t)511) + 3 * K->nloc) * 8 > bytes) return STAN_OK;
-        x = (double *)const_cast<void *>(vals);
-        y = x + ((ng + 511) & ~(int64_t)511);
-    }
-    STANCHK(alloc(ctx, bufs, &partial, 2 * (size_t)K->nslices + 2));   // k_spmv_small leaves one partial per slice
-    STANCHK(alloc(ctx, bufs, &stt, (size_t)T_NSTAT));
-    int64_t init[T_NSTAT] = {0x7fffffffffffffffLL, 0x7fffffffffffffffLL, 0, 0, 0, 0, 0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(stt, init, sizeof(init), hipMemcpyHostToDevice, st_));
-    hipLaunchKernelGGL(k_fill, dim3(vec_grid(ng)), dim3(VEC_T), 0, st_, x, ng, 1.0);
+    // self_pair: the block holds no values yet (only addresses matter to the timing).  The gather vector and the product
+    // must fit into the candidate: a stream with few slots per slice (or a large halo) has no self-paired reference --
+    // *ms_out stays 0, the search then keeps the fastest real pairing (placement.hip)
+    timed_product t;
+    STANCHK(timed_product_setup(ctx, K, precision, vals, self_pair ? const_cast<void *>(vals) : nullptr, bytes, t));
+    if (!t.a.x) return STAN_OK;
     event_bag ev;
     // one launch to warm up, then two groups of three launches back to back, the faster group counts.  (Round 4: single
     // launches between host synchronisations -- the first form of this probe -- start on an idle device and read 2-3 %
     // under the same product inside a sequence of kernels.)
-    auto one = [&]() {
-        if (precision == STAN_PREC_FIXED48)
-            launch_spmv<uint32_t, 1>(ctx, K, (const uint32_t *)vals, x, y, partial, stt, 1);
-        else if (precision == STAN_PREC_MIXED)
-            launch_spmv<float, 1>(ctx, K, (const float *)vals, x, y, partial, stt, 1);
-        else
-            launch_spmv<double, 1>(ctx, K, (const double *)vals, x, y, partial, stt, 1);
-    };
+    auto one = [&]() { launch_product(ctx, K, t.a); };
     one();
     float best = 0;
     for (int g = 0; g < 2; g++) {

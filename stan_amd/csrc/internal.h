@@ -254,7 +254,7 @@ struct stan_ctx {
     int prof_placement_candidates = 0;
     int prof_placement_moved_vectors = 0;   // 1: the search ended by re-allocating the CG's vectors
     int prof_colours = 0;
-    int spmv_variant = -1; // -1 = auto (launch_spmv picks per value stream); >= 0: A/B lab
+    int spmv_variant = -1; // -1 = auto (launch_product picks per value stream); >= 0: A/B lab
     // profiling
     bool profiling = false;
     stan_profile prof{};

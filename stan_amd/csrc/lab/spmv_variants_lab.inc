@@ -1,6 +1,8 @@
-// lab/spmv_variants_lab.inc -- LAB ONLY (make lab, -DSTAN_LAB): included inside k_spmv (cg.hip) in front of the product
-// column loops.  VAR 8 is a timing-only kernel (16-B accesses, WRONG results); 14-16 walk a slice's slots in another
+// lab/spmv_variants_lab.inc -- LAB ONLY (make lab, -DSTAN_LAB): included inside k_spmv (cg.hip) in front of the product's
+// walk over the slots (walk_slots).  VAR 8 is a timing-only kernel (16-B accesses, WRONG results); 14-16 walk a slice's slots in another
 // order (tools/placement_map.py).  The product library never compiles this file.
+        const int32_t *cp = cols + (int64_t)k0 * 64 + lane;
+        const VT *vp = vals + (int64_t)k0 * vstream<VT>::STRIDE + lane;
         if (VAR == 8 && !vstream<VT>::FX) {  // timing only: 16-B accesses, results are wrong
             typedef VT v2 __attribute__((ext_vector_type(2)));
             const v2 *vq = (const v2 *)(vals + (int64_t)k0 * 9 * 64) + lane;

@@ -80,6 +80,106 @@ inline colstream make_colstream(const uint32_t *packed, const int32_t *base, con
     return colstream{packed, base, pair_ptr, ok, base + n, (const unsigned long long *)(base + 2 * n)};
 }
 
+// ---- the pieces every product kernel shares -------------------------------------------------------------------------
+// XCD-chunked workgroup mapping (CH = 0: identity).  Workgroups go round-robin to the 8 XCDs; here every window of 8*CH
+// consecutive workgroups is dealt so that each XCD gets CH CONSECUTIVE ones: an XCD's L2 then holds the x window of one
+// contiguous run of rows while the chip as a whole still sweeps the matrix front to back.
+template <int CH>
+__device__ __forceinline__ int64_t xcd_chunked(int64_t bid) {
+    if constexpr (CH > 0) {
+        const int64_t win = 8 * CH, grp = bid / win, within = bid - grp * win;
+        if ((grp + 1) * win <= (int64_t)gridDim.x)   // the ragged tail keeps the identity mapping
+            bid = grp * win + (within & 7) * CH + (within >> 3);
+    }
+    return bid;
+}
+// position `pos` of a launch -> slice: itself, or through the interior / boundary list (past its end: no slice)
+__device__ __forceinline__ int64_t slice_at(int64_t pos, const int32_t *__restrict__ slist, int32_t nlist, int32_t nslices) {
+    if (slist) pos = pos < nlist ? (int64_t)slist[pos] : (int64_t)nslices;
+    return pos;
+}
+// SELL-C-sigma: position -> block row (nloc: none, a padding position or no slice)
+__device__ __forceinline__ int64_t row_at(int64_t slice, int32_t nslices, const int32_t *__restrict__ rowof, int lane, int64_t nloc) {
+    return slice < nslices ? (int64_t)rowof[slice * 64 + lane] : nloc;
+}
+// the three values of block row `row`; non-temporal where the matrix stream is: A p is read exactly once, by k_step
+template <bool NT>
+__device__ __forceinline__ void store_row(double *__restrict__ y, int64_t row, double y0, double y1, double y2) {
+    if (NT) {
+        __builtin_nontemporal_store(y0, y + 3 * row); __builtin_nontemporal_store(y1, y + 3 * row + 1);
+        __builtin_nontemporal_store(y2, y + 3 * row + 2);
+    } else { y[3 * row] = y0; y[3 * row + 1] = y1; y[3 * row + 2] = y2; }
+}
+// The dot products fused into a product (DOT as in k_spmv).  dot_terms: the row's terms d = x_row . y_row and, DOT = 2,
+// e = x_row . x_row.  dot_reduce (every thread of the block; rows without terms bring zeros): the block's sums to
+// partial[blockIdx.x + poff] -- DOT = 2: the pair [sum e, sum d] -- as agent-scope stores, then the ticket of the folded
+// reduction; the block that draws the last one adds all partials up (fold_arrive / fold_finish, cg.hip).
+template <int DOT>
+__device__ __forceinline__ void dot_terms(const double *__restrict__ x, int64_t row, double y0, double y1, double y2, double &d, double &e) {
+    const double x0 = x[3 * row], x1 = x[3 * row + 1], x2 = x[3 * row + 2];
+    d = y0 * x0 + y1 * x1 + y2 * x2;
+    if (DOT == 2) e = x0 * x0 + x1 * x1 + x2 * x2;
+}
+template <int DOT>
+__device__ __forceinline__ void dot_reduce(double d, double e, double *partial, int32_t poff, const fold_args &fold, double *sh, int *sh_last) {
+    const double t = block_sum(d, sh);
+    if (DOT == 2) {
+        const double u = block_sum(e, sh);
+        if (threadIdx.x == 0) {
+            st_agent(partial + 2 * (int64_t)(blockIdx.x + poff), u);
+            st_agent(partial + 2 * (int64_t)(blockIdx.x + poff) + 1, t);
+        }
+    } else if (threadIdx.x == 0) st_agent(partial + blockIdx.x + poff, t);
+    if (fold.counter && fold_arrive(fold, sh_last)) fold_finish<(DOT == 2 ? 2 : 1)>(fold, partial, sh);
+}
+// The walk of one wavefront over the slots [ka, kb) of `slice` (whose first slot is k0; ka - k0 even), one lane per block
+// row: body(c, vp) for every slot, c the lane's block column, vp its entry of the value stream `vals` ([slot][STRIDE], a
+// carried pointer).  Packed slices (colstream) two slots per trip -- unrolling that further costs 40 VGPRs --, int32
+// columns one slot per trip, unrolled UNR times.
+template <bool NT, int UNR, int STRIDE, typename V, typename BODY>
+__device__ __forceinline__ void walk_slots(const colstream &cs, const int32_t *__restrict__ cols, int64_t slice, int lane,
+                                           int32_t k0, int32_t ka, int32_t kb, V *__restrict__ vals, BODY body) {
+    const int32_t *cp = cols + (int64_t)ka * 64 + lane;
+    V *vp = vals + (int64_t)ka * STRIDE + lane;
+    const int pmode = cs.packed ? (int)cs.ok[slice] : 0;   // wave-uniform: 0 int32 columns, 1 / 2 packed (k_pack_cols)
+    if (pmode != 0) {   // one loop for both packed modes: a one-base slice has cmask 0 and base2 = base
+        // two bases per slot: the lane's class picks (a select between two scalars)
+        const uint32_t *cq = cs.packed + ((int64_t)cs.pair_ptr[slice] + ((ka - k0) >> 1)) * 64 + lane;
+        const int32_t *bp = cs.base + __builtin_amdgcn_readfirstlane(ka);
+        const int32_t *bq = cs.base2 + __builtin_amdgcn_readfirstlane(ka);
+        const bool cb = (cs.cmask[slice] >> lane) & 1ull;
+        int32_t k = ka;
+#pragma unroll 1
+        for (; k + 1 < kb; k += 2) {
+            const uint32_t wd = ld_stream<NT>(cq);
+            // four scalar loads and two selects of VALUES: written as `cb ? bq[0] : bp[0]` the select lands on the
+            // pointer and the bases arrive through a per-lane vector load (+0.6 %, tools/lab/spmv_steps_lab.cpp S35)
+            const int32_t b0 = bp[0], b1 = bp[1], q0 = bq[0], q1 = bq[1];
+            const int64_t c = (int64_t)(cb ? q0 : b0) + (int64_t)(wd & 0xffffu);
+            const int64_t c2 = (int64_t)(cb ? q1 : b1) + (int64_t)(wd >> 16);
+            body(c, vp);
+            body(c2, vp + STRIDE);
+            cq += 64;
+            bp += 2;
+            bq += 2;
+            vp += 2 * STRIDE;
+        }
+        if (k < kb) {
+            const int32_t b0 = bp[0], q0 = bq[0];
+            const int64_t c = (int64_t)(cb ? q0 : b0) + (int64_t)(ld_stream<NT>(cq) & 0xffffu);
+            body(c, vp);
+        }
+    } else {
+#pragma unroll UNR
+        for (int32_t k = ka; k < kb; k++) {
+            const int64_t c = ld_stream<NT>(cp);
+            body(c, vp);
+            cp += 64;
+            vp += STRIDE;
+        }
+    }
+}
+
 #define STAN_SPMV_BLOCK(C, VP)                                                        \
     {                                                                                 \
         double a[9];                                                                  \
@@ -103,86 +203,23 @@ k_spmv(int32_t nslices, int64_t nloc, const int32_t *__restrict__ slot_ptr, cons
     if (stopped(st, kiter)) { fold_skip(fold); return; }
     constexpr bool NT = VAR != 0;
     constexpr int UNR = VAR == 12 ? 4 : 2;
-    constexpr int UNR2 = 1;         // the packed-column loop handles two slots per trip (unrolling it further costs 40 VGPRs)
-    // XCD-chunked mapping.  Workgroups go round-robin to the 8 XCDs; here every window of 8*CH consecutive
-    // workgroups is dealt so that each XCD gets CH CONSECUTIVE ones: an XCD's L2 then holds the x window of one
-    // contiguous run of rows while the chip as a whole still sweeps the matrix front to back.
     constexpr int CH = VAR != 0 ? 32 : 0;
     const int lane = threadIdx.x & 63;
     int64_t bid = blockIdx.x;
-    if (CH > 0) {
-        const int64_t win = 8 * CH, grp = bid / win, within = bid - grp * win;
-        if ((grp + 1) * win <= (int64_t)gridDim.x)   // the ragged tail keeps the identity mapping
-            bid = grp * win + (within & 7) * CH + (within >> 3);
-    }
-    int64_t slice = bid * 4 + (threadIdx.x >> 6);
-    if (slist) slice = slice < nlist ? (int64_t)slist[slice] : (int64_t)nslices;  // interior / boundary list
+    bid = xcd_chunked<CH>(bid);
+    const int64_t slice = slice_at(bid * 4 + (threadIdx.x >> 6), slist, nlist, nslices);
     double y0 = 0, y1 = 0, y2 = 0;
-    const int64_t row = slice < nslices ? (int64_t)rowof[slice * 64 + lane] : nloc;   // SELL-C-sigma: position -> block row
+    const int64_t row = row_at(slice, nslices, rowof, lane, nloc);
     if (slice < nslices) {
         const int32_t k0 = slot_ptr[slice], k1 = slot_ptr[slice + 1];
-        const int32_t *cp = cols + (int64_t)k0 * 64 + lane;
-        const VT *vp = vals + (int64_t)k0 * vstream<VT>::STRIDE + lane;
-        const int pmode = cs.packed ? (int)cs.ok[slice] : 0;   // wave-uniform: 0 int32 columns, 1 / 2 packed (k_pack_cols)
-        if (pmode != 0) {   // one loop for both packed modes: a one-base slice has cmask 0 and base2 = base
-            // two bases per slot: the lane's class picks (a select between two scalars)
-            const uint32_t *cq = cs.packed + (int64_t)cs.pair_ptr[slice] * 64 + lane;
-            const int32_t *bp = cs.base + __builtin_amdgcn_readfirstlane(k0);
-            const int32_t *bq = cs.base2 + __builtin_amdgcn_readfirstlane(k0);
-            const bool cb = (cs.cmask[slice] >> lane) & 1ull;
-            int32_t k = k0;
-#pragma unroll UNR2
-            for (; k + 1 < k1; k += 2) {
-                const uint32_t wd = ld_stream<NT>(cq);
-                // four scalar loads and two selects of VALUES: written as `cb ? bq[0] : bp[0]` the select lands on the
-                // pointer and the bases arrive through a per-lane vector load (+0.6 %, tools/lab/spmv_steps_lab.cpp S35)
-                const int32_t b0 = bp[0], b1 = bp[1], q0 = bq[0], q1 = bq[1];
-                const int64_t c = (int64_t)(cb ? q0 : b0) + (int64_t)(wd & 0xffffu);
-                const int64_t c2 = (int64_t)(cb ? q1 : b1) + (int64_t)(wd >> 16);
-                STAN_SPMV_BLOCK(c, vp)
-                STAN_SPMV_BLOCK(c2, vp + vstream<VT>::STRIDE)
-                cq += 64;
-                bp += 2;
-                bq += 2;
-                vp += 2 * vstream<VT>::STRIDE;
-            }
-            if (k < k1) {
-                const int32_t b0 = bp[0], q0 = bq[0];
-                const int64_t c = (int64_t)(cb ? q0 : b0) + (int64_t)(ld_stream<NT>(cq) & 0xffffu);
-                STAN_SPMV_BLOCK(c, vp)
-            }
-        } else {
-#pragma unroll UNR
-            for (int32_t k = k0; k < k1; k++) {
-                const int64_t c = ld_stream<NT>(cp);
-                STAN_SPMV_BLOCK(c, vp)
-                cp += 64;
-                vp += vstream<VT>::STRIDE;
-            }
-        }
-        if (row < nloc) {   // A p is read exactly once, by k_step
-            if (NT) {
-                __builtin_nontemporal_store(y0, y + 3 * row); __builtin_nontemporal_store(y1, y + 3 * row + 1);
-                __builtin_nontemporal_store(y2, y + 3 * row + 2);
-            } else { y[3 * row] = y0; y[3 * row + 1] = y1; y[3 * row + 2] = y2; }
-        }
+        walk_slots<NT, UNR, vstream<VT>::STRIDE>(cs, cols, slice, lane, k0, k0, k1, vals,
+                                                 [&](int64_t c, const VT *vp) { STAN_SPMV_BLOCK(c, vp) });
+        if (row < nloc) store_row<NT>(y, row, y0, y1, y2);
     }
     if (DOT) {
         double d = 0, e = 0;
-        if (slice < nslices && row < nloc) {
-            const double x0 = x[3 * row], x1 = x[3 * row + 1], x2 = x[3 * row + 2];
-            d = y0 * x0 + y1 * x1 + y2 * x2;
-            if (DOT == 2) e = x0 * x0 + x1 * x1 + x2 * x2;
-        }
-        const double t = block_sum(d, sh);
-        if (DOT == 2) {
-            const double u = block_sum(e, sh);
-            if (threadIdx.x == 0) {
-                st_agent(partial + 2 * (int64_t)(blockIdx.x + poff), u);
-                st_agent(partial + 2 * (int64_t)(blockIdx.x + poff) + 1, t);
-            }
-        } else if (threadIdx.x == 0) st_agent(partial + blockIdx.x + poff, t);
-        if (fold.counter && fold_arrive(fold, &sh_last)) fold_finish<(DOT == 2 ? 2 : 1)>(fold, partial, sh);
+        if (slice < nslices && row < nloc) dot_terms<DOT>(x, row, y0, y1, y2, d, e);
+        dot_reduce<DOT>(d, e, partial, poff, fold, sh, &sh_last);
     }
 }
 
@@ -208,82 +245,27 @@ k_spmv_pair(int32_t nslices, int64_t nloc, const int32_t *__restrict__ slot_ptr,
     __shared__ int sh_last;
     __shared__ double acc[2][3][64];
     if (stopped(st, kiter)) { fold_skip(fold); return; }
-    constexpr int CH = 32;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, sl = w >> 1, half = w & 1;
-    int64_t bid = blockIdx.x;
-    {
-        const int64_t win = 8 * CH, grp = bid / win, within = bid - grp * win;
-        if ((grp + 1) * win <= (int64_t)gridDim.x) bid = grp * win + (within & 7) * CH + (within >> 3);
-    }
-    int64_t slice = bid * 2 + sl;
-    if (slist) slice = slice < nlist ? (int64_t)slist[slice] : (int64_t)nslices;
+    const int64_t slice = slice_at(xcd_chunked<32>(blockIdx.x) * 2 + sl, slist, nlist, nslices);
     double y0 = 0, y1 = 0, y2 = 0;
-    const int64_t row = slice < nslices ? (int64_t)rowof[slice * 64 + lane] : nloc;
+    const int64_t row = row_at(slice, nslices, rowof, lane, nloc);
     if (slice < nslices) {
         const int32_t k0 = slot_ptr[slice], k1 = slot_ptr[slice + 1];
         int32_t mid = k0 + ((((k1 - k0) + 1) / 2 + 1) & ~1);   // an EVEN number of slots for the first wave: packed pairs stay whole
         if (mid > k1) mid = k1;
         const int32_t ka = half ? mid : k0, kb = half ? k1 : mid;
-        const VT *vp = vals + (int64_t)ka * vstream<VT>::STRIDE + lane;
-        const int pmode = cs.packed ? (int)cs.ok[slice] : 0;
-        if (pmode != 0) {
-            const uint32_t *cq = cs.packed + ((int64_t)cs.pair_ptr[slice] + ((ka - k0) >> 1)) * 64 + lane;
-            const int32_t *bp = cs.base + __builtin_amdgcn_readfirstlane(ka);
-            const int32_t *bq = cs.base2 + __builtin_amdgcn_readfirstlane(ka);
-            const bool cb = (cs.cmask[slice] >> lane) & 1ull;
-            int32_t k = ka;
-            for (; k + 1 < kb; k += 2) {
-                const uint32_t wd = ld_stream<NT>(cq);
-                const int32_t b0 = bp[0], b1 = bp[1], q0 = bq[0], q1 = bq[1];
-                const int64_t c = (int64_t)(cb ? q0 : b0) + (int64_t)(wd & 0xffffu);
-                const int64_t c2 = (int64_t)(cb ? q1 : b1) + (int64_t)(wd >> 16);
-                STAN_SPMV_BLOCK(c, vp)
-                STAN_SPMV_BLOCK(c2, vp + vstream<VT>::STRIDE)
-                cq += 64; bp += 2; bq += 2;
-                vp += 2 * vstream<VT>::STRIDE;
-            }
-            if (k < kb) {
-                const int32_t b0 = bp[0], q0 = bq[0];
-                const int64_t c = (int64_t)(cb ? q0 : b0) + (int64_t)(ld_stream<NT>(cq) & 0xffffu);
-                STAN_SPMV_BLOCK(c, vp)
-            }
-        } else {
-            const int32_t *cp = cols + (int64_t)ka * 64 + lane;
-#pragma unroll 2
-            for (int32_t k = ka; k < kb; k++) {
-                const int64_t c = ld_stream<NT>(cp);
-                STAN_SPMV_BLOCK(c, vp)
-                cp += 64;
-                vp += vstream<VT>::STRIDE;
-            }
-        }
+        walk_slots<NT, 2, vstream<VT>::STRIDE>(cs, cols, slice, lane, k0, ka, kb, vals,
+                                               [&](int64_t c, const VT *vp) { STAN_SPMV_BLOCK(c, vp) });
     }
     if (half) { acc[sl][0][lane] = y0; acc[sl][1][lane] = y1; acc[sl][2][lane] = y2; }
     __syncthreads();
     double d = 0, e = 0;
     if (!half && slice < nslices && row < nloc) {
         y0 += acc[sl][0][lane]; y1 += acc[sl][1][lane]; y2 += acc[sl][2][lane];
-        if (NT) {
-            __builtin_nontemporal_store(y0, y + 3 * row); __builtin_nontemporal_store(y1, y + 3 * row + 1);
-            __builtin_nontemporal_store(y2, y + 3 * row + 2);
-        } else { y[3 * row] = y0; y[3 * row + 1] = y1; y[3 * row + 2] = y2; }
-        if (DOT) {
-            const double x0 = x[3 * row], x1 = x[3 * row + 1], x2 = x[3 * row + 2];
-            d = y0 * x0 + y1 * x1 + y2 * x2;
-            if (DOT == 2) e = x0 * x0 + x1 * x1 + x2 * x2;
-        }
+        store_row<NT>(y, row, y0, y1, y2);
+        if (DOT) dot_terms<DOT>(x, row, y0, y1, y2, d, e);
     }
-    if (DOT) {
-        const double t = block_sum(d, sh);
-        if (DOT == 2) {
-            const double u = block_sum(e, sh);
-            if (threadIdx.x == 0) {
-                st_agent(partial + 2 * (int64_t)(blockIdx.x + poff), u);
-                st_agent(partial + 2 * (int64_t)(blockIdx.x + poff) + 1, t);
-            }
-        } else if (threadIdx.x == 0) st_agent(partial + blockIdx.x + poff, t);
-        if (fold.counter && fold_arrive(fold, &sh_last)) fold_finish<(DOT == 2 ? 2 : 1)>(fold, partial, sh);
-    }
+    if (DOT) dot_reduce<DOT>(d, e, partial, poff, fold, sh, &sh_last);
 }
 
 // ---- the yardstick of the product's roofline --------------------------------------------------------------------------
@@ -296,12 +278,8 @@ k_spmv_pair(int32_t nslices, int64_t nloc, const int32_t *__restrict__ slot_ptr,
 __global__ void __launch_bounds__(256)
 k_value_stream(int32_t nslices, const int32_t *__restrict__ slot_ptr, const double *__restrict__ vals, double *sink) {
     __shared__ double sh[4];
-    constexpr int CH = 32;
     const int lane = threadIdx.x & 63;
-    int64_t bid = blockIdx.x;
-    const int64_t win = 8 * CH, grp = bid / win, within = bid - grp * win;
-    if ((grp + 1) * win <= (int64_t)gridDim.x) bid = grp * win + (within & 7) * CH + (within >> 3);
-    const int64_t slice = bid * 4 + (threadIdx.x >> 6);
+    const int64_t slice = xcd_chunked<32>(blockIdx.x) * 4 + (threadIdx.x >> 6);
     double s0 = 0, s1 = 0, s2 = 0;
     if (slice < nslices) {
         const int32_t k0 = slot_ptr[slice], k1 = slot_ptr[slice + 1];
@@ -345,22 +323,13 @@ k_spmv_first(int32_t nslices, int64_t nloc, const int32_t *__restrict__ slot_ptr
     // (never skipped: the scaling must happen even when the solve has stopped at its first residual test -- the caller
     // only launches it for a solve that iterates)
     (void)st; (void)kiter;
-    constexpr int CH = 32;
     const int lane = threadIdx.x & 63;
-    int64_t bid = blockIdx.x;
-    {
-        const int64_t win = 8 * CH, grp = bid / win, within = bid - grp * win;
-        if ((grp + 1) * win <= (int64_t)gridDim.x) bid = grp * win + (within & 7) * CH + (within >> 3);
-    }
-    const int64_t slice = bid * 4 + (threadIdx.x >> 6);
+    const int64_t slice = xcd_chunked<32>(blockIdx.x) * 4 + (threadIdx.x >> 6);
     double y0 = 0, y1 = 0, y2 = 0;
-    const int64_t row = slice < nslices ? (int64_t)rowof[slice * 64 + lane] : nloc;
+    const int64_t row = row_at(slice, nslices, rowof, lane, nloc);
     if (slice < nslices) {
         const int32_t k0 = slot_ptr[slice], k1 = slot_ptr[slice + 1];
         const double sr0 = s[3 * row], sr1 = s[3 * row + 1], sr2 = s[3 * row + 2];
-        const int32_t *cp = cols + (int64_t)k0 * 64 + lane;
-        double *vp = vals + (int64_t)k0 * 9 * 64 + lane;
-        const int pmode = cs.packed ? (int)cs.ok[slice] : 0;
 #define STAN_SPMV_FIRST_BLOCK(C, VP)                                                                   \
     {                                                                                                  \
         double a[9];                                                                                   \
@@ -375,57 +344,15 @@ k_spmv_first(int32_t nslices, int64_t nloc, const int32_t *__restrict__ slot_ptr
         y1 += a[3] * x0 + a[4] * x1 + a[5] * x2;                                                       \
         y2 += a[6] * x0 + a[7] * x1 + a[8] * x2;                                                       \
     }
-        if (pmode != 0) {
-            const uint32_t *cq = cs.packed + (int64_t)cs.pair_ptr[slice] * 64 + lane;
-            const int32_t *bp = cs.base + __builtin_amdgcn_readfirstlane(k0);
-            const int32_t *bq = cs.base2 + __builtin_amdgcn_readfirstlane(k0);
-            const bool cb = (cs.cmask[slice] >> lane) & 1ull;
-            int32_t k = k0;
-            for (; k + 1 < k1; k += 2) {
-                const uint32_t wd = ld_stream<true>(cq);
-                const int32_t b0 = bp[0], b1 = bp[1], q0 = bq[0], q1 = bq[1];
-                const int64_t c = (int64_t)(cb ? q0 : b0) + (int64_t)(wd & 0xffffu);
-                const int64_t c2 = (int64_t)(cb ? q1 : b1) + (int64_t)(wd >> 16);
-                STAN_SPMV_FIRST_BLOCK(c, vp)
-                STAN_SPMV_FIRST_BLOCK(c2, vp + 9 * 64)
-                cq += 64; bp += 2; bq += 2;
-                vp += 2 * 9 * 64;
-            }
-            if (k < k1) {
-                const int32_t b0 = bp[0], q0 = bq[0];
-                const int64_t c = (int64_t)(cb ? q0 : b0) + (int64_t)(ld_stream<true>(cq) & 0xffffu);
-                STAN_SPMV_FIRST_BLOCK(c, vp)
-            }
-        } else {
-            for (int32_t k = k0; k < k1; k++) {
-                const int64_t c = ld_stream<true>(cp);
-                STAN_SPMV_FIRST_BLOCK(c, vp)
-                cp += 64;
-                vp += 9 * 64;
-            }
-        }
+        walk_slots<true, 1, 9 * 64>(cs, cols, slice, lane, k0, k0, k1, vals,
+                                    [&](int64_t c, double *vp) { STAN_SPMV_FIRST_BLOCK(c, vp) });
 #undef STAN_SPMV_FIRST_BLOCK
-        if (row < nloc) {
-            __builtin_nontemporal_store(y0, y + 3 * row); __builtin_nontemporal_store(y1, y + 3 * row + 1);
-            __builtin_nontemporal_store(y2, y + 3 * row + 2);
-        }
+        if (row < nloc) store_row<true>(y, row, y0, y1, y2);
     }
     if (DOT) {
         double d = 0, e = 0;
-        if (slice < nslices && row < nloc) {
-            const double x0 = x[3 * row], x1 = x[3 * row + 1], x2 = x[3 * row + 2];
-            d = y0 * x0 + y1 * x1 + y2 * x2;
-            if (DOT == 2) e = x0 * x0 + x1 * x1 + x2 * x2;
-        }
-        const double t = block_sum(d, sh);
-        if (DOT == 2) {
-            const double u = block_sum(e, sh);
-            if (threadIdx.x == 0) {
-                st_agent(partial + 2 * (int64_t)blockIdx.x, u);
-                st_agent(partial + 2 * (int64_t)blockIdx.x + 1, t);
-            }
-        } else if (threadIdx.x == 0) st_agent(partial + blockIdx.x, t);
-        if (fold.counter && fold_arrive(fold, &sh_last)) fold_finish<(DOT == 2 ? 2 : 1)>(fold, partial, sh);
+        if (slice < nslices && row < nloc) dot_terms<DOT>(x, row, y0, y1, y2, d, e);
+        dot_reduce<DOT>(d, e, partial, 0, fold, sh, &sh_last);
     }
 }
 
@@ -451,10 +378,9 @@ k_spmv_small(int32_t nslices, int64_t nloc, const int32_t *__restrict__ slot_ptr
     if (stopped(st, kiter)) { fold_skip(fold); return; }
     constexpr bool NT = false;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int64_t slice = blockIdx.x;
-    if (slist) slice = slice < nlist ? (int64_t)slist[slice] : (int64_t)nslices;
+    const int64_t slice = slice_at(blockIdx.x, slist, nlist, nslices);
     double y0 = 0, y1 = 0, y2 = 0;
-    const int64_t row = slice < nslices ? (int64_t)rowof[slice * 64 + lane] : nloc;   // SELL-C-sigma: position -> block row
+    const int64_t row = row_at(slice, nslices, rowof, lane, nloc);
     if (slice < nslices) {
         const int32_t k0 = slot_ptr[slice], k1 = slot_ptr[slice + 1];
         const int pmode = cs.packed ? (int)cs.ok[slice] : 0;   // 0 int32 columns, 1 / 2 packed (one / two bases per slot)
@@ -481,25 +407,11 @@ k_spmv_small(int32_t nslices, int64_t nloc, const int32_t *__restrict__ slot_ptr
         y1 = ((acc[1][0][lane] + acc[1][1][lane]) + acc[1][2][lane]) + acc[1][3][lane];
         y2 = ((acc[2][0][lane] + acc[2][1][lane]) + acc[2][2][lane]) + acc[2][3][lane];
         if (slice < nslices && row < nloc) {
-            y[3 * row] = y0; y[3 * row + 1] = y1; y[3 * row + 2] = y2;
-            if (DOT) {
-                const double x0 = x[3 * row], x1 = x[3 * row + 1], x2 = x[3 * row + 2];
-                d = y0 * x0 + y1 * x1 + y2 * x2;
-                if (DOT == 2) e = x0 * x0 + x1 * x1 + x2 * x2;
-            }
+            store_row<NT>(y, row, y0, y1, y2);
+            if (DOT) dot_terms<DOT>(x, row, y0, y1, y2, d, e);
         }
     }
-    if (DOT) {
-        const double t = block_sum(d, sh);
-        if (DOT == 2) {
-            const double u = block_sum(e, sh);
-            if (threadIdx.x == 0) {
-                st_agent(partial + 2 * (int64_t)(blockIdx.x + poff), u);
-                st_agent(partial + 2 * (int64_t)(blockIdx.x + poff) + 1, t);
-            }
-        } else if (threadIdx.x == 0) st_agent(partial + blockIdx.x + poff, t);
-        if (fold.counter && fold_arrive(fold, &sh_last)) fold_finish<(DOT == 2 ? 2 : 1)>(fold, partial, sh);
-    }
+    if (DOT) dot_reduce<DOT>(d, e, partial, poff, fold, sh, &sh_last);
 }
 
 // Two right-hand sides in ONE pass over the matrix: y = A x and y2 = A x2 (+ the x.y partial).
@@ -519,19 +431,12 @@ k_spmv2(int32_t nslices, int64_t nloc, const int32_t *__restrict__ slot_ptr, con
     if (stopped(st, kiter)) { fold_skip(fold); return; }
     const int lane = threadIdx.x & 63;
     int64_t bid = blockIdx.x;
-    {   // XCD-chunked workgroup mapping, as in k_spmv (variant 9)
-        constexpr int CH = 32;
-        const int64_t win = 8 * CH, grp = bid / win, within = bid - grp * win;
-        if ((grp + 1) * win <= (int64_t)gridDim.x) bid = grp * win + (within & 7) * CH + (within >> 3);
-    }
-    int64_t slice = bid * 4 + (threadIdx.x >> 6);
-    if (slist) slice = slice < nlist ? (int64_t)slist[slice] : (int64_t)nslices;
+    bid = xcd_chunked<32>(bid);
+    const int64_t slice = slice_at(bid * 4 + (threadIdx.x >> 6), slist, nlist, nslices);
     double y0 = 0, y1 = 0, yy2 = 0, z0 = 0, z1 = 0, z2 = 0;
-    const int64_t row = slice < nslices ? (int64_t)rowof[slice * 64 + lane] : nloc;   // SELL-C-sigma: position -> block row
+    const int64_t row = row_at(slice, nslices, rowof, lane, nloc);
     if (slice < nslices) {
         const int32_t k0 = slot_ptr[slice], k1 = slot_ptr[slice + 1];
-        const int32_t *cp = cols + (int64_t)k0 * 64 + lane;
-        const VT *vp = vals + (int64_t)k0 * vstream<VT>::STRIDE + lane;
 #define STAN_SPMV2_BLOCK(C, VP)                                                       \
     {                                                                                 \
         double a[9];                                                                  \
@@ -549,51 +454,17 @@ k_spmv2(int32_t nslices, int64_t nloc, const int32_t *__restrict__ slot_ptr, con
         z1 += a[3] * u0 + a[4] * u1 + a[5] * u2;                                      \
         z2 += a[6] * u0 + a[7] * u1 + a[8] * u2;                                      \
     }
-        if (cs.packed && cs.ok[slice] != 0) {   // both packed modes, as in k_spmv: a one-base slice has cmask 0 and base2 = base
-            const uint32_t *cq = cs.packed + (int64_t)cs.pair_ptr[slice] * 64 + lane;
-            const int32_t *bp = cs.base + __builtin_amdgcn_readfirstlane(k0);
-            const int32_t *bq = cs.base2 + __builtin_amdgcn_readfirstlane(k0);
-            const bool cb = (cs.cmask[slice] >> lane) & 1ull;
-            int32_t k = k0;
-            for (; k + 1 < k1; k += 2) {
-                const uint32_t wd = ld_stream<true>(cq);
-                const int32_t b0 = bp[0], b1 = bp[1], q0 = bq[0], q1 = bq[1];   // scalar loads, selects of values (k_spmv)
-                const int64_t c = (int64_t)(cb ? q0 : b0) + (int64_t)(wd & 0xffffu);
-                const int64_t c2 = (int64_t)(cb ? q1 : b1) + (int64_t)(wd >> 16);
-                STAN_SPMV2_BLOCK(c, vp)
-                STAN_SPMV2_BLOCK(c2, vp + vstream<VT>::STRIDE)
-                cq += 64;
-                bp += 2;
-                bq += 2;
-                vp += 2 * vstream<VT>::STRIDE;
-            }
-            if (k < k1) {
-                const int32_t b0 = bp[0], q0 = bq[0];
-                const int64_t c = (int64_t)(cb ? q0 : b0) + (int64_t)(ld_stream<true>(cq) & 0xffffu);
-                STAN_SPMV2_BLOCK(c, vp)
-            }
-        } else {
-#pragma unroll 2
-            for (int32_t k = k0; k < k1; k++) {
-                const int64_t c = ld_stream<true>(cp);
-                STAN_SPMV2_BLOCK(c, vp)
-                cp += 64;
-                vp += vstream<VT>::STRIDE;
-            }
-        }
+        walk_slots<true, 2, vstream<VT>::STRIDE>(cs, cols, slice, lane, k0, k0, k1, vals,
+                                                 [&](int64_t c, const VT *vp) { STAN_SPMV2_BLOCK(c, vp) });
 #undef STAN_SPMV2_BLOCK
-        if (row < nloc) {
-            __builtin_nontemporal_store(y0, y + 3 * row); __builtin_nontemporal_store(y1, y + 3 * row + 1);
-            __builtin_nontemporal_store(yy2, y + 3 * row + 2);
-            __builtin_nontemporal_store(z0, y2 + 3 * row); __builtin_nontemporal_store(z1, y2 + 3 * row + 1);
-            __builtin_nontemporal_store(z2, y2 + 3 * row + 2);
+        if (row < nloc) {   // both products are read exactly once, by k_step
+            store_row<true>(y, row, y0, y1, yy2);
+            store_row<true>(y2, row, z0, z1, z2);
         }
     }
-    double d = 0;
-    if (slice < nslices && row < nloc) d = y0 * x[3 * row] + y1 * x[3 * row + 1] + yy2 * x[3 * row + 2];
-    const double t = block_sum(d, sh);
-    if (threadIdx.x == 0) st_agent(partial + blockIdx.x + poff, t);
-    if (fold.counter && fold_arrive(fold, &sh_last)) fold_finish<1>(fold, partial, sh);
+    double d = 0, e = 0;
+    if (slice < nslices && row < nloc) dot_terms<1>(x, row, y0, y1, yy2, d, e);
+    dot_reduce<1>(d, e, partial, poff, fold, sh, &sh_last);
 }
 
 
@@ -617,16 +488,11 @@ k_spmv_fold(int32_t nslices, int64_t nloc, const int32_t *__restrict__ fold_ptr,
     if (stopped(st, kiter)) { fold_skip(fold); return; }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int64_t bid = blockIdx.x;
-    {   // XCD-chunked workgroup mapping, as in k_spmv (variant 9)
-        constexpr int CH = 32;
-        const int64_t win = 8 * CH, grp = bid / win, within = bid - grp * win;
-        if ((grp + 1) * win <= (int64_t)gridDim.x) bid = grp * win + (within & 7) * CH + (within >> 3);
-    }
-    int64_t slice = bid * 4 + w;
-    if (slist) slice = slice < nlist ? (int64_t)slist[slice] : (int64_t)nslices;
+    bid = xcd_chunked<32>(bid);
+    const int64_t slice = slice_at(bid * 4 + w, slist, nlist, nslices);
     double y0 = 0, y1 = 0, yy2 = 0, z0 = 0, z1 = 0, z2 = 0;     // own row
     double f0 = 0, f1 = 0, f2 = 0, g0 = 0, g1 = 0, g2 = 0;      // the piece of a longer row this lane carries
-    const int64_t row = slice < nslices ? (int64_t)rowof[slice * 64 + lane] : nloc;
+    const int64_t row = row_at(slice, nslices, rowof, lane, nloc);
     uint32_t m = 0;
     if (slice < nslices) {
         m = meta[slice * 64 + lane];
@@ -722,31 +588,13 @@ k_spmv_fold(int32_t nslices, int64_t nloc, const int32_t *__restrict__ fold_ptr,
             if (NRHS == 2) { z0 += fsh[w][3][j]; z1 += fsh[w][4][j]; z2 += fsh[w][5][j]; }
         }
     }
-    if (slice < nslices) {
-        if (row < nloc) {
-            __builtin_nontemporal_store(y0, y + 3 * row); __builtin_nontemporal_store(y1, y + 3 * row + 1);
-            __builtin_nontemporal_store(yy2, y + 3 * row + 2);
-            if (NRHS == 2) {
-                __builtin_nontemporal_store(z0, y2 + 3 * row); __builtin_nontemporal_store(z1, y2 + 3 * row + 1);
-                __builtin_nontemporal_store(z2, y2 + 3 * row + 2);
-            }
-        }
+    if (slice < nslices && row < nloc) {
+        store_row<true>(y, row, y0, y1, yy2);
+        if (NRHS == 2) store_row<true>(y2, row, z0, z1, z2);
     }
     if (DOT) {
         double d = 0, e = 0;
-        if (slice < nslices && row < nloc) {
-            const double x0 = x[3 * row], x1 = x[3 * row + 1], xx2 = x[3 * row + 2];
-            d = y0 * x0 + y1 * x1 + yy2 * xx2;
-            if (DOT == 2) e = x0 * x0 + x1 * x1 + xx2 * xx2;
-        }
-        const double t = block_sum(d, sh);
-        if (DOT == 2) {
-            const double u = block_sum(e, sh);
-            if (threadIdx.x == 0) {
-                st_agent(partial + 2 * (int64_t)(blockIdx.x + poff), u);
-                st_agent(partial + 2 * (int64_t)(blockIdx.x + poff) + 1, t);
-            }
-        } else if (threadIdx.x == 0) st_agent(partial + blockIdx.x + poff, t);
-        if (fold.counter && fold_arrive(fold, &sh_last)) fold_finish<(DOT == 2 ? 2 : 1)>(fold, partial, sh);
+        if (slice < nslices && row < nloc) dot_terms<DOT>(x, row, y0, y1, yy2, d, e);
+        dot_reduce<DOT>(d, e, partial, poff, fold, sh, &sh_last);
     }
 }

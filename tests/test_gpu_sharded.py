@@ -174,8 +174,9 @@ def _broken_library_run(tmp_path, tag, n, env_extra):
 
 def test_a_serialising_stand_in_hides_a_missing_stream_wait_and_the_stream_ordered_one_does_not(built_libs, tmp_path):
     """VERDICT r05 item 1, shown on a DELIBERATELY BROKEN library (stan_amd/csrc/lab/drop_overlap_wait.patch ->
-    build_broken/libstan_hip_no_overlap_wait.so: cg.hip's boundary product and the vector kernels behind it no longer
-    wait for the interior product on the side stream -- `hipStreamWaitEvent(st_, ev_b)` dropped).
+    build_broken/libstan_hip_no_overlap_wait.so: cg.hip's boundary product -- of a single product and of the fused two-product
+    pass alike -- and the vector kernels behind it no longer wait for the interior product on the side stream --
+    `hipStreamWaitEvent(st_, ev_b)` dropped).
       * Over a transport that drains the DEVICE at every call (FAKE_RCCL_SYNC_DEVICE=1: the fully serialising stand-in)
         the interior product has always finished when the exchange returns: the broken library reproduces the oracle
         fixture like the good one.  A suite that only ever ran over such a transport would never see the bug.
