@@ -442,18 +442,6 @@ __global__ void k_count_fixed(int64_t n, const int32_t *red, unsigned long long 
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, (unsigned long long)c);
 }
 
-__global__ void k_i64_to_i32(const int64_t *in, int32_t *out, int64_t n) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (int32_t)in[i];
-}
-
-// halo_glob[rank] = g for every flagged g
-__global__ void k_compact_flags(const int32_t *flag, const int64_t *rank, int32_t *out,
-                                int64_t n) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && flag[i]) out[rank[i]] = (int32_t)i;
-}
-
 // ---- step 3: numeric.  256 threads = 4 wavefronts assemble the block rows of 16 consecutive --
 // positions of a slice (position -> row through rowof: SELL-C-sigma) ---------------------------
 struct numeric_args {
@@ -916,17 +904,288 @@ k_ke_batch(int64_t n, const double *xyz8, double lam, double G, const uint8_t *t
     for (int i = lane; i < 576; i += 64) out[e * 576 + i] = ke[i];
 }
 
-inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
+// One assembly, phase by phase (the shape of cg.hip's cg_run; stan_assemble_device is the driver).  All temporaries
+// belong to the ONE scope `tmp` and live until the driver returns: where a block goes back to the context's pool
+// decides which block a later allocation gets, so no phase frees on its own.
+struct assembly_run {
+    stan_ctx *ctx;
+    int64_t n_nodes; const double *d_xyz; const int32_t *d_node_dof;   // the inputs, in the order of the entry point
+    int64_t n_elem; const int32_t *d_conn, *d_elem_mat; const uint8_t *d_elem_type;
+    int32_t n_mat; const double *mat_E_nu;
+    int64_t n_dof; const int32_t *d_red;
+    stan_matrix *K = nullptr;
+    hipStream_t st = ctx->stream;
+    int64_t *d_status = ctx->d_status;
+    dev_scope tmp{ctx};
+    int64_t nb = 0, r0 = 0, r1 = 0, nloc = 0, nrows_pad = 0;
+    int64_t n_inc = 0, n_big = 0;   // incidences of the owned rows; rows with more than STAN_MAX_INCIDENT of them
+    // the temporaries that cross phases
+    std::vector<double> lamG;   // host side of d_lamG: outlives the copy
+    double *d_lamG = nullptr, *d_xrow = nullptr;
+    int32_t *d_perm = nullptr, *d_crow = nullptr, *d_list = nullptr, *d_ucols = nullptr, *d_width = nullptr;
+    int32_t *d_big_rows = nullptr;   // the n_big rows (listed before the counts become the fill cursor)
+    int64_t *d_ptr = nullptr, *d_halo_rank = nullptr;
+    static constexpr int BIG_LDS_INTS = 32768;   // 128 KB of the CU's 160 KB for k_symbolic_big's two sort buffers (up to 3640 incidences)
 
-struct tmp_free {  // releases device temporaries on every exit path (to the context's pool)
-    stan_ctx *ctx = nullptr;
-    std::vector<void *> p;
-    ~tmp_free() {
-        for (void *q : p) stan_dfree(ctx, q);
-    }
-    template <typename T>
-    void own(T *q) { p.push_back((void *)q); }
+    int partition();     // row starts, slices, status words, materials
+    int incidence();     // node permutation, (element, local node) lists of the owned rows, input errors
+    int symbolic();      // distinct columns per row, SELL-C-sigma positions, halo numbering
+    int layout();        // slice widths -> slot pointers, columns, the value block
+    int numeric();       // row-owner gather (+ wide slices) or colour scatter
+    int slice_lists();   // interior / boundary slices of the overlapped product
+    int halo_plan();     // per-neighbour send rows, recv_off / send_off
 };
+
+int assembly_run::partition() {
+    K->n_dof = n_dof;
+    K->nb_glob = nb = n_dof / 3;
+    K->n_elem_scanned = n_elem;
+    // contiguous block-row partition, cut on slice boundaries
+    K->row_starts.resize(ctx->nranks + 1);
+    for (int r = 0; r <= ctx->nranks; r++) K->row_starts[r] = stan_row_start(nb, ctx->nranks, r);
+    r0 = K->r0 = K->row_starts[ctx->rank], r1 = K->r1 = K->row_starts[ctx->rank + 1];
+    nloc = K->nloc = r1 - r0;
+    K->nslices = (int32_t)((nloc + 63) / 64);
+    nrows_pad = (int64_t)K->nslices * 64;
+    HIPCHK(ctx, hipMemsetAsync(d_status, 0, 16 * 8, st));
+    static const long long init = 0x7fffffffffffffffLL;
+    HIPCHK(ctx, hipMemcpyAsync(d_status + SS_BAD_ELEM, &init, 8, hipMemcpyHostToDevice, st));
+    // materials -> (lambda, G)
+    lamG.resize(2 * (size_t)n_mat);
+    for (int m = 0; m < n_mat; m++) stan_lame(mat_E_nu[2 * m], mat_E_nu[2 * m + 1], &lamG[2 * m], &lamG[2 * m + 1]);
+    STANCHK(tmp.alloc(&d_lamG, lamG.size()));
+    HIPCHK(ctx, hipMemcpyAsync(d_lamG, lamG.data(), lamG.size() * 8, hipMemcpyHostToDevice, st));
+    return STAN_OK;
+}
+
+int assembly_run::incidence() {
+    STANCHK(tmp.alloc(&d_perm, (size_t)n_nodes));
+    STANCHK(stan_dmalloc(ctx, &K->d_fixmask, (size_t)nb));
+    STANCHK(stan_dmalloc(ctx, &K->d_red, (size_t)n_dof));
+    HIPCHK(ctx, hipMemsetAsync(K->d_fixmask, 0, (size_t)nb, st));
+    HIPCHK(ctx, hipMemcpyAsync(K->d_red, d_red, (size_t)n_dof * 4, hipMemcpyDeviceToDevice, st));
+    STANCHK(tmp.alloc(&d_xrow, (size_t)nb * 3));
+    STANCHK(tmp.alloc(&d_crow, (size_t)(n_elem > 0 ? n_elem * 8 : 1)));
+    hipLaunchKernelGGL(k_perm, dim3(nblk(n_nodes, 256)), dim3(256), 0, st, n_nodes, nb, d_node_dof,
+                       d_red, d_xyz, d_perm, K->d_fixmask, d_xrow, d_status);
+    // incidence lists of owned rows
+    int32_t *d_cnt;
+    STANCHK(tmp.alloc(&d_cnt, (size_t)nrows_pad + 1));
+    STANCHK(tmp.alloc(&d_ptr, (size_t)nrows_pad + 2));
+    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, ((size_t)nrows_pad + 1) * 4, st));
+    if (n_elem > 0)
+        hipLaunchKernelGGL(k_count_incident, dim3(nblk(n_elem * 8, 256)), dim3(256), 0, st, n_elem,
+                           n_nodes, d_conn, d_perm, r0, r1, d_cnt, d_crow, d_status);
+    if (nrows_pad > 0)
+        hipLaunchKernelGGL(k_max_incident, dim3(nblk(nrows_pad, 256)), dim3(256), 0, st, nrows_pad, d_cnt, BIG_LDS_INTS, d_status);
+    STANCHK(stan_scan_total(ctx, d_cnt, d_ptr, nrows_pad, SS_H_NINC));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_ERRBITS, d_status + SS_ERRBITS, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_MAXDEG, d_status + SS_MAXDEG, 24, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const int64_t bits = ctx->h_status[SS_ERRBITS];
+    if (bits & ERR_DOF_LAYOUT) { ctx->err = "assemble: Node.DOF is not {3i,3i+1,3i+2} with 3i < n_dof (Node.cs:218-223)"; return STAN_E_DOF_LAYOUT; }
+    if (bits & ERR_CONN_RANGE) { ctx->err = "assemble: connectivity references a node index outside [0,n_nodes)"; return STAN_E_ARG; }
+    n_inc = ctx->h_status[SS_H_NINC];
+    n_big = ctx->h_status[SS_NBIG];
+    if (n_big > 0) {
+        STANCHK(tmp.alloc(&d_big_rows, (size_t)n_big));
+        HIPCHK(ctx, hipMemsetAsync(d_status + SS_COUNTER, 0, 8, st));
+        hipLaunchKernelGGL(k_list_above, dim3(nblk(nrows_pad, 256)), dim3(256), 0, st, nrows_pad, d_cnt, STAN_MAX_INCIDENT, d_big_rows,
+                           (unsigned long long *)(d_status + SS_COUNTER));
+    }
+    STANCHK(tmp.alloc(&d_list, (size_t)n_inc));
+    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, ((size_t)nrows_pad + 1) * 4, st));
+    if (n_elem > 0)
+        hipLaunchKernelGGL(k_fill_incident, dim3(nblk(n_elem * 8, 256)), dim3(256), 0, st, n_elem,
+                           d_crow, r0, r1, d_ptr, d_cnt, d_list);
+    return STAN_OK;
+}
+
+int assembly_run::symbolic() {
+    STANCHK(stan_dmalloc(ctx, &K->d_rowlen, (size_t)nrows_pad));
+    int32_t *d_refflag = nullptr;
+    if (ctx->nranks > 1) {
+        STANCHK(tmp.alloc(&d_refflag, (size_t)nb));
+        STANCHK(tmp.alloc(&d_halo_rank, (size_t)nb + 1));
+        HIPCHK(ctx, hipMemsetAsync(d_refflag, 0, (size_t)nb * 4, st));
+    }
+    // distinct columns of row i land in d_ucols[8 * d_ptr[i] ...] (8 candidates per incidence)
+    STANCHK(tmp.alloc(&d_ucols, (size_t)(n_inc > 0 ? 8 * n_inc : 1)));
+    if (nrows_pad > 0)
+        hipLaunchKernelGGL(k_symbolic, dim3((unsigned)nrows_pad), dim3(64), 0, st, nloc, r0, r1, d_ptr,
+                           d_list, d_crow, K->d_rowlen, d_refflag, d_ucols, d_status);
+    if (n_big > 0) {   // high-valence nodes: the slow symbolic path, one workgroup per listed row
+        int64_t PD = 64, PC = 64;
+        while (PD < ctx->h_status[SS_MAXDEG]) PD <<= 1;
+        while (PC < 8 * ctx->h_status[SS_MAXDEG]) PC <<= 1;
+        if (PC >= (int64_t)1 << 30) { ctx->err = "assemble: a node with more than 2^26 incident elements"; return STAN_E_VALENCE; }
+        const int64_t lds_ints = PD + PC < BIG_LDS_INTS ? PD + PC : BIG_LDS_INTS;
+        int32_t *d_scratch = nullptr;
+        if (ctx->h_status[SS_NGIANT] > 0) STANCHK(tmp.alloc(&d_scratch, (size_t)(ctx->h_status[SS_NGIANT] * (PD + PC))));
+        HIPCHK(ctx, hipMemsetAsync(d_status + SS_COUNTER, 0, 8, st));   // scratch tickets
+        if (lds_ints * 4 > 64 * 1024)
+            HIPCHK(ctx, hipFuncSetAttribute((const void *)k_symbolic_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_ints * 4)));
+        hipLaunchKernelGGL(k_symbolic_big, dim3((unsigned)n_big), dim3(256), (size_t)lds_ints * 4, st, d_big_rows, r0, r1, d_ptr, d_list,
+                           d_crow, K->d_rowlen, d_refflag, d_ucols, (int)lds_ints, d_scratch, PD + PC,
+                           (unsigned long long *)(d_status + SS_COUNTER));
+    }
+    // SELL-C-sigma: positions of the rows inside the sliced layout
+    K->sigma = ctx->sell_sigma < 1 ? 1 : ctx->sell_sigma > 32 ? 32 : ctx->sell_sigma;
+    STANCHK(stan_dmalloc(ctx, &K->d_rowof, (size_t)(nrows_pad > 0 ? nrows_pad : 1)));
+    STANCHK(stan_dmalloc(ctx, &K->d_posof, (size_t)(nrows_pad > 0 ? nrows_pad : 1)));
+    if (nrows_pad > 0)
+        hipLaunchKernelGGL(k_window_sort, dim3(nblk(K->nslices, K->sigma)), dim3(64), 0, st, nrows_pad, K->sigma,
+                           K->d_rowlen, K->d_rowof, K->d_posof);
+    // halo numbering: halo_glob[rank of g among the referenced foreign rows] = g
+    K->nhalo = 0;
+    if (ctx->nranks > 1) STANCHK(stan_compact_flags(ctx, d_refflag, d_halo_rank, nb, SS_H_NHALO, &K->d_halo_glob, &K->nhalo));
+    return STAN_OK;
+}
+
+int assembly_run::layout() {
+    int64_t *d_sp64;
+    STANCHK(tmp.alloc(&d_width, (size_t)K->nslices + 1));
+    STANCHK(tmp.alloc(&d_sp64, (size_t)K->nslices + 2));
+    HIPCHK(ctx, hipMemsetAsync(d_status + SS_WIDTH_SUM, 0, 16, st));
+    if (K->nslices > 0)
+        hipLaunchKernelGGL(k_slice_width, dim3(nblk(K->nslices, 4)), dim3(256), 0, st, K->nslices, K->d_rowlen,
+                           K->d_rowof, d_width, (unsigned long long *)(d_status + SS_WIDTH_SUM), (int32_t *)(d_status + SS_WIDTH_MAX));
+    STANCHK(stan_scan_total(ctx, d_width, d_sp64, K->nslices, SS_H_NSLOTS));
+    STANCHK(stan_slot_ptr_narrow(ctx, d_sp64, K->nslices, &K->d_slot_ptr));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_ERRBITS, d_status + SS_ERRBITS, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_H_NBLOCKS, d_status + SS_WIDTH_SUM, 16, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    K->nslots = ctx->h_status[SS_H_NSLOTS];
+    K->nblocks = ctx->h_status[SS_H_NBLOCKS];
+    K->max_row_blocks = (int32_t)(ctx->h_status[SS_H_MAXROW] & 0xffffffff);
+    // (the cols index fits, but keep slot arithmetic in int32 honest)
+    if (K->nslots * 64 >= (int64_t)1 << 31) { ctx->err = "assemble: more than 2^31 ELL entries on one rank"; return STAN_E_ARG; }
+    STANCHK(stan_dmalloc(ctx, &K->d_cols, (size_t)K->nslots * 64));
+    if (K->nslices > 0) {
+        int32_t wmax = K->max_row_blocks > 0 ? K->max_row_blocks : 1;
+        if (wmax > STAN_MAX_ROW_BLOCKS) wmax = STAN_MAX_ROW_BLOCKS;         // wider slices pass through the tile in chunks
+        const size_t lds = (size_t)4 * 64 * (wmax | 1) * sizeof(int32_t);   // <= 4 * 64 * 97 * 4 = 99 KB
+        if (lds > 64 * 1024)
+            HIPCHK(ctx, hipFuncSetAttribute((const void *)k_fill_cols, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k_fill_cols, dim3(nblk(K->nslices, 4)), dim3(256), lds, st, K->nslices, nloc, r0, r1,
+                           K->d_slot_ptr, K->d_rowof, K->d_rowlen, d_ptr, d_ucols, (const int64_t *)d_halo_rank,
+                           K->d_cols, wmax);
+    }
+    // (after the columns are in place: an allocation by trial times the SpMV itself, which needs the columns)
+    return stan_dmalloc_streamed(ctx, (void **)&K->d_vals, (size_t)K->nslots * 9 * 64 * 8,
+                                 [&](const void *q, float *ms, bool self) {
+                                     return stan_spmv_probe(ctx, K, q, (size_t)K->nslots * 9 * 64 * 8, STAN_PREC_FP64, ms, self);
+                                 });
+}
+
+int assembly_run::numeric() {
+    if (ctx->assembly_mode == 1) {
+        if (ctx->nranks > 1) { ctx->err = "assembly mode 1 (colour scatter) is single-rank only"; return STAN_E_UNSUPPORTED; }
+        STANCHK(stan_assemble_colour_scatter(ctx, K, n_elem, d_conn, d_perm, d_xyz, d_elem_mat, d_elem_type,
+                                             d_lamG, d_ptr, d_list, (long long *)(d_status + SS_BAD_ELEM)));
+    } else {
+        ctx->prof_colours = 0;
+        numeric_args A;
+        A.nloc = nloc; A.r0 = r0; A.r1 = r1; A.nhalo = K->nhalo;
+        A.ptr = d_ptr; A.list = d_list; A.crow = d_crow; A.xrow = d_xrow;
+        A.elem_mat = d_elem_mat; A.elem_type = d_elem_type; A.mat_lamG = d_lamG;
+        A.fixmask = K->d_fixmask; A.halo_glob = K->d_halo_glob; A.halo_rank = d_halo_rank;
+        A.rowlen = K->d_rowlen; A.rowof = K->d_rowof; A.slot_ptr = K->d_slot_ptr; A.cols = K->d_cols; A.vals = K->d_vals;
+        A.bad_elem = (long long *)(d_status + SS_BAD_ELEM);
+        A.wide_slices = nullptr;
+        A.wmax = K->max_row_blocks > 0 ? K->max_row_blocks : 1;
+        const bool wide = A.wmax > STAN_MAX_ROW_BLOCKS;   // some slice holds a high-valence row: it goes to k_numeric_wide
+        if (wide) A.wmax = STAN_MAX_ROW_BLOCKS;
+        const size_t lds = (size_t)STAN_NUM_ROWS * A.wmax * 9 * 8 + (size_t)4 * 8 * STAN_NUM_XS * 8 +
+                           (size_t)4 * 8 * 8 * STAN_NUM_GS * 8 + (size_t)2 * STAN_NUM_ROWS * A.wmax * 4;
+        if (lds > 64 * 1024)
+            HIPCHK(ctx, hipFuncSetAttribute((const void *)k_numeric, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (K->nslices > 0)
+            hipLaunchKernelGGL(k_numeric, dim3((unsigned)K->nslices * (64 / STAN_NUM_ROWS)), dim3(256), lds, st, A);
+        if (wide) {   // the slices k_numeric skipped, listed from their widths (a handful: one launch of 64 waves per slice)
+            int32_t *d_wide;
+            STANCHK(tmp.alloc(&d_wide, (size_t)K->nslices));
+            HIPCHK(ctx, hipMemsetAsync(d_status + SS_COUNTER, 0, 8, st));
+            hipLaunchKernelGGL(k_list_above, dim3(nblk(K->nslices, 256)), dim3(256), 0, st, (int64_t)K->nslices, d_width, STAN_MAX_ROW_BLOCKS, d_wide,
+                               (unsigned long long *)(d_status + SS_COUNTER));
+            HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_COUNTER, d_status + SS_COUNTER, 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(ctx, hipStreamSynchronize(st));
+            const int64_t n_wide = ctx->h_status[SS_COUNTER];
+            A.wide_slices = d_wide;
+            if (n_wide * 64 >= (int64_t)1 << 31) { ctx->err = "assemble: too many wide slices for one launch"; return STAN_E_ARG; }
+            if (n_wide > 0) hipLaunchKernelGGL(k_numeric_wide, dim3((unsigned)(n_wide * 64)), dim3(64), 0, st, A);
+        }
+    }
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemsetAsync(d_status + SS_AUX, 0, 8, st));
+    hipLaunchKernelGGL(k_count_fixed, dim3(nblk(n_dof, 256) > 2048 ? 2048 : nblk(n_dof, 256)), dim3(256), 0, st, n_dof, d_red,
+                       (unsigned long long *)(d_status + SS_AUX));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_BAD_ELEM, d_status + SS_BAD_ELEM, 16, hipMemcpyDeviceToHost, st));
+    return STAN_OK;
+}
+
+// (also built for a 1-rank communicator, where every slice is interior, so that the two-stream path can be tested)
+int assembly_run::slice_lists() {
+    if (!(ctx->nranks > 1 || ctx->comm) || K->nslices <= 0) return STAN_OK;
+    const int64_t ns = K->nslices;
+    int32_t *d_fb, *d_fi; int64_t *d_sb, *d_si;
+    STANCHK(tmp.alloc(&d_fb, (size_t)ns + 1));
+    STANCHK(tmp.alloc(&d_fi, (size_t)ns + 1));
+    STANCHK(tmp.alloc(&d_sb, (size_t)ns + 2));
+    STANCHK(tmp.alloc(&d_si, (size_t)ns + 2));
+    hipLaunchKernelGGL(k_slice_class, dim3((unsigned)K->nslices), dim3(64), 0, st, nloc,
+                       K->d_rowlen, K->d_rowof, K->d_slot_ptr, K->d_cols, d_fb, d_fi);
+    STANCHK(stan_scan_total(ctx, d_fb, d_sb, ns, SS_H_COUNT_A));
+    STANCHK(stan_scan_total(ctx, d_fi, d_si, ns, SS_H_COUNT_B));
+    HIPCHK(ctx, hipStreamSynchronize(st));   // one wait for both counts
+    int64_t n_bnd, n_int;
+    STANCHK(stan_compact_collect(ctx, d_fb, d_sb, ns, SS_H_COUNT_A, &K->d_sl_bnd, &n_bnd));
+    STANCHK(stan_compact_collect(ctx, d_fi, d_si, ns, SS_H_COUNT_B, &K->d_sl_int, &n_int));
+    K->n_sl_bnd = (int32_t)n_bnd, K->n_sl_int = (int32_t)n_int;
+    return STAN_OK;
+}
+
+int assembly_run::halo_plan() {
+    if (ctx->nranks <= 1) return STAN_OK;
+    std::vector<int32_t> hg((size_t)K->nhalo);
+    HIPCHK(ctx, hipMemcpyAsync(hg.data(), K->d_halo_glob, hg.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    int32_t *d_flag; int64_t *d_rk;
+    STANCHK(tmp.alloc(&d_flag, (size_t)nloc + 1));
+    STANCHK(tmp.alloc(&d_rk, (size_t)nloc + 2));
+    std::vector<int32_t *> lists;
+    K->recv_off.push_back(0);
+    K->send_off.push_back(0);
+    for (int q = 0; q < ctx->nranks; q++) {
+        if (q == ctx->rank) continue;
+        const int64_t q0 = K->row_starts[q], q1 = K->row_starts[q + 1];
+        // halo columns owned by q: contiguous in the (ascending) halo list
+        int64_t lo = std::lower_bound(hg.begin(), hg.end(), (int32_t)q0) - hg.begin();
+        int64_t hi = std::lower_bound(hg.begin(), hg.end(), (int32_t)q1) - hg.begin();
+        if (q1 > 0x7fffffff) hi = (int64_t)hg.size();
+        if (hi == lo) continue;  // structural symmetry: no recv <=> no send
+        hipLaunchKernelGGL(k_row_rankflag, dim3(nblk(nloc, 256)), dim3(256), 0, st, nloc,
+                           K->d_rowlen, K->d_posof, K->d_slot_ptr, K->d_cols, K->d_halo_glob, q0, q1, d_flag);
+        int32_t *d_l; int64_t ns;
+        STANCHK(stan_compact_flags(ctx, d_flag, d_rk, nloc, SS_H_COUNT_A, &d_l, &ns, &tmp));
+        lists.push_back(d_l);
+        K->nbr.push_back(q);
+        K->recv_off.push_back(hi);
+        K->send_off.push_back(K->send_off.back() + ns);
+        // recv segment of q starts at lo: halo list is grouped by owner in rank order
+        if ((int64_t)K->recv_off[K->recv_off.size() - 2] != lo) {
+            ctx->err = "assemble: internal halo plan inconsistency";
+            return STAN_E_COMM;
+        }
+    }
+    const int64_t stot = K->send_off.back();
+    STANCHK(stan_dmalloc(ctx, &K->d_send_rows, (size_t)stot));
+    STANCHK(stan_dmalloc(ctx, &K->d_sendbuf, (size_t)stot * 3));
+    for (size_t i = 0; i < lists.size(); i++)
+        HIPCHK(ctx, hipMemcpyAsync(K->d_send_rows + K->send_off[i], lists[i], (size_t)(K->send_off[i + 1] - K->send_off[i]) * 4,
+                                   hipMemcpyDeviceToDevice, st));
+    return STAN_OK;
+}
 
 }  // namespace
 
@@ -943,13 +1202,7 @@ int stan_ke_batch_device(stan_ctx *ctx, int64_t n, const double *d_xyz8, double 
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_BAD_ELEM, ctx->d_status + SS_BAD_ELEM, 8, hipMemcpyDeviceToHost,
                                ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->h_status[SS_BAD_ELEM] != init) {
-        ctx->bad_elem = ctx->h_status[SS_BAD_ELEM];
-        ctx->err = "det J == 0 in element " + std::to_string(ctx->bad_elem) +
-                   " (MatrixST.Inverse would throw)";
-        return STAN_E_DETJ;
-    }
-    return STAN_OK;
+    return stan_detj_check(ctx, " (MatrixST.Inverse would throw)");
 }
 
 int stan_assemble_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
@@ -973,301 +1226,25 @@ int stan_assemble_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
         ev0 = events.make(); ev1 = events.make(); ev2 = events.make();
         hipEventRecord(ev0, st);
     }
-    tmp_free tmp;
-    tmp.ctx = ctx;
-    stan_matrix *K = new stan_matrix();
+    assembly_run A{ctx, n_nodes, d_xyz, d_node_dof, n_elem, d_conn, d_elem_mat, d_elem_type, n_mat, mat_E_nu, n_dof, d_red};
+    stan_matrix *K = A.K = new stan_matrix();
     K->ctx = ctx;
     ctx->matrices.push_back(K);
-    struct guard {
+    struct guard {   // (declared after A: a failed assembly frees the matrix first, then the temporaries)
         stan_matrix *k; bool ok = false;
         ~guard() { if (!ok) stan_hip_matrix_free(k); }
     } g{K};
-    const int64_t nb = n_dof / 3;
-    K->n_dof = n_dof;
-    K->nb_glob = nb;
-    K->n_elem_scanned = n_elem;
-    // contiguous block-row partition, cut on slice boundaries
-    K->row_starts.resize(ctx->nranks + 1);
-    for (int r = 0; r <= ctx->nranks; r++) K->row_starts[r] = stan_row_start(nb, ctx->nranks, r);
-    const int64_t r0 = K->r0 = K->row_starts[ctx->rank], r1 = K->r1 = K->row_starts[ctx->rank + 1];
-    const int64_t nloc = K->nloc = r1 - r0;
-    K->nslices = (int32_t)((nloc + 63) / 64);
-    const int64_t nrows_pad = (int64_t)K->nslices * 64;
-
-    int64_t *d_status = ctx->d_status;
-    HIPCHK(ctx, hipMemsetAsync(d_status, 0, 16 * 8, st));
-    {
-        long long init = 0x7fffffffffffffffLL;
-        HIPCHK(ctx, hipMemcpyAsync(d_status + SS_BAD_ELEM, &init, 8, hipMemcpyHostToDevice, st));
-    }
-
-    // materials -> (lambda, G)
-    std::vector<double> lamG(2 * (size_t)n_mat);
-    for (int m = 0; m < n_mat; m++) stan_lame(mat_E_nu[2 * m], mat_E_nu[2 * m + 1], &lamG[2 * m], &lamG[2 * m + 1]);
-    double *d_lamG; STANCHK(stan_dmalloc(ctx, &d_lamG, lamG.size())); tmp.own(d_lamG);
-    HIPCHK(ctx, hipMemcpyAsync(d_lamG, lamG.data(), lamG.size() * 8, hipMemcpyHostToDevice, st));
-
-    int32_t *d_perm; STANCHK(stan_dmalloc(ctx, &d_perm, (size_t)n_nodes)); tmp.own(d_perm);
-    STANCHK(stan_dmalloc(ctx, &K->d_fixmask, (size_t)nb));
-    STANCHK(stan_dmalloc(ctx, &K->d_red, (size_t)n_dof));
-    HIPCHK(ctx, hipMemsetAsync(K->d_fixmask, 0, (size_t)nb, st));
-    HIPCHK(ctx, hipMemcpyAsync(K->d_red, d_red, (size_t)n_dof * 4, hipMemcpyDeviceToDevice, st));
-    double *d_xrow; STANCHK(stan_dmalloc(ctx, &d_xrow, (size_t)nb * 3)); tmp.own(d_xrow);
-    int32_t *d_crow; STANCHK(stan_dmalloc(ctx, &d_crow, (size_t)(n_elem > 0 ? n_elem * 8 : 1))); tmp.own(d_crow);
-    hipLaunchKernelGGL(k_perm, dim3(nblk(n_nodes, 256)), dim3(256), 0, st, n_nodes, nb, d_node_dof,
-                       d_red, d_xyz, d_perm, K->d_fixmask, d_xrow, d_status);
-
-    // incidence lists of owned rows
-    int32_t *d_cnt; STANCHK(stan_dmalloc(ctx, &d_cnt, (size_t)nrows_pad + 1)); tmp.own(d_cnt);
-    int32_t *d_big_rows = nullptr;   // rows with more than STAN_MAX_INCIDENT incidences (listed before d_cnt becomes the fill cursor)
-    int64_t *d_ptr; STANCHK(stan_dmalloc(ctx, &d_ptr, (size_t)nrows_pad + 2)); tmp.own(d_ptr);
-    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, ((size_t)nrows_pad + 1) * 4, st));
-    if (n_elem > 0)
-        hipLaunchKernelGGL(k_count_incident, dim3(nblk(n_elem * 8, 256)), dim3(256), 0, st, n_elem,
-                           n_nodes, d_conn, d_perm, r0, r1, d_cnt, d_crow, d_status);
-    constexpr int BIG_LDS_INTS = 32768;   // 128 KB of the CU's 160 KB for k_symbolic_big's two sort buffers (up to 3640 incidences)
-    if (nrows_pad > 0)
-        hipLaunchKernelGGL(k_max_incident, dim3(nblk(nrows_pad, 256)), dim3(256), 0, st, nrows_pad, d_cnt, BIG_LDS_INTS, d_status);
-    STANCHK(stan_scan_exclusive(ctx, d_cnt, d_ptr, nrows_pad));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_ERRBITS, d_status + SS_ERRBITS, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_H_NINC, d_ptr + nrows_pad, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_MAXDEG, d_status + SS_MAXDEG, 24, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (ctx->h_status[SS_ERRBITS] & ERR_DOF_LAYOUT) {
-        ctx->err = "assemble: Node.DOF is not {3i,3i+1,3i+2} with 3i < n_dof (Node.cs:218-223)";
-        return STAN_E_DOF_LAYOUT;
-    }
-    if (ctx->h_status[SS_ERRBITS] & ERR_CONN_RANGE) {
-        ctx->err = "assemble: connectivity references a node index outside [0,n_nodes)";
-        return STAN_E_ARG;
-    }
-    const int64_t n_inc = ctx->h_status[SS_H_NINC];
-    const int64_t n_big = ctx->h_status[SS_NBIG];
-    if (n_big > 0) {
-        STANCHK(stan_dmalloc(ctx, &d_big_rows, (size_t)n_big)); tmp.own(d_big_rows);
-        HIPCHK(ctx, hipMemsetAsync(d_status + SS_COUNTER, 0, 8, st));
-        hipLaunchKernelGGL(k_list_above, dim3(nblk(nrows_pad, 256)), dim3(256), 0, st, nrows_pad, d_cnt, STAN_MAX_INCIDENT, d_big_rows,
-                           (unsigned long long *)(d_status + SS_COUNTER));
-    }
-    int32_t *d_list; STANCHK(stan_dmalloc(ctx, &d_list, (size_t)n_inc)); tmp.own(d_list);
-    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, ((size_t)nrows_pad + 1) * 4, st));
-    if (n_elem > 0)
-        hipLaunchKernelGGL(k_fill_incident, dim3(nblk(n_elem * 8, 256)), dim3(256), 0, st, n_elem,
-                           d_crow, r0, r1, d_ptr, d_cnt, d_list);
-
-    // symbolic count
-    STANCHK(stan_dmalloc(ctx, &K->d_rowlen, (size_t)nrows_pad));
-    int32_t *d_refflag = nullptr; int64_t *d_halo_rank = nullptr;
-    if (ctx->nranks > 1) {
-        STANCHK(stan_dmalloc(ctx, &d_refflag, (size_t)nb)); tmp.own(d_refflag);
-        STANCHK(stan_dmalloc(ctx, &d_halo_rank, (size_t)nb + 1)); tmp.own(d_halo_rank);
-        HIPCHK(ctx, hipMemsetAsync(d_refflag, 0, (size_t)nb * 4, st));
-    }
-    // distinct columns of row i land in d_ucols[8 * d_ptr[i] ...] (8 candidates per incidence)
-    int32_t *d_ucols; STANCHK(stan_dmalloc(ctx, &d_ucols, (size_t)(n_inc > 0 ? 8 * n_inc : 1))); tmp.own(d_ucols);
-    if (nrows_pad > 0)
-        hipLaunchKernelGGL(k_symbolic, dim3((unsigned)nrows_pad), dim3(64), 0, st, nloc, r0, r1, d_ptr,
-                           d_list, d_crow, K->d_rowlen, d_refflag, d_ucols, d_status);
-    if (n_big > 0) {   // high-valence nodes: the slow symbolic path, one workgroup per listed row
-        int64_t PD = 64, PC = 64;
-        while (PD < ctx->h_status[SS_MAXDEG]) PD <<= 1;
-        while (PC < 8 * ctx->h_status[SS_MAXDEG]) PC <<= 1;
-        if (PC >= (int64_t)1 << 30) { ctx->err = "assemble: a node with more than 2^26 incident elements"; return STAN_E_VALENCE; }
-        const int64_t lds_ints = PD + PC < BIG_LDS_INTS ? PD + PC : BIG_LDS_INTS;
-        int32_t *d_scratch = nullptr;
-        if (ctx->h_status[SS_NGIANT] > 0) {
-            STANCHK(stan_dmalloc(ctx, &d_scratch, (size_t)(ctx->h_status[SS_NGIANT] * (PD + PC))));
-            tmp.own(d_scratch);
-        }
-        HIPCHK(ctx, hipMemsetAsync(d_status + SS_COUNTER, 0, 8, st));   // scratch tickets
-        if (lds_ints * 4 > 64 * 1024)
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)k_symbolic_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_ints * 4)));
-        hipLaunchKernelGGL(k_symbolic_big, dim3((unsigned)n_big), dim3(256), (size_t)lds_ints * 4, st, d_big_rows, r0, r1, d_ptr, d_list,
-                           d_crow, K->d_rowlen, d_refflag, d_ucols, (int)lds_ints, d_scratch, PD + PC,
-                           (unsigned long long *)(d_status + SS_COUNTER));
-    }
-    // SELL-C-sigma: positions of the rows inside the sliced layout
-    K->sigma = ctx->sell_sigma < 1 ? 1 : ctx->sell_sigma > 32 ? 32 : ctx->sell_sigma;
-    STANCHK(stan_dmalloc(ctx, &K->d_rowof, (size_t)(nrows_pad > 0 ? nrows_pad : 1)));
-    STANCHK(stan_dmalloc(ctx, &K->d_posof, (size_t)(nrows_pad > 0 ? nrows_pad : 1)));
-    if (nrows_pad > 0)
-        hipLaunchKernelGGL(k_window_sort, dim3(nblk(K->nslices, K->sigma)), dim3(64), 0, st, nrows_pad, K->sigma,
-                           K->d_rowlen, K->d_rowof, K->d_posof);
-    // halo numbering
-    K->nhalo = 0;
-    if (ctx->nranks > 1) {
-        STANCHK(stan_scan_exclusive(ctx, d_refflag, d_halo_rank, nb));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_H_NHALO, d_halo_rank + nb, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        K->nhalo = ctx->h_status[SS_H_NHALO];
-        STANCHK(stan_dmalloc(ctx, &K->d_halo_glob, (size_t)K->nhalo));
-        hipLaunchKernelGGL(k_compact_flags, dim3(nblk(nb, 256)), dim3(256), 0, st, d_refflag,
-                           d_halo_rank, K->d_halo_glob, nb);
-    }
-    // slice widths -> slot pointers
-    int32_t *d_width; STANCHK(stan_dmalloc(ctx, &d_width, (size_t)K->nslices + 1)); tmp.own(d_width);
-    int64_t *d_sp64; STANCHK(stan_dmalloc(ctx, &d_sp64, (size_t)K->nslices + 2)); tmp.own(d_sp64);
-    HIPCHK(ctx, hipMemsetAsync(d_status + SS_WIDTH_SUM, 0, 16, st));
-    if (K->nslices > 0)
-        hipLaunchKernelGGL(k_slice_width, dim3(nblk(K->nslices, 4)), dim3(256), 0, st, K->nslices, K->d_rowlen,
-                           K->d_rowof, d_width, (unsigned long long *)(d_status + SS_WIDTH_SUM), (int32_t *)(d_status + SS_WIDTH_MAX));
-    STANCHK(stan_scan_exclusive(ctx, d_width, d_sp64, K->nslices));
-    STANCHK(stan_dmalloc(ctx, &K->d_slot_ptr, (size_t)K->nslices + 1));
-    hipLaunchKernelGGL(k_i64_to_i32, dim3(nblk(K->nslices + 1, 256)), dim3(256), 0, st, d_sp64,
-                       K->d_slot_ptr, (int64_t)K->nslices + 1);
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_ERRBITS, d_status + SS_ERRBITS, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_H_NSLOTS, d_sp64 + K->nslices, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_H_NBLOCKS, d_status + SS_WIDTH_SUM, 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    K->nslots = ctx->h_status[SS_H_NSLOTS];
-    K->nblocks = ctx->h_status[SS_H_NBLOCKS];
-    K->max_row_blocks = (int32_t)(ctx->h_status[SS_H_MAXROW] & 0xffffffff);
-    if (K->nslots * 64 >= (int64_t)1 << 31) {
-        // cols index fits, but keep slot arithmetic in int32 honest
-        ctx->err = "assemble: more than 2^31 ELL entries on one rank";
-        return STAN_E_ARG;
-    }
-    STANCHK(stan_dmalloc(ctx, &K->d_cols, (size_t)K->nslots * 64));
-    if (K->nslices > 0) {
-        int32_t wmax = K->max_row_blocks > 0 ? K->max_row_blocks : 1;
-        if (wmax > STAN_MAX_ROW_BLOCKS) wmax = STAN_MAX_ROW_BLOCKS;         // wider slices pass through the tile in chunks
-        const size_t lds = (size_t)4 * 64 * (wmax | 1) * sizeof(int32_t);   // <= 4 * 64 * 97 * 4 = 99 KB
-        if (lds > 64 * 1024)
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)k_fill_cols, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_fill_cols, dim3(nblk(K->nslices, 4)), dim3(256), lds, st, K->nslices, nloc, r0, r1,
-                           K->d_slot_ptr, K->d_rowof, K->d_rowlen, d_ptr, d_ucols, (const int64_t *)d_halo_rank,
-                           K->d_cols, wmax);
-    }
-    // (after the columns are in place: an allocation by trial times the SpMV itself, which needs the columns)
-    STANCHK(stan_dmalloc_streamed(ctx, (void **)&K->d_vals, (size_t)K->nslots * 9 * 64 * 8,
-                                  [&](const void *q, float *ms, bool self) {
-                                      return stan_spmv_probe(ctx, K, q, (size_t)K->nslots * 9 * 64 * 8, STAN_PREC_FP64, ms, self);
-                                  }));
+    STANCHK(A.partition());
+    STANCHK(A.incidence());
+    STANCHK(A.symbolic());
+    STANCHK(A.layout());
     if (ctx->profiling) hipEventRecord(ev1, st);
-
-    // numeric
-    if (ctx->assembly_mode == 1) {
-        if (ctx->nranks > 1) { ctx->err = "assembly mode 1 (colour scatter) is single-rank only"; return STAN_E_UNSUPPORTED; }
-        STANCHK(stan_assemble_colour_scatter(ctx, K, n_elem, d_conn, d_perm, d_xyz, d_elem_mat, d_elem_type,
-                                             d_lamG, d_ptr, d_list, (long long *)(d_status + SS_BAD_ELEM)));
-    } else {
-        ctx->prof_colours = 0;
-        numeric_args A;
-        A.nloc = nloc; A.r0 = r0; A.r1 = r1; A.nhalo = K->nhalo;
-        A.ptr = d_ptr; A.list = d_list; A.crow = d_crow; A.xrow = d_xrow;
-        A.elem_mat = d_elem_mat; A.elem_type = d_elem_type; A.mat_lamG = d_lamG;
-        A.fixmask = K->d_fixmask; A.halo_glob = K->d_halo_glob; A.halo_rank = d_halo_rank;
-        A.rowlen = K->d_rowlen; A.rowof = K->d_rowof; A.slot_ptr = K->d_slot_ptr; A.cols = K->d_cols; A.vals = K->d_vals;
-        A.bad_elem = (long long *)(d_status + SS_BAD_ELEM);
-        A.wide_slices = nullptr;
-        A.wmax = K->max_row_blocks > 0 ? K->max_row_blocks : 1;
-        const bool wide = A.wmax > STAN_MAX_ROW_BLOCKS;   // some slice holds a high-valence row: it goes to k_numeric_wide
-        if (wide) A.wmax = STAN_MAX_ROW_BLOCKS;
-        const size_t lds = (size_t)STAN_NUM_ROWS * A.wmax * 9 * 8 + (size_t)4 * 8 * STAN_NUM_XS * 8 +
-                           (size_t)4 * 8 * 8 * STAN_NUM_GS * 8 + (size_t)2 * STAN_NUM_ROWS * A.wmax * 4;
-        size_t lds_launch = lds;
-        if (lds_launch > 64 * 1024)
-            HIPCHK(ctx, hipFuncSetAttribute((const void *)k_numeric,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_launch));
-        if (K->nslices > 0)
-            hipLaunchKernelGGL(k_numeric, dim3((unsigned)K->nslices * (64 / STAN_NUM_ROWS)), dim3(256), lds_launch, st, A);
-        if (wide) {   // the slices k_numeric skipped, listed from their widths (a handful: one launch of 64 waves per slice)
-            int32_t *d_wide; STANCHK(stan_dmalloc(ctx, &d_wide, (size_t)K->nslices)); tmp.own(d_wide);
-            HIPCHK(ctx, hipMemsetAsync(d_status + SS_COUNTER, 0, 8, st));
-            hipLaunchKernelGGL(k_list_above, dim3(nblk(K->nslices, 256)), dim3(256), 0, st, (int64_t)K->nslices, d_width, STAN_MAX_ROW_BLOCKS, d_wide,
-                               (unsigned long long *)(d_status + SS_COUNTER));
-            HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_COUNTER, d_status + SS_COUNTER, 8, hipMemcpyDeviceToHost, st));
-            HIPCHK(ctx, hipStreamSynchronize(st));
-            const int64_t n_wide = ctx->h_status[SS_COUNTER];
-            A.wide_slices = d_wide;
-            if (n_wide * 64 >= (int64_t)1 << 31) { ctx->err = "assemble: too many wide slices for one launch"; return STAN_E_ARG; }
-            if (n_wide > 0) hipLaunchKernelGGL(k_numeric_wide, dim3((unsigned)(n_wide * 64)), dim3(64), 0, st, A);
-        }
-    }
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemsetAsync(d_status + SS_AUX, 0, 8, st));
-    hipLaunchKernelGGL(k_count_fixed, dim3(nblk(n_dof, 256) > 2048 ? 2048 : nblk(n_dof, 256)), dim3(256), 0, st, n_dof, d_red,
-                       (unsigned long long *)(d_status + SS_AUX));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_BAD_ELEM, d_status + SS_BAD_ELEM, 16, hipMemcpyDeviceToHost, st));
-
-    // interior / boundary slice lists for the overlapped SpMV (also built for a 1-rank
-    // communicator, where every slice is interior, so that the two-stream path can be tested)
-    if ((ctx->nranks > 1 || ctx->comm) && K->nslices > 0) {
-        int32_t *d_fb, *d_fi; int64_t *d_sb, *d_si;
-        STANCHK(stan_dmalloc(ctx, &d_fb, (size_t)K->nslices + 1)); tmp.own(d_fb);
-        STANCHK(stan_dmalloc(ctx, &d_fi, (size_t)K->nslices + 1)); tmp.own(d_fi);
-        STANCHK(stan_dmalloc(ctx, &d_sb, (size_t)K->nslices + 2)); tmp.own(d_sb);
-        STANCHK(stan_dmalloc(ctx, &d_si, (size_t)K->nslices + 2)); tmp.own(d_si);
-        hipLaunchKernelGGL(k_slice_class, dim3((unsigned)K->nslices), dim3(64), 0, st, nloc,
-                           K->d_rowlen, K->d_rowof, K->d_slot_ptr, K->d_cols, d_fb, d_fi);
-        STANCHK(stan_scan_exclusive(ctx, d_fb, d_sb, K->nslices));
-        STANCHK(stan_scan_exclusive(ctx, d_fi, d_si, K->nslices));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_H_COUNT_A, d_sb + K->nslices, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_H_COUNT_B, d_si + K->nslices, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        K->n_sl_bnd = (int32_t)ctx->h_status[SS_H_COUNT_A];
-        K->n_sl_int = (int32_t)ctx->h_status[SS_H_COUNT_B];
-        STANCHK(stan_dmalloc(ctx, &K->d_sl_bnd, (size_t)K->n_sl_bnd));
-        STANCHK(stan_dmalloc(ctx, &K->d_sl_int, (size_t)K->n_sl_int));
-        hipLaunchKernelGGL(k_compact_flags, dim3(nblk(K->nslices, 256)), dim3(256), 0, st, d_fb, d_sb,
-                           K->d_sl_bnd, (int64_t)K->nslices);
-        hipLaunchKernelGGL(k_compact_flags, dim3(nblk(K->nslices, 256)), dim3(256), 0, st, d_fi, d_si,
-                           K->d_sl_int, (int64_t)K->nslices);
-    }
-    // halo exchange plan
-    if (ctx->nranks > 1) {
-        std::vector<int32_t> hg((size_t)K->nhalo);
-        HIPCHK(ctx, hipMemcpyAsync(hg.data(), K->d_halo_glob, hg.size() * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        int32_t *d_flag; STANCHK(stan_dmalloc(ctx, &d_flag, (size_t)nloc + 1)); tmp.own(d_flag);
-        int64_t *d_rk; STANCHK(stan_dmalloc(ctx, &d_rk, (size_t)nloc + 2)); tmp.own(d_rk);
-        std::vector<int32_t *> lists;
-        std::vector<int64_t> counts;
-        K->recv_off.push_back(0);
-        K->send_off.push_back(0);
-        for (int q = 0; q < ctx->nranks; q++) {
-            if (q == ctx->rank) continue;
-            const int64_t q0 = K->row_starts[q], q1 = K->row_starts[q + 1];
-            // halo columns owned by q: contiguous in the (ascending) halo list
-            int64_t lo = std::lower_bound(hg.begin(), hg.end(), (int32_t)q0) - hg.begin();
-            int64_t hi = std::lower_bound(hg.begin(), hg.end(), (int32_t)q1) - hg.begin();
-            if (q1 > 0x7fffffff) hi = (int64_t)hg.size();
-            if (hi == lo) continue;  // structural symmetry: no recv <=> no send
-            hipLaunchKernelGGL(k_row_rankflag, dim3(nblk(nloc, 256)), dim3(256), 0, st, nloc,
-                               K->d_rowlen, K->d_posof, K->d_slot_ptr, K->d_cols, K->d_halo_glob, q0, q1, d_flag);
-            STANCHK(stan_scan_exclusive(ctx, d_flag, d_rk, nloc));
-            HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_H_COUNT_A, d_rk + nloc, 8, hipMemcpyDeviceToHost, st));
-            HIPCHK(ctx, hipStreamSynchronize(st));
-            const int64_t ns = ctx->h_status[SS_H_COUNT_A];
-            int32_t *d_l; STANCHK(stan_dmalloc(ctx, &d_l, (size_t)ns)); tmp.own(d_l);
-            hipLaunchKernelGGL(k_compact_flags, dim3(nblk(nloc, 256)), dim3(256), 0, st, d_flag, d_rk,
-                               d_l, nloc);
-            lists.push_back(d_l);
-            counts.push_back(ns);
-            K->nbr.push_back(q);
-            K->recv_off.push_back(hi);
-            K->send_off.push_back(K->send_off.back() + ns);
-            // recv segment of q starts at lo: halo list is grouped by owner in rank order
-            if ((int64_t)K->recv_off[K->recv_off.size() - 2] != lo) {
-                ctx->err = "assemble: internal halo plan inconsistency";
-                return STAN_E_COMM;
-            }
-        }
-        const int64_t stot = K->send_off.back();
-        STANCHK(stan_dmalloc(ctx, &K->d_send_rows, (size_t)stot));
-        STANCHK(stan_dmalloc(ctx, &K->d_sendbuf, (size_t)stot * 3));
-        for (size_t i = 0; i < lists.size(); i++)
-            HIPCHK(ctx, hipMemcpyAsync(K->d_send_rows + K->send_off[i], lists[i], (size_t)counts[i] * 4,
-                                       hipMemcpyDeviceToDevice, st));
-    }
+    STANCHK(A.numeric());
+    STANCHK(A.slice_lists());
+    STANCHK(A.halo_plan());
     if (ctx->profiling) hipEventRecord(ev2, st);
     HIPCHK(ctx, hipStreamSynchronize(st));
-    if (ctx->h_status[SS_BAD_ELEM] != 0x7fffffffffffffffLL) {
-        ctx->bad_elem = ctx->h_status[SS_BAD_ELEM];
-        ctx->err = "det J == 0 in element " + std::to_string(ctx->bad_elem) +
-                   " (MatrixST.Inverse would throw, MatrixST.cs:315-318)";
-        return STAN_E_DETJ;
-    }
+    STANCHK(stan_detj_check(ctx, " (MatrixST.Inverse would throw, MatrixST.cs:315-318)"));
     K->n_red = n_dof - ctx->h_status[SS_AUX];
     if (ctx->profiling) {
         float a = 0, b = 0;

@@ -186,8 +186,6 @@ k_apply_bc(int32_t nslices, int64_t nloc, const int32_t *slot_ptr, const int32_t
     }
 }
 
-inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 }  // namespace
 
 int stan_assemble_colour_scatter(stan_ctx *ctx, stan_matrix *K, int64_t n_elem, const int32_t *d_conn,
@@ -200,12 +198,10 @@ int stan_assemble_colour_scatter(stan_ctx *ctx, stan_matrix *K, int64_t n_elem, 
     if (n_elem > 0) {
         int32_t *d_col[2], *d_tent, *d_cnt = nullptr, *d_order, *d_maxc;
         unsigned long long *d_rem;
-        std::vector<void *> owned;
-        auto A = [&](auto **p, size_t n) { int rc = stan_dmalloc(ctx, p, n); if (!rc) owned.push_back((void *)*p); return rc; };
-        struct F { stan_ctx *c; std::vector<void *> &v; ~F() { for (void *q : v) stan_dfree(c, q); } } fr{ctx, owned};
-        STANCHK(A(&d_col[0], (size_t)n_elem)); STANCHK(A(&d_col[1], (size_t)n_elem));
-        STANCHK(A(&d_tent, (size_t)n_elem)); STANCHK(A(&d_maxc, 2)); STANCHK(A(&d_order, (size_t)n_elem));
-        STANCHK(A(&d_rem, 1));
+        dev_scope tmp(ctx);
+        STANCHK(tmp.alloc(&d_col[0], (size_t)n_elem)); STANCHK(tmp.alloc(&d_col[1], (size_t)n_elem));
+        STANCHK(tmp.alloc(&d_tent, (size_t)n_elem)); STANCHK(tmp.alloc(&d_maxc, 2)); STANCHK(tmp.alloc(&d_order, (size_t)n_elem));
+        STANCHK(tmp.alloc(&d_rem, 1));
         HIPCHK(ctx, hipMemsetAsync(d_col[0], 0xff, (size_t)n_elem * 4, st));  // -1 = uncoloured
         int cur = 0;
         for (int round = 0; round < 4096; round++) {
@@ -227,7 +223,7 @@ int stan_assemble_colour_scatter(stan_ctx *ctx, stan_matrix *K, int64_t n_elem, 
         HIPCHK(ctx, hipMemcpyAsync(&maxc, d_maxc, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
         const int32_t nc = maxc + 1;
-        STANCHK(A(&d_cnt, (size_t)3 * nc));
+        STANCHK(tmp.alloc(&d_cnt, (size_t)3 * nc));
         HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, (size_t)3 * nc * 4, st));
         hipLaunchKernelGGL(k_col_count, dim3(nblk(n_elem, 256)), dim3(256), 0, st, n_elem, d_col[cur], d_cnt);
         std::vector<int32_t> cnt((size_t)nc), off((size_t)nc);

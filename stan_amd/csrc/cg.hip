@@ -195,26 +195,10 @@ __device__ __forceinline__ bool stopped(const int64_t *st, int64_t k) {
 
 #include "cg_vector_kernels.inc"   // the vector kernels of the CG loop: k_step, k_refresh, k_update, k_vec_sr (single-reduction form), result / expand / compress
 
-inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
 inline unsigned vec_grid(int64_t n) {
     int64_t b = (n + VEC_T - 1) / VEC_T;
     if (b < 1) b = 1;
     return (unsigned)(b > VEC_BLOCKS ? VEC_BLOCKS : b);
-}
-
-struct dev_bufs {
-    stan_ctx *ctx = nullptr;
-    std::vector<void *> p;
-    ~dev_bufs() {
-        for (void *q : p) stan_dfree(ctx, q);
-    }
-};
-template <typename T>
-int alloc(stan_ctx *ctx, dev_bufs &b, T **p, size_t n) {
-    b.ctx = ctx;
-    int rc = stan_dmalloc(ctx, p, n);
-    if (rc == STAN_OK) b.p.push_back((void *)*p);
-    return rc;
 }
 
 // k_spmv_small instead of k_spmv: decided by the GLOBAL number of block rows, so that a shard and the
@@ -253,8 +237,8 @@ inline int64_t gather_len(const stan_matrix *K) {
     return 3 * (npad > K->nloc + K->nhalo ? npad : K->nloc + K->nhalo);
 }
 // status words for kernels launched outside a solve: never stopped
-int alloc_never_stopped(stan_ctx *ctx, dev_bufs &b, int64_t **stt, hipStream_t s) {
-    STANCHK(alloc(ctx, b, stt, (size_t)T_NSTAT));
+int alloc_never_stopped(stan_ctx *ctx, dev_scope &b, int64_t **stt, hipStream_t s) {
+    STANCHK(b.alloc(stt, (size_t)T_NSTAT));
     const int64_t init[T_NSTAT] = {0x7fffffffffffffffLL, 0x7fffffffffffffffLL, 0, 0, 0, 0, 0, 0};
     HIPCHK(ctx, hipMemcpyAsync(*stt, init, sizeof(init), hipMemcpyHostToDevice, s));
     return STAN_OK;
@@ -568,27 +552,22 @@ int stan_pack_columns(stan_ctx *ctx, int32_t nslices, int64_t nslots, const int3
                       uint32_t **packed_out, int32_t **base_out, int32_t **pair_ptr_out, uint8_t **ok_out, int64_t *slots_packed,
                       int64_t nloc, const int32_t *d_rowof, const int32_t *d_rowlen, int64_t *slots_packed2) {
     hipStream_t st_ = ctx->stream;
-    dev_bufs bufs;
+    dev_scope bufs(ctx);
     int32_t *cnt; int64_t *ptr64;
-    STANCHK(alloc(ctx, bufs, &cnt, (size_t)nslices + 1));
-    STANCHK(alloc(ctx, bufs, &ptr64, (size_t)nslices + 2));
+    STANCHK(bufs.alloc(&cnt, (size_t)nslices + 1));
+    STANCHK(bufs.alloc(&ptr64, (size_t)nslices + 2));
     hipLaunchKernelGGL(k_pair_counts, dim3(nblk(nslices, 256)), dim3(256), 0, st_, nslices, d_slot_ptr, cnt);
-    STANCHK(stan_scan_exclusive(ctx, cnt, ptr64, nslices));
-    std::vector<int64_t> h((size_t)nslices + 1);
-    HIPCHK(ctx, hipMemcpyAsync(h.data(), ptr64, h.size() * 8, hipMemcpyDeviceToHost, st_));
+    STANCHK(stan_scan_total(ctx, cnt, ptr64, nslices, SS_H_NSLOTS));
     HIPCHK(ctx, hipStreamSynchronize(st_));
-    const int64_t npairs = h[(size_t)nslices];
+    const int64_t npairs = ctx->h_status[SS_H_NSLOTS];
     if (npairs >= ((int64_t)1 << 31)) return STAN_OK;   // pair index is int32: keep the plain columns
-    std::vector<int32_t> h32(h.size());
-    for (size_t i = 0; i < h.size(); i++) h32[i] = (int32_t)h[i];
-    STANCHK(stan_dmalloc(ctx, pair_ptr_out, h32.size()));
+    STANCHK(stan_slot_ptr_narrow(ctx, ptr64, nslices, pair_ptr_out));
     // one allocation: [n] base, [n] base2, [nslices] cmask (64-bit words), n = max(nslots, 1): make_colstream
     const size_t nb_ = (size_t)(nslots > 0 ? nslots : 1);
     STANCHK(stan_dmalloc(ctx, base_out, 2 * nb_ + 2 * (size_t)nslices + 2));
     STANCHK(stan_dmalloc(ctx, ok_out, (size_t)nslices));
     uint32_t *packed;
     STANCHK(stan_dmalloc(ctx, &packed, (size_t)(npairs > 0 ? npairs : 1) * 64));
-    HIPCHK(ctx, hipMemcpyAsync(*pair_ptr_out, h32.data(), h32.size() * 4, hipMemcpyHostToDevice, st_));
     int32_t *b2_ = *base_out + nb_;
     unsigned long long *cm_ = (unsigned long long *)(*base_out + 2 * nb_);
     if (((uintptr_t)cm_ & 7) != 0) cm_ = (unsigned long long *)((uintptr_t)cm_ + 4);   // (never: 2 n ints from an aligned block)
@@ -599,7 +578,7 @@ int stan_pack_columns(stan_ctx *ctx, int32_t nslices, int64_t nslots, const int3
     hipLaunchKernelGGL(k_count_ok, dim3(nblk(nslices, 256)), dim3(256), 0, st_, nslices, *ok_out, d_slot_ptr, d_cnt);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_COUNTER, d_cnt, 16, hipMemcpyDeviceToHost, st_));
-    HIPCHK(ctx, hipStreamSynchronize(st_));   // h32 must outlive the copy
+    HIPCHK(ctx, hipStreamSynchronize(st_));
     *slots_packed = ctx->h_status[SS_COUNTER];
     if (slots_packed2) *slots_packed2 = ctx->h_status[SS_COUNTER + 1];
     *packed_out = packed;
@@ -675,7 +654,7 @@ struct cg_run {
     bool reduced = false;             // the caller asked for a reduced-precision stream: fp64 check + refinement (every rank alike)
     int refine = 0;                   // STAN_OPT_CG_REFINE, reduced-precision modes only
     int64_t n3 = 0, npad = 0, ng = 0, dof0 = 0;
-    dev_bufs bufs;
+    dev_scope bufs{ctx};
     double *xb[2] = {nullptr, nullptr}, *p = nullptr, *r = nullptr, *v = nullptr, *w = nullptr, *bh = nullptr;
     double *partial = nullptr, *sc = nullptr, *sv = nullptr;
     double *xacc = nullptr, *b0 = nullptr;   // refinement: the sum of the passes' iterates, the original b^ (allocated when a second pass starts)
@@ -871,10 +850,10 @@ int cg_run::setup() {
     if (sr) sv = ctx->ws.sv;
     const unsigned spmv_blocks = stan_small_system(ctx, K) ? (unsigned)K->nslices : nblk(K->nslices, stan_pair_kernel(ctx) ? 2 : 4);
     const size_t npart = 2 * (size_t)(spmv_blocks > VEC_BLOCKS ? spmv_blocks : VEC_BLOCKS) + 16;
-    STANCHK(alloc(ctx, bufs, &partial, npart));
-    STANCHK(alloc(ctx, bufs, &sc, (size_t)S_NSCAL));
-    STANCHK(alloc(ctx, bufs, &stt, (size_t)T_NSTAT));
-    STANCHK(alloc(ctx, bufs, &tick, (size_t)(2 * FOLD_WORDS)));   // two ticket-counter sets
+    STANCHK(bufs.alloc(&partial, npart));
+    STANCHK(bufs.alloc(&sc, (size_t)S_NSCAL));
+    STANCHK(bufs.alloc(&stt, (size_t)T_NSTAT));
+    STANCHK(bufs.alloc(&tick, (size_t)(2 * FOLD_WORDS)));   // two ticket-counter sets
     HIPCHK(ctx, hipMemsetAsync(sc, 0, S_NSCAL * 8, st_));
     HIPCHK(ctx, hipMemsetAsync(tick, 0, 2 * FOLD_WORDS * 8, st_));
     HIPCHK(ctx, hipMemsetAsync(xb[0], 0, (size_t)ng * 8, st_));
@@ -1137,7 +1116,7 @@ int cg_run::finish(const double *x_result, int type, int64_t its, double rel_rec
                            x_result, d_U);
     } else {
         double *full;
-        STANCHK(alloc(ctx, bufs, &full, (size_t)K->n_dof));
+        STANCHK(bufs.alloc(&full, (size_t)K->n_dof));
         hipLaunchKernelGGL(k_result_full, dim3(vg), dim3(VEC_T), 0, st_, n3, K->d_scale, x_result,
                            full + dof0);
         STANCHK(stan_comm_allgather_rows(ctx, K, full));
@@ -1264,8 +1243,8 @@ int stan_cg_device(stan_ctx *ctx, stan_matrix *K, const double *d_F, double eps_
             break;
         }
         if (passes == 1) {
-            STANCHK(alloc(ctx, R.bufs, &R.xacc, (size_t)(R.n3 > 0 ? R.n3 : 1)));
-            STANCHK(alloc(ctx, R.bufs, &R.b0, (size_t)(R.n3 > 0 ? R.n3 : 1)));
+            STANCHK(R.bufs.alloc(&R.xacc, (size_t)(R.n3 > 0 ? R.n3 : 1)));
+            STANCHK(R.bufs.alloc(&R.b0, (size_t)(R.n3 > 0 ? R.n3 : 1)));
             HIPCHK(ctx, hipMemcpyAsync(R.xacc, R.xfin, (size_t)R.n3 * 8, hipMemcpyDeviceToDevice, R.st_));
             HIPCHK(ctx, hipMemcpyAsync(R.b0, R.bh, (size_t)R.n3 * 8, hipMemcpyDeviceToDevice, R.st_));
         }
@@ -1282,10 +1261,10 @@ int stan_spmv_reduced(stan_ctx *ctx, stan_matrix *K, const double *d_x, double *
     if (ctx->nranks != 1) { ctx->err = "spmv: single-rank contexts only"; return STAN_E_UNSUPPORTED; }
     hipStream_t st_ = ctx->stream;
     const int64_t n3 = 3 * K->nloc, npad3 = 3 * (int64_t)K->nslices * 64;
-    dev_bufs bufs;
+    dev_scope bufs(ctx);
     double *xf, *yf; int64_t *stt;
-    STANCHK(alloc(ctx, bufs, &xf, (size_t)npad3));
-    STANCHK(alloc(ctx, bufs, &yf, (size_t)npad3));
+    STANCHK(bufs.alloc(&xf, (size_t)npad3));
+    STANCHK(bufs.alloc(&yf, (size_t)npad3));
     STANCHK(alloc_never_stopped(ctx, bufs, &stt, st_));
     HIPCHK(ctx, hipMemsetAsync(xf, 0, (size_t)npad3 * 8, st_));
     const double *sdiv = K->scaled ? K->d_scale : nullptr;
@@ -1305,9 +1284,9 @@ int stan_matrix_diagonal(stan_ctx *ctx, stan_matrix *K, double *d_diag) {
     if (ctx->nranks != 1) { ctx->err = "matrix_diagonal: single-rank contexts only"; return STAN_E_UNSUPPORTED; }
     hipStream_t st_ = ctx->stream;
     const int64_t n3 = 3 * K->nloc;
-    dev_bufs bufs;
+    dev_scope bufs(ctx);
     double *full;
-    STANCHK(alloc(ctx, bufs, &full, (size_t)(n3 > 0 ? n3 : 1)));
+    STANCHK(bufs.alloc(&full, (size_t)(n3 > 0 ? n3 : 1)));
     if (K->nloc > 0)
         hipLaunchKernelGGL(k_diag_get, dim3(nblk(K->nloc, 256)), dim3(256), 0, st_, K->nloc, K->d_rowlen, K->d_posof,
                            K->d_slot_ptr, K->d_cols, K->d_vals, K->scaled ? K->d_scale : (const double *)nullptr, full);
@@ -1319,7 +1298,7 @@ int stan_matrix_diagonal(stan_ctx *ctx, stan_matrix *K, double *d_diag) {
 
 // y_owned = A_local x_local, x_local = [owned rows | halo columns] (plan checks; any rank)
 int stan_spmv_local(stan_ctx *ctx, stan_matrix *K, const double *d_x, double *d_y) {
-    dev_bufs bufs;
+    dev_scope bufs(ctx);
     int64_t *stt;
     STANCHK(alloc_never_stopped(ctx, bufs, &stt, ctx->stream));
     if (K->d_sl_bnd) {  // sharded: interior + boundary lists must cover every slice exactly once
@@ -1337,12 +1316,8 @@ int stan_spmv_local(stan_ctx *ctx, stan_matrix *K, const double *d_x, double *d_
 // K's own of that precision), on the CG's own gather vector and product buffer -- the pair (value block, vector blocks)
 // that is timed is the pair the solve will run on -- or, self_block given, on vectors carved out of the front of that
 // block (a.x stays nullptr when they do not fit).  The gather vector is filled with ones.
-struct timed_product {
-    dev_bufs bufs;
-    product_args a{};
-};
 static int timed_product_setup(stan_ctx *ctx, stan_matrix *K, int32_t precision, const void *vals, void *self_block,
-                               size_t self_bytes, timed_product &t) {
+                               size_t self_bytes, dev_scope &bufs, product_args &a) {
     hipStream_t st_ = ctx->stream;
     const int64_t ng = gather_len(K), ngpad = (ng + 511) & ~(int64_t)511;
     STANCHK(stan_cg_workspace(ctx, K));
@@ -1353,10 +1328,10 @@ static int timed_product_setup(stan_ctx *ctx, stan_matrix *K, int32_t precision,
         x = (double *)self_block;
         y = x + ngpad;
     }
-    STANCHK(alloc(ctx, t.bufs, &partial, 2 * (size_t)K->nslices + 2));   // k_spmv_small leaves one partial per slice
-    STANCHK(alloc_never_stopped(ctx, t.bufs, &stt, st_));
+    STANCHK(bufs.alloc(&partial, 2 * (size_t)K->nslices + 2));   // k_spmv_small leaves one partial per slice
+    STANCHK(alloc_never_stopped(ctx, bufs, &stt, st_));
     hipLaunchKernelGGL(k_fill, dim3(vec_grid(ng)), dim3(VEC_T), 0, st_, x, ng, 1.0);
-    t.a = product_args{x, y, nullptr, nullptr, 1, partial, stt, 1, precision, vals, false};
+    a = product_args{x, y, nullptr, nullptr, 1, partial, stt, 1, precision, vals, false};
     return STAN_OK;
 }
 
@@ -1369,13 +1344,14 @@ int stan_spmv_bench_device(stan_ctx *ctx, stan_matrix *K, int32_t precision_mode
         STANCHK(stan_matrix_make_fx48(ctx, K));
         if (!K->d_vals48) { ctx->err = "spmv_bench: matrix not representable in FIXED48"; return STAN_E_UNSUPPORTED; }
     }
-    timed_product t;
-    STANCHK(timed_product_setup(ctx, K, precision_mode, nullptr, nullptr, 0, t));
+    dev_scope bufs(ctx);
+    product_args pa{};
+    STANCHK(timed_product_setup(ctx, K, precision_mode, nullptr, nullptr, 0, bufs, pa));
     event_bag events;
     hipEvent_t a = events.make(), b = events.make();
-    for (int i = 0; i < 3; i++) launch_product(ctx, K, t.a);
+    for (int i = 0; i < 3; i++) launch_product(ctx, K, pa);
     hipEventRecord(a, st_);
-    for (int i = 0; i < reps; i++) launch_product(ctx, K, t.a);
+    for (int i = 0; i < reps; i++) launch_product(ctx, K, pa);
     hipEventRecord(b, st_);
     HIPCHK(ctx, hipEventSynchronize(b));
     float ms = 0;
@@ -1393,9 +1369,9 @@ int stan_stream_bench_device(stan_ctx *ctx, stan_matrix *K, int32_t reps, double
     *bytes = (int64_t)K->nslots * 64 * 72;
     if (K->nslices <= 0 || !K->d_vals) return STAN_OK;
     const unsigned grid = nblk(K->nslices, 4);
-    dev_bufs bufs;
+    dev_scope bufs(ctx);
     double *sink;
-    STANCHK(alloc(ctx, bufs, &sink, (size_t)grid));
+    STANCHK(bufs.alloc(&sink, (size_t)grid));
     event_bag events;
     hipEvent_t a = events.make(), b = events.make();
     auto one = [&]() { hipLaunchKernelGGL(k_value_stream, dim3(grid), dim3(256), 0, st_, K->nslices, K->d_slot_ptr, K->d_vals, sink); };
@@ -1424,14 +1400,15 @@ int stan_spmv_probe(stan_ctx *ctx, stan_matrix *K, const void *vals, size_t byte
     // self_pair: the block holds no values yet (only addresses matter to the timing).  The gather vector and the product
     // must fit into the candidate: a stream with few slots per slice (or a large halo) has no self-paired reference --
     // *ms_out stays 0, the search then keeps the fastest real pairing (placement.hip)
-    timed_product t;
-    STANCHK(timed_product_setup(ctx, K, precision, vals, self_pair ? const_cast<void *>(vals) : nullptr, bytes, t));
-    if (!t.a.x) return STAN_OK;
+    dev_scope bufs(ctx);
+    product_args pa{};
+    STANCHK(timed_product_setup(ctx, K, precision, vals, self_pair ? const_cast<void *>(vals) : nullptr, bytes, bufs, pa));
+    if (!pa.x) return STAN_OK;
     event_bag ev;
     // one launch to warm up, then two groups of three launches back to back, the faster group counts.  (Round 4: single
     // launches between host synchronisations -- the first form of this probe -- start on an idle device and read 2-3 %
     // under the same product inside a sequence of kernels.)
-    auto one = [&]() { launch_product(ctx, K, t.a); };
+    auto one = [&]() { launch_product(ctx, K, pa); };
     one();
     float best = 0;
     for (int g = 0; g < 2; g++) {

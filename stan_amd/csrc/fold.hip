@@ -128,25 +128,22 @@ int stan_matrix_make_folded(stan_ctx *ctx, stan_matrix *K, int32_t stream_kind, 
     hipStream_t st = ctx->stream;
     const unsigned grid = (unsigned)((K->nslices + 3) / 4);
     if (K->fold_state == 0) {
-        int32_t *width = nullptr;
-        int64_t *ptr64 = nullptr;
-        struct tmp { stan_ctx *c; int32_t **a; int64_t **b; ~tmp() { stan_dfree(c, *a); stan_dfree(c, *b); } } guard{ctx, &width, &ptr64};
+        dev_scope tmp(ctx);
+        int32_t *width; int64_t *ptr64;
         // (an earlier attempt that ran out of memory may have left these behind)
         stan_dfree(ctx, K->d_fold_plan); K->d_fold_plan = nullptr;
         stan_dfree(ctx, K->d_fold_meta); K->d_fold_meta = nullptr;
-        STANCHK(stan_dmalloc(ctx, &width, (size_t)K->nslices + 1));
-        STANCHK(stan_dmalloc(ctx, &ptr64, (size_t)K->nslices + 2));
+        STANCHK(tmp.alloc(&width, (size_t)K->nslices + 1));
+        STANCHK(tmp.alloc(&ptr64, (size_t)K->nslices + 2));
         STANCHK(stan_dmalloc(ctx, &K->d_fold_plan, (size_t)K->nslices * 64));
         STANCHK(stan_dmalloc(ctx, &K->d_fold_meta, (size_t)K->nslices * 64));
         unsigned long long *d_uns = (unsigned long long *)(ctx->d_status + SS_COUNTER);
         HIPCHK(ctx, hipMemsetAsync(d_uns, 0, 8, st));
         hipLaunchKernelGGL(k_fold_plan, dim3(grid), dim3(256), 0, st, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_rowlen,
                            width, K->d_fold_plan, K->d_fold_meta, d_uns);
-        STANCHK(stan_scan_exclusive(ctx, width, ptr64, K->nslices));
-        std::vector<int64_t> h((size_t)K->nslices + 1);
-        HIPCHK(ctx, hipMemcpyAsync(h.data(), ptr64, h.size() * 8, hipMemcpyDeviceToHost, st));
+        STANCHK(stan_scan_total(ctx, width, ptr64, K->nslices, SS_H_NSLOTS));
         HIPCHK(ctx, hipStreamSynchronize(st));
-        K->nfslots = h[(size_t)K->nslices];
+        K->nfslots = ctx->h_status[SS_H_NSLOTS];
         // not worth a second copy of the matrix: a layout that is already tight (the cube: 0.7 % padding)
         if (K->nfslots >= ((int64_t)1 << 31) || (ctx->row_folding < 0 && (double)K->nfslots > 0.95 * (double)K->nslots)) {
             stan_dfree(ctx, K->d_fold_plan); K->d_fold_plan = nullptr;
@@ -154,11 +151,7 @@ int stan_matrix_make_folded(stan_ctx *ctx, stan_matrix *K, int32_t stream_kind, 
             K->fold_state = K->nfslots >= ((int64_t)1 << 31) ? -1 : -2;
             return STAN_OK;
         }
-        std::vector<int32_t> h32(h.size());
-        for (size_t i = 0; i < h.size(); i++) h32[i] = (int32_t)h[i];
-        STANCHK(stan_dmalloc(ctx, &K->d_fold_ptr, h32.size()));
-        HIPCHK(ctx, hipMemcpyAsync(K->d_fold_ptr, h32.data(), h32.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));   // h32 must outlive the copy
+        STANCHK(stan_slot_ptr_narrow(ctx, ptr64, K->nslices, &K->d_fold_ptr));
         STANCHK(stan_dmalloc(ctx, &K->d_fold_cols, (size_t)(K->nfslots > 0 ? K->nfslots : 1) * 64));
         K->fold_state = 1;
     }

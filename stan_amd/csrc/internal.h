@@ -341,6 +341,16 @@ static inline int64_t stan_row_start(int64_t nb, int nranks, int r) {
 // ---- scan.hip -------------------------------------------------------------------------------
 // out[i] = sum_{j<i} in[j] (int32 in, int64 out), out has n+1 entries (out[n] = total).
 int stan_scan_exclusive(stan_ctx *ctx, const int32_t *d_in, int64_t *d_out, int64_t n);
+// ... and the total on its way to the pinned h_status[slot] (valid after the caller's next synchronisation).
+int stan_scan_total(stan_ctx *ctx, const int32_t *d_in, int64_t *d_out, int64_t n, int slot);
+// Flags -> the ascending list of the flagged indices: stan_scan_total(d_flag -> d_rank), a synchronisation (one may serve
+// several lists), then collect: reads the count, allocates *out (a temporary of `tmp`, or the caller's) and fills it.
+struct dev_scope;
+int stan_compact_collect(stan_ctx *ctx, const int32_t *d_flag, const int64_t *d_rank, int64_t n, int slot, int32_t **out, int64_t *count, dev_scope *tmp = nullptr);
+int stan_compact_flags(stan_ctx *ctx, const int32_t *d_flag, int64_t *d_rank, int64_t n, int slot, int32_t **out, int64_t *count, dev_scope *tmp = nullptr);   // all three
+// Widths -> int32 slot pointers: stan_scan_total(d_width -> d_ptr64), then (behind a synchronisation when the total
+// must be checked first) narrow: allocates *d_ptr32[n + 1], the caller's, and fills it.
+int stan_slot_ptr_narrow(stan_ctx *ctx, const int64_t *d_ptr64, int64_t n, int32_t **d_ptr32);
 
 // ---- assembly.hip ---------------------------------------------------------------------------
 int stan_assemble_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
@@ -472,6 +482,28 @@ static inline void stan_flush_deferred(stan_ctx *ctx) {
     for (void *q : ctx->deferred) hipFree(q);
     ctx->deferred.clear();
 }
+// device temporaries of one call: given back to the context in the order of allocation, on every exit path
+struct dev_scope {
+    stan_ctx *ctx;
+    std::vector<void *> p;
+    explicit dev_scope(stan_ctx *c) : ctx(c) {}
+    dev_scope(const dev_scope &) = delete; dev_scope &operator=(const dev_scope &) = delete;
+    ~dev_scope() { for (void *q : p) stan_dfree(ctx, q); }
+    template <typename T>
+    int alloc(T **q, size_t n) {
+        const int rc = stan_dmalloc(ctx, q, n);
+        if (rc == STAN_OK) p.push_back((void *)*q);
+        return rc;
+    }
+};
+// the det J == 0 report of the element kernels (the caller has copied h_status[SS_BAD_ELEM] back and synchronised)
+static inline int stan_detj_check(stan_ctx *ctx, const char *why) {
+    if (ctx->h_status[SS_BAD_ELEM] == 0x7fffffffffffffffLL) return STAN_OK;
+    ctx->bad_elem = ctx->h_status[SS_BAD_ELEM];
+    ctx->err = "det J == 0 in element " + std::to_string(ctx->bad_elem) + why;
+    return STAN_E_DETJ;
+}
+static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }   // blocks of t threads over n items
 
 // ---- multi.hip: fan-out of the public entry points for a group handle ------------------------
 void stan_set_global_error(const std::string &msg);   // api.hip: errors raised before a context exists

@@ -10,18 +10,18 @@ int stan_spmv_probe_range(stan_ctx *ctx, stan_matrix *K, const double *vals, int
     if (s1 <= s0) return STAN_OK;
     const int64_t npad = (int64_t)K->nslices * 64;
     const int64_t ng = 3 * ((npad > K->nloc + K->nhalo ? npad : K->nloc + K->nhalo));
-    dev_bufs bufs;
+    dev_scope bufs(ctx);
     double *x, *y, *partial; int64_t *stt; int32_t *list;
     if (xy_region) {   // lab: gather vector and product live inside a block the caller chose
         x = xy_region;
         y = y_region ? y_region : xy_region + ((ng + 511) & ~(int64_t)511);
     } else {
-        STANCHK(alloc(ctx, bufs, &x, (size_t)ng));
-        STANCHK(alloc(ctx, bufs, &y, (size_t)ng));
+        STANCHK(bufs.alloc(&x, (size_t)ng));
+        STANCHK(bufs.alloc(&y, (size_t)ng));
     }
-    STANCHK(alloc(ctx, bufs, &partial, 2 * (size_t)K->nslices + 2));   // k_spmv_small leaves one partial per slice
-    STANCHK(alloc(ctx, bufs, &stt, (size_t)T_NSTAT));
-    STANCHK(alloc(ctx, bufs, &list, (size_t)(s1 - s0)));
+    STANCHK(bufs.alloc(&partial, 2 * (size_t)K->nslices + 2));   // k_spmv_small leaves one partial per slice
+    STANCHK(bufs.alloc(&stt, (size_t)T_NSTAT));
+    STANCHK(bufs.alloc(&list, (size_t)(s1 - s0)));
     std::vector<int32_t> h((size_t)(s1 - s0));
     for (int32_t i = s0; i < s1; i++) h[i - s0] = i;
     int64_t init[T_NSTAT] = {0x7fffffffffffffffLL, 0x7fffffffffffffffLL, 0, 0, 0, 0, 0, 0};
@@ -95,10 +95,10 @@ int stan_spmv_incg_lab(stan_ctx *ctx, stan_matrix *K, int reps, double *out_ms) 
     STANCHK(stan_cg_workspace(ctx, K));
     const int64_t ng = ctx->ws.ng, n3 = 3 * K->nloc;
     double *x = ctx->ws.p, *y = ctx->ws.v;
-    dev_bufs bufs;
+    dev_scope bufs(ctx);
     double *partial; int64_t *stt;
-    STANCHK(alloc(ctx, bufs, &partial, 2 * (size_t)nblk(K->nslices, 4) + 16));
-    STANCHK(alloc(ctx, bufs, &stt, (size_t)T_NSTAT));
+    STANCHK(bufs.alloc(&partial, 2 * (size_t)nblk(K->nslices, 4) + 16));
+    STANCHK(bufs.alloc(&stt, (size_t)T_NSTAT));
     int64_t init[T_NSTAT] = {0x7fffffffffffffffLL, 0x7fffffffffffffffLL, 0, 0, 0, 0, 0, 0};
     HIPCHK(ctx, hipMemcpyAsync(stt, init, sizeof(init), hipMemcpyHostToDevice, st_));
     hipLaunchKernelGGL(k_fill, dim3(vec_grid(ng)), dim3(VEC_T), 0, st_, x, ng, 1.0);
@@ -115,7 +115,7 @@ int stan_spmv_incg_lab(stan_ctx *ctx, stan_matrix *K, int reps, double *out_ms) 
                 a.n3 = n3; a.k = 1; a.sc = nullptr; a.st = stt; a.xcur = ctx->ws.xb[0]; a.xnext = ctx->ws.xb[1];
                 a.r = ctx->ws.r; a.p = ctx->ws.w; a.v = y; a.bh = ctx->ws.bh; a.partial = partial; a.w = ctx->ws.w;
                 a.merit = 0; a.refresh = 0; a.defer_x = 0; a.fold = NO_FOLD;
-                double *scal; STANCHK(alloc(ctx, bufs, &scal, (size_t)S_NSCAL));
+                double *scal; STANCHK(bufs.alloc(&scal, (size_t)S_NSCAL));
                 double hs[S_NSCAL] = {0}; hs[S_VMV] = 1.0; hs[S_RHO0] = hs[S_RHO1] = 1e-30;
                 HIPCHK(ctx, hipMemcpyAsync(scal, hs, sizeof(hs), hipMemcpyHostToDevice, st_));
                 a.sc = scal;

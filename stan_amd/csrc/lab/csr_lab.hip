@@ -53,8 +53,6 @@ k_csr_spmv(int64_t nrows, const int64_t *__restrict__ rp, const int32_t *__restr
     if (row < nrows && l == 0) y[row] = a;
 }
 
-inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
-
 }  // namespace
 
 extern "C" int stan_hip_csr_spmv_bench(stan_ctx *ctx, stan_matrix *K, int32_t reps, double *avg_ms,
@@ -68,13 +66,11 @@ extern "C" int stan_hip_csr_spmv_bench(stan_ctx *ctx, stan_matrix *K, int32_t re
     int64_t *rp = nullptr;
     double *cv = nullptr, *x = nullptr, *y = nullptr, *y2 = nullptr;
     int64_t *stt = nullptr;
-    std::vector<void *> own;
-    auto A = [&](auto **p, size_t n) { int rc = stan_dmalloc(ctx, p, n); if (!rc) own.push_back((void *)*p); return rc; };
-    struct F { stan_ctx *c; std::vector<void *> &v; ~F() { for (void *q : v) stan_dfree(c, q); } } fr{ctx, own};
+    dev_scope tmp(ctx);
     const int64_t npad3 = 3 * (int64_t)K->nslices * 64;
-    STANCHK(A(&len3, (size_t)n3 + 1)); STANCHK(A(&rp, (size_t)n3 + 2)); STANCHK(A(&ci, (size_t)nnz));
-    STANCHK(A(&cv, (size_t)nnz)); STANCHK(A(&x, (size_t)npad3)); STANCHK(A(&y, (size_t)npad3));
-    STANCHK(A(&y2, (size_t)npad3)); STANCHK(A(&stt, 8));
+    STANCHK(tmp.alloc(&len3, (size_t)n3 + 1)); STANCHK(tmp.alloc(&rp, (size_t)n3 + 2)); STANCHK(tmp.alloc(&ci, (size_t)nnz));
+    STANCHK(tmp.alloc(&cv, (size_t)nnz)); STANCHK(tmp.alloc(&x, (size_t)npad3)); STANCHK(tmp.alloc(&y, (size_t)npad3));
+    STANCHK(tmp.alloc(&y2, (size_t)npad3)); STANCHK(tmp.alloc(&stt, 8));
     hipLaunchKernelGGL(k_csr_rowlen, dim3(nblk(n3, 256)), dim3(256), 0, st, nloc, K->d_rowlen, len3);
     STANCHK(stan_scan_exclusive(ctx, len3, rp, n3));
     hipLaunchKernelGGL(k_csr_fill, dim3(nblk(nloc, 256)), dim3(256), 0, st, nloc, K->d_rowlen, K->d_posof, K->d_slot_ptr,

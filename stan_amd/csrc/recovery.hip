@@ -169,8 +169,9 @@ int stan_recover_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, con
     if (n_elem <= 0) return STAN_OK;
     std::vector<double> lamG(2 * (size_t)n_mat);
     for (int m = 0; m < n_mat; m++) stan_lame(mat_E_nu[2 * m], mat_E_nu[2 * m + 1], &lamG[2 * m], &lamG[2 * m + 1]);
+    dev_scope tmp(ctx);
     double *d_lamG;
-    STANCHK(stan_dmalloc(ctx, &d_lamG, lamG.size()));
+    STANCHK(tmp.alloc(&d_lamG, lamG.size()));
     hipStream_t st = ctx->stream;
     long long init[2] = {0x7fffffffffffffffLL, 0x7fffffffffffffffLL};
     hipError_t e1 = hipMemcpyAsync(d_lamG, lamG.data(), lamG.size() * 8, hipMemcpyHostToDevice, st);
@@ -187,7 +188,6 @@ int stan_recover_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, con
     hipError_t e3 = hipGetLastError();
     hipError_t e4 = hipMemcpyAsync(ctx->h_status + SS_BAD_ELEM, ctx->d_status + SS_BAD_ELEM, 16, hipMemcpyDeviceToHost, st);
     hipError_t e5 = hipStreamSynchronize(st);
-    stan_dfree(ctx, d_lamG);
     for (hipError_t e : {e1, e2, e3, e4, e5})
         if (e != hipSuccess) { ctx->err = std::string("recover: ") + hipGetErrorString(e); return STAN_E_HIP; }
     if (ctx->h_status[SS_AUX] != init[0]) {
@@ -196,10 +196,5 @@ int stan_recover_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, con
                    " is HEX8_G1 (the reference throws: N has one row, Element.cs:242)";
         return STAN_E_UNSUPPORTED;
     }
-    if (ctx->h_status[SS_BAD_ELEM] != init[0]) {
-        ctx->bad_elem = ctx->h_status[SS_BAD_ELEM];
-        ctx->err = "det J == 0 in element " + std::to_string(ctx->bad_elem);
-        return STAN_E_DETJ;
-    }
-    return STAN_OK;
+    return stan_detj_check(ctx, "");
 }

@@ -79,6 +79,17 @@ __global__ void k_set_total(const int64_t *excl_last, const int32_t *in_last32,
     *out_total = *excl_last + (in_last32 ? (int64_t)*in_last32 : *in_last64);
 }
 
+__global__ void k_i64_to_i32(const int64_t *in, int32_t *out, int64_t n) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (int32_t)in[i];
+}
+
+// out[rank[i]] = i for every flagged i
+__global__ void k_compact_flags(const int32_t *flag, const int64_t *rank, int32_t *out, int64_t n) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && flag[i]) out[rank[i]] = (int32_t)i;
+}
+
 template <typename Tin>
 int scan_rec(stan_ctx *ctx, const Tin *d_in, int64_t *d_out, int64_t n) {
     // out[0..n-1] exclusive, out[n] total
@@ -91,20 +102,15 @@ int scan_rec(stan_ctx *ctx, const Tin *d_in, int64_t *d_out, int64_t n) {
         hipLaunchKernelGGL(k_tile_scan<Tin>, dim3(1), dim3(SCAN_T), 0, ctx->stream, d_in,
                            (const int64_t *)nullptr, d_out, n);
     } else {
-        int64_t *d_tsum = nullptr, *d_toff = nullptr;
-        STANCHK(stan_dmalloc(ctx, &d_tsum, (size_t)ntiles));
-        STANCHK(stan_dmalloc(ctx, &d_toff, (size_t)ntiles + 1));
+        dev_scope tmp(ctx);   // (pooled blocks are reused in stream order; smaller ones go through hipFree, which waits for the device itself)
+        int64_t *d_tsum, *d_toff;
+        STANCHK(tmp.alloc(&d_tsum, (size_t)ntiles));
+        STANCHK(tmp.alloc(&d_toff, (size_t)ntiles + 1));
         hipLaunchKernelGGL(k_tile_sums<Tin>, dim3((unsigned)ntiles), dim3(SCAN_T), 0, ctx->stream,
                            d_in, d_tsum, n);
-        int rc = scan_rec<int64_t>(ctx, d_tsum, d_toff, ntiles);
-        if (rc == STAN_OK)
-            hipLaunchKernelGGL(k_tile_scan<Tin>, dim3((unsigned)ntiles), dim3(SCAN_T), 0,
-                               ctx->stream, d_in, (const int64_t *)d_toff, d_out, n);
-        // pooled blocks are reused in stream order; smaller ones go through hipFree, which waits
-        // for the device itself
-        stan_dfree(ctx, d_tsum);
-        stan_dfree(ctx, d_toff);
-        STANCHK(rc);
+        STANCHK(scan_rec<int64_t>(ctx, d_tsum, d_toff, ntiles));
+        hipLaunchKernelGGL(k_tile_scan<Tin>, dim3((unsigned)ntiles), dim3(SCAN_T), 0,
+                           ctx->stream, d_in, (const int64_t *)d_toff, d_out, n);
     }
     if (sizeof(Tin) == 4)
         hipLaunchKernelGGL(k_set_total, dim3(1), dim3(1), 0, ctx->stream, d_out + (n - 1),
@@ -120,4 +126,25 @@ int scan_rec(stan_ctx *ctx, const Tin *d_in, int64_t *d_out, int64_t n) {
 
 int stan_scan_exclusive(stan_ctx *ctx, const int32_t *d_in, int64_t *d_out, int64_t n) {
     return scan_rec<int32_t>(ctx, d_in, d_out, n);
+}
+int stan_scan_total(stan_ctx *ctx, const int32_t *d_in, int64_t *d_out, int64_t n, int slot) {
+    STANCHK(stan_scan_exclusive(ctx, d_in, d_out, n));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + slot, d_out + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    return STAN_OK;
+}
+int stan_compact_collect(stan_ctx *ctx, const int32_t *d_flag, const int64_t *d_rank, int64_t n, int slot, int32_t **out, int64_t *count, dev_scope *tmp) {
+    *count = ctx->h_status[slot];
+    STANCHK(tmp ? tmp->alloc(out, (size_t)*count) : stan_dmalloc(ctx, out, (size_t)*count));
+    hipLaunchKernelGGL(k_compact_flags, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, d_flag, d_rank, *out, n);
+    return STAN_OK;
+}
+int stan_compact_flags(stan_ctx *ctx, const int32_t *d_flag, int64_t *d_rank, int64_t n, int slot, int32_t **out, int64_t *count, dev_scope *tmp) {
+    STANCHK(stan_scan_total(ctx, d_flag, d_rank, n, slot));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return stan_compact_collect(ctx, d_flag, d_rank, n, slot, out, count, tmp);
+}
+int stan_slot_ptr_narrow(stan_ctx *ctx, const int64_t *d_ptr64, int64_t n, int32_t **d_ptr32) {
+    STANCHK(stan_dmalloc(ctx, d_ptr32, (size_t)n + 1));
+    hipLaunchKernelGGL(k_i64_to_i32, dim3(nblk(n + 1, 256)), dim3(256), 0, ctx->stream, d_ptr64, *d_ptr32, n + 1);
+    return STAN_OK;
 }
