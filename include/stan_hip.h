@@ -342,6 +342,35 @@ int stan_hip_cg_solve_dev(stan_ctx *ctx, stan_matrix *K, const double *d_F, doub
                           int32_t max_its, int32_t precision_mode, double *d_U,
                           int32_t *termination_type, int32_t *iterations, double *rel_residual);
 
+/* ---- several load cases against one K ----------------------------------------------------- */
+/* n_rhs load vectors against one K.  F, U: [n_rhs][N], one load case after the other, each as stan_hip_cg_solve
+ * takes it.  termination_type, iterations, rel_residual: [n_rhs] (any of them may be NULL).  Every column is
+ * alglib's loop on its own data with its own scalars and its own stop: the columns share only the pass over K
+ * (groups of 8, 4, 2, 1 columns, one loop per group).  Per column the semantics are stan_hip_cg_solve's: both
+ * conditions zero -> eps_f = 1e-6, codes 1 / 5 / 7 / -5 / -4, the previous point on type 7, a restart every N
+ * iterations, STAN_OPT_CG_MERIT_STOP and STAN_OPT_CG_RUPDATE honoured, a zero column ends at iteration 0 with type 1,
+ * U returned for every code.  A column that has stopped is frozen; the call returns when every column has stopped.
+ * A column's result does not depend on the other columns, on n_rhs or on its position -- bit for bit, under any
+ * option setting (so n_rhs = 1 runs this loop too, it is not forwarded to stan_hip_cg_solve).
+ * Supported: a single-rank context, STAN_PREC_FP64, the classic loop.  STAN_E_UNSUPPORTED for a multi-device handle, a
+ * context with a communicator, any other precision_mode, STAN_OPT_CG_SINGLE_REDUCE = 1; STAN_E_ARG for n_rhs <= 0,
+ * NULL F / U, a K of another context.
+ * The options that only pick between equivalent forms of the single solve (STAN_OPT_SPMV_VARIANT, STAN_OPT_SPMV_SMALL,
+ * STAN_OPT_ROW_FOLDING, STAN_OPT_CG_FUSED_REFRESH, STAN_OPT_CG_LAZY_SCALING, STAN_OPT_CG_DEFER_X, STAN_OPT_VEC_STORE_NT,
+ * STAN_OPT_CG_FOLD_REDUCE) select nothing here.  The batched loop has ONE form: the padded BSELL streams (packed
+ * columns when the context has them), one wavefront per slice with the non-temporal matrix stream and the XCD-chunked
+ * mapping, the matrix scaled before the loop, reductions folded into their producers, the residual refresh as
+ * alglib's literal second product A(x + a p).  With STAN_OPT_SPMV_SMALL = 0, STAN_OPT_CG_FUSED_REFRESH = 0 and
+ * STAN_OPT_ROW_FOLDING = 0 stan_hip_cg_solve runs the same sums in the same order: column j then has its bits.
+ * stan_profile is not touched. */
+int stan_hip_cg_solve_multi(stan_ctx *ctx, stan_matrix *K, int32_t n_rhs, const double *F, double eps_f,
+                            int32_t max_its, int32_t precision_mode, double *U, int32_t *termination_type,
+                            int32_t *iterations, double *rel_residual);
+/* F and U in device memory. */
+int stan_hip_cg_solve_multi_dev(stan_ctx *ctx, stan_matrix *K, int32_t n_rhs, const double *d_F, double eps_f,
+                                int32_t max_its, int32_t precision_mode, double *d_U, int32_t *termination_type,
+                                int32_t *iterations, double *rel_residual);
+
 /* ---- stress recovery: replaces Element.Recovery_Stress + Update_StrainStress ------------ */
 /* (Element.cs:211-246, 257-267, called from Solver.cs:184-210).  disp [n_nodes*3] = the
  * nodal dU_buffer in NodeLib order (Solver.cs:171-178).  strain/stress [n_elem*48]: per

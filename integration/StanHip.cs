@@ -122,6 +122,14 @@ namespace STAN_Solver
             IntPtr ctx, IntPtr K, IntPtr d_F, double eps_f, int max_its, int precision_mode, IntPtr d_U,
             out int termination_type, out int iterations, out double rel_residual);
 
+        // ---- several load cases against one K: F, U [n_rhs * N]; termination_type, iterations, rel_residual [n_rhs]
+        [DllImport(Lib)] internal static extern int stan_hip_cg_solve_multi(
+            IntPtr ctx, IntPtr K, int n_rhs, double[] F, double eps_f, int max_its, int precision_mode, [Out] double[] U,
+            [Out] int[] termination_type, [Out] int[] iterations, [Out] double[] rel_residual);
+        [DllImport(Lib)] internal static extern int stan_hip_cg_solve_multi_dev(
+            IntPtr ctx, IntPtr K, int n_rhs, IntPtr d_F, double eps_f, int max_its, int precision_mode, IntPtr d_U,
+            [Out] int[] termination_type, [Out] int[] iterations, [Out] double[] rel_residual);
+
         // ---- Element.Recovery_Stress + Update_StrainStress (Element.cs:211-246, 257-267)
         [DllImport(Lib)] internal static extern int stan_hip_recover_hex8(
             IntPtr ctx, long n_nodes, double[] xyz, double[] disp, long n_elem, int[] conn, int[] elem_mat,

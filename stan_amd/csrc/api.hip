@@ -395,6 +395,36 @@ int stan_hip_cg_solve(stan_ctx *ctx, stan_matrix *K, const double *F, double eps
     return STAN_OK;
 }
 
+// Several load cases against one K (cg.hip: stan_cg_multi_device).  One device, one rank: a multi-device handle is refused.
+int stan_hip_cg_solve_multi_dev(stan_ctx *ctx, stan_matrix *K, int32_t n_rhs, const double *d_F, double eps_f,
+                                int32_t max_its, int32_t precision_mode, double *d_U, int32_t *termination_type,
+                                int32_t *iterations, double *rel_residual) {
+    if (!ctx || !K || !d_F || !d_U || K->ctx != ctx) return STAN_E_ARG;
+    STAN_NO_GROUP(ctx, "cg_solve_multi_dev");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return stan_cg_multi_device(ctx, K, n_rhs, d_F, eps_f, max_its, precision_mode, d_U, termination_type, iterations,
+                                rel_residual);
+}
+
+int stan_hip_cg_solve_multi(stan_ctx *ctx, stan_matrix *K, int32_t n_rhs, const double *F, double eps_f, int32_t max_its,
+                            int32_t precision_mode, double *U, int32_t *termination_type, int32_t *iterations,
+                            double *rel_residual) {
+    if (!ctx || !K || !F || !U || K->ctx != ctx) return STAN_E_ARG;
+    STAN_NO_GROUP(ctx, "cg_solve_multi");
+    if (n_rhs <= 0) { ctx->err = "cg_solve_multi: n_rhs must be > 0"; return STAN_E_ARG; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)K->n_red * (size_t)n_rhs;
+    dbuf<double> dF, dU;
+    STANCHK(dF.upload(ctx, F, n));
+    STANCHK(dU.alloc(ctx, n));
+    HIPCHK(ctx, hipMemsetAsync(dU.p, 0, (n ? n : 1) * 8, ctx->stream));
+    STANCHK(stan_cg_multi_device(ctx, K, n_rhs, dF.p, eps_f, max_its, precision_mode, dU.p, termination_type, iterations,
+                                 rel_residual));
+    if (n) HIPCHK(ctx, hipMemcpyAsync(U, dU.p, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return STAN_OK;
+}
+
 int stan_hip_recover_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
                               const double *d_disp, int64_t n_elem, const int32_t *d_conn,
                               const int32_t *d_elem_mat, const uint8_t *d_elem_type,

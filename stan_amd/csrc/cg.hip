@@ -195,6 +195,8 @@ __device__ __forceinline__ bool stopped(const int64_t *st, int64_t k) {
 
 #include "cg_vector_kernels.inc"   // the vector kernels of the CG loop: k_step, k_refresh, k_update, k_vec_sr (single-reduction form), result / expand / compress
 
+#include "cg_multi.inc"   // the batched loop (several load cases, one pass over K): k_spmm and the M-column forms of k_init / k_step / k_refresh / k_update / k_result
+
 inline unsigned vec_grid(int64_t n) {
     int64_t b = (n + VEC_T - 1) / VEC_T;
     if (b < 1) b = 1;
@@ -1431,3 +1433,184 @@ int stan_spmv_probe(stan_ctx *ctx, stan_matrix *K, const void *vals, size_t byte
 // scaled values on the way out, whether or not a solve has happened, so an export before a solve and one after it are
 // the same bits (rounds 1-4 un-scaled the values in place for an export and re-scaled them for the next solve)
 int stan_matrix_ensure_scaled(stan_ctx *ctx, stan_matrix *K) { return ensure_scaled(ctx, K); }
+
+// ---- several load cases in one loop over a single pass of K (stan_hip_cg_solve_multi) -------------------------------------
+// n_rhs right-hand sides are cut into groups of 8, 4, 2, 1 columns, run one after the other; a group is ONE loop of the
+// shape of cg_run::iterate on interleaved vectors of its own (cg_multi.inc), whose every kernel serves all live columns.
+// One form only: padded BSELL streams (packed columns when the context has them), k_spmm, ensure_scaled before the loop,
+// folded reductions, the literal second product on refresh iterations.  One rank, fp64 stream, classic loop.
+namespace {
+
+constexpr int MULTI_MAX = 8;   // widest group (k_spmm<8>: register table in DESIGN.md)
+
+struct pinned_words {
+    int64_t *p = nullptr;
+    ~pinned_words() { if (p) (void)hipHostFree(p); }
+};
+
+struct cg_multi_run {
+    stan_ctx *ctx;
+    stan_matrix *K;
+    double eps_f;
+    int32_t max_its;
+    hipStream_t st_ = nullptr;
+    dev_scope bufs{ctx};
+    int64_t n3 = 0, ng = 0, pstride = 0, its_before_restart = 1;
+    unsigned vg = 1, pg = 0;
+    double *xb[2] = {nullptr, nullptr}, *p = nullptr, *r = nullptr, *v = nullptr, *bh = nullptr, *partial = nullptr, *sc = nullptr;
+    int64_t *stt = nullptr;
+    unsigned long long *tick = nullptr;
+    pinned_words host;          // [2][MULTI_MAX][T_NSTAT] poll slots, [MULTI_MAX][T_NSTAT] final status, [MULTI_MAX][S_NSCAL] scalars
+    event_bag events;
+    hipEvent_t poll[2] = {nullptr, nullptr};
+    static constexpr int64_t hard_cap = 0x7fffffff;
+
+    int setup(int mmax) {
+        st_ = ctx->stream;
+        STANCHK(ensure_scaled(ctx, K));
+        if (ctx->cols16) STANCHK(stan_matrix_make_cols16(ctx, K));
+        n3 = 3 * K->nloc;
+        ng = gather_len(K);
+        vg = vec_grid(n3);
+        pg = nblk(K->nslices, 4);
+        pstride = 2 * (int64_t)(pg > VEC_BLOCKS ? pg : VEC_BLOCKS) + 16;
+        its_before_restart = K->n_red > 0 ? K->n_red : 1;
+        const size_t m = (size_t)mmax, g = (size_t)(ng > 0 ? ng : 1), n = (size_t)(n3 > 0 ? n3 : 1);
+        for (double **q : {&xb[0], &xb[1], &p}) STANCHK(bufs.alloc(q, g * m));
+        for (double **q : {&r, &v, &bh}) STANCHK(bufs.alloc(q, n * m));
+        STANCHK(bufs.alloc(&partial, (size_t)pstride * m));
+        STANCHK(bufs.alloc(&sc, (size_t)S_NSCAL * m));
+        STANCHK(bufs.alloc(&stt, (size_t)T_NSTAT * m));
+        STANCHK(bufs.alloc(&tick, (size_t)(2 * FOLD_WORDS)));
+        HIPCHK(ctx, hipHostMalloc((void **)&host.p, (size_t)(3 * T_NSTAT + S_NSCAL) * MULTI_MAX * 8, hipHostMallocDefault));
+        poll[0] = events.make(hipEventDisableTiming);
+        poll[1] = events.make(hipEventDisableTiming);
+        return STAN_OK;
+    }
+
+    // one group: columns [c0, c0 + M) of F and U
+    template <int M>
+    int group(const double *d_F, double *d_U, int32_t *term_out, int32_t *iters_out, double *rel_out) {
+        const int64_t nr = K->n_red;
+        const size_t g = (size_t)(ng > 0 ? ng : 1);
+        const int merit = ctx->cg_merit_stop ? 1 : 0, rupdate = ctx->cg_rupdate;
+        const colstream cs = colstream_of(ctx, K);
+        const fold_args fvec{tick + FOLD_WORDS, vg, (int)vg, nullptr, NO_P2P};   // counter set 1 serves the vector kernels,
+        const fold_args fprod{tick, pg, (int)pg, nullptr, NO_P2P};               // set 0 the products
+        int64_t *h_poll = host.p, *h_st = host.p + 2 * MULTI_MAX * T_NSTAT;
+        double *h_sc = (double *)(host.p + 3 * MULTI_MAX * T_NSTAT);
+        HIPCHK(ctx, hipMemsetAsync(sc, 0, (size_t)S_NSCAL * M * 8, st_));
+        HIPCHK(ctx, hipMemsetAsync(stt, 0, (size_t)T_NSTAT * M * 8, st_));
+        HIPCHK(ctx, hipMemsetAsync(tick, 0, 2 * FOLD_WORDS * 8, st_));
+        for (double *q : {xb[0], xb[1], p}) HIPCHK(ctx, hipMemsetAsync(q, 0, g * M * 8, st_));
+        hipLaunchKernelGGL(k_init_m<M>, dim3(vg), dim3(VEC_T), 0, st_, n3, nr, K->d_red, d_F, K->d_scale, bh, xb[0], r, p, partial,
+                           pstride, sc, fvec);
+        hipLaunchKernelGGL(k_init_scalars_m<M>, dim3(1), dim3(64), 0, st_, sc, stt, eps_f);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(h_st, stt, (size_t)T_NSTAT * M * 8, hipMemcpyDeviceToHost, st_));
+        HIPCHK(ctx, hipStreamSynchronize(st_));
+        auto all_stopped = [&](const int64_t *w) {
+            for (int c = 0; c < M; c++) if (w[c * T_NSTAT + T_TYPE] == 0) return false;
+            return true;
+        };
+        bool done = all_stopped(h_st) || pg == 0;   // the first residual test ended every column (b = 0, or eps >= 1)
+        int64_t k = 1;
+        int chunk_id = 0;
+        while (!done) {
+            for (int c = 0; c < CHUNK && k < hard_cap; c++, k++) {
+                const bool refresh = rupdate > 0 && (k % rupdate) == 0;
+                hipLaunchKernelGGL((k_spmm<M, 1>), dim3(pg), dim3(256), 0, st_, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols,
+                                   K->d_vals, p, v, partial, pstride, sc, stt, k, fprod, cs);
+                mstep_args a;
+                a.n3 = n3; a.k = k; a.sc = sc; a.st = stt;
+                a.xcur = xb[(k - 1) & 1]; a.xnext = xb[k & 1];
+                a.r = r; a.p = p; a.v = v; a.bh = bh; a.partial = partial; a.pstride = pstride;
+                a.merit = merit; a.refresh = refresh ? 1 : 0; a.fold = fvec;
+                hipLaunchKernelGGL(k_step_m<M>, dim3(vg), dim3(VEC_T), 0, st_, a);
+                if (refresh) {   // r = b^ - A^ x' from alglib's literal second product
+                    hipLaunchKernelGGL((k_spmm<M, 0>), dim3(pg), dim3(256), 0, st_, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof,
+                                       K->d_cols, K->d_vals, xb[k & 1], v, partial, pstride, sc, stt, k, NO_FOLD, cs);
+                    hipLaunchKernelGGL(k_refresh_m<M>, dim3(vg), dim3(VEC_T), 0, st_, n3, k, sc, (const int64_t *)stt, bh, v, xb[k & 1],
+                                       r, partial, pstride, fvec);
+                }
+                hipLaunchKernelGGL(k_update_m<M>, dim3(vg), dim3(VEC_T), 0, st_, n3, k, sc, stt, eps_f, (int64_t)max_its,
+                                   its_before_restart, merit, r, p);
+            }
+            HIPCHK(ctx, hipGetLastError());
+            // poll: read the status of the PREVIOUS chunk while this one runs; done when every column has stopped
+            int64_t *slot = h_poll + MULTI_MAX * T_NSTAT * (chunk_id & 1);
+            HIPCHK(ctx, hipMemcpyAsync(slot, stt, (size_t)T_NSTAT * M * 8, hipMemcpyDeviceToHost, st_));
+            HIPCHK(ctx, hipEventRecord(poll[chunk_id & 1], st_));
+            if (chunk_id > 0) {
+                HIPCHK(ctx, hipEventSynchronize(poll[(chunk_id - 1) & 1]));
+                if (all_stopped(h_poll + MULTI_MAX * T_NSTAT * ((chunk_id - 1) & 1))) done = true;
+            }
+            if (k >= hard_cap) done = true;
+            chunk_id++;
+        }
+        HIPCHK(ctx, hipStreamSynchronize(st_));
+        HIPCHK(ctx, hipMemcpyAsync(h_st, stt, (size_t)T_NSTAT * M * 8, hipMemcpyDeviceToHost, st_));
+        HIPCHK(ctx, hipMemcpyAsync(h_sc, sc, (size_t)S_NSCAL * M * 8, hipMemcpyDeviceToHost, st_));
+        HIPCHK(ctx, hipStreamSynchronize(st_));
+        bool capped = false;
+        for (int c = 0; c < M; c++) {
+            int64_t *w = h_st + c * T_NSTAT;
+            if (w[T_TYPE] == 0) { w[T_TYPE] = 5; w[T_ITERS] = k - 1; w[T_XSEL] = (k - 1) & 1; capped = true; }   // hard cap
+        }
+        if (capped) HIPCHK(ctx, hipMemcpyAsync(stt, h_st, (size_t)T_NSTAT * M * 8, hipMemcpyHostToDevice, st_));
+        hipLaunchKernelGGL(k_result_m<M>, dim3(vg), dim3(VEC_T), 0, st_, n3, nr, K->d_red, K->d_scale, xb[0], xb[1],
+                           (const int64_t *)stt, d_U);
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipStreamSynchronize(st_));
+        for (int c = 0; c < M; c++) {
+            const int64_t *w = h_st + c * T_NSTAT;
+            const double bnorm = h_sc[c * S_NSCAL + S_BNORM];
+            if (term_out) term_out[c] = (int32_t)w[T_TYPE];
+            if (iters_out) iters_out[c] = (int32_t)(w[T_ITERS] > hard_cap ? hard_cap : w[T_ITERS]);
+            if (rel_out) rel_out[c] = bnorm > 0 ? std::sqrt(h_sc[c * S_NSCAL + S_R2OUT]) / bnorm : 0.0;
+        }
+        return STAN_OK;
+    }
+};
+
+}  // namespace
+
+int stan_cg_multi_device(stan_ctx *ctx, stan_matrix *K, int32_t n_rhs, const double *d_F, double eps_f, int32_t max_its,
+                         int32_t precision_mode, double *d_U, int32_t *term_out, int32_t *iters_out, double *rel_res_out) {
+    if (ctx->comm != nullptr || ctx->nranks > 1) {
+        ctx->err = "cg_solve_multi: single-rank contexts only (no communicator)";
+        return STAN_E_UNSUPPORTED;
+    }
+    if (precision_mode != STAN_PREC_FP64) {
+        ctx->err = "cg_solve_multi: only the fp64 value stream (STAN_PREC_FP64) is supported";
+        return STAN_E_UNSUPPORTED;
+    }
+    if (ctx->cg_single_reduce) {
+        ctx->err = "cg_solve_multi: the single-reduction loop (STAN_OPT_CG_SINGLE_REDUCE) is not supported";
+        return STAN_E_UNSUPPORTED;
+    }
+    if (n_rhs <= 0) {
+        ctx->err = "cg_solve_multi: n_rhs must be > 0";
+        return STAN_E_ARG;
+    }
+    if (eps_f < 0 || max_its < 0) {
+        ctx->err = "cg_solve_multi: eps_f and max_its must be >= 0";
+        return STAN_E_ARG;
+    }
+    if (eps_f == 0 && max_its == 0) eps_f = 1.0e-6;  // lincgsetcond
+    cg_multi_run R{ctx, K, eps_f, max_its};
+    STANCHK(R.setup(n_rhs >= 8 ? 8 : n_rhs >= 4 ? 4 : n_rhs >= 2 ? 2 : 1));
+    const int64_t N = K->n_red;
+    for (int32_t c0 = 0; c0 < n_rhs;) {
+        const int32_t left = n_rhs - c0;
+        const double *F = d_F + (int64_t)c0 * N;
+        double *U = d_U + (int64_t)c0 * N;
+        int32_t *t = term_out ? term_out + c0 : nullptr, *i = iters_out ? iters_out + c0 : nullptr;
+        double *rr = rel_res_out ? rel_res_out + c0 : nullptr;
+        if (left >= 8) { STANCHK(R.group<8>(F, U, t, i, rr)); c0 += 8; }
+        else if (left >= 4) { STANCHK(R.group<4>(F, U, t, i, rr)); c0 += 4; }
+        else if (left >= 2) { STANCHK(R.group<2>(F, U, t, i, rr)); c0 += 2; }
+        else { STANCHK(R.group<1>(F, U, t, i, rr)); c0 += 1; }
+    }
+    return STAN_OK;
+}

@@ -371,6 +371,9 @@ int stan_assemble_colour_scatter(stan_ctx *ctx, stan_matrix *K, int64_t n_elem, 
 int stan_cg_device(stan_ctx *ctx, stan_matrix *K, const double *d_F, double eps_f,
                    int32_t max_its, int32_t precision_mode, double *d_U, int32_t *term,
                    int32_t *iters, double *rel_res);
+// n_rhs load vectors, one loop over a single pass of K per group of columns (cg.hip, cg_multi.inc); d_F, d_U: [n_rhs][n_red]
+int stan_cg_multi_device(stan_ctx *ctx, stan_matrix *K, int32_t n_rhs, const double *d_F, double eps_f, int32_t max_its,
+                         int32_t precision_mode, double *d_U, int32_t *term, int32_t *iters, double *rel_res);
 int stan_spmv_reduced(stan_ctx *ctx, stan_matrix *K, const double *d_x, double *d_y);
 int stan_matrix_diagonal(stan_ctx *ctx, stan_matrix *K, double *d_diag);
 int stan_spmv_bench_device(stan_ctx *ctx, stan_matrix *K, int32_t precision_mode, int32_t reps,

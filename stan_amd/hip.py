@@ -41,7 +41,7 @@ EXPORTS = [
     "stan_hip_init", "stan_hip_init_multi", "stan_hip_destroy", "stan_hip_last_error", "stan_hip_last_bad_element",
     "stan_hip_set_stream", "stan_hip_comm_unique_id", "stan_hip_comm_init",
     "stan_hip_assemble_hex8", "stan_hip_assemble_hex8_dev", "stan_hip_matrix_free",
-    "stan_hip_cg_solve", "stan_hip_cg_solve_dev", "stan_hip_matrix_info", "stan_hip_ke_hex8",
+    "stan_hip_cg_solve", "stan_hip_cg_solve_dev", "stan_hip_cg_solve_multi", "stan_hip_cg_solve_multi_dev", "stan_hip_matrix_info", "stan_hip_ke_hex8",
     "stan_hip_ke_hex8_batch", "stan_hip_matrix_to_csr", "stan_hip_spmv", "stan_hip_spmv_bench", "stan_hip_stream_bench",
     "stan_hip_set_profiling", "stan_hip_get_profile", "stan_hip_set_option", "stan_hip_recover_hex8", "stan_hip_recover_hex8_dev",
     "stan_hip_nodal_forces_hex8", "stan_hip_pool_info",
@@ -397,6 +397,35 @@ class Matrix:
             C.c_int32(precision_mode), _dev(d_U, C.c_double), C.byref(term), C.byref(its),
             C.byref(rel)))
         return dict(terminationtype=term.value, iterations=its.value, rel_residual=rel.value)
+
+    @staticmethod
+    def _multi_reports(term, its, rel):
+        return [dict(terminationtype=int(t), iterations=int(i), rel_residual=float(r)) for t, i, r in zip(term, its, rel)]
+
+    def cg_solve_multi(self, F2d, eps_f, max_its=0, precision_mode=PREC_FP64):
+        """F2d [n_rhs, N]: one load case per row, all solved in one loop over a single pass of K per iteration
+        (stan_hip_cg_solve_multi).  Returns (U2d, [report dict per column, keys as cg_solve])."""
+        F = np.ascontiguousarray(F2d, dtype=np.float64)
+        if F.ndim != 2:
+            raise ValueError("cg_solve_multi: F2d must be [n_rhs, N]")
+        m = F.shape[0]
+        U = np.zeros_like(F)
+        term, its, rel = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1))
+        self.ctx._chk(self.ctx.lib.stan_hip_cg_solve_multi(
+            self.ctx.h, self.k, C.c_int32(m), _ptr(F, C.c_double), C.c_double(eps_f), C.c_int32(max_its),
+            C.c_int32(precision_mode), _ptr(U, C.c_double), _ptr(term, C.c_int32), _ptr(its, C.c_int32),
+            _ptr(rel, C.c_double)))
+        return U, self._multi_reports(term[:m], its[:m], rel[:m])
+
+    def cg_solve_multi_dev(self, d_F, d_U, n_rhs, eps_f, max_its=0, precision_mode=PREC_FP64):
+        """d_F, d_U: device pointers (ints) of [n_rhs, N] arrays.  Returns the list of report dicts."""
+        m = int(n_rhs)
+        term, its, rel = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1))
+        self.ctx._chk(self.ctx.lib.stan_hip_cg_solve_multi_dev(
+            self.ctx.h, self.k, C.c_int32(m), _dev(d_F, C.c_double), C.c_double(eps_f), C.c_int32(max_its),
+            C.c_int32(precision_mode), _dev(d_U, C.c_double), _ptr(term, C.c_int32), _ptr(its, C.c_int32),
+            _ptr(rel, C.c_double)))
+        return self._multi_reports(term[:m], its[:m], rel[:m])
 
     def to_csr(self, upper_only=True):
         nnz = C.c_int64(0)
