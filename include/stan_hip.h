@@ -400,6 +400,60 @@ int stan_hip_recover_hex8_keep(stan_ctx *ctx, int64_t n_nodes, const double *xyz
 int stan_hip_results_map(stan_results *res, int64_t e0, int64_t e1, const double **strain, const double **stress);
 void stan_hip_results_free(stan_results *res);
 
+/* ---- result scalars for post-processing: Part.Load_Scalar (Part.cs:231-528) ----------------- */
+/* The 24 scalars the reference's GUI contours and exports, in Load_Scalar's order (Part.cs:272-297). */
+#define STAN_SCALAR_COUNT 24
+#define STAN_SCALAR_DISP_X 0
+#define STAN_SCALAR_DISP_Y 1
+#define STAN_SCALAR_DISP_Z 2
+#define STAN_SCALAR_DISP_TOTAL 3
+#define STAN_SCALAR_STRESS_XX 4
+#define STAN_SCALAR_STRESS_YY 5
+#define STAN_SCALAR_STRESS_ZZ 6
+#define STAN_SCALAR_STRESS_XY 7
+#define STAN_SCALAR_STRESS_YZ 8
+#define STAN_SCALAR_STRESS_XZ 9
+#define STAN_SCALAR_STRESS_P1 10
+#define STAN_SCALAR_STRESS_P2 11
+#define STAN_SCALAR_STRESS_P3 12
+#define STAN_SCALAR_STRESS_VON_MISES 13
+#define STAN_SCALAR_STRAIN_XX 14
+#define STAN_SCALAR_STRAIN_YY 15
+#define STAN_SCALAR_STRAIN_ZZ 16
+#define STAN_SCALAR_STRAIN_XY 17
+#define STAN_SCALAR_STRAIN_YZ 18
+#define STAN_SCALAR_STRAIN_XZ 19
+#define STAN_SCALAR_STRAIN_P1 20
+#define STAN_SCALAR_STRAIN_P2 21
+#define STAN_SCALAR_STRAIN_P3 22
+#define STAN_SCALAR_STRAIN_EFFECTIVE 23
+/* Per (element, local node) corner: the node's displacement and its length; row i of the element's 8x6 stress and
+ * strain blocks; the eigenvalues P1 >= P2 >= P3 of the tensor built from xx, yy, zz, xy, yz, xz (the shear strain as
+ * stored, not halved: Part.cs:352-360); von Mises = sqrt(((P1-P2)^2 + (P2-P3)^2 + (P3-P1)^2) / 2) from the principals;
+ * effective strain = 2/3 of the same expression on the strain principals (Part.cs:318-379).
+ *   cell  [n_sel][3][n_elem]: max, average, min over the element's 8 corners (:386-388); the average is the sum in local
+ *                             node order 0..7 divided by 8.
+ *   point [n_sel][n_nodes]:   average over the node's incident elements (:431-519) in element order, each element once,
+ *                             its corner the FIRST local position naming the node (collapsed hexes); the sum in
+ *                             ascending element order divided by the count.  A node no element references gets 0 (the
+ *                             reference would divide by zero).
+ * strain, stress [n_elem*48] as stan_hip_recover_hex8 returns them; disp [n_nodes*3]; sel [n_sel] distinct indices
+ * 0..23: only these are computed and stored, row k of the outputs is scalar sel[k].  point or cell may be NULL, not
+ * both.  All outputs are fp64 host arrays and bit-reproducible from run to run (the point scalars are a gather over
+ * ordered incidence lists, not atomics).  No element type is taken: the scalars are defined for any 8x6 block.
+ * The eigenvalues come from a cyclic Jacobi iteration (6 sweeps) and lie within a few units of 2^-52 ||S||_F of the
+ * exact ones, also for coinciding eigenvalues; finite input never gives NaN.
+ * STAN_E_ARG: n_sel <= 0, an index outside 0..23 or listed twice, a node index out of range, n_elem >= 2^28.
+ * STAN_E_UNSUPPORTED on a multi-device handle (stan_hip_init_multi): a node on a chunk boundary has incidences on two
+ * devices, and keeping the bits of the ordered sum across devices is a separate piece of work. */
+int stan_hip_result_scalars_hex8(stan_ctx *ctx, int64_t n_nodes, const double *disp, int64_t n_elem, const int32_t *conn,
+                                 const double *strain, const double *stress, int32_t n_sel, const int32_t *sel,
+                                 double *point, double *cell);
+/* The same from results kept on the device (stan_hip_recover_hex8_keep): no download of the 2 x 48 x n_elem values.
+ * conn [results' n_elem * 8].  STAN_E_ARG also when the results do not live, whole, on the context's device. */
+int stan_hip_results_scalars(stan_ctx *ctx, stan_results *res, int64_t n_nodes, const double *disp, const int32_t *conn,
+                             int32_t n_sel, const int32_t *sel, double *point, double *cell);
+
 /* ---- element nodal forces: replaces Element.Compute_NodalForces + the R assembly ---------- */
 /* (Element.cs:248-255, Solver.cs:184-196).  f_e = sum_g BL[g]^T dS[g] det J_g w, where dS[g] is
  * the NODE-extrapolated stress row g that Recovery_Stress left behind -- the reference indexes
@@ -525,6 +579,9 @@ typedef struct stan_profile {
     int32_t refine_passes;            /* passes of the loop the last solve made (1: no refinement pass was needed) */
     int32_t fp64_products;            /* products with the fp64 values inside a reduced-precision solve (checks, STAN_OPT_CG_REFINE = 2 refreshes) */
     double fp64_products_ms;          /* their stream time, not part of spmv_ms_total */
+    double scalars_cell_ms;           /* last result-scalars call: the cell kernel, */
+    double scalars_list_ms;           /*   the node -> (element, corner) lists,     */
+    double scalars_point_ms;          /*   the point kernel                          */
 } stan_profile;
 int stan_hip_set_profiling(stan_ctx *ctx, int32_t enabled);
 int stan_hip_get_profile(stan_ctx *ctx, stan_profile *out);

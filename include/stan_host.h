@@ -86,6 +86,22 @@ int stan_host_partition_elements(int64_t n_nodes, const int32_t *node_index, int
                                  const int32_t *conn, int32_t nranks, int32_t rank,
                                  int32_t *elem_idx_out, int64_t *n_out);
 
+/* ---- result scalars: names and the .vtu export (Part.Load_Scalar / Part.ExportGrid) ----------
+ * The result string of scalar s (0..23, the STAN_SCALAR_* of stan_hip.h) as the reference's GUI lists it
+ * (Part.cs:403-428: "Displacement X" ... "von Mises Stress" ... "Effective Strain"); NULL outside the range. */
+const char *stan_host_scalar_name(int32_t s);
+/* What Part.ExportGrid + ExportWindow.Export_Click leave on disk (Part.cs:858-939, ExportWindow.xaml.cs:43-108): a VTK
+ * XML UnstructuredGrid, one piece over the whole model in wire order, byte_order LittleEndian, header_type UInt64, all
+ * arrays in one uncompressed <AppendedData encoding="raw"> block.  Points = xyz + disp (Part.UpdateNode; disp NULL = xyz)
+ * as Float64; connectivity = conn [n_elem*8] node indices in CHEXA order (= VTK_HEXAHEDRON's) and offsets as Int64; types
+ * UInt8 = 12.  point_values [n_point_arrays][n_nodes] / cell_values [n_cell_arrays][n_elem] (fp64, as
+ * stan_hip_result_scalars_hex8 returns them) are stored as Float32 -- the reference holds vtkFloatArray -- under
+ * names[k] / cell_names[k]: a point array is named by its result string (Part.cs:931), a cell array carries the
+ * "Max " / "Average " / "Min " prefix; either count may be 0.  STAN_HOST_E_IO when the file cannot be written. */
+int stan_host_write_vtu(const char *path, int64_t n_nodes, const double *xyz, const double *disp, int64_t n_elem,
+                        const int32_t *conn, int32_t n_point_arrays, const char *const *names, const double *point_values,
+                        int32_t n_cell_arrays, const char *const *cell_names, const double *cell_values);
+
 /* ---- STAN_Database object model + STdb codec (stan_amd/host/model.h) -----------------------
  * stan_db wraps a Database (Database.cs:10-21).  Text comes back through
  * stan_host_db_last_error.  Strings are UTF-8, NUL-terminated. */

@@ -68,6 +68,9 @@ namespace STAN_Solver
         public int refine_passes;
         public int fp64_products;
         public double fp64_products_ms;
+        public double scalars_cell_ms;
+        public double scalars_list_ms;
+        public double scalars_point_ms;
     }
 
     internal static class StanHipNative
@@ -151,6 +154,13 @@ namespace STAN_Solver
             int n_mat, double[] mat_E_nu, out IntPtr results);
         [DllImport(Lib)] internal static extern int stan_hip_results_map(IntPtr results, long e0, long e1, out IntPtr strain, out IntPtr stress);
         [DllImport(Lib)] internal static extern void stan_hip_results_free(IntPtr results);
+        // ---- Part.Load_Scalar (Part.cs:231-528): point [n_sel * n_nodes], cell [n_sel * 3 * n_elem]; either may be null
+        [DllImport(Lib)] internal static extern int stan_hip_result_scalars_hex8(
+            IntPtr ctx, long n_nodes, double[] disp, long n_elem, int[] conn, double[] strain, double[] stress, int n_sel,
+            int[] sel, [Out] double[] point, [Out] double[] cell);
+        [DllImport(Lib)] internal static extern int stan_hip_results_scalars(
+            IntPtr ctx, IntPtr results, long n_nodes, double[] disp, int[] conn, int n_sel, int[] sel, [Out] double[] point,
+            [Out] double[] cell);
         [DllImport(Lib)] internal static extern int stan_hip_matrix_diagonal(IntPtr ctx, IntPtr K, [Out] double[] diag);
         [DllImport(Lib)] internal static extern int stan_hip_matrix_part_info(IntPtr K, int part, out StanMatrixInfo info);
         [DllImport(Lib)] internal static extern int stan_hip_ke_hex8(IntPtr ctx, double[] xyz8, double E, double nu, int type, [Out] double[] ke576);

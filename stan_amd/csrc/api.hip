@@ -610,6 +610,73 @@ void stan_hip_results_free(stan_results *res) {
     delete res;
 }
 
+}  // extern "C"
+namespace {
+// Part.Load_Scalar (scalars.hip) with the strain / stress blocks already on the device: argument checks, the uploads of
+// disp and conn, the downloads of the selected rows
+int result_scalars(stan_ctx *ctx, const char *who, int64_t n_nodes, const double *disp, int64_t n_elem, const int32_t *conn,
+                   const double *d_strain, const double *d_stress, int32_t n_sel, const int32_t *sel, double *point, double *cell) {
+    auto bad = [&](const char *why) { ctx->err = std::string(who) + ": " + why; return (int)STAN_E_ARG; };
+    if (n_sel <= 0 || n_sel > STAN_SCALAR_COUNT) return bad("n_sel must be 1..24");
+    uint32_t seen = 0;
+    for (int32_t k = 0; k < n_sel; k++) {
+        if (sel[k] < 0 || sel[k] >= STAN_SCALAR_COUNT) return bad("scalar index outside 0..23");
+        if (seen & (1u << sel[k])) return bad("scalar index listed twice");
+        seen |= 1u << sel[k];
+    }
+    if (n_elem >= (int64_t)1 << 28) return bad("more than 2^28 elements");
+    for (int64_t t = 0; t < n_elem * 8; t++)
+        if (conn[t] < 0 || conn[t] >= n_nodes) return bad("node index out of range");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    dbuf<double> du, dp, dcell; dbuf<int32_t> dc;
+    STANCHK(du.upload(ctx, disp, (size_t)n_nodes * 3));
+    STANCHK(dc.upload(ctx, conn, (size_t)n_elem * 8));
+    const size_t np = (size_t)n_sel * (size_t)n_nodes, nc = (size_t)n_sel * 3 * (size_t)n_elem;
+    if (point) STANCHK(dp.alloc(ctx, np));
+    if (cell) STANCHK(dcell.alloc(ctx, nc));
+    STANCHK(stan_scalars_device(ctx, n_nodes, du.p, n_elem, dc.p, d_strain, d_stress, n_sel, sel, point ? dp.p : nullptr,
+                                cell ? dcell.p : nullptr));
+    if (point) HIPCHK(ctx, hipMemcpyAsync(point, dp.p, np * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (cell && nc) HIPCHK(ctx, hipMemcpyAsync(cell, dcell.p, nc * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return STAN_OK;
+}
+}  // namespace
+extern "C" {
+
+int stan_hip_result_scalars_hex8(stan_ctx *ctx, int64_t n_nodes, const double *disp, int64_t n_elem, const int32_t *conn,
+                                 const double *strain, const double *stress, int32_t n_sel, const int32_t *sel,
+                                 double *point, double *cell) {
+    if (!ctx) return STAN_E_ARG;
+    STAN_NO_GROUP(ctx, "result_scalars_hex8 (a node on a chunk boundary has incidences on two devices)");
+    if (!disp || !sel || n_nodes <= 0 || n_elem < 0 || (!point && !cell) || (n_elem > 0 && (!conn || !strain || !stress))) {
+        ctx->err = "result_scalars_hex8: null or empty argument";
+        return STAN_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    dbuf<double> de, ds;
+    STANCHK(de.upload(ctx, strain, (size_t)n_elem * 48));
+    STANCHK(ds.upload(ctx, stress, (size_t)n_elem * 48));
+    return result_scalars(ctx, "result_scalars_hex8", n_nodes, disp, n_elem, conn, de.p, ds.p, n_sel, sel, point, cell);
+}
+
+int stan_hip_results_scalars(stan_ctx *ctx, stan_results *res, int64_t n_nodes, const double *disp, const int32_t *conn,
+                             int32_t n_sel, const int32_t *sel, double *point, double *cell) {
+    if (!ctx) return STAN_E_ARG;
+    STAN_NO_GROUP(ctx, "results_scalars (a node on a chunk boundary has incidences on two devices)");
+    if (!res || !disp || !sel || n_nodes <= 0 || (!point && !cell) || (res->n_elem > 0 && !conn)) {
+        ctx->err = "results_scalars: null or empty argument";
+        return STAN_E_ARG;
+    }
+    if (res->parts.size() != 1 || res->parts[0].device != ctx->device || res->parts[0].e0 != 0 ||
+        res->parts[0].e1 != res->n_elem) {
+        ctx->err = "results_scalars: the results are not held, whole, on this context's device";
+        return STAN_E_ARG;
+    }
+    return result_scalars(ctx, "results_scalars", n_nodes, disp, res->n_elem, conn, res->parts[0].d_strain,
+                          res->parts[0].d_stress, n_sel, sel, point, cell);
+}
+
 int stan_hip_nodal_forces_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const double *disp,
                                const int32_t *node_dof, int64_t n_elem, const int32_t *conn,
                                const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat,

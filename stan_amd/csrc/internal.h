@@ -405,6 +405,13 @@ int stan_recover_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, con
                         double *d_strain, double *d_stress, const int32_t *d_node_dof,
                         double *d_elem_forces, double *d_R);
 
+// ---- scalars.hip ----------------------------------------------------------------------------
+// Part.Load_Scalar on device arrays; sel: n_sel distinct indices in [0, STAN_SCALAR_COUNT), d_conn checked by the caller;
+// d_point [n_sel][n_nodes] / d_cell [n_sel][3][n_elem], either may be null.  Synchronises the stream.
+int stan_scalars_device(stan_ctx *ctx, int64_t n_nodes, const double *d_disp, int64_t n_elem, const int32_t *d_conn,
+                        const double *d_strain, const double *d_stress, int32_t n_sel, const int32_t *sel, double *d_point,
+                        double *d_cell);
+
 // ---- comm.cpp -------------------------------------------------------------------------------
 int stan_comm_allreduce_sum_f64(stan_ctx *ctx, double *d_buf, size_t count);
 int stan_comm_info(stan_ctx *ctx, int *version, int *count, int *rank);

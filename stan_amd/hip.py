@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STAN_HIP_LIB") or os.path.join(_HERE, "lib", "libstan_hip.so")
 
 HEX8_G1, HEX8_G2 = 1, 2
+N_SCALARS = 24   # STAN_SCALAR_COUNT; indices as include/stan_hip.h's STAN_SCALAR_*
 PREC_FP64, PREC_MIXED, PREC_FIXED48 = 0, 1, 2
 OPT_CG_MERIT_STOP, OPT_CG_RUPDATE, OPT_SPMV_VARIANT, OPT_OVERLAP_HALO, OPT_ASSEMBLY_MODE = 1, 2, 3, 4, 5
 OPT_CG_FUSED_REFRESH = 6
@@ -48,6 +49,7 @@ EXPORTS = [
     "stan_hip_matrix_plan", "stan_hip_spmv_local", "stan_hip_comm_info", "stan_hip_comm_library",
     "stan_hip_matrix_part_info", "stan_hip_get_profile_rank", "stan_hip_device_info", "stan_hip_matrix_diagonal",
     "stan_hip_recover_hex8_keep", "stan_hip_results_map", "stan_hip_results_free",
+    "stan_hip_result_scalars_hex8", "stan_hip_results_scalars",
 ]
 # only in the lab build (stan_amd/csrc/lab/stan_hip_lab.h, selected with STAN_HIP_LIB)
 LAB_EXPORTS = ["stan_hip_csr_spmv_bench", "stan_hip_lab_placement_map", "stan_hip_lab_placement_variants", "stan_hip_lab_placement_alloc", "stan_hip_lab_placement_rounds", "stan_hip_lab_placement_cross", "stan_hip_lab_incg_penalty", "stan_hip_lab_placement_vecalloc", "stan_hip_lab_placement_vecshape", "stan_hip_lab_pairing_pmc"]
@@ -75,7 +77,8 @@ class Profile(C.Structure):
                 ("loop_stream_waits", C.c_int64), ("comm_reduce_ms_total", C.c_double),
                 ("comm_reduce_calls", C.c_int64), ("comm_halo_ms_total", C.c_double), ("comm_halo_calls", C.c_int64),
                 ("rel_residual_recurrence", C.c_double), ("rel_residual_fp64", C.c_double), ("refine_passes", C.c_int32),
-                ("fp64_products", C.c_int32), ("fp64_products_ms", C.c_double)]
+                ("fp64_products", C.c_int32), ("fp64_products_ms", C.c_double),
+                ("scalars_cell_ms", C.c_double), ("scalars_list_ms", C.c_double), ("scalars_point_ms", C.c_double)]
 
 
 class StanHipError(RuntimeError):
@@ -269,6 +272,32 @@ class Context:
             _ptr(elem_type, C.c_uint8), C.c_int32(mat_E_nu.shape[0]), _ptr(mat_E_nu, C.c_double), C.byref(h)))
         return Results(self, h, conn.shape[0])
 
+    # -- result scalars (Part.Load_Scalar) ------------------------------------------------------
+    def _scalars(self, call, disp, conn, sel, point, cell):
+        disp = np.ascontiguousarray(disp, dtype=np.float64).reshape(-1, 3)
+        conn = np.ascontiguousarray(conn, dtype=np.int32).reshape(-1, 8)
+        sel = np.ascontiguousarray(range(N_SCALARS) if sel is None else sel, dtype=np.int32).reshape(-1)
+        nn, ne, ns = disp.shape[0], conn.shape[0], sel.shape[0]
+        pt = np.zeros((ns, nn)) if point else None
+        ce = np.zeros((ns, 3, ne)) if cell else None
+        self._chk(call(C.c_int64(nn), _ptr(disp, C.c_double), C.c_int64(ne), _ptr(conn, C.c_int32), C.c_int32(ns),
+                       _ptr(sel, C.c_int32), _ptr(pt, C.c_double), _ptr(ce, C.c_double)))
+        return pt, ce
+
+    def result_scalars(self, disp, conn, strain, stress, sel=None, point=True, cell=True):
+        """The scalars `sel` (indices 0..23, default all 24) of stan_hip_result_scalars_hex8 from host arrays
+        strain / stress [n_elem, 8, 6]: (point [n_sel, n_nodes], cell [n_sel, 3, n_elem] = max, average, min); an
+        output not asked for is None."""
+        strain = np.ascontiguousarray(strain, dtype=np.float64)
+        stress = np.ascontiguousarray(stress, dtype=np.float64)
+        ne = np.asarray(conn).size // 8
+        if strain.size != ne * 48 or stress.size != ne * 48:
+            raise ValueError("result_scalars: strain / stress must be [n_elem, 8, 6]")
+        return self._scalars(
+            lambda nn, d, n_e, c, ns, s, pt, ce: self.lib.stan_hip_result_scalars_hex8(
+                self.h, nn, d, n_e, c, _ptr(strain, C.c_double), _ptr(stress, C.c_double), ns, s, pt, ce),
+            disp, conn, sel, point, cell)
+
     def nodal_forces_hex8(self, xyz, disp, node_dof, conn, elem_mat, elem_type, mat_E_nu):
         """Element.NodalForces [n_elem,24] and the assembled R [n_dof] (Solver.cs:184-196)."""
         xyz = np.ascontiguousarray(xyz, dtype=np.float64)
@@ -336,6 +365,15 @@ class Results:
             return np.zeros((0, 8, 6)), np.zeros((0, 8, 6))
         return (np.ctypeslib.as_array(ps, shape=(n,)).reshape(-1, 8, 6).copy(),
                 np.ctypeslib.as_array(pt, shape=(n,)).reshape(-1, 8, 6).copy())
+
+    def scalars(self, disp, conn, sel=None, point=True, cell=True):
+        """Context.result_scalars on the kept results (stan_hip_results_scalars): nothing of the 2 x 48 x n_elem values
+        is downloaded."""
+        if np.asarray(conn).size != self.n_elem * 8:
+            raise ValueError("Results.scalars: conn must be [n_elem, 8]")
+        return self.ctx._scalars(
+            lambda nn, d, n_e, c, ns, s, pt, ce: self.ctx.lib.stan_hip_results_scalars(self.ctx.h, self.h, nn, d, c, ns, s, pt, ce),
+            disp, conn, sel, point, cell)
 
     def free(self):
         if getattr(self, "h", None):

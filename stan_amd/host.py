@@ -165,6 +165,41 @@ def partition_elements(node_index, conn, nranks, rank):
     return out[:n.value].copy()
 
 
+# ---- result scalars: names + .vtu export (Part.Load_Scalar / Part.ExportGrid) -------------------
+EXPORTS += ["stan_host_scalar_name", "stan_host_write_vtu"]
+N_SCALARS = 24
+
+
+def scalar_name(s):
+    """Result string of scalar s as the reference's GUI lists it (Part.cs:403-428); None outside 0..23."""
+    lib = load()
+    lib.stan_host_scalar_name.restype = C.c_char_p
+    r = lib.stan_host_scalar_name(C.c_int32(s))
+    return r.decode() if r is not None else None
+
+
+def write_vtu(path, xyz, disp, conn, point_arrays=(), cell_arrays=()):
+    """One-piece UnstructuredGrid .vtu (appended raw data): points xyz + disp (disp may be None), hexahedra conn
+    [n_elem, 8]; point_arrays / cell_arrays: sequences of (name, values[n_nodes] / values[n_elem]), stored as Float32."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+    disp = None if disp is None else np.ascontiguousarray(disp, dtype=np.float64).reshape(-1, 3)
+    conn = np.ascontiguousarray(conn, dtype=np.int32).reshape(-1, 8)
+    nn, ne = xyz.shape[0], conn.shape[0]
+
+    def pack(arrays, n):
+        names = (C.c_char_p * max(len(arrays), 1))(*[a[0].encode() for a in arrays])
+        vals = np.ascontiguousarray([np.asarray(a[1], dtype=np.float64).reshape(n) for a in arrays], dtype=np.float64).reshape(len(arrays), n)
+        return names, vals
+
+    pn, pv = pack(list(point_arrays), nn)
+    cn, cv = pack(list(cell_arrays), ne)
+    rc = load().stan_host_write_vtu(os.fsencode(path), C.c_int64(nn), _p(xyz, C.c_double), _p(disp, C.c_double) if disp is not None else None,
+                                    C.c_int64(ne), _p(conn, C.c_int32), C.c_int32(pv.shape[0]), pn, _p(pv, C.c_double),
+                                    C.c_int32(cv.shape[0]), cn, _p(cv, C.c_double))
+    if rc:
+        raise StanHostError(rc, "write_vtu")
+
+
 # ---- STAN_Database mirror + STdb codec (stan_db part of include/stan_host.h) -----------------
 EXPORTS += [
     "stan_host_db_new", "stan_host_db_free", "stan_host_db_last_error", "stan_host_db_read_stdb",

@@ -13,7 +13,9 @@
 // --p2p (several GPUs: the CG exchanges peer to peer instead of over RCCL, STAN_OPT_COMM_P2P),
 // --object-results (store the results in the Node / Element objects before the export, as the reference does,
 // instead of encoding them from the flat arrays: same bytes), --json (one JSON line with sizes, iterations,
-// device and host phase times and the SpMV's HBM rate).
+// device and host phase times and the SpMV's HBM rate), --vtu PREFIX (after the solve, PREFIX_001.vtu with the point
+// scalars of Part.Load_Scalar as Part.ExportGrid exports them; --vtu-results "name,name,..." picks them by the reference's
+// result strings, default all 24; --vtu-cells adds their Max / Average / Min cell arrays; one device only).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -51,6 +53,8 @@ int main(int argc, char **argv) {
     int device = 0, precision = STAN_PREC_FP64, placement_tries = 16;
     bool merit_stop = true, packed = false, json = false, object_results = false, p2p = false;
     std::vector<int> devices;
+    std::string vtu_prefix, vtu_results;
+    bool vtu = false, vtu_cells = false;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) {
@@ -72,12 +76,30 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--json")) json = true;
         else if (!strcmp(argv[i], "--object-results")) object_results = true;
         else if (!strcmp(argv[i], "--p2p")) p2p = true;
+        else if (!strcmp(argv[i], "--vtu") && i + 1 < argc) { vtu = true; vtu_prefix = argv[++i]; }
+        else if (!strcmp(argv[i], "--vtu-results") && i + 1 < argc) vtu_results = argv[++i];
+        else if (!strcmp(argv[i], "--vtu-cells")) vtu_cells = true;
         else path = argv[i];
     }
     if (path.empty()) {  // Path = path[0] -> IndexOutOfRangeException in the reference
         fprintf(stderr, "usage: stan_solver [--device N | --gpus N | --devices a,b,..] [--p2p] [--mixed|--fixed48] "
-                        "[--no-merit-stop] [--packed] [--object-results] [--json] <model.STdb>\n");
+                        "[--no-merit-stop] [--packed] [--object-results] [--json] [--vtu PREFIX [--vtu-results \"name,..\"] [--vtu-cells]] "
+                        "<model.STdb>\n");
         return 2;
+    }
+    // --vtu is checked before anything is read: the input file is overwritten by a run that gets further
+    std::vector<int32_t> vtu_sel;
+    if (vtu) {
+        std::string why;
+        if (devices.size() > 1) {
+            fprintf(stderr, "stan_solver: --vtu works on one device: the result scalars average over all elements at a node, "
+                            "and a multi-device handle holds them in chunks (drop --gpus/--devices, or export in a second run)\n");
+            return 2;
+        }
+        if (!SolverFunctions::ParseScalarNames(vtu_results, &vtu_sel, &why)) {
+            fprintf(stderr, "stan_solver: --vtu-results: %s\n", why.c_str());
+            return 2;
+        }
     }
     SolverOptions opt;
     opt.device = device; opt.devices = devices; opt.precision = precision; opt.placement_tries = placement_tries; opt.merit_stop = merit_stop; opt.profile = json;
@@ -88,7 +110,7 @@ int main(int argc, char **argv) {
 
     // host phase times of this run (--json): the path around the GPU hot path is host work, and at scale most
     // of the wall clock
-    double t_read = 0, t_dof = 0, t_bc = 0, t_disp = 0, t_recover = 0, t_store = 0, t_write = 0, t_hot = 0;
+    double t_read = 0, t_dof = 0, t_bc = 0, t_disp = 0, t_recover = 0, t_store = 0, t_write = 0, t_hot = 0, t_scalars = 0, t_vtu = 0;
     const auto t_wall = clk::now();
     printf("   Reading input file: ");  // Solver.cs:23-41
     fflush(stdout);
@@ -164,6 +186,12 @@ int main(int argc, char **argv) {
         printf("            Done\n");
         stan_profile pr{};
         if (json) stan_hip_get_profile(K.ctx, &pr);
+        // the .vtu takes its scalars from the results while they are still on the device (the STdb export frees them)
+        if (vtu) {
+            Functions.Export_Vtu(K, disp, object_results ? &strain : nullptr, object_results ? &stress : nullptr, vtu_prefix,
+                                 vtu_sel, vtu_cells, &t_scalars, &t_vtu);
+            printf("   VTU export: %s_001.vtu\n", vtu_prefix.c_str());
+        }
         // Solver.cs:81-90 (initialise step 0/1), :203-210 (update), Main :56
         t0 = clk::now();
         // Solver.cs:81-90, 203-210: every node / element object is initialised and updated with the results, then
@@ -213,12 +241,12 @@ int main(int argc, char **argv) {
                    "\"host_threads\": %d, \"t_wall_s\": %.3f, \"t_device_assembly_plus_cg_s\": %.4f, "
                    "\"phases_s\": {\"read_parse\": %.3f, \"assign_dof\": %.3f, \"bc_tables\": %.3f, "
                    "\"flatten_upload_assemble_solve\": %.3f, \"displacements\": %.3f, \"stress_recovery\": %.3f, "
-                   "\"store_results\": %.3f, \"serialize_write\": %.3f}}\n",
+                   "\"store_results\": %.3f, \"serialize_write\": %.3f, \"result_scalars\": %.3f, \"write_vtu\": %.3f}}\n",
                    devices.size() > 1 ? (int)devices.size() : 1, DB.nDOF, (long long)minfo.n_reduced, (long long)minfo.n_blocks, Functions.last_iterations,
                    Functions.last_termination_type, Functions.last_rel_residual, Functions.last_assembly_s,
                    Functions.last_cg_s, spmv_ms, spmv_ms > 0 ? pr.spmv_bytes / spmv_ms / 1e6 : 0.0,
                    spmv_ms > 0 ? pr.spmv_bytes / spmv_ms / 1e6 / 8000.0 : 0.0,
-                   HostThreads(), wall, dev, t_read, t_dof, t_bc, t_hot, t_disp, t_recover, t_store, t_write);
+                   HostThreads(), wall, dev, t_read, t_dof, t_bc, t_hot, t_disp, t_recover, t_store, t_write, t_scalars, t_vtu);
         }
         return 0;
     } catch (const std::exception &e) {  // the C# lets these escape Main as unhandled exceptions

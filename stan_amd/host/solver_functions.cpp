@@ -190,6 +190,63 @@ void SolverFunctions::Recovery_Stress_Keep(SparseMatrixHandle &K, const std::vec
         throw std::runtime_error(stan_hip_last_error(K.ctx));  // HEX8_G1: the reference throws too (Element.cs:242)
 }
 
+bool SolverFunctions::ParseScalarNames(const std::string &text, std::vector<int32_t> *sel, std::string *err) {
+    sel->clear();
+    if (text.empty()) {
+        for (int32_t s = 0; s < STAN_SCALAR_COUNT; s++) sel->push_back(s);
+        return true;
+    }
+    for (size_t a = 0; a <= text.size();) {
+        size_t b = text.find(',', a);
+        if (b == std::string::npos) b = text.size();
+        size_t x = a, y = b;
+        while (x < y && text[x] == ' ') x++;
+        while (y > x && text[y - 1] == ' ') y--;
+        const std::string name = text.substr(x, y - x);
+        int32_t found = -1;
+        for (int32_t s = 0; s < STAN_SCALAR_COUNT; s++)
+            if (name == stan_host_scalar_name(s)) found = s;
+        if (found < 0) { *err = "unknown result \"" + name + "\" (the names are those of the reference's result box, e.g. \"von Mises Stress\")"; return false; }
+        for (int32_t s : *sel)
+            if (s == found) { *err = "result \"" + name + "\" listed twice"; return false; }
+        sel->push_back(found);
+        a = b + 1;
+    }
+    return true;
+}
+
+void SolverFunctions::Export_Vtu(SparseMatrixHandle &K, const std::vector<double> &dU, const std::vector<double> *strain,
+                                 const std::vector<double> *stress, const std::string &prefix, const std::vector<int32_t> &sel,
+                                 bool cells, double *t_scalars, double *t_write) const {
+    const FlatModel &f = K.flat;
+    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
+    const int32_t n_sel = (int32_t)sel.size();
+    auto t0 = clk::now();
+    std::vector<double> point((size_t)n_sel * (size_t)n_nodes), cell(cells ? (size_t)n_sel * 3 * (size_t)n_elem : 0);
+    const int rc = strain && stress
+                       ? stan_hip_result_scalars_hex8(K.ctx, n_nodes, dU.data(), n_elem, f.conn.data(), strain->data(), stress->data(),
+                                                      n_sel, sel.data(), point.data(), cells ? cell.data() : nullptr)
+                       : stan_hip_results_scalars(K.ctx, K.results, n_nodes, dU.data(), f.conn.data(), n_sel, sel.data(),
+                                                  point.data(), cells ? cell.data() : nullptr);
+    if (rc) throw std::runtime_error(stan_hip_last_error(K.ctx));
+    *t_scalars = secs(t0);
+    t0 = clk::now();
+    // a point array is named by its result string (Part.cs:931); the cell arrays keep Load_Scalar's prefixes (:266-297)
+    std::vector<std::string> cell_names;
+    std::vector<const char *> pn, cn;
+    for (int32_t s : sel) {
+        pn.push_back(stan_host_scalar_name(s));
+        if (cells)
+            for (const char *pre : {"Max ", "Average ", "Min "}) cell_names.push_back(std::string(pre) + stan_host_scalar_name(s));
+    }
+    for (const std::string &n : cell_names) cn.push_back(n.c_str());
+    const std::string path = prefix + "_001.vtu";   // ExportWindow.xaml.cs:100
+    if (stan_host_write_vtu(path.c_str(), n_nodes, f.xyz.data(), dU.data(), n_elem, f.conn.data(), n_sel, pn.data(), point.data(),
+                            (int32_t)cn.size(), cn.data(), cell.data()))
+        throw std::runtime_error("cannot write " + path);
+    *t_write = secs(t0);
+}
+
 std::vector<double> SolverFunctions::Include_BC_DOF(const std::vector<double> &A, const std::vector<int32_t> &red) const {
     std::vector<double> full(red.size(), 0.0);  // SolverFunctions.cs:520-538
     for (size_t i = 0; i < red.size(); i++) full[i] = red[i] == -1 ? 0.0 : A[i - (size_t)red[i]];

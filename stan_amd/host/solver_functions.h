@@ -75,6 +75,16 @@ class SolverFunctions {
     // (stan_hip_results_map through Database::ResultView::fetch) instead of holding 1.5 KB per element on the host
     void Recovery_Stress_Keep(SparseMatrixHandle &K, const std::vector<double> &nodal_dU) const;
 
+    // Part.Load_Scalar + Part.ExportGrid / ExportWindow.Export_Click (Part.cs:231-528, 858-939; ExportWindow.xaml.cs:43-108):
+    // the point scalars `sel` (indices of stan_hip.h's STAN_SCALAR_*; with `cells` also their Max / Average / Min cell
+    // arrays) of increment 1, from the results kept on the device (K.results) or, when strain / stress are given, from
+    // those host arrays, written to <prefix>_001.vtu (inc.ToString("000")).  Seconds spent go to *t_scalars / *t_write.
+    void Export_Vtu(SparseMatrixHandle &K, const std::vector<double> &nodal_dU, const std::vector<double> *strain,
+                    const std::vector<double> *stress, const std::string &prefix, const std::vector<int32_t> &sel, bool cells,
+                    double *t_scalars, double *t_write) const;
+    // "name,name,..." of --vtu-results -> indices (stan_host_scalar_name's strings; empty text = all 24); false + *err on an unknown name
+    static bool ParseScalarNames(const std::string &text, std::vector<int32_t> *sel, std::string *err);
+
     std::vector<double> Include_BC_DOF(const std::vector<double> &A, const std::vector<int32_t> &nDOF_reduction) const;
     std::vector<double> Exclude_BC_DOF(const std::vector<double> &A, const std::vector<int32_t> &nDOF_reduction) const;
     double Vector_Norm(const std::vector<double> &v) const;
