@@ -468,6 +468,55 @@ int stan_hip_nodal_forces_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz
                                const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat,
                                const double *mat_E_nu, int64_t n_dof, double *elem_forces, double *R);
 
+/* ---- internal forces, support reactions and the equilibrium check ----------------------------- */
+/* f_int(u) = sum_e int B^T D B u_e dV, element by element from the coordinates and ANY full nodal vector disp
+ * [n_nodes*3] (values at fixed DOFs are used as given): f_e = sum_g B_g^T (D (B_g u_e)) det J_g w with B_g, D, the
+ * Gauss points and the weights exactly those of K_Initial (Element.cs:118-155, FE_Library.cs:63-131) -- the stress is the
+ * GAUSS-POINT stress, not the node-extrapolated one stan_hip_nodal_forces_hex8 keeps from the reference, so f_int is
+ * K u of the full (unreduced) K up to rounding.  HEX8_G1 is supported (one point, weight 8), as in the assembly.
+ * It forms no K, touches no sparse layout and scales nothing: F - f_int(U) is a witness of assembly and solve that
+ * shares no code with them.
+ *   f_int    [n_dof]  f_int[node_dof[3n+c]] = sum of component c over EVERY (element, corner) that names node n, as the K
+ *                     scatter counts them (SolverFunctions.cs:143-173): a collapsed hex that names a node twice gives both
+ *                     corners; a node no element references gets 0.
+ *   reaction [n_dof]  f_int[i] where ndof_reduction[i] == -1, else 0: the force the support exerts on the structure.  The
+ *                     reference drops loads on fixed DOFs (Solver.cs:136-152), and so does this entry point.
+ *   eq                the sums below; the residual at free DOF i is F[i - red[i]] - f_int[i].  Declared void * so that
+ *                     the prototype stays within the types tests/test_integration_shim.py maps; it points to a
+ *                     stan_equilibrium.
+ * F [N] is the reduced load vector as stan_hip_cg_solve takes it, or NULL = 0 (load_* are then 0).  At least one of
+ * f_int, reaction, eq must be non-NULL (STAN_E_ARG); f_int has the same bits whichever outputs are requested.
+ * Bit-reproducible from run to run: no atomics on doubles anywhere.  The node sum runs over the node's ordered incidence
+ * list in ascending element * 8 + corner; the sums of stan_equilibrium are per-block partial sums in block order, finished
+ * by one block.
+ * STAN_E_DETJ (element via stan_hip_last_bad_element) when det J == 0 at a Gauss point; STAN_E_ARG for a node index,
+ * elem_mat or element type out of range, n_dof != 3 n_nodes, an ndof_reduction entry outside -1 / [0, i], n_elem >= 2^28;
+ * STAN_E_DOF_LAYOUT when Node.DOF is not {3i,3i+1,3i+2} or two nodes name the same DOFs (every entry of f_int is written
+ * by exactly one node).  STAN_E_UNSUPPORTED on a multi-device handle
+ * (stan_hip_init_multi) and on a context with a communicator: a node on a chunk boundary has incidences on two devices,
+ * and keeping the bits of the ordered sum across devices is a separate piece of work. */
+typedef struct stan_equilibrium {
+    double reaction_sum[3];   /* sum of f_int over FIXED DOFs, by direction c of node_dof[3n+c]          */
+    double load_sum[3];       /* sum of F over free DOFs, by direction                                    */
+    double fint_sum[3];       /* sum of f_int over ALL DOFs: zero up to rounding for ANY disp             */
+    double residual_norm2;    /* || F - f_int ||_2 over free DOFs                                         */
+    double load_norm2;        /* || F ||_2                                                                */
+    double residual_max;      /* max | F - f_int | over free DOFs ...                                     */
+    int64_t residual_max_dof; /* ... and the full DOF index where it is attained (lowest index on a tie; -1: no free DOF) */
+    int64_t n_fixed;
+} stan_equilibrium;
+int stan_hip_internal_forces_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const double *disp,
+                                  const int32_t *node_dof, int64_t n_elem, const int32_t *conn,
+                                  const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat,
+                                  const double *mat_E_nu, int64_t n_dof, const int32_t *ndof_reduction,
+                                  const double *F, double *f_int, double *reaction, void *eq);
+/* The same with every array except mat_E_nu and eq in device memory on the context's GPU. */
+int stan_hip_internal_forces_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const double *d_disp,
+                                      const int32_t *d_node_dof, int64_t n_elem, const int32_t *d_conn,
+                                      const int32_t *d_elem_mat, const uint8_t *d_elem_type, int32_t n_mat,
+                                      const double *mat_E_nu, int64_t n_dof, const int32_t *d_ndof_reduction,
+                                      const double *d_F, double *d_f_int, double *d_reaction, void *eq);
+
 /* ---- introspection / parity helpers ------------------------------------------------------- */
 typedef struct stan_matrix_info {
     int64_t n_dof;        /* full DOF count                                      */
@@ -582,6 +631,9 @@ typedef struct stan_profile {
     double scalars_cell_ms;           /* last result-scalars call: the cell kernel, */
     double scalars_list_ms;           /*   the node -> (element, corner) lists,     */
     double scalars_point_ms;          /*   the point kernel                          */
+    double forces_elem_ms;            /* last internal-forces call: the element pass, */
+    double forces_list_ms;            /*   the node -> (element, corner) lists,       */
+    double forces_gather_ms;          /*   the node gather with its reductions        */
 } stan_profile;
 int stan_hip_set_profiling(stan_ctx *ctx, int32_t enabled);
 int stan_hip_get_profile(stan_ctx *ctx, stan_profile *out);

@@ -71,6 +71,24 @@ namespace STAN_Solver
         public double scalars_cell_ms;
         public double scalars_list_ms;
         public double scalars_point_ms;
+        public double forces_elem_ms;
+        public double forces_list_ms;
+        public double forces_gather_ms;
+    }
+
+    /// stan_equilibrium (include/stan_hip.h); filled through the IntPtr argument of stan_hip_internal_forces_hex8
+    /// (Marshal.AllocHGlobal(Marshal.SizeOf<StanEquilibrium>()), then Marshal.PtrToStructure)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct StanEquilibrium
+    {
+        public double reaction_sum_x, reaction_sum_y, reaction_sum_z;
+        public double load_sum_x, load_sum_y, load_sum_z;
+        public double fint_sum_x, fint_sum_y, fint_sum_z;
+        public double residual_norm2;
+        public double load_norm2;
+        public double residual_max;
+        public long residual_max_dof;
+        public long n_fixed;
     }
 
     internal static class StanHipNative
@@ -146,6 +164,17 @@ namespace STAN_Solver
             IntPtr ctx, long n_nodes, double[] xyz, double[] disp, int[] node_dof, long n_elem, int[] conn,
             int[] elem_mat, byte[] elem_type, int n_mat, double[] mat_E_nu, long n_dof, [Out] double[] elem_forces,
             [Out] double[] R);
+
+        // ---- internal forces f_int = sum_e int B^T D B u dV, support reactions, equilibrium sums: f_int, reaction [n_dof],
+        //      F [N] or null, eq -> StanEquilibrium or IntPtr.Zero; at least one output
+        [DllImport(Lib)] internal static extern int stan_hip_internal_forces_hex8(
+            IntPtr ctx, long n_nodes, double[] xyz, double[] disp, int[] node_dof, long n_elem, int[] conn, int[] elem_mat,
+            byte[] elem_type, int n_mat, double[] mat_E_nu, long n_dof, int[] ndof_reduction, double[] F,
+            [Out] double[] f_int, [Out] double[] reaction, IntPtr eq);
+        [DllImport(Lib)] internal static extern int stan_hip_internal_forces_hex8_dev(
+            IntPtr ctx, long n_nodes, IntPtr d_xyz, IntPtr d_disp, IntPtr d_node_dof, long n_elem, IntPtr d_conn,
+            IntPtr d_elem_mat, IntPtr d_elem_type, int n_mat, double[] mat_E_nu, long n_dof, IntPtr d_ndof_reduction,
+            IntPtr d_F, IntPtr d_f_int, IntPtr d_reaction, IntPtr eq);
 
         // ---- introspection / parity helpers
         [DllImport(Lib)] internal static extern int stan_hip_matrix_info(IntPtr K, out StanMatrixInfo info);

@@ -718,6 +718,80 @@ int stan_hip_nodal_forces_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz
     return STAN_OK;
 }
 
+// f_int = sum_e int B^T D B u_e dV, reactions and the equilibrium sums (internal_forces.hip).  One device, one rank: a node on
+// a chunk boundary would have incidences on two devices.
+static int internal_forces_refused(stan_ctx *ctx) {
+    STAN_NO_GROUP(ctx, "internal_forces_hex8 (a node on a chunk boundary has incidences on two devices)");
+    if (ctx->nranks > 1 || ctx->comm) {
+        ctx->err = "internal_forces_hex8: not available on a context with a communicator";
+        return STAN_E_UNSUPPORTED;
+    }
+    return STAN_OK;
+}
+
+int stan_hip_internal_forces_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const double *d_disp,
+                                      const int32_t *d_node_dof, int64_t n_elem, const int32_t *d_conn,
+                                      const int32_t *d_elem_mat, const uint8_t *d_elem_type, int32_t n_mat,
+                                      const double *mat_E_nu, int64_t n_dof, const int32_t *d_red, const double *d_F,
+                                      double *d_f_int, double *d_reaction, void *eq) {
+    if (!ctx) return STAN_E_ARG;
+    STANCHK(internal_forces_refused(ctx));
+    if (!d_xyz || !d_disp || !d_node_dof || !d_red || !mat_E_nu || (!d_f_int && !d_reaction && !eq) ||
+        (n_elem > 0 && (!d_conn || !d_elem_mat || !d_elem_type))) {
+        ctx->err = "internal_forces_hex8_dev: null argument, or none of f_int / reaction / eq asked for";
+        return STAN_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return stan_internal_forces_device(ctx, n_nodes, d_xyz, d_disp, d_node_dof, n_elem, d_conn, d_elem_mat, d_elem_type, n_mat,
+                                       mat_E_nu, n_dof, d_red, d_F, d_f_int, d_reaction, (stan_equilibrium *)eq);
+}
+
+int stan_hip_internal_forces_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const double *disp,
+                                  const int32_t *node_dof, int64_t n_elem, const int32_t *conn, const int32_t *elem_mat,
+                                  const uint8_t *elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
+                                  const int32_t *red, const double *F, double *f_int, double *reaction, void *eq) {
+    if (!ctx) return STAN_E_ARG;
+    STANCHK(internal_forces_refused(ctx));
+    if (!xyz || !disp || !node_dof || !red || !mat_E_nu || n_nodes <= 0 || n_mat <= 0 || n_elem < 0 || n_dof != n_nodes * 3 ||
+        (!f_int && !reaction && !eq) || (n_elem > 0 && (!conn || !elem_mat || !elem_type))) {
+        ctx->err = "internal_forces_hex8: null or empty argument, or none of f_int / reaction / eq asked for";
+        return STAN_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // the checks of stan_hip_nodal_forces_hex8, with the element named (the device repeats them for the _dev entry)
+    for (int64_t e = 0; e < n_elem; e++) {
+        if (elem_mat[e] < 0 || elem_mat[e] >= n_mat) { ctx->err = "internal_forces_hex8: elem_mat out of range at element " + std::to_string(e); return STAN_E_ARG; }
+        if (elem_type[e] != STAN_HEX8_G1 && elem_type[e] != STAN_HEX8_G2) { ctx->err = "internal_forces_hex8: unsupported element type at element " + std::to_string(e); return STAN_E_ARG; }
+        for (int a = 0; a < 8; a++)
+            if (conn[e * 8 + a] < 0 || conn[e * 8 + a] >= n_nodes) { ctx->err = "internal_forces_hex8: node index out of range at element " + std::to_string(e); return STAN_E_ARG; }
+    }
+    for (int64_t k = 0; k < n_dof; k++)
+        if (node_dof[k] < 0 || node_dof[k] >= n_dof) { ctx->err = "internal_forces_hex8: DOF out of range"; return STAN_E_DOF_LAYOUT; }
+    int64_t n_fixed = 0;
+    for (int64_t k = 0; k < n_dof; k++) n_fixed += red[k] == -1;
+    const size_t N = (size_t)(n_dof - n_fixed);
+    dbuf<double> dx, du, dF, dfi, dre; dbuf<int32_t> dc, dm, dd, dr; dbuf<uint8_t> dt;
+    STANCHK(dx.upload(ctx, xyz, (size_t)n_nodes * 3));
+    STANCHK(du.upload(ctx, disp, (size_t)n_nodes * 3));
+    STANCHK(dd.upload(ctx, node_dof, (size_t)n_nodes * 3));
+    STANCHK(dc.upload(ctx, conn, (size_t)n_elem * 8));
+    STANCHK(dm.upload(ctx, elem_mat, (size_t)n_elem));
+    STANCHK(dt.upload(ctx, elem_type, (size_t)n_elem));
+    STANCHK(dr.upload(ctx, red, (size_t)n_dof));
+    if (F) STANCHK(dF.upload(ctx, F, N));
+    if (f_int) STANCHK(dfi.alloc(ctx, (size_t)n_dof));
+    if (reaction) STANCHK(dre.alloc(ctx, (size_t)n_dof));
+    const int rc = stan_internal_forces_device(ctx, n_nodes, dx.p, du.p, dd.p, n_elem, dc.p, dm.p, dt.p, n_mat, mat_E_nu, n_dof, dr.p,
+                                               F ? dF.p : nullptr, f_int ? dfi.p : nullptr, reaction ? dre.p : nullptr, (stan_equilibrium *)eq);
+    if (rc == STAN_OK) {
+        if (f_int) HIPCHK(ctx, hipMemcpyAsync(f_int, dfi.p, (size_t)n_dof * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (reaction) HIPCHK(ctx, hipMemcpyAsync(reaction, dre.p, (size_t)n_dof * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    // the uploads above are stream-ordered with the kernels; the host arrays must outlive them
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return rc;
+}
+
 int stan_hip_matrix_part_info(stan_matrix *K, int32_t part, stan_matrix_info *o) {
     if (!K || !o || part < 0) return STAN_E_ARG;
     if (K->parts.empty()) return part == 0 ? stan_hip_matrix_info(K, o) : STAN_E_ARG;

@@ -412,6 +412,21 @@ int stan_scalars_device(stan_ctx *ctx, int64_t n_nodes, const double *d_disp, in
                         const double *d_strain, const double *d_stress, int32_t n_sel, const int32_t *sel, double *d_point,
                         double *d_cell);
 
+// node -> (element, corner) lists in ascending element * 8 + corner: first corners only (the point scalars) or every corner
+// (internal_forces.hip); ptr / list are temporaries of `tmp`, the work is enqueued on the context's stream
+int stan_incidence_lists(stan_ctx *ctx, dev_scope &tmp, int64_t n_nodes, int64_t n_elem, const int32_t *d_conn, bool all_corners,
+                         int64_t **ptr_out, int32_t **list_out);
+
+// ---- internal_forces.hip --------------------------------------------------------------------
+// f_int = sum_e int B^T D B u_e dV gathered per node, reactions and the equilibrium sums (stan_hip_internal_forces_hex8);
+// every array in device memory except mat_E_nu and eq; d_F, d_fint, d_reaction, eq may be null.  Checks its arguments on
+// the device before anything is indexed with them.  Synchronises the stream.
+int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const double *d_disp,
+                                const int32_t *d_node_dof, int64_t n_elem, const int32_t *d_conn, const int32_t *d_elem_mat,
+                                const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
+                                const int32_t *d_red, const double *d_F, double *d_fint, double *d_reaction,
+                                stan_equilibrium *eq);
+
 // ---- comm.cpp -------------------------------------------------------------------------------
 int stan_comm_allreduce_sum_f64(stan_ctx *ctx, double *d_buf, size_t count);
 int stan_comm_info(stan_ctx *ctx, int *version, int *count, int *rank);

@@ -154,27 +154,28 @@ k_scalars_point(int64_t n_nodes, const int64_t *__restrict__ ptr, const int32_t 
             point[(int64_t)sel.row[s] * n_nodes + n] = k1 > k0 ? acc[s] / cnt : 0.0;
 }
 
-// ---- node -> (element, first corner) lists ---------------------------------------------------------------------------
-// corner a of element e counts when no earlier corner of e names the same node (EList holds an element once,
-// Database.cs:149-158; NList.IndexOf finds the first position)
+// ---- node -> (element, corner) lists -----------------------------------------------------------------------------------
+// first corners only (the point scalars): corner a of element e counts when no earlier corner of e names the same node
+// (EList holds an element once, Database.cs:149-158; NList.IndexOf finds the first position); all corners (the internal
+// forces, internal_forces.hip): every corner counts, as the K scatter counts them
 __device__ inline bool first_corner(const int32_t *__restrict__ conn, int64_t t, int32_t nd) {
     const int64_t e8 = t & ~(int64_t)7;
     for (int64_t j = e8; j < t; j++)
         if (conn[j] == nd) return false;
     return true;
 }
-__global__ void k_scal_count(int64_t n_inc, const int32_t *__restrict__ conn, int32_t *cnt) {
+__global__ void k_scal_count(int64_t n_inc, const int32_t *__restrict__ conn, bool all_corners, int32_t *cnt) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_inc) return;
     const int32_t nd = conn[t];
-    if (first_corner(conn, t, nd)) atomicAdd(&cnt[nd], 1);
+    if (all_corners || first_corner(conn, t, nd)) atomicAdd(&cnt[nd], 1);
 }
-__global__ void k_scal_fill(int64_t n_inc, const int32_t *__restrict__ conn, const int64_t *__restrict__ ptr, int32_t *cursor,
-                            int32_t *unsorted) {
+__global__ void k_scal_fill(int64_t n_inc, const int32_t *__restrict__ conn, bool all_corners, const int64_t *__restrict__ ptr,
+                            int32_t *cursor, int32_t *unsorted) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_inc) return;
     const int32_t nd = conn[t];
-    if (first_corner(conn, t, nd)) unsorted[ptr[nd] + atomicAdd(&cursor[nd], 1)] = (int32_t)t;
+    if (all_corners || first_corner(conn, t, nd)) unsorted[ptr[nd] + atomicAdd(&cursor[nd], 1)] = (int32_t)t;
 }
 // the entries of a segment are distinct: the rank of one among its segment is its place in ascending order
 __global__ void k_scal_rank(const int64_t *__restrict__ ptr, int64_t n_nodes, const int32_t *__restrict__ conn,
@@ -190,6 +191,31 @@ __global__ void k_scal_rank(const int64_t *__restrict__ ptr, int64_t n_nodes, co
 }
 
 }  // namespace
+
+// ptr [n_nodes + 1], list [ptr[n_nodes]] = element * 8 + corner, every node's segment ascending: temporaries of `tmp`,
+// enqueued on the context's stream (the caller synchronises before `tmp` goes).  d_conn entries are in [0, n_nodes).
+int stan_incidence_lists(stan_ctx *ctx, dev_scope &tmp, int64_t n_nodes, int64_t n_elem, const int32_t *d_conn, bool all_corners,
+                         int64_t **ptr_out, int32_t **list_out) {
+    hipStream_t st = ctx->stream;
+    const int64_t n_inc = n_elem * 8;
+    int32_t *d_cnt, *d_unsorted, *d_list;
+    int64_t *d_ptr;
+    STANCHK(tmp.alloc(&d_cnt, (size_t)n_nodes));
+    STANCHK(tmp.alloc(&d_ptr, (size_t)n_nodes + 1));
+    STANCHK(tmp.alloc(&d_unsorted, (size_t)(n_inc > 0 ? n_inc : 1)));
+    STANCHK(tmp.alloc(&d_list, (size_t)(n_inc > 0 ? n_inc : 1)));
+    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, (size_t)n_nodes * 4, st));
+    if (n_inc > 0) hipLaunchKernelGGL(k_scal_count, dim3(nblk(n_inc, 256)), dim3(256), 0, st, n_inc, d_conn, all_corners, d_cnt);
+    STANCHK(stan_scan_exclusive(ctx, d_cnt, d_ptr, n_nodes));
+    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, (size_t)n_nodes * 4, st));
+    if (n_inc > 0) {
+        hipLaunchKernelGGL(k_scal_fill, dim3(nblk(n_inc, 256)), dim3(256), 0, st, n_inc, d_conn, all_corners, d_ptr, d_cnt, d_unsorted);
+        hipLaunchKernelGGL(k_scal_rank, dim3(nblk(n_inc, 256)), dim3(256), 0, st, d_ptr, n_nodes, d_conn, d_unsorted, d_list);
+    }
+    *ptr_out = d_ptr;
+    *list_out = d_list;
+    return STAN_OK;
+}
 
 // d_conn entries are in [0, n_nodes) (the callers check on the host); sel: n_sel distinct indices in [0, 24)
 int stan_scalars_device(stan_ctx *ctx, int64_t n_nodes, const double *d_disp, int64_t n_elem, const int32_t *d_conn,
@@ -212,21 +238,10 @@ int stan_scalars_device(stan_ctx *ctx, int64_t n_nodes, const double *d_disp, in
     }
     if (d_point) {
         dev_scope tmp(ctx);
-        int32_t *d_cnt, *d_unsorted, *d_list;
+        int32_t *d_list;
         int64_t *d_ptr;
         if (ev[2]) HIPCHK(ctx, hipEventRecord(ev[2], st));
-        STANCHK(tmp.alloc(&d_cnt, (size_t)n_nodes));
-        STANCHK(tmp.alloc(&d_ptr, (size_t)n_nodes + 1));
-        STANCHK(tmp.alloc(&d_unsorted, (size_t)(n_inc > 0 ? n_inc : 1)));
-        STANCHK(tmp.alloc(&d_list, (size_t)(n_inc > 0 ? n_inc : 1)));
-        HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, (size_t)n_nodes * 4, st));
-        if (n_inc > 0) hipLaunchKernelGGL(k_scal_count, dim3(nblk(n_inc, 256)), dim3(256), 0, st, n_inc, d_conn, d_cnt);
-        STANCHK(stan_scan_exclusive(ctx, d_cnt, d_ptr, n_nodes));
-        HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, (size_t)n_nodes * 4, st));
-        if (n_inc > 0) {
-            hipLaunchKernelGGL(k_scal_fill, dim3(nblk(n_inc, 256)), dim3(256), 0, st, n_inc, d_conn, d_ptr, d_cnt, d_unsorted);
-            hipLaunchKernelGGL(k_scal_rank, dim3(nblk(n_inc, 256)), dim3(256), 0, st, d_ptr, n_nodes, d_conn, d_unsorted, d_list);
-        }
+        STANCHK(stan_incidence_lists(ctx, tmp, n_nodes, n_elem, d_conn, false, &d_ptr, &d_list));
         if (ev[3]) HIPCHK(ctx, hipEventRecord(ev[3], st));
         hipLaunchKernelGGL(k_scalars_point, dim3(nblk(n_nodes, 256)), dim3(256), 0, st, n_nodes, d_ptr, d_list, d_disp, d_strain,
                            d_stress, ss, d_point);

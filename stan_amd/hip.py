@@ -50,6 +50,7 @@ EXPORTS = [
     "stan_hip_matrix_part_info", "stan_hip_get_profile_rank", "stan_hip_device_info", "stan_hip_matrix_diagonal",
     "stan_hip_recover_hex8_keep", "stan_hip_results_map", "stan_hip_results_free",
     "stan_hip_result_scalars_hex8", "stan_hip_results_scalars",
+    "stan_hip_internal_forces_hex8", "stan_hip_internal_forces_hex8_dev",
 ]
 # only in the lab build (stan_amd/csrc/lab/stan_hip_lab.h, selected with STAN_HIP_LIB)
 LAB_EXPORTS = ["stan_hip_csr_spmv_bench", "stan_hip_lab_placement_map", "stan_hip_lab_placement_variants", "stan_hip_lab_placement_alloc", "stan_hip_lab_placement_rounds", "stan_hip_lab_placement_cross", "stan_hip_lab_incg_penalty", "stan_hip_lab_placement_vecalloc", "stan_hip_lab_placement_vecshape", "stan_hip_lab_pairing_pmc"]
@@ -78,7 +79,18 @@ class Profile(C.Structure):
                 ("comm_reduce_calls", C.c_int64), ("comm_halo_ms_total", C.c_double), ("comm_halo_calls", C.c_int64),
                 ("rel_residual_recurrence", C.c_double), ("rel_residual_fp64", C.c_double), ("refine_passes", C.c_int32),
                 ("fp64_products", C.c_int32), ("fp64_products_ms", C.c_double),
-                ("scalars_cell_ms", C.c_double), ("scalars_list_ms", C.c_double), ("scalars_point_ms", C.c_double)]
+                ("scalars_cell_ms", C.c_double), ("scalars_list_ms", C.c_double), ("scalars_point_ms", C.c_double),
+                ("forces_elem_ms", C.c_double), ("forces_list_ms", C.c_double), ("forces_gather_ms", C.c_double)]
+
+
+class Equilibrium(C.Structure):
+    """stan_equilibrium (include/stan_hip.h)"""
+    _fields_ = [("reaction_sum", C.c_double * 3), ("load_sum", C.c_double * 3), ("fint_sum", C.c_double * 3),
+                ("residual_norm2", C.c_double), ("load_norm2", C.c_double), ("residual_max", C.c_double),
+                ("residual_max_dof", C.c_int64), ("n_fixed", C.c_int64)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k.endswith("_sum") else getattr(self, k)) for k, _ in self._fields_}
 
 
 class StanHipError(RuntimeError):
@@ -316,6 +328,47 @@ class Context:
             _ptr(elem_type, C.c_uint8), C.c_int32(mat_E_nu.shape[0]), _ptr(mat_E_nu, C.c_double),
             C.c_int64(n_dof), _ptr(f, C.c_double), _ptr(R, C.c_double)))
         return f, R
+
+    # -- internal forces, reactions, equilibrium ------------------------------------------------
+    def internal_forces_hex8(self, xyz, disp, node_dof, conn, elem_mat, elem_type, mat_E_nu, red, F=None,
+                             f_int=True, reaction=True, eq=True):
+        """stan_hip_internal_forces_hex8: (f_int [n_dof], reaction [n_dof], eq Equilibrium) from host arrays; disp is any
+        full nodal vector [n_nodes, 3], F the reduced load vector or None (= 0).  An output not asked for is None."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        disp = np.ascontiguousarray(disp, dtype=np.float64)
+        node_dof = np.ascontiguousarray(node_dof, dtype=np.int32)
+        conn = np.ascontiguousarray(conn, dtype=np.int32).reshape(-1, 8)
+        elem_mat = np.ascontiguousarray(elem_mat, dtype=np.int32)
+        elem_type = np.ascontiguousarray(elem_type, dtype=np.uint8)
+        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        red = np.ascontiguousarray(red, dtype=np.int32)
+        F = None if F is None else np.ascontiguousarray(F, dtype=np.float64)
+        n_dof = red.shape[0]
+        if disp.size != xyz.size or (F is not None and F.shape[0] != n_dof - int((red == -1).sum())):
+            raise ValueError("internal_forces_hex8: disp must be [n_nodes, 3] and F [n_dof - n_fixed]")
+        fi = np.zeros(n_dof) if f_int else None
+        re = np.zeros(n_dof) if reaction else None
+        q = Equilibrium() if eq else None
+        self._chk(self.lib.stan_hip_internal_forces_hex8(
+            self.h, C.c_int64(xyz.shape[0]), _ptr(xyz, C.c_double), _ptr(disp, C.c_double), _ptr(node_dof, C.c_int32),
+            C.c_int64(conn.shape[0]), _ptr(conn, C.c_int32), _ptr(elem_mat, C.c_int32), _ptr(elem_type, C.c_uint8),
+            C.c_int32(mat_E_nu.shape[0]), _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _ptr(red, C.c_int32),
+            _ptr(F, C.c_double), _ptr(fi, C.c_double), _ptr(re, C.c_double), C.byref(q) if eq else None))
+        return fi, re, q
+
+    def internal_forces_hex8_dev(self, n_nodes, d_xyz, d_disp, d_node_dof, n_elem, d_conn, d_elem_mat, d_elem_type, mat_E_nu,
+                                 n_dof, d_red, d_F=None, d_f_int=None, d_reaction=None, eq=True):
+        """All d_* are device pointers (ints, e.g. torch tensor.data_ptr()); d_F, d_f_int, d_reaction may be None.
+        Returns the Equilibrium (None when not asked for)."""
+        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        q = Equilibrium() if eq else None
+        opt = lambda p: None if p is None else _dev(p, C.c_double)
+        self._chk(self.lib.stan_hip_internal_forces_hex8_dev(
+            self.h, C.c_int64(n_nodes), _dev(d_xyz, C.c_double), _dev(d_disp, C.c_double), _dev(d_node_dof, C.c_int32),
+            C.c_int64(n_elem), _dev(d_conn, C.c_int32), _dev(d_elem_mat, C.c_int32), _dev(d_elem_type, C.c_uint8),
+            C.c_int32(mat_E_nu.shape[0]), _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _dev(d_red, C.c_int32),
+            opt(d_F), opt(d_f_int), opt(d_reaction), C.byref(q) if eq else None))
+        return q
 
     # -- assembly ------------------------------------------------------------------------
     def assemble_hex8(self, xyz, node_dof, conn, elem_mat, elem_type, mat_E_nu, red):

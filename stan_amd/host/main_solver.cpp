@@ -15,7 +15,11 @@
 // instead of encoding them from the flat arrays: same bytes), --json (one JSON line with sizes, iterations,
 // device and host phase times and the SpMV's HBM rate), --vtu PREFIX (after the solve, PREFIX_001.vtu with the point
 // scalars of Part.Load_Scalar as Part.ExportGrid exports them; --vtu-results "name,name,..." picks them by the reference's
-// result strings, default all 24; --vtu-cells adds their Max / Average / Min cell arrays; one device only).
+// result strings, default all 24; --vtu-cells adds their Max / Average / Min cell arrays; one device only), --reactions
+// (after the solve: support reactions and applied load by axis, the out-of-balance norm of F - f_int(U) against |F| and the
+// largest out-of-balance force with its node, from stan_hip_internal_forces_hex8 -- no step of the reference, nothing of it
+// reaches the STdb; with --json an "equilibrium" object, with --vtu the point arrays "Reaction Force X / Y / Z"; one device
+// only).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -54,7 +58,7 @@ int main(int argc, char **argv) {
     bool merit_stop = true, packed = false, json = false, object_results = false, p2p = false;
     std::vector<int> devices;
     std::string vtu_prefix, vtu_results;
-    bool vtu = false, vtu_cells = false;
+    bool vtu = false, vtu_cells = false, reactions = false;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) {
@@ -79,11 +83,12 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--vtu") && i + 1 < argc) { vtu = true; vtu_prefix = argv[++i]; }
         else if (!strcmp(argv[i], "--vtu-results") && i + 1 < argc) vtu_results = argv[++i];
         else if (!strcmp(argv[i], "--vtu-cells")) vtu_cells = true;
+        else if (!strcmp(argv[i], "--reactions")) reactions = true;
         else path = argv[i];
     }
     if (path.empty()) {  // Path = path[0] -> IndexOutOfRangeException in the reference
         fprintf(stderr, "usage: stan_solver [--device N | --gpus N | --devices a,b,..] [--p2p] [--mixed|--fixed48] "
-                        "[--no-merit-stop] [--packed] [--object-results] [--json] [--vtu PREFIX [--vtu-results \"name,..\"] [--vtu-cells]] "
+                        "[--no-merit-stop] [--packed] [--object-results] [--json] [--vtu PREFIX [--vtu-results \"name,..\"] [--vtu-cells]] [--reactions] "
                         "<model.STdb>\n");
         return 2;
     }
@@ -101,6 +106,11 @@ int main(int argc, char **argv) {
             return 2;
         }
     }
+    if (reactions && devices.size() > 1) {
+        fprintf(stderr, "stan_solver: --reactions works on one device: the internal forces add up all elements at a node, and a "
+                        "multi-device handle holds them in chunks (drop --gpus/--devices)\n");
+        return 2;
+    }
     SolverOptions opt;
     opt.device = device; opt.devices = devices; opt.precision = precision; opt.placement_tries = placement_tries; opt.merit_stop = merit_stop; opt.profile = json;
     opt.p2p = p2p;
@@ -110,7 +120,7 @@ int main(int argc, char **argv) {
 
     // host phase times of this run (--json): the path around the GPU hot path is host work, and at scale most
     // of the wall clock
-    double t_read = 0, t_dof = 0, t_bc = 0, t_disp = 0, t_recover = 0, t_store = 0, t_write = 0, t_hot = 0, t_scalars = 0, t_vtu = 0;
+    double t_read = 0, t_dof = 0, t_bc = 0, t_disp = 0, t_recover = 0, t_store = 0, t_write = 0, t_hot = 0, t_scalars = 0, t_vtu = 0, t_react = 0;
     const auto t_wall = clk::now();
     printf("   Reading input file: ");  // Solver.cs:23-41
     fflush(stdout);
@@ -186,10 +196,29 @@ int main(int argc, char **argv) {
         printf("            Done\n");
         stan_profile pr{};
         if (json) stan_hip_get_profile(K.ctx, &pr);
+        // --reactions: f_int(U) element by element, never through K; the displacement vector carries 0 at the fixed DOFs
+        stan_equilibrium eq{};
+        std::vector<double> reaction;
+        if (reactions) {
+            t0 = clk::now();
+            Functions.Equilibrium(K, disp, F, nDOF_reduction, nullptr, vtu ? &reaction : nullptr, &eq);
+            t_react = secs(t0);
+            int64_t node = -1;
+            for (int64_t n = 0; n < n_nodes && eq.residual_max_dof >= 0; n++)
+                if (K.flat.node_dof[(size_t)(3 * n)] == (int32_t)(eq.residual_max_dof - eq.residual_max_dof % 3)) { node = n; break; }
+            printf("   Equilibrium check (internal forces of the solved displacements):\n");
+            printf("     Support reactions:  X %14.6e   Y %14.6e   Z %14.6e\n", eq.reaction_sum[0], eq.reaction_sum[1], eq.reaction_sum[2]);
+            printf("     Applied load:       X %14.6e   Y %14.6e   Z %14.6e\n", eq.load_sum[0], eq.load_sum[1], eq.load_sum[2]);
+            printf("     Out of balance:     |F - f_int| = %.3e, %.3e of |F|\n", eq.residual_norm2,
+                   eq.load_norm2 > 0 ? eq.residual_norm2 / eq.load_norm2 : 0.0);
+            if (node >= 0)
+                printf("     Largest:            %.3e at node %d, direction %c\n", eq.residual_max, DB.NodeLib.Items()[(size_t)node].first,
+                       "XYZ"[eq.residual_max_dof % 3]);
+        }
         // the .vtu takes its scalars from the results while they are still on the device (the STdb export frees them)
         if (vtu) {
             Functions.Export_Vtu(K, disp, object_results ? &strain : nullptr, object_results ? &stress : nullptr, vtu_prefix,
-                                 vtu_sel, vtu_cells, &t_scalars, &t_vtu);
+                                 vtu_sel, vtu_cells, &t_scalars, &t_vtu, reactions ? &reaction : nullptr);
             printf("   VTU export: %s_001.vtu\n", vtu_prefix.c_str());
         }
         // Solver.cs:81-90 (initialise step 0/1), :203-210 (update), Main :56
@@ -241,12 +270,20 @@ int main(int argc, char **argv) {
                    "\"host_threads\": %d, \"t_wall_s\": %.3f, \"t_device_assembly_plus_cg_s\": %.4f, "
                    "\"phases_s\": {\"read_parse\": %.3f, \"assign_dof\": %.3f, \"bc_tables\": %.3f, "
                    "\"flatten_upload_assemble_solve\": %.3f, \"displacements\": %.3f, \"stress_recovery\": %.3f, "
-                   "\"store_results\": %.3f, \"serialize_write\": %.3f, \"result_scalars\": %.3f, \"write_vtu\": %.3f}}\n",
+                   "\"store_results\": %.3f, \"serialize_write\": %.3f, \"result_scalars\": %.3f, \"write_vtu\": %.3f}",
                    devices.size() > 1 ? (int)devices.size() : 1, DB.nDOF, (long long)minfo.n_reduced, (long long)minfo.n_blocks, Functions.last_iterations,
                    Functions.last_termination_type, Functions.last_rel_residual, Functions.last_assembly_s,
                    Functions.last_cg_s, spmv_ms, spmv_ms > 0 ? pr.spmv_bytes / spmv_ms / 1e6 : 0.0,
                    spmv_ms > 0 ? pr.spmv_bytes / spmv_ms / 1e6 / 8000.0 : 0.0,
                    HostThreads(), wall, dev, t_read, t_dof, t_bc, t_hot, t_disp, t_recover, t_store, t_write, t_scalars, t_vtu);
+            if (reactions)   // %.17g: the doubles round-trip
+                printf(", \"equilibrium\": {\"reaction_sum\": [%.17g, %.17g, %.17g], \"load_sum\": [%.17g, %.17g, %.17g], "
+                       "\"fint_sum\": [%.17g, %.17g, %.17g], \"residual_norm2\": %.17g, \"load_norm2\": %.17g, \"residual_max\": %.17g, "
+                       "\"residual_max_dof\": %lld, \"n_fixed\": %lld, \"t_s\": %.3f}",
+                       eq.reaction_sum[0], eq.reaction_sum[1], eq.reaction_sum[2], eq.load_sum[0], eq.load_sum[1], eq.load_sum[2],
+                       eq.fint_sum[0], eq.fint_sum[1], eq.fint_sum[2], eq.residual_norm2, eq.load_norm2, eq.residual_max,
+                       (long long)eq.residual_max_dof, (long long)eq.n_fixed, t_react);
+            printf("}\n");
         }
         return 0;
     } catch (const std::exception &e) {  // the C# lets these escape Main as unhandled exceptions

@@ -181,6 +181,20 @@ void SolverFunctions::Recovery_Stress(SparseMatrixHandle &K, const std::vector<d
         throw std::runtime_error(stan_hip_last_error(K.ctx));  // HEX8_G1: the reference throws too (Element.cs:242)
 }
 
+void SolverFunctions::Equilibrium(SparseMatrixHandle &K, const std::vector<double> &dU, const std::vector<double> &F,
+                                  const std::vector<int32_t> &red, std::vector<double> *f_int, std::vector<double> *reaction,
+                                  stan_equilibrium *eq) const {
+    const FlatModel &f = K.flat;
+    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
+    if (f_int) f_int->assign(red.size(), 0.0);
+    if (reaction) reaction->assign(red.size(), 0.0);
+    if (stan_hip_internal_forces_hex8(K.ctx, n_nodes, f.xyz.data(), dU.data(), f.node_dof.data(), n_elem, f.conn.data(),
+                                      f.elem_mat.data(), f.elem_type.data(), (int32_t)(f.mat_E_nu.size() / 2), f.mat_E_nu.data(),
+                                      (int64_t)red.size(), red.data(), F.empty() ? nullptr : F.data(),
+                                      f_int ? f_int->data() : nullptr, reaction ? reaction->data() : nullptr, eq))
+        throw std::runtime_error(stan_hip_last_error(K.ctx));
+}
+
 void SolverFunctions::Recovery_Stress_Keep(SparseMatrixHandle &K, const std::vector<double> &dU) const {
     const FlatModel &f = K.flat;
     const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
@@ -217,7 +231,7 @@ bool SolverFunctions::ParseScalarNames(const std::string &text, std::vector<int3
 
 void SolverFunctions::Export_Vtu(SparseMatrixHandle &K, const std::vector<double> &dU, const std::vector<double> *strain,
                                  const std::vector<double> *stress, const std::string &prefix, const std::vector<int32_t> &sel,
-                                 bool cells, double *t_scalars, double *t_write) const {
+                                 bool cells, double *t_scalars, double *t_write, const std::vector<double> *reaction) const {
     const FlatModel &f = K.flat;
     const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
     const int32_t n_sel = (int32_t)sel.size();
@@ -240,8 +254,17 @@ void SolverFunctions::Export_Vtu(SparseMatrixHandle &K, const std::vector<double
             for (const char *pre : {"Max ", "Average ", "Min "}) cell_names.push_back(std::string(pre) + stan_host_scalar_name(s));
     }
     for (const std::string &n : cell_names) cn.push_back(n.c_str());
+    if (reaction) {   // by node and direction: reaction[Node.DOF[c]]
+        static const char *const rn[3] = {"Reaction Force X", "Reaction Force Y", "Reaction Force Z"};
+        point.resize((size_t)(n_sel + 3) * (size_t)n_nodes);
+        for (int c = 0; c < 3; c++) {
+            pn.push_back(rn[c]);
+            for (int64_t n = 0; n < n_nodes; n++)
+                point[(size_t)(n_sel + c) * (size_t)n_nodes + (size_t)n] = (*reaction)[(size_t)f.node_dof[(size_t)(3 * n + c)]];
+        }
+    }
     const std::string path = prefix + "_001.vtu";   // ExportWindow.xaml.cs:100
-    if (stan_host_write_vtu(path.c_str(), n_nodes, f.xyz.data(), dU.data(), n_elem, f.conn.data(), n_sel, pn.data(), point.data(),
+    if (stan_host_write_vtu(path.c_str(), n_nodes, f.xyz.data(), dU.data(), n_elem, f.conn.data(), (int32_t)pn.size(), pn.data(), point.data(),
                             (int32_t)cn.size(), cn.data(), cell.data()))
         throw std::runtime_error("cannot write " + path);
     *t_write = secs(t0);

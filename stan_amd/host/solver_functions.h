@@ -79,9 +79,18 @@ class SolverFunctions {
     // the point scalars `sel` (indices of stan_hip.h's STAN_SCALAR_*; with `cells` also their Max / Average / Min cell
     // arrays) of increment 1, from the results kept on the device (K.results) or, when strain / stress are given, from
     // those host arrays, written to <prefix>_001.vtu (inc.ToString("000")).  Seconds spent go to *t_scalars / *t_write.
+    // `reaction` (full DOF numbering, from Equilibrium) adds the point arrays "Reaction Force X" / "Y" / "Z" behind them.
     void Export_Vtu(SparseMatrixHandle &K, const std::vector<double> &nodal_dU, const std::vector<double> *strain,
                     const std::vector<double> *stress, const std::string &prefix, const std::vector<int32_t> &sel, bool cells,
-                    double *t_scalars, double *t_write) const;
+                    double *t_scalars, double *t_write, const std::vector<double> *reaction = nullptr) const;
+
+    // Internal forces f_int(u) = sum_e int B^T D B u_e dV from coordinates and displacements alone, the support reactions
+    // and the out-of-balance sums of F - f_int (stan_hip_internal_forces_hex8): no step of the reference -- a check of
+    // assembly and solve that shares no code with them.  nodal_dU [n_nodes*3] in NodeLib order, F the reduced load vector;
+    // f_int / reaction [nDOF] (either may be null), *eq always filled.
+    void Equilibrium(SparseMatrixHandle &K, const std::vector<double> &nodal_dU, const std::vector<double> &F,
+                     const std::vector<int32_t> &nDOF_reduction, std::vector<double> *f_int, std::vector<double> *reaction,
+                     stan_equilibrium *eq) const;
     // "name,name,..." of --vtu-results -> indices (stan_host_scalar_name's strings; empty text = all 24); false + *err on an unknown name
     static bool ParseScalarNames(const std::string &text, std::vector<int32_t> *sel, std::string *err);
 
