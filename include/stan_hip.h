@@ -517,6 +517,65 @@ int stan_hip_internal_forces_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const doub
                                       const double *mat_E_nu, int64_t n_dof, const int32_t *d_ndof_reduction,
                                       const double *d_F, double *d_f_int, double *d_reaction, void *eq);
 
+/* ---- distributed loads and prescribed displacements: the load vector ------------------------- */
+/* Consistent nodal loads of body forces (self-weight) and face pressures, and the right-hand side for supports moved by a
+ * given amount.  No step of the reference (its BuildReductionAndLoads takes point loads and zero-valued SPCs only).
+ * Faces in CHEXA order, with the natural coordinates of FE_Library.cs:225-235:
+ *     0: xi = -1 {0,3,4,7}   1: xi = +1 {1,2,5,6}   2: eta = -1 {0,1,4,5}   3: eta = +1 {2,3,6,7}
+ *     4: zeta = -1 {0,1,2,3} 5: zeta = +1 {4,5,6,7}
+ * The surface vector of face (axis, s) is n dA = s (x_beta x x_gamma) d beta d gamma with (beta, gamma) the cyclic successors
+ * of the axis (xi -> eta, zeta; eta -> zeta, xi; zeta -> xi, eta): outward for det J > 0.  A positive pressure pushes onto
+ * the face (traction -p n).
+ *   pressure    f_a = -p sum_{2x2} N_a(q) n dA(q)       unit weights, face points at +-1/sqrt 3: exact for a bilinear face
+ *   body force  f_a = b_m sum_{2x2x2} N_a(q) det J(q)   b_m = mat_body[3m..3m+2], a force per unit volume (rho g); the 2x2x2
+ *                                                       rule also for HEX8_G1 elements (exact; no J^-1, det J == 0 is no error)
+ *   prescribed  disp0 [n_nodes*3] is used at the FIXED DOFs only (its entries at free DOFs count as 0):
+ *               F_solve = F - f_int(u0)|free, f_int as stan_hip_internal_forces_hex8 computes it.  The solved field is U on
+ *               the free DOFs and u0 on the fixed ones.
+ * The nodal load l [n_dof] is the sum over every (element, corner) that names the node, as the K scatter counts them.
+ *   mat_body      [n_mat*3] host array or NULL
+ *   face_elem, face_id, face_pressure [n_faces]: the list is canonical, face_elem * 6 + face_id strictly ascending
+ *   F         [N] in/out or NULL: F[j] = F[j] + l[j] on the free DOFs, ONE fp64 add per entry
+ *   F_solve   [N] out: (F after the add, or l when F is NULL) - f_int(u0); required when disp0 is given, and only then differs
+ *   load_full [n_dof] out or NULL: l before the reduction, fixed DOFs included
+ *   sums      stan_load_sums or NULL (void * for the same reason as eq above)
+ * Bit-reproducible: no atomics on doubles.  Within an element the body term comes first (8 Gauss-point terms in three
+ * butterfly stages), then its listed faces in ascending face id; a node adds its incidence list in ascending
+ * element * 8 + corner; the sums are per-block partial sums in block order, finished by one block.  Every output has the same
+ * bits whichever other outputs are asked for.
+ * STAN_E_ARG: face keys not strictly ascending, an element, face id, material or node index out of range, n_dof != 3 n_nodes,
+ * an ndof_reduction entry outside -1 / [0, i], n_elem >= 2^28, none of mat_body / faces / disp0 given, every output NULL,
+ * disp0 without F_solve.  STAN_E_DOF_LAYOUT as in stan_hip_internal_forces_hex8.  STAN_E_DETJ only from the disp0 part, which
+ * needs J^-1.  STAN_E_UNSUPPORTED on a multi-device handle and on a context with a communicator, as there.  On an error no
+ * output has been written. */
+typedef struct stan_load_sums {
+    double load_sum[3];   /* body + pressure over ALL DOFs, by direction                                   */
+    double free_sum[3];   /* the part that reached F (free DOFs); the rest fell on supports                */
+    double volume;        /* sum_q det J(q) over the elements whose material carries a body force          */
+    double area;          /* sum over the listed faces of sum_q |n dA(q)|                                  */
+    int64_t n_fixed;
+    int64_t n_faces;
+} stan_load_sums;
+int stan_hip_load_vector_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const int32_t *node_dof,
+                              int64_t n_elem, const int32_t *conn, const int32_t *elem_mat, const uint8_t *elem_type,
+                              int32_t n_mat, const double *mat_E_nu, int64_t n_dof, const int32_t *ndof_reduction,
+                              const double *mat_body, int64_t n_faces, const int32_t *face_elem, const uint8_t *face_id,
+                              const double *face_pressure, const double *disp0, double *F, double *F_solve,
+                              double *load_full, void *sums);
+/* The same with every array except mat_E_nu, mat_body and sums in device memory on the context's GPU. */
+int stan_hip_load_vector_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const int32_t *d_node_dof,
+                                  int64_t n_elem, const int32_t *d_conn, const int32_t *d_elem_mat,
+                                  const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
+                                  const int32_t *d_ndof_reduction, const double *mat_body, int64_t n_faces,
+                                  const int32_t *d_face_elem, const uint8_t *d_face_id, const double *d_face_pressure,
+                                  const double *d_disp0, double *d_F, double *d_F_solve, double *d_load_full, void *sums);
+
+/* Phase times of the most recent load-vector call on this context, by HIP events (profiling must be enabled first):
+ * ms[0] the element pass, ms[1] the node -> (element, corner) lists, ms[2] the node gather with its reductions; the f_int(u0)
+ * of a prescribed displacement is reported in stan_profile's forces_* fields.  A record of its own: stan_profile is ABI and
+ * ends with the internal forces' fields. */
+int stan_hip_load_vector_times(stan_ctx *ctx, double ms[3]);
+
 /* ---- introspection / parity helpers ------------------------------------------------------- */
 typedef struct stan_matrix_info {
     int64_t n_dof;        /* full DOF count                                      */

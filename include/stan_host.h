@@ -50,6 +50,20 @@ int stan_host_load_vector(int64_t n_dof, const int32_t *node_dof, const int32_t 
 int stan_host_nodal_displacements(int64_t n_nodes, const int32_t *node_dof, const int32_t *red,
                                   const double *U, double *disp_out);
 
+/* ---- distributed loads (no counterpart in the reference) ---------------
+ * The pressure faces of a node set, as stan_hip_load_vector_hex8 takes them.  Faces in CHEXA order: 0 xi=-1 {0,3,4,7},
+ * 1 xi=+1 {1,2,5,6}, 2 eta=-1 {0,1,4,5}, 3 eta=+1 {2,3,6,7}, 4 zeta=-1 {0,1,2,3}, 5 zeta=+1 {4,5,6,7}.  conn [n_elem*8] node
+ * indices; set_nodes [n_set] node indices with their values set_p [n_set] (a node listed twice keeps the last value).
+ * A face counts when every one of its corner nodes is in the set; faces that name fewer than three distinct nodes are
+ * left out; faces are paired by their sorted distinct node set and a set seen twice is an interior face: both copies are
+ * dropped.  face_p = 0.25 x the sum of the four corners' values in local face-node order.  The output is ascending by
+ * face_elem * 6 + face_id.  Only candidate faces are sorted, never all 6 n_elem.  Two calls: with face_elem = face_id =
+ * face_p = NULL only *n_faces is set; with arrays of `capacity` >= *n_faces entries they are filled (a smaller capacity is
+ * STAN_HOST_E_ARG, *n_faces still set). */
+int stan_host_pressure_faces(int64_t n_nodes, int64_t n_elem, const int32_t *conn, int64_t n_set, const int32_t *set_nodes,
+                             const double *set_p, int64_t capacity, int32_t *face_elem, uint8_t *face_id, double *face_p,
+                             int64_t *n_faces);
+
 /* ---- direct solvers: CPU fallback for Analysis.LinSolver = "Cholesky" / "LU" -----------------
  * (SolverFunctions.cs:332-444, 446-516; not on the GPU hot path).  K = the reduced upper-triangle
  * CRS the reference's alglib.sparsematrix holds: rowptr [n+1], col/val [nnz], col >= row
@@ -159,6 +173,15 @@ int stan_host_db_get_flat(stan_db *db, double *xyz, int32_t *node_ids, int32_t *
 /* Solver.cs:104-152 from the BCLib: red[nDOF], *n_fixed, F[nDOF - n_fixed] (F may be NULL
  * on a first call that only asks for n_fixed). */
 int stan_host_db_get_reduction(stan_db *db, int32_t *red, int64_t *n_fixed, double *F);
+/* The BoundaryCondition Types "Pressure" (node IDs, component 0 = p), "BodyForce" (MATERIAL IDs, force per unit volume;
+ * several such BCs add up) and "Displacement" (node IDs, prescribed components on DOFs an SPC fixes) of the BCLib as the
+ * arrays stan_hip_load_vector_hex8 takes (needs AssignDOF).  counts[4] = {1 when the file holds such a BC, n_mat when a
+ * BodyForce exists else 0, n_faces, fixed DOFs with a non-zero prescribed value}.  mat_body [cap_mat*3], the face arrays
+ * [cap_faces] and disp0 [n_nodes*3] are filled when non-NULL (disp0 with zeros when no Displacement exists); a capacity that
+ * is too small, an unknown material ID and a non-zero Displacement on a free DOF (reported with the node ID) are
+ * STAN_HOST_E_ARG.  The reference ignores Types it does not know (Solver.cs:106, 138). */
+int stan_host_db_get_distributed_loads(stan_db *db, int64_t counts[4], int32_t cap_mat, double *mat_body, int64_t cap_faces,
+                                       int32_t *face_elem, uint8_t *face_id, double *face_p, double *disp0);
 /* Result write-back of SolverLinearStatics (Solver.cs:81-90, 171-178, 203-210, Main :56):
  * re-initialises step 0/1, stores disp[n*3] into Node.DispX/Y/Z[1] and strain/stress
  * [e*48] (may be NULL) into Element.Strain[1]/Stress[1], sets Result_StepNo = 1. */

@@ -91,6 +91,18 @@ namespace STAN_Solver
         public long n_fixed;
     }
 
+    /// stan_load_sums (include/stan_hip.h); filled through the IntPtr argument of stan_hip_load_vector_hex8
+    [StructLayout(LayoutKind.Sequential)]
+    public struct StanLoadSums
+    {
+        public double load_sum_x, load_sum_y, load_sum_z;
+        public double free_sum_x, free_sum_y, free_sum_z;
+        public double volume;
+        public double area;
+        public long n_fixed;
+        public long n_faces;
+    }
+
     internal static class StanHipNative
     {
         // "stan_hip" resolves to libstan_hip.so on Linux (.NET probes lib<name>.so; Mono: <dllmap> or the same probing)
@@ -175,6 +187,21 @@ namespace STAN_Solver
             IntPtr ctx, long n_nodes, IntPtr d_xyz, IntPtr d_disp, IntPtr d_node_dof, long n_elem, IntPtr d_conn,
             IntPtr d_elem_mat, IntPtr d_elem_type, int n_mat, double[] mat_E_nu, long n_dof, IntPtr d_ndof_reduction,
             IntPtr d_F, IntPtr d_f_int, IntPtr d_reaction, IntPtr eq);
+
+        // ---- distributed loads and prescribed displacements: mat_body [n_mat * 3] or null; the face list sorted by
+        //      face_elem * 6 + face_id; disp0 [n_nodes * 3] or null; F [N] in/out or null; F_solve [N] (required with disp0);
+        //      load_full [n_dof] or null; sums -> StanLoadSums or IntPtr.Zero; at least one output (F is pinned: updated in place)
+        [DllImport(Lib)] internal static extern int stan_hip_load_vector_hex8(
+            IntPtr ctx, long n_nodes, double[] xyz, int[] node_dof, long n_elem, int[] conn, int[] elem_mat, byte[] elem_type,
+            int n_mat, double[] mat_E_nu, long n_dof, int[] ndof_reduction, double[] mat_body, long n_faces, int[] face_elem,
+            byte[] face_id, double[] face_pressure, double[] disp0, double[] F, [Out] double[] F_solve,
+            [Out] double[] load_full, IntPtr sums);
+        [DllImport(Lib)] internal static extern int stan_hip_load_vector_hex8_dev(
+            IntPtr ctx, long n_nodes, IntPtr d_xyz, IntPtr d_node_dof, long n_elem, IntPtr d_conn, IntPtr d_elem_mat,
+            IntPtr d_elem_type, int n_mat, double[] mat_E_nu, long n_dof, IntPtr d_ndof_reduction, double[] mat_body,
+            long n_faces, IntPtr d_face_elem, IntPtr d_face_id, IntPtr d_face_pressure, IntPtr d_disp0, IntPtr d_F,
+            IntPtr d_F_solve, IntPtr d_load_full, IntPtr sums);
+        [DllImport(Lib)] internal static extern int stan_hip_load_vector_times(IntPtr ctx, [Out] double[] ms);
 
         // ---- introspection / parity helpers
         [DllImport(Lib)] internal static extern int stan_hip_matrix_info(IntPtr K, out StanMatrixInfo info);

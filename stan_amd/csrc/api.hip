@@ -720,10 +720,10 @@ int stan_hip_nodal_forces_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz
 
 // f_int = sum_e int B^T D B u_e dV, reactions and the equilibrium sums (internal_forces.hip).  One device, one rank: a node on
 // a chunk boundary would have incidences on two devices.
-static int internal_forces_refused(stan_ctx *ctx) {
-    STAN_NO_GROUP(ctx, "internal_forces_hex8 (a node on a chunk boundary has incidences on two devices)");
+static int internal_forces_refused(stan_ctx *ctx, const char *entry = "internal_forces_hex8") {
+    STAN_NO_GROUP(ctx, std::string(entry) + " (a node on a chunk boundary has incidences on two devices)");
     if (ctx->nranks > 1 || ctx->comm) {
-        ctx->err = "internal_forces_hex8: not available on a context with a communicator";
+        ctx->err = std::string(entry) + ": not available on a context with a communicator";
         return STAN_E_UNSUPPORTED;
     }
     return STAN_OK;
@@ -790,6 +790,80 @@ int stan_hip_internal_forces_hex8(stan_ctx *ctx, int64_t n_nodes, const double *
     // the uploads above are stream-ordered with the kernels; the host arrays must outlive them
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return rc;
+}
+
+// The load vector of body forces, face pressures and prescribed displacements (loads.hip).  One device, one rank, for the
+// reason the internal forces give.
+int stan_hip_load_vector_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const int32_t *d_node_dof,
+                                  int64_t n_elem, const int32_t *d_conn, const int32_t *d_elem_mat,
+                                  const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
+                                  const int32_t *d_red, const double *mat_body, int64_t n_faces,
+                                  const int32_t *d_face_elem, const uint8_t *d_face_id, const double *d_face_pressure,
+                                  const double *d_disp0, double *d_F, double *d_F_solve, double *d_load_full, void *sums) {
+    if (!ctx) return STAN_E_ARG;
+    STANCHK(internal_forces_refused(ctx, "load_vector_hex8"));
+    if (!d_xyz || !d_node_dof || !d_red || !mat_E_nu || (n_elem > 0 && (!d_conn || !d_elem_mat || !d_elem_type)) ||
+        (n_faces > 0 && (!d_face_elem || !d_face_id || !d_face_pressure))) {
+        ctx->err = "load_vector_hex8_dev: null argument";
+        return STAN_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return stan_load_vector_device(ctx, n_nodes, d_xyz, d_node_dof, n_elem, d_conn, d_elem_mat, d_elem_type, n_mat, mat_E_nu, n_dof,
+                                   d_red, mat_body, n_faces, d_face_elem, d_face_id, d_face_pressure, d_disp0, d_F, d_F_solve,
+                                   d_load_full, (stan_load_sums *)sums);
+}
+
+int stan_hip_load_vector_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const int32_t *node_dof, int64_t n_elem,
+                              const int32_t *conn, const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat,
+                              const double *mat_E_nu, int64_t n_dof, const int32_t *red, const double *mat_body,
+                              int64_t n_faces, const int32_t *face_elem, const uint8_t *face_id, const double *face_pressure,
+                              const double *disp0, double *F, double *F_solve, double *load_full, void *sums) {
+    if (!ctx) return STAN_E_ARG;
+    STANCHK(internal_forces_refused(ctx, "load_vector_hex8"));
+    if (!xyz || !node_dof || !red || !mat_E_nu || n_nodes <= 0 || n_mat <= 0 || n_elem < 0 || n_dof != n_nodes * 3 || n_faces < 0 ||
+        (n_elem > 0 && (!conn || !elem_mat || !elem_type)) || (n_faces > 0 && (!face_elem || !face_id || !face_pressure))) {
+        ctx->err = "load_vector_hex8: null or empty argument, or n_dof != 3 n_nodes";
+        return STAN_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // the length of F is fixed by the reduction map alone; every other integer is checked on the device (loads.hip)
+    int64_t n_fixed = 0;
+    for (int64_t k = 0; k < n_dof; k++) n_fixed += red[k] == -1;
+    const size_t N = (size_t)(n_dof - n_fixed);
+    dbuf<double> dx, dp, du, dF, dFs, dl; dbuf<int32_t> dc, dm, dd, dr, dfe; dbuf<uint8_t> dt, dfi;
+    STANCHK(dx.upload(ctx, xyz, (size_t)n_nodes * 3));
+    STANCHK(dd.upload(ctx, node_dof, (size_t)n_nodes * 3));
+    STANCHK(dc.upload(ctx, conn, (size_t)n_elem * 8));
+    STANCHK(dm.upload(ctx, elem_mat, (size_t)n_elem));
+    STANCHK(dt.upload(ctx, elem_type, (size_t)n_elem));
+    STANCHK(dr.upload(ctx, red, (size_t)n_dof));
+    if (n_faces > 0) {
+        STANCHK(dfe.upload(ctx, face_elem, (size_t)n_faces));
+        STANCHK(dfi.upload(ctx, face_id, (size_t)n_faces));
+        STANCHK(dp.upload(ctx, face_pressure, (size_t)n_faces));
+    }
+    if (disp0) STANCHK(du.upload(ctx, disp0, (size_t)n_nodes * 3));
+    if (F) STANCHK(dF.upload(ctx, F, N));
+    if (F_solve) STANCHK(dFs.alloc(ctx, N));
+    if (load_full) STANCHK(dl.alloc(ctx, (size_t)n_dof));
+    const int rc = stan_load_vector_device(ctx, n_nodes, dx.p, dd.p, n_elem, dc.p, dm.p, dt.p, n_mat, mat_E_nu, n_dof, dr.p, mat_body,
+                                           n_faces, dfe.p, dfi.p, dp.p, disp0 ? du.p : nullptr, F ? dF.p : nullptr,
+                                           F_solve ? dFs.p : nullptr, load_full ? dl.p : nullptr, (stan_load_sums *)sums);
+    if (rc == STAN_OK) {
+        if (F && N) HIPCHK(ctx, hipMemcpyAsync(F, dF.p, N * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (F_solve && N) HIPCHK(ctx, hipMemcpyAsync(F_solve, dFs.p, N * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (load_full) HIPCHK(ctx, hipMemcpyAsync(load_full, dl.p, (size_t)n_dof * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    // the uploads above are stream-ordered with the kernels; the host arrays must outlive them
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return rc;
+}
+
+int stan_hip_load_vector_times(stan_ctx *ctx, double ms[3]) {
+    if (!ctx || !ms) return STAN_E_ARG;
+    STAN_NO_GROUP(ctx, "load_vector_times");
+    for (int k = 0; k < 3; k++) ms[k] = ctx->prof_loads_ms[k];
+    return STAN_OK;
 }
 
 int stan_hip_matrix_part_info(stan_matrix *K, int32_t part, stan_matrix_info *o) {

@@ -35,6 +35,34 @@ __device__ __forceinline__ void hex8_dnl(int i, double px, double py, double pz,
     d[2] = 0.125 * sz * fx * fy;
 }
 
+// N_i at natural point (px,py,pz): 1/8 (1+xi_i xi)(1+eta_i eta)(1+zeta_i zeta) (FE_Library.cs:225-235)
+__device__ __forceinline__ double hex8_shape(int i, double px, double py, double pz) {
+    const double fx = 1.0 + hex8_sign(HEX8_SX, i) * px, fy = 1.0 + hex8_sign(HEX8_SY, i) * py,
+                 fz = 1.0 + hex8_sign(HEX8_SZ, i) * pz;
+    return 0.125 * fx * fy * fz;
+}
+
+// J = dN_dLocal * X at natural point (px,py,pz), row-major: row r = d x / d(natural coordinate r).  No inverse is formed
+// (the load vector needs det J and the rows of J only: loads.hip).
+__device__ __forceinline__ void hex8_jacobian(const double *x, double px, double py, double pz, double J[9]) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) J[k] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        double d[3];
+        hex8_dnl(i, px, py, pz, d);
+        const double x0 = x[3 * i], x1 = x[3 * i + 1], x2 = x[3 * i + 2];
+        J[0] += d[0] * x0; J[1] += d[0] * x1; J[2] += d[0] * x2;
+        J[3] += d[1] * x0; J[4] += d[1] * x1; J[5] += d[1] * x2;
+        J[6] += d[2] * x0; J[7] += d[2] * x1; J[8] += d[2] * x2;
+    }
+}
+// MatrixST.cs:270-287 Det3
+__device__ __forceinline__ double hex8_det3(const double J[9]) {
+    return J[0] * J[4] * J[8] + J[3] * J[7] * J[2] + J[6] * J[1] * J[5] -
+           J[2] * J[4] * J[6] - J[0] * J[5] * J[7] - J[8] * J[1] * J[3];
+}
+
 // Gauss point location (FE_Library.cs:75,103) and weight (:72,:100) of point g for `type`.
 // HEX8_G1 has one point at the origin with weight 8: points g>0 get weight 0.
 __device__ __forceinline__ double hex8_gauss_loc(int type) {

@@ -258,6 +258,7 @@ struct stan_ctx {
     // profiling
     bool profiling = false;
     stan_profile prof{};
+    double prof_loads_ms[3] = {0, 0, 0};   // last load-vector call: element pass | lists | gather (stan_hip_load_vector_times)
     stan_pool pool;
     stan_cg_ws ws;
     std::vector<stan_matrix *> matrices;  // alive matrices of this context (detached when it is destroyed)
@@ -426,6 +427,22 @@ int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_
                                 const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
                                 const int32_t *d_red, const double *d_F, double *d_fint, double *d_reaction,
                                 stan_equilibrium *eq);
+// Its argument check (k_if_check), shared with loads.hip: status[SS_ERRBITS] |= IF_*, status[SS_AUX] += fixed DOFs, both
+// reset by the caller; d_claim [n_nodes] zeroed by the caller.  Enqueued on the context's stream.
+enum stan_if_bits { IF_CONN = 1, IF_MAT = 2, IF_TYPE = 4, IF_DOF = 8, IF_RED = 16, IF_FACE = 32 };
+void stan_if_check_enqueue(stan_ctx *ctx, int64_t n_nodes, int64_t n_elem, int64_t n_dof, int32_t n_mat, const int32_t *d_conn,
+                           const int32_t *d_elem_mat, const uint8_t *d_elem_type, const int32_t *d_node_dof, const int32_t *d_red,
+                           int32_t *d_claim);
+
+// ---- loads.hip ------------------------------------------------------------------------------
+// Consistent nodal loads of body forces and face pressures, and the right-hand side for prescribed displacements
+// (stan_hip_load_vector_hex8); every array in device memory except mat_E_nu, mat_body and sums.  Checks its arguments on
+// the device before anything is indexed with them.  Synchronises the stream.
+int stan_load_vector_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const int32_t *d_node_dof, int64_t n_elem,
+                            const int32_t *d_conn, const int32_t *d_elem_mat, const uint8_t *d_elem_type, int32_t n_mat,
+                            const double *mat_E_nu, int64_t n_dof, const int32_t *d_red, const double *mat_body, int64_t n_faces,
+                            const int32_t *d_face_elem, const uint8_t *d_face_id, const double *d_face_pressure,
+                            const double *d_disp0, double *d_F, double *d_F_solve, double *d_load_full, stan_load_sums *sums);
 
 // ---- comm.cpp -------------------------------------------------------------------------------
 int stan_comm_allreduce_sum_f64(stan_ctx *ctx, double *d_buf, size_t count);

@@ -21,7 +21,6 @@
 namespace {
 
 constexpr int REC = 50;   // doubles per element record in LDS, as k_recover's (48 + 2: the records of a wave start 36 banks apart, 16-B aligned)
-constexpr int IF_CONN = 1, IF_MAT = 2, IF_TYPE = 4, IF_DOF = 8, IF_RED = 16;
 constexpr int NSUM = 11;  // reaction_sum[3], load_sum[3], fint_sum[3], residual^2, load^2
 constexpr long long NONE = 0x7fffffffffffffffLL;
 
@@ -261,6 +260,14 @@ k_if_finish(int64_t n_blocks, const double *__restrict__ partial, const long lon
 
 }  // namespace
 
+void stan_if_check_enqueue(stan_ctx *ctx, int64_t n_nodes, int64_t n_elem, int64_t n_dof, int32_t n_mat, const int32_t *d_conn,
+                           const int32_t *d_elem_mat, const uint8_t *d_elem_type, const int32_t *d_node_dof, const int32_t *d_red,
+                           int32_t *d_claim) {
+    const int64_t n_chk = n_elem * 8 > n_dof ? n_elem * 8 : n_dof;   // (n_dof = 3 n_nodes)
+    hipLaunchKernelGGL(k_if_check, dim3(nblk(n_chk, 256)), dim3(256), 0, ctx->stream, n_nodes, n_elem, n_dof, n_mat, d_conn,
+                       d_elem_mat, d_elem_type, d_node_dof, d_red, d_claim, ctx->d_status);
+}
+
 int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const double *d_disp,
                                 const int32_t *d_node_dof, int64_t n_elem, const int32_t *d_conn, const int32_t *d_elem_mat,
                                 const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
@@ -281,9 +288,7 @@ int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_
     int32_t *d_claim;
     STANCHK(tmp.alloc(&d_claim, (size_t)n_nodes));
     HIPCHK(ctx, hipMemsetAsync(d_claim, 0, (size_t)n_nodes * 4, st));
-    const int64_t n_chk = n_elem * 8 > n_dof ? n_elem * 8 : n_dof;   // (n_dof = 3 n_nodes)
-    hipLaunchKernelGGL(k_if_check, dim3(nblk(n_chk, 256)), dim3(256), 0, st, n_nodes, n_elem, n_dof, n_mat, d_conn, d_elem_mat,
-                       d_elem_type, d_node_dof, d_red, d_claim, status);
+    stan_if_check_enqueue(ctx, n_nodes, n_elem, n_dof, n_mat, d_conn, d_elem_mat, d_elem_type, d_node_dof, d_red, d_claim);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_ERRBITS, status + SS_ERRBITS, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, status + SS_AUX, 8, hipMemcpyDeviceToHost, st));

@@ -1,0 +1,349 @@
+// loads.hip -- the load vector of distributed loads and prescribed displacements:
+//   body force   f_a = b_m sum_{2x2x2} N_a(q) det J(q)            b_m a force per unit volume of material m; the 2x2x2 rule for
+//                                                                 HEX8_G1 elements too (exact: degree <= 3 per variable)
+//   pressure     f_a = -p sum_{2x2} N_a(q) n dA(q)                n dA = s (x_beta x x_gamma) on face (axis, s), (beta, gamma)
+//                                                                 the cyclic successors of the axis; unit weights, +-1/sqrt 3
+//   prescribed   F_solve = F - f_int(u0)|free                     u0 used at the fixed DOFs only (stan_internal_forces_device)
+// No J^-1 is formed for the first two: det J == 0 is no error there.  No counterpart in the reference.
+// Faces in CHEXA order:  0 xi=-1 {0,3,4,7}  1 xi=+1 {1,2,5,6}  2 eta=-1 {0,1,4,5}  3 eta=+1 {2,3,6,7}  4 zeta=-1 {0,1,2,3}
+// 5 zeta=+1 {4,5,6,7}; the face list is sorted by face_elem * 6 + face_id, strictly.
+// Phases, all bit-reproducible (no atomics on doubles):
+//   element pass  k_ld_elem: the layout of k_if_elem (8 lanes per element, lane g loads node g only, records 50 doubles apart
+//                 in LDS); body term first (lane g = Gauss point g, three butterfly stages), then the element's listed faces
+//                 in ascending face id (lanes 0..3 one face point each, lanes 4..7 add zero to the same butterfly); f_e leaves
+//                 node-major through LDS as full lines; a wave without any loaded element stores zeros and nothing else;
+//   lists         node -> (element, corner), all corners, ascending (stan_incidence_lists);
+//   node gather   k_ld_gather: one lane per node adds its list's entries in order and writes load_full, F, F_solve through
+//                 node_dof / the reduction map, with the block's partial sums; k_ld_finish adds the partials in block order.
+#include "internal.h"
+#include "hex8_device.h"
+
+namespace {
+
+constexpr int REC = 50;    // doubles per element record in LDS, as k_if_elem's
+constexpr int NGS = 6;     // gather sums: load_sum[3], free_sum[3]
+constexpr int NES = 2;     // element sums: volume, area
+constexpr double GL = 0.57735026918962576451;   // sqrt(1/3)
+
+// face list: element and face id in range, keys strictly ascending.  Reads the lists by position only.
+__global__ void __launch_bounds__(256)
+k_ld_check_faces(int64_t n_faces, int64_t n_elem, const int32_t *__restrict__ face_elem, const uint8_t *__restrict__ face_id,
+                 int64_t *status) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_faces) return;
+    const int64_t e = face_elem[t], f = face_id[t];
+    bool bad = e < 0 || e >= n_elem || f >= 6;
+    if (t > 0 && (int64_t)face_elem[t - 1] * 6 + face_id[t - 1] >= e * 6 + f) bad = true;
+    if (bad) atomicOr((unsigned long long *)&status[SS_ERRBITS], (unsigned long long)IF_FACE);
+}
+
+__device__ __forceinline__ void wave_sync() {   // wave-local exchange through LDS (as in k_if_elem)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// sums of the block's 256 lanes in a fixed order (six butterfly stages per wave, then the four waves in order) on thread 0
+template <int N>
+__device__ __forceinline__ void block_sums(double (&s)[N], double (*sh)[N]) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+        for (int k = 0; k < N; k++) s[k] += __shfl_xor(s[k], off, 64);
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < N; k++) sh[wv][k] = s[k];
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < 4; w++)
+#pragma unroll
+            for (int k = 0; k < N; k++) s[k] += sh[w][k];
+}
+
+// sum over the 8 lanes of an element (three butterfly stages: a fixed order)
+__device__ __forceinline__ double elem_sum(double v) {
+    v += __shfl_xor(v, 1, 64);
+    v += __shfl_xor(v, 2, 64);
+    v += __shfl_xor(v, 4, 64);
+    return v;
+}
+
+// ---- element pass: f_e [n_elem * 24], node-major; partial [gridDim.x * 2] = the block's volume and area ------------------
+__global__ void __launch_bounds__(256)
+k_ld_elem(int64_t n_elem, const double *__restrict__ xyz, const int32_t *__restrict__ conn, const int32_t *__restrict__ elem_mat,
+          const double *__restrict__ mat_body, int64_t n_faces, const int32_t *__restrict__ face_elem,
+          const uint8_t *__restrict__ face_id, const double *__restrict__ face_p, double *__restrict__ fe,
+          double *__restrict__ partial) {
+    __shared__ __attribute__((aligned(16))) double lds[4][8 * REC];
+    __shared__ double sh[4][NES];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int el = lane >> 3, g = lane & 7;
+    const int64_t e0 = ((int64_t)blockIdx.x * 4 + wv) * 8;   // first element of this wave
+    const int64_t e = e0 + el;
+    const bool valid = e < n_elem;
+    double b[3] = {0, 0, 0};
+    int64_t k0 = 0;          // first listed face of this element
+    unsigned fmask = 0;      // bit f: face f of this element is listed
+    if (valid) {
+        if (mat_body) {
+            const int32_t m = elem_mat[e];
+            b[0] = mat_body[3 * m]; b[1] = mat_body[3 * m + 1]; b[2] = mat_body[3 * m + 2];
+        }
+        if (n_faces > 0 && g == 0) {   // one lower-bound search per element for key e * 6 in the sorted keys (its lane 0)
+            int64_t lo = 0, hi = n_faces;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if ((int64_t)face_elem[mid] < e) lo = mid + 1; else hi = mid;
+            }
+            k0 = lo;
+            for (int64_t k = lo; k < n_faces && k < lo + 6 && (int64_t)face_elem[k] == e; k++) fmask |= 1u << face_id[k];
+        }
+    }
+    if (n_faces > 0) {   // lane 0 of the element hands its result to the other seven (all lanes active here)
+        k0 = __shfl(k0, lane & ~7, 64);
+        fmask = __shfl(fmask, lane & ~7, 64);
+    }
+    const bool has_body = b[0] != 0.0 || b[1] != 0.0 || b[2] != 0.0;
+    double mine[3] = {0, 0, 0}, acc[NES] = {0, 0};
+    if (__any(has_body || fmask != 0)) {   // wave-uniform: a wave without loads stores zeros and does nothing else
+        double *rec = lds[wv] + el * REC;
+        if (valid) {
+            const int64_t nd = conn[e * 8 + g];
+#pragma unroll
+            for (int c = 0; c < 3; c++) rec[3 * g + c] = xyz[3 * nd + c];
+        }
+        wave_sync();
+        if (__any(has_body)) {
+            // lane g: Gauss point g of the 2x2x2 rule, whatever the element's type
+            double w = 0.0;
+            const double px = hex8_sign(HEX8_SX, g) * GL, py = hex8_sign(HEX8_SY, g) * GL, pz = hex8_sign(HEX8_SZ, g) * GL;
+            if (valid && has_body) {
+                double J[9];
+                hex8_jacobian(rec, px, py, pz, J);
+                w = hex8_det3(J);
+                acc[0] = w;
+            }
+#pragma unroll
+            for (int a = 0; a < 8; a++) {
+                const double v = elem_sum(hex8_shape(a, px, py, pz) * w);   // sum_q N_a(q) det J(q)
+                if (a == g) { mine[0] = b[0] * v; mine[1] = b[1] * v; mine[2] = b[2] * v; }
+            }
+        }
+        for (int f = 0; f < 6; f++) {
+            const bool has = (fmask >> f) & 1u;
+            if (!__any(has)) continue;   // wave-uniform
+            // lanes 0..3 of the element: face point (bit 0 -> beta, bit 1 -> gamma); lanes 4..7 add zero
+            const int axis = f >> 1;
+            const double s = (f & 1) ? 1.0 : -1.0;
+            const double tb = (g & 1) ? GL : -GL, tg = (g & 2) ? GL : -GL;
+            const double px = axis == 0 ? s : (axis == 1 ? tg : tb);   // xi:   axis | gamma of eta  | beta of zeta
+            const double py = axis == 1 ? s : (axis == 2 ? tg : tb);   // eta:  axis | gamma of zeta | beta of xi
+            const double pz = axis == 2 ? s : (axis == 0 ? tg : tb);   // zeta: axis | gamma of xi   | beta of eta
+            double n[3] = {0, 0, 0}, p = 0.0;
+            if (valid && has && g < 4) {
+                double J[9];
+                hex8_jacobian(rec, px, py, pz, J);
+                // rows beta = axis + 1 and gamma = axis + 2 (mod 3) of J, picked by selects (no runtime-indexed array)
+                const double bx = axis == 0 ? J[3] : (axis == 1 ? J[6] : J[0]), cx = axis == 0 ? J[6] : (axis == 1 ? J[0] : J[3]);
+                const double by = axis == 0 ? J[4] : (axis == 1 ? J[7] : J[1]), cy = axis == 0 ? J[7] : (axis == 1 ? J[1] : J[4]);
+                const double bz = axis == 0 ? J[5] : (axis == 1 ? J[8] : J[2]), cz = axis == 0 ? J[8] : (axis == 1 ? J[2] : J[5]);
+                n[0] = s * (by * cz - bz * cy);
+                n[1] = s * (bz * cx - bx * cz);
+                n[2] = s * (bx * cy - by * cx);
+                acc[1] += sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+            }
+            if (valid && has) p = face_p[k0 + __popc(fmask & ((1u << f) - 1u))];
+#pragma unroll
+            for (int a = 0; a < 8; a++) {
+                const double Na = hex8_shape(a, px, py, pz);
+#pragma unroll
+                for (int c = 0; c < 3; c++) {
+                    const double v = elem_sum(Na * n[c]);   // sum_q N_a(q) n dA(q)
+                    if (a == g) mine[c] -= p * v;
+                }
+            }
+        }
+        wave_sync();   // every lane is done with the records
+    }
+    // the wave's 8 x 24 values are contiguous in memory: through LDS, out as three 512-B lines
+    double *stg = lds[wv];
+#pragma unroll
+    for (int c = 0; c < 3; c++) stg[lane * 3 + c] = mine[c];
+    wave_sync();
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const int idx = j * 64 + lane;
+        if (e0 + idx / 24 < n_elem) fe[e0 * 24 + idx] = stg[idx];
+    }
+    block_sums<NES>(acc, sh);
+    if (threadIdx.x == 0) {
+        partial[(int64_t)blockIdx.x * NES] = acc[0];
+        partial[(int64_t)blockIdx.x * NES + 1] = acc[1];
+    }
+}
+
+// ---- u0 masked to the fixed DOFs (entries at free DOFs count as 0) ------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_ld_mask(int64_t n_dof, const double *__restrict__ disp0, const int32_t *__restrict__ node_dof, const int32_t *__restrict__ red,
+          double *__restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;   // 3 * node + component
+    if (t < n_dof) out[t] = red[node_dof[t]] == -1 ? disp0[t] : 0.0;
+}
+
+// ---- node gather + the block's partial sums ----------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_ld_gather(int64_t n_nodes, const int64_t *__restrict__ ptr, const int32_t *__restrict__ list, const double *__restrict__ fe,
+            const int32_t *__restrict__ node_dof, const int32_t *__restrict__ red, int64_t n_red, const double *__restrict__ fint0,
+            double *F, double *F_solve, double *__restrict__ load_full, double *__restrict__ partial) {
+    __shared__ double sh[4][NGS];
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double s[NGS] = {0, 0, 0, 0, 0, 0};
+    if (n < n_nodes) {
+        double l[3] = {0.0, 0.0, 0.0};
+        const int64_t k0 = ptr[n], k1 = ptr[n + 1];
+        for (int64_t k = k0; k < k1; k++) {
+            const int64_t t = list[k];   // element * 8 + corner
+            l[0] += fe[3 * t]; l[1] += fe[3 * t + 1]; l[2] += fe[3 * t + 2];
+        }
+        const int64_t d0 = node_dof[3 * n];   // {d0, d0 + 1, d0 + 2}, no other node's (k_if_check)
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const int64_t d = d0 + c;
+            const int32_t r = red[d];
+            if (load_full) load_full[d] = l[c];
+            s[c] = l[c];
+            if (r == -1) continue;
+            s[3 + c] = l[c];
+            const int64_t j = d - r;
+            if (j >= n_red) continue;   // (a map that is not the count of fixed DOFs before d)
+            double v = l[c];
+            if (F) { v = F[j] + l[c]; F[j] = v; }
+            if (F_solve) F_solve[j] = fint0 ? v - fint0[d] : v;
+        }
+    }
+    block_sums<NGS>(s, sh);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < NGS; k++) partial[(int64_t)blockIdx.x * NGS + k] = s[k];
+}
+
+// one block: thread t adds the partials of blocks t, t + 256, ... in ascending order, then the block's fixed order
+__global__ void __launch_bounds__(256)
+k_ld_finish(int64_t n_gblocks, const double *__restrict__ gpartial, int64_t n_eblocks, const double *__restrict__ epartial,
+            double *out) {
+    __shared__ double sh[4][NGS + NES];
+    double a[NGS + NES];
+#pragma unroll
+    for (int k = 0; k < NGS + NES; k++) a[k] = 0.0;
+    for (int64_t b = threadIdx.x; b < n_gblocks; b += 256)
+#pragma unroll
+        for (int k = 0; k < NGS; k++) a[k] += gpartial[b * NGS + k];
+    for (int64_t b = threadIdx.x; b < n_eblocks; b += 256)
+#pragma unroll
+        for (int k = 0; k < NES; k++) a[NGS + k] += epartial[b * NES + k];
+    block_sums<NGS + NES>(a, sh);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < NGS + NES; k++) out[k] = a[k];
+}
+
+}  // namespace
+
+int stan_load_vector_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const int32_t *d_node_dof, int64_t n_elem,
+                            const int32_t *d_conn, const int32_t *d_elem_mat, const uint8_t *d_elem_type, int32_t n_mat,
+                            const double *mat_E_nu, int64_t n_dof, const int32_t *d_red, const double *mat_body, int64_t n_faces,
+                            const int32_t *d_face_elem, const uint8_t *d_face_id, const double *d_face_pressure,
+                            const double *d_disp0, double *d_F, double *d_F_solve, double *d_load_full, stan_load_sums *sums) {
+    auto bad = [&](const char *why, int rc) { ctx->err = std::string("load_vector_hex8: ") + why; return rc; };
+    if (n_nodes <= 0 || n_elem < 0 || n_mat <= 0 || n_dof != n_nodes * 3) return bad("n_dof must be 3 n_nodes > 0, n_mat > 0", STAN_E_ARG);
+    if (n_elem >= (int64_t)1 << 28) return bad("more than 2^28 elements", STAN_E_ARG);
+    if (n_dof > 0x7fffffffLL) return bad("more than 2^31 DOFs", STAN_E_ARG);
+    if (n_faces < 0 || n_faces > n_elem * 6) return bad("n_faces outside [0, 6 n_elem]", STAN_E_ARG);
+    if (!mat_body && n_faces == 0 && !d_disp0) return bad("no body force, no face and no prescribed displacement", STAN_E_ARG);
+    if (!d_F && !d_F_solve && !d_load_full && !sums) return bad("none of F / F_solve / load_full / sums asked for", STAN_E_ARG);
+    if (d_disp0 && !d_F_solve) return bad("disp0 without F_solve", STAN_E_ARG);
+    hipStream_t st = ctx->stream;
+    ctx->prof_loads_ms[0] = ctx->prof_loads_ms[1] = ctx->prof_loads_ms[2] = 0;
+    // ---- the checks, before anything is indexed with the caller's integers
+    int64_t *status = ctx->d_status;
+    const long long init[3] = {0, 0x7fffffffffffffffLL, 0};
+    HIPCHK(ctx, hipMemcpyAsync(status + SS_ERRBITS, &init[0], 8, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(status + SS_BAD_ELEM, &init[1], 16, hipMemcpyHostToDevice, st));   // SS_BAD_ELEM, SS_AUX
+    dev_scope tmp(ctx);
+    int32_t *d_claim;
+    STANCHK(tmp.alloc(&d_claim, (size_t)n_nodes));
+    HIPCHK(ctx, hipMemsetAsync(d_claim, 0, (size_t)n_nodes * 4, st));
+    stan_if_check_enqueue(ctx, n_nodes, n_elem, n_dof, n_mat, d_conn, d_elem_mat, d_elem_type, d_node_dof, d_red, d_claim);
+    if (n_faces > 0)
+        hipLaunchKernelGGL(k_ld_check_faces, dim3(nblk(n_faces, 256)), dim3(256), 0, st, n_faces, n_elem, d_face_elem, d_face_id, status);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_ERRBITS, status + SS_ERRBITS, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, status + SS_AUX, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const int64_t bits = ctx->h_status[SS_ERRBITS], n_fixed = ctx->h_status[SS_AUX];
+    if (bits & IF_DOF) return bad("Node.DOF is not {3i,3i+1,3i+2} with 3i < n_dof, or two nodes share one (Node.cs:218-223)", STAN_E_DOF_LAYOUT);
+    if (bits & IF_CONN) return bad("node index out of range", STAN_E_ARG);
+    if (bits & IF_MAT) return bad("elem_mat out of range", STAN_E_ARG);
+    if (bits & IF_TYPE) return bad("element type is neither HEX8_G1 nor HEX8_G2", STAN_E_ARG);
+    if (bits & IF_RED) return bad("ndof_reduction entry outside -1 / [0, i]", STAN_E_ARG);
+    if (bits & IF_FACE) return bad("face list: element or face id out of range, or face_elem * 6 + face_id not strictly ascending", STAN_E_ARG);
+    const int64_t n_red = n_dof - n_fixed;
+
+    // ---- prescribed displacements first: f_int(u0 at the fixed DOFs), an error of it leaves every output untouched
+    double *d_fint0 = nullptr;
+    if (d_disp0) {
+        double *d_u0;
+        STANCHK(tmp.alloc(&d_u0, (size_t)n_dof));
+        STANCHK(tmp.alloc(&d_fint0, (size_t)n_dof));
+        hipLaunchKernelGGL(k_ld_mask, dim3(nblk(n_dof, 256)), dim3(256), 0, st, n_dof, d_disp0, d_node_dof, d_red, d_u0);
+        HIPCHK(ctx, hipGetLastError());
+        STANCHK(stan_internal_forces_device(ctx, n_nodes, d_xyz, d_u0, d_node_dof, n_elem, d_conn, d_elem_mat, d_elem_type, n_mat,
+                                            mat_E_nu, n_dof, d_red, nullptr, d_fint0, nullptr, nullptr));
+    }
+
+    event_bag evs;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // profiling: element pass | lists | gather + reductions
+    if (ctx->profiling)
+        for (hipEvent_t &e : ev) e = evs.make();
+    const int64_t n_gblocks = nblk(n_nodes, 256), n_eblocks = nblk(n_elem, 32);
+    double *d_body = nullptr, *d_fe, *d_gpartial, *d_epartial, *d_out;
+    STANCHK(tmp.alloc(&d_fe, (size_t)(n_elem > 0 ? n_elem : 1) * 24));
+    STANCHK(tmp.alloc(&d_gpartial, (size_t)n_gblocks * NGS));
+    STANCHK(tmp.alloc(&d_epartial, (size_t)(n_eblocks > 0 ? n_eblocks : 1) * NES));
+    STANCHK(tmp.alloc(&d_out, (size_t)NGS + NES));
+    if (mat_body) {
+        STANCHK(tmp.alloc(&d_body, (size_t)n_mat * 3));
+        HIPCHK(ctx, hipMemcpyAsync(d_body, mat_body, (size_t)n_mat * 24, hipMemcpyHostToDevice, st));
+    }
+    if (ev[0]) HIPCHK(ctx, hipEventRecord(ev[0], st));
+    if (n_elem > 0)   // 8 lanes per element, 8 elements per wave, 32 per workgroup
+        hipLaunchKernelGGL(k_ld_elem, dim3((unsigned)n_eblocks), dim3(256), 0, st, n_elem, d_xyz, d_conn, d_elem_mat, d_body, n_faces,
+                           d_face_elem, d_face_id, d_face_pressure, d_fe, d_epartial);
+    if (ev[1]) HIPCHK(ctx, hipEventRecord(ev[1], st));
+    int64_t *d_ptr;
+    int32_t *d_list;
+    STANCHK(stan_incidence_lists(ctx, tmp, n_nodes, n_elem, d_conn, true, &d_ptr, &d_list));
+    if (ev[2]) HIPCHK(ctx, hipEventRecord(ev[2], st));
+    hipLaunchKernelGGL(k_ld_gather, dim3((unsigned)n_gblocks), dim3(256), 0, st, n_nodes, d_ptr, d_list, d_fe, d_node_dof, d_red, n_red,
+                       d_fint0, d_F, d_F_solve, d_load_full, d_gpartial);
+    if (sums) hipLaunchKernelGGL(k_ld_finish, dim3(1), dim3(256), 0, st, n_gblocks, d_gpartial, n_eblocks, d_epartial, d_out);
+    if (ev[3]) HIPCHK(ctx, hipEventRecord(ev[3], st));
+    HIPCHK(ctx, hipGetLastError());
+    double out[NGS + NES];
+    if (sums) HIPCHK(ctx, hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));   // the temporaries go back to the context behind the kernels
+    if (ctx->profiling) {
+        float ms = 0;
+        for (int k = 0; k < 3; k++) {
+            HIPCHK(ctx, hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+            ctx->prof_loads_ms[k] = ms;
+        }
+    }
+    if (sums) {
+        for (int c = 0; c < 3; c++) { sums->load_sum[c] = out[c]; sums->free_sum[c] = out[3 + c]; }
+        sums->volume = out[NGS];
+        sums->area = out[NGS + 1];
+        sums->n_fixed = n_fixed;
+        sums->n_faces = n_faces;
+    }
+    return STAN_OK;
+}

@@ -51,6 +51,7 @@ EXPORTS = [
     "stan_hip_recover_hex8_keep", "stan_hip_results_map", "stan_hip_results_free",
     "stan_hip_result_scalars_hex8", "stan_hip_results_scalars",
     "stan_hip_internal_forces_hex8", "stan_hip_internal_forces_hex8_dev",
+    "stan_hip_load_vector_hex8", "stan_hip_load_vector_hex8_dev", "stan_hip_load_vector_times",
 ]
 # only in the lab build (stan_amd/csrc/lab/stan_hip_lab.h, selected with STAN_HIP_LIB)
 LAB_EXPORTS = ["stan_hip_csr_spmv_bench", "stan_hip_lab_placement_map", "stan_hip_lab_placement_variants", "stan_hip_lab_placement_alloc", "stan_hip_lab_placement_rounds", "stan_hip_lab_placement_cross", "stan_hip_lab_incg_penalty", "stan_hip_lab_placement_vecalloc", "stan_hip_lab_placement_vecshape", "stan_hip_lab_pairing_pmc"]
@@ -88,6 +89,15 @@ class Equilibrium(C.Structure):
     _fields_ = [("reaction_sum", C.c_double * 3), ("load_sum", C.c_double * 3), ("fint_sum", C.c_double * 3),
                 ("residual_norm2", C.c_double), ("load_norm2", C.c_double), ("residual_max", C.c_double),
                 ("residual_max_dof", C.c_int64), ("n_fixed", C.c_int64)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k.endswith("_sum") else getattr(self, k)) for k, _ in self._fields_}
+
+
+class LoadSums(C.Structure):
+    """stan_load_sums (include/stan_hip.h)"""
+    _fields_ = [("load_sum", C.c_double * 3), ("free_sum", C.c_double * 3), ("volume", C.c_double), ("area", C.c_double),
+                ("n_fixed", C.c_int64), ("n_faces", C.c_int64)]
 
     def as_dict(self):
         return {k: (list(getattr(self, k)) if k.endswith("_sum") else getattr(self, k)) for k, _ in self._fields_}
@@ -369,6 +379,73 @@ class Context:
             C.c_int32(mat_E_nu.shape[0]), _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _dev(d_red, C.c_int32),
             opt(d_F), opt(d_f_int), opt(d_reaction), C.byref(q) if eq else None))
         return q
+
+    # -- distributed loads and prescribed displacements -----------------------------------------
+    def load_vector_hex8(self, xyz, node_dof, conn, elem_mat, elem_type, mat_E_nu, red, mat_body=None, face_elem=None,
+                         face_id=None, face_pressure=None, disp0=None, F=None, F_solve=None, load_full=True, sums=True):
+        """stan_hip_load_vector_hex8 from host arrays: (F, F_solve, load_full, sums LoadSums).  mat_body [n_mat, 3] or None;
+        the face list (face_elem, face_id, face_pressure) sorted by face_elem * 6 + face_id, or None; disp0 [n_nodes, 3] or
+        None.  F: the reduced load vector to add to (a copy is returned) or None; F_solve: True / False, default = disp0
+        given.  An output not asked for is None."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        node_dof = np.ascontiguousarray(node_dof, dtype=np.int32)
+        conn = np.ascontiguousarray(conn, dtype=np.int32).reshape(-1, 8)
+        elem_mat = np.ascontiguousarray(elem_mat, dtype=np.int32)
+        elem_type = np.ascontiguousarray(elem_type, dtype=np.uint8)
+        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        red = np.ascontiguousarray(red, dtype=np.int32)
+        n_dof = red.shape[0]
+        N = n_dof - int((red == -1).sum())
+        mb = None if mat_body is None else np.ascontiguousarray(mat_body, dtype=np.float64).reshape(-1, 3)
+        if mb is not None and mb.shape[0] != mat_E_nu.shape[0]:
+            raise ValueError("load_vector_hex8: mat_body must be [n_mat, 3]")
+        fe = None if face_elem is None else np.ascontiguousarray(face_elem, dtype=np.int32).reshape(-1)
+        fi = None if face_elem is None else np.ascontiguousarray(face_id, dtype=np.uint8).reshape(-1)
+        fp = None if face_elem is None else np.ascontiguousarray(face_pressure, dtype=np.float64).reshape(-1)
+        nf = 0 if fe is None else fe.shape[0]
+        if fe is not None and not (fi.shape[0] == fp.shape[0] == nf):
+            raise ValueError("load_vector_hex8: face_elem, face_id, face_pressure must have one length")
+        u0 = None if disp0 is None else np.ascontiguousarray(disp0, dtype=np.float64)
+        if u0 is not None and u0.size != xyz.size:
+            raise ValueError("load_vector_hex8: disp0 must be [n_nodes, 3]")
+        Fo = None if F is None else np.array(F, dtype=np.float64).reshape(-1)
+        if Fo is not None and Fo.shape[0] != N:
+            raise ValueError("load_vector_hex8: F must be [n_dof - n_fixed]")
+        if F_solve is None:
+            F_solve = u0 is not None
+        Fs = np.zeros(N) if F_solve else None
+        lf = np.zeros(n_dof) if load_full else None
+        q = LoadSums() if sums else None
+        self._chk(self.lib.stan_hip_load_vector_hex8(
+            self.h, C.c_int64(xyz.shape[0]), _ptr(xyz, C.c_double), _ptr(node_dof, C.c_int32), C.c_int64(conn.shape[0]),
+            _ptr(conn, C.c_int32), _ptr(elem_mat, C.c_int32), _ptr(elem_type, C.c_uint8), C.c_int32(mat_E_nu.shape[0]),
+            _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _ptr(red, C.c_int32), _ptr(mb, C.c_double), C.c_int64(nf),
+            _ptr(fe, C.c_int32), _ptr(fi, C.c_uint8), _ptr(fp, C.c_double), _ptr(u0, C.c_double), _ptr(Fo, C.c_double),
+            _ptr(Fs, C.c_double), _ptr(lf, C.c_double), C.byref(q) if sums else None))
+        return Fo, Fs, lf, q
+
+    def load_vector_hex8_dev(self, n_nodes, d_xyz, d_node_dof, n_elem, d_conn, d_elem_mat, d_elem_type, mat_E_nu, n_dof, d_red,
+                             mat_body=None, n_faces=0, d_face_elem=None, d_face_id=None, d_face_pressure=None, d_disp0=None,
+                             d_F=None, d_F_solve=None, d_load_full=None, sums=True):
+        """All d_* are device pointers (ints, e.g. torch tensor.data_ptr()) or None; mat_body a host array or None.
+        Returns the LoadSums (None when not asked for)."""
+        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        mb = None if mat_body is None else np.ascontiguousarray(mat_body, dtype=np.float64).reshape(-1, 3)
+        q = LoadSums() if sums else None
+        opt = lambda p, t=C.c_double: None if p is None else _dev(p, t)
+        self._chk(self.lib.stan_hip_load_vector_hex8_dev(
+            self.h, C.c_int64(n_nodes), _dev(d_xyz, C.c_double), _dev(d_node_dof, C.c_int32), C.c_int64(n_elem),
+            _dev(d_conn, C.c_int32), _dev(d_elem_mat, C.c_int32), _dev(d_elem_type, C.c_uint8), C.c_int32(mat_E_nu.shape[0]),
+            _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _dev(d_red, C.c_int32), _ptr(mb, C.c_double), C.c_int64(n_faces),
+            opt(d_face_elem, C.c_int32), opt(d_face_id, C.c_uint8), opt(d_face_pressure), opt(d_disp0), opt(d_F),
+            opt(d_F_solve), opt(d_load_full), C.byref(q) if sums else None))
+        return q
+
+    def load_vector_times(self):
+        """dict(loads_elem_ms, loads_list_ms, loads_gather_ms) of the last load-vector call (profiling enabled)."""
+        ms = (C.c_double * 3)()
+        self._chk(self.lib.stan_hip_load_vector_times(self.h, ms))
+        return dict(loads_elem_ms=ms[0], loads_list_ms=ms[1], loads_gather_ms=ms[2])
 
     # -- assembly ------------------------------------------------------------------------
     def assemble_hex8(self, xyz, node_dof, conn, elem_mat, elem_type, mat_E_nu, red):

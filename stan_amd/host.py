@@ -165,6 +165,33 @@ def partition_elements(node_index, conn, nranks, rank):
     return out[:n.value].copy()
 
 
+# ---- distributed loads: the pressure faces of a node set -------------------------------------------
+EXPORTS += ["stan_host_pressure_faces"]
+
+
+def pressure_faces(n_nodes, conn, set_nodes, set_p, capacity=None):
+    """stan_host_pressure_faces -> (face_elem int32[], face_id uint8[], face_p float64[]) ascending by face_elem * 6 +
+    face_id: the faces all of whose corners are in the node set, interior and collapsed (< 3 distinct nodes) faces left
+    out.  capacity: the size of the arrays of the second call (default: what the first call reports)."""
+    conn = np.ascontiguousarray(conn, dtype=np.int32).reshape(-1, 8)
+    set_nodes = np.ascontiguousarray(set_nodes, dtype=np.int32).reshape(-1)
+    set_p = np.ascontiguousarray(set_p, dtype=np.float64).reshape(-1)
+    if set_nodes.shape[0] != set_p.shape[0]:
+        raise ValueError("pressure_faces: set_nodes and set_p must have one length")
+    n = C.c_int64(0)
+    args = (C.c_int64(n_nodes), C.c_int64(conn.shape[0]), _p(conn, C.c_int32), C.c_int64(set_nodes.shape[0]),
+            _p(set_nodes, C.c_int32), _p(set_p, C.c_double))
+    rc = load().stan_host_pressure_faces(*args, C.c_int64(0), None, None, None, C.byref(n))
+    if rc:
+        raise StanHostError(rc, "pressure_faces")
+    cap = n.value if capacity is None else int(capacity)
+    fe, fi, fp = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1))
+    rc = load().stan_host_pressure_faces(*args, C.c_int64(cap), _p(fe, C.c_int32), _p(fi, C.c_uint8), _p(fp, C.c_double), C.byref(n))
+    if rc:
+        raise StanHostError(rc, "pressure_faces")
+    return fe[:n.value].copy(), fi[:n.value].copy(), fp[:n.value].copy()
+
+
 # ---- result scalars: names + .vtu export (Part.Load_Scalar / Part.ExportGrid) -------------------
 EXPORTS += ["stan_host_scalar_name", "stan_host_write_vtu"]
 N_SCALARS = 24
@@ -208,7 +235,7 @@ EXPORTS += [
     "stan_host_db_assign_part", "stan_host_db_add_bc", "stan_host_db_set_analysis",
     "stan_host_db_sizes", "stan_host_db_get_analysis", "stan_host_db_assign_dof",
     "stan_host_db_get_flat", "stan_host_db_get_reduction", "stan_host_db_set_results",
-    "stan_host_db_get_results",
+    "stan_host_db_get_results", "stan_host_db_get_distributed_loads",
 ]
 
 
@@ -354,6 +381,23 @@ class Db:
         self._chk(self.lib.stan_host_db_get_reduction(self.h, _p(red, C.c_int32), C.byref(nfix),
                                                       _p(F, C.c_double)), "get_reduction")
         return red, int(nfix.value), F[:ndof - nfix.value].copy()
+
+    def distributed_loads(self):
+        """BuildDistributedLoads: dict(any, mat_body [n_mat, 3] or None, face_elem, face_id, face_p (or None), disp0
+        [n_nodes, 3] or None, n_prescribed) from the "Pressure" / "BodyForce" / "Displacement" BCs (needs assign_dof)."""
+        cnt = (C.c_int64 * 4)()
+        self._chk(self.lib.stan_host_db_get_distributed_loads(self.h, cnt, C.c_int32(0), None, C.c_int64(0), None, None, None,
+                                                              None), "distributed_loads")
+        nm, nf, nn = int(cnt[1]), int(cnt[2]), self.sizes()["nodes"]
+        mb = np.zeros((max(nm, 1), 3))
+        fe, fi, fp = np.zeros(max(nf, 1), np.int32), np.zeros(max(nf, 1), np.uint8), np.zeros(max(nf, 1))
+        u0 = np.zeros((nn, 3))
+        self._chk(self.lib.stan_host_db_get_distributed_loads(
+            self.h, cnt, C.c_int32(mb.shape[0]), _p(mb, C.c_double), C.c_int64(fe.shape[0]), _p(fe, C.c_int32),
+            _p(fi, C.c_uint8), _p(fp, C.c_double), _p(u0, C.c_double)), "distributed_loads")
+        return dict(any=bool(cnt[0]), mat_body=mb[:nm] if nm else None, face_elem=fe[:nf] if nf else None,
+                    face_id=fi[:nf] if nf else None, face_p=fp[:nf] if nf else None,
+                    disp0=u0 if np.any(u0) else None, n_prescribed=int(cnt[3]))
 
     def set_results(self, disp, strain=None, stress=None):
         disp = np.ascontiguousarray(disp, dtype=np.float64)

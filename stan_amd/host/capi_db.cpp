@@ -1,4 +1,5 @@
 // capi_db.cpp -- C-ABI over the STAN_Database mirror (include/stan_host.h, stan_db part).
+#include <algorithm>
 #include <cstring>
 
 #include "../../include/stan_host.h"
@@ -131,7 +132,7 @@ int stan_host_db_add_bc(stan_db *d, int32_t id, const char *name, const char *ty
     bc.Type = type; bc.has_type = true;
     bc.ID = id; bc.ColorID = id % 9;
     for (int64_t i = 0; i < n; i++) {
-        if (!d->db.NodeLib.ContainsKey(node_ids[i])) continue;  // BoundaryCondition.cs:89
+        if (bc.Type != "BodyForce" && !d->db.NodeLib.ContainsKey(node_ids[i])) continue;  // BoundaryCondition.cs:89 (a BodyForce is keyed by material IDs)
         MatrixST v(3, 1);
         v.M[0] = vals[3 * i]; v.M[1] = vals[3 * i + 1]; v.M[2] = vals[3 * i + 2];
         if (!bc.NodalValues.Add(node_ids[i], v)) { d->err = "BC lists node " + std::to_string(node_ids[i]) + " twice (Dictionary.Add throws)"; return STAN_HOST_E_ARG; }
@@ -210,6 +211,39 @@ int stan_host_db_get_reduction(stan_db *d, int32_t *red, int64_t *n_fixed, doubl
     if (rc) return rc;
     if (red) memcpy(red, r.data(), r.size() * 4);
     if (F) memcpy(F, f.data(), f.size() * 8);
+    return STAN_HOST_OK;
+}
+
+int stan_host_db_get_distributed_loads(stan_db *d, int64_t counts[4], int32_t cap_mat, double *mat_body, int64_t cap_faces,
+                                       int32_t *face_elem, uint8_t *face_id, double *face_p, double *disp0) {
+    if (!d || !counts) return STAN_HOST_E_ARG;
+    FlatModel f;
+    int rc = Flatten(d->db, &f, &d->err);
+    if (rc) return rc;
+    std::vector<int32_t> red;
+    std::vector<double> F;
+    int64_t n_fixed = 0;
+    rc = BuildReductionAndLoads(d->db, &red, &n_fixed, &F, &d->err);
+    if (rc) return rc;
+    DistributedLoads dl;
+    rc = BuildDistributedLoads(d->db, f, red, &dl, &d->err);
+    if (rc) return rc;
+    counts[0] = dl.any; counts[1] = (int64_t)(dl.mat_body.size() / 3); counts[2] = (int64_t)dl.face_elem.size();
+    counts[3] = dl.n_prescribed;
+    if (mat_body) {
+        if ((int64_t)cap_mat < counts[1]) { d->err = "mat_body buffer too small"; return STAN_HOST_E_ARG; }
+        std::copy(dl.mat_body.begin(), dl.mat_body.end(), mat_body);
+    }
+    if (face_elem || face_id || face_p) {
+        if (!face_elem || !face_id || !face_p || cap_faces < counts[2]) { d->err = "face buffers too small"; return STAN_HOST_E_ARG; }
+        std::copy(dl.face_elem.begin(), dl.face_elem.end(), face_elem);
+        std::copy(dl.face_id.begin(), dl.face_id.end(), face_id);
+        std::copy(dl.face_p.begin(), dl.face_p.end(), face_p);
+    }
+    if (disp0) {
+        std::fill(disp0, disp0 + f.xyz.size(), 0.0);
+        std::copy(dl.disp0.begin(), dl.disp0.end(), disp0);
+    }
     return STAN_HOST_OK;
 }
 

@@ -19,7 +19,9 @@
 // (after the solve: support reactions and applied load by axis, the out-of-balance norm of F - f_int(U) against |F| and the
 // largest out-of-balance force with its node, from stan_hip_internal_forces_hex8 -- no step of the reference, nothing of it
 // reaches the STdb; with --json an "equilibrium" object, with --vtu the point arrays "Reaction Force X / Y / Z"; one device
-// only).
+// only).  A file whose BCLib holds the Types "Pressure", "BodyForce" or "Displacement" (loads.cpp; the reference ignores them)
+// gets their consistent nodal loads from stan_hip_load_vector_hex8: a block "Distributed loads:", the solve with
+// F - f_int(u0), u0 written into the displacements at the fixed DOFs, a "loads" object with --json; one device only.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -151,6 +153,10 @@ int main(int argc, char **argv) {
         int64_t n_fixed = 0;
         t0 = clk::now();
         if (BuildReductionAndLoads(DB, &nDOF_reduction, &n_fixed, &F, &err)) return fail("boundary conditions", err);
+        const bool dist_loads = HasDistributedLoads(DB);
+        if (dist_loads && devices.size() > 1)
+            return fail("boundary conditions", "Pressure / BodyForce / Displacement work on one device: the load vector adds up all "
+                                               "elements at a node, and a multi-device handle holds them in chunks (drop --gpus/--devices)");
         t_bc = secs(t0);
         const int64_t n_nodes = (int64_t)DB.NodeLib.Count();
 
@@ -160,18 +166,39 @@ int main(int argc, char **argv) {
         stan_matrix_info minfo;
         stan_hip_matrix_info(K.K, &minfo);
 
+        // distributed loads: F becomes the whole external load, F_solve the right-hand side (F - f_int(u0) on the free DOFs)
+        DistributedLoads dl;
+        stan_load_sums lsum{};
+        std::vector<double> F_rhs;
+        double t_loads = 0;
+        if (dist_loads) {
+            const auto tl = clk::now();
+            if (BuildDistributedLoads(DB, K.flat, nDOF_reduction, &dl, &err)) return fail("boundary conditions", err);
+            if (dl.mat_body.empty() && dl.face_elem.empty() && dl.disp0.empty()) {   // such BCs, but nothing in them (a Pressure
+                F_rhs = F;                                                           // set that forms no boundary face, an empty
+                lsum.n_fixed = n_fixed;                                              // BodyForce): the block with zeros
+            } else Functions.Load_Vector(K, nDOF_reduction, dl, &F, &F_rhs, &lsum);
+            t_loads = secs(tl);
+            printf("   Distributed loads:\n");
+            printf("     Total:              X %14.6e   Y %14.6e   Z %14.6e\n", lsum.load_sum[0], lsum.load_sum[1], lsum.load_sum[2]);
+            printf("     On free DOFs:       X %14.6e   Y %14.6e   Z %14.6e\n", lsum.free_sum[0], lsum.free_sum[1], lsum.free_sum[2]);
+            printf("     Loaded volume: %.6e   loaded area: %.6e (%lld faces)   prescribed DOFs: %lld\n", lsum.volume, lsum.area,
+                   (long long)lsum.n_faces, (long long)dl.n_prescribed);
+        }
+        const std::vector<double> &F_solve = dist_loads ? F_rhs : F;
+
         std::vector<double> U((size_t)(DB.nDOF - n_fixed), 0.0);
         const std::string &ls = DB.AnalysisLib.LinSolver;
         if (ls == "CG") {  // Solver.cs:162
-            U = Functions.LinearSolver_CG(K, F, DB.AnalysisLib);
+            U = Functions.LinearSolver_CG(K, F_solve, DB.AnalysisLib);
             printf("   CG iterations: %d, scaled relative residual %.3e\n", Functions.last_iterations,
                    Functions.last_rel_residual);
         } else if (ls == "Cholesky") {  // Solver.cs:163: CPU fallback, outside the GPU hot path (direct.cpp)
             if (devices.size() > 1) return fail("solver selection", "the direct solvers run on one device's export of K: drop --gpus/--devices");
-            U = Functions.LinearSolver_Cholesky(K, F);
+            U = Functions.LinearSolver_Cholesky(K, F_solve);
         } else if (ls == "LU") {        // Solver.cs:164
             if (devices.size() > 1) return fail("solver selection", "the direct solvers run on one device's export of K: drop --gpus/--devices");
-            U = Functions.LinearSolver_LU(K, F);
+            U = Functions.LinearSolver_LU(K, F_solve);
         }  // any other string: the reference leaves U = 0 (Solver.cs:160-164)
         t_hot = secs(t0);   // flatten + context + upload + assembly + solve + download
 
@@ -182,6 +209,9 @@ int main(int argc, char **argv) {
         parallel_ranges(disp.size(), [&](size_t a, size_t b) {
             for (size_t k = a; k < b; k++) disp[k] = Ufull[(size_t)K.flat.node_dof[k]];
         });
+        if (!dl.disp0.empty())   // the supports' own displacement, before recovery, reactions, .vtu and the export
+            for (size_t k = 0; k < disp.size(); k++)
+                if (nDOF_reduction[(size_t)K.flat.node_dof[k]] == -1) disp[k] = dl.disp0[k];
         t_disp = secs(t0);
 
         printf("   Stress recovery: ");  // Solver.cs:183
@@ -270,11 +300,12 @@ int main(int argc, char **argv) {
                    "\"host_threads\": %d, \"t_wall_s\": %.3f, \"t_device_assembly_plus_cg_s\": %.4f, "
                    "\"phases_s\": {\"read_parse\": %.3f, \"assign_dof\": %.3f, \"bc_tables\": %.3f, "
                    "\"flatten_upload_assemble_solve\": %.3f, \"displacements\": %.3f, \"stress_recovery\": %.3f, "
-                   "\"store_results\": %.3f, \"serialize_write\": %.3f, \"result_scalars\": %.3f, \"write_vtu\": %.3f}",
+                   "\"store_results\": %.3f, \"serialize_write\": %.3f, \"result_scalars\": %.6f, \"write_vtu\": %.6f}",
                    devices.size() > 1 ? (int)devices.size() : 1, DB.nDOF, (long long)minfo.n_reduced, (long long)minfo.n_blocks, Functions.last_iterations,
                    Functions.last_termination_type, Functions.last_rel_residual, Functions.last_assembly_s,
                    Functions.last_cg_s, spmv_ms, spmv_ms > 0 ? pr.spmv_bytes / spmv_ms / 1e6 : 0.0,
                    spmv_ms > 0 ? pr.spmv_bytes / spmv_ms / 1e6 / 8000.0 : 0.0,
+                   // (the two .vtu phases to the microsecond: on a small model they take less than the 0.5 ms that %.3f shows as 0)
                    HostThreads(), wall, dev, t_read, t_dof, t_bc, t_hot, t_disp, t_recover, t_store, t_write, t_scalars, t_vtu);
             if (reactions)   // %.17g: the doubles round-trip
                 printf(", \"equilibrium\": {\"reaction_sum\": [%.17g, %.17g, %.17g], \"load_sum\": [%.17g, %.17g, %.17g], "
@@ -283,6 +314,11 @@ int main(int argc, char **argv) {
                        eq.reaction_sum[0], eq.reaction_sum[1], eq.reaction_sum[2], eq.load_sum[0], eq.load_sum[1], eq.load_sum[2],
                        eq.fint_sum[0], eq.fint_sum[1], eq.fint_sum[2], eq.residual_norm2, eq.load_norm2, eq.residual_max,
                        (long long)eq.residual_max_dof, (long long)eq.n_fixed, t_react);
+            if (dist_loads)
+                printf(", \"loads\": {\"load_sum\": [%.17g, %.17g, %.17g], \"free_sum\": [%.17g, %.17g, %.17g], \"volume\": %.17g, "
+                       "\"area\": %.17g, \"n_faces\": %lld, \"n_fixed\": %lld, \"n_prescribed\": %lld, \"t_s\": %.3f}",
+                       lsum.load_sum[0], lsum.load_sum[1], lsum.load_sum[2], lsum.free_sum[0], lsum.free_sum[1], lsum.free_sum[2],
+                       lsum.volume, lsum.area, (long long)lsum.n_faces, (long long)lsum.n_fixed, (long long)dl.n_prescribed, t_loads);
             printf("}\n");
         }
         return 0;

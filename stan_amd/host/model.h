@@ -318,4 +318,24 @@ int Flatten(const Database &db, FlatModel *out, std::string *err);
 int BuildReductionAndLoads(const Database &db, std::vector<int32_t> *red, int64_t *n_fixed,
                            std::vector<double> *F, std::string *err);
 
+// ---- distributed loads (loads.cpp; no counterpart in the reference) ---------------------------
+// The BoundaryCondition Types "Pressure" (node IDs -> component 0 = p), "BodyForce" (MATERIAL IDs -> force per unit volume;
+// several such BCs add up) and "Displacement" (node IDs -> prescribed components, applied on DOFs an SPC fixes; a non-zero
+// component on a free DOF is an error, a zero one is ignored) as the flat arrays stan_hip_load_vector_hex8 takes.
+struct DistributedLoads {
+    bool any = false;                  // the file holds at least one such BC
+    std::vector<double> mat_body;      // [n_mat*3] in the material order of FlatModel, or empty
+    std::vector<int32_t> face_elem;    // the canonical face list (ascending elem * 6 + face), or empty
+    std::vector<uint8_t> face_id;
+    std::vector<double> face_p;
+    std::vector<double> disp0;         // [n_nodes*3] NodeLib order, or empty
+    int64_t n_prescribed = 0;          // fixed DOFs with a non-zero prescribed value
+};
+bool HasDistributedLoads(const Database &db);
+int BuildDistributedLoads(const Database &db, const FlatModel &flat, const std::vector<int32_t> &red, DistributedLoads *out,
+                          std::string *err);
+// faces all of whose corners are in the node set; see stan_host_pressure_faces
+void PressureFaces(int64_t n_elem, const int32_t *conn, const std::vector<uint8_t> &in_set, const std::vector<double> &node_p,
+                   std::vector<int32_t> *face_elem, std::vector<uint8_t> *face_id, std::vector<double> *face_p);
+
 }  // namespace stan

@@ -195,6 +195,19 @@ void SolverFunctions::Equilibrium(SparseMatrixHandle &K, const std::vector<doubl
         throw std::runtime_error(stan_hip_last_error(K.ctx));
 }
 
+void SolverFunctions::Load_Vector(SparseMatrixHandle &K, const std::vector<int32_t> &red, const DistributedLoads &dl,
+                                  std::vector<double> *F, std::vector<double> *F_solve, stan_load_sums *sums) const {
+    const FlatModel &f = K.flat;
+    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
+    F_solve->assign(F->size(), 0.0);
+    if (stan_hip_load_vector_hex8(K.ctx, n_nodes, f.xyz.data(), f.node_dof.data(), n_elem, f.conn.data(), f.elem_mat.data(),
+                                  f.elem_type.data(), (int32_t)(f.mat_E_nu.size() / 2), f.mat_E_nu.data(), (int64_t)red.size(),
+                                  red.data(), dl.mat_body.empty() ? nullptr : dl.mat_body.data(), (int64_t)dl.face_elem.size(),
+                                  dl.face_elem.data(), dl.face_id.data(), dl.face_p.data(),
+                                  dl.disp0.empty() ? nullptr : dl.disp0.data(), F->data(), F_solve->data(), nullptr, sums))
+        throw std::runtime_error(stan_hip_last_error(K.ctx));
+}
+
 void SolverFunctions::Recovery_Stress_Keep(SparseMatrixHandle &K, const std::vector<double> &dU) const {
     const FlatModel &f = K.flat;
     const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();

@@ -91,6 +91,11 @@ class SolverFunctions {
     void Equilibrium(SparseMatrixHandle &K, const std::vector<double> &nodal_dU, const std::vector<double> &F,
                      const std::vector<int32_t> &nDOF_reduction, std::vector<double> *f_int, std::vector<double> *reaction,
                      stan_equilibrium *eq) const;
+    // Distributed loads and prescribed displacements (stan_hip_load_vector_hex8; no step of the reference): adds the
+    // consistent nodal loads of `dl` to the reduced external load F (in place) and leaves in *F_solve the right-hand side
+    // of the reduced system, F - f_int(u0)|free; *sums always filled.  One device only.
+    void Load_Vector(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const DistributedLoads &dl,
+                     std::vector<double> *F, std::vector<double> *F_solve, stan_load_sums *sums) const;
     // "name,name,..." of --vtu-results -> indices (stan_host_scalar_name's strings; empty text = all 24); false + *err on an unknown name
     static bool ParseScalarNames(const std::string &text, std::vector<int32_t> *sel, std::string *err);
 
