@@ -1,7 +1,9 @@
 """Meshes the reference accepts and the assembly's fast paths do not cover (Database.cs:149-176, SolverFunctions.cs:143-173,
 Node.cs:202-205 bound neither the elements at a node nor repeats in NList): collapsed hexes, solids of revolution with a
 high-valence axis, star meshes, thousands of incidences at one node -- in both assembly modes, sharded, and through
-stress recovery."""
+stress recovery.  K_TOL is the fixed bar against the oracle; the conditioning-aware bar (entrywise, in units of an
+extended-precision reference's rounding scale, k_numeric_wide and the colour scatter included) lives in
+tests/test_gpu_element_precision.py / tests/element_ref.py."""
 import json
 import os
 import subprocess

@@ -2,7 +2,9 @@
 seeded inputs, plus size-independent properties at larger sizes.
 
 Bars: DOF / CSR indexing bit-exact; K values <= 1e-13 relative to max|K| (fp64, different
-summation order than MatrixST); displacements <= 1e-6 relative (BASELINE.json north_star)."""
+summation order than MatrixST); displacements <= 1e-6 relative (BASELINE.json north_star).
+The conditioning-aware bar on the element math (entrywise, in units of the reference's rounding scale, on elements far from
+the origin, stretched, thin and nearly incompressible) lives in tests/test_gpu_element_precision.py / tests/element_ref.py."""
 import os
 
 import numpy as np
