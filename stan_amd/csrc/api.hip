@@ -20,6 +20,45 @@ struct dbuf {  // RAII device buffer filled from host memory
     }
     int alloc(stan_ctx *ctx, size_t n) { owner = ctx; return stan_dmalloc(ctx, &p, n); }
 };
+
+// the device copies of a mesh's host arrays; an array the entry does not have (a null pointer) is skipped and stays null
+struct mesh_dbufs {
+    dbuf<double> xyz, disp;
+    dbuf<int32_t> node_dof, conn, elem_mat, red;
+    dbuf<uint8_t> elem_type;
+    int upload(stan_ctx *ctx, int64_t n_nodes, const double *h_xyz, const double *h_disp, const int32_t *h_node_dof, int64_t n_elem,
+               const int32_t *h_conn, const int32_t *h_elem_mat, const uint8_t *h_elem_type, int64_t n_dof, const int32_t *h_red) {
+        if (h_xyz) STANCHK(xyz.upload(ctx, h_xyz, (size_t)n_nodes * 3));
+        if (h_disp) STANCHK(disp.upload(ctx, h_disp, (size_t)n_nodes * 3));
+        if (h_node_dof) STANCHK(node_dof.upload(ctx, h_node_dof, (size_t)n_nodes * 3));
+        if (h_conn) STANCHK(conn.upload(ctx, h_conn, (size_t)n_elem * 8));
+        if (h_elem_mat) STANCHK(elem_mat.upload(ctx, h_elem_mat, (size_t)n_elem));
+        if (h_elem_type) STANCHK(elem_type.upload(ctx, h_elem_type, (size_t)n_elem));
+        if (h_red) STANCHK(red.upload(ctx, h_red, (size_t)n_dof));
+        return STAN_OK;
+    }
+};
+
+// host range checks of a mesh's integers, in element order: material, type (with_type), the 8 nodes; then node_dof when
+// given.  "<who>: <what>", with " at element N" appended when at_element.
+int mesh_range_check(stan_ctx *ctx, const char *who, bool at_element, bool with_type, int64_t n_nodes, int64_t n_elem,
+                     const int32_t *conn, const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat, int64_t n_dof,
+                     const int32_t *node_dof) {
+    auto bad = [&](const char *why, int64_t e, int rc) {
+        ctx->err = std::string(who) + ": " + why + (at_element && e >= 0 ? " at element " + std::to_string(e) : std::string());
+        return rc;
+    };
+    for (int64_t e = 0; e < n_elem; e++) {
+        if (elem_mat[e] < 0 || elem_mat[e] >= n_mat) return bad("elem_mat out of range", e, STAN_E_ARG);
+        if (with_type && elem_type[e] != STAN_HEX8_G1 && elem_type[e] != STAN_HEX8_G2) return bad("unsupported element type", e, STAN_E_ARG);
+        for (int a = 0; a < 8; a++)
+            if (conn[e * 8 + a] < 0 || conn[e * 8 + a] >= n_nodes) return bad("node index out of range", e, STAN_E_ARG);
+    }
+    if (node_dof)
+        for (int64_t k = 0; k < n_dof; k++)
+            if (node_dof[k] < 0 || node_dof[k] >= n_dof) return bad("DOF out of range", -1, STAN_E_DOF_LAYOUT);
+    return STAN_OK;
+}
 }  // namespace
 
 void stan_set_global_error(const std::string &msg) { g_err = msg; }
@@ -450,20 +489,12 @@ int stan_hip_recover_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz, con
         return stan_group_recover(ctx, n_nodes, xyz, disp, n_elem, conn, elem_mat, elem_type, n_mat, mat_E_nu,
                                   strain, stress);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    for (int64_t e = 0; e < n_elem; e++) {
-        if (elem_mat[e] < 0 || elem_mat[e] >= n_mat) { ctx->err = "recover_hex8: elem_mat out of range"; return STAN_E_ARG; }
-        for (int a = 0; a < 8; a++)
-            if (conn[e * 8 + a] < 0 || conn[e * 8 + a] >= n_nodes) { ctx->err = "recover_hex8: node index out of range"; return STAN_E_ARG; }
-    }
-    dbuf<double> dx, du, de, ds; dbuf<int32_t> dc, dm; dbuf<uint8_t> dt;
-    STANCHK(dx.upload(ctx, xyz, (size_t)n_nodes * 3));
-    STANCHK(du.upload(ctx, disp, (size_t)n_nodes * 3));
-    STANCHK(dc.upload(ctx, conn, (size_t)n_elem * 8));
-    STANCHK(dm.upload(ctx, elem_mat, (size_t)n_elem));
-    STANCHK(dt.upload(ctx, elem_type, (size_t)n_elem));
+    STANCHK(mesh_range_check(ctx, "recover_hex8", false, false, n_nodes, n_elem, conn, elem_mat, elem_type, n_mat, 0, nullptr));
+    mesh_dbufs m; dbuf<double> de, ds;
+    STANCHK(m.upload(ctx, n_nodes, xyz, disp, nullptr, n_elem, conn, elem_mat, elem_type, 0, nullptr));
     STANCHK(de.alloc(ctx, (size_t)n_elem * 48));
     STANCHK(ds.alloc(ctx, (size_t)n_elem * 48));
-    STANCHK(stan_recover_device(ctx, n_nodes, dx.p, du.p, n_elem, dc.p, dm.p, dt.p, n_mat, mat_E_nu,
+    STANCHK(stan_recover_device(ctx, n_nodes, m.xyz.p, m.disp.p, n_elem, m.conn.p, m.elem_mat.p, m.elem_type.p, n_mat, mat_E_nu,
                                 de.p, ds.p, nullptr, nullptr, nullptr));
     if (n_elem) {
         HIPCHK(ctx, hipMemcpyAsync(strain, de.p, (size_t)n_elem * 48 * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -492,17 +523,9 @@ int recover_keep_one(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const do
                      const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat, const double *mat_E_nu, int64_t e_base,
                      stan_results::part *out) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    for (int64_t e = 0; e < n_elem; e++) {
-        if (elem_mat[e] < 0 || elem_mat[e] >= n_mat) { ctx->err = "recover_hex8: elem_mat out of range"; return STAN_E_ARG; }
-        for (int a = 0; a < 8; a++)
-            if (conn[e * 8 + a] < 0 || conn[e * 8 + a] >= n_nodes) { ctx->err = "recover_hex8: node index out of range"; return STAN_E_ARG; }
-    }
-    dbuf<double> dx, du; dbuf<int32_t> dc, dm; dbuf<uint8_t> dt;
-    STANCHK(dx.upload(ctx, xyz, (size_t)n_nodes * 3));
-    STANCHK(du.upload(ctx, disp, (size_t)n_nodes * 3));
-    STANCHK(dc.upload(ctx, conn, (size_t)n_elem * 8));
-    STANCHK(dm.upload(ctx, elem_mat, (size_t)n_elem));
-    STANCHK(dt.upload(ctx, elem_type, (size_t)n_elem));
+    STANCHK(mesh_range_check(ctx, "recover_hex8", false, false, n_nodes, n_elem, conn, elem_mat, elem_type, n_mat, 0, nullptr));
+    mesh_dbufs m;
+    STANCHK(m.upload(ctx, n_nodes, xyz, disp, nullptr, n_elem, conn, elem_mat, elem_type, 0, nullptr));
     // plain device memory, owned by the results object (it may outlive the context's pool)
     double *de = nullptr, *ds = nullptr;
     const size_t bytes = (size_t)(n_elem > 0 ? n_elem : 1) * 48 * 8;
@@ -526,7 +549,8 @@ int recover_keep_one(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const do
             return STAN_E_ALLOC;
         }
     }
-    int rc = stan_recover_device(ctx, n_nodes, dx.p, du.p, n_elem, dc.p, dm.p, dt.p, n_mat, mat_E_nu, de, ds, nullptr, nullptr, nullptr);
+    int rc = stan_recover_device(ctx, n_nodes, m.xyz.p, m.disp.p, n_elem, m.conn.p, m.elem_mat.p, m.elem_type.p, n_mat, mat_E_nu, de, ds,
+                                 nullptr, nullptr, nullptr);
     if (rc == STAN_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = STAN_E_HIP;
     if (rc != STAN_OK) { hipFree(de); hipFree(ds); return rc; }
     *out = stan_results::part{ctx->device, e_base, e_base + n_elem, de, ds};
@@ -690,27 +714,16 @@ int stan_hip_nodal_forces_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz
                                               mat_E_nu, n_dof, elem_forces, R);
         });
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    for (int64_t e = 0; e < n_elem; e++) {
-        if (elem_mat[e] < 0 || elem_mat[e] >= n_mat) { ctx->err = "nodal_forces_hex8: elem_mat out of range"; return STAN_E_ARG; }
-        for (int a = 0; a < 8; a++)
-            if (conn[e * 8 + a] < 0 || conn[e * 8 + a] >= n_nodes) { ctx->err = "nodal_forces_hex8: node index out of range"; return STAN_E_ARG; }
-    }
-    for (int64_t k = 0; k < n_dof; k++)
-        if (node_dof[k] < 0 || node_dof[k] >= n_dof) { ctx->err = "nodal_forces_hex8: DOF out of range"; return STAN_E_DOF_LAYOUT; }
-    dbuf<double> dx, du, df, dR; dbuf<int32_t> dc, dm, dd; dbuf<uint8_t> dt;
-    STANCHK(dx.upload(ctx, xyz, (size_t)n_nodes * 3));
-    STANCHK(du.upload(ctx, disp, (size_t)n_nodes * 3));
-    STANCHK(dd.upload(ctx, node_dof, (size_t)n_nodes * 3));
-    STANCHK(dc.upload(ctx, conn, (size_t)n_elem * 8));
-    STANCHK(dm.upload(ctx, elem_mat, (size_t)n_elem));
-    STANCHK(dt.upload(ctx, elem_type, (size_t)n_elem));
+    STANCHK(mesh_range_check(ctx, "nodal_forces_hex8", false, false, n_nodes, n_elem, conn, elem_mat, elem_type, n_mat, n_dof, node_dof));
+    mesh_dbufs m; dbuf<double> df, dR;
+    STANCHK(m.upload(ctx, n_nodes, xyz, disp, node_dof, n_elem, conn, elem_mat, elem_type, 0, nullptr));
     if (elem_forces) STANCHK(df.alloc(ctx, (size_t)n_elem * 24));
     if (R) {
         STANCHK(dR.alloc(ctx, (size_t)n_dof));
         HIPCHK(ctx, hipMemsetAsync(dR.p, 0, (size_t)n_dof * 8, ctx->stream));
     }
-    STANCHK(stan_recover_device(ctx, n_nodes, dx.p, du.p, n_elem, dc.p, dm.p, dt.p, n_mat, mat_E_nu,
-                                nullptr, nullptr, dd.p, elem_forces ? df.p : nullptr, R ? dR.p : nullptr));
+    STANCHK(stan_recover_device(ctx, n_nodes, m.xyz.p, m.disp.p, n_elem, m.conn.p, m.elem_mat.p, m.elem_type.p, n_mat, mat_E_nu,
+                                nullptr, nullptr, m.node_dof.p, elem_forces ? df.p : nullptr, R ? dR.p : nullptr));
     if (elem_forces && n_elem)
         HIPCHK(ctx, hipMemcpyAsync(elem_forces, df.p, (size_t)n_elem * 24 * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (R) HIPCHK(ctx, hipMemcpyAsync(R, dR.p, (size_t)n_dof * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -759,29 +772,17 @@ int stan_hip_internal_forces_hex8(stan_ctx *ctx, int64_t n_nodes, const double *
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // the checks of stan_hip_nodal_forces_hex8, with the element named (the device repeats them for the _dev entry)
-    for (int64_t e = 0; e < n_elem; e++) {
-        if (elem_mat[e] < 0 || elem_mat[e] >= n_mat) { ctx->err = "internal_forces_hex8: elem_mat out of range at element " + std::to_string(e); return STAN_E_ARG; }
-        if (elem_type[e] != STAN_HEX8_G1 && elem_type[e] != STAN_HEX8_G2) { ctx->err = "internal_forces_hex8: unsupported element type at element " + std::to_string(e); return STAN_E_ARG; }
-        for (int a = 0; a < 8; a++)
-            if (conn[e * 8 + a] < 0 || conn[e * 8 + a] >= n_nodes) { ctx->err = "internal_forces_hex8: node index out of range at element " + std::to_string(e); return STAN_E_ARG; }
-    }
-    for (int64_t k = 0; k < n_dof; k++)
-        if (node_dof[k] < 0 || node_dof[k] >= n_dof) { ctx->err = "internal_forces_hex8: DOF out of range"; return STAN_E_DOF_LAYOUT; }
+    STANCHK(mesh_range_check(ctx, "internal_forces_hex8", true, true, n_nodes, n_elem, conn, elem_mat, elem_type, n_mat, n_dof, node_dof));
     int64_t n_fixed = 0;
     for (int64_t k = 0; k < n_dof; k++) n_fixed += red[k] == -1;
     const size_t N = (size_t)(n_dof - n_fixed);
-    dbuf<double> dx, du, dF, dfi, dre; dbuf<int32_t> dc, dm, dd, dr; dbuf<uint8_t> dt;
-    STANCHK(dx.upload(ctx, xyz, (size_t)n_nodes * 3));
-    STANCHK(du.upload(ctx, disp, (size_t)n_nodes * 3));
-    STANCHK(dd.upload(ctx, node_dof, (size_t)n_nodes * 3));
-    STANCHK(dc.upload(ctx, conn, (size_t)n_elem * 8));
-    STANCHK(dm.upload(ctx, elem_mat, (size_t)n_elem));
-    STANCHK(dt.upload(ctx, elem_type, (size_t)n_elem));
-    STANCHK(dr.upload(ctx, red, (size_t)n_dof));
+    mesh_dbufs m; dbuf<double> dF, dfi, dre;
+    STANCHK(m.upload(ctx, n_nodes, xyz, disp, node_dof, n_elem, conn, elem_mat, elem_type, n_dof, red));
     if (F) STANCHK(dF.upload(ctx, F, N));
     if (f_int) STANCHK(dfi.alloc(ctx, (size_t)n_dof));
     if (reaction) STANCHK(dre.alloc(ctx, (size_t)n_dof));
-    const int rc = stan_internal_forces_device(ctx, n_nodes, dx.p, du.p, dd.p, n_elem, dc.p, dm.p, dt.p, n_mat, mat_E_nu, n_dof, dr.p,
+    const int rc = stan_internal_forces_device(ctx, n_nodes, m.xyz.p, m.disp.p, m.node_dof.p, n_elem, m.conn.p, m.elem_mat.p, m.elem_type.p,
+                                               n_mat, mat_E_nu, n_dof, m.red.p,
                                                F ? dF.p : nullptr, f_int ? dfi.p : nullptr, reaction ? dre.p : nullptr, (stan_equilibrium *)eq);
     if (rc == STAN_OK) {
         if (f_int) HIPCHK(ctx, hipMemcpyAsync(f_int, dfi.p, (size_t)n_dof * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -830,24 +831,19 @@ int stan_hip_load_vector_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz,
     int64_t n_fixed = 0;
     for (int64_t k = 0; k < n_dof; k++) n_fixed += red[k] == -1;
     const size_t N = (size_t)(n_dof - n_fixed);
-    dbuf<double> dx, dp, du, dF, dFs, dl; dbuf<int32_t> dc, dm, dd, dr, dfe; dbuf<uint8_t> dt, dfi;
-    STANCHK(dx.upload(ctx, xyz, (size_t)n_nodes * 3));
-    STANCHK(dd.upload(ctx, node_dof, (size_t)n_nodes * 3));
-    STANCHK(dc.upload(ctx, conn, (size_t)n_elem * 8));
-    STANCHK(dm.upload(ctx, elem_mat, (size_t)n_elem));
-    STANCHK(dt.upload(ctx, elem_type, (size_t)n_elem));
-    STANCHK(dr.upload(ctx, red, (size_t)n_dof));
+    mesh_dbufs m; dbuf<double> dp, dF, dFs, dl; dbuf<int32_t> dfe; dbuf<uint8_t> dfi;
+    STANCHK(m.upload(ctx, n_nodes, xyz, nullptr, node_dof, n_elem, conn, elem_mat, elem_type, n_dof, red));
     if (n_faces > 0) {
         STANCHK(dfe.upload(ctx, face_elem, (size_t)n_faces));
         STANCHK(dfi.upload(ctx, face_id, (size_t)n_faces));
         STANCHK(dp.upload(ctx, face_pressure, (size_t)n_faces));
     }
-    if (disp0) STANCHK(du.upload(ctx, disp0, (size_t)n_nodes * 3));
+    if (disp0) STANCHK(m.disp.upload(ctx, disp0, (size_t)n_nodes * 3));
     if (F) STANCHK(dF.upload(ctx, F, N));
     if (F_solve) STANCHK(dFs.alloc(ctx, N));
     if (load_full) STANCHK(dl.alloc(ctx, (size_t)n_dof));
-    const int rc = stan_load_vector_device(ctx, n_nodes, dx.p, dd.p, n_elem, dc.p, dm.p, dt.p, n_mat, mat_E_nu, n_dof, dr.p, mat_body,
-                                           n_faces, dfe.p, dfi.p, dp.p, disp0 ? du.p : nullptr, F ? dF.p : nullptr,
+    const int rc = stan_load_vector_device(ctx, n_nodes, m.xyz.p, m.node_dof.p, n_elem, m.conn.p, m.elem_mat.p, m.elem_type.p, n_mat,
+                                           mat_E_nu, n_dof, m.red.p, mat_body, n_faces, dfe.p, dfi.p, dp.p, m.disp.p, F ? dF.p : nullptr,
                                            F_solve ? dFs.p : nullptr, load_full ? dl.p : nullptr, (stan_load_sums *)sums);
     if (rc == STAN_OK) {
         if (F && N) HIPCHK(ctx, hipMemcpyAsync(F, dF.p, N * 8, hipMemcpyDeviceToHost, ctx->stream));

@@ -427,12 +427,14 @@ int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_
                                 const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
                                 const int32_t *d_red, const double *d_F, double *d_fint, double *d_reaction,
                                 stan_equilibrium *eq);
-// Its argument check (k_if_check), shared with loads.hip: status[SS_ERRBITS] |= IF_*, status[SS_AUX] += fixed DOFs, both
-// reset by the caller; d_claim [n_nodes] zeroed by the caller.  Enqueued on the context's stream.
+// Its argument check, shared with loads.hip: resets the status words, runs k_if_check (and k_ld_check_faces when
+// n_faces > 0) with a zeroed claim array out of `tmp`, synchronises, and turns the first IF_* bit raised -- tested in the
+// order DOF, CONN, MAT, TYPE, RED, FACE -- into "<who>: <what>" and its return code; *n_fixed = the fixed DOFs of the map.
 enum stan_if_bits { IF_CONN = 1, IF_MAT = 2, IF_TYPE = 4, IF_DOF = 8, IF_RED = 16, IF_FACE = 32 };
-void stan_if_check_enqueue(stan_ctx *ctx, int64_t n_nodes, int64_t n_elem, int64_t n_dof, int32_t n_mat, const int32_t *d_conn,
-                           const int32_t *d_elem_mat, const uint8_t *d_elem_type, const int32_t *d_node_dof, const int32_t *d_red,
-                           int32_t *d_claim);
+int stan_elem_args_check(stan_ctx *ctx, dev_scope &tmp, const char *who, int64_t n_nodes, int64_t n_elem, int64_t n_dof,
+                         int32_t n_mat, const int32_t *d_conn, const int32_t *d_elem_mat, const uint8_t *d_elem_type,
+                         const int32_t *d_node_dof, const int32_t *d_red, int64_t n_faces, const int32_t *d_face_elem,
+                         const uint8_t *d_face_id, int64_t *n_fixed);
 
 // ---- loads.hip ------------------------------------------------------------------------------
 // Consistent nodal loads of body forces and face pressures, and the right-hand side for prescribed displacements
@@ -537,6 +539,34 @@ struct dev_scope {
         if (rc == STAN_OK) p.push_back((void *)*q);
         return rc;
     }
+};
+// the events around a call's phases: mark(k) records event k on the context's stream, read(a, b, &ms) after the stream is
+// synchronised; with profiling off no event is created, mark does nothing and read leaves *ms alone
+struct phase_timer {
+    stan_ctx *ctx;
+    event_bag evs;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    phase_timer(stan_ctx *c, int n_marks) : ctx(c) {   // n_marks <= 5
+        for (int k = 0; ctx->profiling && k < n_marks; k++) ev[k] = evs.make();
+    }
+    int mark(int k) {
+        if (ev[k]) HIPCHK(ctx, hipEventRecord(ev[k], ctx->stream));
+        return STAN_OK;
+    }
+    int read(int a, int b, double *ms) {
+        float t = 0;
+        if (!ctx->profiling) return STAN_OK;
+        HIPCHK(ctx, hipEventElapsedTime(&t, ev[a], ev[b]));
+        *ms = t;
+        return STAN_OK;
+    }
+};
+// lambda and G of every material (stan_lame) in a temporary of `tmp`; the object outlives the stream's copy (recovery.hip)
+struct lamG_buf {
+    std::vector<double> host;
+    double *d = nullptr;
+    int alloc(dev_scope &tmp, int32_t n_mat, const double *mat_E_nu);
+    hipError_t upload(hipStream_t st) const { return hipMemcpyAsync(d, host.data(), host.size() * 8, hipMemcpyHostToDevice, st); }
 };
 // the det J == 0 report of the element kernels (the caller has copied h_status[SS_BAD_ELEM] back and synchronised)
 static inline int stan_detj_check(stan_ctx *ctx, const char *why) {

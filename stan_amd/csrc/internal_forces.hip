@@ -6,21 +6,18 @@
 //   (SolverFunctions.cs:143-173); reaction = f_int on the fixed DOFs; residual = F - f_int on the free ones.
 // Nothing here forms K, reads the sparse layout or scales: the result is an independent witness of assembly and solve.
 // Three phases, all bit-reproducible (no atomics on doubles):
-//   element pass  k_if_elem: 8 lanes per element, one per Gauss point (the layout of k_recover: lane g loads node g only,
-//                 the element's record goes round through LDS, 50 doubles apart); the 8 Gauss-point terms of a node's force
-//                 are added by three butterfly stages, f_e leaves node-major through LDS as full lines;
+//   element pass  k_if_elem: 8 lanes per element, one per Gauss point (the layout of elem_pass.h); the 8 Gauss-point terms
+//                 of a node's force are added by three butterfly stages, f_e leaves node-major through LDS as full lines;
 //   lists         node -> (element, corner), all corners, ascending (stan_incidence_lists, scalars.hip);
 //   node gather   k_if_gather: one lane per node adds its list's entries in order, writes f_int and reaction through
 //                 node_dof and forms the block's partial sums of stan_equilibrium in a fixed order; one block finishes
 //                 them in block order (the pattern of the CG's reductions).
 // The arguments are checked ON THE DEVICE before anything is indexed with them (k_if_check), so the host-pointer entry
 // and the device-pointer entry share every check.
-#include "internal.h"
-#include "hex8_device.h"
+#include "elem_pass.h"
 
 namespace {
 
-constexpr int REC = 50;   // doubles per element record in LDS, as k_recover's (48 + 2: the records of a wave start 36 banks apart, 16-B aligned)
 constexpr int NSUM = 11;  // reaction_sum[3], load_sum[3], fint_sum[3], residual^2, load^2
 constexpr long long NONE = 0x7fffffffffffffffLL;
 
@@ -57,43 +54,42 @@ k_if_check(int64_t n_nodes, int64_t n_elem, int64_t n_dof, int32_t n_mat, const 
     if (nfix) atomicAdd((unsigned long long *)&status[SS_AUX], nfix);
 }
 
-__device__ __forceinline__ void wave_sync() {   // wave-local exchange through LDS (as in k_recover)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+// face list (the load vector's): element and face id in range, keys strictly ascending.  Reads the lists by position only.
+__global__ void __launch_bounds__(256)
+k_ld_check_faces(int64_t n_faces, int64_t n_elem, const int32_t *__restrict__ face_elem, const uint8_t *__restrict__ face_id,
+                 int64_t *status) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_faces) return;
+    const int64_t e = face_elem[t], f = face_id[t];
+    bool bad = e < 0 || e >= n_elem || f >= 6;
+    if (t > 0 && (int64_t)face_elem[t - 1] * 6 + face_id[t - 1] >= e * 6 + f) bad = true;
+    if (bad) atomicOr((unsigned long long *)&status[SS_ERRBITS], (unsigned long long)IF_FACE);
 }
 
 // ---- element pass: f_e [n_elem * 24], node-major ------------------------------------------------------------------------
+// Lane mapping, record load, Gauss point and the staged store are elem_pass.h's.  The strain / stress loop and the B^T sum
+// repeat hex8_strain, hex8_stress and elem_bt_sum word for word: with the helpers called here the backend fuses other
+// products of these sums into FMAs (equal opcode counts, other operands) and f_e, so f_int, changes in its last bits.
 __global__ void __launch_bounds__(256)
 k_if_elem(int64_t n_elem, const double *__restrict__ xyz, const double *__restrict__ disp, const int32_t *__restrict__ conn,
           const int32_t *__restrict__ elem_mat, const uint8_t *__restrict__ elem_type, const double *__restrict__ mat_lamG,
           double *__restrict__ fe, long long *bad_elem) {
-    __shared__ __attribute__((aligned(16))) double lds[4][8 * REC];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int el = lane >> 3, g = lane & 7;
-    const int64_t e0 = ((int64_t)blockIdx.x * 4 + wv) * 8;   // first element of this wave
-    const int64_t e = e0 + el;
-    const bool valid = e < n_elem;
-    double *rec = lds[wv] + el * REC;
+    __shared__ __attribute__((aligned(16))) double lds[4][8 * ELEM_REC];
+    const elem_lanes L = elem_lanes_here(n_elem);
+    double *rec = lds[L.wv] + L.el * ELEM_REC;
     int type = STAN_HEX8_G2;
-    if (valid) {
-        type = elem_type[e];
-        const int64_t nd = conn[e * 8 + g];
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            rec[3 * g + c] = xyz[3 * nd + c];
-            rec[24 + 3 * g + c] = disp[3 * nd + c];
-        }
+    if (L.valid) {
+        type = elem_type[L.e];
+        elem_load_node<true>(rec, L, conn, xyz, disp);
     }
     wave_sync();
     double o[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, sig[6] = {0, 0, 0, 0, 0, 0}, px = 0, py = 0, pz = 0, sc = 0;
-    if (valid) {
-        const double *u = rec + 24;   // coordinates [0, 24), displacements [24, 48)
+    if (L.valid) {
         // HEX8_G1: every lane evaluates the one point (location 0); its weight is 8 on lane 0 and 0 on the others
-        const double det = hex8_gp_setup(rec, type, g, o);
-        if (det == 0.0) atomicMin(bad_elem, (long long)e);
-        const double gl = hex8_gauss_loc(type);
-        px = hex8_sign(HEX8_SX, g) * gl; py = hex8_sign(HEX8_SY, g) * gl; pz = hex8_sign(HEX8_SZ, g) * gl;
+        const double det = hex8_gp_setup(rec, type, L.g, o);
+        if (det == 0.0) atomicMin(bad_elem, (long long)L.e);
+        hex8_gauss_point(type, L.g, px, py, pz);
+        const double *u = rec + 24;
         double eps[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int i = 0; i < 8; i++) {
@@ -107,7 +103,7 @@ k_if_elem(int64_t n_elem, const double *__restrict__ xyz, const double *__restri
             eps[4] += gr[2] * u[3 * i + 1] + gr[1] * u[3 * i + 2];
             eps[5] += gr[2] * u[3 * i] + gr[0] * u[3 * i + 2];
         }
-        const int32_t m = elem_mat[e];
+        const int32_t m = elem_mat[L.e];
         const double lam = mat_lamG[2 * m], G = mat_lamG[2 * m + 1];
         const double tr = lam * (eps[0] + eps[1] + eps[2]);
         sig[0] = tr + 2 * G * eps[0];
@@ -116,8 +112,8 @@ k_if_elem(int64_t n_elem, const double *__restrict__ xyz, const double *__restri
         sig[3] = G * eps[3]; sig[4] = G * eps[4]; sig[5] = G * eps[5];
         sc = det == 0.0 ? 0.0 : o[9];   // det J_g * w (a singular point is reported, its term left out)
     }
-    // lane g: B_g^T sig_g * det J_g w for node a, then the sum over the 8 lanes of the element (three butterfly stages: a
-    // fixed order); node a's three components end up on lane a
+    // lane g: B_g^T sig_g * det J_g w for node a, then the sum over the 8 lanes of the element; node a's three components
+    // end up on lane a
     double mine[3] = {0, 0, 0};
 #pragma unroll
     for (int a = 0; a < 8; a++) {
@@ -129,24 +125,12 @@ k_if_elem(int64_t n_elem, const double *__restrict__ xyz, const double *__restri
         f[2] = (gr[2] * sig[2] + gr[1] * sig[4] + gr[0] * sig[5]) * sc;
 #pragma unroll
         for (int c = 0; c < 3; c++) {
-            double v = f[c];
-            v += __shfl_xor(v, 1, 64);
-            v += __shfl_xor(v, 2, 64);
-            v += __shfl_xor(v, 4, 64);
-            if (a == g) mine[c] = v;
+            const double v = elem_sum(f[c]);
+            if (a == L.g) mine[c] = v;
         }
     }
-    // the wave's 8 x 24 values are contiguous in memory: through LDS, out as three 512-B lines
-    double *stg = lds[wv];
     wave_sync();   // every lane is done with the records
-#pragma unroll
-    for (int c = 0; c < 3; c++) stg[lane * 3 + c] = mine[c];
-    wave_sync();
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const int idx = j * 64 + lane;
-        if (e0 + idx / 24 < n_elem) fe[e0 * 24 + idx] = stg[idx];
-    }
+    elem_store_staged<3, false>(lds[L.wv], L, n_elem, mine, fe);   // three 512-B lines per wave
 }
 
 // ---- node gather + the block's partial sums ----------------------------------------------------------------------------
@@ -158,30 +142,23 @@ struct eq_acc {
 __device__ __forceinline__ void acc_max(double &mx, long long &dof, double omx, long long odof) {
     if (omx > mx || (omx == mx && odof < dof)) { mx = omx; dof = odof; }
 }
-// sums of the block's 256 lanes in a fixed order (six butterfly stages per wave, then the four waves in order) on thread 0
-__device__ __forceinline__ void block_sums(eq_acc &a, double (*sh)[NSUM + 1], long long *shd) {
+// the block's 256 lanes on thread 0: the sums by block_sums; the maximum and its lowest DOF (whatever the order) by a
+// butterfly of their own, the waves' results published by the barrier inside block_sums
+struct eq_shared {
+    double s[4][NSUM + 1];   // a wave's sums, then its maximum
+    long long dof[4];
+};
+__device__ __forceinline__ void eq_block_reduce(eq_acc &a, eq_shared &sh) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < NSUM; k++) a.s[k] += __shfl_xor(a.s[k], off, 64);
         const double omx = __shfl_xor(a.mx, off, 64);
         const long long odof = __shfl_xor(a.dof, off, 64);
         acc_max(a.mx, a.dof, omx, odof);
     }
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < NSUM; k++) sh[wv][k] = a.s[k];
-        sh[wv][NSUM] = a.mx;
-        shd[wv] = a.dof;
-    }
-    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { sh.s[threadIdx.x >> 6][NSUM] = a.mx; sh.dof[threadIdx.x >> 6] = a.dof; }
+    block_sums(a.s, sh.s);
     if (threadIdx.x == 0)
-        for (int w = 1; w < 4; w++) {
-#pragma unroll
-            for (int k = 0; k < NSUM; k++) a.s[k] += sh[w][k];
-            acc_max(a.mx, a.dof, sh[w][NSUM], shd[w]);
-        }
+        for (int w = 1; w < 4; w++) acc_max(a.mx, a.dof, sh.s[w][NSUM], sh.dof[w]);
 }
 
 template <bool EQ>
@@ -189,20 +166,15 @@ __global__ void __launch_bounds__(256)
 k_if_gather(int64_t n_nodes, const int64_t *__restrict__ ptr, const int32_t *__restrict__ list, const double *__restrict__ fe,
             const int32_t *__restrict__ node_dof, const int32_t *__restrict__ red, const double *__restrict__ F, int64_t n_red,
             double *__restrict__ f_int, double *__restrict__ reaction, double *__restrict__ partial, long long *__restrict__ partial_dof) {
-    __shared__ double sh[4][NSUM + 1];
-    __shared__ long long shd[4];
+    __shared__ eq_shared sh;
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     eq_acc a;
 #pragma unroll
     for (int k = 0; k < NSUM; k++) a.s[k] = 0.0;
     a.mx = -1.0; a.dof = NONE;
     if (n < n_nodes) {
-        double f[3] = {0.0, 0.0, 0.0};
-        const int64_t k0 = ptr[n], k1 = ptr[n + 1];
-        for (int64_t k = k0; k < k1; k++) {
-            const int64_t t = list[k];   // element * 8 + corner
-            f[0] += fe[3 * t]; f[1] += fe[3 * t + 1]; f[2] += fe[3 * t + 2];
-        }
+        double f[3];
+        node_gather(ptr, list, fe, n, f);
         const int64_t d0 = node_dof[3 * n];   // {d0, d0 + 1, d0 + 2}, no other node's (k_if_check)
 #pragma unroll
         for (int c = 0; c < 3; c++) {
@@ -227,7 +199,7 @@ k_if_gather(int64_t n_nodes, const int64_t *__restrict__ ptr, const int32_t *__r
         }
     }
     if (EQ) {
-        block_sums(a, sh, shd);
+        eq_block_reduce(a, sh);
         if (threadIdx.x == 0) {
             for (int k = 0; k < NSUM; k++) partial[(int64_t)blockIdx.x * (NSUM + 1) + k] = a.s[k];
             partial[(int64_t)blockIdx.x * (NSUM + 1) + NSUM] = a.mx;
@@ -239,8 +211,7 @@ k_if_gather(int64_t n_nodes, const int64_t *__restrict__ ptr, const int32_t *__r
 // one block: thread t adds the partials of blocks t, t + 256, ... in ascending order, then the block's fixed order
 __global__ void __launch_bounds__(256)
 k_if_finish(int64_t n_blocks, const double *__restrict__ partial, const long long *__restrict__ partial_dof, double *out, long long *out_dof) {
-    __shared__ double sh[4][NSUM + 1];
-    __shared__ long long shd[4];
+    __shared__ eq_shared sh;
     eq_acc a;
 #pragma unroll
     for (int k = 0; k < NSUM; k++) a.s[k] = 0.0;
@@ -250,7 +221,7 @@ k_if_finish(int64_t n_blocks, const double *__restrict__ partial, const long lon
         for (int k = 0; k < NSUM; k++) a.s[k] += partial[b * (NSUM + 1) + k];
         acc_max(a.mx, a.dof, partial[b * (NSUM + 1) + NSUM], partial_dof[b]);
     }
-    block_sums(a, sh, shd);
+    eq_block_reduce(a, sh);
     if (threadIdx.x == 0) {
         for (int k = 0; k < NSUM; k++) out[k] = a.s[k];
         out[NSUM] = a.mx;
@@ -260,12 +231,37 @@ k_if_finish(int64_t n_blocks, const double *__restrict__ partial, const long lon
 
 }  // namespace
 
-void stan_if_check_enqueue(stan_ctx *ctx, int64_t n_nodes, int64_t n_elem, int64_t n_dof, int32_t n_mat, const int32_t *d_conn,
-                           const int32_t *d_elem_mat, const uint8_t *d_elem_type, const int32_t *d_node_dof, const int32_t *d_red,
-                           int32_t *d_claim) {
+int stan_elem_args_check(stan_ctx *ctx, dev_scope &tmp, const char *who, int64_t n_nodes, int64_t n_elem, int64_t n_dof,
+                         int32_t n_mat, const int32_t *d_conn, const int32_t *d_elem_mat, const uint8_t *d_elem_type,
+                         const int32_t *d_node_dof, const int32_t *d_red, int64_t n_faces, const int32_t *d_face_elem,
+                         const uint8_t *d_face_id, int64_t *n_fixed) {
+    auto bad = [&](const char *why, int rc) { ctx->err = std::string(who) + ": " + why; return rc; };
+    hipStream_t st = ctx->stream;
+    int64_t *status = ctx->d_status;
+    const long long init[3] = {0, NONE, 0};
+    HIPCHK(ctx, hipMemcpyAsync(status + SS_ERRBITS, &init[0], 8, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(status + SS_BAD_ELEM, &init[1], 16, hipMemcpyHostToDevice, st));   // SS_BAD_ELEM, SS_AUX
+    int32_t *d_claim;
+    STANCHK(tmp.alloc(&d_claim, (size_t)n_nodes));
+    HIPCHK(ctx, hipMemsetAsync(d_claim, 0, (size_t)n_nodes * 4, st));
     const int64_t n_chk = n_elem * 8 > n_dof ? n_elem * 8 : n_dof;   // (n_dof = 3 n_nodes)
-    hipLaunchKernelGGL(k_if_check, dim3(nblk(n_chk, 256)), dim3(256), 0, ctx->stream, n_nodes, n_elem, n_dof, n_mat, d_conn,
-                       d_elem_mat, d_elem_type, d_node_dof, d_red, d_claim, ctx->d_status);
+    hipLaunchKernelGGL(k_if_check, dim3(nblk(n_chk, 256)), dim3(256), 0, st, n_nodes, n_elem, n_dof, n_mat, d_conn, d_elem_mat,
+                       d_elem_type, d_node_dof, d_red, d_claim, status);
+    if (n_faces > 0)
+        hipLaunchKernelGGL(k_ld_check_faces, dim3(nblk(n_faces, 256)), dim3(256), 0, st, n_faces, n_elem, d_face_elem, d_face_id, status);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_ERRBITS, status + SS_ERRBITS, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, status + SS_AUX, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const int64_t bits = ctx->h_status[SS_ERRBITS];
+    *n_fixed = ctx->h_status[SS_AUX];
+    if (bits & IF_DOF) return bad("Node.DOF is not {3i,3i+1,3i+2} with 3i < n_dof, or two nodes share one (Node.cs:218-223)", STAN_E_DOF_LAYOUT);
+    if (bits & IF_CONN) return bad("node index out of range", STAN_E_ARG);
+    if (bits & IF_MAT) return bad("elem_mat out of range", STAN_E_ARG);
+    if (bits & IF_TYPE) return bad("element type is neither HEX8_G1 nor HEX8_G2", STAN_E_ARG);
+    if (bits & IF_RED) return bad("ndof_reduction entry outside -1 / [0, i]", STAN_E_ARG);
+    if (bits & IF_FACE) return bad("face list: element or face id out of range, or face_elem * 6 + face_id not strictly ascending", STAN_E_ARG);
+    return STAN_OK;
 }
 
 int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const double *d_disp,
@@ -273,7 +269,8 @@ int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_
                                 const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
                                 const int32_t *d_red, const double *d_F, double *d_fint, double *d_reaction,
                                 stan_equilibrium *eq) {
-    auto bad = [&](const char *why, int rc) { ctx->err = std::string("internal_forces_hex8: ") + why; return rc; };
+    const char *who = "internal_forces_hex8";
+    auto bad = [&](const char *why, int rc) { ctx->err = std::string(who) + ": " + why; return rc; };
     if (n_nodes <= 0 || n_elem < 0 || n_mat <= 0 || n_dof != n_nodes * 3) return bad("n_dof must be 3 n_nodes > 0, n_mat > 0", STAN_E_ARG);
     if (n_elem >= (int64_t)1 << 28) return bad("more than 2^28 elements", STAN_E_ARG);
     if (n_dof > 0x7fffffffLL) return bad("more than 2^31 DOFs", STAN_E_ARG);
@@ -281,36 +278,18 @@ int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_
     ctx->prof.forces_elem_ms = ctx->prof.forces_list_ms = ctx->prof.forces_gather_ms = 0;
     // ---- the checks, before anything is indexed with the caller's integers
     int64_t *status = ctx->d_status;
-    const long long init[3] = {0, NONE, 0};
-    HIPCHK(ctx, hipMemcpyAsync(status + SS_ERRBITS, &init[0], 8, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(status + SS_BAD_ELEM, &init[1], 16, hipMemcpyHostToDevice, st));   // SS_BAD_ELEM, SS_AUX
     dev_scope tmp(ctx);
-    int32_t *d_claim;
-    STANCHK(tmp.alloc(&d_claim, (size_t)n_nodes));
-    HIPCHK(ctx, hipMemsetAsync(d_claim, 0, (size_t)n_nodes * 4, st));
-    stan_if_check_enqueue(ctx, n_nodes, n_elem, n_dof, n_mat, d_conn, d_elem_mat, d_elem_type, d_node_dof, d_red, d_claim);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_ERRBITS, status + SS_ERRBITS, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, status + SS_AUX, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    const int64_t bits = ctx->h_status[SS_ERRBITS], n_fixed = ctx->h_status[SS_AUX];
-    if (bits & IF_DOF) return bad("Node.DOF is not {3i,3i+1,3i+2} with 3i < n_dof, or two nodes share one (Node.cs:218-223)", STAN_E_DOF_LAYOUT);
-    if (bits & IF_CONN) return bad("node index out of range", STAN_E_ARG);
-    if (bits & IF_MAT) return bad("elem_mat out of range", STAN_E_ARG);
-    if (bits & IF_TYPE) return bad("element type is neither HEX8_G1 nor HEX8_G2", STAN_E_ARG);
-    if (bits & IF_RED) return bad("ndof_reduction entry outside -1 / [0, i]", STAN_E_ARG);
+    int64_t n_fixed;
+    STANCHK(stan_elem_args_check(ctx, tmp, who, n_nodes, n_elem, n_dof, n_mat, d_conn, d_elem_mat, d_elem_type, d_node_dof, d_red, 0,
+                                 nullptr, nullptr, &n_fixed));
     const int64_t n_red = n_dof - n_fixed;
 
-    std::vector<double> lamG(2 * (size_t)n_mat);
-    for (int m = 0; m < n_mat; m++) stan_lame(mat_E_nu[2 * m], mat_E_nu[2 * m + 1], &lamG[2 * m], &lamG[2 * m + 1]);
-    event_bag evs;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // profiling: element pass | lists | gather + reductions
-    if (ctx->profiling)
-        for (hipEvent_t &e : ev) e = evs.make();
-    double *d_lamG, *d_fe, *d_partial = nullptr, *d_out = nullptr;
+    phase_timer pt(ctx, 4);   // element pass | lists | gather + reductions
+    lamG_buf lamG;
+    double *d_fe, *d_partial = nullptr, *d_out = nullptr;
     long long *d_partial_dof = nullptr, *d_out_dof = nullptr;
     const int64_t n_blocks = nblk(n_nodes, 256);
-    STANCHK(tmp.alloc(&d_lamG, lamG.size()));
+    STANCHK(lamG.alloc(tmp, n_mat, mat_E_nu));
     STANCHK(tmp.alloc(&d_fe, (size_t)(n_elem > 0 ? n_elem : 1) * 24));
     if (eq) {
         STANCHK(tmp.alloc(&d_partial, (size_t)n_blocks * (NSUM + 1)));
@@ -318,16 +297,16 @@ int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_
         STANCHK(tmp.alloc(&d_out, (size_t)NSUM + 1));
         STANCHK(tmp.alloc(&d_out_dof, (size_t)1));
     }
-    HIPCHK(ctx, hipMemcpyAsync(d_lamG, lamG.data(), lamG.size() * 8, hipMemcpyHostToDevice, st));
-    if (ev[0]) HIPCHK(ctx, hipEventRecord(ev[0], st));
+    HIPCHK(ctx, lamG.upload(st));
+    STANCHK(pt.mark(0));
     if (n_elem > 0)   // 8 lanes per element, 8 elements per wave, 32 per workgroup
         hipLaunchKernelGGL(k_if_elem, dim3(nblk(n_elem, 32)), dim3(256), 0, st, n_elem, d_xyz, d_disp, d_conn, d_elem_mat, d_elem_type,
-                           d_lamG, d_fe, (long long *)(status + SS_BAD_ELEM));
-    if (ev[1]) HIPCHK(ctx, hipEventRecord(ev[1], st));
+                           lamG.d, d_fe, (long long *)(status + SS_BAD_ELEM));
+    STANCHK(pt.mark(1));
     int64_t *d_ptr;
     int32_t *d_list;
     STANCHK(stan_incidence_lists(ctx, tmp, n_nodes, n_elem, d_conn, true, &d_ptr, &d_list));
-    if (ev[2]) HIPCHK(ctx, hipEventRecord(ev[2], st));
+    STANCHK(pt.mark(2));
     if (eq) {
         hipLaunchKernelGGL(k_if_gather<true>, dim3((unsigned)n_blocks), dim3(256), 0, st, n_nodes, d_ptr, d_list, d_fe, d_node_dof, d_red,
                            d_F, n_red, d_fint, d_reaction, d_partial, d_partial_dof);
@@ -336,7 +315,7 @@ int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_
         hipLaunchKernelGGL(k_if_gather<false>, dim3((unsigned)n_blocks), dim3(256), 0, st, n_nodes, d_ptr, d_list, d_fe, d_node_dof, d_red,
                            d_F, n_red, d_fint, d_reaction, nullptr, nullptr);
     }
-    if (ev[3]) HIPCHK(ctx, hipEventRecord(ev[3], st));
+    STANCHK(pt.mark(3));
     HIPCHK(ctx, hipGetLastError());
     double out[NSUM + 1];
     long long out_dof = NONE;
@@ -346,12 +325,9 @@ int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_
     }
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_BAD_ELEM, status + SS_BAD_ELEM, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));   // the temporaries go back to the context behind the kernels
-    if (ctx->profiling) {
-        float ms = 0;
-        HIPCHK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1])); ctx->prof.forces_elem_ms = ms;
-        HIPCHK(ctx, hipEventElapsedTime(&ms, ev[1], ev[2])); ctx->prof.forces_list_ms = ms;
-        HIPCHK(ctx, hipEventElapsedTime(&ms, ev[2], ev[3])); ctx->prof.forces_gather_ms = ms;
-    }
+    STANCHK(pt.read(0, 1, &ctx->prof.forces_elem_ms));
+    STANCHK(pt.read(1, 2, &ctx->prof.forces_list_ms));
+    STANCHK(pt.read(2, 3, &ctx->prof.forces_gather_ms));
     STANCHK(stan_detj_check(ctx, " (internal forces)"));
     if (eq) {
         for (int c = 0; c < 3; c++) { eq->reaction_sum[c] = out[c]; eq->load_sum[c] = out[3 + c]; eq->fint_sum[c] = out[6 + c]; }

@@ -8,66 +8,22 @@
 // Faces in CHEXA order:  0 xi=-1 {0,3,4,7}  1 xi=+1 {1,2,5,6}  2 eta=-1 {0,1,4,5}  3 eta=+1 {2,3,6,7}  4 zeta=-1 {0,1,2,3}
 // 5 zeta=+1 {4,5,6,7}; the face list is sorted by face_elem * 6 + face_id, strictly.
 // Phases, all bit-reproducible (no atomics on doubles):
-//   element pass  k_ld_elem: the layout of k_if_elem (8 lanes per element, lane g loads node g only, records 50 doubles apart
-//                 in LDS); body term first (lane g = Gauss point g, three butterfly stages), then the element's listed faces
+//   element pass  k_ld_elem: the layout of elem_pass.h (8 lanes per element, lane g loads node g only, coordinates alone);
+//                 body term first (lane g = Gauss point g, three butterfly stages), then the element's listed faces
 //                 in ascending face id (lanes 0..3 one face point each, lanes 4..7 add zero to the same butterfly); f_e leaves
 //                 node-major through LDS as full lines; a wave without any loaded element stores zeros and nothing else;
 //   lists         node -> (element, corner), all corners, ascending (stan_incidence_lists);
 //   node gather   k_ld_gather: one lane per node adds its list's entries in order and writes load_full, F, F_solve through
 //                 node_dof / the reduction map, with the block's partial sums; k_ld_finish adds the partials in block order.
-#include "internal.h"
-#include "hex8_device.h"
+#include "elem_pass.h"
 
 namespace {
 
-constexpr int REC = 50;    // doubles per element record in LDS, as k_if_elem's
 constexpr int NGS = 6;     // gather sums: load_sum[3], free_sum[3]
 constexpr int NES = 2;     // element sums: volume, area
 constexpr double GL = 0.57735026918962576451;   // sqrt(1/3)
 
-// face list: element and face id in range, keys strictly ascending.  Reads the lists by position only.
-__global__ void __launch_bounds__(256)
-k_ld_check_faces(int64_t n_faces, int64_t n_elem, const int32_t *__restrict__ face_elem, const uint8_t *__restrict__ face_id,
-                 int64_t *status) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n_faces) return;
-    const int64_t e = face_elem[t], f = face_id[t];
-    bool bad = e < 0 || e >= n_elem || f >= 6;
-    if (t > 0 && (int64_t)face_elem[t - 1] * 6 + face_id[t - 1] >= e * 6 + f) bad = true;
-    if (bad) atomicOr((unsigned long long *)&status[SS_ERRBITS], (unsigned long long)IF_FACE);
-}
-
-__device__ __forceinline__ void wave_sync() {   // wave-local exchange through LDS (as in k_if_elem)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// sums of the block's 256 lanes in a fixed order (six butterfly stages per wave, then the four waves in order) on thread 0
-template <int N>
-__device__ __forceinline__ void block_sums(double (&s)[N], double (*sh)[N]) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-        for (int k = 0; k < N; k++) s[k] += __shfl_xor(s[k], off, 64);
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < N; k++) sh[wv][k] = s[k];
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < 4; w++)
-#pragma unroll
-            for (int k = 0; k < N; k++) s[k] += sh[w][k];
-}
-
-// sum over the 8 lanes of an element (three butterfly stages: a fixed order)
-__device__ __forceinline__ double elem_sum(double v) {
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    return v;
-}
+// (the face list's check, k_ld_check_faces, sits with k_if_check in internal_forces.hip: stan_elem_args_check runs both)
 
 // ---- element pass: f_e [n_elem * 24], node-major; partial [gridDim.x * 2] = the block's volume and area ------------------
 __global__ void __launch_bounds__(256)
@@ -75,13 +31,12 @@ k_ld_elem(int64_t n_elem, const double *__restrict__ xyz, const int32_t *__restr
           const double *__restrict__ mat_body, int64_t n_faces, const int32_t *__restrict__ face_elem,
           const uint8_t *__restrict__ face_id, const double *__restrict__ face_p, double *__restrict__ fe,
           double *__restrict__ partial) {
-    __shared__ __attribute__((aligned(16))) double lds[4][8 * REC];
+    __shared__ __attribute__((aligned(16))) double lds[4][8 * ELEM_REC];
     __shared__ double sh[4][NES];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int el = lane >> 3, g = lane & 7;
-    const int64_t e0 = ((int64_t)blockIdx.x * 4 + wv) * 8;   // first element of this wave
-    const int64_t e = e0 + el;
-    const bool valid = e < n_elem;
+    const elem_lanes L = elem_lanes_here(n_elem);
+    const int lane = L.lane, g = L.g;
+    const int64_t e = L.e;
+    const bool valid = L.valid;
     double b[3] = {0, 0, 0};
     int64_t k0 = 0;          // first listed face of this element
     unsigned fmask = 0;      // bit f: face f of this element is listed
@@ -107,12 +62,8 @@ k_ld_elem(int64_t n_elem, const double *__restrict__ xyz, const int32_t *__restr
     const bool has_body = b[0] != 0.0 || b[1] != 0.0 || b[2] != 0.0;
     double mine[3] = {0, 0, 0}, acc[NES] = {0, 0};
     if (__any(has_body || fmask != 0)) {   // wave-uniform: a wave without loads stores zeros and does nothing else
-        double *rec = lds[wv] + el * REC;
-        if (valid) {
-            const int64_t nd = conn[e * 8 + g];
-#pragma unroll
-            for (int c = 0; c < 3; c++) rec[3 * g + c] = xyz[3 * nd + c];
-        }
+        double *rec = lds[L.wv] + L.el * ELEM_REC;
+        if (valid) elem_load_node<false>(rec, L, conn, xyz, nullptr);
         wave_sync();
         if (__any(has_body)) {
             // lane g: Gauss point g of the 2x2x2 rule, whatever the element's type
@@ -166,17 +117,8 @@ k_ld_elem(int64_t n_elem, const double *__restrict__ xyz, const int32_t *__restr
         }
         wave_sync();   // every lane is done with the records
     }
-    // the wave's 8 x 24 values are contiguous in memory: through LDS, out as three 512-B lines
-    double *stg = lds[wv];
-#pragma unroll
-    for (int c = 0; c < 3; c++) stg[lane * 3 + c] = mine[c];
-    wave_sync();
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const int idx = j * 64 + lane;
-        if (e0 + idx / 24 < n_elem) fe[e0 * 24 + idx] = stg[idx];
-    }
-    block_sums<NES>(acc, sh);
+    elem_store_staged<3, false>(lds[L.wv], L, n_elem, mine, fe);   // three 512-B lines per wave
+    block_sums(acc, sh);
     if (threadIdx.x == 0) {
         partial[(int64_t)blockIdx.x * NES] = acc[0];
         partial[(int64_t)blockIdx.x * NES + 1] = acc[1];
@@ -200,12 +142,8 @@ k_ld_gather(int64_t n_nodes, const int64_t *__restrict__ ptr, const int32_t *__r
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     double s[NGS] = {0, 0, 0, 0, 0, 0};
     if (n < n_nodes) {
-        double l[3] = {0.0, 0.0, 0.0};
-        const int64_t k0 = ptr[n], k1 = ptr[n + 1];
-        for (int64_t k = k0; k < k1; k++) {
-            const int64_t t = list[k];   // element * 8 + corner
-            l[0] += fe[3 * t]; l[1] += fe[3 * t + 1]; l[2] += fe[3 * t + 2];
-        }
+        double l[3];
+        node_gather(ptr, list, fe, n, l);
         const int64_t d0 = node_dof[3 * n];   // {d0, d0 + 1, d0 + 2}, no other node's (k_if_check)
 #pragma unroll
         for (int c = 0; c < 3; c++) {
@@ -222,7 +160,7 @@ k_ld_gather(int64_t n_nodes, const int64_t *__restrict__ ptr, const int32_t *__r
             if (F_solve) F_solve[j] = fint0 ? v - fint0[d] : v;
         }
     }
-    block_sums<NGS>(s, sh);
+    block_sums(s, sh);
     if (threadIdx.x == 0)
         for (int k = 0; k < NGS; k++) partial[(int64_t)blockIdx.x * NGS + k] = s[k];
 }
@@ -241,7 +179,7 @@ k_ld_finish(int64_t n_gblocks, const double *__restrict__ gpartial, int64_t n_eb
     for (int64_t b = threadIdx.x; b < n_eblocks; b += 256)
 #pragma unroll
         for (int k = 0; k < NES; k++) a[NGS + k] += epartial[b * NES + k];
-    block_sums<NGS + NES>(a, sh);
+    block_sums(a, sh);
     if (threadIdx.x == 0)
         for (int k = 0; k < NGS + NES; k++) out[k] = a[k];
 }
@@ -253,7 +191,8 @@ int stan_load_vector_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
                             const double *mat_E_nu, int64_t n_dof, const int32_t *d_red, const double *mat_body, int64_t n_faces,
                             const int32_t *d_face_elem, const uint8_t *d_face_id, const double *d_face_pressure,
                             const double *d_disp0, double *d_F, double *d_F_solve, double *d_load_full, stan_load_sums *sums) {
-    auto bad = [&](const char *why, int rc) { ctx->err = std::string("load_vector_hex8: ") + why; return rc; };
+    const char *who = "load_vector_hex8";
+    auto bad = [&](const char *why, int rc) { ctx->err = std::string(who) + ": " + why; return rc; };
     if (n_nodes <= 0 || n_elem < 0 || n_mat <= 0 || n_dof != n_nodes * 3) return bad("n_dof must be 3 n_nodes > 0, n_mat > 0", STAN_E_ARG);
     if (n_elem >= (int64_t)1 << 28) return bad("more than 2^28 elements", STAN_E_ARG);
     if (n_dof > 0x7fffffffLL) return bad("more than 2^31 DOFs", STAN_E_ARG);
@@ -264,28 +203,10 @@ int stan_load_vector_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
     hipStream_t st = ctx->stream;
     ctx->prof_loads_ms[0] = ctx->prof_loads_ms[1] = ctx->prof_loads_ms[2] = 0;
     // ---- the checks, before anything is indexed with the caller's integers
-    int64_t *status = ctx->d_status;
-    const long long init[3] = {0, 0x7fffffffffffffffLL, 0};
-    HIPCHK(ctx, hipMemcpyAsync(status + SS_ERRBITS, &init[0], 8, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(status + SS_BAD_ELEM, &init[1], 16, hipMemcpyHostToDevice, st));   // SS_BAD_ELEM, SS_AUX
     dev_scope tmp(ctx);
-    int32_t *d_claim;
-    STANCHK(tmp.alloc(&d_claim, (size_t)n_nodes));
-    HIPCHK(ctx, hipMemsetAsync(d_claim, 0, (size_t)n_nodes * 4, st));
-    stan_if_check_enqueue(ctx, n_nodes, n_elem, n_dof, n_mat, d_conn, d_elem_mat, d_elem_type, d_node_dof, d_red, d_claim);
-    if (n_faces > 0)
-        hipLaunchKernelGGL(k_ld_check_faces, dim3(nblk(n_faces, 256)), dim3(256), 0, st, n_faces, n_elem, d_face_elem, d_face_id, status);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_ERRBITS, status + SS_ERRBITS, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, status + SS_AUX, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    const int64_t bits = ctx->h_status[SS_ERRBITS], n_fixed = ctx->h_status[SS_AUX];
-    if (bits & IF_DOF) return bad("Node.DOF is not {3i,3i+1,3i+2} with 3i < n_dof, or two nodes share one (Node.cs:218-223)", STAN_E_DOF_LAYOUT);
-    if (bits & IF_CONN) return bad("node index out of range", STAN_E_ARG);
-    if (bits & IF_MAT) return bad("elem_mat out of range", STAN_E_ARG);
-    if (bits & IF_TYPE) return bad("element type is neither HEX8_G1 nor HEX8_G2", STAN_E_ARG);
-    if (bits & IF_RED) return bad("ndof_reduction entry outside -1 / [0, i]", STAN_E_ARG);
-    if (bits & IF_FACE) return bad("face list: element or face id out of range, or face_elem * 6 + face_id not strictly ascending", STAN_E_ARG);
+    int64_t n_fixed;
+    STANCHK(stan_elem_args_check(ctx, tmp, who, n_nodes, n_elem, n_dof, n_mat, d_conn, d_elem_mat, d_elem_type, d_node_dof, d_red,
+                                 n_faces, d_face_elem, d_face_id, &n_fixed));
     const int64_t n_red = n_dof - n_fixed;
 
     // ---- prescribed displacements first: f_int(u0 at the fixed DOFs), an error of it leaves every output untouched
@@ -300,10 +221,7 @@ int stan_load_vector_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
                                             mat_E_nu, n_dof, d_red, nullptr, d_fint0, nullptr, nullptr));
     }
 
-    event_bag evs;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // profiling: element pass | lists | gather + reductions
-    if (ctx->profiling)
-        for (hipEvent_t &e : ev) e = evs.make();
+    phase_timer pt(ctx, 4);   // element pass | lists | gather + reductions
     const int64_t n_gblocks = nblk(n_nodes, 256), n_eblocks = nblk(n_elem, 32);
     double *d_body = nullptr, *d_fe, *d_gpartial, *d_epartial, *d_out;
     STANCHK(tmp.alloc(&d_fe, (size_t)(n_elem > 0 ? n_elem : 1) * 24));
@@ -314,30 +232,24 @@ int stan_load_vector_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
         STANCHK(tmp.alloc(&d_body, (size_t)n_mat * 3));
         HIPCHK(ctx, hipMemcpyAsync(d_body, mat_body, (size_t)n_mat * 24, hipMemcpyHostToDevice, st));
     }
-    if (ev[0]) HIPCHK(ctx, hipEventRecord(ev[0], st));
+    STANCHK(pt.mark(0));
     if (n_elem > 0)   // 8 lanes per element, 8 elements per wave, 32 per workgroup
         hipLaunchKernelGGL(k_ld_elem, dim3((unsigned)n_eblocks), dim3(256), 0, st, n_elem, d_xyz, d_conn, d_elem_mat, d_body, n_faces,
                            d_face_elem, d_face_id, d_face_pressure, d_fe, d_epartial);
-    if (ev[1]) HIPCHK(ctx, hipEventRecord(ev[1], st));
+    STANCHK(pt.mark(1));
     int64_t *d_ptr;
     int32_t *d_list;
     STANCHK(stan_incidence_lists(ctx, tmp, n_nodes, n_elem, d_conn, true, &d_ptr, &d_list));
-    if (ev[2]) HIPCHK(ctx, hipEventRecord(ev[2], st));
+    STANCHK(pt.mark(2));
     hipLaunchKernelGGL(k_ld_gather, dim3((unsigned)n_gblocks), dim3(256), 0, st, n_nodes, d_ptr, d_list, d_fe, d_node_dof, d_red, n_red,
                        d_fint0, d_F, d_F_solve, d_load_full, d_gpartial);
     if (sums) hipLaunchKernelGGL(k_ld_finish, dim3(1), dim3(256), 0, st, n_gblocks, d_gpartial, n_eblocks, d_epartial, d_out);
-    if (ev[3]) HIPCHK(ctx, hipEventRecord(ev[3], st));
+    STANCHK(pt.mark(3));
     HIPCHK(ctx, hipGetLastError());
     double out[NGS + NES];
     if (sums) HIPCHK(ctx, hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));   // the temporaries go back to the context behind the kernels
-    if (ctx->profiling) {
-        float ms = 0;
-        for (int k = 0; k < 3; k++) {
-            HIPCHK(ctx, hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-            ctx->prof_loads_ms[k] = ms;
-        }
-    }
+    for (int k = 0; k < 3; k++) STANCHK(pt.read(k, k + 1, &ctx->prof_loads_ms[k]));
     if (sums) {
         for (int c = 0; c < 3; c++) { sums->load_sum[c] = out[c]; sums->free_sum[c] = out[3 + c]; }
         sums->volume = out[NGS];

@@ -13,81 +13,48 @@
 // driver discards R (Solver.cs:199), so the console driver does not ask for it.
 // HEX8_G1 makes the reference throw (N has one row, indexed by node: Element.cs:242 vs
 // FE_Library.cs:77-81): reported as STAN_E_UNSUPPORTED with the element index.
-#include "internal.h"
-#include "hex8_device.h"
+#include "elem_pass.h"
 
 namespace {
 
 // Round 5 (profiles/r05/k_recover_n148_kernel_trace_summary_r05_final.txt): the first form let each of the 8 lanes of an element load all 8 nodes' coordinates
 // and displacements itself (56 gathers per lane) and store its 6 + 6 values 48 B apart: 1.73 ms at 148^3 for 3.2 GB =
-// 0.23 of the HBM peak, bound by the address pipeline.  Now lane i of an element loads node i only (7 gathers) and the
-// element's 48 values go round through LDS (one record per element, 49 doubles apart: no bank conflicts between the 8
-// elements of a wave); the node extrapolation value_i = sum_g N[i][g] value_g uses the tensor structure of
-// N[i][g] = prod_axis 1/2 (1 + s_i s_g sqrt 3) -- three butterfly stages (x: lane ^ 1, y: lane ^ 3, z: lane ^ 4 in CHEXA
+// 0.23 of the HBM peak, bound by the address pipeline.  Now the element pass of elem_pass.h (lane i loads node i only, the
+// element's record goes round through LDS); the node extrapolation value_i = sum_g N[i][g] value_g uses the tensor structure
+// of N[i][g] = prod_axis 1/2 (1 + s_i s_g sqrt 3) -- three butterfly stages (x: lane ^ 1, y: lane ^ 3, z: lane ^ 4 in CHEXA
 // order) instead of an 8-term sum of shuffles; the results leave through LDS as full 512-B lines.
-constexpr int REC = 50;   // doubles per element record in LDS (48 + 2: the 8 records of a wave start 36 banks apart -- no conflicts between them, and a record stays 16-B aligned: the reads pair up into ds_read_b128)
-
 template <bool FORCES>
 __global__ void __launch_bounds__(256)
 k_recover(int64_t n_elem, const double *__restrict__ xyz, const double *__restrict__ disp, const int32_t *__restrict__ conn,
           const int32_t *__restrict__ elem_mat, const uint8_t *__restrict__ elem_type, const double *__restrict__ mat_lamG,
           double *__restrict__ strain, double *__restrict__ stress, long long *bad_elem, long long *g1_elem,
           const int32_t *__restrict__ node_dof, double *__restrict__ elem_forces, double *R) {
-    __shared__ __attribute__((aligned(16))) double lds[4][8 * REC];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int el = lane >> 3, g = lane & 7;
-    const int64_t e0 = ((int64_t)blockIdx.x * 4 + wv) * 8;   // first element of this wave
-    const int64_t e = e0 + el;
-    const bool valid = e < n_elem;
+    __shared__ __attribute__((aligned(16))) double lds[4][8 * ELEM_REC];
+    const elem_lanes L = elem_lanes_here(n_elem);
+    const int g = L.g;
+    const int64_t e = L.e;
     double eps[6] = {0, 0, 0, 0, 0, 0}, sig[6] = {0, 0, 0, 0, 0, 0};
     double o[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, det = 0, px = 0, py = 0, pz = 0;
     bool live = false;  // a HEX8_G2 element of the batch
     int type = 0;
     int64_t nd = 0;
-    double *rec = lds[wv] + el * REC;
-    if (valid) {
+    double *rec = lds[L.wv] + L.el * ELEM_REC;
+    if (L.valid) {
         type = elem_type[e];
-        nd = conn[e * 8 + g];
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            rec[3 * g + c] = xyz[3 * nd + c];
-            rec[24 + 3 * g + c] = disp[3 * nd + c];
-        }
+        nd = elem_load_node<true>(rec, L, conn, xyz, disp);
     }
-    // wave-local exchange: the LDS executes one wave's instructions in order (as in k_spmv_fold)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (valid) {
+    wave_sync();
+    if (L.valid) {
         if (type != STAN_HEX8_G2) {
             if (g == 0) atomicMin(g1_elem, (long long)e);
         } else {
             live = true;
-            const double *u = rec + 24;   // the element's record stays in LDS: coordinates [0, 24), displacements [24, 48)
             det = hex8_gp_setup(rec, type, g, o);
             if (det == 0.0) atomicMin(bad_elem, (long long)e);
-            const double gl = hex8_gauss_loc(type);
-            px = hex8_sign(HEX8_SX, g) * gl; py = hex8_sign(HEX8_SY, g) * gl;
-            pz = hex8_sign(HEX8_SZ, g) * gl;
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                double gr[3];
-                hex8_grad(o, i, px, py, pz, gr);
-                // BL0 rows (Element.cs:316-324): xx, yy, zz, xy, yz, xz
-                eps[0] += gr[0] * u[3 * i];
-                eps[1] += gr[1] * u[3 * i + 1];
-                eps[2] += gr[2] * u[3 * i + 2];
-                eps[3] += gr[1] * u[3 * i] + gr[0] * u[3 * i + 1];
-                eps[4] += gr[2] * u[3 * i + 1] + gr[1] * u[3 * i + 2];
-                eps[5] += gr[2] * u[3 * i] + gr[0] * u[3 * i + 2];
-            }
+            hex8_gauss_point(type, g, px, py, pz);
+            hex8_strain(o, rec + 24, px, py, pz, eps);
             const int32_t m = elem_mat[e];
-            const double lam = mat_lamG[2 * m], G = mat_lamG[2 * m + 1];
-            const double tr = lam * (eps[0] + eps[1] + eps[2]);
-            sig[0] = tr + 2 * G * eps[0];
-            sig[1] = tr + 2 * G * eps[1];
-            sig[2] = tr + 2 * G * eps[2];
-            sig[3] = G * eps[3]; sig[4] = G * eps[4]; sig[5] = G * eps[5];
+            hex8_stress(mat_lamG[2 * m], mat_lamG[2 * m + 1], eps, sig);
         }
     }
     // node i = this lane's index within the element; N[i][k] = prod over the axes of 1/2 (1 + s_i s_k sqrt 3): a when node
@@ -105,48 +72,16 @@ k_recover(int64_t n_elem, const double *__restrict__ xyz, const double *__restri
         ne[c] = a; ns[c] = b;
     }
     if (strain) {
-        // the wave's 8 x 48 values of each array are contiguous in memory: through LDS, out as six 512-B lines
-        double *stg = lds[wv];
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-            for (int c = 0; c < 6; c++) stg[lane * 6 + c] = q ? ns[c] : ne[c];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            double *dst = (q ? stress : strain) + e0 * 48;
-#pragma unroll
-            for (int j = 0; j < 6; j++) {
-                const int idx = j * 64 + lane;
-                if (e0 + idx / 48 < n_elem) __builtin_nontemporal_store(stg[idx], dst + idx);
-            }
-        }
+        // six 512-B lines per array and wave, non-temporal; each staging waits until no lane reads the wave's LDS any more
+        wave_sync();
+        elem_store_staged<6, true>(lds[L.wv], L, n_elem, ne, strain);
+        wave_sync();
+        elem_store_staged<6, true>(lds[L.wv], L, n_elem, ns, stress);
     }
     if (FORCES) {
-        // lane g: B_g^T ns * det J_g * w (w = 1 for HEX8_G2), then the sum over the 8 lanes of
-        // the element; node a's three components end up on lane a
-        const double sc = live ? det : 0.0;
-        double mine[3] = {0, 0, 0};
-#pragma unroll
-        for (int a = 0; a < 8; a++) {
-            double gr[3] = {0, 0, 0};
-            if (live) hex8_grad(o, a, px, py, pz, gr);
-            double f[3];
-            f[0] = (gr[0] * ns[0] + gr[1] * ns[3] + gr[2] * ns[5]) * sc;
-            f[1] = (gr[1] * ns[1] + gr[0] * ns[3] + gr[2] * ns[4]) * sc;
-            f[2] = (gr[2] * ns[2] + gr[1] * ns[4] + gr[0] * ns[5]) * sc;
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                double v = f[c];
-                v += __shfl_xor(v, 1, 64);
-                v += __shfl_xor(v, 2, 64);
-                v += __shfl_xor(v, 4, 64);
-                if (a == i) mine[c] = v;
-            }
-        }
+        // lane g: B_g^T ns * det J_g * w (w = 1 for HEX8_G2)
+        double mine[3];
+        elem_bt_sum(o, live, g, px, py, pz, ns, live ? det : 0.0, mine);
         if (live) {
 #pragma unroll
             for (int c = 0; c < 3; c++) {
@@ -159,6 +94,12 @@ k_recover(int64_t n_elem, const double *__restrict__ xyz, const double *__restri
 
 }  // namespace
 
+int lamG_buf::alloc(dev_scope &tmp, int32_t n_mat, const double *mat_E_nu) {
+    host.resize(2 * (size_t)n_mat);
+    for (int m = 0; m < n_mat; m++) stan_lame(mat_E_nu[2 * m], mat_E_nu[2 * m + 1], &host[2 * m], &host[2 * m + 1]);
+    return tmp.alloc(&d, host.size());
+}
+
 int stan_recover_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const double *d_disp,
                         int64_t n_elem, const int32_t *d_conn, const int32_t *d_elem_mat,
                         const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu,
@@ -167,14 +108,13 @@ int stan_recover_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, con
     (void)n_nodes;
     const bool forces = d_elem_forces || d_R;
     if (n_elem <= 0) return STAN_OK;
-    std::vector<double> lamG(2 * (size_t)n_mat);
-    for (int m = 0; m < n_mat; m++) stan_lame(mat_E_nu[2 * m], mat_E_nu[2 * m + 1], &lamG[2 * m], &lamG[2 * m + 1]);
     dev_scope tmp(ctx);
-    double *d_lamG;
-    STANCHK(tmp.alloc(&d_lamG, lamG.size()));
+    lamG_buf lamG;
+    STANCHK(lamG.alloc(tmp, n_mat, mat_E_nu));
+    const double *d_lamG = lamG.d;
     hipStream_t st = ctx->stream;
     long long init[2] = {0x7fffffffffffffffLL, 0x7fffffffffffffffLL};
-    hipError_t e1 = hipMemcpyAsync(d_lamG, lamG.data(), lamG.size() * 8, hipMemcpyHostToDevice, st);
+    hipError_t e1 = lamG.upload(st);
     hipError_t e2 = hipMemcpyAsync(ctx->d_status + SS_BAD_ELEM, init, 16, hipMemcpyHostToDevice, st);
     const dim3 grid((unsigned)((n_elem + 31) / 32)), block(256);   // 8 lanes per element, 8 elements per wave
     if (forces)

@@ -225,39 +225,33 @@ int stan_scalars_device(stan_ctx *ctx, int64_t n_nodes, const double *d_disp, in
     for (int32_t k = 0; k < n_sel; k++) { ss.mask |= 1u << sel[k]; ss.row[sel[k]] = (int8_t)k; }
     hipStream_t st = ctx->stream;
     const int64_t n_inc = n_elem * 8;
-    event_bag evs;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // profiling: cell kernel | list | point kernel
-    if (ctx->profiling)
-        for (hipEvent_t &e : ev) e = evs.make();
+    phase_timer pt(ctx, 5);   // cell kernel [0, 1] | list [2, 3] | point kernel [3, 4]
     ctx->prof.scalars_cell_ms = ctx->prof.scalars_list_ms = ctx->prof.scalars_point_ms = 0;
     if (d_cell && n_elem > 0) {
-        if (ev[0]) HIPCHK(ctx, hipEventRecord(ev[0], st));
+        STANCHK(pt.mark(0));
         hipLaunchKernelGGL(k_scalars_cell, dim3(nblk(n_inc, 256)), dim3(256), 0, st, n_elem, d_conn, d_disp, d_strain, d_stress,
                            ss, d_cell);
-        if (ev[1]) HIPCHK(ctx, hipEventRecord(ev[1], st));
+        STANCHK(pt.mark(1));
     }
     if (d_point) {
         dev_scope tmp(ctx);
         int32_t *d_list;
         int64_t *d_ptr;
-        if (ev[2]) HIPCHK(ctx, hipEventRecord(ev[2], st));
+        STANCHK(pt.mark(2));
         STANCHK(stan_incidence_lists(ctx, tmp, n_nodes, n_elem, d_conn, false, &d_ptr, &d_list));
-        if (ev[3]) HIPCHK(ctx, hipEventRecord(ev[3], st));
+        STANCHK(pt.mark(3));
         hipLaunchKernelGGL(k_scalars_point, dim3(nblk(n_nodes, 256)), dim3(256), 0, st, n_nodes, d_ptr, d_list, d_disp, d_strain,
                            d_stress, ss, d_point);
-        if (ev[4]) HIPCHK(ctx, hipEventRecord(ev[4], st));
+        STANCHK(pt.mark(4));
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipStreamSynchronize(st));   // the temporaries go back to the context behind the kernels
     }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(st));
-    if (ctx->profiling) {
-        float ms = 0;
-        if (d_cell && n_elem > 0) { HIPCHK(ctx, hipEventElapsedTime(&ms, ev[0], ev[1])); ctx->prof.scalars_cell_ms = ms; }
-        if (d_point) {
-            HIPCHK(ctx, hipEventElapsedTime(&ms, ev[2], ev[3])); ctx->prof.scalars_list_ms = ms;
-            HIPCHK(ctx, hipEventElapsedTime(&ms, ev[3], ev[4])); ctx->prof.scalars_point_ms = ms;
-        }
+    if (d_cell && n_elem > 0) STANCHK(pt.read(0, 1, &ctx->prof.scalars_cell_ms));
+    if (d_point) {
+        STANCHK(pt.read(2, 3, &ctx->prof.scalars_list_ms));
+        STANCHK(pt.read(3, 4, &ctx->prof.scalars_point_ms));
     }
     return STAN_OK;
 }

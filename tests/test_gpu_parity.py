@@ -538,6 +538,33 @@ def test_nodal_forces_parity(gpu_ctx, oracle):
     assert np.abs(R - Ro).max() <= 1e-12 * np.abs(Ro).max()
 
 
+def test_recovery_and_nodal_forces_parity_on_ragged_strips(gpu_ctx, oracle):
+    """The strips of tests/forces_ref.py (1, 7, 8, 9, 31, 33 elements: one below and one above the element kernel's 8 per
+    wave and 32 per workgroup) with their random displacements: the ragged tail of the wave's staged stores.  Every element's
+    strain, stress and nodal forces against the oracle, 1e-12 of the element's largest reference entry; R against the
+    oracle's scatter."""
+    from tests import forces_ref
+    for n in forces_ref.STRIPS:
+        m, disp = forces_ref.cases()["strip%d" % n]
+        ne = m.conn.shape[0]
+        assert ne == n
+        strain, stress = gpu_ctx.recover_hex8(m.xyz, disp, m.conn, m.elem_mat, m.elem_type, m.mat_E_nu)
+        f, R = gpu_ctx.nodal_forces_hex8(m.xyz, disp, m.node_dof, m.conn, m.elem_mat, m.elem_type, m.mat_E_nu)
+        assert strain.shape[0] == stress.shape[0] == f.shape[0] == ne
+        fo = np.zeros_like(f)
+        for e in range(ne):
+            E, nu = m.mat_E_nu[m.elem_mat[e]]
+            rc, eo, so = oracle.recover_hex8(m.xyz[m.conn[e]], E, nu, int(m.elem_type[e]), disp[m.conn[e]].ravel())
+            rc2, fo[e] = oracle.nodal_forces_hex8(m.xyz[m.conn[e]], int(m.elem_type[e]), so)
+            assert rc == 0 and rc2 == 0
+            assert np.abs(strain[e] - eo).max() <= 1e-12 * np.abs(eo).max(), (n, e)
+            assert np.abs(stress[e] - so).max() <= 1e-12 * np.abs(so).max(), (n, e)
+            assert np.abs(f[e] - fo[e]).max() <= 1e-12 * np.abs(fo[e]).max(), (n, e)
+        Ro = np.zeros(m.n_dof)
+        np.add.at(Ro, np.asarray(m.node_dof).reshape(-1, 3)[m.conn].reshape(-1, 24), fo.reshape(ne, 24))
+        assert np.abs(R - Ro).max() <= 1e-12 * np.abs(Ro).max(), n
+
+
 def test_stress_recovery_g1_is_an_error_like_the_reference(gpu_ctx):
     from stan_amd import hip
     job = problem.cube_job(2, etype=1)
