@@ -735,7 +735,7 @@ int stan_hip_nodal_forces_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz
 // a chunk boundary would have incidences on two devices.
 static int internal_forces_refused(stan_ctx *ctx, const char *entry = "internal_forces_hex8") {
     STAN_NO_GROUP(ctx, std::string(entry) + " (a node on a chunk boundary has incidences on two devices)");
-    if (ctx->nranks > 1 || ctx->comm) {
+    if (stan_sharded(ctx)) {
         ctx->err = std::string(entry) + ": not available on a context with a communicator";
         return STAN_E_UNSUPPORTED;
     }

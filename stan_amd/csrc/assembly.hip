@@ -1126,7 +1126,7 @@ int assembly_run::numeric() {
 
 // (also built for a 1-rank communicator, where every slice is interior, so that the two-stream path can be tested)
 int assembly_run::slice_lists() {
-    if (!(ctx->nranks > 1 || ctx->comm) || K->nslices <= 0) return STAN_OK;
+    if (!stan_sharded(ctx) || K->nslices <= 0) return STAN_OK;
     const int64_t ns = K->nslices;
     int32_t *d_fb, *d_fi; int64_t *d_sb, *d_si;
     STANCHK(tmp.alloc(&d_fb, (size_t)ns + 1));

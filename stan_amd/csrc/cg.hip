@@ -25,6 +25,7 @@
 
 #include "internal.h"
 #include "p2p_device.h"
+#include "fx48.h"
 
 // Cache policy of the vector traffic (measured in round 2, tools/fold_ab.py, profiles/r02/fold_ab_incg_*.txt; the
 // compile-time switches behind those runs are the lab build's, lab/lab_hooks.patch): the in-CG penalty of the SpMV is the
@@ -44,152 +45,9 @@
 
 namespace {
 
-constexpr int VEC_BLOCKS = 2048;  // grid of the streaming vector kernels (8 blocks per CU; 1024 ... 16384 measured: profiles/r04/vector_grid_ab_in_cg.txt)
-constexpr int VEC_T = 256;
-constexpr int CHUNK = 32;         // iterations enqueued between two status polls
-constexpr int CHUNK_DIST = 8;     // ... of a sharded loop
+#include "cg_reduce_device.inc"   // grid constants, scalar / status slots, block sums, the folded reductions, stopped()
 
-// device scalar slots (double)
-enum { S_BNORM = 0, S_VMV = 1, S_R2NEW = 2, S_MERIT = 3, S_RHO0 = 4, S_RHO1 = 5, S_PMF0 = 6,
-       S_PMF1 = 7, S_R2OUT = 8,
-       // single-reduction loop: the three sums of one iteration are contiguous (ONE all-reduce)
-       S_SR_GAMMA = 9, S_SR_DELTA = 10, S_SR_MERIT = 11, S_SR_GP0 = 12, S_SR_GP1 = 13, S_SR_AP0 = 14,
-       S_SR_AP1 = 15,
-       // fp64 check of a reduced-precision solve: ||b - A64 x||^2 and the merit sum of the same pass
-       S_CHK_R2 = 16, S_CHK_MF = 17, S_NSCAL = 24 };
-// device status slots (int64)
-enum { T_ITER_A = 0, T_ITER_B = 1, T_TYPE = 2, T_ITERS = 3, T_XSEL = 4, T_NSTAT = 8 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-// block sum (256 threads), valid in thread 0; fixed combination order
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) sh[w] = v;
-    __syncthreads();
-    return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// ---- reductions folded into their producers ("last block done") --------------------------------
-// Every block of a producing kernel leaves its partial sum(s) in `partial`, then takes a ticket;
-// the block that draws the last ticket adds ALL partials in a fixed order (independent of which
-// block that is: the result is bit-reproducible) and writes the scalar.  That removes the two
-// one-block k_reduce launches per iteration from the stream (2 x (4.5 us + a kernel boundary) at
-// 148^3; more where it matters: the sharded loop, whose per-rank kernels are 8 x shorter).
-// Hand-off across XCDs (their L2s are not coherent, MI355X_MICROARCH.md "inter-workgroup
-// visibility", first row of the table of measured forms): the partial is an agent-scope store
-// (sc1, write-through), the storing lane waits for it (vmcnt(0)) before its agent-scope add to
-// the one unsharded counter, the block whose add returned the last ticket reads every partial
-// with agent-scope (sc1) loads after a workgroup barrier behind that add.
-// STAN_OPT_CG_FOLD_REDUCE = 0 restores the separate k_reduce launches (same order: same bits).
-__device__ __forceinline__ void st_agent(double *p, double v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double ld_agent(const double *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// r[j] = sum_i partial[i*NV + j] over np blocks by one 256-thread block, all NV sums in ONE pass
-// over the partials (their loads overlap), fixed order; valid in thread 0
-template <int NV>
-__device__ __forceinline__ void sum_partials(const double *partial, int np, double *sh, double r[NV]) {
-    constexpr int W = 16 / NV;   // loads in flight per thread: the last block's latency adds to the kernel
-    double a[NV][W];
-#pragma unroll
-    for (int j = 0; j < NV; j++)
-#pragma unroll
-        for (int q = 0; q < W; q++) a[j][q] = 0;
-    int i = threadIdx.x;
-    for (; i + (W - 1) * 256 < np; i += W * 256) {
-#pragma unroll
-        for (int q = 0; q < W; q++)
-#pragma unroll
-            for (int j = 0; j < NV; j++) a[j][q] += ld_agent(partial + (int64_t)(i + q * 256) * NV + j);
-    }
-    for (; i < np; i += 256)
-#pragma unroll
-        for (int j = 0; j < NV; j++) a[j][0] += ld_agent(partial + (int64_t)i * NV + j);
-#pragma unroll
-    for (int j = 0; j < NV; j++) {
-#pragma unroll
-        for (int w = W / 2; w > 0; w >>= 1)   // fixed pairwise tree
-#pragma unroll
-            for (int q = 0; q < w; q++) a[j][q] += a[j][q + w];
-        r[j] = block_sum(a[j][0], sh);
-    }
-}
-// Tickets are two-level: block b first counts itself into sub-counter b % FOLD_SUB (a 128-B line
-// of its own), the last arrival of a sub-counter counts that sub-counter into the top counter, the
-// last arrival there finishes.  One flat counter cost k_step +10 us (rocprofv3, 148^3): its 2048
-// blocks end together and 2048 adds to ONE address are served one after the other at the memory
-// side; with 32 sub-counters the longest queue is 64.
-constexpr int FOLD_SUB = 32;
-constexpr int FOLD_LINE = 16;                               // uint64 per 128-B line
-constexpr int FOLD_WORDS = (1 + FOLD_SUB) * FOLD_LINE;      // one counter set: top + sub-counters
-struct fold_args {
-    unsigned long long *counter;  // counter set (zero between kernels); nullptr: no fold
-    unsigned nblocks;             // tickets this launch hands out (its grid size)
-    int np;                       // partials to add (>= nblocks: earlier launches may have left some)
-    double *out;                  // [NV] results
-    p2p_out po;                   // sharded, peer to peer: the sums go to every rank's mailbox instead (p2p_device.h)
-};
-constexpr p2p_out NO_P2P = {nullptr, 0, 0, 0};
-constexpr fold_args NO_FOLD = {nullptr, 0, 0, nullptr, NO_P2P};
-// the finished sums r[0..NV) (valid in thread 0) to where the consumer will look for them
-template <int NV>
-__device__ __forceinline__ void publish_sums(double *out, const p2p_out &po, const double r[NV], double *sh) {
-    if (po.pp) { p2p_publish<NV>(po, r, sh); return; }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int j = 0; j < NV; j++) out[j] = r[j];  // read by the NEXT kernel: a plain store will do
-    }
-}
-// Thread 0 of every block calls this after storing its partials with st_agent(); true (in every
-// thread) for the block that arrived last.  `sh_last` is one int of LDS.
-__device__ __forceinline__ bool fold_arrive(const fold_args &f, int *sh_last) {
-    if (threadIdx.x == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the partial has left this CU
-        const unsigned sub = blockIdx.x % FOLD_SUB;
-        const unsigned in_sub = (f.nblocks - sub + FOLD_SUB - 1) / FOLD_SUB;     // blocks b with b % SUB == sub
-        const unsigned nsub = f.nblocks < (unsigned)FOLD_SUB ? f.nblocks : (unsigned)FOLD_SUB;
-        int last = 0;
-        unsigned long long t = __hip_atomic_fetch_add(f.counter + (1 + sub) * FOLD_LINE, 1ULL, __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_AGENT);
-        if (t == (unsigned long long)in_sub - 1) {
-            t = __hip_atomic_fetch_add(f.counter, 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            last = t == (unsigned long long)nsub - 1;
-        }
-        *sh_last = last;
-    }
-    __syncthreads();
-    return *sh_last != 0;
-}
-template <int NV>
-__device__ __forceinline__ void fold_finish(const fold_args &f, const double *partial, double *sh) {
-    double r[NV];
-    sum_partials<NV>(partial, f.np, sh, r);
-    publish_sums<NV>(f.out, f.po, r, sh);
-    // every ticket of this launch has been drawn: clear the set for the next one
-    if (threadIdx.x <= FOLD_SUB)
-        __hip_atomic_store(f.counter + threadIdx.x * FOLD_LINE, 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// A producing kernel that returns without doing its work (the solve has stopped; every rank takes the same
-// decision) still owes its peers the arrival count of its reduction: their streams wait for it.
-__device__ __forceinline__ void fold_skip(const fold_args &f) {
-    if (f.counter && f.po.pp && f.po.signal && blockIdx.x == 0 && (int)threadIdx.x < f.po.pp->n)
-        __hip_atomic_fetch_add(f.po.pp->sig_red[threadIdx.x][f.po.slot], 1ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-__device__ __forceinline__ bool stopped(const int64_t *st, int64_t k) {
-    return st[T_ITER_A] < k || st[T_ITER_B] < k;
-}
-
-#include "cg_setup_kernels.inc"   // scaling (k_diag_scale, k_scale_matrix), value-stream copies (fp32, FIXED-48), the packed column stream (k_pack_cols), k_init / k_reduce / k_init_scalars
+#include "cg_setup_kernels.inc"   // scaling (k_diag_scale, k_diag_get, k_scale_matrix), k_init / k_init_b / k_reduce / k_init_scalars
 
 #include "spmv_kernels.inc"   // the products: k_spmv (one wavefront per slice), k_spmv_small (one workgroup per slice), k_spmv2 (two right-hand sides), k_spmv_fold (folded rows)
 
@@ -202,6 +60,57 @@ inline unsigned vec_grid(int64_t n) {
     if (b < 1) b = 1;
     return (unsigned)(b > VEC_BLOCKS ? VEC_BLOCKS : b);
 }
+
+// the one-block reduction of np blocks' partial sums (k_reduce), nv = 1 or 2 sums each
+inline void launch_reduce(hipStream_t stream, int nv, const double *partial, int np, double *out, p2p_out po, const int64_t *st, int64_t k) {
+    if (nv == 2) hipLaunchKernelGGL(k_reduce<2>, dim3(1), dim3(256), 0, stream, partial, np, out, po, st, k);
+    else hipLaunchKernelGGL(k_reduce<1>, dim3(1), dim3(256), 0, stream, partial, np, out, po, st, k);
+}
+
+// Timed spans of a stream: an event before and one behind each, recorded only when the context profiles; k is the
+// iteration a span belongs to.  drain() adds up the spans of iterations <= max_k (those it could measure) and forgets all.
+struct span_list {
+    const stan_ctx *ctx;
+    event_bag *bag;
+    std::vector<hipEvent_t> ev;
+    std::vector<int64_t> its;
+    void mark(hipStream_t s) { ev.push_back(bag->make()); hipEventRecord(ev.back(), s); }
+    void begin(hipStream_t s, int64_t k = 0) { if (ctx->profiling) { mark(s); its.push_back(k); } }
+    void end(hipStream_t s) { if (ctx->profiling) mark(s); }
+    void drain(int64_t max_k, double *ms, int64_t *n) {
+        for (size_t i = 0; i + 1 < ev.size(); i += 2) {
+            float t = 0;
+            if (its[i / 2] <= max_k && hipEventElapsedTime(&t, ev[i], ev[i + 1]) == hipSuccess) { *ms += t; (*n)++; }
+        }
+        ev.clear(); its.clear();
+    }
+};
+
+// The status polls of a loop that enqueues its iterations in chunks, ahead of the device: behind every chunk the status
+// words are copied into one of two pinned slots and an event is recorded; the host then waits for the PREVIOUS chunk's event
+// and shows that chunk's words to `stopped` -- one chunk is always queued while the host looks at the one before.
+struct chunk_poll {
+    static constexpr int64_t hard_cap = 0x7fffffff;   // iteration counter is int32 in the report
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int64_t *slot[2] = {nullptr, nullptr};            // pinned
+    int chunk_id = 0;
+    void setup(event_bag &events, int64_t *pinned, size_t stride) {
+        for (int i = 0; i < 2; i++) { ev[i] = events.make(hipEventDisableTiming); slot[i] = pinned + stride * i; }
+    }
+    // behind a chunk; k: the iteration the next chunk starts with.  wait(event) is the loop's way of waiting on the host.
+    template <typename WAIT, typename STOPPED>
+    int poll(stan_ctx *ctx, hipStream_t st, const int64_t *status, size_t words, int64_t k, WAIT wait, STOPPED stopped, bool *done) {
+        HIPCHK(ctx, hipMemcpyAsync(slot[chunk_id & 1], status, words * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipEventRecord(ev[chunk_id & 1], st));
+        if (chunk_id > 0) {
+            STANCHK(wait(ev[(chunk_id - 1) & 1]));
+            if (stopped(slot[(chunk_id - 1) & 1])) *done = true;
+        }
+        if (k >= hard_cap) *done = true;
+        chunk_id++;
+        return STAN_OK;
+    }
+};
 
 // k_spmv_small instead of k_spmv: decided by the GLOBAL number of block rows, so that a shard and the
 // whole matrix sum their rows in the same order
@@ -231,19 +140,6 @@ inline colstream fold_cols_of(const stan_ctx *ctx, const stan_matrix *K) {
 }
 inline colstream colstream_of(const stan_ctx *ctx, const stan_matrix *K) {
     return ctx->cols16 && K->d_cols16 ? make_colstream(K->d_cols16, K->d_colbase, K->d_pair_ptr, K->d_slice_packed, K->nslots) : NO_COLSTREAM;
-}
-// length of a gather vector of K (NOTE on the halo layout, below): the owned rows padded to whole slices, or the owned
-// rows and the halo columns behind them, whichever is longer
-inline int64_t gather_len(const stan_matrix *K) {
-    const int64_t npad = (int64_t)K->nslices * 64;
-    return 3 * (npad > K->nloc + K->nhalo ? npad : K->nloc + K->nhalo);
-}
-// status words for kernels launched outside a solve: never stopped
-int alloc_never_stopped(stan_ctx *ctx, dev_scope &b, int64_t **stt, hipStream_t s) {
-    STANCHK(b.alloc(stt, (size_t)T_NSTAT));
-    const int64_t init[T_NSTAT] = {0x7fffffffffffffffLL, 0x7fffffffffffffffLL, 0, 0, 0, 0, 0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(*stt, init, sizeof(init), hipMemcpyHostToDevice, s));
-    return STAN_OK;
 }
 
 // One product, as it is enqueued: y = A x with `dot` sums (k_spmv's DOT), or -- x2 given, dot = 1 -- y = A x and
@@ -351,111 +247,8 @@ unsigned launch_product(stan_ctx *ctx, stan_matrix *K, const product_args &a, in
     });
     return grid;
 }
-// y = A x with K's fp64 values, no sums: the products outside a solve
-unsigned launch_plain_product(stan_ctx *ctx, stan_matrix *K, const double *x, double *y, const int64_t *st, int which = 0) {
-    return launch_product(ctx, K, product_args{x, y, nullptr, nullptr, 0, nullptr, st, 1, STAN_PREC_FP64, nullptr, false}, which);
-}
 
 }  // namespace
-
-// Vectors of the CG for a matrix of K's sizes, owned by the context (see stan_cg_ws).
-int stan_cg_workspace(stan_ctx *ctx, const stan_matrix *K) {
-    const int64_t ng = gather_len(K);
-    const int64_t n3 = 3 * K->nloc > 0 ? 3 * K->nloc : 1;
-    stan_cg_ws &ws = ctx->ws;
-    if (ws.p && ws.ng >= ng && ws.n3 >= n3 && ws.ng <= ng + ng / 2 + 64) return STAN_OK;
-    stan_cg_workspace_free(ctx);
-    for (double **q : {&ws.xb[0], &ws.xb[1], &ws.p, &ws.r}) STANCHK(stan_dmalloc(ctx, q, (size_t)(ng > 0 ? ng : 1)));
-    for (double **q : {&ws.v, &ws.w, &ws.bh, &ws.sv}) STANCHK(stan_dmalloc(ctx, q, (size_t)n3));
-    ws.ng = ng; ws.n3 = n3;
-    return STAN_OK;
-}
-void stan_cg_workspace_free(stan_ctx *ctx) {
-    stan_cg_ws &ws = ctx->ws;
-    if (ws.vw_owner) {   // v, w carved out of one block (placement.hip, second stage): plain device memory, not the pool's
-        stan_dfree(ctx, ws.vw_owner);
-        ws.vw_owner = ws.v = ws.w = nullptr;
-        ctx->prof_placement_moved_vectors = 0;   // the next matrix of another size searches afresh
-    }
-    for (double **q : {&ws.xb[0], &ws.xb[1], &ws.p, &ws.r, &ws.v, &ws.w, &ws.bh, &ws.sv}) {
-        if (*q) stan_dfree(ctx, *q);
-        *q = nullptr;
-    }
-    ws.ng = ws.n3 = 0;
-}
-
-// Last resort of the placement search (placement.hip): no value candidate was clear of the vectors'
-// group, and all of them are still allocated -- so NEW vectors, allocated now, lie beyond them.
-// They are taken straight from the driver (a parked pool block would be the old memory again); the
-// caller probes with them and keeps them (commit) or not.
-int stan_cg_workspace_move(stan_ctx *ctx, const stan_matrix *K, bool commit, stan_cg_ws *saved) {
-    stan_cg_ws &ws = ctx->ws;
-    if (saved && !commit && saved->p == nullptr) {          // step 1: swap fresh vectors in, keep the old ones in *saved
-        if (!ws.p) return STAN_OK;
-        *saved = ws;
-        stan_cg_ws nw;   // (nw.vw_owner stays null: eight blocks of their own)
-        nw.ng = ws.ng; nw.n3 = ws.n3;
-        bool ok = true;
-        double **dst[8] = {&nw.xb[0], &nw.xb[1], &nw.p, &nw.r, &nw.v, &nw.w, &nw.bh, &nw.sv};
-        for (int i = 0; i < 8 && ok; i++)
-            ok = hipMalloc((void **)dst[i], (size_t)(i < 4 ? (nw.ng > 0 ? nw.ng : 1) : nw.n3) * 8) == hipSuccess;
-        if (!ok) {
-            (void)hipGetLastError();
-            for (double **q : dst) if (*q) hipFree(*q);
-            saved->p = nullptr;
-            return STAN_OK;   // no memory for it: keep what we have
-        }
-        ws = nw;
-        (void)K;
-        return STAN_OK;
-    }
-    if (!saved || saved->p == nullptr) return STAN_OK;
-    // step 2: keep the new vectors (release the old ones for real) or go back to the old ones
-    stan_cg_ws &drop = commit ? *saved : ws;
-    stan_cg_ws keep = commit ? ws : *saved;
-    if (drop.vw_owner) { ctx->pool.live.erase((void *)drop.vw_owner); hipFree(drop.vw_owner); drop.vw_owner = drop.v = drop.w = nullptr; }
-    for (double *q : {drop.xb[0], drop.xb[1], drop.p, drop.r, drop.v, drop.w, drop.bh, drop.sv}) {
-        if (!q) continue;
-        ctx->pool.live.erase((void *)q);
-        hipFree(q);
-    }
-    ws = keep;
-    if (commit && ctx->pool.enabled)   // the new blocks are pooled-class blocks from now on
-        for (double *q : {ws.xb[0], ws.xb[1], ws.p, ws.r}) if ((size_t)ws.ng * 8 >= stan_pool::MIN_BYTES) ctx->pool.live[(void *)q] = (size_t)ws.ng * 8;
-    if (commit && ctx->pool.enabled)
-        for (double *q : {ws.vw_owner ? (double *)nullptr : ws.v, ws.vw_owner ? (double *)nullptr : ws.w, ws.bh, ws.sv})
-            if (q && (size_t)ws.n3 * 8 >= stan_pool::MIN_BYTES) ctx->pool.live[(void *)q] = (size_t)ws.n3 * 8;
-    saved->p = nullptr;
-    return STAN_OK;
-}
-
-// Round 4 (tools/lab/spmv_steps_lab.cpp, profiles/r04/spmv_steps/): what makes a pairing slow is the vector the product
-// WRITES lying in the memory group of the values it reads -- the gather vector's place does not matter.  So the cheap move is
-// the two product buffers v and w alone, CARVED out of a block the caller has placed (a fresh small allocation would land in
-// whatever hole the allocator finds, not behind the caller's spacers).  set: v, w point into `block` (saved[] takes the old
-// v, w, owner) or, with block == nullptr, back to saved[]; adopt: the carved pair stays, `block` becomes its owner and the
-// saved pair is released.
-static int64_t vw_stride(const stan_cg_ws &ws) { return ((ws.n3 > 0 ? ws.n3 : 1) + 511) & ~(int64_t)511; }
-size_t stan_cg_products_bytes(const stan_ctx *ctx) { return (size_t)(2 * vw_stride(ctx->ws)) * 8; }
-void stan_cg_products_set(stan_ctx *ctx, double *block, double *saved[3]) {
-    stan_cg_ws &ws = ctx->ws;
-    if (block) {
-        saved[0] = ws.v; saved[1] = ws.w; saved[2] = ws.vw_owner;
-        ws.v = block; ws.w = block + vw_stride(ws);
-    } else {
-        ws.v = saved[0]; ws.w = saved[1]; ws.vw_owner = saved[2];
-    }
-}
-void stan_cg_products_adopt(stan_ctx *ctx, double *block, size_t bytes, double *saved[3]) {
-    stan_cg_ws &ws = ctx->ws;
-    if (saved[2]) { ctx->pool.live.erase((void *)saved[2]); hipFree(saved[2]); }
-    else for (int i = 0; i < 2; i++) if (saved[i]) { ctx->pool.live.erase((void *)saved[i]); hipFree(saved[i]); }
-    ws.v = block; ws.w = block + vw_stride(ws); ws.vw_owner = block;
-    // NOT a pooled block: 1-4 GB that hold 2 x n3 doubles would sit in the pool for the context's life once
-    // the workspace is re-sized, matching no later request; stan_cg_workspace_free gives it straight back to the driver
-    (void)bytes;
-    saved[0] = saved[1] = saved[2] = nullptr;
-}
 
 // Diagonal scaling of the matrix (once per matrix): A^ = S K S.  First the vector s (ensure_scale_vector), then the values:
 // by a pass of its own (ensure_scaled), or -- the fp64 loop on one rank -- by the loop's first product (k_spmv_first,
@@ -468,7 +261,7 @@ static int ensure_scale_vector(stan_ctx *ctx, stan_matrix *K) {
     if (K->nloc > 0)
         hipLaunchKernelGGL(k_diag_scale, dim3(nblk(K->nloc, 256)), dim3(256), 0, ctx->stream, K->nloc,
                            K->d_rowlen, K->d_posof, K->d_slot_ptr, K->d_cols, K->d_vals, K->d_scale);
-    if (ctx->comm || ctx->nranks > 1) {
+    if (stan_sharded(ctx)) {
         if (ctx->comm_p2p && ctx->p2p) {
             // Peer to peer, my neighbours write their rows straight into my halo region, which the k_fill above
             // has just initialised: nobody may write before everybody has done that.  One empty reduction
@@ -477,7 +270,7 @@ static int ensure_scale_vector(stan_ctx *ctx, stan_matrix *K) {
             // separate processes, where mapping the peers' vectors delays some ranks by milliseconds: a
             // neighbour's scaling factors arrived before the fill and were overwritten with 1.0.)
             const p2p_out po{stan_p2p_table(ctx), stan_p2p_reduce_slot(ctx), 3, 1};
-            hipLaunchKernelGGL(k_reduce<1>, dim3(1), dim3(256), 0, ctx->stream, (const double *)nullptr, 0, (double *)nullptr, po, (const int64_t *)nullptr, (int64_t)0);
+            launch_reduce(ctx->stream, 1, nullptr, 0, nullptr, po, nullptr, 0);
             STANCHK(stan_p2p_reduce_wait(ctx));
         }
         STANCHK(stan_comm_halo_exchange(ctx, K, K->d_scale));
@@ -506,86 +299,10 @@ static int ensure_scaled(stan_ctx *ctx, stan_matrix *K) {
     return STAN_OK;
 }
 
-int stan_matrix_make_fp32(stan_ctx *ctx, stan_matrix *K) {
-    if (K->d_vals32) return STAN_OK;
-    const int64_t n = K->nslots * 9 * 64;
-    STANCHK(stan_dmalloc_streamed(ctx, (void **)&K->d_vals32, (size_t)n * 4,
-                                  [&](const void *q, float *ms, bool self) {
-                                      return stan_spmv_probe(ctx, K, q, (size_t)n * 4, STAN_PREC_MIXED, ms, self);
-                                  }));
-    hipLaunchKernelGGL(k_to_fp32, dim3(vec_grid(n) * 4), dim3(VEC_T), 0, ctx->stream, K->d_vals,
-                       K->d_vals32, n);
-    HIPCHK(ctx, hipGetLastError());
-    return STAN_OK;
-}
-
-// FIXED-48 copy of the scaled values.  Returns STAN_OK with K->d_vals48 == nullptr when some
-// entry is not representable (K not SPD): the caller then streams the fp64 values.
-int stan_matrix_make_fx48(stan_ctx *ctx, stan_matrix *K) {
-    if (K->d_vals48 || K->fx48_refused) return STAN_OK;
-    if (K->nslots == 0) return STAN_OK;
-    uint32_t *out;
-    STANCHK(stan_dmalloc_streamed(ctx, (void **)&out, (size_t)K->nslots * 14 * 64 * 4,
-                                  [&](const void *q, float *ms, bool self) {
-                                      return stan_spmv_probe(ctx, K, q, (size_t)K->nslots * 14 * 64 * 4, STAN_PREC_FIXED48, ms, self);
-                                  }));
-    unsigned long long *d_bad = (unsigned long long *)(ctx->d_status + SS_COUNTER);
-    HIPCHK(ctx, hipMemsetAsync(d_bad, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(k_to_fx48, dim3((unsigned)nblk(K->nslots * 64, 256)), dim3(256), 0, ctx->stream,
-                       K->nslots, K->d_vals, out, d_bad);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_COUNTER, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->h_status[SS_COUNTER] != 0) { stan_dfree(ctx, out); K->fx48_refused = true; return STAN_OK; }
-    K->d_vals48 = out;
-    return STAN_OK;
-}
-
-// Packed column stream of K (struct colstream), built once per matrix; the int32 columns stay (the
-// assembly, scaling and export kernels use them).
-int stan_matrix_make_cols16(stan_ctx *ctx, stan_matrix *K) {
-    if (K->d_cols16 || K->nslices <= 0) return STAN_OK;
-    return stan_pack_columns(ctx, K->nslices, K->nslots, K->d_slot_ptr, K->d_cols, &K->d_cols16, &K->d_colbase, &K->d_pair_ptr,
-                             &K->d_slice_packed, &K->slots_packed, K->nloc, K->d_rowof, K->d_rowlen, &K->slots_packed2);
-}
-// the same for any sliced column stream (the folded copy of fold.hip has its own); *packed stays nullptr when the
-// pair index would not fit an int32
-int stan_pack_columns(stan_ctx *ctx, int32_t nslices, int64_t nslots, const int32_t *d_slot_ptr, const int32_t *d_cols,
-                      uint32_t **packed_out, int32_t **base_out, int32_t **pair_ptr_out, uint8_t **ok_out, int64_t *slots_packed,
-                      int64_t nloc, const int32_t *d_rowof, const int32_t *d_rowlen, int64_t *slots_packed2) {
-    hipStream_t st_ = ctx->stream;
-    dev_scope bufs(ctx);
-    int32_t *cnt; int64_t *ptr64;
-    STANCHK(bufs.alloc(&cnt, (size_t)nslices + 1));
-    STANCHK(bufs.alloc(&ptr64, (size_t)nslices + 2));
-    hipLaunchKernelGGL(k_pair_counts, dim3(nblk(nslices, 256)), dim3(256), 0, st_, nslices, d_slot_ptr, cnt);
-    STANCHK(stan_scan_total(ctx, cnt, ptr64, nslices, SS_H_NSLOTS));
-    HIPCHK(ctx, hipStreamSynchronize(st_));
-    const int64_t npairs = ctx->h_status[SS_H_NSLOTS];
-    if (npairs >= ((int64_t)1 << 31)) return STAN_OK;   // pair index is int32: keep the plain columns
-    STANCHK(stan_slot_ptr_narrow(ctx, ptr64, nslices, pair_ptr_out));
-    // one allocation: [n] base, [n] base2, [nslices] cmask (64-bit words), n = max(nslots, 1): make_colstream
-    const size_t nb_ = (size_t)(nslots > 0 ? nslots : 1);
-    STANCHK(stan_dmalloc(ctx, base_out, 2 * nb_ + 2 * (size_t)nslices + 2));
-    STANCHK(stan_dmalloc(ctx, ok_out, (size_t)nslices));
-    uint32_t *packed;
-    STANCHK(stan_dmalloc(ctx, &packed, (size_t)(npairs > 0 ? npairs : 1) * 64));
-    int32_t *b2_ = *base_out + nb_;
-    unsigned long long *cm_ = (unsigned long long *)(*base_out + 2 * nb_);
-    if (((uintptr_t)cm_ & 7) != 0) cm_ = (unsigned long long *)((uintptr_t)cm_ + 4);   // (never: 2 n ints from an aligned block)
-    hipLaunchKernelGGL(k_pack_cols, dim3(nblk(nslices, 4)), dim3(256), 0, st_, nslices, nloc, d_slot_ptr, d_cols, d_rowof, d_rowlen,
-                       *pair_ptr_out, packed, *base_out, b2_, cm_, *ok_out);
-    unsigned long long *d_cnt = (unsigned long long *)(ctx->d_status + SS_COUNTER);   // two words: SS_COUNTER, SS_H_ERRCOPY
-    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, 16, st_));
-    hipLaunchKernelGGL(k_count_ok, dim3(nblk(nslices, 256)), dim3(256), 0, st_, nslices, *ok_out, d_slot_ptr, d_cnt);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_COUNTER, d_cnt, 16, hipMemcpyDeviceToHost, st_));
-    HIPCHK(ctx, hipStreamSynchronize(st_));
-    *slots_packed = ctx->h_status[SS_COUNTER];
-    if (slots_packed2) *slots_packed2 = ctx->h_status[SS_COUNTER + 1];
-    *packed_out = packed;
-    return STAN_OK;
-}
+// the matrix carries S K S from its first solve on -- or from its first export: stan_hip_matrix_to_csr divides the
+// scaled values on the way out, whether or not a solve has happened, so an export before a solve and one after it are
+// the same bits (rounds 1-4 un-scaled the values in place for an export and re-scaled them for the next solve)
+int stan_matrix_ensure_scaled(stan_ctx *ctx, stan_matrix *K) { return ensure_scaled(ctx, K); }
 
 // NOTE on the halo layout: vectors that are gathered by the SpMV (p, x) hold the owned
 // block rows first, padded to whole slices, then the halo block columns:
@@ -665,13 +382,11 @@ struct cg_run {
     const stan_p2p_dev *p2p_tab = nullptr;
     unsigned vg = 1;
     int64_t its_before_restart = 1;
-    static constexpr int64_t hard_cap = 0x7fffffff;   // iteration counter is int32 in the report
     int64_t *h_st = nullptr;          // pinned status words
     double *h_sc = nullptr;           // pinned copy of the scalars
-    hipEvent_t poll[2] = {nullptr, nullptr};
-    // profile
-    std::vector<hipEvent_t> red_ev, halo_ev, spmv_ev, spmv2_ev, spmv64_ev;
-    std::vector<int64_t> spmv_k, spmv2_k;   // iteration of each timed launch
+    chunk_poll poll;
+    // profile: reductions' and halos' exchanges, the products (one right-hand side, two, the fp64 products of a reduced-precision solve)
+    span_list red_sp{ctx, &events}, halo_sp{ctx, &events}, spmv_sp{ctx, &events}, spmv2_sp{ctx, &events}, spmv64_sp{ctx, &events};
     int64_t n_coll = 0, n_wait = 0, n_launch = 0, n_enqueued = 0;
     double prof_spmv_ms = 0, prof_spmv2_ms = 0, prof_spmv64_ms = 0;
     int64_t prof_spmv_n = 0, prof_spmv2_n = 0, prof_spmv64_n = 0;
@@ -698,15 +413,14 @@ struct cg_run {
     void reduce_if_unfolded(int np, int nv, double *out, p2p_out po = NO_P2P, int64_t k_ = -1) {
         if (foldr || np <= 0) return;
         const int64_t *sk = k_ >= 1 ? stt : nullptr;   // (k_init's sum is formed before the status exists)
-        if (nv == 2) hipLaunchKernelGGL(k_reduce<2>, dim3(1), dim3(256), 0, st_, partial, np, out, po, sk, k_);
-        else hipLaunchKernelGGL(k_reduce<1>, dim3(1), dim3(256), 0, st_, partial, np, out, po, sk, k_);
+        launch_reduce(st_, nv, partial, np, out, po, sk, k_);
     }
     // One exchange point of the sharded loop: RCCL all-reduce of `count` scalars in place, or the stream
     // wait for every rank's arrival; returns where the consumers find the sums.
     int exchange_sums(double *scalars, int count, red_src *rs) {
         *rs = red_src{nullptr, 0, nullptr, 0};
         if (!dist) return STAN_OK;
-        if (ctx->profiling) { red_ev.push_back(events.make()); hipEventRecord(red_ev.back(), st_); }
+        red_sp.begin(st_);
         int rc_ = STAN_OK;
         if (p2p) {
             *rs = red_src{stan_p2p_mailbox(ctx, stan_p2p_reduce_slot(ctx)), ctx->nranks, nullptr, 0};
@@ -716,14 +430,14 @@ struct cg_run {
             rc_ = stan_comm_allreduce_sum_f64(ctx, scalars, (size_t)count);
             n_coll++;
         }
-        if (ctx->profiling) { red_ev.push_back(events.make()); hipEventRecord(red_ev.back(), st_); }
+        red_sp.end(st_);
         return rc_;
     }
     int halo(double *x) {
-        if (ctx->profiling) { halo_ev.push_back(events.make()); hipEventRecord(halo_ev.back(), st_); }
+        halo_sp.begin(st_);
         const int rc_ = stan_comm_halo_exchange(ctx, K, x);
         if (p2p && !K->nbr.empty()) n_wait++;
-        if (ctx->profiling) { halo_ev.push_back(events.make()); hipEventRecord(halo_ev.back(), st_); }
+        halo_sp.end(st_);
         return rc_;
     }
 
@@ -732,13 +446,8 @@ struct cg_run {
     // folded into the last launch of the product, or formed by k_reduce.  kind: the value stream (the loop's own, or
     // STAN_PREC_FP64 for the check / refresh products of a reduced-precision solve, `extra`: timed apart).
     int product(double *x, double *x2, double *y, int dot, double *out, int64_t k, p2p_out po, int kind, bool extra = false) {
-        std::vector<hipEvent_t> &ev = extra ? spmv64_ev : x2 ? spmv2_ev : spmv_ev;
-        if (ctx->profiling) {
-            hipEvent_t a = events.make(), b = events.make();
-            hipEventRecord(a, st_);
-            ev.push_back(a); ev.push_back(b);
-            if (!extra) (x2 ? spmv2_k : spmv_k).push_back(k);
-        }
+        span_list &span = extra ? spmv64_sp : x2 ? spmv2_sp : spmv_sp;
+        span.begin(st_, k);
         auto go = [&](int which, hipStream_t s, bool last) -> unsigned {
             n_launch++;
             // lazy_scale: the first product of this matrix (one rank, fp64 stream, all slices) scales it on the way
@@ -767,13 +476,11 @@ struct cg_run {
         }
         if (dot && !folded) {
             if (parts > 0 || po.pp) {   // (peer to peer: a rank that owns no rows still sends its zeros)
-                const int64_t *sk = k >= 1 ? stt : nullptr;
-                if (dot == 2) hipLaunchKernelGGL(k_reduce<2>, dim3(1), dim3(256), 0, st_, partial, (int)parts, out, po, sk, k);
-                else hipLaunchKernelGGL(k_reduce<1>, dim3(1), dim3(256), 0, st_, partial, (int)parts, out, po, sk, k);
+                launch_reduce(st_, dot, partial, (int)parts, out, po, k >= 1 ? stt : nullptr, k);
                 n_launch++;
             } else HIPCHK(ctx, hipMemsetAsync(out, 0, 8 * dot, st_));   // a rank that owns no rows
         }
-        if (ctx->profiling) hipEventRecord(ev.back(), st_);
+        span.end(st_);
         return STAN_OK;
     }
 
@@ -794,7 +501,7 @@ int cg_run::setup() {
         ev0 = events.make(); ev1 = events.make();
         hipEventRecord(ev0, st_);
     }
-    dist = ctx->comm != nullptr || ctx->nranks > 1;  // exchanges in the loop
+    dist = stan_sharded(ctx);  // exchanges in the loop
     // peer to peer (one-process group handle, STAN_OPT_COMM_P2P): no RCCL call below this line
     p2p = dist && ctx->comm_p2p && ctx->p2p != nullptr;
     if (p2p && ctx->p2p->broken.load()) {   // refused at once: not another collective with a peer that is gone
@@ -816,7 +523,7 @@ int cg_run::setup() {
     // stream of one rank, the large-system kernel in its default variant, no folded copy (its values are made from the
     // scaled ones), a first product that is a plain one (a residual refresh at iteration 1 is a two-product pass).
     lazy_scale = false;
-    if (!K->scaled && ctx->cg_lazy_scaling && !(ctx->comm != nullptr || ctx->nranks > 1) && precision_mode == STAN_PREC_FP64 &&
+    if (!K->scaled && ctx->cg_lazy_scaling && !dist && precision_mode == STAN_PREC_FP64 &&
         !stan_small_system(ctx, K) && ctx->spmv_variant < 0 && ctx->cg_rupdate != 1 && K->nslices > 0) {
         const int rc_plan = stan_matrix_make_folded(ctx, K, STAN_PREC_FP64, true);   // (decides K->fold_state, touches no value)
         if (rc_plan == STAN_E_ALLOC) { stan_matrix_abandon_folding(ctx, K); ctx->err.clear(); }
@@ -880,8 +587,7 @@ int cg_run::setup() {
     }
     h_st = ctx->h_status + SS_H_CG_STATUS;  // pinned
     h_sc = (double *)(ctx->h_status + SS_H_CG_SCALARS);
-    poll[0] = events.make(hipEventDisableTiming);
-    poll[1] = events.make(hipEventDisableTiming);
+    poll.setup(events, h_st, 8);
     return STAN_OK;
 }
 
@@ -890,8 +596,7 @@ int cg_run::setup() {
 // otherwise b^ = the vector in r (a refinement pass: the fp64 residual fp64_check left there).
 int cg_run::begin_pass(bool from_F, double eps_pass, bool *done) {
     {
-        fold_args f = fold_to(1, sc + S_VMV, p2p_to(0, true));
-        f.nblocks = vg; f.np = (int)vg;
+        const fold_args f = vec_fold(sc + S_VMV, p2p_to(0, true));
         if (from_F)
             hipLaunchKernelGGL(k_init, dim3(vg), dim3(VEC_T), 0, st_, n3, dof0, K->d_red, d_F, K->d_scale,
                                bh, xb[0], r, p, partial, f);
@@ -912,9 +617,9 @@ int cg_run::begin_pass(bool from_F, double eps_pass, bool *done) {
 
 int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
     int64_t k = 1;
-    int chunk_id = 0;
     bool done = false;
     int rc = STAN_OK;
+    poll.chunk_id = 0;
     red_src rs_sr{nullptr, 0, nullptr, 0}, rs_vmv{nullptr, 0, nullptr, 0}, rs_r2{nullptr, 0, nullptr, 0};
     // STAN_OPT_CG_REFINE = 2 on a reduced-precision stream: the periodic residual recomputation (alglib's
     // ItsBeforeRUpdate) multiplies with the fp64 values -- the recurrence is re-anchored to the true residual
@@ -928,7 +633,7 @@ int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
     const int rupdate = refresh64 ? (ctx->cg_rupdate > 0 ? REFRESH64 : 0) : ctx->cg_rupdate;
     if (sr) {   // w_0 = A r_0 with gamma_0, delta_0 (merit_0 = 0 sits in the zeroed scalars)
         if (p2p)         // ... or, peer to peer, is sent as this rank's zero into the slot of the first reduction
-            hipLaunchKernelGGL(k_reduce<1>, dim3(1), dim3(256), 0, st_, partial, 0, sc + S_SR_MERIT, p2p_to(2, false), (const int64_t *)nullptr, (int64_t)0);
+            launch_reduce(st_, 1, partial, 0, sc + S_SR_MERIT, p2p_to(2, false), nullptr, 0);
         rc = product(r, nullptr, w, 2, sc + S_SR_GAMMA, 0, p2p_to(0, true), vs);
         if (rc == STAN_OK) rc = exchange_sums(sc + S_SR_GAMMA, 3, &rs_sr);
     }
@@ -936,7 +641,7 @@ int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
     const int chunk = dist ? CHUNK_DIST : CHUNK;
     while (!done && rc == STAN_OK) {
         // enqueue one chunk of iterations
-        for (int c = 0; c < chunk && k < hard_cap; c++, k++) {
+        for (int c = 0; c < chunk && k < chunk_poll::hard_cap; c++, k++) {
             const bool refresh = rupdate > 0 && (k % rupdate) == 0;
             if (sr) {
                 sr_args a;
@@ -982,8 +687,7 @@ int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
             // iteration at 148^3) unless the merit sum needs x' here or a literal refresh multiplies it
             a.defer_x = (ctx->cg_defer_x && !a.merit && a.refresh != 1) ? 1 : 0;
             a.fold = vec_fold(sc + S_R2NEW, a.refresh == 1 ? NO_P2P : po_r);   // refresh 1: k_refresh forms the sums
-            if (ctx->vec_store_nt & 2) hipLaunchKernelGGL(k_step<true>, dim3(vg), dim3(VEC_T), 0, st_, a);
-            else hipLaunchKernelGGL(k_step<false>, dim3(vg), dim3(VEC_T), 0, st_, a);
+            hipLaunchKernelGGL((ctx->vec_store_nt & 2) ? k_step<true> : k_step<false>, dim3(vg), dim3(VEC_T), 0, st_, a);
             n_launch++;
             if (a.refresh == 1) {
                 // a -5/-4 stop of this iteration is caught by k_refresh/k_update (ITER_B <= k)
@@ -998,30 +702,18 @@ int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
             if (rc) break;
             const double *ux = a.defer_x ? a.xcur : nullptr;
             double *uxn = a.defer_x ? a.xnext : nullptr;
-            if (ctx->vec_store_nt & 1)
-                hipLaunchKernelGGL(k_update<true>, dim3(vg), dim3(VEC_T), 0, st_, n3, k, sc, stt, eps_pass,
-                                   (int64_t)max_its_pass, its_before_restart, ctx->cg_merit_stop ? 1 : 0, r, p, ux, uxn, rs_r2, rs_vmv);
-            else
-                hipLaunchKernelGGL(k_update<false>, dim3(vg), dim3(VEC_T), 0, st_, n3, k, sc, stt, eps_pass,
-                                   (int64_t)max_its_pass, its_before_restart, ctx->cg_merit_stop ? 1 : 0, r, p, ux, uxn, rs_r2, rs_vmv);
+            hipLaunchKernelGGL((ctx->vec_store_nt & 1) ? k_update<true> : k_update<false>, dim3(vg), dim3(VEC_T), 0, st_, n3, k, sc, stt,
+                               eps_pass, (int64_t)max_its_pass, its_before_restart, ctx->cg_merit_stop ? 1 : 0, r, p, ux, uxn, rs_r2, rs_vmv);
             n_launch++;
         }
         if (rc) break;
         // poll: read the status of the PREVIOUS chunk while this one runs
-        int64_t *slot = h_st + 8 * (chunk_id & 1);
-        HIPCHK(ctx, hipMemcpyAsync(slot, stt, T_NSTAT * 8, hipMemcpyDeviceToHost, st_));
-        HIPCHK(ctx, hipEventRecord(poll[chunk_id & 1], st_));
-        if (chunk_id > 0) {
-            STANCHK(cg_wait(ctx, p2p, st_, poll[(chunk_id - 1) & 1]));
-            int64_t *prev = h_st + 8 * ((chunk_id - 1) & 1);
-            if (prev[T_TYPE] != 0) done = true;
-        }
-        if (k >= hard_cap) done = true;
+        STANCHK(poll.poll(ctx, st_, stt, T_NSTAT, k, [&](hipEvent_t e) { return cg_wait(ctx, p2p, st_, e); },
+                          [](const int64_t *w) { return w[T_TYPE] != 0; }, &done));
         if (dist && (ctx->comm_broken.load() || (ctx->p2p && ctx->p2p->broken.load()))) {
             ctx->err = "cg: a peer rank failed (the exchanges were aborted)";
             rc = STAN_E_COMM;
         }
-        chunk_id++;
     }
     n_enqueued += k - 1;
     if (p2p) {   // never a blocking wait on a stream that may sit in front of a peer that is gone
@@ -1061,22 +753,8 @@ int cg_run::pass(bool from_F, double eps_pass, int32_t max_its_pass) {
 // work count: the host runs up to two chunks ahead of the status it polls, so a converged solve is followed by a few
 // dozen launches that return at once (3-4 us each); averaging those in made the SpMV look ~3 % faster than it is.
 void cg_run::account_pass() {
-    if (!ctx->profiling) return;
-    for (size_t i = 0; i + 1 < spmv_ev.size(); i += 2) {
-        if (spmv_k[i / 2] > pass_its) continue;
-        float t = 0;
-        hipEventElapsedTime(&t, spmv_ev[i], spmv_ev[i + 1]);
-        prof_spmv_ms += t;
-        prof_spmv_n++;
-    }
-    for (size_t i = 0; i + 1 < spmv2_ev.size(); i += 2) {
-        if (spmv2_k[i / 2] > pass_its) continue;
-        float t = 0;
-        hipEventElapsedTime(&t, spmv2_ev[i], spmv2_ev[i + 1]);
-        prof_spmv2_ms += t;
-        prof_spmv2_n++;
-    }
-    spmv_ev.clear(); spmv_k.clear(); spmv2_ev.clear(); spmv2_k.clear();
+    spmv_sp.drain(pass_its, &prof_spmv_ms, &prof_spmv_n);
+    spmv2_sp.drain(pass_its, &prof_spmv2_ms, &prof_spmv2_n);
 }
 
 // ---- the fp64 check of a reduced-precision solve ----------------------------------------------------------------
@@ -1096,15 +774,7 @@ int cg_run::fp64_check(double *xg, const double *b, double *r2_out) {
     HIPCHK(ctx, hipMemcpyAsync(h_sc, sc, S_NSCAL * 8, hipMemcpyDeviceToHost, st_));
     STANCHK(cg_wait(ctx, p2p, st_, nullptr));
     *r2_out = h_sc[S_CHK_R2];
-    if (ctx->profiling) {
-        for (size_t i = 0; i + 1 < spmv64_ev.size(); i += 2) {
-            float t = 0;
-            hipEventElapsedTime(&t, spmv64_ev[i], spmv64_ev[i + 1]);
-            prof_spmv64_ms += t;
-            prof_spmv64_n++;
-        }
-        spmv64_ev.clear();
-    }
+    spmv64_sp.drain(chunk_poll::hard_cap, &prof_spmv64_ms, &prof_spmv64_n);   // (every one: they carry the iteration of a refresh, or 0)
     return STAN_OK;
 }
 
@@ -1130,7 +800,7 @@ int cg_run::finish(const double *x_result, int type, int64_t its, double rel_rec
     HIPCHK(ctx, hipStreamSynchronize(st_));
 
     if (term_out) *term_out = type;
-    if (iters_out) *iters_out = (int32_t)(its > hard_cap ? hard_cap : its);
+    if (iters_out) *iters_out = (int32_t)(its > chunk_poll::hard_cap ? chunk_poll::hard_cap : its);
     if (rel_res_out) *rel_res_out = rel64 >= 0 ? rel64 : rel_rec;
     if (!ctx->profiling) return STAN_OK;
     float ms = 0;
@@ -1151,21 +821,17 @@ int cg_run::finish(const double *x_result, int type, int64_t its, double rel_rec
     const int64_t blk_bytes = vs == STAN_PREC_FIXED48 ? 60 : vs == STAN_PREC_MIXED ? 40 : 76;
     // bytes of the format actually streamed: a block of a packed slice carries a 2-B column offset
     // instead of a 4-B index (+ 4 B per slot for its base, shared by 64 rows)
-    const bool packed = ctx->cols16 && K->d_cols16;
-    const double packed_frac = packed && K->nslots > 0 ? (double)K->slots_packed / (double)K->nslots : 0.0;
-    pf.spmv_bytes = K->nblocks * blk_bytes + 3 * K->nloc * 16 + K->nloc * 4
-                    - (int64_t)(packed_frac * (double)K->nblocks * 2.0) + (packed ? (K->slots_packed + K->slots_packed2) * 4 : 0);
+    // (the folded copy has a packed column stream of its own, one base per slot, and 4 B of plan per row)
     const bool folded = ctx->row_folding != 0 && (vs == STAN_PREC_FIXED48 ? K->d_fold_vals48 != nullptr : vs == STAN_PREC_MIXED ? K->d_fold_vals32 != nullptr
                                                                                                                                 : K->d_fold_vals != nullptr);
-    if (folded) {   // its own packed column stream, 4 B of plan per row
-        const bool fp = ctx->cols16 && K->d_fold_cols16;
-        const double ff = fp && K->nfslots > 0 ? (double)K->fold_slots_packed / (double)K->nfslots : 0.0;
-        pf.spmv_bytes = K->nblocks * blk_bytes + 3 * K->nloc * 16 + K->nloc * 8 - (int64_t)(ff * (double)K->nblocks * 2.0) +
-                        (fp ? K->fold_slots_packed * 4 : 0);
-        pf.col_slots_packed = fp ? K->fold_slots_packed : 0;
-    }
+    const bool packed = ctx->cols16 && K->d_cols16, read_packed = folded ? ctx->cols16 && K->d_fold_cols16 : packed;
+    const int64_t slots = folded ? K->nfslots : K->nslots, slots_packed = folded ? K->fold_slots_packed : K->slots_packed;
+    const int64_t bases = folded ? K->fold_slots_packed : K->slots_packed + K->slots_packed2;
+    const double packed_frac = read_packed && slots > 0 ? (double)slots_packed / (double)slots : 0.0;
+    pf.spmv_bytes = K->nblocks * blk_bytes + 3 * K->nloc * 16 + K->nloc * (folded ? 8 : 4)
+                    - (int64_t)(packed_frac * (double)K->nblocks * 2.0) + (read_packed ? bases * 4 : 0);
     pf.repacked_streams = folded ? 1 : 0;
-    pf.col_slots_packed = packed ? K->slots_packed : 0;
+    pf.col_slots_packed = packed ? K->slots_packed : 0;   // (the padded stream's count even when the products read the folded copy: looks unintended, kept)
     pf.value_stream = vs;
     // vector passes of one classic iteration: k_step reads r, v (+ p, x unless deferred; + b^ for the
     // merit sum) and writes r (+ x); k_update reads r, p (+ x when deferred) and writes p (+ x)
@@ -1175,15 +841,10 @@ int cg_run::finish(const double *x_result, int type, int64_t its, double rel_rec
     pf.loop_stream_waits = n_wait;
     pf.loop_iterations_enqueued = n_enqueued;
     // what the stream spent in the exchanges (RCCL launches, or peer-to-peer waits): events around each
-    auto sum_pairs = [](const std::vector<hipEvent_t> &ev, double *tot, int64_t *cnt) {
-        *tot = 0; *cnt = 0;
-        for (size_t i = 0; i + 1 < ev.size(); i += 2) {
-            float t = 0;
-            if (hipEventElapsedTime(&t, ev[i], ev[i + 1]) == hipSuccess) { *tot += t; (*cnt)++; }
-        }
-    };
-    sum_pairs(red_ev, &pf.comm_reduce_ms_total, &pf.comm_reduce_calls);
-    sum_pairs(halo_ev, &pf.comm_halo_ms_total, &pf.comm_halo_calls);
+    pf.comm_reduce_ms_total = pf.comm_halo_ms_total = 0;
+    pf.comm_reduce_calls = pf.comm_halo_calls = 0;
+    red_sp.drain(chunk_poll::hard_cap, &pf.comm_reduce_ms_total, &pf.comm_reduce_calls);
+    halo_sp.drain(chunk_poll::hard_cap, &pf.comm_halo_ms_total, &pf.comm_halo_calls);
     return STAN_OK;
 }
 
@@ -1258,182 +919,6 @@ int stan_cg_device(stan_ctx *ctx, stan_matrix *K, const double *d_F, double eps_
     return R.finish(x_result, type, its, rel_rec, rel64, passes, term_out, iters_out, rel_res_out);
 }
 
-// y = K x on the reduced system (test helper; single rank)
-int stan_spmv_reduced(stan_ctx *ctx, stan_matrix *K, const double *d_x, double *d_y) {
-    if (ctx->nranks != 1) { ctx->err = "spmv: single-rank contexts only"; return STAN_E_UNSUPPORTED; }
-    hipStream_t st_ = ctx->stream;
-    const int64_t n3 = 3 * K->nloc, npad3 = 3 * (int64_t)K->nslices * 64;
-    dev_scope bufs(ctx);
-    double *xf, *yf; int64_t *stt;
-    STANCHK(bufs.alloc(&xf, (size_t)npad3));
-    STANCHK(bufs.alloc(&yf, (size_t)npad3));
-    STANCHK(alloc_never_stopped(ctx, bufs, &stt, st_));
-    HIPCHK(ctx, hipMemsetAsync(xf, 0, (size_t)npad3 * 8, st_));
-    const double *sdiv = K->scaled ? K->d_scale : nullptr;
-    // K x = S^-1 (A^ (S^-1 x)) when the matrix already carries its scaling
-    hipLaunchKernelGGL(k_expand, dim3(vec_grid(n3)), dim3(VEC_T), 0, st_, n3, (int64_t)0, K->d_red,
-                       d_x, sdiv, xf);
-    launch_plain_product(ctx, K, xf, yf, stt);
-    // compress (and undo the row scaling)
-    hipLaunchKernelGGL(k_compress_div, dim3(vec_grid(n3)), dim3(VEC_T), 0, st_, n3, K->d_red, sdiv, yf, d_y);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipStreamSynchronize(st_));
-    return STAN_OK;
-}
-
-// diag[d - red[d]] = K_dd on the free DOFs (single rank)
-int stan_matrix_diagonal(stan_ctx *ctx, stan_matrix *K, double *d_diag) {
-    if (ctx->nranks != 1) { ctx->err = "matrix_diagonal: single-rank contexts only"; return STAN_E_UNSUPPORTED; }
-    hipStream_t st_ = ctx->stream;
-    const int64_t n3 = 3 * K->nloc;
-    dev_scope bufs(ctx);
-    double *full;
-    STANCHK(bufs.alloc(&full, (size_t)(n3 > 0 ? n3 : 1)));
-    if (K->nloc > 0)
-        hipLaunchKernelGGL(k_diag_get, dim3(nblk(K->nloc, 256)), dim3(256), 0, st_, K->nloc, K->d_rowlen, K->d_posof,
-                           K->d_slot_ptr, K->d_cols, K->d_vals, K->scaled ? K->d_scale : (const double *)nullptr, full);
-    hipLaunchKernelGGL(k_compress_div, dim3(vec_grid(n3)), dim3(VEC_T), 0, st_, n3, K->d_red, (const double *)nullptr, full, d_diag);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipStreamSynchronize(st_));
-    return STAN_OK;
-}
-
-// y_owned = A_local x_local, x_local = [owned rows | halo columns] (plan checks; any rank)
-int stan_spmv_local(stan_ctx *ctx, stan_matrix *K, const double *d_x, double *d_y) {
-    dev_scope bufs(ctx);
-    int64_t *stt;
-    STANCHK(alloc_never_stopped(ctx, bufs, &stt, ctx->stream));
-    if (K->d_sl_bnd) {  // sharded: interior + boundary lists must cover every slice exactly once
-        HIPCHK(ctx, hipMemsetAsync(d_y, 0xff, (size_t)(3 * K->nloc) * 8, ctx->stream));  // NaN
-        launch_plain_product(ctx, K, d_x, d_y, stt, 1);
-        launch_plain_product(ctx, K, d_x, d_y, stt, 2);
-    } else
-        launch_plain_product(ctx, K, d_x, d_y, stt);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return STAN_OK;
-}
-
-// What stan_spmv_bench_device and stan_spmv_probe time: the product with its p.Ap sum, of the value stream `vals` (nullptr:
-// K's own of that precision), on the CG's own gather vector and product buffer -- the pair (value block, vector blocks)
-// that is timed is the pair the solve will run on -- or, self_block given, on vectors carved out of the front of that
-// block (a.x stays nullptr when they do not fit).  The gather vector is filled with ones.
-static int timed_product_setup(stan_ctx *ctx, stan_matrix *K, int32_t precision, const void *vals, void *self_block,
-                               size_t self_bytes, dev_scope &bufs, product_args &a) {
-    hipStream_t st_ = ctx->stream;
-    const int64_t ng = gather_len(K), ngpad = (ng + 511) & ~(int64_t)511;
-    STANCHK(stan_cg_workspace(ctx, K));
-    double *x = ctx->ws.p, *y = ctx->ws.v, *partial;
-    int64_t *stt;
-    if (self_block) {
-        if ((size_t)(ngpad + 3 * K->nloc) * 8 > self_bytes) return STAN_OK;
-        x = (double *)self_block;
-        y = x + ngpad;
-    }
-    STANCHK(bufs.alloc(&partial, 2 * (size_t)K->nslices + 2));   // k_spmv_small leaves one partial per slice
-    STANCHK(alloc_never_stopped(ctx, bufs, &stt, st_));
-    hipLaunchKernelGGL(k_fill, dim3(vec_grid(ng)), dim3(VEC_T), 0, st_, x, ng, 1.0);
-    a = product_args{x, y, nullptr, nullptr, 1, partial, stt, 1, precision, vals, false};
-    return STAN_OK;
-}
-
-int stan_spmv_bench_device(stan_ctx *ctx, stan_matrix *K, int32_t precision_mode, int32_t reps,
-                           double *avg_ms) {
-    hipStream_t st_ = ctx->stream;
-    if (precision_mode == STAN_PREC_MIXED) STANCHK(stan_matrix_make_fp32(ctx, K));
-    if (precision_mode == STAN_PREC_FIXED48) {
-        STANCHK(ensure_scaled(ctx, K));
-        STANCHK(stan_matrix_make_fx48(ctx, K));
-        if (!K->d_vals48) { ctx->err = "spmv_bench: matrix not representable in FIXED48"; return STAN_E_UNSUPPORTED; }
-    }
-    dev_scope bufs(ctx);
-    product_args pa{};
-    STANCHK(timed_product_setup(ctx, K, precision_mode, nullptr, nullptr, 0, bufs, pa));
-    event_bag events;
-    hipEvent_t a = events.make(), b = events.make();
-    for (int i = 0; i < 3; i++) launch_product(ctx, K, pa);
-    hipEventRecord(a, st_);
-    for (int i = 0; i < reps; i++) launch_product(ctx, K, pa);
-    hipEventRecord(b, st_);
-    HIPCHK(ctx, hipEventSynchronize(b));
-    float ms = 0;
-    hipEventElapsedTime(&ms, a, b);
-    *avg_ms = reps > 0 ? ms / reps : 0;
-    HIPCHK(ctx, hipGetLastError());
-    return STAN_OK;
-}
-
-// `reps` sweeps of k_value_stream over K's resident fp64 values (see the kernel): average ms per sweep and the bytes one
-// sweep reads (the slots' values: padded slots are streamed like real ones, as the product streams them).
-int stan_stream_bench_device(stan_ctx *ctx, stan_matrix *K, int32_t reps, double *avg_ms, int64_t *bytes) {
-    hipStream_t st_ = ctx->stream;
-    *avg_ms = 0;
-    *bytes = (int64_t)K->nslots * 64 * 72;
-    if (K->nslices <= 0 || !K->d_vals) return STAN_OK;
-    const unsigned grid = nblk(K->nslices, 4);
-    dev_scope bufs(ctx);
-    double *sink;
-    STANCHK(bufs.alloc(&sink, (size_t)grid));
-    event_bag events;
-    hipEvent_t a = events.make(), b = events.make();
-    auto one = [&]() { hipLaunchKernelGGL(k_value_stream, dim3(grid), dim3(256), 0, st_, K->nslices, K->d_slot_ptr, K->d_vals, sink); };
-    for (int i = 0; i < 3; i++) one();
-    hipEventRecord(a, st_);
-    for (int i = 0; i < reps; i++) one();
-    hipEventRecord(b, st_);
-    HIPCHK(ctx, hipEventSynchronize(b));
-    float ms = 0;
-    hipEventElapsedTime(&ms, a, b);
-    *avg_ms = ms / reps;
-    HIPCHK(ctx, hipGetLastError());
-    return STAN_OK;
-}
-
-// Time of the fp64 SpMV of K streaming its values from `vals` (any contents: only the addresses
-// matter), median of 3 launches after a warm-up.  Used by the allocation-by-trial of placement.hip.
-// self_pair: the gather vector and the product are carved out of the FRONT of the candidate block
-// itself instead of the context's vectors -- by construction the same-group (slow) pairing, i.e.
-// the reference the search compares the real pairing with (profiles/r02/placement_cross_self_n148.txt).
-int stan_spmv_probe(stan_ctx *ctx, stan_matrix *K, const void *vals, size_t bytes, int32_t precision,
-                    float *ms_out, bool self_pair) {
-    hipStream_t st_ = ctx->stream;
-    *ms_out = 0;
-    if (K->nslices <= 0) return STAN_OK;
-    // self_pair: the block holds no values yet (only addresses matter to the timing).  The gather vector and the product
-    // must fit into the candidate: a stream with few slots per slice (or a large halo) has no self-paired reference --
-    // *ms_out stays 0, the search then keeps the fastest real pairing (placement.hip)
-    dev_scope bufs(ctx);
-    product_args pa{};
-    STANCHK(timed_product_setup(ctx, K, precision, vals, self_pair ? const_cast<void *>(vals) : nullptr, bytes, bufs, pa));
-    if (!pa.x) return STAN_OK;
-    event_bag ev;
-    // one launch to warm up, then two groups of three launches back to back, the faster group counts.  (Round 4: single
-    // launches between host synchronisations -- the first form of this probe -- start on an idle device and read 2-3 %
-    // under the same product inside a sequence of kernels.)
-    auto one = [&]() { launch_product(ctx, K, pa); };
-    one();
-    float best = 0;
-    for (int g = 0; g < 2; g++) {
-        hipEvent_t a = ev.make(), b = ev.make();
-        hipEventRecord(a, st_);
-        for (int r = 0; r < 3; r++) one();
-        hipEventRecord(b, st_);
-        HIPCHK(ctx, hipEventSynchronize(b));
-        float t = 0;
-        hipEventElapsedTime(&t, a, b);
-        if (g == 0 || t < best) best = t;
-    }
-    HIPCHK(ctx, hipGetLastError());
-    *ms_out = best / 3;
-    return STAN_OK;
-}
-
-
-// the matrix carries S K S from its first solve on -- or from its first export: stan_hip_matrix_to_csr divides the
-// scaled values on the way out, whether or not a solve has happened, so an export before a solve and one after it are
-// the same bits (rounds 1-4 un-scaled the values in place for an export and re-scaled them for the next solve)
-int stan_matrix_ensure_scaled(stan_ctx *ctx, stan_matrix *K) { return ensure_scaled(ctx, K); }
-
 // ---- several load cases in one loop over a single pass of K (stan_hip_cg_solve_multi) -------------------------------------
 // n_rhs right-hand sides are cut into groups of 8, 4, 2, 1 columns, run one after the other; a group is ONE loop of the
 // shape of cg_run::iterate on interleaved vectors of its own (cg_multi.inc), whose every kernel serves all live columns.
@@ -1462,8 +947,7 @@ struct cg_multi_run {
     unsigned long long *tick = nullptr;
     pinned_words host;          // [2][MULTI_MAX][T_NSTAT] poll slots, [MULTI_MAX][T_NSTAT] final status, [MULTI_MAX][S_NSCAL] scalars
     event_bag events;
-    hipEvent_t poll[2] = {nullptr, nullptr};
-    static constexpr int64_t hard_cap = 0x7fffffff;
+    chunk_poll poll;
 
     int setup(int mmax) {
         st_ = ctx->stream;
@@ -1483,8 +967,7 @@ struct cg_multi_run {
         STANCHK(bufs.alloc(&stt, (size_t)T_NSTAT * m));
         STANCHK(bufs.alloc(&tick, (size_t)(2 * FOLD_WORDS)));
         HIPCHK(ctx, hipHostMalloc((void **)&host.p, (size_t)(3 * T_NSTAT + S_NSCAL) * MULTI_MAX * 8, hipHostMallocDefault));
-        poll[0] = events.make(hipEventDisableTiming);
-        poll[1] = events.make(hipEventDisableTiming);
+        poll.setup(events, host.p, MULTI_MAX * T_NSTAT);
         return STAN_OK;
     }
 
@@ -1497,7 +980,7 @@ struct cg_multi_run {
         const colstream cs = colstream_of(ctx, K);
         const fold_args fvec{tick + FOLD_WORDS, vg, (int)vg, nullptr, NO_P2P};   // counter set 1 serves the vector kernels,
         const fold_args fprod{tick, pg, (int)pg, nullptr, NO_P2P};               // set 0 the products
-        int64_t *h_poll = host.p, *h_st = host.p + 2 * MULTI_MAX * T_NSTAT;
+        int64_t *h_st = host.p + 2 * MULTI_MAX * T_NSTAT;
         double *h_sc = (double *)(host.p + 3 * MULTI_MAX * T_NSTAT);
         HIPCHK(ctx, hipMemsetAsync(sc, 0, (size_t)S_NSCAL * M * 8, st_));
         HIPCHK(ctx, hipMemsetAsync(stt, 0, (size_t)T_NSTAT * M * 8, st_));
@@ -1515,9 +998,9 @@ struct cg_multi_run {
         };
         bool done = all_stopped(h_st) || pg == 0;   // the first residual test ended every column (b = 0, or eps >= 1)
         int64_t k = 1;
-        int chunk_id = 0;
+        poll.chunk_id = 0;
         while (!done) {
-            for (int c = 0; c < CHUNK && k < hard_cap; c++, k++) {
+            for (int c = 0; c < CHUNK && k < chunk_poll::hard_cap; c++, k++) {
                 const bool refresh = rupdate > 0 && (k % rupdate) == 0;
                 hipLaunchKernelGGL((k_spmm<M, 1>), dim3(pg), dim3(256), 0, st_, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols,
                                    K->d_vals, p, v, partial, pstride, sc, stt, k, fprod, cs);
@@ -1538,15 +1021,7 @@ struct cg_multi_run {
             }
             HIPCHK(ctx, hipGetLastError());
             // poll: read the status of the PREVIOUS chunk while this one runs; done when every column has stopped
-            int64_t *slot = h_poll + MULTI_MAX * T_NSTAT * (chunk_id & 1);
-            HIPCHK(ctx, hipMemcpyAsync(slot, stt, (size_t)T_NSTAT * M * 8, hipMemcpyDeviceToHost, st_));
-            HIPCHK(ctx, hipEventRecord(poll[chunk_id & 1], st_));
-            if (chunk_id > 0) {
-                HIPCHK(ctx, hipEventSynchronize(poll[(chunk_id - 1) & 1]));
-                if (all_stopped(h_poll + MULTI_MAX * T_NSTAT * ((chunk_id - 1) & 1))) done = true;
-            }
-            if (k >= hard_cap) done = true;
-            chunk_id++;
+            STANCHK(poll.poll(ctx, st_, stt, (size_t)T_NSTAT * M, k, [&](hipEvent_t e) { return cg_wait(ctx, false, st_, e); }, all_stopped, &done));
         }
         HIPCHK(ctx, hipStreamSynchronize(st_));
         HIPCHK(ctx, hipMemcpyAsync(h_st, stt, (size_t)T_NSTAT * M * 8, hipMemcpyDeviceToHost, st_));
@@ -1566,7 +1041,7 @@ struct cg_multi_run {
             const int64_t *w = h_st + c * T_NSTAT;
             const double bnorm = h_sc[c * S_NSCAL + S_BNORM];
             if (term_out) term_out[c] = (int32_t)w[T_TYPE];
-            if (iters_out) iters_out[c] = (int32_t)(w[T_ITERS] > hard_cap ? hard_cap : w[T_ITERS]);
+            if (iters_out) iters_out[c] = (int32_t)(w[T_ITERS] > chunk_poll::hard_cap ? chunk_poll::hard_cap : w[T_ITERS]);
             if (rel_out) rel_out[c] = bnorm > 0 ? std::sqrt(h_sc[c * S_NSCAL + S_R2OUT]) / bnorm : 0.0;
         }
         return STAN_OK;
@@ -1577,7 +1052,7 @@ struct cg_multi_run {
 
 int stan_cg_multi_device(stan_ctx *ctx, stan_matrix *K, int32_t n_rhs, const double *d_F, double eps_f, int32_t max_its,
                          int32_t precision_mode, double *d_U, int32_t *term_out, int32_t *iters_out, double *rel_res_out) {
-    if (ctx->comm != nullptr || ctx->nranks > 1) {
+    if (stan_sharded(ctx)) {
         ctx->err = "cg_solve_multi: single-rank contexts only (no communicator)";
         return STAN_E_UNSUPPORTED;
     }
@@ -1614,3 +1089,5 @@ int stan_cg_multi_device(stan_ctx *ctx, stan_matrix *K, int32_t n_rhs, const dou
     }
     return STAN_OK;
 }
+
+#include "cg_entries.inc"   // test and bench entries: the products outside a solve

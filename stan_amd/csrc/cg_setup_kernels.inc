@@ -1,4 +1,4 @@
-// cg_setup_kernels.inc -- scaling (k_diag_scale, k_scale_matrix), value-stream copies (fp32, FIXED-48), the packed column stream (k_pack_cols), k_init / k_reduce / k_init_scalars
+// cg_setup_kernels.inc -- scaling (k_diag_scale, k_diag_get, k_scale_matrix), k_init / k_init_b / k_reduce / k_init_scalars
 // Part of cg.hip (included there, inside its anonymous namespace; not a translation unit of its own): split out in
 // round 4 so that each piece can be read on its own.  The reference has no counterpart of these kernels beyond the
 // calls they replace: alglib.lincgsolvesparse / sparsesmv behind SolverFunctions.LinearSolver_CG (SolverFunctions.cs:270-330).
@@ -65,131 +65,6 @@ k_scale_matrix(int32_t nslices, const int32_t *slot_ptr, const int32_t *rowof, c
 #pragma unroll
             for (int n = 0; n < 3; n++) v[(3 * m + n) * 64] *= sr[m] * sc[n];
     }
-}
-
-__global__ void k_to_fp32(const double *in, float *out, int64_t n) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) out[i] = (float)in[i];
-}
-
-constexpr double FX48_ONE = 70368744177664.0;                          // 2^46
-constexpr double FX48_INV = 1.0 / 70368744177664.0;                    // 2^-46
-constexpr double FX48_BIAS = 4503599627370496.0 + 140737488355328.0;   // 2^52 + 2^47
-
-// scaled fp64 values -> FIXED-48 stream (see vstream<uint32_t>); *bad counts the entries
-// with |a| >= 2 (not representable: the matrix was not SPD-scalable)
-__global__ void __launch_bounds__(256)
-k_to_fx48(int64_t nslots, const double *vals, uint32_t *out, unsigned long long *bad) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t slot = t >> 6;
-    const int lane = (int)(t & 63);
-    if (slot >= nslots) return;
-    const double *v = vals + slot * 9 * 64 + lane;
-    uint32_t *o = out + slot * 14 * 64 + lane;
-    uint32_t hi[10];
-    int nbad = 0;
-#pragma unroll
-    for (int j = 0; j < 9; j++) {
-        const double a = v[j * 64] * FX48_ONE;
-        long long q = 0;
-        if (!(fabs(a) < 140737488355328.0)) nbad++;  // also catches NaN
-        else q = __double2ll_rn(a);
-        if (q >= 140737488355328LL) { q = 0; nbad++; }
-        const unsigned long long u = (unsigned long long)(q + 140737488355328LL);
-        o[j * 64] = (uint32_t)u;
-        hi[j] = (uint32_t)(u >> 32);
-    }
-    hi[9] = 0;
-#pragma unroll
-    for (int m = 0; m < 5; m++) o[(9 + m) * 64] = hi[2 * m] | (hi[2 * m + 1] << 16);
-    if (nbad) atomicAdd(bad, (unsigned long long)nbad);
-}
-
-// packed column stream (struct colstream): one wavefront per slice.  Mode of a slice (ok[slice]):
-//   1  every slot's 64 columns (padding entries = the row's own column included) lie within 2^16 of the slot's smallest:
-//      one base per slot (round 2);
-//   2  (round 4) the slice mixes rows of different length -- the k-th neighbour of a short row (a node on the surface
-//      of the mesh) plays another part than the k-th neighbour of its 27-neighbour slice mates and, once a breadth-first
-//      level is wider than 2^16 rows (200^3: 120 k), lies further away than an offset reaches.  Two bases per slot: A
-//      for the rows of the slice's full width, B for the shorter ones (cmask[slice]: one bit per lane); a padding
-//      entry (zero values) takes offset 0 from its class's base.  63.9 % -> 99.8 % of the slots at 200^3 / 400^3,
-//      98.4 % -> 99.9 % at 148^3 (profiles/r04/packed_columns_ab_two_bases_n148_n200.txt, packed_columns_simulation.txt);
-//   0  neither: the slice keeps the int32 stream.
-// rowof == nullptr (the folded copy's stream, whose lanes carry foreign pieces): modes 0 / 1 only.
-__global__ void __launch_bounds__(256)
-k_pack_cols(int32_t nslices, int64_t nloc, const int32_t *slot_ptr, const int32_t *cols, const int32_t *rowof, const int32_t *rowlen,
-            const int32_t *pair_ptr, uint32_t *packed, int32_t *base, int32_t *base2, unsigned long long *cmask, uint8_t *ok) {
-    const int lane = threadIdx.x & 63;
-    const int64_t slice = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (slice >= nslices) return;
-    const int32_t k0 = slot_ptr[slice], k1 = slot_ptr[slice + 1];
-    int32_t len = k1 - k0;   // without row lengths every entry counts as live and every lane as class A
-    if (rowof) {
-        const int64_t row = rowof[slice * 64 + lane];
-        len = row < nloc ? rowlen[row] : 0;
-    }
-    const bool cls_b = len < k1 - k0;
-    const int32_t BIG = 0x7fffffff;
-    auto wmin = [](int32_t v) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
-        return v;
-    };
-    auto wmax = [](int32_t v) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-        return v;
-    };
-    bool fits1 = true, fits2 = rowof != nullptr;
-    for (int32_t k = k0; k < k1; k++) {
-        const int32_t c = cols[(int64_t)k * 64 + lane];
-        const bool live = k - k0 < len;
-        fits1 = fits1 && (wmax(c) - wmin(c)) < 65536;
-        if (fits2) {
-            const int32_t mna = wmin(live && !cls_b ? c : BIG), mxa = wmax(live && !cls_b ? c : -1);
-            const int32_t mnb = wmin(live && cls_b ? c : BIG), mxb = wmax(live && cls_b ? c : -1);
-            fits2 = (mxa < 0 || mxa - mna < 65536) && (mxb < 0 || mxb - mnb < 65536);
-        }
-    }
-    const int mode = fits1 ? 1 : fits2 ? 2 : 0;
-    uint32_t *out = packed + (int64_t)pair_ptr[slice] * 64 + lane;
-    uint32_t lo = 0;
-    for (int32_t k = k0; k < k1; k++) {
-        const int32_t c = cols[(int64_t)k * 64 + lane];
-        uint32_t dlt;
-        if (mode == 2) {
-            const bool live = k - k0 < len;
-            int32_t mna = wmin(live && !cls_b ? c : BIG);         // (BIG only if slice widths were ever padded beyond the longest row)
-            int32_t mnb = wmin(live && cls_b ? c : BIG);
-            if (mnb == BIG) mnb = mna;                            // no short row reaches this slot: its padding points at A's base
-            if (mna == BIG) mna = mnb == BIG ? 0 : mnb;           // no class-A lane alive in this slot: never a base of 0x7fffffff
-            if (mnb == BIG) mnb = mna;
-            if (lane == 0) { base[k] = mna; base2[k] = mnb; }
-            dlt = live ? (uint32_t)(c - (cls_b ? mnb : mna)) & 0xffffu : 0u;
-        } else {
-            const int32_t mn = wmin(c);
-            if (lane == 0) { base[k] = mn; base2[k] = mn; }
-            dlt = (uint32_t)(c - mn) & 0xffffu;
-        }
-        if (((k - k0) & 1) == 0) lo = dlt;
-        else { *out = lo | (dlt << 16); out += 64; }
-    }
-    if ((k1 - k0) & 1) *out = lo;
-    const unsigned long long mb = __ballot(cls_b);
-    if (lane == 0) {
-        ok[slice] = (uint8_t)mode;
-        cmask[slice] = mode == 2 ? mb : 0ULL;
-    }
-}
-__global__ void k_pair_counts(int32_t nslices, const int32_t *slot_ptr, int32_t *cnt) {
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s < nslices) cnt[s] = (slot_ptr[s + 1] - slot_ptr[s] + 1) >> 1;
-}
-__global__ void k_count_ok(int32_t nslices, const uint8_t *ok, const int32_t *slot_ptr, unsigned long long *out) {
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s < nslices && ok[s]) atomicAdd(out, (unsigned long long)(slot_ptr[s + 1] - slot_ptr[s]));           // packed slots
-    if (s < nslices && ok[s] == 2) atomicAdd(out + 1, (unsigned long long)(slot_ptr[s + 1] - slot_ptr[s]));  // ... with two bases
 }
 
 // b^[i] = s_i * F[d - red[d]] on free DOFs, 0 on fixed ones; also x0 = 0, r = p = b^ and

@@ -116,7 +116,7 @@ enum stan_status_slot {
     SS_H_CG_SCALARS = 40 // host: the CG scalars at the end of a solve
 };
 
-// Vectors of the CG, kept by the context between solves (cg.hip: stan_cg_workspace).  They are
+// Vectors of the CG, kept by the context between solves (cg_workspace.hip: stan_cg_workspace).  They are
 // allocated BEFORE the value stream of K is placed by search, and the search's probe multiplies
 // with exactly these buffers: whether a block streams fast depends on the PAIR (value block,
 // vector block) -- profiles/r02/PLACEMENT.md -- so the pair that is timed is the pair that runs.
@@ -125,6 +125,13 @@ struct stan_cg_ws {
     double *xb[2] = {nullptr, nullptr}, *p = nullptr, *r = nullptr;   // ng each
     double *v = nullptr, *w = nullptr, *bh = nullptr, *sv = nullptr;  // n3 each
     double *vw_owner = nullptr;    // non-null: v and w are carved out of this one block (placement.hip, second stage): it is what gets freed
+    // the eight vectors, i = 0 .. NVEC - 1 in the order they are allocated: where the pointer is kept, and which capacity it has
+    static constexpr int NVEC = 8;
+    struct slot { double **q; bool gather; };
+    slot vec(int i) {
+        double **const all[NVEC] = {&xb[0], &xb[1], &p, &r, &v, &w, &bh, &sv};
+        return slot{all[i], i < 4};
+    }
 };
 
 // ---- peer-to-peer exchanges of the one-process multi-GPU handle (p2p.hip) ---------------------
@@ -266,6 +273,8 @@ struct stan_ctx {
     int64_t *h_status = nullptr;  // pinned, 64 words
     int64_t *d_status = nullptr;  // device, 64 words
 };
+// a rank of a sharded matrix: halo exchanges and all-reduces belong to every product and reduction
+inline bool stan_sharded(const stan_ctx *ctx) { return ctx->comm != nullptr || ctx->nranks > 1; }
 
 struct stan_matrix {
     stan_ctx *ctx = nullptr;
@@ -392,6 +401,12 @@ int stan_pack_columns(stan_ctx *ctx, int32_t nslices, int64_t nslots, const int3
                       uint32_t **packed_out, int32_t **base_out, int32_t **pair_ptr_out, uint8_t **ok_out, int64_t *slots_packed,
                       int64_t nloc = 0, const int32_t *d_rowof = nullptr, const int32_t *d_rowlen = nullptr, int64_t *slots_packed2 = nullptr);
 int stan_matrix_ensure_scaled(stan_ctx *ctx, stan_matrix *K);   // S K S in place (once per matrix)
+// length of a gather vector of K (NOTE on the halo layout, cg.hip): the owned rows padded to whole slices, or the owned
+// rows and the halo columns behind them, whichever is longer
+inline int64_t gather_len(const stan_matrix *K) {
+    const int64_t npad = (int64_t)K->nslices * 64;
+    return 3 * (npad > K->nloc + K->nhalo ? npad : K->nloc + K->nhalo);
+}
 int stan_cg_workspace(stan_ctx *ctx, const stan_matrix *K);  // (re)allocates ctx->ws for K's sizes
 void stan_cg_workspace_free(stan_ctx *ctx);
 int stan_cg_workspace_move(stan_ctx *ctx, const stan_matrix *K, bool commit, stan_cg_ws *saved);

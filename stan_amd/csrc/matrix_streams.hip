@@ -1,0 +1,214 @@
+// matrix_streams.hip -- the copies of a matrix's streams the products may read instead of the assembled ones, made once per
+// matrix: the fp32 and FIXED-48 value streams (STAN_PREC_MIXED, STAN_PREC_FIXED48) and the packed column stream (struct
+// colstream of spmv_kernels.inc; fold.hip packs the folded copy's columns through stan_pack_columns too).  The reference has
+// no counterpart: alglib.sparsesmv behind SolverFunctions.LinearSolver_CG (SolverFunctions.cs:270-330) reads one CRS matrix.
+#include <algorithm>
+
+#include "internal.h"
+#include "fx48.h"
+
+namespace {
+
+__global__ void k_to_fp32(const double *in, float *out, int64_t n) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) out[i] = (float)in[i];
+}
+
+// scaled fp64 values -> FIXED-48 stream (see vstream<uint32_t>); *bad counts the entries
+// with |a| >= 2 (not representable: the matrix was not SPD-scalable)
+__global__ void __launch_bounds__(256)
+k_to_fx48(int64_t nslots, const double *vals, uint32_t *out, unsigned long long *bad) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t slot = t >> 6;
+    const int lane = (int)(t & 63);
+    if (slot >= nslots) return;
+    const double *v = vals + slot * 9 * 64 + lane;
+    uint32_t *o = out + slot * 14 * 64 + lane;
+    uint32_t hi[10];
+    int nbad = 0;
+#pragma unroll
+    for (int j = 0; j < 9; j++) {
+        const double a = v[j * 64] * FX48_ONE;
+        long long q = 0;
+        if (!(fabs(a) < 140737488355328.0)) nbad++;  // also catches NaN
+        else q = __double2ll_rn(a);
+        if (q >= 140737488355328LL) { q = 0; nbad++; }
+        const unsigned long long u = (unsigned long long)(q + 140737488355328LL);
+        o[j * 64] = (uint32_t)u;
+        hi[j] = (uint32_t)(u >> 32);
+    }
+    hi[9] = 0;
+#pragma unroll
+    for (int m = 0; m < 5; m++) o[(9 + m) * 64] = hi[2 * m] | (hi[2 * m + 1] << 16);
+    if (nbad) atomicAdd(bad, (unsigned long long)nbad);
+}
+
+// packed column stream (struct colstream): one wavefront per slice.  Mode of a slice (ok[slice]):
+//   1  every slot's 64 columns (padding entries = the row's own column included) lie within 2^16 of the slot's smallest:
+//      one base per slot (round 2);
+//   2  (round 4) the slice mixes rows of different length -- the k-th neighbour of a short row (a node on the surface
+//      of the mesh) plays another part than the k-th neighbour of its 27-neighbour slice mates and, once a breadth-first
+//      level is wider than 2^16 rows (200^3: 120 k), lies further away than an offset reaches.  Two bases per slot: A
+//      for the rows of the slice's full width, B for the shorter ones (cmask[slice]: one bit per lane); a padding
+//      entry (zero values) takes offset 0 from its class's base.  63.9 % -> 99.8 % of the slots at 200^3 / 400^3,
+//      98.4 % -> 99.9 % at 148^3 (profiles/r04/packed_columns_ab_two_bases_n148_n200.txt, packed_columns_simulation.txt);
+//   0  neither: the slice keeps the int32 stream.
+// rowof == nullptr (the folded copy's stream, whose lanes carry foreign pieces): modes 0 / 1 only.
+__global__ void __launch_bounds__(256)
+k_pack_cols(int32_t nslices, int64_t nloc, const int32_t *slot_ptr, const int32_t *cols, const int32_t *rowof, const int32_t *rowlen,
+            const int32_t *pair_ptr, uint32_t *packed, int32_t *base, int32_t *base2, unsigned long long *cmask, uint8_t *ok) {
+    const int lane = threadIdx.x & 63;
+    const int64_t slice = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (slice >= nslices) return;
+    const int32_t k0 = slot_ptr[slice], k1 = slot_ptr[slice + 1];
+    int32_t len = k1 - k0;   // without row lengths every entry counts as live and every lane as class A
+    if (rowof) {
+        const int64_t row = rowof[slice * 64 + lane];
+        len = row < nloc ? rowlen[row] : 0;
+    }
+    const bool cls_b = len < k1 - k0;
+    const int32_t BIG = 0x7fffffff;
+    auto wmin = [](int32_t v) {
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
+        return v;
+    };
+    auto wmax = [](int32_t v) {
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
+        return v;
+    };
+    bool fits1 = true, fits2 = rowof != nullptr;
+    for (int32_t k = k0; k < k1; k++) {
+        const int32_t c = cols[(int64_t)k * 64 + lane];
+        const bool live = k - k0 < len;
+        fits1 = fits1 && (wmax(c) - wmin(c)) < 65536;
+        if (fits2) {
+            const int32_t mna = wmin(live && !cls_b ? c : BIG), mxa = wmax(live && !cls_b ? c : -1);
+            const int32_t mnb = wmin(live && cls_b ? c : BIG), mxb = wmax(live && cls_b ? c : -1);
+            fits2 = (mxa < 0 || mxa - mna < 65536) && (mxb < 0 || mxb - mnb < 65536);
+        }
+    }
+    const int mode = fits1 ? 1 : fits2 ? 2 : 0;
+    uint32_t *out = packed + (int64_t)pair_ptr[slice] * 64 + lane;
+    uint32_t lo = 0;
+    for (int32_t k = k0; k < k1; k++) {
+        const int32_t c = cols[(int64_t)k * 64 + lane];
+        uint32_t dlt;
+        if (mode == 2) {
+            const bool live = k - k0 < len;
+            int32_t mna = wmin(live && !cls_b ? c : BIG);         // (BIG only if slice widths were ever padded beyond the longest row)
+            int32_t mnb = wmin(live && cls_b ? c : BIG);
+            if (mnb == BIG) mnb = mna;                            // no short row reaches this slot: its padding points at A's base
+            if (mna == BIG) mna = mnb == BIG ? 0 : mnb;           // no class-A lane alive in this slot: never a base of 0x7fffffff
+            if (mnb == BIG) mnb = mna;
+            if (lane == 0) { base[k] = mna; base2[k] = mnb; }
+            dlt = live ? (uint32_t)(c - (cls_b ? mnb : mna)) & 0xffffu : 0u;
+        } else {
+            const int32_t mn = wmin(c);
+            if (lane == 0) { base[k] = mn; base2[k] = mn; }
+            dlt = (uint32_t)(c - mn) & 0xffffu;
+        }
+        if (((k - k0) & 1) == 0) lo = dlt;
+        else { *out = lo | (dlt << 16); out += 64; }
+    }
+    if ((k1 - k0) & 1) *out = lo;
+    const unsigned long long mb = __ballot(cls_b);
+    if (lane == 0) {
+        ok[slice] = (uint8_t)mode;
+        cmask[slice] = mode == 2 ? mb : 0ULL;
+    }
+}
+__global__ void k_pair_counts(int32_t nslices, const int32_t *slot_ptr, int32_t *cnt) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < nslices) cnt[s] = (slot_ptr[s + 1] - slot_ptr[s] + 1) >> 1;
+}
+__global__ void k_count_ok(int32_t nslices, const uint8_t *ok, const int32_t *slot_ptr, unsigned long long *out) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < nslices && ok[s]) atomicAdd(out, (unsigned long long)(slot_ptr[s + 1] - slot_ptr[s]));           // packed slots
+    if (s < nslices && ok[s] == 2) atomicAdd(out + 1, (unsigned long long)(slot_ptr[s + 1] - slot_ptr[s]));  // ... with two bases
+}
+
+}  // namespace
+
+int stan_matrix_make_fp32(stan_ctx *ctx, stan_matrix *K) {
+    if (K->d_vals32) return STAN_OK;
+    const int64_t n = K->nslots * 9 * 64;
+    STANCHK(stan_dmalloc_streamed(ctx, (void **)&K->d_vals32, (size_t)n * 4,
+                                  [&](const void *q, float *ms, bool self) {
+                                      return stan_spmv_probe(ctx, K, q, (size_t)n * 4, STAN_PREC_MIXED, ms, self);
+                                  }));
+    const unsigned blocks = std::min(std::max(nblk(n, 256), 1u), 2048u);   // (four times the grid of the CG's vector kernels)
+    hipLaunchKernelGGL(k_to_fp32, dim3(blocks * 4), dim3(256), 0, ctx->stream, K->d_vals, K->d_vals32, n);
+    HIPCHK(ctx, hipGetLastError());
+    return STAN_OK;
+}
+
+// FIXED-48 copy of the scaled values.  Returns STAN_OK with K->d_vals48 == nullptr when some
+// entry is not representable (K not SPD): the caller then streams the fp64 values.
+int stan_matrix_make_fx48(stan_ctx *ctx, stan_matrix *K) {
+    if (K->d_vals48 || K->fx48_refused) return STAN_OK;
+    if (K->nslots == 0) return STAN_OK;
+    uint32_t *out;
+    STANCHK(stan_dmalloc_streamed(ctx, (void **)&out, (size_t)K->nslots * 14 * 64 * 4,
+                                  [&](const void *q, float *ms, bool self) {
+                                      return stan_spmv_probe(ctx, K, q, (size_t)K->nslots * 14 * 64 * 4, STAN_PREC_FIXED48, ms, self);
+                                  }));
+    unsigned long long *d_bad = (unsigned long long *)(ctx->d_status + SS_COUNTER);
+    HIPCHK(ctx, hipMemsetAsync(d_bad, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(k_to_fx48, dim3((unsigned)nblk(K->nslots * 64, 256)), dim3(256), 0, ctx->stream,
+                       K->nslots, K->d_vals, out, d_bad);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_COUNTER, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->h_status[SS_COUNTER] != 0) { stan_dfree(ctx, out); K->fx48_refused = true; return STAN_OK; }
+    K->d_vals48 = out;
+    return STAN_OK;
+}
+
+// Packed column stream of K (struct colstream), built once per matrix; the int32 columns stay (the
+// assembly, scaling and export kernels use them).
+int stan_matrix_make_cols16(stan_ctx *ctx, stan_matrix *K) {
+    if (K->d_cols16 || K->nslices <= 0) return STAN_OK;
+    return stan_pack_columns(ctx, K->nslices, K->nslots, K->d_slot_ptr, K->d_cols, &K->d_cols16, &K->d_colbase, &K->d_pair_ptr,
+                             &K->d_slice_packed, &K->slots_packed, K->nloc, K->d_rowof, K->d_rowlen, &K->slots_packed2);
+}
+// the same for any sliced column stream (the folded copy of fold.hip has its own); *packed stays nullptr when the
+// pair index would not fit an int32
+int stan_pack_columns(stan_ctx *ctx, int32_t nslices, int64_t nslots, const int32_t *d_slot_ptr, const int32_t *d_cols,
+                      uint32_t **packed_out, int32_t **base_out, int32_t **pair_ptr_out, uint8_t **ok_out, int64_t *slots_packed,
+                      int64_t nloc, const int32_t *d_rowof, const int32_t *d_rowlen, int64_t *slots_packed2) {
+    hipStream_t st_ = ctx->stream;
+    dev_scope bufs(ctx);
+    int32_t *cnt; int64_t *ptr64;
+    STANCHK(bufs.alloc(&cnt, (size_t)nslices + 1));
+    STANCHK(bufs.alloc(&ptr64, (size_t)nslices + 2));
+    hipLaunchKernelGGL(k_pair_counts, dim3(nblk(nslices, 256)), dim3(256), 0, st_, nslices, d_slot_ptr, cnt);
+    STANCHK(stan_scan_total(ctx, cnt, ptr64, nslices, SS_H_NSLOTS));
+    HIPCHK(ctx, hipStreamSynchronize(st_));
+    const int64_t npairs = ctx->h_status[SS_H_NSLOTS];
+    if (npairs >= ((int64_t)1 << 31)) return STAN_OK;   // pair index is int32: keep the plain columns
+    STANCHK(stan_slot_ptr_narrow(ctx, ptr64, nslices, pair_ptr_out));
+    // one allocation: [n] base, [n] base2, [nslices] cmask (64-bit words), n = max(nslots, 1): make_colstream
+    const size_t nb_ = (size_t)(nslots > 0 ? nslots : 1);
+    STANCHK(stan_dmalloc(ctx, base_out, 2 * nb_ + 2 * (size_t)nslices + 2));
+    STANCHK(stan_dmalloc(ctx, ok_out, (size_t)nslices));
+    uint32_t *packed;
+    STANCHK(stan_dmalloc(ctx, &packed, (size_t)(npairs > 0 ? npairs : 1) * 64));
+    int32_t *b2_ = *base_out + nb_;
+    unsigned long long *cm_ = (unsigned long long *)(*base_out + 2 * nb_);
+    if (((uintptr_t)cm_ & 7) != 0) cm_ = (unsigned long long *)((uintptr_t)cm_ + 4);   // (never: 2 n ints from an aligned block)
+    hipLaunchKernelGGL(k_pack_cols, dim3(nblk(nslices, 4)), dim3(256), 0, st_, nslices, nloc, d_slot_ptr, d_cols, d_rowof, d_rowlen,
+                       *pair_ptr_out, packed, *base_out, b2_, cm_, *ok_out);
+    unsigned long long *d_cnt = (unsigned long long *)(ctx->d_status + SS_COUNTER);   // two words: SS_COUNTER, SS_H_ERRCOPY
+    HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, 16, st_));
+    hipLaunchKernelGGL(k_count_ok, dim3(nblk(nslices, 256)), dim3(256), 0, st_, nslices, *ok_out, d_slot_ptr, d_cnt);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_COUNTER, d_cnt, 16, hipMemcpyDeviceToHost, st_));
+    HIPCHK(ctx, hipStreamSynchronize(st_));
+    *slots_packed = ctx->h_status[SS_COUNTER];
+    if (slots_packed2) *slots_packed2 = ctx->h_status[SS_COUNTER + 1];
+    *packed_out = packed;
+    return STAN_OK;
+}

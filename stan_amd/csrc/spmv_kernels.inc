@@ -113,7 +113,7 @@ __device__ __forceinline__ void store_row(double *__restrict__ y, int64_t row, d
 // The dot products fused into a product (DOT as in k_spmv).  dot_terms: the row's terms d = x_row . y_row and, DOT = 2,
 // e = x_row . x_row.  dot_reduce (every thread of the block; rows without terms bring zeros): the block's sums to
 // partial[blockIdx.x + poff] -- DOT = 2: the pair [sum e, sum d] -- as agent-scope stores, then the ticket of the folded
-// reduction; the block that draws the last one adds all partials up (fold_arrive / fold_finish, cg.hip).
+// reduction; the block that draws the last one adds all partials up (fold_arrive / fold_finish, cg_reduce_device.inc).
 template <int DOT>
 __device__ __forceinline__ void dot_terms(const double *__restrict__ x, int64_t row, double y0, double y1, double y2, double &d, double &e) {
     const double x0 = x[3 * row], x1 = x[3 * row + 1], x2 = x[3 * row + 2];
