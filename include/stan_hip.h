@@ -70,6 +70,9 @@ typedef struct stan_matrix stan_matrix;
  * the unit diagonal); 60 B per 3x3 block instead of 76 B.  If some |a| >= 2 (K not SPD) the
  * fp64 values are streamed instead (stan_profile.value_stream tells). */
 #define STAN_PREC_FIXED48 2
+/* Not a precision_mode of a solve: what stan_profile.value_stream reports when the plain products of an fp64 solve read the
+ * lossless 60-bit stream of the scaled values (STAN_OPT_VALUE_STREAM_60) -- and what stan_hip_spmv_bench takes to time it. */
+#define STAN_VALUE_STREAM_60 3
 
 /* ---- context ------------------------------------------------------------------------- */
 /* `device` = HIP device ordinal this process drives.  Fails loudly (STAN_E_HIP) when no
@@ -111,6 +114,7 @@ int stan_hip_set_stream(stan_ctx *ctx, void *hip_stream);
  *   19 STAN_OPT_ROW_FOLDING          -1    folded rows on irregular meshes (auto)
  *   20 STAN_OPT_CG_REFINE            1     reduced-precision streams: 0 fp64 check only, 1 + refinement passes, 2 + fp64 refresh
  *   21 STAN_OPT_CG_LAZY_SCALING      1     the loop's first product brings K into its Jacobi-scaled form (no pass of its own)
+ *   22 STAN_OPT_VALUE_STREAM_60      -1    fp64 solves stream the scaled values as lossless 60-bit words (auto)
  * The descriptions follow in the order the options were added.
  *   STAN_OPT_CG_MERIT_STOP  1 (default): stop with type 7 when the merit function x'Ax-2b'x
  *                           no longer decreases (rounding floor, ~1e-7 relative residual on
@@ -267,6 +271,25 @@ int stan_hip_set_stream(stan_ctx *ctx, void *hip_stream);
                            memory that is free at the call (bench.py and stan_solver do; at 400^3 the fp64 values and
                            their fp32 copy are 126 + 63 GB: under the default one of them went back to the driver every
                            step, 4.7 s of hipMalloc per step; with the budget the assembly is 0.24 s, its kernels' time). */
+#define STAN_OPT_VALUE_STREAM_60 22 /* -1 (default) / 0 / 1.  Every entry of S K S is at most 1 in magnitude, so four of an
+                           fp64's eleven exponent bits never change: the plain products of an fp64 solve (k_spmv, each
+                           with its p.Ap sum) may read the values as 60-bit words -- sign, 7-bit exponent code, the 52
+                           mantissa bits untouched; 68 B per 3x3 block instead of 72 -- made from the scaled values by one
+                           pass per matrix.  Decoding is integer work and gives back the stored double bit for bit: the
+                           results do not depend on this option.  The fp64 values stay resident (the first product, the
+                           refresh products, exports and every other kernel read them).  1: wherever k_spmv runs those
+                           products (STAN_PREC_FP64, one rank, the classic loop, not the small-system or the pair kernel,
+                           no folded copy); -1: there, and only above 150 000 block rows; 0: never.  A matrix with an
+                           entry outside the format's range (|a| >= 2, 0 < |a| < 2^-126, Inf, NaN) keeps streaming
+                           fp64.  So does, under -1 and 1 alike, a solve that finds no room for the block -- a second copy
+                           of the values, 17/18 of their size, for the life of the matrix.  That is decided before
+                           anything is allocated or the pool is touched: the matrix's values, columns and this block
+                           must fit into STAN_OPT_POOL_MAX_BYTES together (they are parked together when the matrix is
+                           freed), and after the block is taken as much again must stay free on the device, a sixteenth
+                           of it at least (148^3: 6.0 GB next to 6.8; 400^3: 119 GB next to 133, refused under either
+                           pool budget).  stan_profile.value_stream (STAN_VALUE_STREAM_60) and spmv_bytes tell what
+                           ran; placement_candidates / _ms_best / _ms_worst then describe the search for THIS block (the
+                           one the plain products stream), which never moves the solver's vectors. */
 #define STAN_OPT_SPMV_VARIANT 3 /* SpMV kernel variant (cg.hip): -1 = auto (default: 9 for fp64/fp32 streams,
                            12 for FIXED-48), 0 = plain loads + identity mapping, 9 = non-temporal matrix
                            stream + XCD-chunked workgroup mapping, 12 = 9 unrolled by 4: these three add a row's
@@ -642,6 +665,11 @@ int stan_hip_spmv(stan_ctx *ctx, stan_matrix *K, const double *x, double *y);
 int stan_hip_spmv_bench(stan_ctx *ctx, stan_matrix *K, int32_t precision_mode, int32_t reps,
                         double *avg_ms);
 
+/* Test hook of STAN_OPT_VALUE_STREAM_60: n doubles (host) through the solve's encoder and the products' decoder on the
+ * device, out [n] = what the products would multiply with, *refused = entries the format cannot carry (such entries come
+ * back as 0.0; a solve falls back to the fp64 values as soon as one is counted). */
+int stan_hip_stream60_roundtrip(stan_ctx *ctx, int64_t n, const double *in, double *out, int64_t *refused);
+
 /* The yardstick of that roofline: `reps` read-only sweeps over K's resident fp64 values in the product's own access
  * pattern (one wavefront per slice, XCD-chunked mapping, non-temporal loads) with nothing else -- no columns, no gather,
  * no product vector.  avg_ms per sweep, *bytes = what one sweep reads (n_slots * 64 * 72).  bytes / avg_ms is what
@@ -666,7 +694,7 @@ typedef struct stan_profile {
     int32_t iterations;
     int32_t termination_type;
     int32_t assembly_colours; /* element colours of the last mode-1 assembly */
-    int32_t value_stream;     /* STAN_PREC_* of the stream the last CG actually read */
+    int32_t value_stream;     /* STAN_PREC_* of the stream the last CG actually read; STAN_VALUE_STREAM_60: its plain products read the 60-bit stream */
     double spmv2_ms_total;    /* two-product launches of the refresh iterations (k_spmv2),  */
     int64_t spmv2_launches;   /* NOT included in spmv_ms_total / spmv_launches              */
     int64_t loop_kernel_launches;     /* kernels the CG loop enqueued (incl. the run-ahead)  */

@@ -120,7 +120,8 @@ namespace STAN_Solver
                            STAN_OPT_CG_SINGLE_REDUCE = 10, STAN_OPT_CG_FOLD_REDUCE = 11, STAN_OPT_VEC_STORE_NT = 12,
                            STAN_OPT_PACKED_COLUMNS = 13, STAN_OPT_CG_DEFER_X = 14, STAN_OPT_SPMV_SMALL = 15,
                            STAN_OPT_PLACEMENT_MAX_BYTES = 16, STAN_OPT_SELL_SIGMA = 17, STAN_OPT_COMM_P2P = 18,
-                           STAN_OPT_ROW_FOLDING = 19, STAN_OPT_CG_REFINE = 20, STAN_OPT_CG_LAZY_SCALING = 21;
+                           STAN_OPT_ROW_FOLDING = 19, STAN_OPT_CG_REFINE = 20, STAN_OPT_CG_LAZY_SCALING = 21,
+                           STAN_OPT_VALUE_STREAM_60 = 22;
 
         // ---- context
         [DllImport(Lib)] internal static extern int stan_hip_init(int device, out IntPtr ctx);
@@ -229,6 +230,7 @@ namespace STAN_Solver
         [DllImport(Lib)] internal static extern int stan_hip_spmv(IntPtr ctx, IntPtr K, double[] x, [Out] double[] y);
         [DllImport(Lib)] internal static extern int stan_hip_spmv_bench(IntPtr ctx, IntPtr K, int precision_mode, int reps, out double avg_ms);
         [DllImport(Lib)] internal static extern int stan_hip_stream_bench(IntPtr ctx, IntPtr K, int reps, out double avg_ms, out long bytes);
+        [DllImport(Lib)] internal static extern int stan_hip_stream60_roundtrip(IntPtr ctx, long n, double[] input, double[] output, out long refused);
         [DllImport(Lib)] internal static extern int stan_hip_set_profiling(IntPtr ctx, int enabled);
         [DllImport(Lib)] internal static extern int stan_hip_get_profile(IntPtr ctx, out StanProfile profile);
         [DllImport(Lib)] internal static extern int stan_hip_get_profile_rank(IntPtr ctx, int rank, out StanProfile profile);

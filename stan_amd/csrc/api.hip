@@ -189,6 +189,7 @@ int stan_hip_set_option(stan_ctx *ctx, int32_t option, int64_t value) {
             ctx->pool.avail.erase(ctx->pool.avail.begin());
         }
     }
+    else if (option == STAN_OPT_VALUE_STREAM_60 && value >= -1 && value <= 1) ctx->value_stream_60 = (int)value;
     else if (option == STAN_OPT_OVERLAP_HALO) ctx->overlap_halo = value != 0;
     else if (option == STAN_OPT_SELL_SIGMA && value >= 1 && value <= 32) ctx->sell_sigma = (int)value;
     else if (option == STAN_OPT_PLACEMENT_TRIES && value >= 1 && value <= 64) ctx->placement_tries = (int)value;
@@ -381,7 +382,7 @@ void stan_hip_matrix_free(stan_matrix *K) {
     // the solves that used these buffers have been synchronised by their own calls; the blocks go
     // back to the context's pool (stan_pool) or to the driver
     for (void *q : {(void *)K->d_slot_ptr, (void *)K->d_rowlen, (void *)K->d_rowof, (void *)K->d_posof, (void *)K->d_cols, (void *)K->d_vals,
-                    (void *)K->d_vals32, (void *)K->d_vals48, (void *)K->d_cols16, (void *)K->d_colbase,
+                    (void *)K->d_vals32, (void *)K->d_vals48, (void *)K->d_vals60, (void *)K->d_cols16, (void *)K->d_colbase,
                     (void *)K->d_pair_ptr, (void *)K->d_slice_packed, (void *)K->d_red, (void *)K->d_fixmask,
                     (void *)K->d_scale, (void *)K->d_send_rows, (void *)K->d_halo_glob, (void *)K->d_sendbuf,
                     (void *)K->d_sl_int, (void *)K->d_sl_bnd, (void *)K->d_fold_ptr, (void *)K->d_fold_meta,
@@ -1044,6 +1045,13 @@ int stan_hip_spmv_bench(stan_ctx *ctx, stan_matrix *K, int32_t precision_mode, i
     STAN_NO_GROUP(ctx, "spmv_bench");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return stan_spmv_bench_device(ctx, K, precision_mode, reps, avg_ms);
+}
+
+int stan_hip_stream60_roundtrip(stan_ctx *ctx, int64_t n, const double *in, double *out, int64_t *refused) {
+    if (!ctx || n <= 0 || !in || !out || !refused) return STAN_E_ARG;
+    STAN_NO_GROUP(ctx, "stream60_roundtrip");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return stan_stream60_roundtrip_device(ctx, n, in, out, refused);
 }
 
 int stan_hip_stream_bench(stan_ctx *ctx, stan_matrix *K, int32_t reps, double *avg_ms, int64_t *bytes) {

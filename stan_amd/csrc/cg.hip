@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "internal.h"
+#include "s60.h"
 #include "p2p_device.h"
 #include "fx48.h"
 
@@ -120,6 +121,10 @@ inline bool stan_small_system(const stan_ctx *ctx, const stan_matrix *K) {
 
 inline bool stan_pair_kernel(const stan_ctx *ctx) { return ctx->spmv_variant == 20; }
 
+// STAN_OPT_VALUE_STREAM_60 = -1 takes the 60-bit stream above this many block rows -- the small-system kernel's DEFAULT bound,
+// whatever STAN_OPT_SPMV_SMALL is set to: a matrix below it lives in the caches and gains nothing from fewer bytes
+constexpr int64_t STREAM60_AUTO_ROWS = 150000;
+
 // the folded form of the value stream `vals` of K, if the products are to read it (fold.hip)
 template <typename VT> const VT *fold_vals(const stan_ctx *ctx, const stan_matrix *K, const VT *vals);
 template <> const double *fold_vals<double>(const stan_ctx *ctx, const stan_matrix *K, const double *vals) {
@@ -181,7 +186,9 @@ unsigned launch_product(stan_ctx *ctx, stan_matrix *K, const product_args &a, in
     const int32_t nlist = which == 1 ? K->n_sl_int : which == 2 ? K->n_sl_bnd : K->nslices;
     // slices per workgroup: one (k_spmv_small) or two (k_spmv_pair; STAN_OPT_SPMV_VARIANT 20) for a single product
     // that is not a matrix's first, four for every other kernel
-    const bool plain = !a.x2 && !a.first, small = plain && stan_small_system(ctx, K), pair = plain && !small && stan_pair_kernel(ctx);
+    // (the lossless 60-bit stream belongs to k_spmv alone: cg_run picks it only where that kernel would run)
+    const bool s60 = a.kind == STAN_VALUE_STREAM_60;
+    const bool plain = !a.x2 && !a.first, small = plain && !s60 && stan_small_system(ctx, K), pair = plain && !s60 && !small && stan_pair_kernel(ctx);
     const int spb = small ? 1 : pair ? 2 : 4;
     const int32_t poff = which == 2 ? (int32_t)nblk(K->n_sl_int, spb) : 0;
     const unsigned grid = nblk(nlist, spb);
@@ -189,6 +196,17 @@ unsigned launch_product(stan_ctx *ctx, stan_matrix *K, const product_args &a, in
     fold.nblocks = grid;
     fold.np = (int)grid + poff;
     const colstream cs = colstream_of(ctx, K);
+    if (s60) {   // one plain product with its p.Ap sum: k_spmv<s60_t, 1, 9 | 12>, nothing else is instantiated for this stream
+        const s60_t *vals = (const s60_t *)(a.vals ? a.vals : (const void *)K->d_vals60);
+        const dim3 g(grid), b(256);
+        if (ctx->spmv_variant == 12)
+            hipLaunchKernelGGL((k_spmv<s60_t, 1, 12>), g, b, 0, stream, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols,
+                               vals, a.x, a.y, a.partial, a.st, a.k, slist, nlist, poff, fold, cs);
+        else
+            hipLaunchKernelGGL((k_spmv<s60_t, 1, 9>), g, b, 0, stream, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols,
+                               vals, a.x, a.y, a.partial, a.st, a.k, slist, nlist, poff, fold, cs);
+        return grid;
+    }
     with_product_types(K, a, [&](auto *vals, auto dot_tag) {
         using VT = std::remove_cv_t<std::remove_pointer_t<decltype(vals)>>;
         constexpr int DOT = decltype(dot_tag)::value;
@@ -285,8 +303,10 @@ static void mark_scaled(stan_ctx *ctx, stan_matrix *K) {
     // hold the unscaled K: a later solve must not iterate on them
     if (K->d_vals32) { stan_dfree(ctx, K->d_vals32); K->d_vals32 = nullptr; }
     if (K->d_vals48) { stan_dfree(ctx, K->d_vals48); K->d_vals48 = nullptr; }
+    if (K->d_vals60) { stan_dfree(ctx, K->d_vals60); K->d_vals60 = nullptr; }
     stan_matrix_drop_folded_values(ctx, K);
     K->fx48_refused = false;
+    K->s60_refused = false;
 }
 static int ensure_scaled(stan_ctx *ctx, stan_matrix *K) {
     if (K->scaled) return STAN_OK;
@@ -371,6 +391,12 @@ struct cg_run {
                                       // rows or whose shard is not representable: never a base for decisions the ranks must share)
     bool lazy_scale = false;          // the values are still K: the loop's first product scales them (k_spmv_first)
     bool reduced = false;             // the caller asked for a reduced-precision stream: fp64 check + refinement (every rank alike)
+    // STAN_OPT_VALUE_STREAM_60: the plain products of this fp64 solve read the lossless 60-bit stream (the same bits)
+    bool use60 = false;
+    uint32_t *pend60 = nullptr;       // its block, allocated in setup() (the placement search needs the vectors idle); encoded -- and handed to K --
+                                      // in front of the first plain product that finds the values scaled (make_stream60)
+    int64_t n60 = 0;                  // products enqueued on it
+    ~cg_run() { if (pend60) stan_dfree(ctx, pend60); }
     int refine = 0;                   // STAN_OPT_CG_REFINE, reduced-precision modes only
     int64_t n3 = 0, npad = 0, ng = 0, dof0 = 0;
     dev_scope bufs{ctx};
@@ -447,6 +473,9 @@ struct cg_run {
     // STAN_PREC_FP64 for the check / refresh products of a reduced-precision solve, `extra`: timed apart).
     int product(double *x, double *x2, double *y, int dot, double *out, int64_t k, p2p_out po, int kind, bool extra = false) {
         span_list &span = extra ? spmv64_sp : x2 ? spmv2_sp : spmv_sp;
+        if (pend60 && K->scaled) STANCHK(make_stream60());
+        const bool s60 = use60 && K->d_vals60 && !x2 && dot == 1 && !extra && !lazy_scale && kind == STAN_PREC_FP64;
+        if (s60) { kind = STAN_VALUE_STREAM_60; n60++; }
         span.begin(st_, k);
         auto go = [&](int which, hipStream_t s, bool last) -> unsigned {
             n_launch++;
@@ -485,6 +514,7 @@ struct cg_run {
     }
 
     int setup();
+    int make_stream60();
     int begin_pass(bool from_F, double eps_pass, bool *done);
     int iterate(double eps_pass, int32_t max_its_pass);
     int pass(bool from_F, double eps_pass, int32_t max_its_pass);
@@ -549,6 +579,23 @@ int cg_run::setup() {
     }
     sr = ctx->cg_single_reduce;
     foldr = ctx->cg_fold_reduce;
+    // The lossless 60-bit stream (s60.h) for the plain products of the classic fp64 loop on one rank, where k_spmv runs them
+    // on the padded streams: not the small-system kernel, the pair kernel, the folded copy or the single-reduction loop's
+    // DOT = 2 products (they keep the fp64 values, as do k_spmv_first and k_spmv2: the bits are the same either way).
+    // -1 (auto) also wants more than STREAM60_AUTO_ROWS block rows.  Either way the block must fit the pool budget and leave
+    // a floor of free memory (stan_matrix_alloc_s60 decides before it allocates); no room: fp64, and the profile's
+    // value_stream says so.
+    use60 = false;
+    if (ctx->value_stream_60 != 0 && precision_mode == STAN_PREC_FP64 && !dist && !sr && !stan_small_system(ctx, K) &&
+        !stan_pair_kernel(ctx) && (ctx->spmv_variant < 0 || ctx->spmv_variant == 9 || ctx->spmv_variant == 12) &&
+        (ctx->value_stream_60 > 0 || K->nb_glob > STREAM60_AUTO_ROWS) && K->nslices > 0 && !K->s60_refused &&
+        !(ctx->row_folding != 0 && K->fold_state == 1)) {
+        use60 = true;
+        if (!K->d_vals60) {   // (decided per solve: a matrix without room now may have it at its next solve)
+            STANCHK(stan_matrix_alloc_s60(ctx, K, &pend60));
+            if (!pend60) use60 = false;
+        }
+    }
 
     n3 = 3 * K->nloc;
     npad = (int64_t)K->nslices * 64;
@@ -588,6 +635,23 @@ int cg_run::setup() {
     h_st = ctx->h_status + SS_H_CG_STATUS;  // pinned
     h_sc = (double *)(ctx->h_status + SS_H_CG_SCALARS);
     poll.setup(events, h_st, 8);
+    return STAN_OK;
+}
+
+// The scaled fp64 values -> the 60-bit stream, into the block setup() took; waits for the count of refused entries (the
+// host is a few kernels ahead of the device here, no more).  A refused matrix keeps streaming fp64 for good.
+int cg_run::make_stream60() {
+    uint32_t *blk = pend60;
+    pend60 = nullptr;
+    int64_t refused = 0;
+    const int rc = stan_s60_encode(ctx, K->nslots, K->d_vals, blk, &refused);
+    if (rc != STAN_OK || refused != 0) {
+        stan_dfree(ctx, blk);
+        if (rc == STAN_OK) K->s60_refused = true;
+        use60 = false;
+        return rc;
+    }
+    K->d_vals60 = blk;
     return STAN_OK;
 }
 
@@ -818,7 +882,8 @@ int cg_run::finish(const double *x_result, int type, int64_t its, double rel_rec
     pf.rel_residual_recurrence = rel_rec;
     pf.rel_residual_fp64 = rel64;
     pf.refine_passes = passes;
-    const int64_t blk_bytes = vs == STAN_PREC_FIXED48 ? 60 : vs == STAN_PREC_MIXED ? 40 : 76;
+    const bool ran60 = n60 > 0;   // the plain products (what spmv_ms_total times) read the 60-bit stream: 68 B of values per block
+    const int64_t blk_bytes = ran60 ? 72 : vs == STAN_PREC_FIXED48 ? 60 : vs == STAN_PREC_MIXED ? 40 : 76;
     // bytes of the format actually streamed: a block of a packed slice carries a 2-B column offset
     // instead of a 4-B index (+ 4 B per slot for its base, shared by 64 rows)
     // (the folded copy has a packed column stream of its own, one base per slot, and 4 B of plan per row)
@@ -832,7 +897,7 @@ int cg_run::finish(const double *x_result, int type, int64_t its, double rel_rec
                     - (int64_t)(packed_frac * (double)K->nblocks * 2.0) + (read_packed ? bases * 4 : 0);
     pf.repacked_streams = folded ? 1 : 0;
     pf.col_slots_packed = packed ? K->slots_packed : 0;   // (the padded stream's count even when the products read the folded copy: looks unintended, kept)
-    pf.value_stream = vs;
+    pf.value_stream = ran60 ? STAN_VALUE_STREAM_60 : vs;
     // vector passes of one classic iteration: k_step reads r, v (+ p, x unless deferred; + b^ for the
     // merit sum) and writes r (+ x); k_update reads r, p (+ x when deferred) and writes p (+ x)
     pf.cg_iteration_vector_bytes = 3 * K->nloc * 8 * ((ctx->cg_defer_x && !ctx->cg_merit_stop ? 8 : 9) + (ctx->cg_merit_stop ? 1 : 0));

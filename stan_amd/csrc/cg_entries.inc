@@ -130,12 +130,62 @@ int stan_spmv_bench_device(stan_ctx *ctx, stan_matrix *K, int32_t precision_mode
         STANCHK(stan_matrix_make_fx48(ctx, K));
         if (!K->d_vals48) { ctx->err = "spmv_bench: matrix not representable in FIXED48"; return STAN_E_UNSUPPORTED; }
     }
+    if (precision_mode == STAN_VALUE_STREAM_60) {   // k_spmv on the lossless 60-bit stream of the scaled values
+        STANCHK(ensure_scaled(ctx, K));
+        if (!K->d_vals60 && !K->s60_refused && K->nslots > 0) {
+            uint32_t *blk = nullptr;
+            int64_t refused = 0;
+            STANCHK(stan_matrix_alloc_s60(ctx, K, &blk));
+            if (!blk) { ctx->err = "spmv_bench: no room for the 60-bit stream within the pool budget and the free-memory floor"; return STAN_E_ALLOC; }
+            const int rc =stan_s60_encode(ctx, K->nslots, K->d_vals, blk, &refused);
+            if (rc != STAN_OK || refused != 0) { stan_dfree(ctx, blk); K->s60_refused = rc == STAN_OK; STANCHK(rc); }
+            else K->d_vals60 = blk;
+        }
+        if (!K->d_vals60) { ctx->err = "spmv_bench: matrix not representable in the 60-bit stream"; return STAN_E_UNSUPPORTED; }
+    }
     dev_scope bufs(ctx);
     product_args pa{};
     STANCHK(timed_product_setup(ctx, K, precision_mode, nullptr, nullptr, 0, bufs, pa));
     float ms = 0;
     STANCHK(timed_launches(ctx, 3, 1, reps, [&]() { launch_product(ctx, K, pa); }, &ms));
     *avg_ms = reps > 0 ? ms : 0;
+    return STAN_OK;
+}
+
+namespace {
+// the 60-bit stream back to doubles through the products' own load9: out[slot][9][64]
+__global__ void __launch_bounds__(256)
+k_from_s60(int64_t nslots, const s60_t *in, double *out) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t slot = t >> 6;
+    const int lane = (int)(t & 63);
+    if (slot >= nslots) return;
+    double a[9];
+    load9<true, s60_t>(in + slot * vstream<s60_t>::STRIDE + lane, a);
+#pragma unroll
+    for (int j = 0; j < 9; j++) out[slot * 9 * 64 + j * 64 + lane] = a[j];
+}
+}  // namespace
+
+// Test hook of the 60-bit stream (stan_hip_stream60_roundtrip): `n` doubles, laid out as the values of ceil(n / 576) slots
+// (padded with zeros), through the encoder of the solve (k_to_s60) and the decoder of the products (load9) on the device;
+// *refused = the encoder's count.  Host pointers.
+int stan_stream60_roundtrip_device(stan_ctx *ctx, int64_t n, const double *in, double *out, int64_t *refused) {
+    hipStream_t st_ = ctx->stream;
+    const int64_t nslots = (n + 575) / 576, npad = nslots * 576;
+    dev_scope bufs(ctx);
+    double *d_in, *d_out;
+    uint32_t *d_enc;
+    STANCHK(bufs.alloc(&d_in, (size_t)npad));
+    STANCHK(bufs.alloc(&d_out, (size_t)npad));
+    STANCHK(bufs.alloc(&d_enc, (size_t)nslots * vstream<s60_t>::STRIDE));
+    HIPCHK(ctx, hipMemsetAsync(d_in, 0, (size_t)npad * 8, st_));
+    HIPCHK(ctx, hipMemcpyAsync(d_in, in, (size_t)n * 8, hipMemcpyHostToDevice, st_));
+    STANCHK(stan_s60_encode(ctx, nslots, d_in, d_enc, refused));
+    hipLaunchKernelGGL(k_from_s60, dim3(nblk(nslots * 64, 256)), dim3(256), 0, st_, nslots, (const s60_t *)d_enc, d_out);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, st_));
+    HIPCHK(ctx, hipStreamSynchronize(st_));
     return STAN_OK;
 }
 
@@ -157,8 +207,9 @@ int stan_stream_bench_device(stan_ctx *ctx, stan_matrix *K, int32_t reps, double
     return STAN_OK;
 }
 
-// Time of the fp64 SpMV of K streaming its values from `vals` (any contents: only the addresses
-// matter), median of 3 launches after a warm-up.  Used by the allocation-by-trial of placement.hip.
+// Time of the SpMV of K streaming its values from `vals` -- a block of the stream kind `precision` names (STAN_PREC_*, or
+// STAN_VALUE_STREAM_60: the product the loop will launch on it); any contents, only the addresses
+// matter --, median of 3 launches after a warm-up.  Used by the allocation-by-trial of placement.hip.
 // self_pair: the gather vector and the product are carved out of the FRONT of the candidate block
 // itself instead of the context's vectors -- by construction the same-group (slow) pairing, i.e.
 // the reference the search compares the real pairing with (profiles/r02/placement_cross_self_n148.txt).

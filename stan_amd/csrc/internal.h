@@ -262,6 +262,7 @@ struct stan_ctx {
     int prof_placement_moved_vectors = 0;   // 1: the search ended by re-allocating the CG's vectors
     int prof_colours = 0;
     int spmv_variant = -1; // -1 = auto (launch_product picks per value stream); >= 0: A/B lab
+    int value_stream_60 = -1;  // STAN_OPT_VALUE_STREAM_60: -1 = the fp64 loop of a large system on one rank streams the 60-bit values; 1 always where k_spmv runs; 0 never
     // profiling
     bool profiling = false;
     stan_profile prof{};
@@ -305,6 +306,8 @@ struct stan_matrix {
     float *d_vals32 = nullptr;      // same layout, fp32 copy (mixed precision)
     uint32_t *d_vals48 = nullptr;   // FIXED-48 stream of the scaled values, [slot][14][64] dwords
     bool fx48_refused = false;      // some |a_ij| >= 2 after scaling (K not SPD): fp64 is streamed
+    uint32_t *d_vals60 = nullptr;   // lossless 60-bit stream of the scaled values (s60.h), [slot][17][64] dwords
+    bool s60_refused = false;       // some scaled entry is outside its range (>= 2, below 2^-126, not finite): fp64 is streamed
     // Folded copy of the streams (fold.hip, STAN_OPT_ROW_FOLDING): long rows lend their tails to the idle slots of
     // the short rows of their slice; padded-slot layout with ~blocks/64 slots per slice.
     int32_t *d_fold_ptr = nullptr;      // [nslices + 1] first folded slot of every slice
@@ -396,6 +399,9 @@ int stan_matrix_make_folded(stan_ctx *ctx, stan_matrix *K, int32_t stream_kind, 
 void stan_matrix_drop_folded_values(stan_ctx *ctx, stan_matrix *K);
 void stan_matrix_abandon_folding(stan_ctx *ctx, stan_matrix *K);
 int stan_matrix_make_fx48(stan_ctx *ctx, stan_matrix *K);
+int stan_matrix_alloc_s60(stan_ctx *ctx, stan_matrix *K, uint32_t **out);   // a block for K's 60-bit stream, allocated by search like K's values; *out = nullptr (STAN_OK): no room within the budgets
+int stan_s60_encode(stan_ctx *ctx, int64_t nslots, const double *d_vals, uint32_t *d_out, int64_t *refused);   // synchronises the stream
+int stan_stream60_roundtrip_device(stan_ctx *ctx, int64_t n, const double *in, double *out, int64_t *refused);   // cg_entries.inc
 int stan_matrix_make_cols16(stan_ctx *ctx, stan_matrix *K);
 int stan_pack_columns(stan_ctx *ctx, int32_t nslices, int64_t nslots, const int32_t *d_slot_ptr, const int32_t *d_cols,
                       uint32_t **packed_out, int32_t **base_out, int32_t **pair_ptr_out, uint8_t **ok_out, int64_t *slots_packed,
@@ -473,7 +479,9 @@ int stan_comm_allgather_rows(stan_ctx *ctx, stan_matrix *K, double *d_full_block
 void stan_comm_abort(stan_ctx *ctx);
 
 // device memory helpers (see stan_pool)
-static inline int stan_dmalloc_bytes(stan_ctx *ctx, void **p, size_t bytes) {
+// may_flush = false: a block the caller can do without (an optional second copy of a matrix's values) -- a failed hipMalloc
+// leaves the parked blocks where they are
+static inline int stan_dmalloc_bytes(stan_ctx *ctx, void **p, size_t bytes, bool may_flush = true) {
     *p = nullptr;
     if (bytes == 0) bytes = 8;
     stan_pool &pool = ctx->pool;
@@ -493,7 +501,7 @@ static inline int stan_dmalloc_bytes(stan_ctx *ctx, void **p, size_t bytes) {
         }
     }
     hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess && !pool.avail.empty()) {  // make room and try once more
+    if (e != hipSuccess && may_flush && !pool.avail.empty()) {  // make room and try once more
         (void)hipGetLastError();
         pool.flush();
         e = hipMalloc(p, bytes);
@@ -625,7 +633,9 @@ int stan_group_size(stan_ctx *lead);
 
 // placement.hip
 int stan_probe_block(stan_ctx *ctx, const void *p, size_t bytes, float *ms_out);
+// second_copy: an optional further stream of a matrix whose own values are placed already -- the search leaves the CG's
+// vectors where they are (they are paired with the values) and a failure does not flush the pool
 int stan_dmalloc_streamed(stan_ctx *ctx, void **p, size_t bytes,
-                          const std::function<int(const void *, float *, bool)> &probe);
+                          const std::function<int(const void *, float *, bool)> &probe, bool second_copy = false);
 int stan_spmv_probe(stan_ctx *ctx, stan_matrix *K, const void *vals, size_t bytes, int32_t precision,
                     float *ms_out, bool self_pair = false);

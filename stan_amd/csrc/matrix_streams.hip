@@ -1,11 +1,13 @@
 // matrix_streams.hip -- the copies of a matrix's streams the products may read instead of the assembled ones, made once per
-// matrix: the fp32 and FIXED-48 value streams (STAN_PREC_MIXED, STAN_PREC_FIXED48) and the packed column stream (struct
+// matrix: the fp32 and FIXED-48 value streams (STAN_PREC_MIXED, STAN_PREC_FIXED48), the lossless 60-bit stream of the fp64
+// solve (STAN_OPT_VALUE_STREAM_60, s60.h) and the packed column stream (struct
 // colstream of spmv_kernels.inc; fold.hip packs the folded copy's columns through stan_pack_columns too).  The reference has
 // no counterpart: alglib.sparsesmv behind SolverFunctions.LinearSolver_CG (SolverFunctions.cs:270-330) reads one CRS matrix.
 #include <algorithm>
 
 #include "internal.h"
 #include "fx48.h"
+#include "s60.h"
 
 namespace {
 
@@ -41,6 +43,30 @@ k_to_fx48(int64_t nslots, const double *vals, uint32_t *out, unsigned long long 
     hi[9] = 0;
 #pragma unroll
     for (int m = 0; m < 5; m++) o[(9 + m) * 64] = hi[2 * m] | (hi[2 * m + 1] << 16);
+    if (nbad) atomicAdd(bad, (unsigned long long)nbad);
+}
+
+// scaled fp64 values -> the lossless 60-bit stream (s60.h; vstream<s60_t>); *bad counts the refused entries.  One lane per
+// block row of a slot, like k_to_fx48: every load and store is a contiguous wave access; both sides are touched once.
+__global__ void __launch_bounds__(256)
+k_to_s60(int64_t nslots, const double *vals, uint32_t *out, unsigned long long *bad) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t slot = t >> 6;
+    const int lane = (int)(t & 63);
+    if (slot >= nslots) return;
+    const double *v = vals + slot * 9 * 64 + lane;
+    uint32_t *o = out + slot * S60_ROWS * 64 + lane;
+    uint32_t hi[9], w[8];
+    int nbad = 0;
+#pragma unroll
+    for (int j = 0; j < 9; j++) {
+        uint32_t lo;
+        if (!s60_encode((uint64_t)__double_as_longlong(__builtin_nontemporal_load(v + j * 64)), &lo, &hi[j])) nbad++;
+        __builtin_nontemporal_store(lo, o + j * 64);
+    }
+    s60_pack_high(hi, w);
+#pragma unroll
+    for (int m = 0; m < 8; m++) __builtin_nontemporal_store(w[m], o + (9 + m) * 64);
     if (nbad) atomicAdd(bad, (unsigned long long)nbad);
 }
 
@@ -164,6 +190,64 @@ int stan_matrix_make_fx48(stan_ctx *ctx, stan_matrix *K) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->h_status[SS_COUNTER] != 0) { stan_dfree(ctx, out); K->fx48_refused = true; return STAN_OK; }
     K->d_vals48 = out;
+    return STAN_OK;
+}
+
+// The lossless 60-bit stream of the scaled values (STAN_OPT_VALUE_STREAM_60), in two steps, because a solve that scales K
+// with its first product (k_spmv_first) has the values only after its vectors are in use: the block -- from the pool, or by
+// the placement search, which times the very product that will stream it on the very block that is kept -- and the
+// encoding pass, which ends with the count of refused entries on the host.
+//
+// The block is a SECOND copy of the values (17/18 of the fp64 block, which stays) for the life of the matrix, and nothing
+// needs it: so whether there is room is decided BEFORE anything is allocated, and "no" costs nothing -- no hipMalloc that
+// fails, no flush of the parked blocks.  A parked block that fits is room (it is device memory this context holds
+// anyway).  Otherwise
+//  - pool budget: what this matrix gives back to the pool when it is freed -- its fp64 values, its columns and this block,
+//    those of the pool's size class -- must fit into STAN_OPT_POOL_MAX_BYTES together; beyond it the pool would return the
+//    oldest of them, the fp64 values, to the driver at every stan_hip_matrix_free, and the next assembly would pay a
+//    hipMalloc of that size (seconds at 400^3, see stan_pool);
+//  - free-memory floor: after the block is taken, as much again stays free as it takes (one more stream of the matrix --
+//    the folded copy, a reduced-precision stream -- or the arrays of a recovery still fit), and never less than a
+//    sixteenth of the device, the floor of the placement search's second stage.
+// Both are figures of the moment (hipMemGetInfo counts every process on the device).  At 148^3 the block is 6.0 GB next
+// to 6.4 + 0.4 GB; at 400^3 126 + 7 + 119 GB exceed the default pool budget (half of 288 GB) and, with the budget of a
+// process that owns the device, the floor: 2 x 119 GB are not free beside 133 GB.
+static bool s60_room(stan_ctx *ctx, const stan_matrix *K, size_t bytes) {
+    const stan_pool &pool = ctx->pool;
+    if (pool.enabled && bytes >= stan_pool::MIN_BYTES)
+        for (const stan_pool::blk &b : pool.avail)
+            if (b.cap >= bytes && b.cap <= bytes + bytes / 2) return true;
+    if (pool.enabled) {
+        const size_t own[3] = {(size_t)K->nslots * 9 * 64 * 8, (size_t)K->nslots * 64 * 4, bytes};
+        size_t parked = 0;
+        for (size_t b : own) parked += b >= stan_pool::MIN_BYTES ? b : 0;
+        if (bytes >= stan_pool::MIN_BYTES && parked > pool.max_bytes) return false;
+    }
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
+    const size_t floor_b = bytes > total_b / 16 ? bytes : total_b / 16;
+    return free_b >= bytes + floor_b;
+}
+int stan_matrix_alloc_s60(stan_ctx *ctx, stan_matrix *K, uint32_t **out) {
+    const size_t bytes = (size_t)K->nslots * S60_ROWS * 64 * 4;
+    *out = nullptr;
+    if (!s60_room(ctx, K, bytes)) return STAN_OK;
+    const int rc = stan_dmalloc_streamed(ctx, (void **)out, bytes, [&](const void *q, float *ms, bool self) {
+        return stan_spmv_probe(ctx, K, q, bytes, STAN_VALUE_STREAM_60, ms, self);
+    }, true);
+    if (rc == STAN_E_ALLOC) { ctx->err.clear(); *out = nullptr; return STAN_OK; }   // (fragmentation: room by the figures, no block)
+    return rc;
+}
+int stan_s60_encode(stan_ctx *ctx, int64_t nslots, const double *d_vals, uint32_t *d_out, int64_t *refused) {
+    *refused = 0;
+    if (nslots <= 0) return STAN_OK;
+    unsigned long long *d_bad = (unsigned long long *)(ctx->d_status + SS_COUNTER);
+    HIPCHK(ctx, hipMemsetAsync(d_bad, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(k_to_s60, dim3((unsigned)nblk(nslots * 64, 256)), dim3(256), 0, ctx->stream, nslots, d_vals, d_out, d_bad);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_COUNTER, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *refused = ctx->h_status[SS_COUNTER];
     return STAN_OK;
 }
 

@@ -95,14 +95,15 @@ int stan_probe_block(stan_ctx *ctx, const void *p, size_t bytes, float *ms_out) 
 // A hipMalloc of 6.4 GB takes 0.3 ms and a probe four launches: ~10 ms per candidate at 148^3,
 // once per context and size (the pool keeps the winner).
 int stan_dmalloc_streamed(stan_ctx *ctx, void **p, size_t bytes,
-                          const std::function<int(const void *, float *, bool)> &probe) {
+                          const std::function<int(const void *, float *, bool)> &probe, bool second_copy) {
     const int tries = ctx->placement_tries;
-    if (tries <= 1 || bytes < ((size_t)256 << 20) || !probe) return stan_dmalloc_bytes(ctx, p, bytes);
+    const bool may_flush = !second_copy;
+    if (tries <= 1 || bytes < ((size_t)256 << 20) || !probe) return stan_dmalloc_bytes(ctx, p, bytes, may_flush);
     // inside a peer-to-peer solve nothing may call hipFree (stan_ctx::defer_frees): no candidates to give back
-    if (ctx->defer_frees) return stan_dmalloc_bytes(ctx, p, bytes);
+    if (ctx->defer_frees) return stan_dmalloc_bytes(ctx, p, bytes, may_flush);
     // a parked block of the right size was chosen by an earlier search: take it
     for (const stan_pool::blk &b : ctx->pool.avail)
-        if (b.cap >= bytes && b.cap <= bytes + bytes / 2) return stan_dmalloc_bytes(ctx, p, bytes);
+        if (b.cap >= bytes && b.cap <= bytes + bytes / 2) return stan_dmalloc_bytes(ctx, p, bytes, may_flush);
     const bool trace = getenv("STAN_PLACEMENT_TRACE") != nullptr;   // one line per probe on stderr
     std::vector<void *> cand;
     std::vector<float> ms, tself;
@@ -158,7 +159,7 @@ int stan_dmalloc_streamed(stan_ctx *ctx, void **p, size_t bytes,
             if (t <= TOP * t_self || first_rule) stop = true;
         }
     }
-    if (cand.empty()) return stan_dmalloc_bytes(ctx, p, bytes);  // reports the allocation failure
+    if (cand.empty()) return stan_dmalloc_bytes(ctx, p, bytes, may_flush);  // reports the allocation failure
     size_t ibest = 0;   // the fastest real pairing: among the clear ones if there is one (a pairing that is fast but not clear of
     bool have = false;  // its own reference has a fast reference too: nothing the vectors' place would change)
     for (size_t i = 0; i < cand.size(); i++) {
@@ -166,8 +167,11 @@ int stan_dmalloc_streamed(stan_ctx *ctx, void **p, size_t bytes,
         if (clear && !clear_i) continue;
         if (!have || ms[i] < ms[ibest]) { ibest = i; have = true; }
     }
-    ctx->prof_placement_moved_vectors = 0;
-    if (!clear && cand.size() >= 2) {
+    // A second copy of a matrix's values (second_copy) takes the best candidate and leaves the vectors alone: they were
+    // placed for the fp64 values, which the first and the refresh products of the same loop go on streaming, and moving
+    // them for this block would undo that pairing unchecked.  prof_placement_moved_vectors keeps describing the vectors.
+    if (!second_copy) ctx->prof_placement_moved_vectors = 0;
+    if (!second_copy && !clear && cand.size() >= 2) {
         // Every candidate shares the vectors' group and they are all still allocated: vectors
         // allocated NOW lie beyond them.  Move the vectors instead of the values, if that pairing
         // is clear of the chosen candidate's own reference.
@@ -202,7 +206,7 @@ int stan_dmalloc_streamed(stan_ctx *ctx, void **p, size_t bytes,
     // first clear one change nothing (1.032-1.035 ms either way; the 1.00 ms pairings of a box come with the process, not with
     // the search); this stage walking its blocks after every search, keeping nothing, makes the solve 1 % SLOWER (1.013-1.016
     // against 1.004-1.007 ms: what is allocated afterwards lands elsewhere) -- profiles/r04/placement/extra_candidates_and_always_stage2_ab.txt.)
-    if ((sweep || force2 || (!clear && !ctx->prof_placement_moved_vectors)) && tself[ibest] > 0 && ctx->ws.v && ctx->ws.w) {
+    if (!second_copy && (sweep || force2 || (!clear && !ctx->prof_placement_moved_vectors)) && tself[ibest] > 0 && ctx->ws.v && ctx->ws.w) {
         std::vector<void *> blocks;
         std::vector<float> tb;
         size_t free_b = 0, total_b = 0;

@@ -37,8 +37,15 @@ __device__ __forceinline__ T ld_stream(const T *p) {
 // 0x43300000'00000000 | u are the double 2^52 + u.  The 2^-46 is applied to the three
 // gathered x values instead of the nine entries (powers of two commute with rounding), so
 // the arithmetic is the fp64 product with the quantised matrix.
-template <typename VT> struct vstream { static constexpr int STRIDE = 9 * 64; static constexpr bool FX = false; };
-template <> struct vstream<uint32_t> { static constexpr int STRIDE = 14 * 64; static constexpr bool FX = true; };
+// s60_t = the lossless 60-bit stream of the scaled fp64 values (s60.h; STAN_OPT_VALUE_STREAM_60): vals60[slot][17][64]
+// dwords, rows 0..8 the low 32 bits of the nine entries, rows 9..16 their nine 28-bit high parts (sign, 7-bit exponent
+// code, 20 mantissa bits) back to back.  68 B per block instead of 72 B; decoding is integer work only -- a funnel shift
+// or a mask, one add, one select per entry -- and yields the stored double bit for bit, so a product of this stream IS the
+// fp64 product.  (A tag type of its own: uint32_t is FIXED-48's.)
+struct s60_t { uint32_t w; };
+template <typename VT> struct vstream { static constexpr int STRIDE = 9 * 64; static constexpr bool FX = false, P60 = false; };
+template <> struct vstream<uint32_t> { static constexpr int STRIDE = 14 * 64; static constexpr bool FX = true, P60 = false; };
+template <> struct vstream<s60_t> { static constexpr int STRIDE = S60_ROWS * 64; static constexpr bool FX = false, P60 = true; };
 
 template <bool NT, typename VT>
 __device__ __forceinline__ void load9(const VT *vp, double a[9]) {
@@ -53,6 +60,14 @@ __device__ __forceinline__ void load9(const VT *vp, double a[9]) {
             const uint32_t h = (j & 1) ? (hw[j >> 1] >> 16) : (hw[j >> 1] & 0xffffu);
             a[j] = __hiloint2double((int)(0x43300000u | h), (int)lo[j]) - FX48_BIAS;
         }
+    } else if constexpr (vstream<VT>::P60) {
+        uint32_t lo[9], hw[8];
+#pragma unroll
+        for (int j = 0; j < 9; j++) lo[j] = ld_stream<NT>(&vp[j * 64].w);
+#pragma unroll
+        for (int m = 0; m < 8; m++) hw[m] = ld_stream<NT>(&vp[(9 + m) * 64].w);
+#pragma unroll
+        for (int j = 0; j < 9; j++) a[j] = __longlong_as_double((long long)s60_decode(lo[j], s60_high(hw, j)));
     } else {
 #pragma unroll
         for (int j = 0; j < 9; j++) a[j] = (double)ld_stream<NT>(vp + j * 64);
@@ -180,15 +195,35 @@ __device__ __forceinline__ void walk_slots(const colstream &cs, const int32_t *_
     }
 }
 
+// One row of a block on the 60-bit stream: y + (a0 x0 + a1 x1 + a2 x2) as the kernels of the fp64 stream compute it.
+// The library is compiled with fused multiply-adds allowed, and WHICH of the two products of a0 x0 + a1 x1 stays a rounded
+// multiplication of its own is then the compiler's choice: a1 x1 in every k_spmv of the fp64 stream -- but for entries
+// that come out of integer registers it chose a0 x0 in two rows of three, and a solve on the lossless stream ended
+// 1e-8 away from the fp64 one.  So the operations are spelled out here; no product feeds an addition, nothing is left
+// to fuse.  (tests/test_gpu_stream60.py compares solves bit for bit, k_spmv<s60_t, 1, 9> against k_spmv<double, 1, 9> and
+// <.., 12> against <.., 12>: a compiler that changes its mind about either fp64 kernel shows there.)
+__device__ __forceinline__ double s60_row(double a0, double a1, double a2, double x0, double x1, double x2, double y) {
+    double t = a1 * x1;
+    t = __builtin_fma(a0, x0, t);
+    t = __builtin_fma(a2, x2, t);
+    return y + t;
+}
+
 #define STAN_SPMV_BLOCK(C, VP)                                                        \
     {                                                                                 \
         double a[9];                                                                  \
         load9<NT, VT>(VP, a);                                                         \
         double x0 = x[3 * (C)], x1 = x[3 * (C) + 1], x2 = x[3 * (C) + 2];             \
         if (vstream<VT>::FX) { x0 *= FX48_INV; x1 *= FX48_INV; x2 *= FX48_INV; }      \
-        y0 += a[0] * x0 + a[1] * x1 + a[2] * x2;                                      \
-        y1 += a[3] * x0 + a[4] * x1 + a[5] * x2;                                      \
-        y2 += a[6] * x0 + a[7] * x1 + a[8] * x2;                                      \
+        if constexpr (vstream<VT>::P60) {                                             \
+            y0 = s60_row(a[0], a[1], a[2], x0, x1, x2, y0);                           \
+            y1 = s60_row(a[3], a[4], a[5], x0, x1, x2, y1);                           \
+            y2 = s60_row(a[6], a[7], a[8], x0, x1, x2, y2);                           \
+        } else {                                                                      \
+            y0 += a[0] * x0 + a[1] * x1 + a[2] * x2;                                  \
+            y1 += a[3] * x0 + a[4] * x1 + a[5] * x2;                                  \
+            y2 += a[6] * x0 + a[7] * x1 + a[8] * x2;                                  \
+        }                                                                             \
     }
 
 template <typename VT, int DOT, int VAR>

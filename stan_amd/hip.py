@@ -35,6 +35,8 @@ OPT_COMM_P2P = 18
 OPT_ROW_FOLDING = 19
 OPT_CG_REFINE = 20
 OPT_CG_LAZY_SCALING = 21
+OPT_VALUE_STREAM_60 = 22
+VALUE_STREAM_60 = 3   # Profile.value_stream of an fp64 solve whose plain products read the lossless 60-bit stream
 E_HIP, E_ARG, E_ALLOC, E_DETJ, E_DOF_LAYOUT, E_VALENCE, E_COMM, E_UNSUPPORTED = (
     -1, -2, -3, -4, -5, -6, -7, -8)
 
@@ -44,6 +46,7 @@ EXPORTS = [
     "stan_hip_assemble_hex8", "stan_hip_assemble_hex8_dev", "stan_hip_matrix_free",
     "stan_hip_cg_solve", "stan_hip_cg_solve_dev", "stan_hip_cg_solve_multi", "stan_hip_cg_solve_multi_dev", "stan_hip_matrix_info", "stan_hip_ke_hex8",
     "stan_hip_ke_hex8_batch", "stan_hip_matrix_to_csr", "stan_hip_spmv", "stan_hip_spmv_bench", "stan_hip_stream_bench",
+    "stan_hip_stream60_roundtrip",
     "stan_hip_set_profiling", "stan_hip_get_profile", "stan_hip_set_option", "stan_hip_recover_hex8", "stan_hip_recover_hex8_dev",
     "stan_hip_nodal_forces_hex8", "stan_hip_pool_info",
     "stan_hip_matrix_plan", "stan_hip_spmv_local", "stan_hip_comm_info", "stan_hip_comm_library",
@@ -193,6 +196,14 @@ class Context:
 
     def set_profiling(self, on=True):
         self._chk(self.lib.stan_hip_set_profiling(self.h, C.c_int32(1 if on else 0)))
+
+    def stream60_roundtrip(self, values):
+        """(the doubles as the products would decode them from the 60-bit stream, entries the encoder refused)"""
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        out, refused = np.zeros_like(values), C.c_int64(0)
+        self._chk(self.lib.stan_hip_stream60_roundtrip(self.h, C.c_int64(values.size), _ptr(values, C.c_double),
+                                                       _ptr(out, C.c_double), C.byref(refused)))
+        return out, refused.value
 
     def profile(self):
         p = Profile()
