@@ -381,14 +381,14 @@ void stan_hip_matrix_free(stan_matrix *K) {
     }
     // the solves that used these buffers have been synchronised by their own calls; the blocks go
     // back to the context's pool (stan_pool) or to the driver
-    for (void *q : {(void *)K->d_slot_ptr, (void *)K->d_rowlen, (void *)K->d_rowof, (void *)K->d_posof, (void *)K->d_cols, (void *)K->d_vals,
-                    (void *)K->d_vals32, (void *)K->d_vals48, (void *)K->d_vals60, (void *)K->d_cols16, (void *)K->d_colbase,
-                    (void *)K->d_pair_ptr, (void *)K->d_slice_packed, (void *)K->d_red, (void *)K->d_fixmask,
-                    (void *)K->d_scale, (void *)K->d_send_rows, (void *)K->d_halo_glob, (void *)K->d_sendbuf,
-                    (void *)K->d_sl_int, (void *)K->d_sl_bnd, (void *)K->d_fold_ptr, (void *)K->d_fold_meta,
-                    (void *)K->d_fold_plan, (void *)K->d_fold_cols, (void *)K->d_fold_cols16, (void *)K->d_fold_colbase,
-                    (void *)K->d_fold_pair_ptr, (void *)K->d_fold_packed, (void *)K->d_fold_vals, (void *)K->d_fold_vals32, (void *)K->d_fold_vals48})
-        stan_dfree(K->ctx, q);
+    // (the padded streams first, then the folded copy: the order decides which parked block the next matrix gets)
+    auto release = [&](std::initializer_list<void *> blocks) { for (void *q : blocks) stan_dfree(K->ctx, q); };
+    release({K->d_slot_ptr, K->d_rowlen, K->d_rowof, K->d_posof, K->d_cols});
+    for (const stan_value_stream &s : K->vs) release({s.padded});
+    release({K->pk.cols16, K->pk.colbase, K->pk.pair_ptr, K->pk.packed, K->d_red, K->d_fixmask, K->d_scale, K->d_send_rows, K->d_halo_glob,
+             K->d_sendbuf, K->d_sl_int, K->d_sl_bnd, K->d_fold_ptr, K->d_fold_meta, K->d_fold_plan, K->d_fold_cols, K->fold_pk.cols16,
+             K->fold_pk.colbase, K->fold_pk.pair_ptr, K->fold_pk.packed});
+    for (const stan_value_stream &s : K->vs) release({s.folded});
     delete K;
 }
 
@@ -937,7 +937,7 @@ int stan_hip_matrix_to_csr(stan_ctx *ctx, stan_matrix *K, int32_t upper_only, in
     if (!rowlen.empty()) HIPCHK(ctx, hipMemcpyAsync(rowlen.data(), K->d_rowlen, rowlen.size() * 4, hipMemcpyDeviceToHost, st));
     if (!posof.empty()) HIPCHK(ctx, hipMemcpyAsync(posof.data(), K->d_posof, posof.size() * 4, hipMemcpyDeviceToHost, st));
     if (!cols.empty()) HIPCHK(ctx, hipMemcpyAsync(cols.data(), K->d_cols, cols.size() * 4, hipMemcpyDeviceToHost, st));
-    if (!vals.empty()) HIPCHK(ctx, hipMemcpyAsync(vals.data(), K->d_vals, vals.size() * 8, hipMemcpyDeviceToHost, st));
+    if (!vals.empty()) HIPCHK(ctx, hipMemcpyAsync(vals.data(), K->vals64(), vals.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(red.data(), K->d_red, red.size() * 4, hipMemcpyDeviceToHost, st));
     if (scaled && !scale.empty()) HIPCHK(ctx, hipMemcpyAsync(scale.data(), K->d_scale, scale.size() * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));

@@ -1072,10 +1072,7 @@ int assembly_run::layout() {
                            K->d_cols, wmax);
     }
     // (after the columns are in place: an allocation by trial times the SpMV itself, which needs the columns)
-    return stan_dmalloc_streamed(ctx, (void **)&K->d_vals, (size_t)K->nslots * 9 * 64 * 8,
-                                 [&](const void *q, float *ms, bool self) {
-                                     return stan_spmv_probe(ctx, K, q, (size_t)K->nslots * 9 * 64 * 8, STAN_PREC_FP64, ms, self);
-                                 });
+    return stan_matrix_alloc_stream(ctx, K, STAN_PREC_FP64, K->nslots, &K->vs[STAN_PREC_FP64].padded);
 }
 
 int assembly_run::numeric() {
@@ -1090,7 +1087,7 @@ int assembly_run::numeric() {
         A.ptr = d_ptr; A.list = d_list; A.crow = d_crow; A.xrow = d_xrow;
         A.elem_mat = d_elem_mat; A.elem_type = d_elem_type; A.mat_lamG = d_lamG;
         A.fixmask = K->d_fixmask; A.halo_glob = K->d_halo_glob; A.halo_rank = d_halo_rank;
-        A.rowlen = K->d_rowlen; A.rowof = K->d_rowof; A.slot_ptr = K->d_slot_ptr; A.cols = K->d_cols; A.vals = K->d_vals;
+        A.rowlen = K->d_rowlen; A.rowof = K->d_rowof; A.slot_ptr = K->d_slot_ptr; A.cols = K->d_cols; A.vals = K->vals64();
         A.bad_elem = (long long *)(d_status + SS_BAD_ELEM);
         A.wide_slices = nullptr;
         A.wmax = K->max_row_blocks > 0 ? K->max_row_blocks : 1;

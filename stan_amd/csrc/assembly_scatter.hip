@@ -193,7 +193,7 @@ int stan_assemble_colour_scatter(stan_ctx *ctx, stan_matrix *K, int64_t n_elem, 
                                  const uint8_t *d_elem_type, const double *d_lamG, const int64_t *d_ptr,
                                  const int32_t *d_list, long long *d_bad) {
     hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemsetAsync(K->d_vals, 0, (size_t)K->nslots * 9 * 64 * 8, st));
+    HIPCHK(ctx, hipMemsetAsync(K->vals64(), 0, (size_t)K->nslots * 9 * 64 * 8, st));
     ctx->prof_colours = 0;
     if (n_elem > 0) {
         int32_t *d_col[2], *d_tent, *d_cnt = nullptr, *d_order, *d_maxc;
@@ -241,13 +241,13 @@ int stan_assemble_colour_scatter(stan_ctx *ctx, stan_matrix *K, int64_t n_elem, 
             if (cnt[c] > 0)
                 hipLaunchKernelGGL(k_scatter, dim3(nblk(cnt[c], 4)), dim3(256), 0, st, cnt[c], d_order + off[c],
                                    d_conn, d_perm, d_xyz, d_elem_mat, d_elem_type, d_lamG, K->d_rowlen,
-                                   K->d_posof, K->d_slot_ptr, K->d_cols, K->d_vals, d_bad);
+                                   K->d_posof, K->d_slot_ptr, K->d_cols, K->vals64(), d_bad);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipStreamSynchronize(st));  // temporaries are freed on return
     }
     if (K->nslices > 0)
         hipLaunchKernelGGL(k_apply_bc, dim3(nblk(K->nslices, 4)), dim3(256), 0, st, K->nslices, K->nloc,
-                           K->d_slot_ptr, K->d_rowof, K->d_rowlen, K->d_cols, K->d_vals, K->d_fixmask);
+                           K->d_slot_ptr, K->d_rowof, K->d_rowlen, K->d_cols, K->vals64(), K->d_fixmask);
     HIPCHK(ctx, hipGetLastError());
     return STAN_OK;
 }

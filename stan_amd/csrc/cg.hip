@@ -18,10 +18,13 @@
 // bit-reproducible).  alpha, beta and every stopping decision live in device memory; the
 // host only enqueues iterations and polls a status word every CHUNK iterations, so
 // there is no host synchronisation inside an iteration.
+// Which product kernel reads which value stream of K (stan_matrix::vs, a table by kind) is decided in ONE place, plan_products:
+// a product_plan per solve (per call in cg_entries.inc), which launch_product dispatches on and cg_run reads.
 #include <chrono>
 #include <cmath>
 #include <thread>
 #include <type_traits>
+#include <utility>
 
 #include "internal.h"
 #include "s60.h"
@@ -113,38 +116,74 @@ struct chunk_poll {
     }
 };
 
-// k_spmv_small instead of k_spmv: decided by the GLOBAL number of block rows, so that a shard and the
-// whole matrix sum their rows in the same order
-inline bool stan_small_system(const stan_ctx *ctx, const stan_matrix *K) {
-    return ctx->spmv_variant < 0 && K->nb_glob <= ctx->spmv_small_rows;
-}
-
-inline bool stan_pair_kernel(const stan_ctx *ctx) { return ctx->spmv_variant == 20; }
-
 // STAN_OPT_VALUE_STREAM_60 = -1 takes the 60-bit stream above this many block rows -- the small-system kernel's DEFAULT bound,
 // whatever STAN_OPT_SPMV_SMALL is set to: a matrix below it lives in the caches and gains nothing from fewer bytes
 constexpr int64_t STREAM60_AUTO_ROWS = 150000;
 
-// the folded form of the value stream `vals` of K, if the products are to read it (fold.hip)
-template <typename VT> const VT *fold_vals(const stan_ctx *ctx, const stan_matrix *K, const VT *vals);
-template <> const double *fold_vals<double>(const stan_ctx *ctx, const stan_matrix *K, const double *vals) {
-    if (ctx->fold_probe && (const void *)vals == ctx->fold_probe) return vals;
-    return ctx->row_folding != 0 && vals == K->d_vals ? K->d_fold_vals : nullptr;
+// Which kernel reads which stream of K: filled by plan_products; what a solve learns later enters through the named steps below
+struct product_plan {
+    // the kernel of a PLAIN product (one right-hand side, not a matrix's first): one workgroup per slice (k_spmv_small), two
+    // wavefronts per slice (k_spmv_pair; STAN_OPT_SPMV_VARIANT 20), or one wavefront per slice: k_spmv -- k_spmv_fold where
+    // `folding` finds a folded block.  The other products (k_spmv2, k_spmv_first) are wave kernels whatever the form.
+    enum { SMALL, PAIR, WAVE } form = WAVE;
+    int forced_var = -1;      // k_spmv's VAR of the WAVE form; -1: per stream (var())
+    bool folding = false;     // a product of K's own stream of a kind reads the folded block of that kind, where K has one (fold.hip)
+    int spb = 4;              // slices per workgroup of a plain product; every other product: 4
+    unsigned blocks = 0;      // workgroups of a whole-matrix launch in that form, the most of any form: sizes the partial sums
+    int vs = STAN_PREC_FP64;  // the stream the loop's products read on THIS rank (FIXED-48 falls back to fp64 on a rank that owns no
+                              // rows or whose shard is not representable: never a base for decisions the ranks must share)
+    bool may_lazy_scale = false;   // the loop's first product may scale the matrix on its way (k_spmv_first)
+    bool stream60 = false;    // the plain p.Ap products of the fp64 loop read the lossless 60-bit stream (the same bits)
+    bool folded = false;      // the loop's stream has a folded block (what the profile reports as repacked) ...
+    const stan_colpack *cols = nullptr;   // ... and then the folded layout's packed columns and slots are what the profile's bytes count
+    int64_t slots = 0;
+    // auto (-1): non-temporal matrix stream + XCD-chunked workgroup mapping (variant 9), with the
+    // loop unrolled by 4 for the FIXED-48 stream, whose iterations carry 21 % fewer bytes in
+    // flight (variant 12).  One process, one box (tools/fx48_variants.py, min of 3 x 20 launches):
+    // fp64 plain 1.181 / nt 1.102 / nt+chunk 1.100 ms; FIXED-48 1.003 / 0.955 / nt+unroll4 0.925;
+    // fp32 0.636 / 0.583 / 0.580.
+    int var(bool fx) const { return forced_var >= 0 ? forced_var : fx ? 12 : 9; }
+    // behind the planning pass of fold.hip (K->fold_state decided, no value touched): a folded copy is made from the SCALED values
+    void fold_planned(const stan_matrix *K) { may_lazy_scale = may_lazy_scale && !(folding && K->fold_state == 1); }
+    // behind stan_matrix_make_fx48: the FIXED-48 encoder refuses a K that is not SPD-scalable, the fp64 values serve
+    void value_stream_built(const stan_matrix *K) { if (vs == STAN_PREC_FIXED48 && !K->vs[vs].padded) vs = STAN_PREC_FP64; }
+    // behind the packed columns and the folded copy the solve builds: what the products will find
+    void copies_built(const stan_matrix *K) {
+        stream60 = stream60 && !K->vs[STAN_VALUE_STREAM_60].refused && !(folding && K->fold_state == 1);
+        folded = folding && K->vs[vs].folded != nullptr;   // (whatever the form: a small system reports a copy an earlier solve left)
+        cols = folded ? &K->fold_pk : &K->pk;
+        slots = folded ? K->nfslots : K->nslots;
+    }
+    void stream60_unavailable() { stream60 = false; }   // no room for its block, or the encoder refused an entry: the fp64 values serve
+};
+
+// precision_mode: the stream the caller asks for; dist: a rank of a sharded matrix; sr: the single-reduction loop
+product_plan plan_products(const stan_ctx *ctx, const stan_matrix *K, int precision_mode, bool dist, bool sr) {
+    product_plan P;
+    const int v = ctx->spmv_variant;
+    // k_spmv_small: decided by the GLOBAL number of block rows, so that a shard and the whole matrix sum their rows in the same order
+    P.form = v < 0 && K->nb_glob <= ctx->spmv_small_rows ? product_plan::SMALL : v == 20 ? product_plan::PAIR : product_plan::WAVE;
+    P.forced_var = v;
+    P.folding = ctx->row_folding != 0;
+    P.spb = P.form == product_plan::SMALL ? 1 : P.form == product_plan::PAIR ? 2 : 4;
+    P.blocks = nblk(K->nslices, P.spb);
+    P.vs = precision_mode;
+    const bool fp64_one_rank = precision_mode == STAN_PREC_FP64 && !dist && P.form != product_plan::SMALL && K->nslices > 0;
+    // The first product of the loop may scale the matrix on its way (k_spmv_first) instead of a pass of its own: the fp64
+    // stream of one rank, the large-system kernel in its default variant, no folded copy (fold_planned), a first product
+    // that is a plain one (a residual refresh at iteration 1 is a two-product pass).
+    P.may_lazy_scale = !K->scaled && ctx->cg_lazy_scaling && fp64_one_rank && v < 0 && ctx->cg_rupdate != 1;
+    // The lossless 60-bit stream (s60.h) for the plain products of the classic fp64 loop on one rank, where k_spmv runs them
+    // on the padded streams: not the small-system kernel, the pair kernel, the folded copy (copies_built) or the
+    // single-reduction loop's DOT = 2 products (they keep the fp64 values, as do k_spmv_first and k_spmv2: the bits are the
+    // same either way).  -1 (auto) also wants more than STREAM60_AUTO_ROWS block rows.
+    P.stream60 = ctx->value_stream_60 != 0 && fp64_one_rank && !sr && (v < 0 || v == 9 || v == 12) &&
+                 (ctx->value_stream_60 > 0 || K->nb_glob > STREAM60_AUTO_ROWS);
+    return P;
 }
-template <> const float *fold_vals<float>(const stan_ctx *ctx, const stan_matrix *K, const float *vals) {
-    if (ctx->fold_probe && (const void *)vals == ctx->fold_probe) return vals;
-    return ctx->row_folding != 0 && vals == K->d_vals32 ? K->d_fold_vals32 : nullptr;
-}
-template <> const uint32_t *fold_vals<uint32_t>(const stan_ctx *ctx, const stan_matrix *K, const uint32_t *vals) {
-    if (ctx->fold_probe && (const void *)vals == ctx->fold_probe) return vals;
-    return ctx->row_folding != 0 && vals == K->d_vals48 ? K->d_fold_vals48 : nullptr;
-}
-inline colstream fold_cols_of(const stan_ctx *ctx, const stan_matrix *K) {
-    return ctx->cols16 && K->d_fold_cols16 ? make_colstream(K->d_fold_cols16, K->d_fold_colbase, K->d_fold_pair_ptr, K->d_fold_packed, K->nfslots)
-                                           : NO_COLSTREAM;
-}
-inline colstream colstream_of(const stan_ctx *ctx, const stan_matrix *K) {
-    return ctx->cols16 && K->d_cols16 ? make_colstream(K->d_cols16, K->d_colbase, K->d_pair_ptr, K->d_slice_packed, K->nslots) : NO_COLSTREAM;
+
+inline colstream colstream_of(const stan_ctx *ctx, const stan_colpack &c, int64_t nslots) {
+    return ctx->cols16 && c.cols16 ? make_colstream(c, nslots) : NO_COLSTREAM;
 }
 
 // One product, as it is enqueued: y = A x with `dot` sums (k_spmv's DOT), or -- x2 given, dot = 1 -- y = A x and
@@ -160,6 +199,7 @@ struct product_args {
     int64_t k;
     int kind;           // the value stream (STAN_PREC_*)
     const void *vals;   // nullptr: K's own stream of that kind
+    bool vals_folded;   // `vals` is a block for a FOLDED stream (the placement search of fold.hip times its candidates)
     bool first;         // the first product of an unscaled fp64 matrix scales it on the way (k_spmv_first)
 };
 // the run-time choices of a product -- value stream and DOT -- as the types of f's arguments
@@ -170,52 +210,59 @@ void with_product_types(const stan_matrix *K, const product_args &a, F f) {
         else if (a.dot == 1) f(vals, std::integral_constant<int, 1>());
         else f(vals, std::integral_constant<int, 0>());
     };
-    if (a.kind == STAN_PREC_MIXED) by_dot(a.vals ? (const float *)a.vals : K->d_vals32);
-    else if (a.kind == STAN_PREC_FIXED48) by_dot(a.vals ? (const uint32_t *)a.vals : K->d_vals48);
-    else by_dot(a.vals ? (const double *)a.vals : K->d_vals);
+    const void *vals = a.vals ? a.vals : K->vs[a.kind].padded;
+    if (a.kind == STAN_PREC_MIXED) by_dot((const float *)vals);
+    else if (a.kind == STAN_PREC_FIXED48) by_dot((const uint32_t *)vals);
+    else by_dot((const double *)vals);
+}
+// the folded form of the value stream `vals` of K, if the product is to read it (fold.hip)
+template <typename VT>
+const VT *fold_vals(const product_plan &P, const stan_matrix *K, const product_args &a, const VT *vals) {
+    if (a.vals_folded) return vals;
+    const stan_value_stream &s = K->vs[a.kind];
+    return P.folding && (const void *)vals == s.padded ? (const VT *)s.folded : nullptr;
 }
 // which: 0 = all slices, 1 = interior list, 2 = boundary list (partials offset by the
 // interior launch's block count).  Returns the number of partial slots this launch writes.
 // `fold`: counter/out of the folded reduction (counter == nullptr: partials only); nblocks and np
 // are filled in here (np = this launch's slots + poff: the boundary launch of a split product
 // also adds up what the interior launch left).
-unsigned launch_product(stan_ctx *ctx, stan_matrix *K, const product_args &a, int which = 0, hipStream_t stream = nullptr,
-                        fold_args fold = NO_FOLD) {
+unsigned launch_product(stan_ctx *ctx, stan_matrix *K, const product_plan &P, const product_args &a, int which = 0,
+                        hipStream_t stream = nullptr, fold_args fold = NO_FOLD) {
     if (!stream) stream = ctx->stream;
     const int32_t *slist = which == 1 ? K->d_sl_int : which == 2 ? K->d_sl_bnd : nullptr;
     const int32_t nlist = which == 1 ? K->n_sl_int : which == 2 ? K->n_sl_bnd : K->nslices;
-    // slices per workgroup: one (k_spmv_small) or two (k_spmv_pair; STAN_OPT_SPMV_VARIANT 20) for a single product
-    // that is not a matrix's first, four for every other kernel
-    // (the lossless 60-bit stream belongs to k_spmv alone: cg_run picks it only where that kernel would run)
+    // the plan's form and slices per workgroup for a single product that is not a matrix's first, k_spmv's for every other
+    // (the lossless 60-bit stream belongs to k_spmv alone: the plan picks it only where that kernel would run)
     const bool s60 = a.kind == STAN_VALUE_STREAM_60;
-    const bool plain = !a.x2 && !a.first, small = plain && !s60 && stan_small_system(ctx, K), pair = plain && !s60 && !small && stan_pair_kernel(ctx);
-    const int spb = small ? 1 : pair ? 2 : 4;
+    const bool plain = !a.x2 && !a.first && !s60, small = plain && P.form == product_plan::SMALL, pair = plain && P.form == product_plan::PAIR;
+    const int spb = plain ? P.spb : 4;
     const int32_t poff = which == 2 ? (int32_t)nblk(K->n_sl_int, spb) : 0;
     const unsigned grid = nblk(nlist, spb);
     if (grid == 0) return 0;
     fold.nblocks = grid;
     fold.np = (int)grid + poff;
-    const colstream cs = colstream_of(ctx, K);
+    const colstream cs = colstream_of(ctx, K->pk, K->nslots);
     if (s60) {   // one plain product with its p.Ap sum: k_spmv<s60_t, 1, 9 | 12>, nothing else is instantiated for this stream
-        const s60_t *vals = (const s60_t *)(a.vals ? a.vals : (const void *)K->d_vals60);
-        const dim3 g(grid), b(256);
-        if (ctx->spmv_variant == 12)
-            hipLaunchKernelGGL((k_spmv<s60_t, 1, 12>), g, b, 0, stream, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols,
-                               vals, a.x, a.y, a.partial, a.st, a.k, slist, nlist, poff, fold, cs);
-        else
-            hipLaunchKernelGGL((k_spmv<s60_t, 1, 9>), g, b, 0, stream, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols,
-                               vals, a.x, a.y, a.partial, a.st, a.k, slist, nlist, poff, fold, cs);
+        const s60_t *vals = (const s60_t *)(a.vals ? a.vals : K->vs[a.kind].padded);
+        auto launch = [&](auto var) {
+            hipLaunchKernelGGL((k_spmv<s60_t, 1, decltype(var)::value>), dim3(grid), dim3(256), 0, stream, K->nslices, K->nloc, K->d_slot_ptr,
+                               K->d_rowof, K->d_cols, vals, a.x, a.y, a.partial, a.st, a.k, slist, nlist, poff, fold, cs);
+        };
+        if (P.var(false) == 12) launch(std::integral_constant<int, 12>());
+        else launch(std::integral_constant<int, 9>());
         return grid;
     }
     with_product_types(K, a, [&](auto *vals, auto dot_tag) {
         using VT = std::remove_cv_t<std::remove_pointer_t<decltype(vals)>>;
         constexpr int DOT = decltype(dot_tag)::value;
         const dim3 g(grid), b(256);
-        const VT *fv = small || pair || a.first ? nullptr : fold_vals<VT>(ctx, K, vals);
+        const VT *fv = small || pair || a.first ? nullptr : fold_vals(P, K, a, vals);
+        const colstream fcs = colstream_of(ctx, K->fold_pk, K->nfslots);
         if constexpr (std::is_same_v<VT, double>)
             if (a.first) {
                 hipLaunchKernelGGL(k_spmv_first<DOT>, g, b, 0, stream, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols,
-                                   K->d_vals, K->d_scale, a.x, a.y, a.partial, a.st, a.k, fold, cs);
+                                   K->vals64(), K->d_scale, a.x, a.y, a.partial, a.st, a.k, fold, cs);
                 return;
             }
         if constexpr (DOT == 1)
@@ -223,7 +270,7 @@ unsigned launch_product(stan_ctx *ctx, stan_matrix *K, const product_args &a, in
                 if (fv)
                     hipLaunchKernelGGL((k_spmv_fold<VT, 1, 2>), g, b, 0, stream, K->nslices, K->nloc, K->d_fold_ptr, K->d_rowof,
                                        K->d_fold_meta, K->d_fold_cols, fv, a.x, a.x2, a.y, a.y2, a.partial, a.st, a.k, slist, nlist,
-                                       poff, fold, fold_cols_of(ctx, K));
+                                       poff, fold, fcs);
                 else
                     hipLaunchKernelGGL((k_spmv2<VT>), g, b, 0, stream, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols,
                                        vals, a.x, a.x2, a.y, a.y2, a.partial, a.st, a.k, slist, nlist, poff, fold, cs);
@@ -242,7 +289,7 @@ unsigned launch_product(stan_ctx *ctx, stan_matrix *K, const product_args &a, in
         if (fv) {
             hipLaunchKernelGGL((k_spmv_fold<VT, DOT, 1>), g, b, 0, stream, K->nslices, K->nloc, K->d_fold_ptr, K->d_rowof,
                                K->d_fold_meta, K->d_fold_cols, fv, a.x, (const double *)nullptr, a.y, (double *)nullptr, a.partial,
-                               a.st, a.k, slist, nlist, poff, fold, fold_cols_of(ctx, K));
+                               a.st, a.k, slist, nlist, poff, fold, fcs);
             return;
         }
 #define SPMV_CASE(V)                                                                                                          \
@@ -250,13 +297,7 @@ unsigned launch_product(stan_ctx *ctx, stan_matrix *K, const product_args &a, in
         hipLaunchKernelGGL((k_spmv<VT, DOT, V>), g, b, 0, stream, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols, \
                            vals, a.x, a.y, a.partial, a.st, a.k, slist, nlist, poff, fold, cs);                               \
         break;
-        // auto (-1): non-temporal matrix stream + XCD-chunked workgroup mapping (variant 9), with the
-        // loop unrolled by 4 for the FIXED-48 stream, whose iterations carry 21 % fewer bytes in
-        // flight (variant 12).  One process, one box (tools/fx48_variants.py, min of 3 x 20 launches):
-        // fp64 plain 1.181 / nt 1.102 / nt+chunk 1.100 ms; FIXED-48 1.003 / 0.955 / nt+unroll4 0.925;
-        // fp32 0.636 / 0.583 / 0.580.
-        const int variant = ctx->spmv_variant >= 0 ? ctx->spmv_variant : vstream<VT>::FX ? 12 : 9;
-        switch (variant) {
+        switch (P.var(vstream<VT>::FX)) {
             SPMV_CASE(9) SPMV_CASE(12)
             default:
             SPMV_CASE(0)
@@ -278,7 +319,7 @@ static int ensure_scale_vector(stan_ctx *ctx, stan_matrix *K) {
     hipLaunchKernelGGL(k_fill, dim3(vec_grid(ns)), dim3(VEC_T), 0, ctx->stream, K->d_scale, ns, 1.0);
     if (K->nloc > 0)
         hipLaunchKernelGGL(k_diag_scale, dim3(nblk(K->nloc, 256)), dim3(256), 0, ctx->stream, K->nloc,
-                           K->d_rowlen, K->d_posof, K->d_slot_ptr, K->d_cols, K->d_vals, K->d_scale);
+                           K->d_rowlen, K->d_posof, K->d_slot_ptr, K->d_cols, K->vals64(), K->d_scale);
     if (stan_sharded(ctx)) {
         if (ctx->comm_p2p && ctx->p2p) {
             // Peer to peer, my neighbours write their rows straight into my halo region, which the k_fill above
@@ -301,19 +342,19 @@ static void mark_scaled(stan_ctx *ctx, stan_matrix *K) {
     K->scaled = true;
     // copies of the value stream made before the scaling (stan_hip_spmv_bench on a fresh matrix)
     // hold the unscaled K: a later solve must not iterate on them
-    if (K->d_vals32) { stan_dfree(ctx, K->d_vals32); K->d_vals32 = nullptr; }
-    if (K->d_vals48) { stan_dfree(ctx, K->d_vals48); K->d_vals48 = nullptr; }
-    if (K->d_vals60) { stan_dfree(ctx, K->d_vals60); K->d_vals60 = nullptr; }
+    for (int kind = STAN_PREC_FP64 + 1; kind < STAN_NSTREAMS; kind++) {
+        stan_dfree(ctx, K->vs[kind].padded);
+        K->vs[kind].padded = nullptr;
+        K->vs[kind].refused = false;
+    }
     stan_matrix_drop_folded_values(ctx, K);
-    K->fx48_refused = false;
-    K->s60_refused = false;
 }
 static int ensure_scaled(stan_ctx *ctx, stan_matrix *K) {
     if (K->scaled) return STAN_OK;
     STANCHK(ensure_scale_vector(ctx, K));
     if (K->nslices > 0)
         hipLaunchKernelGGL(k_scale_matrix, dim3(nblk(K->nslices, 4)), dim3(256), 0, ctx->stream,
-                           K->nslices, K->d_slot_ptr, K->d_rowof, K->d_cols, K->d_vals, K->d_scale);
+                           K->nslices, K->d_slot_ptr, K->d_rowof, K->d_cols, K->vals64(), K->d_scale);
     HIPCHK(ctx, hipGetLastError());
     mark_scaled(ctx, K);
     return STAN_OK;
@@ -387,14 +428,11 @@ struct cg_run {
     event_bag events;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool dist = false, p2p = false, sr = false, foldr = false, split = false;
-    int vs = STAN_PREC_FP64;          // the stream the loop's products read on THIS rank (FIXED-48 falls back to fp64 on a rank that owns no
-                                      // rows or whose shard is not representable: never a base for decisions the ranks must share)
+    product_plan plan;                // which kernel reads which stream in this solve
     bool lazy_scale = false;          // the values are still K: the loop's first product scales them (k_spmv_first)
     bool reduced = false;             // the caller asked for a reduced-precision stream: fp64 check + refinement (every rank alike)
-    // STAN_OPT_VALUE_STREAM_60: the plain products of this fp64 solve read the lossless 60-bit stream (the same bits)
-    bool use60 = false;
-    uint32_t *pend60 = nullptr;       // its block, allocated in setup() (the placement search needs the vectors idle); encoded -- and handed to K --
-                                      // in front of the first plain product that finds the values scaled (make_stream60)
+    uint32_t *pend60 = nullptr;       // the block of plan.stream60, allocated in setup() (the placement search needs the vectors idle); encoded -- and
+                                      // handed to K -- in front of the first product that finds the values scaled (product())
     int64_t n60 = 0;                  // products enqueued on it
     ~cg_run() { if (pend60) stan_dfree(ctx, pend60); }
     int refine = 0;                   // STAN_OPT_CG_REFINE, reduced-precision modes only
@@ -473,15 +511,19 @@ struct cg_run {
     // STAN_PREC_FP64 for the check / refresh products of a reduced-precision solve, `extra`: timed apart).
     int product(double *x, double *x2, double *y, int dot, double *out, int64_t k, p2p_out po, int kind, bool extra = false) {
         span_list &span = extra ? spmv64_sp : x2 ? spmv2_sp : spmv_sp;
-        if (pend60 && K->scaled) STANCHK(make_stream60());
-        const bool s60 = use60 && K->d_vals60 && !x2 && dot == 1 && !extra && !lazy_scale && kind == STAN_PREC_FP64;
+        if (pend60 && K->scaled) {   // the scaled values -> the 60-bit stream, K's from now on; waits for the encoder's count (the host is a few kernels ahead)
+            const int rc = stan_matrix_encode_s60(ctx, K, std::exchange(pend60, nullptr));
+            if (!K->vs[STAN_VALUE_STREAM_60].padded) plan.stream60_unavailable();
+            STANCHK(rc);
+        }
+        const bool s60 = plan.stream60 && !pend60 && !x2 && dot == 1 && !extra && !lazy_scale && kind == STAN_PREC_FP64;
         if (s60) { kind = STAN_VALUE_STREAM_60; n60++; }
         span.begin(st_, k);
         auto go = [&](int which, hipStream_t s, bool last) -> unsigned {
             n_launch++;
             // lazy_scale: the first product of this matrix (one rank, fp64 stream, all slices) scales it on the way
-            const product_args a{x, y, x2, x2 ? w : nullptr, dot, partial, stt, k, kind, nullptr, lazy_scale};
-            const unsigned blocks = launch_product(ctx, K, a, which, s, (dot && last) ? fold_to(0, out, po) : NO_FOLD);
+            const product_args a{x, y, x2, x2 ? w : nullptr, dot, partial, stt, k, kind, nullptr, false, lazy_scale};
+            const unsigned blocks = launch_product(ctx, K, plan, a, which, s, (dot && last) ? fold_to(0, out, po) : NO_FOLD);
             if (lazy_scale) { lazy_scale = false; mark_scaled(ctx, K); }
             return blocks;
         };
@@ -514,7 +556,6 @@ struct cg_run {
     }
 
     int setup();
-    int make_stream60();
     int begin_pass(bool from_F, double eps_pass, bool *done);
     int iterate(double eps_pass, int32_t max_its_pass);
     int pass(bool from_F, double eps_pass, int32_t max_its_pass);
@@ -549,52 +590,34 @@ int cg_run::setup() {
         double *const pub[5] = {ctx->ws.xb[0], ctx->ws.xb[1], ctx->ws.p, ctx->ws.r, K->d_scale};
         STANCHK(stan_p2p_publish_vectors(ctx, K, pub));
     }
-    // The first product of the loop may scale the matrix on its way (k_spmv_first) instead of a pass of its own: the fp64
-    // stream of one rank, the large-system kernel in its default variant, no folded copy (its values are made from the
-    // scaled ones), a first product that is a plain one (a residual refresh at iteration 1 is a two-product pass).
-    lazy_scale = false;
-    if (!K->scaled && ctx->cg_lazy_scaling && !dist && precision_mode == STAN_PREC_FP64 &&
-        !stan_small_system(ctx, K) && ctx->spmv_variant < 0 && ctx->cg_rupdate != 1 && K->nslices > 0) {
-        const int rc_plan = stan_matrix_make_folded(ctx, K, STAN_PREC_FP64, true);   // (decides K->fold_state, touches no value)
-        if (rc_plan == STAN_E_ALLOC) { stan_matrix_abandon_folding(ctx, K); ctx->err.clear(); }
-        else STANCHK(rc_plan);
-        lazy_scale = ctx->row_folding == 0 || K->fold_state != 1;
+    sr = ctx->cg_single_reduce;
+    foldr = ctx->cg_fold_reduce;
+    plan = plan_products(ctx, K, precision_mode, dist, sr);
+    auto folded_copy = [&](int kind, bool plan_only) {   // an optimisation must not fail the solve: without memory the padded streams serve
+        const int rc = stan_matrix_make_folded(ctx, K, kind, plan_only);
+        if (rc == STAN_E_ALLOC) { stan_matrix_abandon_folding(ctx, K); ctx->err.clear(); }
+        return rc == STAN_E_ALLOC ? (int)STAN_OK : rc;
+    };
+    if (plan.may_lazy_scale) {
+        STANCHK(folded_copy(STAN_PREC_FP64, true));   // (decides K->fold_state, touches no value)
+        plan.fold_planned(K);
     }
+    lazy_scale = plan.may_lazy_scale;
     if (lazy_scale) STANCHK(ensure_scale_vector(ctx, K));
     else STANCHK(ensure_scaled(ctx, K));
     if (ctx->cols16) STANCHK(stan_matrix_make_cols16(ctx, K));
     if (precision_mode == STAN_PREC_MIXED) STANCHK(stan_matrix_make_fp32(ctx, K));
     if (precision_mode == STAN_PREC_FIXED48) STANCHK(stan_matrix_make_fx48(ctx, K));
-    // the stream the products really read (FIXED-48 falls back to fp64 when K is not SPD-scalable)
-    vs = precision_mode == STAN_PREC_FIXED48 ? (K->d_vals48 ? STAN_PREC_FIXED48 : STAN_PREC_FP64) : precision_mode;
     reduced = precision_mode != STAN_PREC_FP64;
     refine = reduced ? ctx->cg_refine : 0;
-    if (!stan_small_system(ctx, K)) {
-        const int rc_fold = stan_matrix_make_folded(ctx, K, vs);
-        if (rc_fold == STAN_E_ALLOC) {   // an optimisation must not fail the solve: the padded streams serve
-            stan_matrix_abandon_folding(ctx, K);
-            ctx->err.clear();
-        } else
-            STANCHK(rc_fold);
-    }
-    sr = ctx->cg_single_reduce;
-    foldr = ctx->cg_fold_reduce;
-    // The lossless 60-bit stream (s60.h) for the plain products of the classic fp64 loop on one rank, where k_spmv runs them
-    // on the padded streams: not the small-system kernel, the pair kernel, the folded copy or the single-reduction loop's
-    // DOT = 2 products (they keep the fp64 values, as do k_spmv_first and k_spmv2: the bits are the same either way).
-    // -1 (auto) also wants more than STREAM60_AUTO_ROWS block rows.  Either way the block must fit the pool budget and leave
-    // a floor of free memory (stan_matrix_alloc_s60 decides before it allocates); no room: fp64, and the profile's
-    // value_stream says so.
-    use60 = false;
-    if (ctx->value_stream_60 != 0 && precision_mode == STAN_PREC_FP64 && !dist && !sr && !stan_small_system(ctx, K) &&
-        !stan_pair_kernel(ctx) && (ctx->spmv_variant < 0 || ctx->spmv_variant == 9 || ctx->spmv_variant == 12) &&
-        (ctx->value_stream_60 > 0 || K->nb_glob > STREAM60_AUTO_ROWS) && K->nslices > 0 && !K->s60_refused &&
-        !(ctx->row_folding != 0 && K->fold_state == 1)) {
-        use60 = true;
-        if (!K->d_vals60) {   // (decided per solve: a matrix without room now may have it at its next solve)
-            STANCHK(stan_matrix_alloc_s60(ctx, K, &pend60));
-            if (!pend60) use60 = false;
-        }
+    plan.value_stream_built(K);
+    if (plan.form != product_plan::SMALL) STANCHK(folded_copy(plan.vs, false));
+    plan.copies_built(K);
+    // The block of the 60-bit stream must fit the pool budget and leave a floor of free memory (stan_matrix_alloc_s60
+    // decides before it allocates); no room: fp64, and the profile's value_stream says so.
+    if (plan.stream60 && !K->vs[STAN_VALUE_STREAM_60].padded) {   // (decided per solve: a matrix without room now may have it at its next solve)
+        STANCHK(stan_matrix_alloc_s60(ctx, K, &pend60));
+        if (!pend60) plan.stream60_unavailable();
     }
 
     n3 = 3 * K->nloc;
@@ -604,8 +627,7 @@ int cg_run::setup() {
     xb[0] = ctx->ws.xb[0]; xb[1] = ctx->ws.xb[1]; p = ctx->ws.p; r = ctx->ws.r;
     v = ctx->ws.v; w = ctx->ws.w; bh = ctx->ws.bh;
     if (sr) sv = ctx->ws.sv;
-    const unsigned spmv_blocks = stan_small_system(ctx, K) ? (unsigned)K->nslices : nblk(K->nslices, stan_pair_kernel(ctx) ? 2 : 4);
-    const size_t npart = 2 * (size_t)(spmv_blocks > VEC_BLOCKS ? spmv_blocks : VEC_BLOCKS) + 16;
+    const size_t npart = 2 * (size_t)(plan.blocks > VEC_BLOCKS ? plan.blocks : VEC_BLOCKS) + 16;
     STANCHK(bufs.alloc(&partial, npart));
     STANCHK(bufs.alloc(&sc, (size_t)S_NSCAL));
     STANCHK(bufs.alloc(&stt, (size_t)T_NSTAT));
@@ -635,23 +657,6 @@ int cg_run::setup() {
     h_st = ctx->h_status + SS_H_CG_STATUS;  // pinned
     h_sc = (double *)(ctx->h_status + SS_H_CG_SCALARS);
     poll.setup(events, h_st, 8);
-    return STAN_OK;
-}
-
-// The scaled fp64 values -> the 60-bit stream, into the block setup() took; waits for the count of refused entries (the
-// host is a few kernels ahead of the device here, no more).  A refused matrix keeps streaming fp64 for good.
-int cg_run::make_stream60() {
-    uint32_t *blk = pend60;
-    pend60 = nullptr;
-    int64_t refused = 0;
-    const int rc = stan_s60_encode(ctx, K->nslots, K->d_vals, blk, &refused);
-    if (rc != STAN_OK || refused != 0) {
-        stan_dfree(ctx, blk);
-        if (rc == STAN_OK) K->s60_refused = true;
-        use60 = false;
-        return rc;
-    }
-    K->d_vals60 = blk;
     return STAN_OK;
 }
 
@@ -689,7 +694,7 @@ int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
     // ItsBeforeRUpdate) multiplies with the fp64 values -- the recurrence is re-anchored to the true residual
     // ("reliable updates"), so the literal second product replaces the fused two-product pass
     const bool refresh64 = refine >= 2;
-    const int kind_refresh = refresh64 ? STAN_PREC_FP64 : vs;
+    const int kind_refresh = refresh64 ? STAN_PREC_FP64 : plan.vs;
     // ... and then every REFRESH64 iterations instead of every STAN_OPT_CG_RUPDATE: a refresh on the reduced stream in
     // between would undo the anchoring, and the iteration count does not depend on the period (148^3, fp32 copy: 2346
     // iterations with 10, 20 and 50; profiles/r05/mixed_refine_n148.txt) while every fp64 product costs two of the others
@@ -698,7 +703,7 @@ int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
     if (sr) {   // w_0 = A r_0 with gamma_0, delta_0 (merit_0 = 0 sits in the zeroed scalars)
         if (p2p)         // ... or, peer to peer, is sent as this rank's zero into the slot of the first reduction
             launch_reduce(st_, 1, partial, 0, sc + S_SR_MERIT, p2p_to(2, false), nullptr, 0);
-        rc = product(r, nullptr, w, 2, sc + S_SR_GAMMA, 0, p2p_to(0, true), vs);
+        rc = product(r, nullptr, w, 2, sc + S_SR_GAMMA, 0, p2p_to(0, true), plan.vs);
         if (rc == STAN_OK) rc = exchange_sums(sc + S_SR_GAMMA, 3, &rs_sr);
     }
     // a sharded loop polls more often: what runs ahead of the stop are exchanges nobody can cut short
@@ -728,14 +733,14 @@ int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
                     n_launch++;
                     reduce_if_unfolded((int)vg, 2, sc + S_SR_DELTA, p2p_to(1, false), k);   // [r.r (rewritten below), merit]
                 }
-                rc = product(r, nullptr, w, 2, sc + S_SR_GAMMA, k, p2p_to(0, true), vs);
+                rc = product(r, nullptr, w, 2, sc + S_SR_GAMMA, k, p2p_to(0, true), plan.vs);
                 if (rc) break;
                 rc = exchange_sums(sc + S_SR_GAMMA, 3, &rs_sr);
                 if (rc) break;
                 continue;
             }
             const bool fused = refresh && ctx->cg_fused_refresh && !refresh64;
-            rc = product(p, fused ? xb[(k - 1) & 1] : nullptr, v, 1, sc + S_VMV, k, p2p_to(0, true), vs);
+            rc = product(p, fused ? xb[(k - 1) & 1] : nullptr, v, 1, sc + S_VMV, k, p2p_to(0, true), plan.vs);
             if (rc) break;
             rc = exchange_sums(sc + S_VMV, 1, &rs_vmv);
             if (rc) break;
@@ -882,22 +887,18 @@ int cg_run::finish(const double *x_result, int type, int64_t its, double rel_rec
     pf.rel_residual_recurrence = rel_rec;
     pf.rel_residual_fp64 = rel64;
     pf.refine_passes = passes;
-    const bool ran60 = n60 > 0;   // the plain products (what spmv_ms_total times) read the 60-bit stream: 68 B of values per block
-    const int64_t blk_bytes = ran60 ? 72 : vs == STAN_PREC_FIXED48 ? 60 : vs == STAN_PREC_MIXED ? 40 : 76;
-    // bytes of the format actually streamed: a block of a packed slice carries a 2-B column offset
-    // instead of a 4-B index (+ 4 B per slot for its base, shared by 64 rows)
+    const int stream = n60 > 0 ? (int)STAN_VALUE_STREAM_60 : plan.vs;   // the stream the plain products (what spmv_ms_total times) read
+    // bytes of the format actually streamed: a block costs its values and a 4-B column index; a block of a packed slice
+    // carries a 2-B column offset instead (+ 4 B per slot for its base, shared by 64 rows)
     // (the folded copy has a packed column stream of its own, one base per slot, and 4 B of plan per row)
-    const bool folded = ctx->row_folding != 0 && (vs == STAN_PREC_FIXED48 ? K->d_fold_vals48 != nullptr : vs == STAN_PREC_MIXED ? K->d_fold_vals32 != nullptr
-                                                                                                                                : K->d_fold_vals != nullptr);
-    const bool packed = ctx->cols16 && K->d_cols16, read_packed = folded ? ctx->cols16 && K->d_fold_cols16 : packed;
-    const int64_t slots = folded ? K->nfslots : K->nslots, slots_packed = folded ? K->fold_slots_packed : K->slots_packed;
-    const int64_t bases = folded ? K->fold_slots_packed : K->slots_packed + K->slots_packed2;
-    const double packed_frac = read_packed && slots > 0 ? (double)slots_packed / (double)slots : 0.0;
-    pf.spmv_bytes = K->nblocks * blk_bytes + 3 * K->nloc * 16 + K->nloc * (folded ? 8 : 4)
-                    - (int64_t)(packed_frac * (double)K->nblocks * 2.0) + (read_packed ? bases * 4 : 0);
-    pf.repacked_streams = folded ? 1 : 0;
-    pf.col_slots_packed = packed ? K->slots_packed : 0;   // (the padded stream's count even when the products read the folded copy: looks unintended, kept)
-    pf.value_stream = ran60 ? STAN_VALUE_STREAM_60 : vs;
+    const stan_colpack &c = *plan.cols;
+    const bool read_packed = ctx->cols16 && c.cols16;
+    const double packed_frac = read_packed && plan.slots > 0 ? (double)c.slots_packed / (double)plan.slots : 0.0;
+    pf.spmv_bytes = K->nblocks * (4 * K->vs[stream].dwords + 4) + 3 * K->nloc * 16 + K->nloc * (plan.folded ? 8 : 4)
+                    - (int64_t)(packed_frac * (double)K->nblocks * 2.0) + (read_packed ? (c.slots_packed + c.slots_packed2) * 4 : 0);
+    pf.repacked_streams = plan.folded ? 1 : 0;
+    pf.col_slots_packed = ctx->cols16 && K->pk.cols16 ? K->pk.slots_packed : 0;   // (the padded stream's count even when the products read the folded copy: looks unintended, kept)
+    pf.value_stream = stream;
     // vector passes of one classic iteration: k_step reads r, v (+ p, x unless deferred; + b^ for the
     // merit sum) and writes r (+ x); k_update reads r, p (+ x when deferred) and writes p (+ x)
     pf.cg_iteration_vector_bytes = 3 * K->nloc * 8 * ((ctx->cg_defer_x && !ctx->cg_merit_stop ? 8 : 9) + (ctx->cg_merit_stop ? 1 : 0));
@@ -1042,7 +1043,7 @@ struct cg_multi_run {
         const int64_t nr = K->n_red;
         const size_t g = (size_t)(ng > 0 ? ng : 1);
         const int merit = ctx->cg_merit_stop ? 1 : 0, rupdate = ctx->cg_rupdate;
-        const colstream cs = colstream_of(ctx, K);
+        const colstream cs = colstream_of(ctx, K->pk, K->nslots);
         const fold_args fvec{tick + FOLD_WORDS, vg, (int)vg, nullptr, NO_P2P};   // counter set 1 serves the vector kernels,
         const fold_args fprod{tick, pg, (int)pg, nullptr, NO_P2P};               // set 0 the products
         int64_t *h_st = host.p + 2 * MULTI_MAX * T_NSTAT;
@@ -1068,7 +1069,7 @@ struct cg_multi_run {
             for (int c = 0; c < CHUNK && k < chunk_poll::hard_cap; c++, k++) {
                 const bool refresh = rupdate > 0 && (k % rupdate) == 0;
                 hipLaunchKernelGGL((k_spmm<M, 1>), dim3(pg), dim3(256), 0, st_, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols,
-                                   K->d_vals, p, v, partial, pstride, sc, stt, k, fprod, cs);
+                                   K->vals64(), p, v, partial, pstride, sc, stt, k, fprod, cs);
                 mstep_args a;
                 a.n3 = n3; a.k = k; a.sc = sc; a.st = stt;
                 a.xcur = xb[(k - 1) & 1]; a.xnext = xb[k & 1];
@@ -1077,7 +1078,7 @@ struct cg_multi_run {
                 hipLaunchKernelGGL(k_step_m<M>, dim3(vg), dim3(VEC_T), 0, st_, a);
                 if (refresh) {   // r = b^ - A^ x' from alglib's literal second product
                     hipLaunchKernelGGL((k_spmm<M, 0>), dim3(pg), dim3(256), 0, st_, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof,
-                                       K->d_cols, K->d_vals, xb[k & 1], v, partial, pstride, sc, stt, k, NO_FOLD, cs);
+                                       K->d_cols, K->vals64(), xb[k & 1], v, partial, pstride, sc, stt, k, NO_FOLD, cs);
                     hipLaunchKernelGGL(k_refresh_m<M>, dim3(vg), dim3(VEC_T), 0, st_, n3, k, sc, (const int64_t *)stt, bh, v, xb[k & 1],
                                        r, partial, pstride, fvec);
                 }

@@ -1,7 +1,7 @@
 // cg_entries.inc -- the products OUTSIDE a solve: test helpers (stan_spmv_reduced, stan_matrix_diagonal, stan_spmv_local) and
 // the timing entries (stan_spmv_bench_device, stan_stream_bench_device, stan_spmv_probe of the placement search)
 // Part of cg.hip (included at its end, at file scope: they need launch_product and the kernels; not a translation unit of
-// its own).
+// its own).  Each entry takes its product_plan from plan_products once: the kernel form a solve under the same options launches.
 
 namespace {
 
@@ -15,7 +15,8 @@ int alloc_never_stopped(stan_ctx *ctx, dev_scope &b, int64_t **stt, hipStream_t 
 
 // y = A x with K's fp64 values, no sums: the products outside a solve
 unsigned launch_plain_product(stan_ctx *ctx, stan_matrix *K, const double *x, double *y, const int64_t *st, int which = 0) {
-    return launch_product(ctx, K, product_args{x, y, nullptr, nullptr, 0, nullptr, st, 1, STAN_PREC_FP64, nullptr, false}, which);
+    const product_args a{x, y, nullptr, nullptr, 0, nullptr, st, 1, STAN_PREC_FP64, nullptr, false, false};
+    return launch_product(ctx, K, plan_products(ctx, K, a.kind, stan_sharded(ctx), false), a, which);
 }
 
 }  // namespace
@@ -53,7 +54,7 @@ int stan_matrix_diagonal(stan_ctx *ctx, stan_matrix *K, double *d_diag) {
     STANCHK(bufs.alloc(&full, (size_t)(n3 > 0 ? n3 : 1)));
     if (K->nloc > 0)
         hipLaunchKernelGGL(k_diag_get, dim3(nblk(K->nloc, 256)), dim3(256), 0, st_, K->nloc, K->d_rowlen, K->d_posof,
-                           K->d_slot_ptr, K->d_cols, K->d_vals, K->scaled ? K->d_scale : (const double *)nullptr, full);
+                           K->d_slot_ptr, K->d_cols, K->vals64(), K->scaled ? K->d_scale : (const double *)nullptr, full);
     hipLaunchKernelGGL(k_compress_div, dim3(vec_grid(n3)), dim3(VEC_T), 0, st_, n3, K->d_red, (const double *)nullptr, full, d_diag);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(st_));
@@ -80,8 +81,8 @@ int stan_spmv_local(stan_ctx *ctx, stan_matrix *K, const double *d_x, double *d_
 // K's own of that precision), on the CG's own gather vector and product buffer -- the pair (value block, vector blocks)
 // that is timed is the pair the solve will run on -- or, self_block given, on vectors carved out of the front of that
 // block (a.x stays nullptr when they do not fit).  The gather vector is filled with ones.
-static int timed_product_setup(stan_ctx *ctx, stan_matrix *K, int32_t precision, const void *vals, void *self_block,
-                               size_t self_bytes, dev_scope &bufs, product_args &a) {
+static int timed_product_setup(stan_ctx *ctx, stan_matrix *K, const product_plan &P, int32_t precision, const void *vals, bool vals_folded,
+                               void *self_block, size_t self_bytes, dev_scope &bufs, product_args &a) {
     hipStream_t st_ = ctx->stream;
     const int64_t ng = gather_len(K), ngpad = (ng + 511) & ~(int64_t)511;
     STANCHK(stan_cg_workspace(ctx, K));
@@ -92,10 +93,10 @@ static int timed_product_setup(stan_ctx *ctx, stan_matrix *K, int32_t precision,
         x = (double *)self_block;
         y = x + ngpad;
     }
-    STANCHK(bufs.alloc(&partial, 2 * (size_t)K->nslices + 2));   // k_spmv_small leaves one partial per slice
+    STANCHK(bufs.alloc(&partial, 2 * (size_t)P.blocks + 2));
     STANCHK(alloc_never_stopped(ctx, bufs, &stt, st_));
     hipLaunchKernelGGL(k_fill, dim3(vec_grid(ng)), dim3(VEC_T), 0, st_, x, ng, 1.0);
-    a = product_args{x, y, nullptr, nullptr, 1, partial, stt, 1, precision, vals, false};
+    a = product_args{x, y, nullptr, nullptr, 1, partial, stt, 1, precision, vals, vals_folded, false};
     return STAN_OK;
 }
 
@@ -128,26 +129,25 @@ int stan_spmv_bench_device(stan_ctx *ctx, stan_matrix *K, int32_t precision_mode
     if (precision_mode == STAN_PREC_FIXED48) {
         STANCHK(ensure_scaled(ctx, K));
         STANCHK(stan_matrix_make_fx48(ctx, K));
-        if (!K->d_vals48) { ctx->err = "spmv_bench: matrix not representable in FIXED48"; return STAN_E_UNSUPPORTED; }
+        if (!K->vs[STAN_PREC_FIXED48].padded) { ctx->err = "spmv_bench: matrix not representable in FIXED48"; return STAN_E_UNSUPPORTED; }
     }
     if (precision_mode == STAN_VALUE_STREAM_60) {   // k_spmv on the lossless 60-bit stream of the scaled values
+        const stan_value_stream &s60 = K->vs[STAN_VALUE_STREAM_60];
         STANCHK(ensure_scaled(ctx, K));
-        if (!K->d_vals60 && !K->s60_refused && K->nslots > 0) {
+        if (!s60.padded && !s60.refused && K->nslots > 0) {
             uint32_t *blk = nullptr;
-            int64_t refused = 0;
             STANCHK(stan_matrix_alloc_s60(ctx, K, &blk));
             if (!blk) { ctx->err = "spmv_bench: no room for the 60-bit stream within the pool budget and the free-memory floor"; return STAN_E_ALLOC; }
-            const int rc =stan_s60_encode(ctx, K->nslots, K->d_vals, blk, &refused);
-            if (rc != STAN_OK || refused != 0) { stan_dfree(ctx, blk); K->s60_refused = rc == STAN_OK; STANCHK(rc); }
-            else K->d_vals60 = blk;
+            STANCHK(stan_matrix_encode_s60(ctx, K, blk));
         }
-        if (!K->d_vals60) { ctx->err = "spmv_bench: matrix not representable in the 60-bit stream"; return STAN_E_UNSUPPORTED; }
+        if (!s60.padded) { ctx->err = "spmv_bench: matrix not representable in the 60-bit stream"; return STAN_E_UNSUPPORTED; }
     }
     dev_scope bufs(ctx);
     product_args pa{};
-    STANCHK(timed_product_setup(ctx, K, precision_mode, nullptr, nullptr, 0, bufs, pa));
+    const product_plan P = plan_products(ctx, K, precision_mode, stan_sharded(ctx), false);
+    STANCHK(timed_product_setup(ctx, K, P, precision_mode, nullptr, false, nullptr, 0, bufs, pa));
     float ms = 0;
-    STANCHK(timed_launches(ctx, 3, 1, reps, [&]() { launch_product(ctx, K, pa); }, &ms));
+    STANCHK(timed_launches(ctx, 3, 1, reps, [&]() { launch_product(ctx, K, P, pa); }, &ms));
     *avg_ms = reps > 0 ? ms : 0;
     return STAN_OK;
 }
@@ -181,7 +181,7 @@ int stan_stream60_roundtrip_device(stan_ctx *ctx, int64_t n, const double *in, d
     STANCHK(bufs.alloc(&d_enc, (size_t)nslots * vstream<s60_t>::STRIDE));
     HIPCHK(ctx, hipMemsetAsync(d_in, 0, (size_t)npad * 8, st_));
     HIPCHK(ctx, hipMemcpyAsync(d_in, in, (size_t)n * 8, hipMemcpyHostToDevice, st_));
-    STANCHK(stan_s60_encode(ctx, nslots, d_in, d_enc, refused));
+    STANCHK(stan_stream_encode(ctx, STAN_VALUE_STREAM_60, nslots, d_in, d_enc, refused));
     hipLaunchKernelGGL(k_from_s60, dim3(nblk(nslots * 64, 256)), dim3(256), 0, st_, nslots, (const s60_t *)d_enc, d_out);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, st_));
@@ -195,12 +195,12 @@ int stan_stream_bench_device(stan_ctx *ctx, stan_matrix *K, int32_t reps, double
     hipStream_t st_ = ctx->stream;
     *avg_ms = 0;
     *bytes = (int64_t)K->nslots * 64 * 72;
-    if (K->nslices <= 0 || !K->d_vals) return STAN_OK;
+    if (K->nslices <= 0 || !K->vals64()) return STAN_OK;
     const unsigned grid = nblk(K->nslices, 4);
     dev_scope bufs(ctx);
     double *sink;
     STANCHK(bufs.alloc(&sink, (size_t)grid));
-    auto one = [&]() { hipLaunchKernelGGL(k_value_stream, dim3(grid), dim3(256), 0, st_, K->nslices, K->d_slot_ptr, K->d_vals, sink); };
+    auto one = [&]() { hipLaunchKernelGGL(k_value_stream, dim3(grid), dim3(256), 0, st_, K->nslices, K->d_slot_ptr, K->vals64(), sink); };
     float ms = 0;
     STANCHK(timed_launches(ctx, 3, 1, reps, one, &ms));
     *avg_ms = ms;
@@ -209,12 +209,13 @@ int stan_stream_bench_device(stan_ctx *ctx, stan_matrix *K, int32_t reps, double
 
 // Time of the SpMV of K streaming its values from `vals` -- a block of the stream kind `precision` names (STAN_PREC_*, or
 // STAN_VALUE_STREAM_60: the product the loop will launch on it); any contents, only the addresses
-// matter --, median of 3 launches after a warm-up.  Used by the allocation-by-trial of placement.hip.
+// matter --, median of 3 launches after a warm-up.  Used by the allocation-by-trial of placement.hip.  folded: the block is
+// a candidate for a FOLDED stream of that kind (fold.hip): the folded kernel is timed on it.
 // self_pair: the gather vector and the product are carved out of the FRONT of the candidate block
 // itself instead of the context's vectors -- by construction the same-group (slow) pairing, i.e.
 // the reference the search compares the real pairing with (profiles/r02/placement_cross_self_n148.txt).
 int stan_spmv_probe(stan_ctx *ctx, stan_matrix *K, const void *vals, size_t bytes, int32_t precision,
-                    float *ms_out, bool self_pair) {
+                    float *ms_out, bool self_pair, bool folded) {
     *ms_out = 0;
     if (K->nslices <= 0) return STAN_OK;
     // self_pair: the block holds no values yet (only addresses matter to the timing).  The gather vector and the product
@@ -222,8 +223,9 @@ int stan_spmv_probe(stan_ctx *ctx, stan_matrix *K, const void *vals, size_t byte
     // *ms_out stays 0, the search then keeps the fastest real pairing (placement.hip)
     dev_scope bufs(ctx);
     product_args pa{};
-    STANCHK(timed_product_setup(ctx, K, precision, vals, self_pair ? const_cast<void *>(vals) : nullptr, bytes, bufs, pa));
+    const product_plan P = plan_products(ctx, K, precision, stan_sharded(ctx), false);
+    STANCHK(timed_product_setup(ctx, K, P, precision, vals, folded, self_pair ? const_cast<void *>(vals) : nullptr, bytes, bufs, pa));
     if (!pa.x) return STAN_OK;
     // one launch to warm up, then two groups of three launches, the faster group counts
-    return timed_launches(ctx, 1, 2, 3, [&]() { launch_product(ctx, K, pa); }, ms_out);
+    return timed_launches(ctx, 1, 2, 3, [&]() { launch_product(ctx, K, P, pa); }, ms_out);
 }

@@ -17,6 +17,8 @@
 // A folded row is summed as own part + piece + piece ...: another order than the padded layout's, fixed by the
 // layout (deterministic, the same for a shard and the whole matrix: shards are cut on slice boundaries).  Rows
 // that are not folded keep their bits.
+#include <type_traits>
+
 #include "internal.h"
 
 namespace {
@@ -101,16 +103,15 @@ k_fold_fill(int32_t nslices, const int32_t *slot_ptr, const int32_t *fold_ptr, c
 }  // namespace
 
 void stan_matrix_drop_folded_values(stan_ctx *ctx, stan_matrix *K) {
-    if (K->d_fold_vals) { stan_dfree(ctx, K->d_fold_vals); K->d_fold_vals = nullptr; }
-    if (K->d_fold_vals32) { stan_dfree(ctx, K->d_fold_vals32); K->d_fold_vals32 = nullptr; }
-    if (K->d_fold_vals48) { stan_dfree(ctx, K->d_fold_vals48); K->d_fold_vals48 = nullptr; }
+    for (stan_value_stream &s : K->vs) { stan_dfree(ctx, s.folded); s.folded = nullptr; }
 }
 
 // no memory for a second copy of the streams: give everything back, the padded streams serve
 void stan_matrix_abandon_folding(stan_ctx *ctx, stan_matrix *K) {
     stan_matrix_drop_folded_values(ctx, K);
+    stan_colpack &c = K->fold_pk;
     for (void **q : {(void **)&K->d_fold_ptr, (void **)&K->d_fold_meta, (void **)&K->d_fold_plan, (void **)&K->d_fold_cols,
-                     (void **)&K->d_fold_cols16, (void **)&K->d_fold_colbase, (void **)&K->d_fold_pair_ptr, (void **)&K->d_fold_packed}) {
+                     (void **)&c.cols16, (void **)&c.colbase, (void **)&c.pair_ptr, (void **)&c.packed}) {
         stan_dfree(ctx, *q);
         *q = nullptr;
     }
@@ -164,36 +165,21 @@ int stan_matrix_make_folded(stan_ctx *ctx, stan_matrix *K, int32_t stream_kind, 
                            K->d_fold_plan, K->d_cols, (const double *)nullptr, K->d_fold_cols, (double *)nullptr);
         HIPCHK(ctx, hipGetLastError());
         K->fold_cols_filled = true;
-        if (ctx->cols16)
-            STANCHK(stan_pack_columns(ctx, K->nslices, K->nfslots, K->d_fold_ptr, K->d_fold_cols, &K->d_fold_cols16, &K->d_fold_colbase,
-                                      &K->d_fold_pair_ptr, &K->d_fold_packed, &K->fold_slots_packed));
+        if (ctx->cols16) STANCHK(stan_pack_columns(ctx, K->nslices, K->nfslots, K->d_fold_ptr, K->d_fold_cols, &K->fold_pk));
     }
-    // the value block is allocated by trial like the padded one (placement.hip): the folded product is timed on
-    // every candidate (stan_ctx::fold_probe tells the dispatch that the candidate is a FOLDED stream)
-    auto streamed = [&](void **p, size_t bytes, int32_t prec) {
-        return stan_dmalloc_streamed(ctx, p, bytes, [&, bytes, prec](const void *q, float *ms, bool self) {
-            ctx->fold_probe = q;
-            const int rc = stan_spmv_probe(ctx, K, q, bytes, prec, ms, self);
-            ctx->fold_probe = nullptr;
-            return rc;
-        });
-    };
-    if (stream_kind == STAN_PREC_MIXED) {
-        if (!K->d_fold_vals32 && K->d_vals32) {
-            STANCHK(streamed((void **)&K->d_fold_vals32, n * 9 * 4, STAN_PREC_MIXED));
-            hipLaunchKernelGGL((k_fold_fill<float, 9>), dim3(grid), dim3(256), 0, st, K->nslices, K->d_slot_ptr, K->d_fold_ptr,
-                               K->d_fold_plan, K->d_cols, K->d_vals32, (int32_t *)nullptr, K->d_fold_vals32);
-        }
-    } else if (stream_kind == STAN_PREC_FIXED48) {
-        if (!K->d_fold_vals48 && K->d_vals48) {
-            STANCHK(streamed((void **)&K->d_fold_vals48, n * 14 * 4, STAN_PREC_FIXED48));
-            hipLaunchKernelGGL((k_fold_fill<uint32_t, 14>), dim3(grid), dim3(256), 0, st, K->nslices, K->d_slot_ptr, K->d_fold_ptr,
-                               K->d_fold_plan, K->d_cols, K->d_vals48, (int32_t *)nullptr, K->d_fold_vals48);
-        }
-    } else if (!K->d_fold_vals) {
-        STANCHK(streamed((void **)&K->d_fold_vals, n * 9 * 8, STAN_PREC_FP64));
-        hipLaunchKernelGGL((k_fold_fill<double, 9>), dim3(grid), dim3(256), 0, st, K->nslices, K->d_slot_ptr, K->d_fold_ptr,
-                           K->d_fold_plan, K->d_cols, K->d_vals, (int32_t *)nullptr, K->d_fold_vals);
+    stan_value_stream &s = K->vs[stream_kind];
+    if (!s.folded && s.padded) {
+        // the value block is allocated by trial like the padded one (placement.hip): the folded product is timed on
+        // every candidate
+        STANCHK(stan_matrix_alloc_stream(ctx, K, stream_kind, (int64_t)(n / 64), &s.folded, true));
+        auto fill = [&](auto *in, auto rows) {   // the kind as k_fold_fill's types
+            using VT = std::remove_const_t<std::remove_pointer_t<decltype(in)>>;
+            hipLaunchKernelGGL((k_fold_fill<VT, decltype(rows)::value>), dim3(grid), dim3(256), 0, st, K->nslices, K->d_slot_ptr,
+                               K->d_fold_ptr, K->d_fold_plan, K->d_cols, in, (int32_t *)nullptr, (VT *)s.folded);
+        };
+        if (stream_kind == STAN_PREC_MIXED) fill((const float *)s.padded, std::integral_constant<int, 9>());
+        else if (stream_kind == STAN_PREC_FIXED48) fill((const uint32_t *)s.padded, std::integral_constant<int, 14>());
+        else fill((const double *)s.padded, std::integral_constant<int, 9>());
     }
     HIPCHK(ctx, hipGetLastError());
     return STAN_OK;

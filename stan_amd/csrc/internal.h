@@ -252,7 +252,6 @@ struct stan_ctx {
     hipStream_t side = nullptr;
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
     int assembly_mode = 0;     // 0 row-owner gather (default), 1 element-wave colour scatter
-    const void *fold_probe = nullptr;  // placement search: this candidate block is a FOLDED value stream (fold.hip)
     int row_folding = -1;      // STAN_OPT_ROW_FOLDING: -1 = products read the folded streams (fold.hip) when they save > 5 % of the slots; 1 always; 0 never
     int sell_sigma = 1;        // SELL-C-sigma: rows sorted by length inside windows of this many slices (1: inside each slice only)
     int placement_tries = 16;  // > 1: allocate the value stream by search (placement.hip); blocks >= 256 MB only
@@ -261,7 +260,7 @@ struct stan_ctx {
     int prof_placement_candidates = 0;
     int prof_placement_moved_vectors = 0;   // 1: the search ended by re-allocating the CG's vectors
     int prof_colours = 0;
-    int spmv_variant = -1; // -1 = auto (launch_product picks per value stream); >= 0: A/B lab
+    int spmv_variant = -1; // -1 = auto (plan_products picks per value stream); >= 0: A/B lab
     int value_stream_60 = -1;  // STAN_OPT_VALUE_STREAM_60: -1 = the fp64 loop of a large system on one rank streams the 60-bit values; 1 always where k_spmv runs; 0 never
     // profiling
     bool profiling = false;
@@ -276,6 +275,25 @@ struct stan_ctx {
 };
 // a rank of a sharded matrix: halo exchanges and all-reduces belong to every product and reduction
 inline bool stan_sharded(const stan_ctx *ctx) { return ctx->comm != nullptr || ctx->nranks > 1; }
+
+// A value stream of K.  Kinds: STAN_PREC_FP64 (the assembled values, scaled in place), STAN_PREC_MIXED (fp32 copy),
+// STAN_PREC_FIXED48 and STAN_VALUE_STREAM_60 (copies of the SCALED values; s60.h: 17 rows); layout [slot][dwords][64].
+constexpr int STAN_NSTREAMS = 4;
+struct stan_value_stream {
+    int dwords;               // dwords per slot and lane
+    void *padded = nullptr;   // [nslots] slots
+    void *folded = nullptr;   // [nfslots] slots, built on demand (fold.hip); the 60-bit stream has none
+    bool refused = false;     // some scaled entry is outside the format's range (FIXED-48: |a_ij| >= 2, K not SPD; 60-bit: also below 2^-126 or not finite): fp64 is streamed
+};
+// A packed column stream (struct colstream of spmv_kernels.inc, stan_pack_columns): of the padded layout, and of the folded one
+struct stan_colpack {
+    uint32_t *cols16 = nullptr;   // [pair][64]
+    int32_t *colbase = nullptr;   // [slots] smallest column of each slot (+ second bases and class masks: make_colstream)
+    int32_t *pair_ptr = nullptr;  // [nslices+1]
+    uint8_t *packed = nullptr;    // [nslices] mode of the slice (k_pack_cols): 0 = not in the packed stream
+    int64_t slots_packed = 0;     // ELL slots of packed slices (modes 1 and 2) ...
+    int64_t slots_packed2 = 0;    // ... of which in two-base slices (4 B more per slot: the second base)
+};
 
 struct stan_matrix {
     stan_ctx *ctx = nullptr;
@@ -296,32 +314,16 @@ struct stan_matrix {
     int32_t *d_posof = nullptr;     // [nslices*64] local block row -> position (slice = pos / 64, lane = pos % 64)
     int sigma = 1;                  // sorting window in slices the matrix was built with
     int32_t *d_cols = nullptr;      // [nslots][64] local block-column index
-    uint32_t *d_cols16 = nullptr;   // packed column stream of the SpMV (cg.hip colstream): [pair][64]
-    int32_t *d_colbase = nullptr;   //   [nslots] smallest column of each slot
-    int32_t *d_pair_ptr = nullptr;  //   [nslices+1]
-    uint8_t *d_slice_packed = nullptr;  // [nslices] 1 = slice is in the packed stream
-    int64_t slots_packed = 0;       // ELL slots of packed slices (modes 1 and 2 of k_pack_cols) ...
-    int64_t slots_packed2 = 0;      // ... of which in two-base slices (4 B more per slot: the second base)
-    double *d_vals = nullptr;       // [nslots][9][64]
-    float *d_vals32 = nullptr;      // same layout, fp32 copy (mixed precision)
-    uint32_t *d_vals48 = nullptr;   // FIXED-48 stream of the scaled values, [slot][14][64] dwords
-    bool fx48_refused = false;      // some |a_ij| >= 2 after scaling (K not SPD): fp64 is streamed
-    uint32_t *d_vals60 = nullptr;   // lossless 60-bit stream of the scaled values (s60.h), [slot][17][64] dwords
-    bool s60_refused = false;       // some scaled entry is outside its range (>= 2, below 2^-126, not finite): fp64 is streamed
+    stan_colpack pk;                // packed column stream of d_cols
+    stan_value_stream vs[STAN_NSTREAMS] = {{9 * 2}, {9}, {14}, {17}};   // the value streams by kind; [STAN_PREC_FP64].padded: the assembled values
+    double *vals64() const { return (double *)vs[STAN_PREC_FP64].padded; }   // [nslots][9][64]
     // Folded copy of the streams (fold.hip, STAN_OPT_ROW_FOLDING): long rows lend their tails to the idle slots of
     // the short rows of their slice; padded-slot layout with ~blocks/64 slots per slice.
     int32_t *d_fold_ptr = nullptr;      // [nslices + 1] first folded slot of every slice
     uint32_t *d_fold_meta = nullptr;    // [nslices * 64] own slots (16 bits) | first helper lane << 16 | helper lanes << 24
     int4 *d_fold_plan = nullptr;        // [nslices * 64] own slots, owner lane (-1), offset in the owner's row, slots taken
     int32_t *d_fold_cols = nullptr;     // [nfslots][64]
-    uint32_t *d_fold_cols16 = nullptr;  // packed column stream of the folded copy (cg.hip colstream) and its
-    int32_t *d_fold_colbase = nullptr;  //   per-slot bases,
-    int32_t *d_fold_pair_ptr = nullptr; //   per-slice first pairs,
-    uint8_t *d_fold_packed = nullptr;   //   per-slice flags
-    int64_t fold_slots_packed = 0;
-    double *d_fold_vals = nullptr;      // [nfslots][9][64], built on demand (per value stream)
-    float *d_fold_vals32 = nullptr;
-    uint32_t *d_fold_vals48 = nullptr;  // [nfslots][14][64]
+    stan_colpack fold_pk;               // packed column stream of d_fold_cols (one base per slot)
     int64_t nfslots = 0;
     bool fold_cols_filled = false;
     int fold_state = 0;                 // 0: not examined, 1: planned, -1: not applicable / abandoned (no memory), -2: declined by the auto threshold (> 95 % of the slots)
@@ -399,13 +401,14 @@ int stan_matrix_make_folded(stan_ctx *ctx, stan_matrix *K, int32_t stream_kind, 
 void stan_matrix_drop_folded_values(stan_ctx *ctx, stan_matrix *K);
 void stan_matrix_abandon_folding(stan_ctx *ctx, stan_matrix *K);
 int stan_matrix_make_fx48(stan_ctx *ctx, stan_matrix *K);
+int stan_matrix_alloc_stream(stan_ctx *ctx, stan_matrix *K, int32_t kind, int64_t slots, void **out, bool folded = false, bool second_copy = false);   // folded: a block of the folded layout; second_copy: see stan_dmalloc_streamed
 int stan_matrix_alloc_s60(stan_ctx *ctx, stan_matrix *K, uint32_t **out);   // a block for K's 60-bit stream, allocated by search like K's values; *out = nullptr (STAN_OK): no room within the budgets
-int stan_s60_encode(stan_ctx *ctx, int64_t nslots, const double *d_vals, uint32_t *d_out, int64_t *refused);   // synchronises the stream
+int stan_stream_encode(stan_ctx *ctx, int32_t kind, int64_t nslots, const double *d_vals, uint32_t *d_out, int64_t *refused);   // FIXED-48 or 60-bit; synchronises the stream
+int stan_matrix_encode_s60(stan_ctx *ctx, stan_matrix *K, uint32_t *blk);   // blk becomes K's 60-bit stream, or -- an entry refused -- is freed
 int stan_stream60_roundtrip_device(stan_ctx *ctx, int64_t n, const double *in, double *out, int64_t *refused);   // cg_entries.inc
 int stan_matrix_make_cols16(stan_ctx *ctx, stan_matrix *K);
-int stan_pack_columns(stan_ctx *ctx, int32_t nslices, int64_t nslots, const int32_t *d_slot_ptr, const int32_t *d_cols,
-                      uint32_t **packed_out, int32_t **base_out, int32_t **pair_ptr_out, uint8_t **ok_out, int64_t *slots_packed,
-                      int64_t nloc = 0, const int32_t *d_rowof = nullptr, const int32_t *d_rowlen = nullptr, int64_t *slots_packed2 = nullptr);
+int stan_pack_columns(stan_ctx *ctx, int32_t nslices, int64_t nslots, const int32_t *d_slot_ptr, const int32_t *d_cols, stan_colpack *out,
+                      int64_t nloc = 0, const int32_t *d_rowof = nullptr, const int32_t *d_rowlen = nullptr);
 int stan_matrix_ensure_scaled(stan_ctx *ctx, stan_matrix *K);   // S K S in place (once per matrix)
 // length of a gather vector of K (NOTE on the halo layout, cg.hip): the owned rows padded to whole slices, or the owned
 // rows and the halo columns behind them, whichever is longer
@@ -638,4 +641,4 @@ int stan_probe_block(stan_ctx *ctx, const void *p, size_t bytes, float *ms_out);
 int stan_dmalloc_streamed(stan_ctx *ctx, void **p, size_t bytes,
                           const std::function<int(const void *, float *, bool)> &probe, bool second_copy = false);
 int stan_spmv_probe(stan_ctx *ctx, stan_matrix *K, const void *vals, size_t bytes, int32_t precision,
-                    float *ms_out, bool self_pair = false);
+                    float *ms_out, bool self_pair = false, bool folded = false);   // folded: `vals` is a block for a FOLDED stream (fold.hip)

@@ -144,7 +144,7 @@ int stan_spmv_incg_lab(stan_ctx *ctx, stan_matrix *K, int reps, double *out_ms) 
             hipEvent_t a0 = ev.make(), b0 = ev.make();
             hipEventRecord(a0, st_);
             hipLaunchKernelGGL((k_spmv<double, 1, 9>), dim3(nblk(K->nslices, 4)), dim3(256), 0, st_, K->nslices, K->nloc,
-                               K->d_slot_ptr, K->d_rowof, K->d_cols, K->d_vals, xg, y, partial, stt, (int64_t)1,
+                               K->d_slot_ptr, K->d_rowof, K->d_cols, K->vals64(), xg, y, partial, stt, (int64_t)1,
                                (const int32_t *)nullptr, K->nslices, 0, NO_FOLD,
                                NO_COLSTREAM);
             hipEventRecord(b0, st_);

@@ -74,7 +74,7 @@ extern "C" int stan_hip_csr_spmv_bench(stan_ctx *ctx, stan_matrix *K, int32_t re
     hipLaunchKernelGGL(k_csr_rowlen, dim3(nblk(n3, 256)), dim3(256), 0, st, nloc, K->d_rowlen, len3);
     STANCHK(stan_scan_exclusive(ctx, len3, rp, n3));
     hipLaunchKernelGGL(k_csr_fill, dim3(nblk(nloc, 256)), dim3(256), 0, st, nloc, K->d_rowlen, K->d_posof, K->d_slot_ptr,
-                       K->d_cols, K->d_vals, rp, ci, cv);
+                       K->d_cols, K->vals64(), rp, ci, cv);
     // x_i = 1 + (i mod 7): cheap, non-constant
     std::vector<double> hx((size_t)npad3);
     for (size_t i = 0; i < hx.size(); i++) hx[i] = 1.0 + (double)(i % 7);

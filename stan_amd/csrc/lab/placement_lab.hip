@@ -24,9 +24,9 @@ extern "C" int stan_hip_lab_placement_map(stan_ctx *ctx, stan_matrix *K, int32_t
     const int per = 1 + 2 * nseg;
     for (int t = 0; t < ntries; t++) {
         void *q = nullptr;
-        if (t == 0) q = K->d_vals;   // candidate 0 = the block the matrix lives in
+        if (t == 0) q = K->vals64();   // candidate 0 = the block the matrix lives in
         else if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); break; }
-        if (t > 0) HIPCHK(ctx, hipMemcpyAsync(q, K->d_vals, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        if (t > 0) HIPCHK(ctx, hipMemcpyAsync(q, K->vals64(), bytes, hipMemcpyDeviceToDevice, ctx->stream));
         cand.push_back(q);
         if (addr) addr[t] = (uint64_t)(uintptr_t)q;
         float f = 0;
@@ -52,8 +52,8 @@ extern "C" int stan_hip_lab_placement_map(stan_ctx *ctx, stan_matrix *K, int32_t
     for (size_t t = 1; t < cand.size(); t++)
         if (t != pick) hipFree(cand[t]);
     if (pick != 0) {   // the old block was handed out by the pool: give it back there
-        stan_dfree(ctx, K->d_vals);
-        K->d_vals = (double *)cand[pick];
+        stan_dfree(ctx, K->vals64());
+        K->vs[STAN_PREC_FP64].padded = cand[pick];
     }
     return STAN_OK;
 }
@@ -69,9 +69,9 @@ extern "C" int stan_hip_lab_placement_variants(stan_ctx *ctx, stan_matrix *K, in
     std::vector<void *> cand;
     for (int t = 0; t < ntries; t++) {
         void *q = nullptr;
-        if (t == 0) q = K->d_vals;
+        if (t == 0) q = K->vals64();
         else if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); break; }
-        if (t > 0) HIPCHK(ctx, hipMemcpyAsync(q, K->d_vals, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        if (t > 0) HIPCHK(ctx, hipMemcpyAsync(q, K->vals64(), bytes, hipMemcpyDeviceToDevice, ctx->stream));
         cand.push_back(q);
     }
     for (int round = 0; round < 2; round++)   // second round overwrites the first: warm
@@ -133,14 +133,14 @@ extern "C" int stan_hip_lab_placement_alloc(stan_ctx *ctx, stan_matrix *K, int32
         event_bag ev;
         const auto t0 = std::chrono::steady_clock::now();
         hipError_t e = hipSuccess;
-        if (strategy[t] == 4) q = K->d_vals;
+        if (strategy[t] == 4) q = K->vals64();
         else if (strategy[t] == 3) e = hipExtMallocWithFlags(&q, req, hipDeviceMallocUncached);
         else e = hipMalloc(&q, req);
         const double alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         if (e != hipSuccess) { (void)hipGetLastError(); for (int v = 0; v < 5; v++) out[t * 5 + v] = -1; continue; }
         cand[(size_t)t] = q;
         if (addr) addr[t] = (uint64_t)(uintptr_t)q;
-        if (q != K->d_vals) HIPCHK(ctx, hipMemcpyAsync(q, K->d_vals, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        if (q != K->vals64()) HIPCHK(ctx, hipMemcpyAsync(q, K->vals64(), bytes, hipMemcpyDeviceToDevice, ctx->stream));
         float f = 0;
         STANCHK(stan_spmv_probe_range(ctx, K, (const double *)q, 0, K->nslices, 10, &f, 9));
         out[t * 5] = f;
@@ -151,7 +151,7 @@ extern "C" int stan_hip_lab_placement_alloc(stan_ctx *ctx, stan_matrix *K, int32
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     for (int t = 0; t < n; t++)
-        if (cand[(size_t)t] && cand[(size_t)t] != K->d_vals) hipFree(cand[(size_t)t]);
+        if (cand[(size_t)t] && cand[(size_t)t] != K->vals64()) hipFree(cand[(size_t)t]);
     return STAN_OK;
 }
 
@@ -167,9 +167,9 @@ extern "C" int stan_hip_lab_placement_rounds(stan_ctx *ctx, stan_matrix *K, int3
     std::vector<void *> cand;
     for (int t = 0; t < ntries; t++) {
         void *q = nullptr;
-        if (t == 0) q = K->d_vals;
+        if (t == 0) q = K->vals64();
         else if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); break; }
-        if (t > 0) HIPCHK(ctx, hipMemcpyAsync(q, K->d_vals, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        if (t > 0) HIPCHK(ctx, hipMemcpyAsync(q, K->vals64(), bytes, hipMemcpyDeviceToDevice, ctx->stream));
         cand.push_back(q);
     }
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -200,9 +200,9 @@ extern "C" int stan_hip_lab_placement_cross(stan_ctx *ctx, stan_matrix *K, int32
     std::vector<void *> cand;
     for (int t = 0; t < ntries; t++) {
         void *q = nullptr;
-        if (t == 0) q = K->d_vals;
+        if (t == 0) q = K->vals64();
         else if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); break; }
-        if (t > 0) HIPCHK(ctx, hipMemcpyAsync(q, K->d_vals, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        if (t > 0) HIPCHK(ctx, hipMemcpyAsync(q, K->vals64(), bytes, hipMemcpyDeviceToDevice, ctx->stream));
         cand.push_back(q);
         float f = 0;
         STANCHK(stan_spmv_probe_range(ctx, K, (const double *)q, 0, K->nslices, 10, &f, 9));
@@ -254,18 +254,18 @@ extern "C" int stan_hip_lab_placement_vecalloc(stan_ctx *ctx, stan_matrix *K, do
     // keep a copy of the front of the values (mode 0 overwrites it)
     void *save = nullptr;
     HIPCHK(ctx, hipMalloc(&save, vbytes));
-    HIPCHK(ctx, hipMemcpy(save, K->d_vals, vbytes, hipMemcpyDeviceToDevice));
-    STANCHK(stan_spmv_probe_range(ctx, K, K->d_vals, 0, K->nslices, 10, &f, 9, K->d_vals)); out[0] = f;
-    HIPCHK(ctx, hipMemcpy(K->d_vals, save, vbytes, hipMemcpyDeviceToDevice));
+    HIPCHK(ctx, hipMemcpy(save, K->vals64(), vbytes, hipMemcpyDeviceToDevice));
+    STANCHK(stan_spmv_probe_range(ctx, K, K->vals64(), 0, K->nslices, 10, &f, 9, K->vals64())); out[0] = f;
+    HIPCHK(ctx, hipMemcpy(K->vals64(), save, vbytes, hipMemcpyDeviceToDevice));
     hipFree(save);
     void *a = nullptr;
     if (hipMalloc(&a, vbytes) == hipSuccess) {
-        STANCHK(stan_spmv_probe_range(ctx, K, K->d_vals, 0, K->nslices, 10, &f, 9, (double *)a)); out[1] = f;
+        STANCHK(stan_spmv_probe_range(ctx, K, K->vals64(), 0, K->nslices, 10, &f, 9, (double *)a)); out[1] = f;
         hipFree(a);
     }
     a = nullptr;
     if (hipMallocAsync(&a, vbytes, ctx->stream) == hipSuccess) {
-        STANCHK(stan_spmv_probe_range(ctx, K, K->d_vals, 0, K->nslices, 10, &f, 9, (double *)a)); out[2] = f;
+        STANCHK(stan_spmv_probe_range(ctx, K, K->vals64(), 0, K->nslices, 10, &f, 9, (double *)a)); out[2] = f;
         hipFreeAsync(a, ctx->stream);
         hipStreamSynchronize(ctx->stream);
     } else (void)hipGetLastError();
@@ -285,7 +285,7 @@ extern "C" int stan_hip_lab_placement_vecalloc(stan_ctx *ctx, stan_matrix *K, do
                     acc.location = prop.location;
                     acc.flags = hipMemAccessFlagsProtReadWrite;
                     if (hipMemMap(va, sz, 0, h, 0) == hipSuccess && hipMemSetAccess(va, sz, &acc, 1) == hipSuccess) {
-                        STANCHK(stan_spmv_probe_range(ctx, K, K->d_vals, 0, K->nslices, 10, &f, 9, (double *)va)); out[3] = f;
+                        STANCHK(stan_spmv_probe_range(ctx, K, K->vals64(), 0, K->nslices, 10, &f, 9, (double *)va)); out[3] = f;
                         hipMemUnmap(va, sz);
                     }
                     hipMemAddressFree(va, sz);
@@ -298,7 +298,7 @@ extern "C" int stan_hip_lab_placement_vecalloc(stan_ctx *ctx, stan_matrix *K, do
     STANCHK(stan_cg_workspace(ctx, K));
     {   // the context's own vectors: region = ws.p .. (x) and ws.v (y) are separate blocks; use the probe
         float t = 0;
-        STANCHK(stan_spmv_probe(ctx, K, K->d_vals, (size_t)K->nslots * 9 * 64 * 8, STAN_PREC_FP64, &t, false)); out[4] = t;
+        STANCHK(stan_spmv_probe(ctx, K, K->vals64(), (size_t)K->nslots * 9 * 64 * 8, STAN_PREC_FP64, &t, false)); out[4] = t;
     }
     return STAN_OK;
 }
@@ -326,7 +326,7 @@ extern "C" int stan_hip_lab_placement_vecshape(stan_ctx *ctx, stan_matrix *K, do
             if (kind == 2) { x = get((size_t)1 << 30); y = x ? x + vb / 8 : nullptr; }
             if (kind == 3) { double *q[8]; for (int i = 0; i < 8; i++) q[i] = get(vb); x = q[2]; y = q[4]; }
             if (x && y) {
-                STANCHK(stan_spmv_probe_range(ctx, K, K->d_vals, 0, K->nslices, 10, &f, 9, x, y));
+                STANCHK(stan_spmv_probe_range(ctx, K, K->vals64(), 0, K->nslices, 10, &f, 9, x, y));
                 out[pass * 4 + kind] = f;
             }
             for (void *q : blk) hipFree(q);
@@ -360,16 +360,16 @@ extern "C" int stan_hip_lab_pairing_pmc(stan_ctx *ctx, stan_matrix *K, int32_t r
     if (hipMalloc((void **)&far, 2 * vb) != hipSuccess) { (void)hipGetLastError(); for (void *q : spacer) hipFree(q); return STAN_E_ALLOC; }
     float f = 0;
     for (int phase = 0; phase < 3; phase++) {
-        double *x = phase == 1 ? K->d_vals : far;
+        double *x = phase == 1 ? K->vals64() : far;
         double *y = x + vb / 8;
         if (phase == 1) {   // the block holds the matrix: save what the vectors overwrite
             // (the probe fills x with ones and writes y: 2 vb bytes at the front of the value block)
         }
         std::vector<char> keep;
-        if (phase == 1) { keep.resize(2 * vb); HIPCHK(ctx, hipMemcpy(keep.data(), K->d_vals, 2 * vb, hipMemcpyDeviceToHost)); }
-        STANCHK(stan_spmv_probe_range(ctx, K, K->d_vals, 0, K->nslices, reps, &f, 9, x, y));
+        if (phase == 1) { keep.resize(2 * vb); HIPCHK(ctx, hipMemcpy(keep.data(), K->vals64(), 2 * vb, hipMemcpyDeviceToHost)); }
+        STANCHK(stan_spmv_probe_range(ctx, K, K->vals64(), 0, K->nslices, reps, &f, 9, x, y));
         out_ms[phase] = f;
-        if (phase == 1) HIPCHK(ctx, hipMemcpy(K->d_vals, keep.data(), 2 * vb, hipMemcpyHostToDevice));
+        if (phase == 1) HIPCHK(ctx, hipMemcpy(K->vals64(), keep.data(), 2 * vb, hipMemcpyHostToDevice));
     }
     hipFree(far);
     for (void *q : spacer) hipFree(q);

@@ -3,8 +3,9 @@
 // order (tools/placement_map.py).  The product library never compiles this file.
         const int32_t *cp = cols + (int64_t)k0 * 64 + lane;
         const VT *vp = vals + (int64_t)k0 * vstream<VT>::STRIDE + lane;
-        if (VAR == 8 && !vstream<VT>::FX) {  // timing only: 16-B accesses, results are wrong
-            typedef VT v2 __attribute__((ext_vector_type(2)));
+        if (VAR == 8 && !vstream<VT>::FX && std::is_arithmetic_v<VT>) {  // timing only: 16-B accesses, results are wrong
+            typedef std::conditional_t<std::is_arithmetic_v<VT>, VT, float> e2;   // (the 60-bit stream's words are no vector element)
+            typedef e2 v2 __attribute__((ext_vector_type(2)));
             const v2 *vq = (const v2 *)(vals + (int64_t)k0 * 9 * 64) + lane;
             for (int32_t k = k0; k + 1 < k1; k += 2) {
                 const int64_t c = __builtin_nontemporal_load(cp), c2 = __builtin_nontemporal_load(cp + 64);

@@ -8,6 +8,7 @@
 #include "internal.h"
 #include "fx48.h"
 #include "s60.h"
+static_assert(S60_ROWS == 17, "stan_matrix::vs: dwords per slot of the 60-bit stream");
 
 namespace {
 
@@ -158,38 +159,50 @@ __global__ void k_count_ok(int32_t nslices, const uint8_t *ok, const int32_t *sl
 
 }  // namespace
 
+// A block for `slots` slots of a value stream of K, allocated by trial (placement.hip) with the very product that will stream it
+int stan_matrix_alloc_stream(stan_ctx *ctx, stan_matrix *K, int32_t kind, int64_t slots, void **out, bool folded, bool second_copy) {
+    const size_t bytes = (size_t)slots * K->vs[kind].dwords * 64 * 4;
+    return stan_dmalloc_streamed(ctx, out, bytes, [&, bytes](const void *q, float *ms, bool self) {
+        return stan_spmv_probe(ctx, K, q, bytes, kind, ms, self, folded);
+    }, second_copy);
+}
+// The encoding pass of the FIXED-48 or the 60-bit stream over scaled values; *bad = the entries it refused.  Synchronises the stream.
+int stan_stream_encode(stan_ctx *ctx, int32_t kind, int64_t nslots, const double *d_vals, uint32_t *d_out, int64_t *bad) {
+    unsigned long long *d_bad = (unsigned long long *)(ctx->d_status + SS_COUNTER);
+    *bad = 0;
+    if (nslots <= 0) return STAN_OK;
+    HIPCHK(ctx, hipMemsetAsync(d_bad, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(kind == STAN_PREC_FIXED48 ? k_to_fx48 : k_to_s60, dim3((unsigned)nblk(nslots * 64, 256)), dim3(256), 0, ctx->stream, nslots, d_vals, d_out, d_bad);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_COUNTER, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    *bad = ctx->h_status[SS_COUNTER];
+    return STAN_OK;
+}
+
 int stan_matrix_make_fp32(stan_ctx *ctx, stan_matrix *K) {
-    if (K->d_vals32) return STAN_OK;
+    stan_value_stream &s = K->vs[STAN_PREC_MIXED];
+    if (s.padded) return STAN_OK;
     const int64_t n = K->nslots * 9 * 64;
-    STANCHK(stan_dmalloc_streamed(ctx, (void **)&K->d_vals32, (size_t)n * 4,
-                                  [&](const void *q, float *ms, bool self) {
-                                      return stan_spmv_probe(ctx, K, q, (size_t)n * 4, STAN_PREC_MIXED, ms, self);
-                                  }));
+    STANCHK(stan_matrix_alloc_stream(ctx, K, STAN_PREC_MIXED, K->nslots, &s.padded));
     const unsigned blocks = std::min(std::max(nblk(n, 256), 1u), 2048u);   // (four times the grid of the CG's vector kernels)
-    hipLaunchKernelGGL(k_to_fp32, dim3(blocks * 4), dim3(256), 0, ctx->stream, K->d_vals, K->d_vals32, n);
+    hipLaunchKernelGGL(k_to_fp32, dim3(blocks * 4), dim3(256), 0, ctx->stream, K->vals64(), (float *)s.padded, n);
     HIPCHK(ctx, hipGetLastError());
     return STAN_OK;
 }
 
-// FIXED-48 copy of the scaled values.  Returns STAN_OK with K->d_vals48 == nullptr when some
+// FIXED-48 copy of the scaled values.  Returns STAN_OK with no block (and the stream marked refused) when some
 // entry is not representable (K not SPD): the caller then streams the fp64 values.
 int stan_matrix_make_fx48(stan_ctx *ctx, stan_matrix *K) {
-    if (K->d_vals48 || K->fx48_refused) return STAN_OK;
+    stan_value_stream &s = K->vs[STAN_PREC_FIXED48];
+    if (s.padded || s.refused) return STAN_OK;
     if (K->nslots == 0) return STAN_OK;
-    uint32_t *out;
-    STANCHK(stan_dmalloc_streamed(ctx, (void **)&out, (size_t)K->nslots * 14 * 64 * 4,
-                                  [&](const void *q, float *ms, bool self) {
-                                      return stan_spmv_probe(ctx, K, q, (size_t)K->nslots * 14 * 64 * 4, STAN_PREC_FIXED48, ms, self);
-                                  }));
-    unsigned long long *d_bad = (unsigned long long *)(ctx->d_status + SS_COUNTER);
-    HIPCHK(ctx, hipMemsetAsync(d_bad, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(k_to_fx48, dim3((unsigned)nblk(K->nslots * 64, 256)), dim3(256), 0, ctx->stream,
-                       K->nslots, K->d_vals, out, d_bad);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_COUNTER, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->h_status[SS_COUNTER] != 0) { stan_dfree(ctx, out); K->fx48_refused = true; return STAN_OK; }
-    K->d_vals48 = out;
+    void *out;
+    int64_t bad = 0;
+    STANCHK(stan_matrix_alloc_stream(ctx, K, STAN_PREC_FIXED48, K->nslots, &out));
+    STANCHK(stan_stream_encode(ctx, STAN_PREC_FIXED48, K->nslots, K->vals64(), (uint32_t *)out, &bad));
+    if (bad != 0) { stan_dfree(ctx, out); s.refused = true; return STAN_OK; }
+    s.padded = out;
     return STAN_OK;
 }
 
@@ -232,37 +245,31 @@ int stan_matrix_alloc_s60(stan_ctx *ctx, stan_matrix *K, uint32_t **out) {
     const size_t bytes = (size_t)K->nslots * S60_ROWS * 64 * 4;
     *out = nullptr;
     if (!s60_room(ctx, K, bytes)) return STAN_OK;
-    const int rc = stan_dmalloc_streamed(ctx, (void **)out, bytes, [&](const void *q, float *ms, bool self) {
-        return stan_spmv_probe(ctx, K, q, bytes, STAN_VALUE_STREAM_60, ms, self);
-    }, true);
+    const int rc = stan_matrix_alloc_stream(ctx, K, STAN_VALUE_STREAM_60, K->nslots, (void **)out, false, true);
     if (rc == STAN_E_ALLOC) { ctx->err.clear(); *out = nullptr; return STAN_OK; }   // (fragmentation: room by the figures, no block)
     return rc;
 }
-int stan_s60_encode(stan_ctx *ctx, int64_t nslots, const double *d_vals, uint32_t *d_out, int64_t *refused) {
-    *refused = 0;
-    if (nslots <= 0) return STAN_OK;
-    unsigned long long *d_bad = (unsigned long long *)(ctx->d_status + SS_COUNTER);
-    HIPCHK(ctx, hipMemsetAsync(d_bad, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(k_to_s60, dim3((unsigned)nblk(nslots * 64, 256)), dim3(256), 0, ctx->stream, nslots, d_vals, d_out, d_bad);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_COUNTER, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    *refused = ctx->h_status[SS_COUNTER];
+// K's scaled values into `blk` (stan_matrix_alloc_s60's), which becomes K's 60-bit stream -- or, an entry refused, goes back:
+// the matrix then streams fp64 for good
+int stan_matrix_encode_s60(stan_ctx *ctx, stan_matrix *K, uint32_t *blk) {
+    stan_value_stream &s = K->vs[STAN_VALUE_STREAM_60];
+    int64_t refused = 0;
+    const int rc = stan_stream_encode(ctx, STAN_VALUE_STREAM_60, K->nslots, K->vals64(), blk, &refused);
+    if (rc != STAN_OK || refused != 0) { stan_dfree(ctx, blk); s.refused = rc == STAN_OK; return rc; }
+    s.padded = blk;
     return STAN_OK;
 }
 
 // Packed column stream of K (struct colstream), built once per matrix; the int32 columns stay (the
 // assembly, scaling and export kernels use them).
 int stan_matrix_make_cols16(stan_ctx *ctx, stan_matrix *K) {
-    if (K->d_cols16 || K->nslices <= 0) return STAN_OK;
-    return stan_pack_columns(ctx, K->nslices, K->nslots, K->d_slot_ptr, K->d_cols, &K->d_cols16, &K->d_colbase, &K->d_pair_ptr,
-                             &K->d_slice_packed, &K->slots_packed, K->nloc, K->d_rowof, K->d_rowlen, &K->slots_packed2);
+    if (K->pk.cols16 || K->nslices <= 0) return STAN_OK;
+    return stan_pack_columns(ctx, K->nslices, K->nslots, K->d_slot_ptr, K->d_cols, &K->pk, K->nloc, K->d_rowof, K->d_rowlen);
 }
-// the same for any sliced column stream (the folded copy of fold.hip has its own); *packed stays nullptr when the
-// pair index would not fit an int32
-int stan_pack_columns(stan_ctx *ctx, int32_t nslices, int64_t nslots, const int32_t *d_slot_ptr, const int32_t *d_cols,
-                      uint32_t **packed_out, int32_t **base_out, int32_t **pair_ptr_out, uint8_t **ok_out, int64_t *slots_packed,
-                      int64_t nloc, const int32_t *d_rowof, const int32_t *d_rowlen, int64_t *slots_packed2) {
+// the same for any sliced column stream (the folded copy of fold.hip has its own: no row lengths, so no two-base slices);
+// out->cols16 stays nullptr when the pair index would not fit an int32
+int stan_pack_columns(stan_ctx *ctx, int32_t nslices, int64_t nslots, const int32_t *d_slot_ptr, const int32_t *d_cols, stan_colpack *out,
+                      int64_t nloc, const int32_t *d_rowof, const int32_t *d_rowlen) {
     hipStream_t st_ = ctx->stream;
     dev_scope bufs(ctx);
     int32_t *cnt; int64_t *ptr64;
@@ -273,26 +280,26 @@ int stan_pack_columns(stan_ctx *ctx, int32_t nslices, int64_t nslots, const int3
     HIPCHK(ctx, hipStreamSynchronize(st_));
     const int64_t npairs = ctx->h_status[SS_H_NSLOTS];
     if (npairs >= ((int64_t)1 << 31)) return STAN_OK;   // pair index is int32: keep the plain columns
-    STANCHK(stan_slot_ptr_narrow(ctx, ptr64, nslices, pair_ptr_out));
+    STANCHK(stan_slot_ptr_narrow(ctx, ptr64, nslices, &out->pair_ptr));
     // one allocation: [n] base, [n] base2, [nslices] cmask (64-bit words), n = max(nslots, 1): make_colstream
     const size_t nb_ = (size_t)(nslots > 0 ? nslots : 1);
-    STANCHK(stan_dmalloc(ctx, base_out, 2 * nb_ + 2 * (size_t)nslices + 2));
-    STANCHK(stan_dmalloc(ctx, ok_out, (size_t)nslices));
+    STANCHK(stan_dmalloc(ctx, &out->colbase, 2 * nb_ + 2 * (size_t)nslices + 2));
+    STANCHK(stan_dmalloc(ctx, &out->packed, (size_t)nslices));
     uint32_t *packed;
     STANCHK(stan_dmalloc(ctx, &packed, (size_t)(npairs > 0 ? npairs : 1) * 64));
-    int32_t *b2_ = *base_out + nb_;
-    unsigned long long *cm_ = (unsigned long long *)(*base_out + 2 * nb_);
+    int32_t *b2_ = out->colbase + nb_;
+    unsigned long long *cm_ = (unsigned long long *)(out->colbase + 2 * nb_);
     if (((uintptr_t)cm_ & 7) != 0) cm_ = (unsigned long long *)((uintptr_t)cm_ + 4);   // (never: 2 n ints from an aligned block)
     hipLaunchKernelGGL(k_pack_cols, dim3(nblk(nslices, 4)), dim3(256), 0, st_, nslices, nloc, d_slot_ptr, d_cols, d_rowof, d_rowlen,
-                       *pair_ptr_out, packed, *base_out, b2_, cm_, *ok_out);
+                       out->pair_ptr, packed, out->colbase, b2_, cm_, out->packed);
     unsigned long long *d_cnt = (unsigned long long *)(ctx->d_status + SS_COUNTER);   // two words: SS_COUNTER, SS_H_ERRCOPY
     HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, 16, st_));
-    hipLaunchKernelGGL(k_count_ok, dim3(nblk(nslices, 256)), dim3(256), 0, st_, nslices, *ok_out, d_slot_ptr, d_cnt);
+    hipLaunchKernelGGL(k_count_ok, dim3(nblk(nslices, 256)), dim3(256), 0, st_, nslices, out->packed, d_slot_ptr, d_cnt);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_COUNTER, d_cnt, 16, hipMemcpyDeviceToHost, st_));
     HIPCHK(ctx, hipStreamSynchronize(st_));
-    *slots_packed = ctx->h_status[SS_COUNTER];
-    if (slots_packed2) *slots_packed2 = ctx->h_status[SS_COUNTER + 1];
-    *packed_out = packed;
+    out->slots_packed = ctx->h_status[SS_COUNTER];
+    out->slots_packed2 = ctx->h_status[SS_COUNTER + 1];
+    out->cols16 = packed;
     return STAN_OK;
 }

@@ -90,9 +90,9 @@ struct colstream {
 };
 constexpr colstream NO_COLSTREAM = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 // the arrays behind `base` (one allocation, stan_pack_columns): [nslots] base, [nslots] base2, [nslices] cmask
-inline colstream make_colstream(const uint32_t *packed, const int32_t *base, const int32_t *pair_ptr, const uint8_t *ok, int64_t nslots) {
+inline colstream make_colstream(const stan_colpack &c, int64_t nslots) {
     const int64_t n = nslots > 0 ? nslots : 1;
-    return colstream{packed, base, pair_ptr, ok, base + n, (const unsigned long long *)(base + 2 * n)};
+    return colstream{c.cols16, c.colbase, c.pair_ptr, c.packed, c.colbase + n, (const unsigned long long *)(c.colbase + 2 * n)};
 }
 
 // ---- the pieces every product kernel shares -------------------------------------------------------------------------

@@ -18,7 +18,9 @@ Cases: problem.cube_job(n, jitter=0.05), eps 1e-10, on
     n = 6     343 block rows, 6 slices: fewer blocks than the ticket counters of a folded reduction has sub-counters
     n = 14    3375 block rows, 53 slices (a ragged last workgroup), 40 vector blocks: more than sub-counters
 each with the small-system product kernel (OPT_SPMV_SMALL 1) and with the large-system kernels (OPT_SPMV_SMALL 0) on
-padded (OPT_ROW_FOLDING 0) and folded (1) streams; every loop form of FORMS, one option at a time off its default; and
+padded (OPT_ROW_FOLDING 0) and folded (1) streams; every loop form of _forms, one option at a time off its default; the
+60-bit value stream alone and with each option it shares the choice of kernel and stream with (_stream60_forms: on
+every matrix form, so that "inert here" is recorded too); solves on a fresh matrix each (_fresh_forms); and
 cg_solve_multi with 7 right-hand sides (groups of 4 + 2 + 1; one of them zero), one record per column.
 Only stan_amd's public Python API is used.
 """
@@ -72,6 +74,35 @@ def _forms(hip):
     return forms
 
 
+def _stream60_forms(hip):
+    """The lossless 60-bit value stream (OPT_VALUE_STREAM_60 1) alone and next to every option that decides with it which
+    kernel reads which stream, and the two large-system kernel variants alone.  Run BEHIND the forms above (the list only
+    grows: the cases in front keep the sequence they were recorded in)."""
+    s60 = (hip.OPT_VALUE_STREAM_60, 1, -1)
+    forms = [("value_stream_60_1", [s60], {}, 1.0)]
+    for v in (12, 9, 0, 20):
+        forms.append(("value_stream_60_1_spmv_variant_%d" % v, [s60, (hip.OPT_SPMV_VARIANT, v, -1)], {}, 1.0))
+    forms.append(("value_stream_60_1_single_reduce_1", [s60, (hip.OPT_CG_SINGLE_REDUCE, 1, 0)], {}, 1.0))
+    forms.append(("value_stream_60_1_fused_refresh_0", [s60, (hip.OPT_CG_FUSED_REFRESH, 0, 1)], {}, 1.0))
+    for prec, mode in (("mixed", hip.PREC_MIXED), ("fixed48", hip.PREC_FIXED48)):
+        forms.append(("value_stream_60_1_%s_refine_1" % prec, [s60, (hip.OPT_CG_REFINE, 1, 1)], {"precision_mode": mode}, 1.0))
+    forms.append(("spmv_variant_9", [(hip.OPT_SPMV_VARIANT, 9, -1)], {}, 1.0))
+    forms.append(("spmv_variant_12", [(hip.OPT_SPMV_VARIANT, 12, -1)], {}, 1.0))
+    return forms
+
+
+def _fresh_forms(hip):
+    """Solves that must find the matrix as the assembly left it (unscaled, no copy of a stream): a fresh matrix each."""
+    s60 = (hip.OPT_VALUE_STREAM_60, 1, -1)
+    lazy0 = (hip.OPT_CG_LAZY_SCALING, 0, 1)
+    return [
+        ("lazy_scaling_0", [lazy0]),                                   # the scaling pass of its own instead of the first product's
+        ("fresh_value_stream_60_1", [s60]),                            # the first product scales, then the encoding pass
+        ("fresh_value_stream_60_1_lazy_scaling_0", [s60, lazy0]),
+        ("fresh_rupdate_1", [(hip.OPT_CG_RUPDATE, 1, 10)]),            # a refresh at iteration 1: no plain first product
+    ]
+
+
 def _solve_record(ctx, K, F, kw):
     U, rep = K.cg_solve(F, EPS, **kw)
     pf = ctx.profile()
@@ -92,18 +123,22 @@ def cases(ctx, n, matrix_form):
     if folding is not None:
         ctx.set_option(hip.OPT_ROW_FOLDING, folding)
     ctx.set_profiling(True)
+
+    def solve_with(fname, opts, K, F, kw):
+        try:
+            for o, v, _ in opts:
+                ctx.set_option(o, v)
+            out[fname] = _solve_record(ctx, K, F, kw)
+        finally:
+            for o, _, d in opts:
+                ctx.set_option(o, d)
+
     try:
         K = ctx.assemble_hex8(*args)
         # "default" comes first: the solve that finds the matrix unscaled (the large-system fp64 loop scales it in its
         # first product); "default_scaled_matrix" repeats it on the scaled one
-        for fname, opts, kw, fscale in _forms(hip) + [("default_scaled_matrix", [], {}, 1.0)]:
-            try:
-                for o, v, _ in opts:
-                    ctx.set_option(o, v)
-                out[fname] = _solve_record(ctx, K, job.F * fscale, kw)
-            finally:
-                for o, _, d in opts:
-                    ctx.set_option(o, d)
+        for fname, opts, kw, fscale in _forms(hip) + [("default_scaled_matrix", [], {}, 1.0)] + _stream60_forms(hip):
+            solve_with(fname, opts, K, job.F * fscale, kw)
         # several load cases in one loop: F scaled by 1 .. 7, one column zero
         F2 = np.stack([job.F * float(c + 1) for c in range(N_RHS)])
         F2[ZERO_COLUMN] = 0.0
@@ -113,14 +148,10 @@ def cases(ctx, n, matrix_form):
                 "U_sha256": hashlib.sha256(U2[c].tobytes()).hexdigest(), "terminationtype": int(reps[c]["terminationtype"]),
                 "iterations": int(reps[c]["iterations"]), "rel_residual": float(reps[c]["rel_residual"]).hex()}
         K.free()
-        # the scaling pass of its own instead of the first product's: once per matrix, so a fresh one
-        ctx.set_option(hip.OPT_CG_LAZY_SCALING, 0)
-        try:
+        for fname, opts in _fresh_forms(hip):
             K = ctx.assemble_hex8(*args)
-            out["lazy_scaling_0"] = _solve_record(ctx, K, job.F, {})
+            solve_with(fname, opts, K, job.F, {})
             K.free()
-        finally:
-            ctx.set_option(hip.OPT_CG_LAZY_SCALING, 1)
     finally:
         ctx.set_profiling(False)
         ctx.set_option(hip.OPT_SPMV_SMALL, 1)
