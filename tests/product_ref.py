@@ -15,6 +15,11 @@ diagonal / scaled_residual and cg_solve / cg_solve_multi with max_its = k; nothi
    np.longdouble on an exported CSR and returns every iterate U_k = S x_k with sqrt(r_k . r_k) / ||b^||.  "The same
    iterates" then reads in units of 2^-53 instead of 1e-9.
 
+3. THE SHARDED RESTATEMENT.  rank_of_rows / halo_entries / slice_census read the host's partition plan onto the exported CSR,
+   rank_dot is the sum of a solve on several ranks (per-rank partials added in rank order), and cg_iterates /
+   cg_single_reduce_f64 take it for every sum of the loop (dot=): the float64 loop as a sharded solve orders it, which
+   tests/test_product_ref.py holds inside the one-rank bounds -- and the mutants of a halo exchange outside them.
+
 Row sums (row_units) are counted in units of 2^-53 sum_j |a_ij| |x_j|, the rounding scale of the row itself: a wrong entry
 in a row far below max|y| cannot hide there.  A row of m stored entries summed in ANY order, with or without fused
 multiply-adds, errs by at most m units (m - 1 additions and m products, each product sharing its rounding with an addition
@@ -315,24 +320,26 @@ def _dot(a, b):
     return (a * b).sum()
 
 
-def cg_iterates(A, F, kmax, rupdate=10, pap=_dot, late_beta=False, mv=None):
+def cg_iterates(A, F, kmax, rupdate=10, pap=None, late_beta=False, mv=None, dot=_dot):
     """The classic loop of stan_oracle_cg_opt (merit stop off) on the Scaled matrix A in A's number type:
-    [(U_k, sqrt(r_k . r_k) / ||b^||) for k = 1 .. kmax].  pap(p, v): the sum p . A p; late_beta: beta from the rho of one
-    iteration earlier; mv: another product -- the hooks of the mutants."""
+    [(U_k, sqrt(r_k . r_k) / ||b^||) for k = 1 .. kmax].  dot(a, b): every sum of the loop (rho, r . r, ||b^||^2, p . A p) --
+    rank_dot() for the order of a sharded solve; pap(p, v): the sum p . A p alone (default: dot); late_beta: beta from the rho
+    of one iteration earlier; mv: another product -- the hooks of the mutants."""
     mv = A.mv if mv is None else mv
+    pap = dot if pap is None else pap
     b = A.rhs(F)
     x, r = np.zeros_like(b), b.copy()
     p = r.copy()
-    rho = _dot(r, r)
+    rho = dot(r, r)
     rho_before = rho
-    bnorm = np.sqrt(_dot(b, b))
+    bnorm = np.sqrt(dot(b, b))
     out = []
     for k in range(1, kmax + 1):
         v = mv(p)
         alpha = rho / pap(p, v)
         x = x + alpha * p
         r = b - mv(x) if rupdate and k % rupdate == 0 else r - alpha * v
-        r2 = _dot(r, r)
+        r2 = dot(r, r)
         out.append((A.s * x, np.sqrt(r2) / bnorm))
         beta = r2 / (rho_before if late_beta else rho)
         rho_before, rho = rho, r2
@@ -346,21 +353,22 @@ def cg_reference(csr, F, kmax, rupdate=10, quantise=None):
     return [u for u, _r in its], [r for _u, r in its]
 
 
-def cg_single_reduce_f64(csr, F, kmax, rupdate=10):
+def cg_single_reduce_f64(csr, F, kmax, rupdate=10, dot=_dot):
     """The Chronopoulos-Gear recurrences as the comment block of cg_vector_kernels.inc states them, in plain float64 numpy:
       w_k = A r_k, gamma_k = r_k . r_k, delta_k = r_k . w_k
       beta_k = gamma_k / gamma_{k-1}, p_k . A p_k = delta_k - beta_k gamma_k / alpha_{k-1}, alpha_k = gamma_k / p_k . A p_k
       p = r + beta p, s = w + beta s, x' = x + alpha p, r' = r - alpha s      (refresh iterations: r' = b^ - A x')
-    Returns [(U_k, sqrt(gamma_k) / ||b^||)] with gamma_k the sum the product behind iteration k forms."""
+    Returns [(U_k, sqrt(gamma_k) / ||b^||)] with gamma_k the sum the product behind iteration k forms.  dot(a, b): every sum
+    (||b^||^2, gamma, delta), as in cg_iterates."""
     A = Scaled(*csr, T=np.float64)
     b = A.rhs(F)
     x, r, p, s = np.zeros_like(b), b.copy(), np.zeros_like(b), np.zeros_like(b)
-    bnorm = np.sqrt(_dot(b, b))
+    bnorm = np.sqrt(dot(b, b))
     gamma_prev = alpha_prev = None
     out = []
     for k in range(1, kmax + 2):
         w = A.mv(r)
-        gamma, delta = _dot(r, r), _dot(r, w)
+        gamma, delta = dot(r, r), dot(r, w)
         if k > 1:
             out.append((A.s * x, np.sqrt(gamma) / bnorm))
         if k == 1:
@@ -375,6 +383,72 @@ def cg_single_reduce_f64(csr, F, kmax, rupdate=10):
         r = b - A.mv(x) if rupdate and k % rupdate == 0 else r - alpha * s
         gamma_prev, alpha_prev = gamma, alpha
     return out
+
+
+# ---- the sharded loop -----------------------------------------------------------------------------------------------------------
+# What a solve on several ranks changes in the ARITHMETIC of the loop, restated on the exported CSR: every sum is formed rank
+# by rank and the partials are added in rank order (the all-reduce of the stand-in transport and the mailboxes of p2p.hip
+# alike); the product itself keeps its rows, whoever owns them.  Which row belongs to whom, which stored entries cross a cut
+# (the terms whose x_j arrives through the halo exchange) and which 64-row slices the split product puts on its boundary
+# list follow from the host's partition plan alone.
+
+def rank_of_rows(j, nranks):
+    """rank [N] of every reduced row of job j on nranks ranks: the host plan's cut of the block rows (host/partition.cpp: whole
+    64-row slices, ranks may stay empty), a reduced row belonging to the block row of its node."""
+    from stan_amd import host
+    rs = host.partition_plan(j.node_index, j.conn, nranks, 0)["row_starts"]
+    return np.searchsorted(rs, block_rows(j), side="right") - 1
+
+
+def block_rows(j):
+    """block row [N] (the node's place in the reference's DOF order) of every reduced row."""
+    return np.asarray(j.node_index, dtype=np.int64)[row_dofs(j)[0]]
+
+
+def halo_entries(csr, rank):
+    """Boolean mask over the stored entries: row and column lie on different ranks (rank: rank_of_rows)."""
+    rowptr, col, _val = csr
+    return rank[rows_of(rowptr)] != rank[col]
+
+
+def slice_census(j, csr, nranks):
+    """[(interior, boundary)] per rank: its 64-block-row slices without / with a halo entry in any of their rows -- the two lists
+    of the split product (assembly.hip: k_slice_class).  Counted on the reduced pattern: the device classes the block pattern,
+    in which a clamped node keeps its columns, so a slice whose only coupling across the cut runs through clamped DOFs would
+    be boundary there and interior here."""
+    from stan_amd import host
+    rs = host.partition_plan(j.node_index, j.conn, nranks, 0)["row_starts"]
+    rank, blk = rank_of_rows(j, nranks), block_rows(j)
+    touched = np.unique(blk[rows_of(csr[0])[halo_entries(csr, rank)]] // 64)          # (cuts sit on slice boundaries)
+    out = []
+    for r in range(nranks):
+        s0, s1 = int(rs[r]) // 64, -(-int(rs[r + 1]) // 64)
+        bnd = int(((touched >= s0) & (touched < s1)).sum()) if rs[r + 1] > rs[r] else 0
+        out.append(((s1 - s0 if rs[r + 1] > rs[r] else 0) - bnd, bnd))
+    return out
+
+
+def rank_dot(rank, nranks, ranks=None):
+    """dot(a, b) of a sharded solve: each rank sums its rows, the partials are added in rank order 0 .. nranks - 1, a rank
+    without rows adds nothing.  ranks: the ranks that take part (a mutant leaves one out)."""
+    parts = [np.nonzero(rank == r)[0] for r in (range(nranks) if ranks is None else ranks)]
+    parts = [q for q in parts if q.size]
+
+    def dot(a, b):
+        total = (a[parts[0]] * b[parts[0]]).sum()
+        for q in parts[1:]:
+            total = total + (a[q] * b[q]).sum()
+        return total
+    return dot
+
+
+def sharded_cg_bounds(name, lc, single_reduction=False):
+    """(U, residual) bound in units of 2^-53 of a sharded loop form: the one-rank loop's own, DEVICE_CG_FACTOR x the oracle's
+    figure for that load vector, or x the single-reduction yardstick (the job's own load vector only)."""
+    if single_reduction:
+        assert lc == 0
+        return DEVICE_CG_FACTOR * SR_CG_U_UNITS_MEASURED[name], DEVICE_CG_FACTOR * SR_CG_RES_UNITS_MEASURED[name]
+    return DEVICE_CG_FACTOR * ORACLE_CG_U_UNITS_MEASURED[name][lc], DEVICE_CG_FACTOR * ORACLE_CG_RES_UNITS_MEASURED[name][lc]
 
 
 def u_units(U, U_ref):

@@ -646,8 +646,10 @@ def test_plain_c_consumer_end_to_end(built_libs, oracle, tmp_path):
 @pytest.mark.parametrize("nranks", [2, 3, 8])
 def test_shards_and_halo_plan_on_one_gpu(built_libs, nranks):
     """Every rank's shard, assembled as a DETACHED rank on this GPU: the device-derived halo
-    plan equals the host plan (tests/test_distributed.py runs the sharded CG on it over gloo)
-    and shard x [owned | halo] reproduces the rows of the unsharded product bit for bit."""
+    plan equals the host plan (tests/test_distributed.py restates the sharded CG on it over gloo)
+    and shard x [owned | halo] reproduces the rows of the unsharded product bit for bit.  That is
+    the unsplit product of an unscaled matrix, outside the loop: the split product INSIDE the
+    loop, halo exchange included, is held entrywise by tests/test_gpu_sharded_precision.py."""
     import torch  # noqa: F401
     from stan_amd import hip, host
     job = problem.cube_job(11, jitter=0.1)

@@ -22,12 +22,10 @@ import pytest
 
 from stan_amd import hip
 from tests import product_ref as P
+from tests.gpu_models import DEFAULTS, assemble as _assemble, model as _model, reduced_reference, reference as _reference
 
 pytestmark = pytest.mark.gpu
 
-DEFAULTS = {hip.OPT_CG_MERIT_STOP: 1, hip.OPT_SPMV_VARIANT: -1, hip.OPT_SPMV_SMALL: 1, hip.OPT_PACKED_COLUMNS: 1, hip.OPT_SELL_SIGMA: 1,
-            hip.OPT_ROW_FOLDING: -1, hip.OPT_VALUE_STREAM_60: -1, hip.OPT_CG_FOLD_REDUCE: 1, hip.OPT_CG_FUSED_REFRESH: 1,
-            hip.OPT_CG_DEFER_X: 1, hip.OPT_CG_SINGLE_REDUCE: 0, hip.OPT_CG_REFINE: 1}
 LARGE = {hip.OPT_SPMV_SMALL: 0}
 PADDED = {**LARGE, hip.OPT_ROW_FOLDING: 0}            # the padded streams: left to itself (-1) the library folds where that saves slots
 # form -> options: what launch_product (cg.hip) routes a plain fp64 product to
@@ -63,30 +61,6 @@ class _options:
                 self.ctx.set_option(k, DEFAULTS[k])
         finally:
             self.ctx.set_profiling(False)
-
-
-def _assemble(ctx, name, sigma=1):
-    j = P.job(name)
-    ctx.set_option(hip.OPT_SELL_SIGMA, sigma)
-    try:
-        K = ctx.assemble_hex8(j.xyz, j.node_dof, j.conn, j.elem_mat, j.elem_type, j.mat_E_nu, j.red)
-    finally:
-        ctx.set_option(hip.OPT_SELL_SIGMA, DEFAULTS[hip.OPT_SELL_SIGMA])
-    assert K.info()["scaled"] == 0 and K.info()["sell_sigma"] == sigma
-    return K
-
-
-def _model(ctx, name):
-    """(csr, probes) of a model: the matrix as a fresh assembly exports it (the exact bits, nothing scaled), the colouring
-    computed once per module."""
-    def make():
-        K = _assemble(ctx, name)
-        csr = K.to_csr(upper_only=False)
-        assert K.info()["scaled"] == 0
-        K.free()
-        colour = P.colours(csr[0], csr[1], P.cube_grid(name))
-        return csr, P.Probes(csr[0], csr[1], colour, P.weights(csr[0].shape[0] - 1))
-    return P.cached(("gpu", name), make)
 
 
 def _same_export(K, csr):
@@ -223,11 +197,6 @@ LOOPS = {
 LOOP_CASES = [(m, f) for f, (_o, _fresh, models) in LOOPS.items() for m in models]
 
 
-def _reference(ctx, name, lc=0):
-    csr, _probes = _model(ctx, name)
-    return P.cached(("gpu", "cg", name, lc), lambda: P.cg_reference(csr, P.load_cases(name)[lc], P.KMAX))
-
-
 @pytest.mark.parametrize("name,form", LOOP_CASES)
 def test_every_iterate_against_the_long_double_cg(gpu_ctx, name, form):
     """cg_solve(F, 1e-30, max_its = k), merit stop off, for every k in 1 .. 22 (refreshes at 10 and 20): termination type 5 after
@@ -335,7 +304,7 @@ def test_every_iterate_of_a_reduced_precision_solve(gpu_ctx, name, stream):
     quantisation to two units; float32 8.7 / 3.3 (9.7 / 14.1) and 7.7 / 7.2 (7.4 / 6.9)."""
     j = P.job(name)
     csr, _probes = _model(gpu_ctx, name)
-    Us, rels = P.cached(("gpu", "cg", name, stream), lambda: P.cg_reference(csr, j.F, P.KMAX_REDUCED, quantise=P.QUANTISE[stream]))
+    Us, rels = reduced_reference(gpu_ctx, name, stream)
     mode = {"fixed48": hip.PREC_FIXED48, "mixed": hip.PREC_MIXED}[stream]
     its = P.cg_iterates(P.Scaled(*csr, T=np.float64, quantise=P.QUANTISE[stream]), j.F, P.KMAX_REDUCED)
     yu = max(P.u_units(x, Us[k]) for k, (x, _r) in enumerate(its))

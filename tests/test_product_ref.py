@@ -2,7 +2,9 @@
 (oracle.smv_upper rebuilt bit for bit), the yardsticks the device bounds derive from (measured on the oracle on every run and
 held within a factor of two of the recorded constants, both ways), the condition the CG comparison stands on (no compared
 iterate sits on a converged recurrence), and mutants: numpy stand-ins of a subtly wrong product or loop that every assertion
-of tests/test_gpu_product_precision.py must catch.  The real library is never asked to misbehave."""
+of tests/test_gpu_product_precision.py must catch; and the same for the sharded loop (tests/test_gpu_sharded_precision.py): the
+float64 loop with the sums of a solve on several ranks as its yardstick, the cuts its cases are chosen for, the mutants of a halo
+exchange.  The real library is never asked to misbehave."""
 import numpy as np
 import pytest
 
@@ -294,3 +296,148 @@ def test_reduced_precision_yardstick_and_the_decode_mutant(oracle, name, stream)
     print("%s %s: one entry of nine off by 2^-30: U %.3g / residual %.3g units at k = 3 (bounds %.0f / %.0f)" %
           (name, stream, u, r, P.DEVICE_CG_FACTOR * ru, P.DEVICE_CG_FACTOR * rr))
     assert u > P.DEVICE_CG_FACTOR * ru and r > P.DEVICE_CG_FACTOR * rr
+
+
+# ---- the sharded loop: yardstick and mutants ----------------------------------------------------------------------------------------
+
+SHARD_RANKS = (2, 3, 4, 8)
+
+
+def _ranks_of(name, nranks):
+    return P.cached(("rank_of_rows", name, nranks), lambda: P.rank_of_rows(P.job(name), nranks))
+
+
+def _series(its, Us, rels):
+    """(U units, residual units) per k; an iterate that is not finite (a mutant's division by a zero sum) counts as infinitely far."""
+    finite = [bool(np.isfinite(u).all() and np.isfinite(r)) for u, r in its]
+    return ([P.u_units(u, Us[k]) if finite[k] else np.inf for k, (u, _r) in enumerate(its)],
+            [P.res_units(r, rels[k]) if finite[k] else np.inf for k, (_u, r) in enumerate(its)])
+
+
+@pytest.mark.parametrize("name", P.CG_MODELS)
+def test_rank_ordered_sums_stay_inside_the_one_rank_bounds(oracle, built_libs, name):
+    """The yardstick of tests/test_gpu_sharded_precision.py: the float64 loop with every sum formed rank by rank and added in
+    rank order (P.rank_dot), on 2, 3, 4 and 8 ranks, keeps the bounds of the one-rank loop -- 4 x the oracle's figures for the
+    classic loop under the job's own load vector and under the seeded normal one, 4 x the single-reduction yardstick for the
+    Chronopoulos-Gear recurrences -- so a sharded solve that exceeds them does so for another reason than the order of its
+    sums.  Load case 2 is left out here and on the device: its margin on perforated12 is a few per cent (a restatement that
+    took the node number for the block row read 233 units against 245).
+    Measured, worst over k = 1 .. 22, U / residual units on 2, 3, 4, 8 ranks (rows dealt to the ranks as the device deals them:
+    the block row of a node is its place in the reference's DOF order, node_index, not its number):
+      classic, load case 0     cube6 39.1/102.6 37.8/63.6 36.3/45.5 35.6/62.9 (bounds 84/142)
+                               perforated12 76.5/104.0 70.3/110.3 73.4/114.5 77.1/119.7 (432/346)
+      classic, load case 1     cube6 7.9/45.2 8.4/22.2 8.9/19.6 11.4/27.4 (54/217)
+                               perforated12 11.9/31.6 12.8/35.8 14.2/30.2 14.2/38.6 (130/295)
+      single reduction, 0      cube6 44.1/56.7 42.3/93.0 62.1/183.1 70.2/148.1 (219/380)
+                               perforated12 201.4/313.3 132.6/219.1 164.1/236.9 159.1/273.5 (880/1299)"""
+    j, _A, csr = _model(oracle, name)
+    F = P.load_cases(name)
+    A = P.Scaled(*csr, T=np.float64)
+    for nranks in SHARD_RANKS:
+        dot = P.rank_dot(_ranks_of(name, nranks), nranks)
+        for lc in (0, 1):
+            bu, br = P.sharded_cg_bounds(name, lc)
+            u, r = _series(P.cg_iterates(A, F[lc], P.KMAX, dot=dot), *_cg_reference(oracle, name, lc))
+            print("%s on %d ranks, classic, load case %d: U %.1f / residual %.1f units (bounds %.0f / %.0f)" % (name, nranks, lc, max(u), max(r), bu, br))
+            assert max(u) <= bu and max(r) <= br, (nranks, lc)
+        bu, br = P.sharded_cg_bounds(name, 0, single_reduction=True)
+        u, r = _series(P.cg_single_reduce_f64(csr, F[0], P.KMAX, dot=dot), *_cg_reference(oracle, name, 0))
+        print("%s on %d ranks, single reduction, load case 0: U %.1f / residual %.1f units (bounds %.0f / %.0f)" % (name, nranks, max(u), max(r), bu, br))
+        assert max(u) <= bu and max(r) <= br, nranks
+    assert np.array_equal(F[0], j.F) and (F[1] != 0).all()      # load case 1 is nonzero in every row: every halo entry works from k = 1
+
+
+def test_the_sharded_cases_cut_where_they_are_meant_to(oracle, built_libs):
+    """What the cases of tests/test_gpu_sharded_precision.py are there for, on the oracle's pattern: every rank that owns rows has
+    entries across a cut, whatever the model and the rank count; cube6 on 2 ranks runs both lists of the split product on both
+    ranks ((1, 2) and (1, 2) interior / boundary slices), on 4 ranks no rank has an interior slice at all (the boundary launch
+    alone: (0, 1) (0, 2) (0, 1) (0, 2)), on 8 ranks ranks 0 and 4 own no row (block rows cut at 0 0 64 128 192 192 256 320 343).
+    perforated12 on 3 ranks: (7, 4) (0, 11) (5, 7); on 4: (5, 3) (0, 9) (0, 8) (2, 7)."""
+    from stan_amd import host
+    for name in P.CG_MODELS:
+        j, _A, csr = _model(oracle, name)
+        for nranks in SHARD_RANKS:
+            rank = _ranks_of(name, nranks)
+            halo = P.halo_entries(csr, rank)
+            owners = np.unique(rank)
+            census = P.slice_census(j, csr, nranks)
+            print("%s on %d ranks: %d halo entries of %d, slices (interior, boundary) %s" % (name, nranks, halo.sum(), halo.shape[0], census))
+            assert np.array_equal(np.unique(rank[P.rows_of(csr[0])[halo]]), owners)
+            assert all((i + b > 0) == (r in owners) for r, (i, b) in enumerate(census))
+            assert sum(i + b for i, b in census) == -(-j.xyz.shape[0] // 64)
+    j, _A, csr = _model(oracle, "cube6")
+    assert P.slice_census(j, csr, 2) == [(1, 2), (1, 2)]
+    assert any(i == 0 and b > 0 for i, b in P.slice_census(j, csr, 4))
+    assert any(i + b == 0 for i, b in P.slice_census(j, csr, 8))
+    assert list(host.partition_plan(j.node_index, j.conn, 8, 0)["row_starts"]) == [0, 0, 64, 128, 192, 192, 256, 320, 343]
+    assert np.array_equal(np.bincount(_ranks_of("cube6", 8), minlength=8) == 0, [True, False, False, False, True, False, False, False])
+
+
+class _HaloProduct:
+    """y = A^ x with the terms across a cut reading another vector than x: seen(x, previous) -- what the halo region holds when
+    the product runs; previous is the vector of the product before this one (the first product: x itself)."""
+
+    def __init__(self, A, halo, seen):
+        self.A, self.halo, self.seen, self.previous = A, halo, seen, None
+
+    def __call__(self, x):
+        xh = self.seen(x, x if self.previous is None else self.previous)
+        self.previous = x
+        return np.add.reduceat(self.A.a * np.where(self.halo, xh[self.A.col], x[self.A.col]), self.A.rowptr[:-1])
+
+
+def _first_over(u, r, bu, br):
+    return next((k + 1 for k in range(len(u)) if u[k] > bu or r[k] > br), None)
+
+
+@pytest.mark.parametrize("nranks", [2, 3, 4])
+@pytest.mark.parametrize("name", P.CG_MODELS)
+def test_sharded_mutants_exceed_the_bounds(oracle, built_libs, name, nranks):
+    """Stand-ins of what a sharded loop can get wrong and both transports would share, each in the float64 classic loop with
+    rank-ordered sums, each over the bound of the yardstick test at the stated k AND at every later k:
+      (a) the halo columns read the vector of the product before (a missing wait for the exchange): load case 0, from k = 2;
+      (b) the halo columns read float32(p): load case 0, from k = 1 -- the first product whose vector is not float32 in a halo
+          column: k = 2 for perforated12 on 2 ranks, whose cut lies where the job's load vector is still zero;
+      (c) p . A p without the last rank's partial: load case 0, from k = 1;
+      (d) ONE term a_ij x_j across a cut dropped -- the first, the middle and the last of the non-zero halo entries: load case 1,
+          from k = 1.  Under the job's own load vector the same mutant is first caught as late as k = 6 (cube6) or k = 9
+          (perforated12 on 4 ranks): the load reaches that row late.  That is why the device test runs load case 1 as well.
+    A bar of 1e-4 of max|U| passes (b) by three orders (1e9 units are 1e-7) and (d) where the dropped term is small (cube6 on 4
+    ranks, the middle entry: 4.2e11 units, 4.6e-5)."""
+    j, _A, csr = _model(oracle, name)
+    A = P.Scaled(*csr, T=np.float64)
+    F = P.load_cases(name)
+    rank = _ranks_of(name, nranks)
+    halo = P.halo_entries(csr, rank)
+    dot = P.rank_dot(rank, nranks)
+    owners = [int(r) for r in np.unique(rank)]
+
+    def run(lc, **kw):
+        bu, br = P.sharded_cg_bounds(name, lc)
+        u, r = _series(P.cg_iterates(A, F[lc], P.KMAX, dot=dot, **kw), *_cg_reference(oracle, name, lc))
+        first = _first_over(u, r, bu, br)
+        return first, first is not None and all(u[k] > bu or r[k] > br for k in range(first - 1, P.KMAX)), max(u), max(r)
+
+    f32 = lambda x, _previous: x.astype(np.float32).astype(np.float64)      # noqa: E731
+    # (b) can act from the first product whose vector is no float32 number in a column some non-zero halo entry reads
+    seen = []
+    P.cg_iterates(A, F[0], 3, dot=dot, mv=lambda x: (seen.append(x), A.mv(x))[1])
+    live = np.nonzero(halo & (A.a != 0))[0]
+    k_f32 = next(k + 1 for k, x in enumerate(seen) if (f32(x, None) != x)[A.col[live]].any())
+    assert k_f32 == (2 if (name, nranks) == ("perforated12", 2) else 1)
+    mutants = [("(a) stale halo", 0, 2, dict(mv=_HaloProduct(A, halo, lambda _x, previous: previous))),
+               ("(b) float32 halo", 0, k_f32, dict(mv=_HaloProduct(A, halo, f32))),
+               ("(c) p.Ap without the last rank", 0, 1, dict(pap=P.rank_dot(rank, nranks, ranks=owners[:-1])))]
+    late = []
+    for label, q in (("first", live[0]), ("middle", live[live.shape[0] // 2]), ("last", live[-1])):
+        B = P.Scaled(*csr, T=np.float64)
+        B.a[q] = 0.0
+        mutants.append(("(d) %s halo term dropped" % label, 1, 1, dict(mv=B.mv)))
+        late.append(run(0, mv=B.mv)[0])
+    for label, lc, k_stated, kw in mutants:
+        first, stays, wu, wr = run(lc, **kw)
+        print("%s on %d ranks, %s, load case %d: first iterate over the bound k = %s; worst U %.3g / residual %.3g units" %
+              (name, nranks, label, lc, first, wu, wr))
+        assert first == k_stated and stays, label
+    print("%s on %d ranks, (d) under load case 0: first caught at k = %s" % (name, nranks, late))
+    assert all(k is not None for k in late) and max(late) > 1
