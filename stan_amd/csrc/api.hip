@@ -21,47 +21,137 @@ struct dbuf {  // RAII device buffer filled from host memory
     int alloc(stan_ctx *ctx, size_t n) { owner = ctx; return stan_dmalloc(ctx, &p, n); }
 };
 
-// the device copies of a mesh's host arrays; an array the entry does not have (a null pointer) is skipped and stays null
+// the device copies of a mesh's host arrays: upload() takes the host view and yields the device view `dev`; an array the
+// entry does not have (a null pointer) is skipped and stays null.  The blocks are allocated in the order of upload()'s lines
+// and given back in the reverse order of the members: elem_type, red, elem_mat, conn, node_dof, disp, xyz.
 struct mesh_dbufs {
     dbuf<double> xyz, disp;
     dbuf<int32_t> node_dof, conn, elem_mat, red;
     dbuf<uint8_t> elem_type;
-    int upload(stan_ctx *ctx, int64_t n_nodes, const double *h_xyz, const double *h_disp, const int32_t *h_node_dof, int64_t n_elem,
-               const int32_t *h_conn, const int32_t *h_elem_mat, const uint8_t *h_elem_type, int64_t n_dof, const int32_t *h_red) {
-        if (h_xyz) STANCHK(xyz.upload(ctx, h_xyz, (size_t)n_nodes * 3));
-        if (h_disp) STANCHK(disp.upload(ctx, h_disp, (size_t)n_nodes * 3));
-        if (h_node_dof) STANCHK(node_dof.upload(ctx, h_node_dof, (size_t)n_nodes * 3));
-        if (h_conn) STANCHK(conn.upload(ctx, h_conn, (size_t)n_elem * 8));
-        if (h_elem_mat) STANCHK(elem_mat.upload(ctx, h_elem_mat, (size_t)n_elem));
-        if (h_elem_type) STANCHK(elem_type.upload(ctx, h_elem_type, (size_t)n_elem));
-        if (h_red) STANCHK(red.upload(ctx, h_red, (size_t)n_dof));
+    stan_mesh dev;
+    int upload(stan_ctx *ctx, const stan_mesh &h) {
+        if (h.xyz) STANCHK(xyz.upload(ctx, h.xyz, (size_t)h.n_nodes * 3));
+        if (h.disp) STANCHK(disp.upload(ctx, h.disp, (size_t)h.n_nodes * 3));
+        if (h.node_dof) STANCHK(node_dof.upload(ctx, h.node_dof, (size_t)h.n_nodes * 3));
+        if (h.conn) STANCHK(conn.upload(ctx, h.conn, (size_t)h.n_elem * 8));
+        if (h.elem_mat) STANCHK(elem_mat.upload(ctx, h.elem_mat, (size_t)h.n_elem));
+        if (h.elem_type) STANCHK(elem_type.upload(ctx, h.elem_type, (size_t)h.n_elem));
+        if (h.red) STANCHK(red.upload(ctx, h.red, (size_t)h.n_dof));
+        dev = h;   // the counts and mat_E_nu
+        dev.xyz = xyz.p; dev.disp = disp.p; dev.node_dof = node_dof.p; dev.conn = conn.p;
+        dev.elem_mat = elem_mat.p; dev.elem_type = elem_type.p; dev.red = red.p;
         return STAN_OK;
     }
 };
 
-// host range checks of a mesh's integers, in element order: material, type (with_type), the 8 nodes; then node_dof when
+// host range checks of a host view's integers, in element order: material, type (with_type), the 8 nodes; then node_dof when
 // given.  "<who>: <what>", with " at element N" appended when at_element.
-int mesh_range_check(stan_ctx *ctx, const char *who, bool at_element, bool with_type, int64_t n_nodes, int64_t n_elem,
-                     const int32_t *conn, const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat, int64_t n_dof,
-                     const int32_t *node_dof) {
+int mesh_range_check(stan_ctx *ctx, const char *who, bool at_element, bool with_type, const stan_mesh &m) {
     auto bad = [&](const char *why, int64_t e, int rc) {
         ctx->err = std::string(who) + ": " + why + (at_element && e >= 0 ? " at element " + std::to_string(e) : std::string());
         return rc;
     };
-    for (int64_t e = 0; e < n_elem; e++) {
-        if (elem_mat[e] < 0 || elem_mat[e] >= n_mat) return bad("elem_mat out of range", e, STAN_E_ARG);
-        if (with_type && elem_type[e] != STAN_HEX8_G1 && elem_type[e] != STAN_HEX8_G2) return bad("unsupported element type", e, STAN_E_ARG);
+    for (int64_t e = 0; e < m.n_elem; e++) {
+        if (m.elem_mat[e] < 0 || m.elem_mat[e] >= m.n_mat) return bad("elem_mat out of range", e, STAN_E_ARG);
+        if (with_type && m.elem_type[e] != STAN_HEX8_G1 && m.elem_type[e] != STAN_HEX8_G2) return bad("unsupported element type", e, STAN_E_ARG);
         for (int a = 0; a < 8; a++)
-            if (conn[e * 8 + a] < 0 || conn[e * 8 + a] >= n_nodes) return bad("node index out of range", e, STAN_E_ARG);
+            if (m.conn[e * 8 + a] < 0 || m.conn[e * 8 + a] >= m.n_nodes) return bad("node index out of range", e, STAN_E_ARG);
     }
-    if (node_dof)
-        for (int64_t k = 0; k < n_dof; k++)
-            if (node_dof[k] < 0 || node_dof[k] >= n_dof) return bad("DOF out of range", -1, STAN_E_DOF_LAYOUT);
+    if (m.node_dof)
+        for (int64_t k = 0; k < m.n_dof; k++)
+            if (m.node_dof[k] < 0 || m.node_dof[k] >= m.n_dof) return bad("DOF out of range", -1, STAN_E_DOF_LAYOUT);
+    return STAN_OK;
+}
+
+// the fixed DOFs of a reduction map: the reduced vectors (F, U) have n_dof minus this many entries
+int64_t count_fixed(const stan_mesh &m) {
+    int64_t n_fixed = 0;
+    for (int64_t k = 0; k < m.n_dof; k++) n_fixed += m.red[k] == -1;
+    return n_fixed;
+}
+
+// A rank of a sharded run only needs the elements that touch its block rows (boundary elements
+// are assembled by both owners): they are picked on the host, in element order (the
+// accumulation order of a row is the element order, so K keeps its bits), and only they go to
+// the device -- neither the upload nor the incidence scan of a rank grows with the ranks of
+// the others.  The node arrays stay whole: any node may be a halo column.
+struct shard_pick {
+    std::vector<int32_t> elems, conn, mat;   // the picked elements by their numbers in the whole model, ascending; their arrays
+    std::vector<uint8_t> type;
+    stan_mesh mesh;                          // host view: the picked element arrays, everything else as in the whole model
+};
+int pick_shard_elements(stan_ctx *ctx, const stan_mesh &m, shard_pick *out) {
+    const int64_t nb = m.n_dof / 3;
+    const int64_t r0 = stan_row_start(nb, ctx->nranks, ctx->rank), r1 = stan_row_start(nb, ctx->nranks, ctx->rank + 1);
+    for (int64_t e = 0; e < m.n_elem; e++) {
+        bool mine = false;
+        for (int a = 0; a < 8; a++) {
+            const int32_t nd = m.conn[e * 8 + a];
+            if (nd < 0 || nd >= m.n_nodes) {
+                ctx->err = "assemble: connectivity references a node index outside [0,n_nodes)";
+                return STAN_E_ARG;
+            }
+            const int64_t row = m.node_dof[3 * (int64_t)nd] / 3;   // a bad DOF layout is caught on the device
+            mine |= row >= r0 && row < r1;
+        }
+        if (mine) out->elems.push_back((int32_t)e);
+    }
+    const size_t n = out->elems.size();
+    out->conn.resize(n * 8); out->mat.resize(n); out->type.resize(n);
+    for (size_t i = 0; i < n; i++) {
+        memcpy(&out->conn[8 * i], m.conn + 8 * (int64_t)out->elems[i], 8 * sizeof(int32_t));
+        out->mat[i] = m.elem_mat[out->elems[i]];
+        out->type[i] = m.elem_type[out->elems[i]];
+    }
+    out->mesh = m;
+    out->mesh.n_elem = (int64_t)n;
+    out->mesh.conn = out->conn.data(); out->mesh.elem_mat = out->mat.data(); out->mesh.elem_type = out->type.data();
     return STAN_OK;
 }
 }  // namespace
 
 void stan_set_global_error(const std::string &msg) { g_err = msg; }
+
+// ---- the host entries of one context, behind the argument checks of the public entries (a group's ranks start here) ----
+int stan_assemble_host(stan_ctx *ctx, const stan_mesh &whole, stan_matrix **outK) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    // (not mesh_range_check: a foreign element type is STAN_E_UNSUPPORTED here, the connectivity is left to the pick or the device)
+    auto bad = [&](const char *why, int64_t e, int rc) { ctx->err = std::string("assemble_hex8: ") + why + " at element " + std::to_string(e); return rc; };
+    for (int64_t e = 0; e < whole.n_elem; e++) {
+        if (whole.elem_mat[e] < 0 || whole.elem_mat[e] >= whole.n_mat) return bad("elem_mat out of range", e, STAN_E_ARG);
+        if (whole.elem_type[e] != STAN_HEX8_G1 && whole.elem_type[e] != STAN_HEX8_G2) return bad("unsupported element type", e, STAN_E_UNSUPPORTED);
+    }
+    shard_pick pick;
+    const bool shard = ctx->nranks > 1 && whole.n_elem > 0;
+    if (shard) STANCHK(pick_shard_elements(ctx, whole, &pick));
+    mesh_dbufs bufs;
+    STANCHK(bufs.upload(ctx, shard ? pick.mesh : whole));
+    const int rc = stan_assemble_device(ctx, bufs.dev, outK);
+    if (rc == STAN_OK) (*outK)->n_elem_scanned = bufs.dev.n_elem;
+    if (rc == STAN_E_DETJ && shard && ctx->bad_elem >= 0 && ctx->bad_elem < (int64_t)pick.elems.size()) {
+        ctx->bad_elem = pick.elems[(size_t)ctx->bad_elem];   // element number of the whole model
+        ctx->err = "det J == 0 in element " + std::to_string(ctx->bad_elem) + " (MatrixST.Inverse would throw)";
+    }
+    // the uploads above are stream-ordered with the assembly; the host vectors must outlive them
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return rc;
+}
+
+int stan_recover_host(stan_ctx *ctx, const stan_mesh &m, double *strain, double *stress) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    STANCHK(mesh_range_check(ctx, "recover_hex8", false, false, m));
+    mesh_dbufs bufs; dbuf<double> de, ds;
+    STANCHK(bufs.upload(ctx, m));
+    STANCHK(de.alloc(ctx, (size_t)m.n_elem * 48));
+    STANCHK(ds.alloc(ctx, (size_t)m.n_elem * 48));
+    STANCHK(stan_recover_device(ctx, bufs.dev, de.p, ds.p));
+    if (m.n_elem) {
+        HIPCHK(ctx, hipMemcpyAsync(strain, de.p, (size_t)m.n_elem * 48 * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(stress, ds.p, (size_t)m.n_elem * 48 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return STAN_OK;
+}
 
 extern "C" {
 
@@ -290,8 +380,10 @@ int stan_hip_assemble_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *d_x
         return STAN_E_ARG;
     STAN_NO_GROUP(ctx, "assemble_hex8_dev (device pointers belong to one device)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return stan_assemble_device(ctx, n_nodes, d_xyz, d_node_dof, n_elem, d_conn, d_elem_mat,
-                                d_elem_type, n_mat, mat_E_nu, n_dof, d_red, outK);
+    const stan_mesh d{.n_nodes = n_nodes, .n_elem = n_elem, .n_dof = n_dof, .n_mat = n_mat, .xyz = d_xyz,
+                      .node_dof = d_node_dof, .conn = d_conn, .elem_mat = d_elem_mat, .elem_type = d_elem_type, .red = d_red,
+                      .mat_E_nu = mat_E_nu};
+    return stan_assemble_device(ctx, d, outK);
 }
 
 int stan_hip_assemble_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz,
@@ -304,70 +396,9 @@ int stan_hip_assemble_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz,
         if (ctx) ctx->err = "assemble_hex8: null or empty argument";
         return STAN_E_ARG;
     }
-    if (ctx->group)
-        return stan_group_assemble(ctx, n_nodes, xyz, node_dof, n_elem, conn, elem_mat, elem_type, n_mat,
-                                   mat_E_nu, n_dof, red, outK);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    for (int64_t e = 0; e < n_elem; e++) {
-        if (elem_mat[e] < 0 || elem_mat[e] >= n_mat) {
-            ctx->err = "assemble_hex8: elem_mat out of range at element " + std::to_string(e);
-            return STAN_E_ARG;
-        }
-        if (elem_type[e] != STAN_HEX8_G1 && elem_type[e] != STAN_HEX8_G2) {
-            ctx->err = "assemble_hex8: unsupported element type at element " + std::to_string(e);
-            return STAN_E_UNSUPPORTED;
-        }
-    }
-    // A rank of a sharded run only needs the elements that touch its block rows (boundary elements
-    // are assembled by both owners): they are picked on the host, in element order (the
-    // accumulation order of a row is the element order, so K keeps its bits), and only they go to
-    // the device -- neither the upload nor the incidence scan of a rank grows with the ranks of
-    // the others.  The node arrays stay whole: any node may be a halo column.
-    std::vector<int32_t> sub, conn_s, mat_s;
-    std::vector<uint8_t> type_s;
-    const bool shard = ctx->nranks > 1 && n_elem > 0;
-    if (shard) {
-        const int64_t nb = n_dof / 3;
-        const int64_t r0 = stan_row_start(nb, ctx->nranks, ctx->rank), r1 = stan_row_start(nb, ctx->nranks, ctx->rank + 1);
-        for (int64_t e = 0; e < n_elem; e++) {
-            bool mine = false;
-            for (int a = 0; a < 8; a++) {
-                const int32_t nd = conn[e * 8 + a];
-                if (nd < 0 || nd >= n_nodes) {
-                    ctx->err = "assemble: connectivity references a node index outside [0,n_nodes)";
-                    return STAN_E_ARG;
-                }
-                const int64_t row = node_dof[3 * (int64_t)nd] / 3;   // a bad DOF layout is caught on the device
-                mine |= row >= r0 && row < r1;
-            }
-            if (mine) sub.push_back((int32_t)e);
-        }
-        conn_s.resize(sub.size() * 8); mat_s.resize(sub.size()); type_s.resize(sub.size());
-        for (size_t i = 0; i < sub.size(); i++) {
-            memcpy(&conn_s[8 * i], conn + 8 * (int64_t)sub[i], 8 * sizeof(int32_t));
-            mat_s[i] = elem_mat[sub[i]];
-            type_s[i] = elem_type[sub[i]];
-        }
-        conn = conn_s.data(); elem_mat = mat_s.data(); elem_type = type_s.data();
-        n_elem = (int64_t)sub.size();
-    }
-    dbuf<double> dx; dbuf<int32_t> dd, dc, dm, dr; dbuf<uint8_t> dt;
-    STANCHK(dx.upload(ctx, xyz, (size_t)n_nodes * 3));
-    STANCHK(dd.upload(ctx, node_dof, (size_t)n_nodes * 3));
-    STANCHK(dc.upload(ctx, conn, (size_t)n_elem * 8));
-    STANCHK(dm.upload(ctx, elem_mat, (size_t)n_elem));
-    STANCHK(dt.upload(ctx, elem_type, (size_t)n_elem));
-    STANCHK(dr.upload(ctx, red, (size_t)n_dof));
-    const int rc = stan_assemble_device(ctx, n_nodes, dx.p, dd.p, n_elem, dc.p, dm.p, dt.p, n_mat, mat_E_nu,
-                                        n_dof, dr.p, outK);
-    if (rc == STAN_OK) (*outK)->n_elem_scanned = n_elem;
-    if (rc == STAN_E_DETJ && shard && ctx->bad_elem >= 0 && ctx->bad_elem < (int64_t)sub.size()) {
-        ctx->bad_elem = sub[(size_t)ctx->bad_elem];   // element number of the whole model
-        ctx->err = "det J == 0 in element " + std::to_string(ctx->bad_elem) + " (MatrixST.Inverse would throw)";
-    }
-    // the uploads above are stream-ordered with the assembly; the host vectors must outlive them
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return rc;
+    const stan_mesh m{.n_nodes = n_nodes, .n_elem = n_elem, .n_dof = n_dof, .n_mat = n_mat, .xyz = xyz, .node_dof = node_dof,
+                      .conn = conn, .elem_mat = elem_mat, .elem_type = elem_type, .red = red, .mat_E_nu = mat_E_nu};
+    return ctx->group ? stan_group_assemble(ctx, m, outK) : stan_assemble_host(ctx, m, outK);
 }
 
 void stan_hip_matrix_free(stan_matrix *K) {
@@ -475,8 +506,9 @@ int stan_hip_recover_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *d_xy
         return STAN_E_ARG;
     STAN_NO_GROUP(ctx, "recover_hex8_dev (device pointers belong to one device)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return stan_recover_device(ctx, n_nodes, d_xyz, d_disp, n_elem, d_conn, d_elem_mat, d_elem_type,
-                               n_mat, mat_E_nu, d_strain, d_stress, nullptr, nullptr, nullptr);
+    const stan_mesh d{.n_nodes = n_nodes, .n_elem = n_elem, .n_mat = n_mat, .xyz = d_xyz, .disp = d_disp, .conn = d_conn,
+                      .elem_mat = d_elem_mat, .elem_type = d_elem_type, .mat_E_nu = mat_E_nu};
+    return stan_recover_device(ctx, d, d_strain, d_stress);
 }
 
 int stan_hip_recover_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const double *disp,
@@ -486,23 +518,9 @@ int stan_hip_recover_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz, con
     if (!ctx || !xyz || !disp || !mat_E_nu || n_nodes <= 0 || n_mat <= 0 || n_elem < 0 ||
         (n_elem > 0 && (!conn || !elem_mat || !elem_type || !strain || !stress)))
         return STAN_E_ARG;
-    if (ctx->group)
-        return stan_group_recover(ctx, n_nodes, xyz, disp, n_elem, conn, elem_mat, elem_type, n_mat, mat_E_nu,
-                                  strain, stress);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    STANCHK(mesh_range_check(ctx, "recover_hex8", false, false, n_nodes, n_elem, conn, elem_mat, elem_type, n_mat, 0, nullptr));
-    mesh_dbufs m; dbuf<double> de, ds;
-    STANCHK(m.upload(ctx, n_nodes, xyz, disp, nullptr, n_elem, conn, elem_mat, elem_type, 0, nullptr));
-    STANCHK(de.alloc(ctx, (size_t)n_elem * 48));
-    STANCHK(ds.alloc(ctx, (size_t)n_elem * 48));
-    STANCHK(stan_recover_device(ctx, n_nodes, m.xyz.p, m.disp.p, n_elem, m.conn.p, m.elem_mat.p, m.elem_type.p, n_mat, mat_E_nu,
-                                de.p, ds.p, nullptr, nullptr, nullptr));
-    if (n_elem) {
-        HIPCHK(ctx, hipMemcpyAsync(strain, de.p, (size_t)n_elem * 48 * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipMemcpyAsync(stress, ds.p, (size_t)n_elem * 48 * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return STAN_OK;
+    const stan_mesh m{.n_nodes = n_nodes, .n_elem = n_elem, .n_mat = n_mat, .xyz = xyz, .disp = disp, .conn = conn,
+                      .elem_mat = elem_mat, .elem_type = elem_type, .mat_E_nu = mat_E_nu};
+    return ctx->group ? stan_group_recover(ctx, m, strain, stress) : stan_recover_host(ctx, m, strain, stress);
 }
 
 // ---- results kept on the device(s) (stan_hip_recover_hex8_keep) ------------------------------------------------------
@@ -520,16 +538,15 @@ struct map_stage {
     ~map_stage() { if (p) hipHostFree(p); }
 };
 thread_local map_stage g_stage;
-int recover_keep_one(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const double *disp, int64_t n_elem, const int32_t *conn,
-                     const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat, const double *mat_E_nu, int64_t e_base,
-                     stan_results::part *out) {
+// m: the elements from e_base on of the whole model (a host view)
+int recover_keep_one(stan_ctx *ctx, const stan_mesh &m, int64_t e_base, stan_results::part *out) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    STANCHK(mesh_range_check(ctx, "recover_hex8", false, false, n_nodes, n_elem, conn, elem_mat, elem_type, n_mat, 0, nullptr));
-    mesh_dbufs m;
-    STANCHK(m.upload(ctx, n_nodes, xyz, disp, nullptr, n_elem, conn, elem_mat, elem_type, 0, nullptr));
+    STANCHK(mesh_range_check(ctx, "recover_hex8", false, false, m));
+    mesh_dbufs bufs;
+    STANCHK(bufs.upload(ctx, m));
     // plain device memory, owned by the results object (it may outlive the context's pool)
     double *de = nullptr, *ds = nullptr;
-    const size_t bytes = (size_t)(n_elem > 0 ? n_elem : 1) * 48 * 8;
+    const size_t bytes = (size_t)(m.n_elem > 0 ? m.n_elem : 1) * 48 * 8;
     auto both = [&]() {
         if (hipMalloc((void **)&de, bytes) == hipSuccess && hipMalloc((void **)&ds, bytes) == hipSuccess) return true;
         (void)hipGetLastError();
@@ -550,11 +567,10 @@ int recover_keep_one(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const do
             return STAN_E_ALLOC;
         }
     }
-    int rc = stan_recover_device(ctx, n_nodes, m.xyz.p, m.disp.p, n_elem, m.conn.p, m.elem_mat.p, m.elem_type.p, n_mat, mat_E_nu, de, ds,
-                                 nullptr, nullptr, nullptr);
+    int rc = stan_recover_device(ctx, bufs.dev, de, ds);
     if (rc == STAN_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = STAN_E_HIP;
     if (rc != STAN_OK) { hipFree(de); hipFree(ds); return rc; }
-    *out = stan_results::part{ctx->device, e_base, e_base + n_elem, de, ds};
+    *out = stan_results::part{ctx->device, e_base, e_base + m.n_elem, de, ds};
     return STAN_OK;
 }
 }  // namespace
@@ -567,6 +583,8 @@ int stan_hip_recover_hex8_keep(stan_ctx *ctx, int64_t n_nodes, const double *xyz
         (n_elem > 0 && (!conn || !elem_mat || !elem_type)))
         return STAN_E_ARG;
     *out = nullptr;
+    const stan_mesh m{.n_nodes = n_nodes, .n_elem = n_elem, .n_mat = n_mat, .xyz = xyz, .disp = disp, .conn = conn,
+                      .elem_mat = elem_mat, .elem_type = elem_type, .mat_E_nu = mat_E_nu};
     stan_results *res = new stan_results();
     res->n_elem = n_elem;
     int rc = STAN_OK;
@@ -577,18 +595,13 @@ int stan_hip_recover_hex8_keep(stan_ctx *ctx, int64_t n_nodes, const double *xyz
             const int64_t e0 = n_elem * r / n, e1 = n_elem * (r + 1) / n;
             res->parts[(size_t)r] = stan_results::part{c->device, e0, e0, nullptr, nullptr};
             if (e1 <= e0) return (int)STAN_OK;
-            const int e = recover_keep_one(c, n_nodes, xyz, disp, e1 - e0, conn + 8 * e0, elem_mat + e0, elem_type + e0, n_mat,
-                                           mat_E_nu, e0, &res->parts[(size_t)r]);
-            if (e == STAN_E_UNSUPPORTED || e == STAN_E_DETJ) {   // element numbers of the whole model
-                ctx->bad_elem = c->bad_elem + e0;
-                c->err = (e == STAN_E_DETJ ? "det J == 0 in element " : "stress recovery: HEX8_G1 element ") + std::to_string(ctx->bad_elem) +
-                         (e == STAN_E_DETJ ? "" : " (the reference throws: N has one row, Element.cs:242)");
-            }
+            const int e = recover_keep_one(c, m.chunk(e0, e1), e0, &res->parts[(size_t)r]);
+            stan_chunk_bad_element(ctx, c, e, e0);
             return e;
         });
     } else {
         res->parts.assign(1, stan_results::part{ctx->device, 0, 0, nullptr, nullptr});
-        if (n_elem > 0) rc = recover_keep_one(ctx, n_nodes, xyz, disp, n_elem, conn, elem_mat, elem_type, n_mat, mat_E_nu, 0, &res->parts[0]);
+        if (n_elem > 0) rc = recover_keep_one(ctx, m, 0, &res->parts[0]);
     }
     if (rc != STAN_OK) { stan_hip_results_free(res); return rc; }
     *out = res;
@@ -666,6 +679,24 @@ int result_scalars(stan_ctx *ctx, const char *who, int64_t n_nodes, const double
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return STAN_OK;
 }
+// Compute_NodalForces and the R assembly (recovery.hip) on one context, behind the entry's checks
+int nodal_forces_host(stan_ctx *ctx, const stan_mesh &m, double *elem_forces, double *R) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    STANCHK(mesh_range_check(ctx, "nodal_forces_hex8", false, false, m));
+    mesh_dbufs bufs; dbuf<double> df, dR;
+    STANCHK(bufs.upload(ctx, m));
+    if (elem_forces) STANCHK(df.alloc(ctx, (size_t)m.n_elem * 24));
+    if (R) {
+        STANCHK(dR.alloc(ctx, (size_t)m.n_dof));
+        HIPCHK(ctx, hipMemsetAsync(dR.p, 0, (size_t)m.n_dof * 8, ctx->stream));
+    }
+    STANCHK(stan_recover_device(ctx, bufs.dev, nullptr, nullptr, elem_forces ? df.p : nullptr, R ? dR.p : nullptr));
+    if (elem_forces && m.n_elem)
+        HIPCHK(ctx, hipMemcpyAsync(elem_forces, df.p, (size_t)m.n_elem * 24 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (R) HIPCHK(ctx, hipMemcpyAsync(R, dR.p, (size_t)m.n_dof * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return STAN_OK;
+}
 }  // namespace
 extern "C" {
 
@@ -709,27 +740,11 @@ int stan_hip_nodal_forces_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz
     if (!ctx || !xyz || !disp || !node_dof || !mat_E_nu || n_nodes <= 0 || n_mat <= 0 || n_elem < 0 ||
         n_dof != n_nodes * 3 || (!elem_forces && !R) || (n_elem > 0 && (!conn || !elem_mat || !elem_type)))
         return STAN_E_ARG;
+    const stan_mesh m{.n_nodes = n_nodes, .n_elem = n_elem, .n_dof = n_dof, .n_mat = n_mat, .xyz = xyz, .disp = disp,
+                      .node_dof = node_dof, .conn = conn, .elem_mat = elem_mat, .elem_type = elem_type, .mat_E_nu = mat_E_nu};
     if (ctx->group)   // R is an all-element sum: one device (rank 0); its error text follows the handle
-        return stan_group_rank0_call(ctx, [&](stan_ctx *c) {
-            return stan_hip_nodal_forces_hex8(c, n_nodes, xyz, disp, node_dof, n_elem, conn, elem_mat, elem_type, n_mat,
-                                              mat_E_nu, n_dof, elem_forces, R);
-        });
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    STANCHK(mesh_range_check(ctx, "nodal_forces_hex8", false, false, n_nodes, n_elem, conn, elem_mat, elem_type, n_mat, n_dof, node_dof));
-    mesh_dbufs m; dbuf<double> df, dR;
-    STANCHK(m.upload(ctx, n_nodes, xyz, disp, node_dof, n_elem, conn, elem_mat, elem_type, 0, nullptr));
-    if (elem_forces) STANCHK(df.alloc(ctx, (size_t)n_elem * 24));
-    if (R) {
-        STANCHK(dR.alloc(ctx, (size_t)n_dof));
-        HIPCHK(ctx, hipMemsetAsync(dR.p, 0, (size_t)n_dof * 8, ctx->stream));
-    }
-    STANCHK(stan_recover_device(ctx, n_nodes, m.xyz.p, m.disp.p, n_elem, m.conn.p, m.elem_mat.p, m.elem_type.p, n_mat, mat_E_nu,
-                                nullptr, nullptr, m.node_dof.p, elem_forces ? df.p : nullptr, R ? dR.p : nullptr));
-    if (elem_forces && n_elem)
-        HIPCHK(ctx, hipMemcpyAsync(elem_forces, df.p, (size_t)n_elem * 24 * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (R) HIPCHK(ctx, hipMemcpyAsync(R, dR.p, (size_t)n_dof * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return STAN_OK;
+        return stan_group_rank0_call(ctx, [&](stan_ctx *c) { return nodal_forces_host(c, m, elem_forces, R); });
+    return nodal_forces_host(ctx, m, elem_forces, R);
 }
 
 // f_int = sum_e int B^T D B u_e dV, reactions and the equilibrium sums (internal_forces.hip).  One device, one rank: a node on
@@ -756,8 +771,10 @@ int stan_hip_internal_forces_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const doub
         return STAN_E_ARG;
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return stan_internal_forces_device(ctx, n_nodes, d_xyz, d_disp, d_node_dof, n_elem, d_conn, d_elem_mat, d_elem_type, n_mat,
-                                       mat_E_nu, n_dof, d_red, d_F, d_f_int, d_reaction, (stan_equilibrium *)eq);
+    const stan_mesh d{.n_nodes = n_nodes, .n_elem = n_elem, .n_dof = n_dof, .n_mat = n_mat, .xyz = d_xyz, .disp = d_disp,
+                      .node_dof = d_node_dof, .conn = d_conn, .elem_mat = d_elem_mat, .elem_type = d_elem_type, .red = d_red,
+                      .mat_E_nu = mat_E_nu};
+    return stan_internal_forces_device(ctx, d, d_F, d_f_int, d_reaction, (stan_equilibrium *)eq);
 }
 
 int stan_hip_internal_forces_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const double *disp,
@@ -772,19 +789,19 @@ int stan_hip_internal_forces_hex8(stan_ctx *ctx, int64_t n_nodes, const double *
         return STAN_E_ARG;
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    const stan_mesh m{.n_nodes = n_nodes, .n_elem = n_elem, .n_dof = n_dof, .n_mat = n_mat, .xyz = xyz, .disp = disp,
+                      .node_dof = node_dof, .conn = conn, .elem_mat = elem_mat, .elem_type = elem_type, .red = red,
+                      .mat_E_nu = mat_E_nu};
     // the checks of stan_hip_nodal_forces_hex8, with the element named (the device repeats them for the _dev entry)
-    STANCHK(mesh_range_check(ctx, "internal_forces_hex8", true, true, n_nodes, n_elem, conn, elem_mat, elem_type, n_mat, n_dof, node_dof));
-    int64_t n_fixed = 0;
-    for (int64_t k = 0; k < n_dof; k++) n_fixed += red[k] == -1;
-    const size_t N = (size_t)(n_dof - n_fixed);
-    mesh_dbufs m; dbuf<double> dF, dfi, dre;
-    STANCHK(m.upload(ctx, n_nodes, xyz, disp, node_dof, n_elem, conn, elem_mat, elem_type, n_dof, red));
+    STANCHK(mesh_range_check(ctx, "internal_forces_hex8", true, true, m));
+    const size_t N = (size_t)(n_dof - count_fixed(m));
+    mesh_dbufs bufs; dbuf<double> dF, dfi, dre;
+    STANCHK(bufs.upload(ctx, m));
     if (F) STANCHK(dF.upload(ctx, F, N));
     if (f_int) STANCHK(dfi.alloc(ctx, (size_t)n_dof));
     if (reaction) STANCHK(dre.alloc(ctx, (size_t)n_dof));
-    const int rc = stan_internal_forces_device(ctx, n_nodes, m.xyz.p, m.disp.p, m.node_dof.p, n_elem, m.conn.p, m.elem_mat.p, m.elem_type.p,
-                                               n_mat, mat_E_nu, n_dof, m.red.p,
-                                               F ? dF.p : nullptr, f_int ? dfi.p : nullptr, reaction ? dre.p : nullptr, (stan_equilibrium *)eq);
+    const int rc = stan_internal_forces_device(ctx, bufs.dev, F ? dF.p : nullptr, f_int ? dfi.p : nullptr, reaction ? dre.p : nullptr,
+                                               (stan_equilibrium *)eq);
     if (rc == STAN_OK) {
         if (f_int) HIPCHK(ctx, hipMemcpyAsync(f_int, dfi.p, (size_t)n_dof * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (reaction) HIPCHK(ctx, hipMemcpyAsync(reaction, dre.p, (size_t)n_dof * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -810,8 +827,10 @@ int stan_hip_load_vector_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *
         return STAN_E_ARG;
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return stan_load_vector_device(ctx, n_nodes, d_xyz, d_node_dof, n_elem, d_conn, d_elem_mat, d_elem_type, n_mat, mat_E_nu, n_dof,
-                                   d_red, mat_body, n_faces, d_face_elem, d_face_id, d_face_pressure, d_disp0, d_F, d_F_solve,
+    const stan_mesh d{.n_nodes = n_nodes, .n_elem = n_elem, .n_dof = n_dof, .n_mat = n_mat, .xyz = d_xyz,
+                      .node_dof = d_node_dof, .conn = d_conn, .elem_mat = d_elem_mat, .elem_type = d_elem_type, .red = d_red,
+                      .mat_E_nu = mat_E_nu};
+    return stan_load_vector_device(ctx, d, mat_body, n_faces, d_face_elem, d_face_id, d_face_pressure, d_disp0, d_F, d_F_solve,
                                    d_load_full, (stan_load_sums *)sums);
 }
 
@@ -828,23 +847,22 @@ int stan_hip_load_vector_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz,
         return STAN_E_ARG;
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    const stan_mesh m{.n_nodes = n_nodes, .n_elem = n_elem, .n_dof = n_dof, .n_mat = n_mat, .xyz = xyz, .node_dof = node_dof,
+                      .conn = conn, .elem_mat = elem_mat, .elem_type = elem_type, .red = red, .mat_E_nu = mat_E_nu};
     // the length of F is fixed by the reduction map alone; every other integer is checked on the device (loads.hip)
-    int64_t n_fixed = 0;
-    for (int64_t k = 0; k < n_dof; k++) n_fixed += red[k] == -1;
-    const size_t N = (size_t)(n_dof - n_fixed);
-    mesh_dbufs m; dbuf<double> dp, dF, dFs, dl; dbuf<int32_t> dfe; dbuf<uint8_t> dfi;
-    STANCHK(m.upload(ctx, n_nodes, xyz, nullptr, node_dof, n_elem, conn, elem_mat, elem_type, n_dof, red));
+    const size_t N = (size_t)(n_dof - count_fixed(m));
+    mesh_dbufs bufs; dbuf<double> dp, dF, dFs, dl; dbuf<int32_t> dfe; dbuf<uint8_t> dfi;
+    STANCHK(bufs.upload(ctx, m));
     if (n_faces > 0) {
         STANCHK(dfe.upload(ctx, face_elem, (size_t)n_faces));
         STANCHK(dfi.upload(ctx, face_id, (size_t)n_faces));
         STANCHK(dp.upload(ctx, face_pressure, (size_t)n_faces));
     }
-    if (disp0) STANCHK(m.disp.upload(ctx, disp0, (size_t)n_nodes * 3));
+    if (disp0) STANCHK(bufs.disp.upload(ctx, disp0, (size_t)n_nodes * 3));   // (behind the face lists: the order of the blocks)
     if (F) STANCHK(dF.upload(ctx, F, N));
     if (F_solve) STANCHK(dFs.alloc(ctx, N));
     if (load_full) STANCHK(dl.alloc(ctx, (size_t)n_dof));
-    const int rc = stan_load_vector_device(ctx, n_nodes, m.xyz.p, m.node_dof.p, n_elem, m.conn.p, m.elem_mat.p, m.elem_type.p, n_mat,
-                                           mat_E_nu, n_dof, m.red.p, mat_body, n_faces, dfe.p, dfi.p, dp.p, m.disp.p, F ? dF.p : nullptr,
+    const int rc = stan_load_vector_device(ctx, bufs.dev, mat_body, n_faces, dfe.p, dfi.p, dp.p, bufs.disp.p, F ? dF.p : nullptr,
                                            F_solve ? dFs.p : nullptr, load_full ? dl.p : nullptr, (stan_load_sums *)sums);
     if (rc == STAN_OK) {
         if (F && N) HIPCHK(ctx, hipMemcpyAsync(F, dF.p, N * 8, hipMemcpyDeviceToHost, ctx->stream));

@@ -909,10 +909,7 @@ k_ke_batch(int64_t n, const double *xyz8, double lam, double G, const uint8_t *t
 // decides which block a later allocation gets, so no phase frees on its own.
 struct assembly_run {
     stan_ctx *ctx;
-    int64_t n_nodes; const double *d_xyz; const int32_t *d_node_dof;   // the inputs, in the order of the entry point
-    int64_t n_elem; const int32_t *d_conn, *d_elem_mat; const uint8_t *d_elem_type;
-    int32_t n_mat; const double *mat_E_nu;
-    int64_t n_dof; const int32_t *d_red;
+    const stan_mesh m;   // the inputs: a device view with node_dof and red
     stan_matrix *K = nullptr;
     hipStream_t st = ctx->stream;
     int64_t *d_status = ctx->d_status;
@@ -937,9 +934,9 @@ struct assembly_run {
 };
 
 int assembly_run::partition() {
-    K->n_dof = n_dof;
-    K->nb_glob = nb = n_dof / 3;
-    K->n_elem_scanned = n_elem;
+    K->n_dof = m.n_dof;
+    K->nb_glob = nb = m.n_dof / 3;
+    K->n_elem_scanned = m.n_elem;
     // contiguous block-row partition, cut on slice boundaries
     K->row_starts.resize(ctx->nranks + 1);
     for (int r = 0; r <= ctx->nranks; r++) K->row_starts[r] = stan_row_start(nb, ctx->nranks, r);
@@ -951,31 +948,31 @@ int assembly_run::partition() {
     static const long long init = 0x7fffffffffffffffLL;
     HIPCHK(ctx, hipMemcpyAsync(d_status + SS_BAD_ELEM, &init, 8, hipMemcpyHostToDevice, st));
     // materials -> (lambda, G)
-    lamG.resize(2 * (size_t)n_mat);
-    for (int m = 0; m < n_mat; m++) stan_lame(mat_E_nu[2 * m], mat_E_nu[2 * m + 1], &lamG[2 * m], &lamG[2 * m + 1]);
+    lamG.resize(2 * (size_t)m.n_mat);
+    for (int i = 0; i < m.n_mat; i++) stan_lame(m.mat_E_nu[2 * i], m.mat_E_nu[2 * i + 1], &lamG[2 * i], &lamG[2 * i + 1]);
     STANCHK(tmp.alloc(&d_lamG, lamG.size()));
     HIPCHK(ctx, hipMemcpyAsync(d_lamG, lamG.data(), lamG.size() * 8, hipMemcpyHostToDevice, st));
     return STAN_OK;
 }
 
 int assembly_run::incidence() {
-    STANCHK(tmp.alloc(&d_perm, (size_t)n_nodes));
+    STANCHK(tmp.alloc(&d_perm, (size_t)m.n_nodes));
     STANCHK(stan_dmalloc(ctx, &K->d_fixmask, (size_t)nb));
-    STANCHK(stan_dmalloc(ctx, &K->d_red, (size_t)n_dof));
+    STANCHK(stan_dmalloc(ctx, &K->d_red, (size_t)m.n_dof));
     HIPCHK(ctx, hipMemsetAsync(K->d_fixmask, 0, (size_t)nb, st));
-    HIPCHK(ctx, hipMemcpyAsync(K->d_red, d_red, (size_t)n_dof * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(K->d_red, m.red, (size_t)m.n_dof * 4, hipMemcpyDeviceToDevice, st));
     STANCHK(tmp.alloc(&d_xrow, (size_t)nb * 3));
-    STANCHK(tmp.alloc(&d_crow, (size_t)(n_elem > 0 ? n_elem * 8 : 1)));
-    hipLaunchKernelGGL(k_perm, dim3(nblk(n_nodes, 256)), dim3(256), 0, st, n_nodes, nb, d_node_dof,
-                       d_red, d_xyz, d_perm, K->d_fixmask, d_xrow, d_status);
+    STANCHK(tmp.alloc(&d_crow, (size_t)(m.n_elem > 0 ? m.n_elem * 8 : 1)));
+    hipLaunchKernelGGL(k_perm, dim3(nblk(m.n_nodes, 256)), dim3(256), 0, st, m.n_nodes, nb, m.node_dof,
+                       m.red, m.xyz, d_perm, K->d_fixmask, d_xrow, d_status);
     // incidence lists of owned rows
     int32_t *d_cnt;
     STANCHK(tmp.alloc(&d_cnt, (size_t)nrows_pad + 1));
     STANCHK(tmp.alloc(&d_ptr, (size_t)nrows_pad + 2));
     HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, ((size_t)nrows_pad + 1) * 4, st));
-    if (n_elem > 0)
-        hipLaunchKernelGGL(k_count_incident, dim3(nblk(n_elem * 8, 256)), dim3(256), 0, st, n_elem,
-                           n_nodes, d_conn, d_perm, r0, r1, d_cnt, d_crow, d_status);
+    if (m.n_elem > 0)
+        hipLaunchKernelGGL(k_count_incident, dim3(nblk(m.n_elem * 8, 256)), dim3(256), 0, st, m.n_elem,
+                           m.n_nodes, m.conn, d_perm, r0, r1, d_cnt, d_crow, d_status);
     if (nrows_pad > 0)
         hipLaunchKernelGGL(k_max_incident, dim3(nblk(nrows_pad, 256)), dim3(256), 0, st, nrows_pad, d_cnt, BIG_LDS_INTS, d_status);
     STANCHK(stan_scan_total(ctx, d_cnt, d_ptr, nrows_pad, SS_H_NINC));
@@ -995,8 +992,8 @@ int assembly_run::incidence() {
     }
     STANCHK(tmp.alloc(&d_list, (size_t)n_inc));
     HIPCHK(ctx, hipMemsetAsync(d_cnt, 0, ((size_t)nrows_pad + 1) * 4, st));
-    if (n_elem > 0)
-        hipLaunchKernelGGL(k_fill_incident, dim3(nblk(n_elem * 8, 256)), dim3(256), 0, st, n_elem,
+    if (m.n_elem > 0)
+        hipLaunchKernelGGL(k_fill_incident, dim3(nblk(m.n_elem * 8, 256)), dim3(256), 0, st, m.n_elem,
                            d_crow, r0, r1, d_ptr, d_cnt, d_list);
     return STAN_OK;
 }
@@ -1078,14 +1075,14 @@ int assembly_run::layout() {
 int assembly_run::numeric() {
     if (ctx->assembly_mode == 1) {
         if (ctx->nranks > 1) { ctx->err = "assembly mode 1 (colour scatter) is single-rank only"; return STAN_E_UNSUPPORTED; }
-        STANCHK(stan_assemble_colour_scatter(ctx, K, n_elem, d_conn, d_perm, d_xyz, d_elem_mat, d_elem_type,
+        STANCHK(stan_assemble_colour_scatter(ctx, K, m.n_elem, m.conn, d_perm, m.xyz, m.elem_mat, m.elem_type,
                                              d_lamG, d_ptr, d_list, (long long *)(d_status + SS_BAD_ELEM)));
     } else {
         ctx->prof_colours = 0;
         numeric_args A;
         A.nloc = nloc; A.r0 = r0; A.r1 = r1; A.nhalo = K->nhalo;
         A.ptr = d_ptr; A.list = d_list; A.crow = d_crow; A.xrow = d_xrow;
-        A.elem_mat = d_elem_mat; A.elem_type = d_elem_type; A.mat_lamG = d_lamG;
+        A.elem_mat = m.elem_mat; A.elem_type = m.elem_type; A.mat_lamG = d_lamG;
         A.fixmask = K->d_fixmask; A.halo_glob = K->d_halo_glob; A.halo_rank = d_halo_rank;
         A.rowlen = K->d_rowlen; A.rowof = K->d_rowof; A.slot_ptr = K->d_slot_ptr; A.cols = K->d_cols; A.vals = K->vals64();
         A.bad_elem = (long long *)(d_status + SS_BAD_ELEM);
@@ -1115,7 +1112,7 @@ int assembly_run::numeric() {
     }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemsetAsync(d_status + SS_AUX, 0, 8, st));
-    hipLaunchKernelGGL(k_count_fixed, dim3(nblk(n_dof, 256) > 2048 ? 2048 : nblk(n_dof, 256)), dim3(256), 0, st, n_dof, d_red,
+    hipLaunchKernelGGL(k_count_fixed, dim3(nblk(m.n_dof, 256) > 2048 ? 2048 : nblk(m.n_dof, 256)), dim3(256), 0, st, m.n_dof, m.red,
                        (unsigned long long *)(d_status + SS_AUX));
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_BAD_ELEM, d_status + SS_BAD_ELEM, 16, hipMemcpyDeviceToHost, st));
     return STAN_OK;
@@ -1202,17 +1199,13 @@ int stan_ke_batch_device(stan_ctx *ctx, int64_t n, const double *d_xyz8, double 
     return stan_detj_check(ctx, " (MatrixST.Inverse would throw)");
 }
 
-int stan_assemble_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
-                         const int32_t *d_node_dof, int64_t n_elem, const int32_t *d_conn,
-                         const int32_t *d_elem_mat, const uint8_t *d_elem_type, int32_t n_mat,
-                         const double *mat_E_nu, int64_t n_dof, const int32_t *d_red,
-                         stan_matrix **outK) {
+int stan_assemble_device(stan_ctx *ctx, const stan_mesh &d, stan_matrix **outK) {
     *outK = nullptr;
-    if (n_nodes <= 0 || n_elem < 0 || n_dof != 3 * n_nodes || n_mat <= 0) {
+    if (d.n_nodes <= 0 || d.n_elem < 0 || d.n_dof != 3 * d.n_nodes || d.n_mat <= 0) {
         ctx->err = "assemble: need n_nodes > 0, n_dof == 3*n_nodes, n_mat > 0";
         return STAN_E_ARG;
     }
-    if (n_elem * 8 >= (int64_t)1 << 31) {
+    if (d.n_elem * 8 >= (int64_t)1 << 31) {
         ctx->err = "assemble: n_elem*8 must fit int32";
         return STAN_E_ARG;
     }
@@ -1223,7 +1216,7 @@ int stan_assemble_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
         ev0 = events.make(); ev1 = events.make(); ev2 = events.make();
         hipEventRecord(ev0, st);
     }
-    assembly_run A{ctx, n_nodes, d_xyz, d_node_dof, n_elem, d_conn, d_elem_mat, d_elem_type, n_mat, mat_E_nu, n_dof, d_red};
+    assembly_run A{ctx, d};
     stan_matrix *K = A.K = new stan_matrix();
     K->ctx = ctx;
     ctx->matrices.push_back(K);
@@ -1242,7 +1235,7 @@ int stan_assemble_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
     if (ctx->profiling) hipEventRecord(ev2, st);
     HIPCHK(ctx, hipStreamSynchronize(st));
     STANCHK(stan_detj_check(ctx, " (MatrixST.Inverse would throw, MatrixST.cs:315-318)"));
-    K->n_red = n_dof - ctx->h_status[SS_AUX];
+    K->n_red = d.n_dof - ctx->h_status[SS_AUX];
     if (ctx->profiling) {
         float a = 0, b = 0;
         hipEventElapsedTime(&a, ev0, ev1);

@@ -353,6 +353,30 @@ static inline int64_t stan_row_start(int64_t nb, int nranks, int r) {
     return s > nb ? nb : s;
 }
 
+// ---- the mesh, as every layer below the C ABI passes it on ---------------------------------------------------------------
+// A view: plain pointers and counts, nothing owned.  ONE type for both sides of the upload -- a HOST view holds the caller's
+// arrays (a public entry builds it behind its checks), a DEVICE view their copies in device memory (mesh_dbufs of api.hip makes
+// it, a _dev entry builds it from its arguments, the stan_*_device drivers take it); mat_E_nu is a host array in both.
+// May be null: disp, node_dof and red where the entry has no such array (n_dof is 0 where it is not passed either); conn,
+// elem_mat and elem_type only where n_elem == 0.  Built with designated initialisers, so that no array is passed by position.
+struct stan_mesh {
+    int64_t n_nodes = 0, n_elem = 0, n_dof = 0;
+    int32_t n_mat = 0;
+    const double *xyz = nullptr, *disp = nullptr;   // [n_nodes][3]
+    const int32_t *node_dof = nullptr;              // [n_nodes][3]
+    const int32_t *conn = nullptr;                  // [n_elem][8]
+    const int32_t *elem_mat = nullptr;              // [n_elem]
+    const uint8_t *elem_type = nullptr;             // [n_elem]
+    const int32_t *red = nullptr;                   // [n_dof]
+    const double *mat_E_nu = nullptr;               // [n_mat][2], host
+    // the elements [e0, e1) of a mesh that has some: the element arrays start at e0, the node arrays stay whole
+    stan_mesh chunk(int64_t e0, int64_t e1) const {
+        stan_mesh c = *this;
+        c.n_elem = e1 - e0; c.conn = conn + 8 * e0; c.elem_mat = elem_mat + e0; c.elem_type = elem_type + e0;
+        return c;
+    }
+};
+
 // ---- scan.hip -------------------------------------------------------------------------------
 // out[i] = sum_{j<i} in[j] (int32 in, int64 out), out has n+1 entries (out[n] = total).
 int stan_scan_exclusive(stan_ctx *ctx, const int32_t *d_in, int64_t *d_out, int64_t n);
@@ -368,11 +392,7 @@ int stan_compact_flags(stan_ctx *ctx, const int32_t *d_flag, int64_t *d_rank, in
 int stan_slot_ptr_narrow(stan_ctx *ctx, const int64_t *d_ptr64, int64_t n, int32_t **d_ptr32);
 
 // ---- assembly.hip ---------------------------------------------------------------------------
-int stan_assemble_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
-                         const int32_t *d_node_dof, int64_t n_elem, const int32_t *d_conn,
-                         const int32_t *d_elem_mat, const uint8_t *d_elem_type, int32_t n_mat,
-                         const double *mat_E_nu, int64_t n_dof, const int32_t *d_red,
-                         stan_matrix **outK);
+int stan_assemble_device(stan_ctx *ctx, const stan_mesh &d, stan_matrix **outK);   // d: device view with node_dof and red
 int stan_ke_batch_device(stan_ctx *ctx, int64_t n, const double *d_xyz8, double E, double nu,
                          const uint8_t *d_type, double *d_out);
 
@@ -424,11 +444,10 @@ void stan_cg_products_set(stan_ctx *ctx, double *block, double *saved[3]);   // 
 void stan_cg_products_adopt(stan_ctx *ctx, double *block, size_t bytes, double *saved[3]);   // keep the carved pair for good, release the saved one
 
 // ---- recovery.hip ---------------------------------------------------------------------------
-int stan_recover_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const double *d_disp,
-                        int64_t n_elem, const int32_t *d_conn, const int32_t *d_elem_mat,
-                        const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu,
-                        double *d_strain, double *d_stress, const int32_t *d_node_dof,
-                        double *d_elem_forces, double *d_R);
+// d: device view with disp (and node_dof when forces are asked for).  Strain / stress (both or neither), the element nodal
+// forces and their sum R over the DOFs: outputs that are null are not computed.
+int stan_recover_device(stan_ctx *ctx, const stan_mesh &d, double *d_strain, double *d_stress, double *d_elem_forces = nullptr,
+                        double *d_R = nullptr);
 
 // ---- scalars.hip ----------------------------------------------------------------------------
 // Part.Load_Scalar on device arrays; sel: n_sel distinct indices in [0, STAN_SCALAR_COUNT), d_conn checked by the caller;
@@ -444,31 +463,25 @@ int stan_incidence_lists(stan_ctx *ctx, dev_scope &tmp, int64_t n_nodes, int64_t
 
 // ---- internal_forces.hip --------------------------------------------------------------------
 // f_int = sum_e int B^T D B u_e dV gathered per node, reactions and the equilibrium sums (stan_hip_internal_forces_hex8);
-// every array in device memory except mat_E_nu and eq; d_F, d_fint, d_reaction, eq may be null.  Checks its arguments on
+// d: device view with every array; eq is host memory; d_F, d_fint, d_reaction, eq may be null.  Checks its arguments on
 // the device before anything is indexed with them.  Synchronises the stream.
-int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const double *d_disp,
-                                const int32_t *d_node_dof, int64_t n_elem, const int32_t *d_conn, const int32_t *d_elem_mat,
-                                const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
-                                const int32_t *d_red, const double *d_F, double *d_fint, double *d_reaction,
+int stan_internal_forces_device(stan_ctx *ctx, const stan_mesh &d, const double *d_F, double *d_fint, double *d_reaction,
                                 stan_equilibrium *eq);
 // Its argument check, shared with loads.hip: resets the status words, runs k_if_check (and k_ld_check_faces when
 // n_faces > 0) with a zeroed claim array out of `tmp`, synchronises, and turns the first IF_* bit raised -- tested in the
 // order DOF, CONN, MAT, TYPE, RED, FACE -- into "<who>: <what>" and its return code; *n_fixed = the fixed DOFs of the map.
 enum stan_if_bits { IF_CONN = 1, IF_MAT = 2, IF_TYPE = 4, IF_DOF = 8, IF_RED = 16, IF_FACE = 32 };
-int stan_elem_args_check(stan_ctx *ctx, dev_scope &tmp, const char *who, int64_t n_nodes, int64_t n_elem, int64_t n_dof,
-                         int32_t n_mat, const int32_t *d_conn, const int32_t *d_elem_mat, const uint8_t *d_elem_type,
-                         const int32_t *d_node_dof, const int32_t *d_red, int64_t n_faces, const int32_t *d_face_elem,
-                         const uint8_t *d_face_id, int64_t *n_fixed);
+int stan_elem_args_check(stan_ctx *ctx, dev_scope &tmp, const char *who, const stan_mesh &d, int64_t n_faces,
+                         const int32_t *d_face_elem, const uint8_t *d_face_id, int64_t *n_fixed);
 
 // ---- loads.hip ------------------------------------------------------------------------------
 // Consistent nodal loads of body forces and face pressures, and the right-hand side for prescribed displacements
-// (stan_hip_load_vector_hex8); every array in device memory except mat_E_nu, mat_body and sums.  Checks its arguments on
-// the device before anything is indexed with them.  Synchronises the stream.
-int stan_load_vector_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const int32_t *d_node_dof, int64_t n_elem,
-                            const int32_t *d_conn, const int32_t *d_elem_mat, const uint8_t *d_elem_type, int32_t n_mat,
-                            const double *mat_E_nu, int64_t n_dof, const int32_t *d_red, const double *mat_body, int64_t n_faces,
-                            const int32_t *d_face_elem, const uint8_t *d_face_id, const double *d_face_pressure,
-                            const double *d_disp0, double *d_F, double *d_F_solve, double *d_load_full, stan_load_sums *sums);
+// (stan_hip_load_vector_hex8); d: device view with node_dof and red (its disp is not read: the prescribed displacements are
+// d_disp0); mat_body and sums are host memory.  Checks its arguments on the device before anything is indexed with them.
+// Synchronises the stream.
+int stan_load_vector_device(stan_ctx *ctx, const stan_mesh &d, const double *mat_body, int64_t n_faces, const int32_t *d_face_elem,
+                            const uint8_t *d_face_id, const double *d_face_pressure, const double *d_disp0, double *d_F,
+                            double *d_F_solve, double *d_load_full, stan_load_sums *sums);
 
 // ---- comm.cpp -------------------------------------------------------------------------------
 int stan_comm_allreduce_sum_f64(stan_ctx *ctx, double *d_buf, size_t count);
@@ -609,17 +622,17 @@ void stan_group_destroy(stan_ctx *lead);
 const char *stan_group_last_error(stan_ctx *lead);
 int stan_group_ctx_call(stan_ctx *lead, const std::function<int(stan_ctx *)> &fn);
 int stan_group_ctx_call_ranked(stan_ctx *lead, const std::function<int(stan_ctx *, int)> &fn);   // fn(rank context, rank) on every worker
-int stan_group_assemble(stan_ctx *lead, int64_t n_nodes, const double *xyz, const int32_t *node_dof,
-                        int64_t n_elem, const int32_t *conn, const int32_t *elem_mat,
-                        const uint8_t *elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
-                        const int32_t *red, stan_matrix **outK);
+int stan_group_assemble(stan_ctx *lead, const stan_mesh &m, stan_matrix **outK);   // m: host view, as in stan_assemble_host
 void stan_group_matrix_free(stan_matrix *K);
 int stan_group_cg_solve(stan_ctx *lead, stan_matrix *K, const double *F, double eps_f, int32_t max_its,
                         int32_t precision_mode, double *U, int32_t *termination_type, int32_t *iterations,
                         double *rel_residual);
-int stan_group_recover(stan_ctx *lead, int64_t n_nodes, const double *xyz, const double *disp, int64_t n_elem,
-                       const int32_t *conn, const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat,
-                       const double *mat_E_nu, double *strain, double *stress);
+int stan_group_recover(stan_ctx *lead, const stan_mesh &m, double *strain, double *stress);   // one chunk of m per rank
+// a rank's STAN_E_DETJ / STAN_E_UNSUPPORTED over the chunk from element e0 on: lead->bad_elem and the rank's text name the whole model's element
+void stan_chunk_bad_element(stan_ctx *lead, stan_ctx *c, int rc, int64_t e0);
+// api.hip: the host entries of ONE context behind their argument checks (the public entries and the group's ranks call them)
+int stan_assemble_host(stan_ctx *ctx, const stan_mesh &m, stan_matrix **outK);
+int stan_recover_host(stan_ctx *ctx, const stan_mesh &m, double *strain, double *stress);
 int stan_group_set_p2p(stan_ctx *lead, bool on);
 int stan_group_rank0_call(stan_ctx *lead, const std::function<int(stan_ctx *)> &fn);
 stan_ctx *stan_group_rank0(stan_ctx *lead);

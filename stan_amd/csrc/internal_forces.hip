@@ -231,10 +231,8 @@ k_if_finish(int64_t n_blocks, const double *__restrict__ partial, const long lon
 
 }  // namespace
 
-int stan_elem_args_check(stan_ctx *ctx, dev_scope &tmp, const char *who, int64_t n_nodes, int64_t n_elem, int64_t n_dof,
-                         int32_t n_mat, const int32_t *d_conn, const int32_t *d_elem_mat, const uint8_t *d_elem_type,
-                         const int32_t *d_node_dof, const int32_t *d_red, int64_t n_faces, const int32_t *d_face_elem,
-                         const uint8_t *d_face_id, int64_t *n_fixed) {
+int stan_elem_args_check(stan_ctx *ctx, dev_scope &tmp, const char *who, const stan_mesh &d, int64_t n_faces,
+                         const int32_t *d_face_elem, const uint8_t *d_face_id, int64_t *n_fixed) {
     auto bad = [&](const char *why, int rc) { ctx->err = std::string(who) + ": " + why; return rc; };
     hipStream_t st = ctx->stream;
     int64_t *status = ctx->d_status;
@@ -242,13 +240,13 @@ int stan_elem_args_check(stan_ctx *ctx, dev_scope &tmp, const char *who, int64_t
     HIPCHK(ctx, hipMemcpyAsync(status + SS_ERRBITS, &init[0], 8, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(status + SS_BAD_ELEM, &init[1], 16, hipMemcpyHostToDevice, st));   // SS_BAD_ELEM, SS_AUX
     int32_t *d_claim;
-    STANCHK(tmp.alloc(&d_claim, (size_t)n_nodes));
-    HIPCHK(ctx, hipMemsetAsync(d_claim, 0, (size_t)n_nodes * 4, st));
-    const int64_t n_chk = n_elem * 8 > n_dof ? n_elem * 8 : n_dof;   // (n_dof = 3 n_nodes)
-    hipLaunchKernelGGL(k_if_check, dim3(nblk(n_chk, 256)), dim3(256), 0, st, n_nodes, n_elem, n_dof, n_mat, d_conn, d_elem_mat,
-                       d_elem_type, d_node_dof, d_red, d_claim, status);
+    STANCHK(tmp.alloc(&d_claim, (size_t)d.n_nodes));
+    HIPCHK(ctx, hipMemsetAsync(d_claim, 0, (size_t)d.n_nodes * 4, st));
+    const int64_t n_chk = d.n_elem * 8 > d.n_dof ? d.n_elem * 8 : d.n_dof;   // (n_dof = 3 n_nodes)
+    hipLaunchKernelGGL(k_if_check, dim3(nblk(n_chk, 256)), dim3(256), 0, st, d.n_nodes, d.n_elem, d.n_dof, d.n_mat, d.conn, d.elem_mat,
+                       d.elem_type, d.node_dof, d.red, d_claim, status);
     if (n_faces > 0)
-        hipLaunchKernelGGL(k_ld_check_faces, dim3(nblk(n_faces, 256)), dim3(256), 0, st, n_faces, n_elem, d_face_elem, d_face_id, status);
+        hipLaunchKernelGGL(k_ld_check_faces, dim3(nblk(n_faces, 256)), dim3(256), 0, st, n_faces, d.n_elem, d_face_elem, d_face_id, status);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_ERRBITS, status + SS_ERRBITS, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, status + SS_AUX, 8, hipMemcpyDeviceToHost, st));
@@ -264,12 +262,10 @@ int stan_elem_args_check(stan_ctx *ctx, dev_scope &tmp, const char *who, int64_t
     return STAN_OK;
 }
 
-int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const double *d_disp,
-                                const int32_t *d_node_dof, int64_t n_elem, const int32_t *d_conn, const int32_t *d_elem_mat,
-                                const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
-                                const int32_t *d_red, const double *d_F, double *d_fint, double *d_reaction,
+int stan_internal_forces_device(stan_ctx *ctx, const stan_mesh &d, const double *d_F, double *d_fint, double *d_reaction,
                                 stan_equilibrium *eq) {
     const char *who = "internal_forces_hex8";
+    const int64_t n_nodes = d.n_nodes, n_elem = d.n_elem, n_dof = d.n_dof, n_mat = d.n_mat;
     auto bad = [&](const char *why, int rc) { ctx->err = std::string(who) + ": " + why; return rc; };
     if (n_nodes <= 0 || n_elem < 0 || n_mat <= 0 || n_dof != n_nodes * 3) return bad("n_dof must be 3 n_nodes > 0, n_mat > 0", STAN_E_ARG);
     if (n_elem >= (int64_t)1 << 28) return bad("more than 2^28 elements", STAN_E_ARG);
@@ -280,8 +276,7 @@ int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_
     int64_t *status = ctx->d_status;
     dev_scope tmp(ctx);
     int64_t n_fixed;
-    STANCHK(stan_elem_args_check(ctx, tmp, who, n_nodes, n_elem, n_dof, n_mat, d_conn, d_elem_mat, d_elem_type, d_node_dof, d_red, 0,
-                                 nullptr, nullptr, &n_fixed));
+    STANCHK(stan_elem_args_check(ctx, tmp, who, d, 0, nullptr, nullptr, &n_fixed));
     const int64_t n_red = n_dof - n_fixed;
 
     phase_timer pt(ctx, 4);   // element pass | lists | gather + reductions
@@ -289,7 +284,7 @@ int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_
     double *d_fe, *d_partial = nullptr, *d_out = nullptr;
     long long *d_partial_dof = nullptr, *d_out_dof = nullptr;
     const int64_t n_blocks = nblk(n_nodes, 256);
-    STANCHK(lamG.alloc(tmp, n_mat, mat_E_nu));
+    STANCHK(lamG.alloc(tmp, n_mat, d.mat_E_nu));
     STANCHK(tmp.alloc(&d_fe, (size_t)(n_elem > 0 ? n_elem : 1) * 24));
     if (eq) {
         STANCHK(tmp.alloc(&d_partial, (size_t)n_blocks * (NSUM + 1)));
@@ -300,19 +295,19 @@ int stan_internal_forces_device(stan_ctx *ctx, int64_t n_nodes, const double *d_
     HIPCHK(ctx, lamG.upload(st));
     STANCHK(pt.mark(0));
     if (n_elem > 0)   // 8 lanes per element, 8 elements per wave, 32 per workgroup
-        hipLaunchKernelGGL(k_if_elem, dim3(nblk(n_elem, 32)), dim3(256), 0, st, n_elem, d_xyz, d_disp, d_conn, d_elem_mat, d_elem_type,
+        hipLaunchKernelGGL(k_if_elem, dim3(nblk(n_elem, 32)), dim3(256), 0, st, n_elem, d.xyz, d.disp, d.conn, d.elem_mat, d.elem_type,
                            lamG.d, d_fe, (long long *)(status + SS_BAD_ELEM));
     STANCHK(pt.mark(1));
     int64_t *d_ptr;
     int32_t *d_list;
-    STANCHK(stan_incidence_lists(ctx, tmp, n_nodes, n_elem, d_conn, true, &d_ptr, &d_list));
+    STANCHK(stan_incidence_lists(ctx, tmp, n_nodes, n_elem, d.conn, true, &d_ptr, &d_list));
     STANCHK(pt.mark(2));
     if (eq) {
-        hipLaunchKernelGGL(k_if_gather<true>, dim3((unsigned)n_blocks), dim3(256), 0, st, n_nodes, d_ptr, d_list, d_fe, d_node_dof, d_red,
+        hipLaunchKernelGGL(k_if_gather<true>, dim3((unsigned)n_blocks), dim3(256), 0, st, n_nodes, d_ptr, d_list, d_fe, d.node_dof, d.red,
                            d_F, n_red, d_fint, d_reaction, d_partial, d_partial_dof);
         hipLaunchKernelGGL(k_if_finish, dim3(1), dim3(256), 0, st, n_blocks, d_partial, d_partial_dof, d_out, d_out_dof);
     } else {
-        hipLaunchKernelGGL(k_if_gather<false>, dim3((unsigned)n_blocks), dim3(256), 0, st, n_nodes, d_ptr, d_list, d_fe, d_node_dof, d_red,
+        hipLaunchKernelGGL(k_if_gather<false>, dim3((unsigned)n_blocks), dim3(256), 0, st, n_nodes, d_ptr, d_list, d_fe, d.node_dof, d.red,
                            d_F, n_red, d_fint, d_reaction, nullptr, nullptr);
     }
     STANCHK(pt.mark(3));

@@ -186,12 +186,11 @@ k_ld_finish(int64_t n_gblocks, const double *__restrict__ gpartial, int64_t n_eb
 
 }  // namespace
 
-int stan_load_vector_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const int32_t *d_node_dof, int64_t n_elem,
-                            const int32_t *d_conn, const int32_t *d_elem_mat, const uint8_t *d_elem_type, int32_t n_mat,
-                            const double *mat_E_nu, int64_t n_dof, const int32_t *d_red, const double *mat_body, int64_t n_faces,
-                            const int32_t *d_face_elem, const uint8_t *d_face_id, const double *d_face_pressure,
-                            const double *d_disp0, double *d_F, double *d_F_solve, double *d_load_full, stan_load_sums *sums) {
+int stan_load_vector_device(stan_ctx *ctx, const stan_mesh &d, const double *mat_body, int64_t n_faces, const int32_t *d_face_elem,
+                            const uint8_t *d_face_id, const double *d_face_pressure, const double *d_disp0, double *d_F,
+                            double *d_F_solve, double *d_load_full, stan_load_sums *sums) {
     const char *who = "load_vector_hex8";
+    const int64_t n_nodes = d.n_nodes, n_elem = d.n_elem, n_dof = d.n_dof, n_mat = d.n_mat;
     auto bad = [&](const char *why, int rc) { ctx->err = std::string(who) + ": " + why; return rc; };
     if (n_nodes <= 0 || n_elem < 0 || n_mat <= 0 || n_dof != n_nodes * 3) return bad("n_dof must be 3 n_nodes > 0, n_mat > 0", STAN_E_ARG);
     if (n_elem >= (int64_t)1 << 28) return bad("more than 2^28 elements", STAN_E_ARG);
@@ -205,8 +204,7 @@ int stan_load_vector_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
     // ---- the checks, before anything is indexed with the caller's integers
     dev_scope tmp(ctx);
     int64_t n_fixed;
-    STANCHK(stan_elem_args_check(ctx, tmp, who, n_nodes, n_elem, n_dof, n_mat, d_conn, d_elem_mat, d_elem_type, d_node_dof, d_red,
-                                 n_faces, d_face_elem, d_face_id, &n_fixed));
+    STANCHK(stan_elem_args_check(ctx, tmp, who, d, n_faces, d_face_elem, d_face_id, &n_fixed));
     const int64_t n_red = n_dof - n_fixed;
 
     // ---- prescribed displacements first: f_int(u0 at the fixed DOFs), an error of it leaves every output untouched
@@ -215,10 +213,11 @@ int stan_load_vector_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
         double *d_u0;
         STANCHK(tmp.alloc(&d_u0, (size_t)n_dof));
         STANCHK(tmp.alloc(&d_fint0, (size_t)n_dof));
-        hipLaunchKernelGGL(k_ld_mask, dim3(nblk(n_dof, 256)), dim3(256), 0, st, n_dof, d_disp0, d_node_dof, d_red, d_u0);
+        hipLaunchKernelGGL(k_ld_mask, dim3(nblk(n_dof, 256)), dim3(256), 0, st, n_dof, d_disp0, d.node_dof, d.red, d_u0);
         HIPCHK(ctx, hipGetLastError());
-        STANCHK(stan_internal_forces_device(ctx, n_nodes, d_xyz, d_u0, d_node_dof, n_elem, d_conn, d_elem_mat, d_elem_type, n_mat,
-                                            mat_E_nu, n_dof, d_red, nullptr, d_fint0, nullptr, nullptr));
+        stan_mesh at_u0 = d;
+        at_u0.disp = d_u0;
+        STANCHK(stan_internal_forces_device(ctx, at_u0, nullptr, d_fint0, nullptr, nullptr));
     }
 
     phase_timer pt(ctx, 4);   // element pass | lists | gather + reductions
@@ -234,14 +233,14 @@ int stan_load_vector_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
     }
     STANCHK(pt.mark(0));
     if (n_elem > 0)   // 8 lanes per element, 8 elements per wave, 32 per workgroup
-        hipLaunchKernelGGL(k_ld_elem, dim3((unsigned)n_eblocks), dim3(256), 0, st, n_elem, d_xyz, d_conn, d_elem_mat, d_body, n_faces,
+        hipLaunchKernelGGL(k_ld_elem, dim3((unsigned)n_eblocks), dim3(256), 0, st, n_elem, d.xyz, d.conn, d.elem_mat, d_body, n_faces,
                            d_face_elem, d_face_id, d_face_pressure, d_fe, d_epartial);
     STANCHK(pt.mark(1));
     int64_t *d_ptr;
     int32_t *d_list;
-    STANCHK(stan_incidence_lists(ctx, tmp, n_nodes, n_elem, d_conn, true, &d_ptr, &d_list));
+    STANCHK(stan_incidence_lists(ctx, tmp, n_nodes, n_elem, d.conn, true, &d_ptr, &d_list));
     STANCHK(pt.mark(2));
-    hipLaunchKernelGGL(k_ld_gather, dim3((unsigned)n_gblocks), dim3(256), 0, st, n_nodes, d_ptr, d_list, d_fe, d_node_dof, d_red, n_red,
+    hipLaunchKernelGGL(k_ld_gather, dim3((unsigned)n_gblocks), dim3(256), 0, st, n_nodes, d_ptr, d_list, d_fe, d.node_dof, d.red, n_red,
                        d_fint0, d_F, d_F_solve, d_load_full, d_gpartial);
     if (sums) hipLaunchKernelGGL(k_ld_finish, dim3(1), dim3(256), 0, st, n_gblocks, d_gpartial, n_eblocks, d_epartial, d_out);
     STANCHK(pt.mark(3));

@@ -159,13 +159,18 @@ void stop_workers(stan_group *g) {
     g->w.clear();
 }
 
+// two ranks of the group drive the same device (a test topology; a node gives every rank its own)
+bool shares_a_device(const std::vector<int> &devices) {
+    for (size_t a = 0; a < devices.size(); a++)
+        for (size_t b = a + 1; b < devices.size(); b++)
+            if (devices[a] == devices[b]) return true;
+    return false;
+}
+
 // peer-to-peer resources of the group; failure only means the option is unavailable
 void setup_p2p(stan_group *g) {
     const int n = (int)g->devices.size();
-    bool shared = false;
-    for (int a = 0; a < n; a++)
-        for (int b = a + 1; b < n; b++) shared |= g->devices[a] == g->devices[b];
-    if (shared) {
+    if (shares_a_device(g->devices)) {
         // Ranks that share a device (a test topology) share its hardware queues: the runtime multiplexes
         // streams onto GPU_MAX_HW_QUEUES (default 4) queues, and a stream wait blocks the queue it sits in --
         // with a producer of another rank queued behind it that is a deadlock (measured:
@@ -242,9 +247,7 @@ extern "C" int stan_hip_init_multi(int n_devices, const int *devices, stan_ctx *
         // transport (RCCL; tests/fake_rccl in its asynchronous mode), wait for exchanges THIS rank has not enqueued yet.
         // Such ranks keep their frees for the end of the solve on every transport (stan_ctx::defer_frees; round 6: config 4
         // on 8 ranks of one GPU hung exactly there, rounds 3-5 knew the hazard from the peer-to-peer path only).
-        bool shared = false;
-        for (int a = 0; a < n_devices; a++)
-            for (int b = a + 1; b < n_devices; b++) shared |= g->devices[(size_t)a] == g->devices[(size_t)b];
+        const bool shared = shares_a_device(g->devices);
         for (stan_ctx *c : g->ctx) c->peers_share_device = shared;
         for (stan_ctx *c : g->ctx) c->result_segment = true;
         setup_p2p(g);
@@ -302,10 +305,8 @@ int stan_group_set_p2p(stan_ctx *lead, bool on) {
     return STAN_OK;
 }
 
-int stan_group_assemble(stan_ctx *lead, int64_t n_nodes, const double *xyz, const int32_t *node_dof,
-                        int64_t n_elem, const int32_t *conn, const int32_t *elem_mat,
-                        const uint8_t *elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
-                        const int32_t *red, stan_matrix **outK) {
+// Every rank gets the whole mesh and picks the elements of its block rows itself (api.hip: pick_shard_elements).
+int stan_group_assemble(stan_ctx *lead, const stan_mesh &m, stan_matrix **outK) {
     stan_group *g = lead->group;
     lead->err.clear();
     if (g->broken) { lead->err = "a rank failed earlier and the exchanges were aborted: destroy this handle"; return STAN_E_COMM; }
@@ -313,8 +314,7 @@ int stan_group_assemble(stan_ctx *lead, int64_t n_nodes, const double *xyz, cons
     K->ctx = lead;
     K->parts.assign(g->ctx.size(), nullptr);
     const int rc = run_all(g, [&](int r) {
-        const int e = stan_hip_assemble_hex8(g->ctx[(size_t)r], n_nodes, xyz, node_dof, n_elem, conn, elem_mat, elem_type,
-                                             n_mat, mat_E_nu, n_dof, red, &K->parts[(size_t)r]);
+        const int e = stan_assemble_host(g->ctx[(size_t)r], m, &K->parts[(size_t)r]);
         if (e == STAN_E_DETJ) lead->bad_elem = g->ctx[(size_t)r]->bad_elem;
         return e;
     }, RUN_JOIN);
@@ -335,9 +335,9 @@ int stan_group_assemble(stan_ctx *lead, int64_t n_nodes, const double *xyz, cons
     {
         size_t r = 0;
         int64_t nfree = 0;
-        for (int64_t d = 0; d <= n_dof; d++) {
+        for (int64_t d = 0; d <= m.n_dof; d++) {
             while (r < K->parts.size() && d == 3 * K->parts[r]->r0) { K->parts[r]->u0 = nfree; r++; }
-            if (d < n_dof && red[d] != -1) nfree++;
+            if (d < m.n_dof && m.red[d] != -1) nfree++;
         }
         for (size_t q = 0; q < K->parts.size(); q++)
             K->parts[q]->u1 = q + 1 < K->parts.size() ? K->parts[q + 1]->u0 : nfree;
@@ -387,26 +387,25 @@ int stan_group_cg_solve(stan_ctx *lead, stan_matrix *K, const double *F, double 
 }
 
 // Stress recovery is per element: the elements are cut into one contiguous chunk per device.
-int stan_group_recover(stan_ctx *lead, int64_t n_nodes, const double *xyz, const double *disp, int64_t n_elem,
-                       const int32_t *conn, const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat,
-                       const double *mat_E_nu, double *strain, double *stress) {
+int stan_group_recover(stan_ctx *lead, const stan_mesh &m, double *strain, double *stress) {
     stan_group *g = lead->group;
     lead->err.clear();
     const int64_t n = (int64_t)g->ctx.size();
     return run_all(g, [&](int r) {
-        const int64_t e0 = n_elem * r / n, e1 = n_elem * (r + 1) / n;
+        const int64_t e0 = m.n_elem * r / n, e1 = m.n_elem * (r + 1) / n;
         if (e1 <= e0) return (int)STAN_OK;
         stan_ctx *c = g->ctx[(size_t)r];
-        const int rc = stan_hip_recover_hex8(c, n_nodes, xyz, disp, e1 - e0, conn + 8 * e0, elem_mat + e0,
-                                             elem_type + e0, n_mat, mat_E_nu, strain + 48 * e0, stress + 48 * e0);
-        if (rc == STAN_E_UNSUPPORTED || rc == STAN_E_DETJ) {   // element numbers of the whole model
-            lead->bad_elem = c->bad_elem + e0;
-            c->err = (rc == STAN_E_DETJ ? "det J == 0 in element " : "stress recovery: HEX8_G1 element ") +
-                     std::to_string(lead->bad_elem) +
-                     (rc == STAN_E_DETJ ? "" : " (the reference throws: N has one row, Element.cs:242)");
-        }
+        const int rc = stan_recover_host(c, m.chunk(e0, e1), strain + 48 * e0, stress + 48 * e0);
+        stan_chunk_bad_element(lead, c, rc, e0);
         return rc;
     }, RUN_JOIN);
+}
+
+void stan_chunk_bad_element(stan_ctx *lead, stan_ctx *c, int rc, int64_t e0) {
+    if (rc != STAN_E_UNSUPPORTED && rc != STAN_E_DETJ) return;
+    lead->bad_elem = c->bad_elem + e0;
+    c->err = (rc == STAN_E_DETJ ? "det J == 0 in element " : "stress recovery: HEX8_G1 element ") + std::to_string(lead->bad_elem) +
+             (rc == STAN_E_DETJ ? "" : " (the reference throws: N has one row, Element.cs:242)");
 }
 
 // single-rank helpers that a group handle redirects to rank 0 (K_e, nodal forces, pool info): run on rank

@@ -100,17 +100,13 @@ int lamG_buf::alloc(dev_scope &tmp, int32_t n_mat, const double *mat_E_nu) {
     return tmp.alloc(&d, host.size());
 }
 
-int stan_recover_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const double *d_disp,
-                        int64_t n_elem, const int32_t *d_conn, const int32_t *d_elem_mat,
-                        const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu,
-                        double *d_strain, double *d_stress, const int32_t *d_node_dof,
-                        double *d_elem_forces, double *d_R) {
-    (void)n_nodes;
+int stan_recover_device(stan_ctx *ctx, const stan_mesh &d, double *d_strain, double *d_stress, double *d_elem_forces, double *d_R) {
     const bool forces = d_elem_forces || d_R;
+    const int64_t n_elem = d.n_elem;
     if (n_elem <= 0) return STAN_OK;
     dev_scope tmp(ctx);
     lamG_buf lamG;
-    STANCHK(lamG.alloc(tmp, n_mat, mat_E_nu));
+    STANCHK(lamG.alloc(tmp, d.n_mat, d.mat_E_nu));
     const double *d_lamG = lamG.d;
     hipStream_t st = ctx->stream;
     long long init[2] = {0x7fffffffffffffffLL, 0x7fffffffffffffffLL};
@@ -118,12 +114,12 @@ int stan_recover_device(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, con
     hipError_t e2 = hipMemcpyAsync(ctx->d_status + SS_BAD_ELEM, init, 16, hipMemcpyHostToDevice, st);
     const dim3 grid((unsigned)((n_elem + 31) / 32)), block(256);   // 8 lanes per element, 8 elements per wave
     if (forces)
-        hipLaunchKernelGGL(k_recover<true>, grid, block, 0, st, n_elem, d_xyz, d_disp, d_conn, d_elem_mat,
-                           d_elem_type, d_lamG, d_strain, d_stress, (long long *)(ctx->d_status + SS_BAD_ELEM),
-                           (long long *)(ctx->d_status + SS_AUX), d_node_dof, d_elem_forces, d_R);
+        hipLaunchKernelGGL(k_recover<true>, grid, block, 0, st, n_elem, d.xyz, d.disp, d.conn, d.elem_mat,
+                           d.elem_type, d_lamG, d_strain, d_stress, (long long *)(ctx->d_status + SS_BAD_ELEM),
+                           (long long *)(ctx->d_status + SS_AUX), d.node_dof, d_elem_forces, d_R);
     else
-        hipLaunchKernelGGL(k_recover<false>, grid, block, 0, st, n_elem, d_xyz, d_disp, d_conn, d_elem_mat,
-                           d_elem_type, d_lamG, d_strain, d_stress, (long long *)(ctx->d_status + SS_BAD_ELEM),
+        hipLaunchKernelGGL(k_recover<false>, grid, block, 0, st, n_elem, d.xyz, d.disp, d.conn, d.elem_mat,
+                           d.elem_type, d_lamG, d_strain, d_stress, (long long *)(ctx->d_status + SS_BAD_ELEM),
                            (long long *)(ctx->d_status + SS_AUX), nullptr, nullptr, nullptr);
     hipError_t e3 = hipGetLastError();
     hipError_t e4 = hipMemcpyAsync(ctx->h_status + SS_BAD_ELEM, ctx->d_status + SS_BAD_ELEM, 16, hipMemcpyDeviceToHost, st);
