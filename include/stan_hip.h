@@ -88,7 +88,14 @@ int stan_hip_init_multi(int n_devices, const int *devices, stan_ctx **out);
 void stan_hip_destroy(stan_ctx *ctx);
 const char *stan_hip_last_error(stan_ctx *ctx);
 int64_t stan_hip_last_bad_element(stan_ctx *ctx);
-/* Use an existing hipStream_t (e.g. torch's current stream) for all work; NULL = own stream. */
+/* Use an existing hipStream_t (e.g. torch's current stream) for all work; NULL = own stream (a fresh non-blocking one).
+ * The call drains the stream the context had and parks or releases no pool block; matrices live across it.  Every entry
+ * enqueues on the context's stream and returns with its outputs complete (it synchronises that stream itself), so:
+ *   - device inputs (*_dev) must be ready ON THAT STREAM: work the caller enqueued on it before the call -- a copy into d_F
+ *     behind a long kernel, say -- is seen by the call without any host synchronisation;
+ *   - on the context's OWN stream nothing orders a call behind another stream's work: the caller synchronises that stream
+ *     first (or gives it to the context).  tests/test_gpu_device_entries.py shows both, the second by reading stale data.
+ * STAN_E_UNSUPPORTED on a handle of stan_hip_init_multi. */
 int stan_hip_set_stream(stan_ctx *ctx, void *hip_stream);
 
 /* Solver options (defaults reproduce alglib.lincg as the reference uses it).  The numbers are ABI and stay as they were
@@ -340,7 +347,13 @@ int stan_hip_assemble_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz,
  * in HBM on the context's GPU.  This is the entry bench.py times.  A rank of a sharded run may
  * pass only the elements that touch its block rows, in ascending order of their index in the whole
  * model (stan_host_partition_elements): K's bits do not change, and the element number reported
- * with STAN_E_DETJ is then an index into the arrays that were passed. */
+ * with STAN_E_DETJ is then an index into the arrays that were passed.
+ * The device arrays are read only, must be ready on the context's stream (stan_hip_set_stream) and need their natural
+ * alignment only (8 B for doubles, 4 B for int32, none for elem_type): every access through a caller's pointer is one
+ * element wide.  K is complete when the call returns; the arrays may then be changed or freed.  The host entry's host-side
+ * range checks of conn and elem_mat do not run here and none is promised in their place: an index outside [0, n_nodes) /
+ * [0, n_mat) is the caller's to exclude.
+ * STAN_E_UNSUPPORTED on a handle of stan_hip_init_multi (so for every *_dev entry). */
 int stan_hip_assemble_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz,
                                const int32_t *d_node_dof, int64_t n_elem, const int32_t *d_conn,
                                const int32_t *d_elem_mat, const uint8_t *d_elem_type,
@@ -360,7 +373,12 @@ void stan_hip_matrix_free(stan_matrix *K);
 int stan_hip_cg_solve(stan_ctx *ctx, stan_matrix *K, const double *F, double eps_f,
                       int32_t max_its, int32_t precision_mode, double *U,
                       int32_t *termination_type, int32_t *iterations, double *rel_residual);
-/* F and U in device memory. */
+/* F and U in device memory: d_F [N] read only and ready on the context's stream (stan_hip_set_stream), d_U [N]; natural
+ * alignment (8 B) is enough, and the two may sit anywhere in larger allocations: nothing outside [0, N) is read or stored.
+ * d_U need NOT be initialised: every one of its N entries is stored for every termination code (the one epilogue of the loop
+ * runs on every path; zeros where the loop never moved: F = 0, a model without elements, an empty row), and U is complete
+ * when the call returns.  N = 0
+ * (every DOF fixed): type 1 at iteration 0, the pointers must still be non-null and nothing is read or stored through them. */
 int stan_hip_cg_solve_dev(stan_ctx *ctx, stan_matrix *K, const double *d_F, double eps_f,
                           int32_t max_its, int32_t precision_mode, double *d_U,
                           int32_t *termination_type, int32_t *iterations, double *rel_residual);
@@ -389,7 +407,8 @@ int stan_hip_cg_solve_dev(stan_ctx *ctx, stan_matrix *K, const double *d_F, doub
 int stan_hip_cg_solve_multi(stan_ctx *ctx, stan_matrix *K, int32_t n_rhs, const double *F, double eps_f,
                             int32_t max_its, int32_t precision_mode, double *U, int32_t *termination_type,
                             int32_t *iterations, double *rel_residual);
-/* F and U in device memory. */
+/* F and U in device memory, as stan_hip_cg_solve_dev takes them: [n_rhs][N] each, natural alignment, d_F ready on the
+ * context's stream, every entry of d_U stored (a zero column included) and nothing beside them, complete on return. */
 int stan_hip_cg_solve_multi_dev(stan_ctx *ctx, stan_matrix *K, int32_t n_rhs, const double *d_F, double eps_f,
                                 int32_t max_its, int32_t precision_mode, double *d_U, int32_t *termination_type,
                                 int32_t *iterations, double *rel_residual);
@@ -398,7 +417,11 @@ int stan_hip_cg_solve_multi_dev(stan_ctx *ctx, stan_matrix *K, int32_t n_rhs, co
 /* (Element.cs:211-246, 257-267, called from Solver.cs:184-210).  disp [n_nodes*3] = the
  * nodal dU_buffer in NodeLib order (Solver.cs:171-178).  strain/stress [n_elem*48]: per
  * element 8 nodes x {xx,yy,zz,xy,yz,xz} = the 8x6 MatrixST stored in Element.Strain[1] /
- * Stress[1].  A HEX8_G1 element is STAN_E_UNSUPPORTED (the reference throws there). */
+ * Stress[1].  A HEX8_G1 element is STAN_E_UNSUPPORTED (the reference throws there).
+ * _dev: the arrays in device memory, the inputs read only and ready on the context's stream (stan_hip_set_stream), natural
+ * alignment only.  d_strain / d_stress need not be initialised: all 48 * n_elem entries of each are stored, nothing behind
+ * element n_elem - 1, and they are complete when the call returns STAN_OK; after an error code their contents are
+ * unspecified (still nothing outside them is touched).  Connectivity and material indices are not range-checked. */
 int stan_hip_recover_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const double *disp,
                           int64_t n_elem, const int32_t *conn, const int32_t *elem_mat,
                           const uint8_t *elem_type, int32_t n_mat, const double *mat_E_nu,

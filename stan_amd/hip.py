@@ -290,6 +290,14 @@ class Context:
             _ptr(strain, C.c_double), _ptr(stress, C.c_double)))
         return strain, stress
 
+    def recover_hex8_dev(self, n_nodes, d_xyz, d_disp, n_elem, d_conn, d_elem_mat, d_elem_type, mat_E_nu, d_strain, d_stress):
+        """All d_* are device pointers (ints, e.g. torch tensor.data_ptr()); d_strain, d_stress: [n_elem, 8, 6] doubles."""
+        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        self._chk(self.lib.stan_hip_recover_hex8_dev(
+            self.h, C.c_int64(n_nodes), _dev(d_xyz, C.c_double), _dev(d_disp, C.c_double), C.c_int64(n_elem),
+            _dev(d_conn, C.c_int32), _dev(d_elem_mat, C.c_int32), _dev(d_elem_type, C.c_uint8),
+            C.c_int32(mat_E_nu.shape[0]), _ptr(mat_E_nu, C.c_double), _dev(d_strain, C.c_double), _dev(d_stress, C.c_double)))
+
     def recover_hex8_keep(self, xyz, disp, conn, elem_mat, elem_type, mat_E_nu):
         """Stress recovery with the results kept on the device(s): returns a Results handle (map(e0, e1), free())."""
         xyz = np.ascontiguousarray(xyz, dtype=np.float64)
