@@ -622,6 +622,68 @@ int stan_hip_load_vector_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *
  * ends with the internal forces' fields. */
 int stan_hip_load_vector_times(stan_ctx *ctx, double ms[3]);
 
+/* ---- thermal loads: a temperature field as load vector and as stress correction --------------- */
+/* No step of the reference.  dT [n_nodes] is the temperature change from the stress-free state at every node, mat_alpha
+ * [n_mat] the expansion coefficient per row of mat_E_nu (host arrays in every entry).  With dT(q) = sum_a N_a(q) dT_a the
+ * thermal strain is eps0(q) = alpha_m dT(q) (1,1,1,0,0,0) and D eps0 = beta_m dT(q) (1,1,1,0,0,0), beta_m = E alpha / (1 - 2 nu)
+ * formed once per material on the host in fp64, exactly as written.
+ *   load    f_a = sum_g B_a(q_g)^T (D eps0(q_g)) det J_g w over the element's own STIFFNESS rule (HEX8_G2 2x2x2 with weight 1,
+ *           HEX8_G1 one point with weight 8): K u = f holds term by term for u = alpha dT x, free expansion is stress-free
+ *           on any mesh.  The nodal load l [n_dof] is the sum over every (element, corner) that names the node.
+ *   stress  the nodal stress of element e at corner i loses beta_m dT[conn[e][i]] in xx, yy, zz (one fused multiply-add per
+ *           entry); shear entries are returned as they came, the strain array stays the total strain.
+ *   F         [N] in/out or NULL: F[j] = F[j] + l[j] on the free DOFs, ONE fp64 add per entry
+ *   load_full [n_dof] out or NULL: l before the reduction, fixed DOFs included.  With a thermal load the force a support exerts
+ *             is f_int(U) - l at the fixed DOFs.
+ *   sums      stan_thermal_sums or NULL (void * as for stan_hip_load_vector_hex8)
+ * An element whose material has alpha == 0 contributes exact zeros and is not looked at.  Bit-reproducible: no atomics on
+ * doubles; the 8 Gauss-point terms in three butterfly stages, a node's incidence list in ascending element * 8 + corner, the
+ * sums as per-block partial sums in block order finished by one block; every output has the same bits whichever other
+ * outputs are asked for, from the host and from the _dev entry.
+ * STAN_E_ARG: mat_alpha or dT NULL, every output NULL, a material or node index or element type out of range, n_dof != 3
+ * n_nodes, an ndof_reduction entry outside -1 / [0, i], n_elem >= 2^28.  STAN_E_DOF_LAYOUT as in
+ * stan_hip_internal_forces_hex8.  STAN_E_DETJ (element via stan_hip_last_bad_element) when det J == 0 at a point of an element
+ * with alpha != 0.  The stress entries: STAN_E_UNSUPPORTED for a HEX8_G1 element (element via stan_hip_last_bad_element), as in
+ * the recovery.  STAN_E_UNSUPPORTED on a multi-device handle and on a context with a communicator.  On an error no output has
+ * been written. */
+typedef struct stan_thermal_sums {
+    double load_sum[3];   /* l over ALL DOFs, by direction: zero up to rounding (sum_a grad N_a = 0)        */
+    double free_sum[3];   /* the part that reached F (free DOFs)                                           */
+    double volume;        /* sum det J w over the elements with alpha != 0                                 */
+    double dT_integral;   /* sum dT(q) det J w over the same elements                                      */
+    int64_t n_fixed;
+} stan_thermal_sums;
+int stan_hip_thermal_load_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const int32_t *node_dof,
+                               int64_t n_elem, const int32_t *conn, const int32_t *elem_mat, const uint8_t *elem_type,
+                               int32_t n_mat, const double *mat_E_nu, int64_t n_dof, const int32_t *ndof_reduction,
+                               const double *mat_alpha, const double *dT, double *F, double *load_full, void *sums);
+/* The same with every array except mat_E_nu, mat_alpha and sums in device memory on the context's GPU: read only, ready on
+ * the context's stream, naturally aligned; nothing is stored outside the outputs; complete on return. */
+int stan_hip_thermal_load_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const int32_t *d_node_dof,
+                                   int64_t n_elem, const int32_t *d_conn, const int32_t *d_elem_mat,
+                                   const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
+                                   const int32_t *d_ndof_reduction, const double *mat_alpha, const double *d_dT, double *d_F,
+                                   double *d_load_full, void *sums);
+/* stress [n_elem*48] in/out, as stan_hip_recover_hex8 returns it. */
+int stan_hip_thermal_stress_hex8(stan_ctx *ctx, int64_t n_nodes, const double *dT, int64_t n_elem, const int32_t *conn,
+                                 const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat, const double *mat_E_nu,
+                                 const double *mat_alpha, double *stress);
+int stan_hip_thermal_stress_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *d_dT, int64_t n_elem, const int32_t *d_conn,
+                                     const int32_t *d_elem_mat, const uint8_t *d_elem_type, int32_t n_mat,
+                                     const double *mat_E_nu, const double *mat_alpha, double *d_stress);
+/* The same on the stress kept on the device by stan_hip_recover_hex8_keep (host arrays dT, conn, elem_mat, elem_type of the
+ * results' n_elem elements).  STAN_E_ARG also when the results do not live, whole, on the context's device.  The kept stress
+ * is corrected IN PLACE and the results keep no record of it: call it once per recovery -- a second call takes beta dT off
+ * again, as a second stan_hip_thermal_stress_hex8 on the same array does. */
+int stan_hip_results_thermal_stress(stan_ctx *ctx, stan_results *res, int64_t n_nodes, const double *dT, const int32_t *conn,
+                                    const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat, const double *mat_E_nu,
+                                    const double *mat_alpha);
+/* Phase times of the most recent thermal-load call on this context, as stan_hip_load_vector_times gives them: ms[0] the
+ * element pass, ms[1] the lists, ms[2] the node gather with its reductions; zeros without profiling.  It reads a record of the
+ * context and touches no device: STAN_E_UNSUPPORTED on a multi-device handle (which is no one context); on a context with a
+ * communicator it returns the zeros of a context on which no thermal-load call has run. */
+int stan_hip_thermal_load_times(stan_ctx *ctx, double ms[3]);
+
 /* ---- introspection / parity helpers ------------------------------------------------------- */
 typedef struct stan_matrix_info {
     int64_t n_dof;        /* full DOF count                                      */

@@ -182,6 +182,13 @@ int stan_host_db_get_reduction(stan_db *db, int32_t *red, int64_t *n_fixed, doub
  * STAN_HOST_E_ARG.  The reference ignores Types it does not know (Solver.cs:106, 138). */
 int stan_host_db_get_distributed_loads(stan_db *db, int64_t counts[4], int32_t cap_mat, double *mat_body, int64_t cap_faces,
                                        int32_t *face_elem, uint8_t *face_id, double *face_p, double *disp0);
+/* The BoundaryCondition Types "Temperature" (node IDs, component 0 = dT, the temperature change from the stress-free state;
+ * unlisted nodes have 0; several such BCs add up) and "ThermalExpansion" (MATERIAL IDs, component 0 = alpha, resolved like
+ * "BodyForce"; several add up) of the BCLib as the arrays stan_hip_thermal_load_hex8 takes.  counts[2] = {1 when the file
+ * holds such a BC, n_mat}.  mat_alpha [cap_mat] and dT [n_nodes] are filled when non-NULL (with zeros where no BC speaks); a
+ * capacity that is too small, an unknown node ID and an unknown or non-elastic material ID (reported with the ID) are
+ * STAN_HOST_E_ARG.  The reference ignores Types it does not know. */
+int stan_host_db_get_thermal_loads(stan_db *db, int64_t counts[2], int32_t cap_mat, double *mat_alpha, double *dT);
 /* Result write-back of SolverLinearStatics (Solver.cs:81-90, 171-178, 203-210, Main :56):
  * re-initialises step 0/1, stores disp[n*3] into Node.DispX/Y/Z[1] and strain/stress
  * [e*48] (may be NULL) into Element.Strain[1]/Stress[1], sets Result_StepNo = 1. */

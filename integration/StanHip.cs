@@ -103,6 +103,17 @@ namespace STAN_Solver
         public long n_faces;
     }
 
+    /// stan_thermal_sums (include/stan_hip.h); filled through the IntPtr argument of stan_hip_thermal_load_hex8
+    [StructLayout(LayoutKind.Sequential)]
+    public struct StanThermalSums
+    {
+        public double load_sum_x, load_sum_y, load_sum_z;
+        public double free_sum_x, free_sum_y, free_sum_z;
+        public double volume;
+        public double dT_integral;
+        public long n_fixed;
+    }
+
     internal static class StanHipNative
     {
         // "stan_hip" resolves to libstan_hip.so on Linux (.NET probes lib<name>.so; Mono: <dllmap> or the same probing)
@@ -203,6 +214,28 @@ namespace STAN_Solver
             long n_faces, IntPtr d_face_elem, IntPtr d_face_id, IntPtr d_face_pressure, IntPtr d_disp0, IntPtr d_F,
             IntPtr d_F_solve, IntPtr d_load_full, IntPtr sums);
         [DllImport(Lib)] internal static extern int stan_hip_load_vector_times(IntPtr ctx, [Out] double[] ms);
+
+        // ---- thermal loads: mat_alpha [n_mat], dT [n_nodes]; F [N] in/out or null (pinned: updated in place); load_full
+        //      [n_dof] or null; sums -> StanThermalSums or IntPtr.Zero; at least one output.  The stress [n_elem * 48] loses
+        //      beta dT at its corner's node in xx, yy, zz (pinned: updated in place)
+        [DllImport(Lib)] internal static extern int stan_hip_thermal_load_hex8(
+            IntPtr ctx, long n_nodes, double[] xyz, int[] node_dof, long n_elem, int[] conn, int[] elem_mat, byte[] elem_type,
+            int n_mat, double[] mat_E_nu, long n_dof, int[] ndof_reduction, double[] mat_alpha, double[] dT, double[] F,
+            [Out] double[] load_full, IntPtr sums);
+        [DllImport(Lib)] internal static extern int stan_hip_thermal_load_hex8_dev(
+            IntPtr ctx, long n_nodes, IntPtr d_xyz, IntPtr d_node_dof, long n_elem, IntPtr d_conn, IntPtr d_elem_mat,
+            IntPtr d_elem_type, int n_mat, double[] mat_E_nu, long n_dof, IntPtr d_ndof_reduction, double[] mat_alpha,
+            IntPtr d_dT, IntPtr d_F, IntPtr d_load_full, IntPtr sums);
+        [DllImport(Lib)] internal static extern int stan_hip_thermal_stress_hex8(
+            IntPtr ctx, long n_nodes, double[] dT, long n_elem, int[] conn, int[] elem_mat, byte[] elem_type, int n_mat,
+            double[] mat_E_nu, double[] mat_alpha, double[] stress);
+        [DllImport(Lib)] internal static extern int stan_hip_thermal_stress_hex8_dev(
+            IntPtr ctx, long n_nodes, IntPtr d_dT, long n_elem, IntPtr d_conn, IntPtr d_elem_mat, IntPtr d_elem_type, int n_mat,
+            double[] mat_E_nu, double[] mat_alpha, IntPtr d_stress);
+        [DllImport(Lib)] internal static extern int stan_hip_results_thermal_stress(
+            IntPtr ctx, IntPtr results, long n_nodes, double[] dT, int[] conn, int[] elem_mat, byte[] elem_type, int n_mat,
+            double[] mat_E_nu, double[] mat_alpha);
+        [DllImport(Lib)] internal static extern int stan_hip_thermal_load_times(IntPtr ctx, [Out] double[] ms);
 
         // ---- introspection / parity helpers
         [DllImport(Lib)] internal static extern int stan_hip_matrix_info(IntPtr K, out StanMatrixInfo info);

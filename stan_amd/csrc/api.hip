@@ -881,6 +881,135 @@ int stan_hip_load_vector_times(stan_ctx *ctx, double ms[3]) {
     return STAN_OK;
 }
 
+// Thermal loads (loads.hip): the load vector of a nodal temperature change, and the stress correction.  One device, one rank,
+// for the reason the internal forces give.
+int stan_hip_thermal_load_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const int32_t *d_node_dof,
+                                   int64_t n_elem, const int32_t *d_conn, const int32_t *d_elem_mat,
+                                   const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
+                                   const int32_t *d_red, const double *mat_alpha, const double *d_dT, double *d_F,
+                                   double *d_load_full, void *sums) {
+    if (!ctx) return STAN_E_ARG;
+    STANCHK(internal_forces_refused(ctx, "thermal_load_hex8"));
+    if (!d_xyz || !d_node_dof || !d_red || !mat_E_nu || !mat_alpha || !d_dT || (n_elem > 0 && (!d_conn || !d_elem_mat || !d_elem_type))) {
+        ctx->err = "thermal_load_hex8_dev: null argument";
+        return STAN_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const stan_mesh d{.n_nodes = n_nodes, .n_elem = n_elem, .n_dof = n_dof, .n_mat = n_mat, .xyz = d_xyz,
+                      .node_dof = d_node_dof, .conn = d_conn, .elem_mat = d_elem_mat, .elem_type = d_elem_type, .red = d_red,
+                      .mat_E_nu = mat_E_nu};
+    return stan_thermal_load_device(ctx, d, mat_alpha, d_dT, d_F, d_load_full, (stan_thermal_sums *)sums);
+}
+
+int stan_hip_thermal_load_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const int32_t *node_dof, int64_t n_elem,
+                               const int32_t *conn, const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat,
+                               const double *mat_E_nu, int64_t n_dof, const int32_t *red, const double *mat_alpha,
+                               const double *dT, double *F, double *load_full, void *sums) {
+    if (!ctx) return STAN_E_ARG;
+    STANCHK(internal_forces_refused(ctx, "thermal_load_hex8"));
+    if (!xyz || !node_dof || !red || !mat_E_nu || !mat_alpha || !dT || n_nodes <= 0 || n_mat <= 0 || n_elem < 0 ||
+        n_dof != n_nodes * 3 || (n_elem > 0 && (!conn || !elem_mat || !elem_type))) {
+        ctx->err = "thermal_load_hex8: null or empty argument, or n_dof != 3 n_nodes";
+        return STAN_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const stan_mesh m{.n_nodes = n_nodes, .n_elem = n_elem, .n_dof = n_dof, .n_mat = n_mat, .xyz = xyz, .node_dof = node_dof,
+                      .conn = conn, .elem_mat = elem_mat, .elem_type = elem_type, .red = red, .mat_E_nu = mat_E_nu};
+    // the length of F is fixed by the reduction map alone; every other integer is checked on the device (loads.hip)
+    const size_t N = (size_t)(n_dof - count_fixed(m));
+    mesh_dbufs bufs; dbuf<double> dt, dF, dl;
+    STANCHK(bufs.upload(ctx, m));
+    STANCHK(dt.upload(ctx, dT, (size_t)n_nodes));
+    if (F) STANCHK(dF.upload(ctx, F, N));
+    if (load_full) STANCHK(dl.alloc(ctx, (size_t)n_dof));
+    const int rc = stan_thermal_load_device(ctx, bufs.dev, mat_alpha, dt.p, F ? dF.p : nullptr, load_full ? dl.p : nullptr,
+                                            (stan_thermal_sums *)sums);
+    if (rc == STAN_OK) {
+        if (F && N) HIPCHK(ctx, hipMemcpyAsync(F, dF.p, N * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (load_full) HIPCHK(ctx, hipMemcpyAsync(load_full, dl.p, (size_t)n_dof * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    // the uploads above are stream-ordered with the kernels; the host arrays must outlive them
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return rc;
+}
+
+int stan_hip_thermal_load_times(stan_ctx *ctx, double ms[3]) {
+    if (!ctx || !ms) return STAN_E_ARG;
+    STAN_NO_GROUP(ctx, "thermal_load_times");
+    for (int k = 0; k < 3; k++) ms[k] = ctx->prof_thermal_ms[k];
+    return STAN_OK;
+}
+
+int stan_hip_thermal_stress_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *d_dT, int64_t n_elem, const int32_t *d_conn,
+                                     const int32_t *d_elem_mat, const uint8_t *d_elem_type, int32_t n_mat,
+                                     const double *mat_E_nu, const double *mat_alpha, double *d_stress) {
+    if (!ctx) return STAN_E_ARG;
+    STANCHK(internal_forces_refused(ctx, "thermal_stress_hex8"));
+    if (!d_dT || !mat_E_nu || !mat_alpha || (n_elem > 0 && (!d_conn || !d_elem_mat || !d_elem_type || !d_stress))) {
+        ctx->err = "thermal_stress_hex8_dev: null argument";
+        return STAN_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return stan_thermal_stress_device(ctx, n_nodes, d_dT, n_elem, d_conn, d_elem_mat, d_elem_type, n_mat, mat_E_nu, mat_alpha, d_stress);
+}
+}  // extern "C"
+namespace {
+// the host arrays of the thermal stress pass go to the device; d_stress is there already, or null: then `stress` goes up and
+// comes back corrected
+int thermal_stress_host(stan_ctx *ctx, int64_t n_nodes, const double *dT, int64_t n_elem, const int32_t *conn, const int32_t *elem_mat,
+                        const uint8_t *elem_type, int32_t n_mat, const double *mat_E_nu, const double *mat_alpha, double *stress,
+                        double *d_stress) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    dbuf<double> dt, ds; dbuf<int32_t> dc, dm; dbuf<uint8_t> dty;
+    STANCHK(dt.upload(ctx, dT, (size_t)n_nodes));
+    STANCHK(dc.upload(ctx, conn, (size_t)n_elem * 8));
+    STANCHK(dm.upload(ctx, elem_mat, (size_t)n_elem));
+    STANCHK(dty.upload(ctx, elem_type, (size_t)n_elem));
+    if (!d_stress) {
+        STANCHK(ds.upload(ctx, stress, (size_t)n_elem * 48));
+        d_stress = ds.p;
+    }
+    const int rc = stan_thermal_stress_device(ctx, n_nodes, dt.p, n_elem, dc.p, dm.p, dty.p, n_mat, mat_E_nu, mat_alpha, d_stress);
+    if (rc == STAN_OK && ds.p && n_elem)
+        HIPCHK(ctx, hipMemcpyAsync(stress, ds.p, (size_t)n_elem * 48 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    // the uploads above are stream-ordered with the kernels; the host arrays must outlive them
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return rc;
+}
+}  // namespace
+extern "C" {
+
+int stan_hip_thermal_stress_hex8(stan_ctx *ctx, int64_t n_nodes, const double *dT, int64_t n_elem, const int32_t *conn,
+                                 const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat, const double *mat_E_nu,
+                                 const double *mat_alpha, double *stress) {
+    if (!ctx) return STAN_E_ARG;
+    STANCHK(internal_forces_refused(ctx, "thermal_stress_hex8"));
+    if (!dT || !mat_E_nu || !mat_alpha || n_nodes <= 0 || n_mat <= 0 || n_elem < 0 ||
+        (n_elem > 0 && (!conn || !elem_mat || !elem_type || !stress))) {
+        ctx->err = "thermal_stress_hex8: null or empty argument";
+        return STAN_E_ARG;
+    }
+    return thermal_stress_host(ctx, n_nodes, dT, n_elem, conn, elem_mat, elem_type, n_mat, mat_E_nu, mat_alpha, stress, nullptr);
+}
+
+int stan_hip_results_thermal_stress(stan_ctx *ctx, stan_results *res, int64_t n_nodes, const double *dT, const int32_t *conn,
+                                    const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat, const double *mat_E_nu,
+                                    const double *mat_alpha) {
+    if (!ctx) return STAN_E_ARG;
+    STANCHK(internal_forces_refused(ctx, "results_thermal_stress"));
+    if (!res || !dT || !mat_E_nu || !mat_alpha || n_nodes <= 0 || n_mat <= 0 || (res->n_elem > 0 && (!conn || !elem_mat || !elem_type))) {
+        ctx->err = "results_thermal_stress: null or empty argument";
+        return STAN_E_ARG;
+    }
+    if (res->parts.size() != 1 || res->parts[0].device != ctx->device || res->parts[0].e0 != 0 ||
+        res->parts[0].e1 != res->n_elem) {
+        ctx->err = "results_thermal_stress: the results are not held, whole, on this context's device";
+        return STAN_E_ARG;
+    }
+    return thermal_stress_host(ctx, n_nodes, dT, res->n_elem, conn, elem_mat, elem_type, n_mat, mat_E_nu, mat_alpha, nullptr,
+                               res->parts[0].d_stress);
+}
+
 int stan_hip_matrix_part_info(stan_matrix *K, int32_t part, stan_matrix_info *o) {
     if (!K || !o || part < 0) return STAN_E_ARG;
     if (K->parts.empty()) return part == 0 ? stan_hip_matrix_info(K, o) : STAN_E_ARG;

@@ -266,6 +266,7 @@ struct stan_ctx {
     bool profiling = false;
     stan_profile prof{};
     double prof_loads_ms[3] = {0, 0, 0};   // last load-vector call: element pass | lists | gather (stan_hip_load_vector_times)
+    double prof_thermal_ms[3] = {0, 0, 0}; // last thermal-load call, the same phases (stan_hip_thermal_load_times)
     stan_pool pool;
     stan_cg_ws ws;
     std::vector<stan_matrix *> matrices;  // alive matrices of this context (detached when it is destroyed)
@@ -482,6 +483,15 @@ int stan_elem_args_check(stan_ctx *ctx, dev_scope &tmp, const char *who, const s
 int stan_load_vector_device(stan_ctx *ctx, const stan_mesh &d, const double *mat_body, int64_t n_faces, const int32_t *d_face_elem,
                             const uint8_t *d_face_id, const double *d_face_pressure, const double *d_disp0, double *d_F,
                             double *d_F_solve, double *d_load_full, stan_load_sums *sums);
+// The thermal load of a nodal temperature change d_dT [n_nodes] (stan_hip_thermal_load_hex8); d as above; mat_alpha [n_mat]
+// and sums are host memory.  The same checks; det J == 0 in a heated element is found before any output is stored.
+int stan_thermal_load_device(stan_ctx *ctx, const stan_mesh &d, const double *mat_alpha, const double *d_dT, double *d_F,
+                             double *d_load_full, stan_thermal_sums *sums);
+// d_stress [n_elem][8][6] loses beta_m dT at its corner's node in xx, yy, zz (stan_hip_thermal_stress_hex8); the integers are
+// checked on the device first.  Synchronises the stream.
+int stan_thermal_stress_device(stan_ctx *ctx, int64_t n_nodes, const double *d_dT, int64_t n_elem, const int32_t *d_conn,
+                               const int32_t *d_elem_mat, const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu,
+                               const double *mat_alpha, double *d_stress);
 
 // ---- comm.cpp -------------------------------------------------------------------------------
 int stan_comm_allreduce_sum_f64(stan_ctx *ctx, double *d_buf, size_t count);

@@ -5,6 +5,8 @@
 //                                                                 the cyclic successors of the axis; unit weights, +-1/sqrt 3
 //   prescribed   F_solve = F - f_int(u0)|free                     u0 used at the fixed DOFs only (stan_internal_forces_device)
 // No J^-1 is formed for the first two: det J == 0 is no error there.  No counterpart in the reference.
+// The thermal load and the thermal stress of section 3.9 are at the end of the kernels: one more element pass (k_th_elem) in
+// front of the same gather, and one pass over the recovered stress (k_th_stress).
 // Faces in CHEXA order:  0 xi=-1 {0,3,4,7}  1 xi=+1 {1,2,5,6}  2 eta=-1 {0,1,4,5}  3 eta=+1 {2,3,6,7}  4 zeta=-1 {0,1,2,3}
 // 5 zeta=+1 {4,5,6,7}; the face list is sorted by face_elem * 6 + face_id, strictly.
 // Phases, all bit-reproducible (no atomics on doubles):
@@ -184,7 +186,216 @@ k_ld_finish(int64_t n_gblocks, const double *__restrict__ gpartial, int64_t n_eb
         for (int k = 0; k < NGS + NES; k++) out[k] = a[k];
 }
 
+// ---- thermal loads ------------------------------------------------------------------------------
+//   f_a = sum_g B_a(q_g)^T (beta_m dT(q_g) (1,1,1,0,0,0)) det J_g w,  dT(q) = sum_a N_a(q) dT_a,  beta_m = E alpha / (1 - 2 nu)
+// at the element's own STIFFNESS rule (HEX8_G1: one point, weight 8), unlike the body force above: with it K u = f_th holds
+// term by term for u = alpha dT x.  The element pass is k_th_elem; the node gather and the finishing block are k_ld_gather and
+// k_ld_finish as they stand (the element sums are the heated volume and the integral of dT).
+// mat_beta [n_mat][2] = {beta, alpha}: an element whose alpha is 0 stores zeros, is not looked at and raises no STAN_E_DETJ.
+// Launch bound 4 waves per SIMD: without it the backend hoists all eight gradients (130 VGPRs, 3 waves); with it 70 VGPRs,
+// 7 waves, no scratch -- the pass waits on its node gathers, so the waves are worth more than the hoisting.
+__global__ void __launch_bounds__(256, 4)
+k_th_elem(int64_t n_elem, const double *__restrict__ xyz, const double *__restrict__ dT, const int32_t *__restrict__ conn,
+          const int32_t *__restrict__ elem_mat, const uint8_t *__restrict__ elem_type, const double *__restrict__ mat_beta,
+          double *__restrict__ fe, double *__restrict__ partial, long long *bad_elem) {
+    __shared__ __attribute__((aligned(16))) double lds[4][8 * ELEM_REC];
+    __shared__ double sh[4][NES];
+    const elem_lanes L = elem_lanes_here(n_elem);
+    const int g = L.g;
+    int type = STAN_HEX8_G2;
+    double beta = 0.0;
+    bool hot = false;   // a valid element whose material expands
+    if (L.valid) {
+        const int32_t m = elem_mat[L.e];
+        type = elem_type[L.e];
+        beta = mat_beta[2 * m];
+        hot = mat_beta[2 * m + 1] != 0.0;
+    }
+    double mine[3] = {0, 0, 0}, acc[NES] = {0, 0};
+    if (__any(hot)) {   // wave-uniform: a wave without a heated element stores zeros and does nothing else
+        double *rec = lds[L.wv] + L.el * ELEM_REC;
+        if (L.valid) {   // lane g loads node g only: its coordinates, and its dT into the record's displacement slot
+            const int64_t nd = elem_load_node<false>(rec, L, conn, xyz, nullptr);
+            rec[24 + g] = dT[nd];
+        }
+        wave_sync();
+        double o[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, px = 0, py = 0, pz = 0, s = 0, sc = 0;
+        if (hot) {
+            // HEX8_G1: every lane evaluates the one point (location 0); its weight is 8 on lane 0 and 0 on the others
+            const double det = hex8_gp_setup(rec, type, g, o);
+            if (det == 0.0) atomicMin(bad_elem, (long long)L.e);
+            hex8_gauss_point(type, g, px, py, pz);
+            double t = 0.0;
+#pragma unroll
+            for (int a = 0; a < 8; a++) t += hex8_shape(a, px, py, pz) * rec[24 + a];   // dT(q)
+            sc = det == 0.0 ? 0.0 : o[9];   // det J_g * w (a singular point is reported, its term left out)
+            s = beta * t;
+            acc[0] = sc;
+            acc[1] = t * sc;
+        }
+        // lane g: B_g^T (s, s, s, 0, 0, 0) * det J_g w for node a = grad N_a * s * sc, then the sum over the 8 lanes of the
+        // element; node a's three components end up on lane a.  (elem_bt_sum with the three zero shear terms left out)
+#pragma unroll
+        for (int a = 0; a < 8; a++) {
+            double gr[3] = {0, 0, 0};
+            if (sc != 0.0) hex8_grad(o, a, px, py, pz, gr);
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const double v = elem_sum((gr[c] * s) * sc);
+                if (a == g) mine[c] = v;
+            }
+        }
+        wave_sync();   // every lane is done with the records
+    }
+    elem_store_staged<3, false>(lds[L.wv], L, n_elem, mine, fe);   // three 512-B lines per wave
+    block_sums(acc, sh);
+    if (threadIdx.x == 0) {
+        partial[(int64_t)blockIdx.x * NES] = acc[0];
+        partial[(int64_t)blockIdx.x * NES + 1] = acc[1];
+    }
+}
+
+// ---- thermal stress: sigma[e][i][c] -= beta_m dT[conn[e][i]] for c = xx, yy, zz, one fused multiply-add (one rounding) --------
+// One lane per entry of [n_elem][8][6]: the whole array is read and written back as full lines; the shear entries return as
+// they came.
+__global__ void __launch_bounds__(256)
+k_th_stress(int64_t n_entries, const double *__restrict__ dT, const int32_t *__restrict__ conn, const int32_t *__restrict__ elem_mat,
+            const double *__restrict__ mat_beta, double *stress) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_entries) return;
+    double v = stress[t];
+    if (t % 6 < 3) v = fma(-mat_beta[2 * elem_mat[t / 48]], dT[conn[t / 6]], v);
+    stress[t] = v;
+}
+
+// the integers of the thermal stress pass: status[SS_ERRBITS] |= IF_*, status[SS_AUX] = the first HEX8_G1 element
+__global__ void __launch_bounds__(256)
+k_th_stress_check(int64_t n_nodes, int64_t n_elem, int32_t n_mat, const int32_t *__restrict__ conn, const int32_t *__restrict__ elem_mat,
+                  const uint8_t *__restrict__ elem_type, int64_t *status) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_elem * 8) return;
+    unsigned long long bits = 0;
+    if (conn[t] < 0 || conn[t] >= n_nodes) bits |= IF_CONN;
+    if ((t & 7) == 0) {
+        const int64_t e = t >> 3;
+        if (elem_mat[e] < 0 || elem_mat[e] >= n_mat) bits |= IF_MAT;
+        if (elem_type[e] == STAN_HEX8_G1) atomicMin((long long *)&status[SS_AUX], (long long)e);
+        else if (elem_type[e] != STAN_HEX8_G2) bits |= IF_TYPE;
+    }
+    if (bits) atomicOr((unsigned long long *)&status[SS_ERRBITS], bits);
+}
+
+// {beta, alpha} of every material, beta = E alpha / (1 - 2 nu) in fp64 exactly as written
+std::vector<double> thermal_beta(int32_t n_mat, const double *mat_E_nu, const double *mat_alpha) {
+    std::vector<double> b(2 * (size_t)n_mat);
+    for (int32_t m = 0; m < n_mat; m++) {
+        const double E = mat_E_nu[2 * m], nu = mat_E_nu[2 * m + 1], alpha = mat_alpha[m];
+        b[2 * m] = E * alpha / (1 - 2 * nu);
+        b[2 * m + 1] = alpha;
+    }
+    return b;
+}
+
 }  // namespace
+
+int stan_thermal_load_device(stan_ctx *ctx, const stan_mesh &d, const double *mat_alpha, const double *d_dT, double *d_F,
+                             double *d_load_full, stan_thermal_sums *sums) {
+    const char *who = "thermal_load_hex8";
+    const int64_t n_nodes = d.n_nodes, n_elem = d.n_elem, n_dof = d.n_dof, n_mat = d.n_mat;
+    auto bad = [&](const char *why, int rc) { ctx->err = std::string(who) + ": " + why; return rc; };
+    if (n_nodes <= 0 || n_elem < 0 || n_mat <= 0 || n_dof != n_nodes * 3) return bad("n_dof must be 3 n_nodes > 0, n_mat > 0", STAN_E_ARG);
+    if (n_elem >= (int64_t)1 << 28) return bad("more than 2^28 elements", STAN_E_ARG);
+    if (n_dof > 0x7fffffffLL) return bad("more than 2^31 DOFs", STAN_E_ARG);
+    if (!d_F && !d_load_full && !sums) return bad("none of F / load_full / sums asked for", STAN_E_ARG);
+    hipStream_t st = ctx->stream;
+    ctx->prof_thermal_ms[0] = ctx->prof_thermal_ms[1] = ctx->prof_thermal_ms[2] = 0;
+    // ---- the checks, before anything is indexed with the caller's integers
+    dev_scope tmp(ctx);
+    int64_t n_fixed;
+    STANCHK(stan_elem_args_check(ctx, tmp, who, d, 0, nullptr, nullptr, &n_fixed));
+    const int64_t n_red = n_dof - n_fixed;
+
+    phase_timer pt(ctx, 5);   // element pass | lists | (the det J report) | gather + reductions
+    const int64_t n_gblocks = nblk(n_nodes, 256), n_eblocks = nblk(n_elem, 32);
+    const std::vector<double> beta = thermal_beta((int32_t)n_mat, d.mat_E_nu, mat_alpha);   // outlives the stream's copy
+    double *d_beta, *d_fe, *d_gpartial, *d_epartial, *d_out;
+    STANCHK(tmp.alloc(&d_beta, beta.size()));
+    STANCHK(tmp.alloc(&d_fe, (size_t)(n_elem > 0 ? n_elem : 1) * 24));
+    STANCHK(tmp.alloc(&d_gpartial, (size_t)n_gblocks * NGS));
+    STANCHK(tmp.alloc(&d_epartial, (size_t)(n_eblocks > 0 ? n_eblocks : 1) * NES));
+    STANCHK(tmp.alloc(&d_out, (size_t)NGS + NES));
+    HIPCHK(ctx, hipMemcpyAsync(d_beta, beta.data(), beta.size() * 8, hipMemcpyHostToDevice, st));
+    STANCHK(pt.mark(0));
+    if (n_elem > 0)   // 8 lanes per element, 8 elements per wave, 32 per workgroup
+        hipLaunchKernelGGL(k_th_elem, dim3((unsigned)n_eblocks), dim3(256), 0, st, n_elem, d.xyz, d_dT, d.conn, d.elem_mat, d.elem_type,
+                           d_beta, d_fe, d_epartial, (long long *)(ctx->d_status + SS_BAD_ELEM));
+    STANCHK(pt.mark(1));
+    int64_t *d_ptr;
+    int32_t *d_list;
+    STANCHK(stan_incidence_lists(ctx, tmp, n_nodes, n_elem, d.conn, true, &d_ptr, &d_list));
+    STANCHK(pt.mark(2));
+    // det J == 0 in a heated element: known before the gather stores into the caller's arrays
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_BAD_ELEM, ctx->d_status + SS_BAD_ELEM, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    STANCHK(stan_detj_check(ctx, " (thermal load)"));
+    STANCHK(pt.mark(3));
+    hipLaunchKernelGGL(k_ld_gather, dim3((unsigned)n_gblocks), dim3(256), 0, st, n_nodes, d_ptr, d_list, d_fe, d.node_dof, d.red, n_red,
+                       nullptr, d_F, nullptr, d_load_full, d_gpartial);
+    if (sums) hipLaunchKernelGGL(k_ld_finish, dim3(1), dim3(256), 0, st, n_gblocks, d_gpartial, n_eblocks, d_epartial, d_out);
+    STANCHK(pt.mark(4));
+    HIPCHK(ctx, hipGetLastError());
+    double out[NGS + NES];
+    if (sums) HIPCHK(ctx, hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));   // the temporaries go back to the context behind the kernels
+    STANCHK(pt.read(0, 1, &ctx->prof_thermal_ms[0]));
+    STANCHK(pt.read(1, 2, &ctx->prof_thermal_ms[1]));
+    STANCHK(pt.read(3, 4, &ctx->prof_thermal_ms[2]));
+    if (sums) {
+        for (int c = 0; c < 3; c++) { sums->load_sum[c] = out[c]; sums->free_sum[c] = out[3 + c]; }
+        sums->volume = out[NGS];
+        sums->dT_integral = out[NGS + 1];
+        sums->n_fixed = n_fixed;
+    }
+    return STAN_OK;
+}
+
+int stan_thermal_stress_device(stan_ctx *ctx, int64_t n_nodes, const double *d_dT, int64_t n_elem, const int32_t *d_conn,
+                               const int32_t *d_elem_mat, const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu,
+                               const double *mat_alpha, double *d_stress) {
+    auto bad = [&](const char *why, int rc) { ctx->err = std::string("thermal_stress_hex8: ") + why; return rc; };
+    if (n_nodes <= 0 || n_elem < 0 || n_mat <= 0) return bad("n_nodes and n_mat must be positive", STAN_E_ARG);
+    if (n_elem >= (int64_t)1 << 28) return bad("more than 2^28 elements", STAN_E_ARG);
+    if (n_elem == 0) return STAN_OK;
+    hipStream_t st = ctx->stream;
+    int64_t *status = ctx->d_status;
+    const long long init[3] = {0, 0x7fffffffffffffffLL, 0x7fffffffffffffffLL};
+    HIPCHK(ctx, hipMemcpyAsync(status + SS_ERRBITS, &init[0], 8, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(status + SS_BAD_ELEM, &init[1], 16, hipMemcpyHostToDevice, st));   // SS_BAD_ELEM, SS_AUX
+    hipLaunchKernelGGL(k_th_stress_check, dim3(nblk(n_elem * 8, 256)), dim3(256), 0, st, n_nodes, n_elem, n_mat, d_conn, d_elem_mat,
+                       d_elem_type, status);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_ERRBITS, status + SS_ERRBITS, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, status + SS_AUX, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const int64_t bits = ctx->h_status[SS_ERRBITS];
+    if (bits & IF_CONN) return bad("node index out of range", STAN_E_ARG);
+    if (bits & IF_MAT) return bad("elem_mat out of range", STAN_E_ARG);
+    if (bits & IF_TYPE) return bad("element type is neither HEX8_G1 nor HEX8_G2", STAN_E_ARG);
+    if (ctx->h_status[SS_AUX] != init[2]) {
+        ctx->bad_elem = ctx->h_status[SS_AUX];
+        return bad(("element " + std::to_string(ctx->bad_elem) + " is HEX8_G1 (no nodal stress: the recovery refuses it)").c_str(), STAN_E_UNSUPPORTED);
+    }
+    dev_scope tmp(ctx);
+    const std::vector<double> beta = thermal_beta(n_mat, mat_E_nu, mat_alpha);   // outlives the stream's copy
+    double *d_beta;
+    STANCHK(tmp.alloc(&d_beta, beta.size()));
+    HIPCHK(ctx, hipMemcpyAsync(d_beta, beta.data(), beta.size() * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_th_stress, dim3(nblk(n_elem * 48, 256)), dim3(256), 0, st, n_elem * 48, d_dT, d_conn, d_elem_mat, d_beta, d_stress);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return STAN_OK;
+}
 
 int stan_load_vector_device(stan_ctx *ctx, const stan_mesh &d, const double *mat_body, int64_t n_faces, const int32_t *d_face_elem,
                             const uint8_t *d_face_id, const double *d_face_pressure, const double *d_disp0, double *d_F,

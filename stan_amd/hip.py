@@ -55,6 +55,8 @@ EXPORTS = [
     "stan_hip_result_scalars_hex8", "stan_hip_results_scalars",
     "stan_hip_internal_forces_hex8", "stan_hip_internal_forces_hex8_dev",
     "stan_hip_load_vector_hex8", "stan_hip_load_vector_hex8_dev", "stan_hip_load_vector_times",
+    "stan_hip_thermal_load_hex8", "stan_hip_thermal_load_hex8_dev", "stan_hip_thermal_load_times",
+    "stan_hip_thermal_stress_hex8", "stan_hip_thermal_stress_hex8_dev", "stan_hip_results_thermal_stress",
 ]
 # only in the lab build (stan_amd/csrc/lab/stan_hip_lab.h, selected with STAN_HIP_LIB)
 LAB_EXPORTS = ["stan_hip_csr_spmv_bench", "stan_hip_lab_placement_map", "stan_hip_lab_placement_variants", "stan_hip_lab_placement_alloc", "stan_hip_lab_placement_rounds", "stan_hip_lab_placement_cross", "stan_hip_lab_incg_penalty", "stan_hip_lab_placement_vecalloc", "stan_hip_lab_placement_vecshape", "stan_hip_lab_pairing_pmc"]
@@ -101,6 +103,15 @@ class LoadSums(C.Structure):
     """stan_load_sums (include/stan_hip.h)"""
     _fields_ = [("load_sum", C.c_double * 3), ("free_sum", C.c_double * 3), ("volume", C.c_double), ("area", C.c_double),
                 ("n_fixed", C.c_int64), ("n_faces", C.c_int64)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k.endswith("_sum") else getattr(self, k)) for k, _ in self._fields_}
+
+
+class ThermalSums(C.Structure):
+    """stan_thermal_sums (include/stan_hip.h)"""
+    _fields_ = [("load_sum", C.c_double * 3), ("free_sum", C.c_double * 3), ("volume", C.c_double), ("dT_integral", C.c_double),
+                ("n_fixed", C.c_int64)]
 
     def as_dict(self):
         return {k: (list(getattr(self, k)) if k.endswith("_sum") else getattr(self, k)) for k, _ in self._fields_}
@@ -466,6 +477,92 @@ class Context:
         self._chk(self.lib.stan_hip_load_vector_times(self.h, ms))
         return dict(loads_elem_ms=ms[0], loads_list_ms=ms[1], loads_gather_ms=ms[2])
 
+    # -- thermal loads --------------------------------------------------------------------------
+    def thermal_load_hex8(self, xyz, node_dof, conn, elem_mat, elem_type, mat_E_nu, red, mat_alpha, dT, F=None, load_full=True,
+                          sums=True):
+        """stan_hip_thermal_load_hex8 from host arrays: (F, load_full, sums ThermalSums).  mat_alpha [n_mat], dT [n_nodes]
+        (None is passed on as NULL); F: the reduced load vector to add to (a copy is returned) or None.  An output not asked
+        for is None."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        node_dof = np.ascontiguousarray(node_dof, dtype=np.int32)
+        conn = np.ascontiguousarray(conn, dtype=np.int32).reshape(-1, 8)
+        elem_mat = np.ascontiguousarray(elem_mat, dtype=np.int32)
+        elem_type = np.ascontiguousarray(elem_type, dtype=np.uint8)
+        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        red = np.ascontiguousarray(red, dtype=np.int32)
+        n_dof = red.shape[0]
+        N = n_dof - int((red == -1).sum())
+        al = None if mat_alpha is None else np.ascontiguousarray(mat_alpha, dtype=np.float64).reshape(-1)
+        if al is not None and al.shape[0] != mat_E_nu.shape[0]:
+            raise ValueError("thermal_load_hex8: mat_alpha must be [n_mat]")
+        t = None if dT is None else np.ascontiguousarray(dT, dtype=np.float64).reshape(-1)
+        if t is not None and t.shape[0] != xyz.shape[0]:
+            raise ValueError("thermal_load_hex8: dT must be [n_nodes]")
+        Fo = None if F is None else np.array(F, dtype=np.float64).reshape(-1)
+        if Fo is not None and Fo.shape[0] != N:
+            raise ValueError("thermal_load_hex8: F must be [n_dof - n_fixed]")
+        lf = np.zeros(n_dof) if load_full else None
+        q = ThermalSums() if sums else None
+        self._chk(self.lib.stan_hip_thermal_load_hex8(
+            self.h, C.c_int64(xyz.shape[0]), _ptr(xyz, C.c_double), _ptr(node_dof, C.c_int32), C.c_int64(conn.shape[0]),
+            _ptr(conn, C.c_int32), _ptr(elem_mat, C.c_int32), _ptr(elem_type, C.c_uint8), C.c_int32(mat_E_nu.shape[0]),
+            _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _ptr(red, C.c_int32), _ptr(al, C.c_double), _ptr(t, C.c_double),
+            _ptr(Fo, C.c_double), _ptr(lf, C.c_double), C.byref(q) if sums else None))
+        return Fo, lf, q
+
+    def thermal_load_hex8_dev(self, n_nodes, d_xyz, d_node_dof, n_elem, d_conn, d_elem_mat, d_elem_type, mat_E_nu, n_dof, d_red,
+                              mat_alpha, d_dT, d_F=None, d_load_full=None, sums=True):
+        """All d_* are device pointers (ints, e.g. torch tensor.data_ptr()) or None; mat_alpha a host array.  Returns the
+        ThermalSums (None when not asked for)."""
+        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        al = None if mat_alpha is None else np.ascontiguousarray(mat_alpha, dtype=np.float64).reshape(-1)
+        q = ThermalSums() if sums else None
+        opt = lambda p: None if p is None else _dev(p, C.c_double)
+        self._chk(self.lib.stan_hip_thermal_load_hex8_dev(
+            self.h, C.c_int64(n_nodes), _dev(d_xyz, C.c_double), _dev(d_node_dof, C.c_int32), C.c_int64(n_elem),
+            _dev(d_conn, C.c_int32), _dev(d_elem_mat, C.c_int32), _dev(d_elem_type, C.c_uint8), C.c_int32(mat_E_nu.shape[0]),
+            _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _dev(d_red, C.c_int32), _ptr(al, C.c_double), opt(d_dT), opt(d_F),
+            opt(d_load_full), C.byref(q) if sums else None))
+        return q
+
+    def thermal_load_times(self):
+        """dict(thermal_elem_ms, thermal_list_ms, thermal_gather_ms) of the last thermal-load call (profiling enabled)."""
+        ms = (C.c_double * 3)()
+        self._chk(self.lib.stan_hip_thermal_load_times(self.h, ms))
+        return dict(thermal_elem_ms=ms[0], thermal_list_ms=ms[1], thermal_gather_ms=ms[2])
+
+    def _thermal_stress_args(self, dT, conn, elem_mat, elem_type, mat_E_nu, mat_alpha):
+        dT = np.ascontiguousarray(dT, dtype=np.float64).reshape(-1)
+        conn = np.ascontiguousarray(conn, dtype=np.int32).reshape(-1, 8)
+        elem_mat = np.ascontiguousarray(elem_mat, dtype=np.int32)
+        elem_type = np.ascontiguousarray(elem_type, dtype=np.uint8)
+        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        al = np.ascontiguousarray(mat_alpha, dtype=np.float64).reshape(-1)
+        if al.shape[0] != mat_E_nu.shape[0] or elem_mat.shape[0] != conn.shape[0] or elem_type.shape[0] != conn.shape[0]:
+            raise ValueError("thermal stress: mat_alpha must be [n_mat], elem_mat and elem_type [n_elem]")
+        return dT, conn, elem_mat, elem_type, mat_E_nu, al
+
+    def thermal_stress_hex8(self, dT, conn, elem_mat, elem_type, mat_E_nu, mat_alpha, stress):
+        """stan_hip_thermal_stress_hex8: the corrected copy of stress [n_elem, 8, 6]."""
+        dT, conn, elem_mat, elem_type, mat_E_nu, al = self._thermal_stress_args(dT, conn, elem_mat, elem_type, mat_E_nu, mat_alpha)
+        out = np.array(stress, dtype=np.float64).reshape(-1, 8, 6)
+        if out.shape[0] != conn.shape[0]:
+            raise ValueError("thermal_stress_hex8: stress must be [n_elem, 8, 6]")
+        self._chk(self.lib.stan_hip_thermal_stress_hex8(
+            self.h, C.c_int64(dT.shape[0]), _ptr(dT, C.c_double), C.c_int64(conn.shape[0]), _ptr(conn, C.c_int32),
+            _ptr(elem_mat, C.c_int32), _ptr(elem_type, C.c_uint8), C.c_int32(mat_E_nu.shape[0]), _ptr(mat_E_nu, C.c_double),
+            _ptr(al, C.c_double), _ptr(out, C.c_double)))
+        return out
+
+    def thermal_stress_hex8_dev(self, n_nodes, d_dT, n_elem, d_conn, d_elem_mat, d_elem_type, mat_E_nu, mat_alpha, d_stress):
+        """All d_* are device pointers (ints); d_stress [n_elem, 8, 6] doubles is corrected in place."""
+        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        al = np.ascontiguousarray(mat_alpha, dtype=np.float64).reshape(-1)
+        self._chk(self.lib.stan_hip_thermal_stress_hex8_dev(
+            self.h, C.c_int64(n_nodes), _dev(d_dT, C.c_double), C.c_int64(n_elem), _dev(d_conn, C.c_int32),
+            _dev(d_elem_mat, C.c_int32), _dev(d_elem_type, C.c_uint8), C.c_int32(mat_E_nu.shape[0]), _ptr(mat_E_nu, C.c_double),
+            _ptr(al, C.c_double), _dev(d_stress, C.c_double)))
+
     # -- assembly ------------------------------------------------------------------------
     def assemble_hex8(self, xyz, node_dof, conn, elem_mat, elem_type, mat_E_nu, red):
         xyz = np.ascontiguousarray(xyz, dtype=np.float64)
@@ -523,6 +620,15 @@ class Results:
         return self.ctx._scalars(
             lambda nn, d, n_e, c, ns, s, pt, ce: self.ctx.lib.stan_hip_results_scalars(self.ctx.h, self.h, nn, d, c, ns, s, pt, ce),
             disp, conn, sel, point, cell)
+
+    def thermal_stress(self, dT, conn, elem_mat, elem_type, mat_E_nu, mat_alpha):
+        """Context.thermal_stress_hex8 on the kept stress, in place (stan_hip_results_thermal_stress)."""
+        dT, conn, elem_mat, elem_type, mat_E_nu, al = self.ctx._thermal_stress_args(dT, conn, elem_mat, elem_type, mat_E_nu, mat_alpha)
+        if conn.shape[0] != self.n_elem:
+            raise ValueError("Results.thermal_stress: conn must be [n_elem, 8]")
+        self.ctx._chk(self.ctx.lib.stan_hip_results_thermal_stress(
+            self.ctx.h, self.h, C.c_int64(dT.shape[0]), _ptr(dT, C.c_double), _ptr(conn, C.c_int32), _ptr(elem_mat, C.c_int32),
+            _ptr(elem_type, C.c_uint8), C.c_int32(mat_E_nu.shape[0]), _ptr(mat_E_nu, C.c_double), _ptr(al, C.c_double)))
 
     def free(self):
         if getattr(self, "h", None):

@@ -235,7 +235,7 @@ EXPORTS += [
     "stan_host_db_assign_part", "stan_host_db_add_bc", "stan_host_db_set_analysis",
     "stan_host_db_sizes", "stan_host_db_get_analysis", "stan_host_db_assign_dof",
     "stan_host_db_get_flat", "stan_host_db_get_reduction", "stan_host_db_set_results",
-    "stan_host_db_get_results", "stan_host_db_get_distributed_loads",
+    "stan_host_db_get_results", "stan_host_db_get_distributed_loads", "stan_host_db_get_thermal_loads",
 ]
 
 
@@ -398,6 +398,16 @@ class Db:
         return dict(any=bool(cnt[0]), mat_body=mb[:nm] if nm else None, face_elem=fe[:nf] if nf else None,
                     face_id=fi[:nf] if nf else None, face_p=fp[:nf] if nf else None,
                     disp0=u0 if np.any(u0) else None, n_prescribed=int(cnt[3]))
+
+    def thermal_loads(self):
+        """BuildThermalLoads: dict(any, mat_alpha [n_mat], dT [n_nodes]) from the "Temperature" / "ThermalExpansion" BCs."""
+        cnt = (C.c_int64 * 2)()
+        self._chk(self.lib.stan_host_db_get_thermal_loads(self.h, cnt, C.c_int32(0), None, None), "thermal_loads")
+        nm, nn = int(cnt[1]), self.sizes()["nodes"]
+        al, dT = np.zeros(max(nm, 1)), np.zeros(nn)
+        self._chk(self.lib.stan_host_db_get_thermal_loads(self.h, cnt, C.c_int32(al.shape[0]), _p(al, C.c_double),
+                                                          _p(dT, C.c_double)), "thermal_loads")
+        return dict(any=bool(cnt[0]), mat_alpha=al[:nm], dT=dT)
 
     def set_results(self, disp, strain=None, stress=None):
         disp = np.ascontiguousarray(disp, dtype=np.float64)

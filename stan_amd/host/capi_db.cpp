@@ -132,7 +132,8 @@ int stan_host_db_add_bc(stan_db *d, int32_t id, const char *name, const char *ty
     bc.Type = type; bc.has_type = true;
     bc.ID = id; bc.ColorID = id % 9;
     for (int64_t i = 0; i < n; i++) {
-        if (bc.Type != "BodyForce" && !d->db.NodeLib.ContainsKey(node_ids[i])) continue;  // BoundaryCondition.cs:89 (a BodyForce is keyed by material IDs)
+        const bool by_material = bc.Type == "BodyForce" || bc.Type == "ThermalExpansion";   // keyed by material IDs
+        if (!by_material && !d->db.NodeLib.ContainsKey(node_ids[i])) continue;  // BoundaryCondition.cs:89
         MatrixST v(3, 1);
         v.M[0] = vals[3 * i]; v.M[1] = vals[3 * i + 1]; v.M[2] = vals[3 * i + 2];
         if (!bc.NodalValues.Add(node_ids[i], v)) { d->err = "BC lists node " + std::to_string(node_ids[i]) + " twice (Dictionary.Add throws)"; return STAN_HOST_E_ARG; }
@@ -244,6 +245,23 @@ int stan_host_db_get_distributed_loads(stan_db *d, int64_t counts[4], int32_t ca
         std::fill(disp0, disp0 + f.xyz.size(), 0.0);
         std::copy(dl.disp0.begin(), dl.disp0.end(), disp0);
     }
+    return STAN_HOST_OK;
+}
+
+int stan_host_db_get_thermal_loads(stan_db *d, int64_t counts[2], int32_t cap_mat, double *mat_alpha, double *dT) {
+    if (!d || !counts) return STAN_HOST_E_ARG;
+    FlatModel f;
+    int rc = Flatten(d->db, &f, &d->err);
+    if (rc) return rc;
+    ThermalLoads tl;
+    rc = BuildThermalLoads(d->db, f, &tl, &d->err);
+    if (rc) return rc;
+    counts[0] = tl.any; counts[1] = (int64_t)tl.mat_alpha.size();
+    if (mat_alpha) {
+        if ((int64_t)cap_mat < counts[1]) { d->err = "mat_alpha buffer too small"; return STAN_HOST_E_ARG; }
+        std::copy(tl.mat_alpha.begin(), tl.mat_alpha.end(), mat_alpha);
+    }
+    if (dT) std::copy(tl.dT.begin(), tl.dT.end(), dT);
     return STAN_HOST_OK;
 }
 

@@ -1,7 +1,8 @@
 // loads.cpp -- host side of the distributed loads (include/stan_host.h): the pressure faces of a node
 // set, and BuildDistributedLoads, which reads the BoundaryCondition Types "Pressure", "BodyForce" and "Displacement" into
-// the flat arrays stan_hip_load_vector_hex8 takes.  No counterpart in the reference, which ignores Types it does not know
-// (Solver.cs:106, 138): a file with such BCs stays readable by it.
+// the flat arrays stan_hip_load_vector_hex8 takes; and of the thermal loads (section 3.9): BuildThermalLoads reads the Types
+// "Temperature" and "ThermalExpansion" into the arrays stan_hip_thermal_load_hex8 takes.  No counterpart in the reference,
+// which ignores Types it does not know (Solver.cs:106, 138): a file with such BCs stays readable by it.
 #include <algorithm>
 #include <array>
 #include <string>
@@ -135,6 +136,46 @@ int BuildDistributedLoads(const Database &db, const FlatModel &flat, const std::
         }
     }
     for (double v : out->disp0) out->n_prescribed += v != 0.0;
+    return STAN_HOST_OK;
+}
+
+bool HasThermalLoads(const Database &db) {
+    for (const auto &kv : db.BCLib.Items())
+        if (kv.second.Type == "Temperature" || kv.second.Type == "ThermalExpansion") return true;
+    return false;
+}
+
+int BuildThermalLoads(const Database &db, const FlatModel &flat, ThermalLoads *out, std::string *err) {
+    auto fail = [&](const std::string &why) { if (err) *err = why; return STAN_HOST_E_ARG; };
+    *out = ThermalLoads();
+    const size_t nn = db.NodeLib.Count(), nm = flat.mat_E_nu.size() / 2;
+    if (flat.xyz.size() != nn * 3) return fail("the flat model does not belong to this database");
+    // the elastic materials in MatLib order are the rows of mat_E_nu (Flatten)
+    std::vector<std::pair<int, int>> mat_row;
+    for (const auto &kv : db.MatLib.Items())
+        if (kv.second.Type.find("Elastic") != std::string::npos) mat_row.emplace_back(kv.first, (int)mat_row.size());
+    if (mat_row.size() != nm) return fail("the flat model does not belong to this database");
+    out->mat_alpha.assign(nm, 0.0);
+    out->dT.assign(nn, 0.0);
+    for (const auto &kv : db.BCLib.Items()) {
+        const BoundaryCondition &bc = kv.second;
+        const bool temp = bc.Type == "Temperature", expansion = bc.Type == "ThermalExpansion";
+        if (!temp && !expansion) continue;
+        out->any = true;
+        for (const auto &nv : bc.NodalValues.Items()) {   // several such BCs add up
+            if (nv.second.M.size() < 3) return fail(bc.Type + " value is not 3x1");
+            if (temp) {
+                const int64_t i = db.NodeLib.IndexOf(nv.first);
+                if (i < 0) return fail("Temperature on unknown node " + std::to_string(nv.first));
+                out->dT[(size_t)i] += nv.second.M[0];
+            } else {                                      // keys are material IDs
+                int row = -1;
+                for (const auto &mr : mat_row) if (mr.first == nv.first) row = mr.second;
+                if (row < 0) return fail("ThermalExpansion on unknown (or not elastic) material " + std::to_string(nv.first));
+                out->mat_alpha[(size_t)row] += nv.second.M[0];
+            }
+        }
+    }
     return STAN_HOST_OK;
 }
 

@@ -22,6 +22,9 @@
 // only).  A file whose BCLib holds the Types "Pressure", "BodyForce" or "Displacement" (loads.cpp; the reference ignores them)
 // gets their consistent nodal loads from stan_hip_load_vector_hex8: a block "Distributed loads:", the solve with
 // F - f_int(u0), u0 written into the displacements at the fixed DOFs, a "loads" object with --json; one device only.
+// The Types "Temperature" and "ThermalExpansion"  give the thermal load from stan_hip_thermal_load_hex8,
+// added to F in front of the distributed loads: a block "Thermal loads:", the recovered stress less beta dT, the reactions of
+// --reactions as f_int - l, a "thermal" object with --json; one device only.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -157,6 +160,10 @@ int main(int argc, char **argv) {
         if (dist_loads && devices.size() > 1)
             return fail("boundary conditions", "Pressure / BodyForce / Displacement work on one device: the load vector adds up all "
                                                "elements at a node, and a multi-device handle holds them in chunks (drop --gpus/--devices)");
+        const bool thermal = HasThermalLoads(DB);
+        if (thermal && devices.size() > 1)
+            return fail("boundary conditions", "Temperature / ThermalExpansion work on one device: the thermal load adds up all "
+                                               "elements at a node, and a multi-device handle holds them in chunks (drop --gpus/--devices)");
         t_bc = secs(t0);
         const int64_t n_nodes = (int64_t)DB.NodeLib.Count();
 
@@ -165,6 +172,22 @@ int main(int argc, char **argv) {
         Functions.ParallelAssembly_K(DB, nDOF_reduction, 1, "Initial", &K);  // Solver.cs:157
         stan_matrix_info minfo;
         stan_hip_matrix_info(K.K, &minfo);
+
+        // thermal loads, in front of the distributed loads: their F - f_int(u0) then holds this load too
+        ThermalLoads thermal_bc;
+        stan_thermal_sums tsum{};
+        std::vector<double> thermal_full;   // the thermal load over all DOFs: the supports exert f_int - this
+        double t_thermal = 0;
+        if (thermal) {
+            const auto tt = clk::now();
+            if (BuildThermalLoads(DB, K.flat, &thermal_bc, &err)) return fail("boundary conditions", err);
+            Functions.Thermal_Load(K, nDOF_reduction, thermal_bc, &F, &thermal_full, &tsum);
+            t_thermal = secs(tt);
+            printf("   Thermal loads:\n");
+            printf("     Total:              X %14.6e   Y %14.6e   Z %14.6e\n", tsum.load_sum[0], tsum.load_sum[1], tsum.load_sum[2]);
+            printf("     On free DOFs:       X %14.6e   Y %14.6e   Z %14.6e\n", tsum.free_sum[0], tsum.free_sum[1], tsum.free_sum[2]);
+            printf("     Heated volume: %.6e   mean dT: %.6e\n", tsum.volume, tsum.volume != 0 ? tsum.dT_integral / tsum.volume : 0.0);
+        }
 
         // distributed loads: F becomes the whole external load, F_solve the right-hand side (F - f_int(u0) on the free DOFs)
         DistributedLoads dl;
@@ -222,6 +245,7 @@ int main(int argc, char **argv) {
         // download overlaps the encoding and the file writes); --object-results needs them as whole host arrays
         if (object_results) Functions.Recovery_Stress(K, disp, &strain, &stress);
         else Functions.Recovery_Stress_Keep(K, disp);
+        if (thermal) Functions.Thermal_Stress(K, thermal_bc, object_results ? &stress : nullptr);   // before .vtu, scalars and export
         t_recover = secs(t0);
         printf("            Done\n");
         stan_profile pr{};
@@ -231,7 +255,15 @@ int main(int argc, char **argv) {
         std::vector<double> reaction;
         if (reactions) {
             t0 = clk::now();
-            Functions.Equilibrium(K, disp, F, nDOF_reduction, nullptr, vtu ? &reaction : nullptr, &eq);
+            Functions.Equilibrium(K, disp, F, nDOF_reduction, nullptr, vtu || thermal ? &reaction : nullptr, &eq);
+            if (thermal)   // the supports exert f_int - l at the fixed DOFs: the arrays, and the sums by direction in node order
+                for (int64_t n = 0; n < n_nodes; n++)
+                    for (int c = 0; c < 3; c++) {
+                        const size_t d = (size_t)K.flat.node_dof[(size_t)(3 * n + c)];
+                        if (nDOF_reduction[d] != -1) continue;
+                        reaction[d] -= thermal_full[d];
+                        eq.reaction_sum[c] -= thermal_full[d];
+                    }
             t_react = secs(t0);
             int64_t node = -1;
             for (int64_t n = 0; n < n_nodes && eq.residual_max_dof >= 0; n++)
@@ -319,6 +351,12 @@ int main(int argc, char **argv) {
                        "\"area\": %.17g, \"n_faces\": %lld, \"n_fixed\": %lld, \"n_prescribed\": %lld, \"t_s\": %.3f}",
                        lsum.load_sum[0], lsum.load_sum[1], lsum.load_sum[2], lsum.free_sum[0], lsum.free_sum[1], lsum.free_sum[2],
                        lsum.volume, lsum.area, (long long)lsum.n_faces, (long long)lsum.n_fixed, (long long)dl.n_prescribed, t_loads);
+            if (thermal)
+                printf(", \"thermal\": {\"load_sum\": [%.17g, %.17g, %.17g], \"free_sum\": [%.17g, %.17g, %.17g], \"volume\": %.17g, "
+                       "\"dT_integral\": %.17g, \"mean_dT\": %.17g, \"n_fixed\": %lld, \"t_s\": %.3f}",
+                       tsum.load_sum[0], tsum.load_sum[1], tsum.load_sum[2], tsum.free_sum[0], tsum.free_sum[1], tsum.free_sum[2],
+                       tsum.volume, tsum.dT_integral, tsum.volume != 0 ? tsum.dT_integral / tsum.volume : 0.0, (long long)tsum.n_fixed,
+                       t_thermal);
             printf("}\n");
         }
         return 0;

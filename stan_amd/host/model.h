@@ -334,6 +334,17 @@ struct DistributedLoads {
 bool HasDistributedLoads(const Database &db);
 int BuildDistributedLoads(const Database &db, const FlatModel &flat, const std::vector<int32_t> &red, DistributedLoads *out,
                           std::string *err);
+// ---- thermal loads (loads.cpp; no counterpart in the reference) ------------------------------
+// The BoundaryCondition Types "Temperature" (node IDs -> component 0 = dT, the change from the stress-free state; unlisted
+// nodes have 0; several such BCs add up) and "ThermalExpansion" (MATERIAL IDs -> component 0 = alpha, resolved like
+// "BodyForce"; several add up) as the flat arrays stan_hip_thermal_load_hex8 takes.
+struct ThermalLoads {
+    bool any = false;                  // the file holds at least one such BC
+    std::vector<double> mat_alpha;     // [n_mat] in the material order of FlatModel (zeros without a "ThermalExpansion")
+    std::vector<double> dT;            // [n_nodes] NodeLib order (zeros without a "Temperature")
+};
+bool HasThermalLoads(const Database &db);
+int BuildThermalLoads(const Database &db, const FlatModel &flat, ThermalLoads *out, std::string *err);
 // faces all of whose corners are in the node set; see stan_host_pressure_faces
 void PressureFaces(int64_t n_elem, const int32_t *conn, const std::vector<uint8_t> &in_set, const std::vector<double> &node_p,
                    std::vector<int32_t> *face_elem, std::vector<uint8_t> *face_id, std::vector<double> *face_p);

@@ -208,6 +208,29 @@ void SolverFunctions::Load_Vector(SparseMatrixHandle &K, const std::vector<int32
         throw std::runtime_error(stan_hip_last_error(K.ctx));
 }
 
+void SolverFunctions::Thermal_Load(SparseMatrixHandle &K, const std::vector<int32_t> &red, const ThermalLoads &tl,
+                                   std::vector<double> *F, std::vector<double> *load_full, stan_thermal_sums *sums) const {
+    const FlatModel &f = K.flat;
+    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
+    load_full->assign(red.size(), 0.0);
+    if (stan_hip_thermal_load_hex8(K.ctx, n_nodes, f.xyz.data(), f.node_dof.data(), n_elem, f.conn.data(), f.elem_mat.data(),
+                                   f.elem_type.data(), (int32_t)(f.mat_E_nu.size() / 2), f.mat_E_nu.data(), (int64_t)red.size(),
+                                   red.data(), tl.mat_alpha.data(), tl.dT.data(), F->data(), load_full->data(), sums))
+        throw std::runtime_error(stan_hip_last_error(K.ctx));
+}
+
+void SolverFunctions::Thermal_Stress(SparseMatrixHandle &K, const ThermalLoads &tl, std::vector<double> *stress) const {
+    const FlatModel &f = K.flat;
+    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
+    const int32_t n_mat = (int32_t)(f.mat_E_nu.size() / 2);
+    const int rc = stress ? stan_hip_thermal_stress_hex8(K.ctx, n_nodes, tl.dT.data(), n_elem, f.conn.data(), f.elem_mat.data(),
+                                                         f.elem_type.data(), n_mat, f.mat_E_nu.data(), tl.mat_alpha.data(),
+                                                         stress->data())
+                          : stan_hip_results_thermal_stress(K.ctx, K.results, n_nodes, tl.dT.data(), f.conn.data(), f.elem_mat.data(),
+                                                            f.elem_type.data(), n_mat, f.mat_E_nu.data(), tl.mat_alpha.data());
+    if (rc) throw std::runtime_error(stan_hip_last_error(K.ctx));
+}
+
 void SolverFunctions::Recovery_Stress_Keep(SparseMatrixHandle &K, const std::vector<double> &dU) const {
     const FlatModel &f = K.flat;
     const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();

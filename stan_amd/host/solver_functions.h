@@ -96,6 +96,14 @@ class SolverFunctions {
     // of the reduced system, F - f_int(u0)|free; *sums always filled.  One device only.
     void Load_Vector(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const DistributedLoads &dl,
                      std::vector<double> *F, std::vector<double> *F_solve, stan_load_sums *sums) const;
+    // Thermal loads (stan_hip_thermal_load_hex8; no step of the reference): adds the load of `tl` to the reduced external
+    // load F (in place) and leaves the load over all DOFs in *load_full (the supports exert f_int - load_full); *sums always
+    // filled.  One device only.
+    void Thermal_Load(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const ThermalLoads &tl,
+                      std::vector<double> *F, std::vector<double> *load_full, stan_thermal_sums *sums) const;
+    // ... and the recovered stress loses beta dT at every corner: the host array when given, else the results kept on the
+    // device (K.results)
+    void Thermal_Stress(SparseMatrixHandle &K, const ThermalLoads &tl, std::vector<double> *stress) const;
     // "name,name,..." of --vtu-results -> indices (stan_host_scalar_name's strings; empty text = all 24); false + *err on an unknown name
     static bool ParseScalarNames(const std::string &text, std::vector<int32_t> *sel, std::string *err);
 
