@@ -356,7 +356,7 @@ static inline int64_t stan_row_start(int64_t nb, int nranks, int r) {
 
 // ---- the mesh, as every layer below the C ABI passes it on ---------------------------------------------------------------
 // A view: plain pointers and counts, nothing owned.  ONE type for both sides of the upload -- a HOST view holds the caller's
-// arrays (a public entry builds it behind its checks), a DEVICE view their copies in device memory (mesh_dbufs of api.hip makes
+// arrays (a public entry builds it behind its checks), a DEVICE view their copies in device memory (mesh_dbufs of api_stage.h makes
 // it, a _dev entry builds it from its arguments, the stan_*_device drivers take it); mat_E_nu is a host array in both.
 // May be null: disp, node_dof and red where the entry has no such array (n_dof is 0 where it is not passed either); conn,
 // elem_mat and elem_type only where n_elem == 0.  Built with designated initialisers, so that no array is passed by position.
@@ -474,6 +474,9 @@ int stan_internal_forces_device(stan_ctx *ctx, const stan_mesh &d, const double 
 enum stan_if_bits { IF_CONN = 1, IF_MAT = 2, IF_TYPE = 4, IF_DOF = 8, IF_RED = 16, IF_FACE = 32 };
 int stan_elem_args_check(stan_ctx *ctx, dev_scope &tmp, const char *who, const stan_mesh &d, int64_t n_faces,
                          const int32_t *d_face_elem, const uint8_t *d_face_id, int64_t *n_fixed);
+// The limits of the drivers that take every array, on the host, before it: n_dof = 3 n_nodes > 0 and n_mat > 0, fewer than
+// 2^28 elements, at most 2^31 - 1 DOFs; "<who>: <what>", STAN_E_ARG.
+int stan_elem_limits_check(stan_ctx *ctx, const char *who, const stan_mesh &d);
 
 // ---- loads.hip ------------------------------------------------------------------------------
 // Consistent nodal loads of body forces and face pressures, and the right-hand side for prescribed displacements
@@ -487,11 +490,10 @@ int stan_load_vector_device(stan_ctx *ctx, const stan_mesh &d, const double *mat
 // and sums are host memory.  The same checks; det J == 0 in a heated element is found before any output is stored.
 int stan_thermal_load_device(stan_ctx *ctx, const stan_mesh &d, const double *mat_alpha, const double *d_dT, double *d_F,
                              double *d_load_full, stan_thermal_sums *sums);
-// d_stress [n_elem][8][6] loses beta_m dT at its corner's node in xx, yy, zz (stan_hip_thermal_stress_hex8); the integers are
-// checked on the device first.  Synchronises the stream.
-int stan_thermal_stress_device(stan_ctx *ctx, int64_t n_nodes, const double *d_dT, int64_t n_elem, const int32_t *d_conn,
-                               const int32_t *d_elem_mat, const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu,
-                               const double *mat_alpha, double *d_stress);
+// d_stress [n_elem][8][6] loses beta_m dT at its corner's node in xx, yy, zz (stan_hip_thermal_stress_hex8); d: device view
+// with conn, elem_mat and elem_type (no node array but d_dT); the integers are checked on the device first.  Synchronises
+// the stream.
+int stan_thermal_stress_device(stan_ctx *ctx, const stan_mesh &d, const double *d_dT, const double *mat_alpha, double *d_stress);
 
 // ---- comm.cpp -------------------------------------------------------------------------------
 int stan_comm_allreduce_sum_f64(stan_ctx *ctx, double *d_buf, size_t count);
@@ -640,7 +642,7 @@ int stan_group_cg_solve(stan_ctx *lead, stan_matrix *K, const double *F, double 
 int stan_group_recover(stan_ctx *lead, const stan_mesh &m, double *strain, double *stress);   // one chunk of m per rank
 // a rank's STAN_E_DETJ / STAN_E_UNSUPPORTED over the chunk from element e0 on: lead->bad_elem and the rank's text name the whole model's element
 void stan_chunk_bad_element(stan_ctx *lead, stan_ctx *c, int rc, int64_t e0);
-// api.hip: the host entries of ONE context behind their argument checks (the public entries and the group's ranks call them)
+// api_solve.hip, api_post.hip: the host entries of ONE context behind their argument checks (the public entries and the group's ranks call them)
 int stan_assemble_host(stan_ctx *ctx, const stan_mesh &m, stan_matrix **outK);
 int stan_recover_host(stan_ctx *ctx, const stan_mesh &m, double *strain, double *stress);
 int stan_group_set_p2p(stan_ctx *lead, bool on);

@@ -262,14 +262,19 @@ int stan_elem_args_check(stan_ctx *ctx, dev_scope &tmp, const char *who, const s
     return STAN_OK;
 }
 
+int stan_elem_limits_check(stan_ctx *ctx, const char *who, const stan_mesh &d) {
+    auto bad = [&](const char *why, int rc) { ctx->err = std::string(who) + ": " + why; return rc; };
+    if (d.n_nodes <= 0 || d.n_elem < 0 || d.n_mat <= 0 || d.n_dof != d.n_nodes * 3) return bad("n_dof must be 3 n_nodes > 0, n_mat > 0", STAN_E_ARG);
+    if (d.n_elem >= (int64_t)1 << 28) return bad("more than 2^28 elements", STAN_E_ARG);
+    if (d.n_dof > 0x7fffffffLL) return bad("more than 2^31 DOFs", STAN_E_ARG);
+    return STAN_OK;
+}
+
 int stan_internal_forces_device(stan_ctx *ctx, const stan_mesh &d, const double *d_F, double *d_fint, double *d_reaction,
                                 stan_equilibrium *eq) {
     const char *who = "internal_forces_hex8";
     const int64_t n_nodes = d.n_nodes, n_elem = d.n_elem, n_dof = d.n_dof, n_mat = d.n_mat;
-    auto bad = [&](const char *why, int rc) { ctx->err = std::string(who) + ": " + why; return rc; };
-    if (n_nodes <= 0 || n_elem < 0 || n_mat <= 0 || n_dof != n_nodes * 3) return bad("n_dof must be 3 n_nodes > 0, n_mat > 0", STAN_E_ARG);
-    if (n_elem >= (int64_t)1 << 28) return bad("more than 2^28 elements", STAN_E_ARG);
-    if (n_dof > 0x7fffffffLL) return bad("more than 2^31 DOFs", STAN_E_ARG);
+    STANCHK(stan_elem_limits_check(ctx, who, d));
     hipStream_t st = ctx->stream;
     ctx->prof.forces_elem_ms = ctx->prof.forces_list_ms = ctx->prof.forces_gather_ms = 0;
     // ---- the checks, before anything is indexed with the caller's integers

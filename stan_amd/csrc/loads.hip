@@ -303,9 +303,7 @@ int stan_thermal_load_device(stan_ctx *ctx, const stan_mesh &d, const double *ma
     const char *who = "thermal_load_hex8";
     const int64_t n_nodes = d.n_nodes, n_elem = d.n_elem, n_dof = d.n_dof, n_mat = d.n_mat;
     auto bad = [&](const char *why, int rc) { ctx->err = std::string(who) + ": " + why; return rc; };
-    if (n_nodes <= 0 || n_elem < 0 || n_mat <= 0 || n_dof != n_nodes * 3) return bad("n_dof must be 3 n_nodes > 0, n_mat > 0", STAN_E_ARG);
-    if (n_elem >= (int64_t)1 << 28) return bad("more than 2^28 elements", STAN_E_ARG);
-    if (n_dof > 0x7fffffffLL) return bad("more than 2^31 DOFs", STAN_E_ARG);
+    STANCHK(stan_elem_limits_check(ctx, who, d));
     if (!d_F && !d_load_full && !sums) return bad("none of F / load_full / sums asked for", STAN_E_ARG);
     hipStream_t st = ctx->stream;
     ctx->prof_thermal_ms[0] = ctx->prof_thermal_ms[1] = ctx->prof_thermal_ms[2] = 0;
@@ -360,9 +358,9 @@ int stan_thermal_load_device(stan_ctx *ctx, const stan_mesh &d, const double *ma
     return STAN_OK;
 }
 
-int stan_thermal_stress_device(stan_ctx *ctx, int64_t n_nodes, const double *d_dT, int64_t n_elem, const int32_t *d_conn,
-                               const int32_t *d_elem_mat, const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu,
-                               const double *mat_alpha, double *d_stress) {
+int stan_thermal_stress_device(stan_ctx *ctx, const stan_mesh &d, const double *d_dT, const double *mat_alpha, double *d_stress) {
+    const int64_t n_nodes = d.n_nodes, n_elem = d.n_elem;
+    const int32_t n_mat = d.n_mat;
     auto bad = [&](const char *why, int rc) { ctx->err = std::string("thermal_stress_hex8: ") + why; return rc; };
     if (n_nodes <= 0 || n_elem < 0 || n_mat <= 0) return bad("n_nodes and n_mat must be positive", STAN_E_ARG);
     if (n_elem >= (int64_t)1 << 28) return bad("more than 2^28 elements", STAN_E_ARG);
@@ -372,8 +370,8 @@ int stan_thermal_stress_device(stan_ctx *ctx, int64_t n_nodes, const double *d_d
     const long long init[3] = {0, 0x7fffffffffffffffLL, 0x7fffffffffffffffLL};
     HIPCHK(ctx, hipMemcpyAsync(status + SS_ERRBITS, &init[0], 8, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemcpyAsync(status + SS_BAD_ELEM, &init[1], 16, hipMemcpyHostToDevice, st));   // SS_BAD_ELEM, SS_AUX
-    hipLaunchKernelGGL(k_th_stress_check, dim3(nblk(n_elem * 8, 256)), dim3(256), 0, st, n_nodes, n_elem, n_mat, d_conn, d_elem_mat,
-                       d_elem_type, status);
+    hipLaunchKernelGGL(k_th_stress_check, dim3(nblk(n_elem * 8, 256)), dim3(256), 0, st, n_nodes, n_elem, n_mat, d.conn, d.elem_mat,
+                       d.elem_type, status);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_ERRBITS, status + SS_ERRBITS, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, status + SS_AUX, 8, hipMemcpyDeviceToHost, st));
@@ -387,11 +385,11 @@ int stan_thermal_stress_device(stan_ctx *ctx, int64_t n_nodes, const double *d_d
         return bad(("element " + std::to_string(ctx->bad_elem) + " is HEX8_G1 (no nodal stress: the recovery refuses it)").c_str(), STAN_E_UNSUPPORTED);
     }
     dev_scope tmp(ctx);
-    const std::vector<double> beta = thermal_beta(n_mat, mat_E_nu, mat_alpha);   // outlives the stream's copy
+    const std::vector<double> beta = thermal_beta(n_mat, d.mat_E_nu, mat_alpha);   // outlives the stream's copy
     double *d_beta;
     STANCHK(tmp.alloc(&d_beta, beta.size()));
     HIPCHK(ctx, hipMemcpyAsync(d_beta, beta.data(), beta.size() * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_th_stress, dim3(nblk(n_elem * 48, 256)), dim3(256), 0, st, n_elem * 48, d_dT, d_conn, d_elem_mat, d_beta, d_stress);
+    hipLaunchKernelGGL(k_th_stress, dim3(nblk(n_elem * 48, 256)), dim3(256), 0, st, n_elem * 48, d_dT, d.conn, d.elem_mat, d_beta, d_stress);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(st));
     return STAN_OK;
@@ -403,9 +401,7 @@ int stan_load_vector_device(stan_ctx *ctx, const stan_mesh &d, const double *mat
     const char *who = "load_vector_hex8";
     const int64_t n_nodes = d.n_nodes, n_elem = d.n_elem, n_dof = d.n_dof, n_mat = d.n_mat;
     auto bad = [&](const char *why, int rc) { ctx->err = std::string(who) + ": " + why; return rc; };
-    if (n_nodes <= 0 || n_elem < 0 || n_mat <= 0 || n_dof != n_nodes * 3) return bad("n_dof must be 3 n_nodes > 0, n_mat > 0", STAN_E_ARG);
-    if (n_elem >= (int64_t)1 << 28) return bad("more than 2^28 elements", STAN_E_ARG);
-    if (n_dof > 0x7fffffffLL) return bad("more than 2^31 DOFs", STAN_E_ARG);
+    STANCHK(stan_elem_limits_check(ctx, who, d));
     if (n_faces < 0 || n_faces > n_elem * 6) return bad("n_faces outside [0, 6 n_elem]", STAN_E_ARG);
     if (!mat_body && n_faces == 0 && !d_disp0) return bad("no body force, no face and no prescribed displacement", STAN_E_ARG);
     if (!d_F && !d_F_solve && !d_load_full && !sums) return bad("none of F / F_solve / load_full / sums asked for", STAN_E_ARG);

@@ -256,7 +256,7 @@ extern "C" int stan_hip_init_multi(int n_devices, const int *devices, stan_ctx *
     return STAN_OK;
 }
 
-// ---- the fan-out of each public entry point (called from api.hip when ctx->group is set) ----------
+// ---- the fan-out of each public entry point (called from api*.hip when ctx->group is set) ----------
 
 void stan_group_destroy(stan_ctx *lead) {
     stan_group *g = lead->group;
@@ -305,7 +305,7 @@ int stan_group_set_p2p(stan_ctx *lead, bool on) {
     return STAN_OK;
 }
 
-// Every rank gets the whole mesh and picks the elements of its block rows itself (api.hip: pick_shard_elements).
+// Every rank gets the whole mesh and picks the elements of its block rows itself (api_solve.hip: pick_shard_elements).
 int stan_group_assemble(stan_ctx *lead, const stan_mesh &m, stan_matrix **outK) {
     stan_group *g = lead->group;
     lead->err.clear();

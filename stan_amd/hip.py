@@ -89,32 +89,30 @@ class Profile(C.Structure):
                 ("forces_elem_ms", C.c_double), ("forces_list_ms", C.c_double), ("forces_gather_ms", C.c_double)]
 
 
-class Equilibrium(C.Structure):
+class _Sums(C.Structure):
+    """the result structures of sums: as_dict() gives the 3-vectors (*_sum) as lists"""
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k.endswith("_sum") else getattr(self, k)) for k, _ in self._fields_}
+
+
+class Equilibrium(_Sums):
     """stan_equilibrium (include/stan_hip.h)"""
     _fields_ = [("reaction_sum", C.c_double * 3), ("load_sum", C.c_double * 3), ("fint_sum", C.c_double * 3),
                 ("residual_norm2", C.c_double), ("load_norm2", C.c_double), ("residual_max", C.c_double),
                 ("residual_max_dof", C.c_int64), ("n_fixed", C.c_int64)]
 
-    def as_dict(self):
-        return {k: (list(getattr(self, k)) if k.endswith("_sum") else getattr(self, k)) for k, _ in self._fields_}
 
-
-class LoadSums(C.Structure):
+class LoadSums(_Sums):
     """stan_load_sums (include/stan_hip.h)"""
     _fields_ = [("load_sum", C.c_double * 3), ("free_sum", C.c_double * 3), ("volume", C.c_double), ("area", C.c_double),
                 ("n_fixed", C.c_int64), ("n_faces", C.c_int64)]
 
-    def as_dict(self):
-        return {k: (list(getattr(self, k)) if k.endswith("_sum") else getattr(self, k)) for k, _ in self._fields_}
 
-
-class ThermalSums(C.Structure):
+class ThermalSums(_Sums):
     """stan_thermal_sums (include/stan_hip.h)"""
     _fields_ = [("load_sum", C.c_double * 3), ("free_sum", C.c_double * 3), ("volume", C.c_double), ("dT_integral", C.c_double),
                 ("n_fixed", C.c_int64)]
-
-    def as_dict(self):
-        return {k: (list(getattr(self, k)) if k.endswith("_sum") else getattr(self, k)) for k, _ in self._fields_}
 
 
 class StanHipError(RuntimeError):
@@ -159,6 +157,22 @@ def _ptr(a, t):
 def _dev(p, t):
     """device pointer given as int (torch tensor.data_ptr())"""
     return C.cast(C.c_void_p(int(p)), C.POINTER(t))
+
+
+def _opt(p, t=C.c_double):
+    """an optional device pointer: None stays None (NULL)"""
+    return None if p is None else _dev(p, t)
+
+
+_MESH = dict(xyz=np.float64, disp=np.float64, node_dof=np.int32, conn=np.int32, elem_mat=np.int32, elem_type=np.uint8,
+             mat_E_nu=np.float64, red=np.int32)
+
+
+def _mesh(**arrays):
+    """The mesh arrays an entry takes, by name and in the order given, as the ABI wants them: C-contiguous, its type, conn
+    [n_elem, 8], mat_E_nu [n_mat, 2]."""
+    out = {k: np.ascontiguousarray(a, dtype=_MESH[k]) for k, a in arrays.items()}
+    return [a.reshape(-1, 8 if k == "conn" else 2) if k in ("conn", "mat_E_nu") else a for k, a in out.items()]
 
 
 class Context:
@@ -285,12 +299,8 @@ class Context:
 
     # -- stress recovery ---------------------------------------------------------------
     def recover_hex8(self, xyz, disp, conn, elem_mat, elem_type, mat_E_nu):
-        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
-        disp = np.ascontiguousarray(disp, dtype=np.float64)
-        conn = np.ascontiguousarray(conn, dtype=np.int32).reshape(-1, 8)
-        elem_mat = np.ascontiguousarray(elem_mat, dtype=np.int32)
-        elem_type = np.ascontiguousarray(elem_type, dtype=np.uint8)
-        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        xyz, disp, conn, elem_mat, elem_type, mat_E_nu = _mesh(
+            xyz=xyz, disp=disp, conn=conn, elem_mat=elem_mat, elem_type=elem_type, mat_E_nu=mat_E_nu)
         ne = conn.shape[0]
         strain = np.zeros((ne, 8, 6))
         stress = np.zeros((ne, 8, 6))
@@ -311,12 +321,8 @@ class Context:
 
     def recover_hex8_keep(self, xyz, disp, conn, elem_mat, elem_type, mat_E_nu):
         """Stress recovery with the results kept on the device(s): returns a Results handle (map(e0, e1), free())."""
-        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
-        disp = np.ascontiguousarray(disp, dtype=np.float64)
-        conn = np.ascontiguousarray(conn, dtype=np.int32).reshape(-1, 8)
-        elem_mat = np.ascontiguousarray(elem_mat, dtype=np.int32)
-        elem_type = np.ascontiguousarray(elem_type, dtype=np.uint8)
-        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        xyz, disp, conn, elem_mat, elem_type, mat_E_nu = _mesh(
+            xyz=xyz, disp=disp, conn=conn, elem_mat=elem_mat, elem_type=elem_type, mat_E_nu=mat_E_nu)
         h = C.c_void_p()
         self._chk(self.lib.stan_hip_recover_hex8_keep(
             self.h, C.c_int64(xyz.shape[0]), _ptr(xyz, C.c_double), _ptr(disp, C.c_double),
@@ -352,13 +358,8 @@ class Context:
 
     def nodal_forces_hex8(self, xyz, disp, node_dof, conn, elem_mat, elem_type, mat_E_nu):
         """Element.NodalForces [n_elem,24] and the assembled R [n_dof] (Solver.cs:184-196)."""
-        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
-        disp = np.ascontiguousarray(disp, dtype=np.float64)
-        node_dof = np.ascontiguousarray(node_dof, dtype=np.int32)
-        conn = np.ascontiguousarray(conn, dtype=np.int32).reshape(-1, 8)
-        elem_mat = np.ascontiguousarray(elem_mat, dtype=np.int32)
-        elem_type = np.ascontiguousarray(elem_type, dtype=np.uint8)
-        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        xyz, disp, node_dof, conn, elem_mat, elem_type, mat_E_nu = _mesh(
+            xyz=xyz, disp=disp, node_dof=node_dof, conn=conn, elem_mat=elem_mat, elem_type=elem_type, mat_E_nu=mat_E_nu)
         ne, n_dof = conn.shape[0], xyz.shape[0] * 3
         f = np.zeros((ne, 24))
         R = np.zeros(n_dof)
@@ -374,14 +375,8 @@ class Context:
                              f_int=True, reaction=True, eq=True):
         """stan_hip_internal_forces_hex8: (f_int [n_dof], reaction [n_dof], eq Equilibrium) from host arrays; disp is any
         full nodal vector [n_nodes, 3], F the reduced load vector or None (= 0).  An output not asked for is None."""
-        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
-        disp = np.ascontiguousarray(disp, dtype=np.float64)
-        node_dof = np.ascontiguousarray(node_dof, dtype=np.int32)
-        conn = np.ascontiguousarray(conn, dtype=np.int32).reshape(-1, 8)
-        elem_mat = np.ascontiguousarray(elem_mat, dtype=np.int32)
-        elem_type = np.ascontiguousarray(elem_type, dtype=np.uint8)
-        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
-        red = np.ascontiguousarray(red, dtype=np.int32)
+        xyz, disp, node_dof, conn, elem_mat, elem_type, mat_E_nu, red = _mesh(
+            xyz=xyz, disp=disp, node_dof=node_dof, conn=conn, elem_mat=elem_mat, elem_type=elem_type, mat_E_nu=mat_E_nu, red=red)
         F = None if F is None else np.ascontiguousarray(F, dtype=np.float64)
         n_dof = red.shape[0]
         if disp.size != xyz.size or (F is not None and F.shape[0] != n_dof - int((red == -1).sum())):
@@ -402,12 +397,11 @@ class Context:
         Returns the Equilibrium (None when not asked for)."""
         mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
         q = Equilibrium() if eq else None
-        opt = lambda p: None if p is None else _dev(p, C.c_double)
         self._chk(self.lib.stan_hip_internal_forces_hex8_dev(
             self.h, C.c_int64(n_nodes), _dev(d_xyz, C.c_double), _dev(d_disp, C.c_double), _dev(d_node_dof, C.c_int32),
             C.c_int64(n_elem), _dev(d_conn, C.c_int32), _dev(d_elem_mat, C.c_int32), _dev(d_elem_type, C.c_uint8),
             C.c_int32(mat_E_nu.shape[0]), _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _dev(d_red, C.c_int32),
-            opt(d_F), opt(d_f_int), opt(d_reaction), C.byref(q) if eq else None))
+            _opt(d_F), _opt(d_f_int), _opt(d_reaction), C.byref(q) if eq else None))
         return q
 
     # -- distributed loads and prescribed displacements -----------------------------------------
@@ -417,13 +411,8 @@ class Context:
         the face list (face_elem, face_id, face_pressure) sorted by face_elem * 6 + face_id, or None; disp0 [n_nodes, 3] or
         None.  F: the reduced load vector to add to (a copy is returned) or None; F_solve: True / False, default = disp0
         given.  An output not asked for is None."""
-        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
-        node_dof = np.ascontiguousarray(node_dof, dtype=np.int32)
-        conn = np.ascontiguousarray(conn, dtype=np.int32).reshape(-1, 8)
-        elem_mat = np.ascontiguousarray(elem_mat, dtype=np.int32)
-        elem_type = np.ascontiguousarray(elem_type, dtype=np.uint8)
-        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
-        red = np.ascontiguousarray(red, dtype=np.int32)
+        xyz, node_dof, conn, elem_mat, elem_type, mat_E_nu, red = _mesh(
+            xyz=xyz, node_dof=node_dof, conn=conn, elem_mat=elem_mat, elem_type=elem_type, mat_E_nu=mat_E_nu, red=red)
         n_dof = red.shape[0]
         N = n_dof - int((red == -1).sum())
         mb = None if mat_body is None else np.ascontiguousarray(mat_body, dtype=np.float64).reshape(-1, 3)
@@ -462,13 +451,12 @@ class Context:
         mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
         mb = None if mat_body is None else np.ascontiguousarray(mat_body, dtype=np.float64).reshape(-1, 3)
         q = LoadSums() if sums else None
-        opt = lambda p, t=C.c_double: None if p is None else _dev(p, t)
         self._chk(self.lib.stan_hip_load_vector_hex8_dev(
             self.h, C.c_int64(n_nodes), _dev(d_xyz, C.c_double), _dev(d_node_dof, C.c_int32), C.c_int64(n_elem),
             _dev(d_conn, C.c_int32), _dev(d_elem_mat, C.c_int32), _dev(d_elem_type, C.c_uint8), C.c_int32(mat_E_nu.shape[0]),
             _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _dev(d_red, C.c_int32), _ptr(mb, C.c_double), C.c_int64(n_faces),
-            opt(d_face_elem, C.c_int32), opt(d_face_id, C.c_uint8), opt(d_face_pressure), opt(d_disp0), opt(d_F),
-            opt(d_F_solve), opt(d_load_full), C.byref(q) if sums else None))
+            _opt(d_face_elem, C.c_int32), _opt(d_face_id, C.c_uint8), _opt(d_face_pressure), _opt(d_disp0), _opt(d_F),
+            _opt(d_F_solve), _opt(d_load_full), C.byref(q) if sums else None))
         return q
 
     def load_vector_times(self):
@@ -483,13 +471,8 @@ class Context:
         """stan_hip_thermal_load_hex8 from host arrays: (F, load_full, sums ThermalSums).  mat_alpha [n_mat], dT [n_nodes]
         (None is passed on as NULL); F: the reduced load vector to add to (a copy is returned) or None.  An output not asked
         for is None."""
-        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
-        node_dof = np.ascontiguousarray(node_dof, dtype=np.int32)
-        conn = np.ascontiguousarray(conn, dtype=np.int32).reshape(-1, 8)
-        elem_mat = np.ascontiguousarray(elem_mat, dtype=np.int32)
-        elem_type = np.ascontiguousarray(elem_type, dtype=np.uint8)
-        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
-        red = np.ascontiguousarray(red, dtype=np.int32)
+        xyz, node_dof, conn, elem_mat, elem_type, mat_E_nu, red = _mesh(
+            xyz=xyz, node_dof=node_dof, conn=conn, elem_mat=elem_mat, elem_type=elem_type, mat_E_nu=mat_E_nu, red=red)
         n_dof = red.shape[0]
         N = n_dof - int((red == -1).sum())
         al = None if mat_alpha is None else np.ascontiguousarray(mat_alpha, dtype=np.float64).reshape(-1)
@@ -517,12 +500,11 @@ class Context:
         mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
         al = None if mat_alpha is None else np.ascontiguousarray(mat_alpha, dtype=np.float64).reshape(-1)
         q = ThermalSums() if sums else None
-        opt = lambda p: None if p is None else _dev(p, C.c_double)
         self._chk(self.lib.stan_hip_thermal_load_hex8_dev(
             self.h, C.c_int64(n_nodes), _dev(d_xyz, C.c_double), _dev(d_node_dof, C.c_int32), C.c_int64(n_elem),
             _dev(d_conn, C.c_int32), _dev(d_elem_mat, C.c_int32), _dev(d_elem_type, C.c_uint8), C.c_int32(mat_E_nu.shape[0]),
-            _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _dev(d_red, C.c_int32), _ptr(al, C.c_double), opt(d_dT), opt(d_F),
-            opt(d_load_full), C.byref(q) if sums else None))
+            _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _dev(d_red, C.c_int32), _ptr(al, C.c_double), _opt(d_dT), _opt(d_F),
+            _opt(d_load_full), C.byref(q) if sums else None))
         return q
 
     def thermal_load_times(self):
@@ -533,10 +515,7 @@ class Context:
 
     def _thermal_stress_args(self, dT, conn, elem_mat, elem_type, mat_E_nu, mat_alpha):
         dT = np.ascontiguousarray(dT, dtype=np.float64).reshape(-1)
-        conn = np.ascontiguousarray(conn, dtype=np.int32).reshape(-1, 8)
-        elem_mat = np.ascontiguousarray(elem_mat, dtype=np.int32)
-        elem_type = np.ascontiguousarray(elem_type, dtype=np.uint8)
-        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        conn, elem_mat, elem_type, mat_E_nu = _mesh(conn=conn, elem_mat=elem_mat, elem_type=elem_type, mat_E_nu=mat_E_nu)
         al = np.ascontiguousarray(mat_alpha, dtype=np.float64).reshape(-1)
         if al.shape[0] != mat_E_nu.shape[0] or elem_mat.shape[0] != conn.shape[0] or elem_type.shape[0] != conn.shape[0]:
             raise ValueError("thermal stress: mat_alpha must be [n_mat], elem_mat and elem_type [n_elem]")
@@ -565,13 +544,8 @@ class Context:
 
     # -- assembly ------------------------------------------------------------------------
     def assemble_hex8(self, xyz, node_dof, conn, elem_mat, elem_type, mat_E_nu, red):
-        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
-        node_dof = np.ascontiguousarray(node_dof, dtype=np.int32)
-        conn = np.ascontiguousarray(conn, dtype=np.int32).reshape(-1, 8)
-        elem_mat = np.ascontiguousarray(elem_mat, dtype=np.int32)
-        elem_type = np.ascontiguousarray(elem_type, dtype=np.uint8)
-        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
-        red = np.ascontiguousarray(red, dtype=np.int32)
+        xyz, node_dof, conn, elem_mat, elem_type, mat_E_nu, red = _mesh(
+            xyz=xyz, node_dof=node_dof, conn=conn, elem_mat=elem_mat, elem_type=elem_type, mat_E_nu=mat_E_nu, red=red)
         k = C.c_void_p()
         self._chk(self.lib.stan_hip_assemble_hex8(
             self.h, C.c_int64(xyz.shape[0]), _ptr(xyz, C.c_double), _ptr(node_dof, C.c_int32),
