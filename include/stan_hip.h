@@ -684,6 +684,91 @@ int stan_hip_results_thermal_stress(stan_ctx *ctx, stan_results *res, int64_t n_
  * communicator it returns the zeros of a context on which no thermal-load call has run. */
 int stan_hip_thermal_load_times(stan_ctx *ctx, double ms[3]);
 
+/* ---- modal analysis: lumped mass and the lowest natural frequencies ---------------------------- */
+/* No step of the reference.  The row-sum lumped mass of a HEX8 is the body-force integral with
+ * b = rho: m_node = sum over every (element, corner) that names the node of rho_m sum_{2x2x2} N_a(q) det J(q), from the element
+ * pass and the node gather of stan_hip_load_vector_hex8 -- the mass of node n has the bits of that entry's
+ * load_full[node_dof[3n]] under mat_body = (rho_m, 0, 0).
+ *   mat_rho   [n_mat] host array: the density per row of mat_E_nu
+ *   M         [N] out or NULL: the node's mass at each of its free DOFs, in the reduced numbering (what stan_hip_modes takes)
+ *   mass_node [n_nodes] out or NULL, in NodeLib (wire) order
+ *   sums      stan_mass_sums or NULL (void * as for stan_hip_load_vector_hex8)
+ * Bit-reproducible, from the host and from the _dev entry, whichever outputs are asked for.
+ * STAN_E_ARG: as stan_hip_load_vector_hex8 for the mesh; mat_rho NULL, a density that is negative or not finite, every output
+ * NULL, a node with a free DOF whose mass is not positive (the node in stan_hip_last_error).  STAN_E_DOF_LAYOUT as there.
+ * STAN_E_UNSUPPORTED on a multi-device handle and on a context with a communicator.  On an error no output has been written. */
+typedef struct stan_mass_sums {
+    double total_mass;    /* sum of m_node over all nodes                                                  */
+    double volume;        /* sum_q det J(q) over the elements whose material has rho != 0                  */
+    double free_sum[3];   /* the mass on free DOFs, by direction c of node_dof[3n+c] (the sum of M by direction) */
+    double fixed_sum[3];  /* the mass sitting on fixed DOFs, by direction: free + fixed = total in every direction */
+    int64_t n_fixed;
+} stan_mass_sums;
+int stan_hip_lumped_mass_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const int32_t *node_dof, int64_t n_elem,
+                              const int32_t *conn, const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat,
+                              const double *mat_E_nu, int64_t n_dof, const int32_t *ndof_reduction, const double *mat_rho,
+                              double *M, double *mass_node, void *sums);
+/* The same with every array except mat_E_nu, mat_rho and sums in device memory on the context's GPU: read only, ready on the
+ * context's stream, naturally aligned; nothing is stored outside the outputs; complete on return. */
+int stan_hip_lumped_mass_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const int32_t *d_node_dof,
+                                  int64_t n_elem, const int32_t *d_conn, const int32_t *d_elem_mat,
+                                  const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
+                                  const int32_t *d_ndof_reduction, const double *mat_rho, double *d_M, double *d_mass_node,
+                                  void *sums);
+
+/* The n_modes lowest eigenpairs of K phi = lambda M phi on the free DOFs: K a matrix of this context (a supported model: K
+ * positive definite), M [N] the diagonal mass (stan_hip_lumped_mass_hex8), every entry positive.  Block inverse iteration in
+ * correction form with a Rayleigh-Ritz step per outer step:
+ *   block   q = min(N, min(2 n_modes, n_modes + 8)) columns, at most 32 (so n_modes <= 24 unless N is as small);
+ *           column 0 starts as M, column j > 0 as a fixed integer hash of (row, j) in [-0.5, 0.5): no random state;
+ *   first   K Z = M o X0 by stan_hip_cg_solve_multi_dev's loop (solve_eps, solve_max_its per column, as that entry takes them);
+ *   step    W = K Z (true products); A = Z^T W, B = Z^T (M o Z) in one pass; A Q = B Q Lambda on the host (Cholesky of B, cyclic
+ *           Jacobi); X = Z Q, K X = W Q, R = K X - (M o X) Lambda, rho_j = ||R_j||_{M^-1} / lambda_j in one pass; stop when
+ *           rho_j <= tol for every j < n_modes or after max_outer steps; else K D = -R Lambda^-1 for the columns with
+ *           rho_j > tol only and Z_j = X_j / lambda_j + D_j.
+ *   tol = 0 selects 1e-6, max_outer = 0 selects 100, solve_eps = solve_max_its = 0 selects 1e-6 (lincgsetcond).
+ * Outputs: lambda [n_modes] ascending; phi [n_modes][N], M-orthonormal, the entry of largest magnitude of every mode positive
+ * (the lowest index on a tie); rho [n_modes] as computed on the final vectors: rho_j lambda_j bounds the distance from lambda_j
+ * to an exact eigenvalue.  rep: a stan_modes_report or NULL (void * as for the sums above); behind the argument checks it is
+ * written on every way out, errors included, with what the call had reached (zeros where it had not).
+ * STAN_OK with converged = 0 when max_outer runs out: the outputs are the current Ritz pairs with their rho.
+ * K stays usable: a later solve on it has the bits it has on a freshly assembled K.  Two calls give the same bits, and so do
+ * the host and the _dev entry; _dev stores all of d_lambda, d_phi, d_rho and nothing beside them.
+ * STAN_E_ARG: n_modes <= 0 or > N, a block of more than 32 columns, a NULL pointer, an entry of M that is not positive and
+ * finite, negative tol, solve_eps, max_outer or solve_max_its, a K of another context.  STAN_E_UNSUPPORTED: a multi-device
+ * handle, a context with a communicator; a CG column that ends with type -5 or -4 (a K that is not positive definite: a
+ * free-free model), the type in the report and in stan_hip_last_error; a block that loses rank. */
+typedef struct stan_modes_report {
+    int32_t block;            /* q                                                                             */
+    int32_t outer;            /* outer steps made (Rayleigh-Ritz steps)                                        */
+    int32_t converged;        /* 1: rho_j <= tol for every returned mode                                       */
+    int32_t cg_worst_type;    /* the worst termination type a CG column met: negative < 5 < 7 < 1             */
+    int64_t cg_iterations;    /* summed over every column of every solve                                       */
+    double max_rho;           /* over the returned modes                                                       */
+    double solve_ms;          /* stream time in the solves, the products W = K Z and the block kernels, by     */
+    double product_ms;        /*   events when profiling is on, else zeros                                     */
+    double block_ms;
+    double gram_ms;           /* of block_ms: the gram passes with their finishing sums,                      */
+    double rotate_ms;         /*   the rotate + residual passes with theirs                                   */
+} stan_modes_report;
+int stan_hip_modes(stan_ctx *ctx, stan_matrix *K, const double *M, int32_t n_modes, double tol, int32_t max_outer,
+                   double solve_eps, int32_t solve_max_its, double *lambda, double *phi, double *rho, void *rep);
+int stan_hip_modes_dev(stan_ctx *ctx, stan_matrix *K, const double *d_M, int32_t n_modes, double tol, int32_t max_outer,
+                       double solve_eps, int32_t solve_max_its, double *d_lambda, double *d_phi, double *d_rho, void *rep);
+/* The block kernels of stan_hip_modes on host arrays (introspection, as stan_hip_spmv is): a block vector is [q][N], one
+ * column after the other, q <= 32.  Deterministic: per-workgroup partial sums in workgroup order, no atomics on doubles.
+ *   gram    A [q*q] = Z^T W and B [q*q] = Z^T (M o Z), row-major, from one pass over Z, W and M.  A term of A is one fused
+ *           multiply-add, a term of B is (z_i z_j) m: B is symmetric to the bit.
+ *   rotate  X = Z Q, KX = W Q (Q [q*q] row-major), R = KX - (M o X) diag(lambda), rho2 [q] = sum_i R_ij^2 / M_i, and for every
+ *           column j with mask[j] == 0 (mask NULL: every column) rhs_j = -R_j / lambda_j; the columns of rhs [q][N] that are
+ *           masked come back as they were passed.  in_place != 0: X and KX are formed in the device copies of Z and W
+ *           themselves (the aliased call of the driver); the results are the same bits. */
+int stan_hip_block_gram(stan_ctx *ctx, int64_t N, int32_t q, const double *Z, const double *W, const double *M, double *A,
+                        double *B);
+int stan_hip_block_rotate(stan_ctx *ctx, int64_t N, int32_t q, const double *Z, const double *W, const double *M,
+                          const double *Q, const double *lambda, const uint8_t *mask, int32_t in_place, double *X,
+                          double *KX, double *rhs, double *rho2);
+
 /* ---- introspection / parity helpers ------------------------------------------------------- */
 typedef struct stan_matrix_info {
     int64_t n_dof;        /* full DOF count                                      */

@@ -189,6 +189,11 @@ int stan_host_db_get_distributed_loads(stan_db *db, int64_t counts[4], int32_t c
  * capacity that is too small, an unknown node ID and an unknown or non-elastic material ID (reported with the ID) are
  * STAN_HOST_E_ARG.  The reference ignores Types it does not know. */
 int stan_host_db_get_thermal_loads(stan_db *db, int64_t counts[2], int32_t cap_mat, double *mat_alpha, double *dT);
+/* The BoundaryCondition Type "Density" (MATERIAL IDs, component 0 = rho, resolved exactly like "ThermalExpansion"; several
+ * add up) of the BCLib as the array stan_hip_lumped_mass_hex8 takes.  counts[2] = {1 when the file holds such a BC, n_mat}.
+ * mat_rho [cap_mat] is filled when non-NULL (zeros where no BC speaks); a capacity that is too small and an unknown or
+ * non-elastic material ID (reported with the ID) are STAN_HOST_E_ARG. */
+int stan_host_db_get_density(stan_db *db, int64_t counts[2], int32_t cap_mat, double *mat_rho);
 /* Result write-back of SolverLinearStatics (Solver.cs:81-90, 171-178, 203-210, Main :56):
  * re-initialises step 0/1, stores disp[n*3] into Node.DispX/Y/Z[1] and strain/stress
  * [e*48] (may be NULL) into Element.Strain[1]/Stress[1], sets Result_StepNo = 1. */

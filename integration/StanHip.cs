@@ -114,6 +114,34 @@ namespace STAN_Solver
         public long n_fixed;
     }
 
+    /// stan_mass_sums (include/stan_hip.h); filled through the IntPtr argument of stan_hip_lumped_mass_hex8
+    [StructLayout(LayoutKind.Sequential)]
+    public struct StanMassSums
+    {
+        public double total_mass;
+        public double volume;
+        public double free_sum_x, free_sum_y, free_sum_z;
+        public double fixed_sum_x, fixed_sum_y, fixed_sum_z;
+        public long n_fixed;
+    }
+
+    /// stan_modes_report (include/stan_hip.h); filled through the IntPtr argument of stan_hip_modes
+    [StructLayout(LayoutKind.Sequential)]
+    public struct StanModesReport
+    {
+        public int block;
+        public int outer;
+        public int converged;
+        public int cg_worst_type;
+        public long cg_iterations;
+        public double max_rho;
+        public double solve_ms;
+        public double product_ms;
+        public double block_ms;
+        public double gram_ms;
+        public double rotate_ms;
+    }
+
     internal static class StanHipNative
     {
         // "stan_hip" resolves to libstan_hip.so on Linux (.NET probes lib<name>.so; Mono: <dllmap> or the same probing)
@@ -236,6 +264,29 @@ namespace STAN_Solver
             IntPtr ctx, IntPtr results, long n_nodes, double[] dT, int[] conn, int[] elem_mat, byte[] elem_type, int n_mat,
             double[] mat_E_nu, double[] mat_alpha);
         [DllImport(Lib)] internal static extern int stan_hip_thermal_load_times(IntPtr ctx, [Out] double[] ms);
+
+        // ---- modal analysis: mat_rho [n_mat]; M [N], mass_node [n_nodes] or null; sums -> StanMassSums or IntPtr.Zero.  modes:
+        //      M [N], lambda / rho [n_modes], phi [n_modes * N]; rep -> StanModesReport or IntPtr.Zero.  The block helpers take
+        //      [q * N] blocks, Q [q * q], mask [q] or null; rhs is pinned and updated in place
+        [DllImport(Lib)] internal static extern int stan_hip_lumped_mass_hex8(
+            IntPtr ctx, long n_nodes, double[] xyz, int[] node_dof, long n_elem, int[] conn, int[] elem_mat, byte[] elem_type,
+            int n_mat, double[] mat_E_nu, long n_dof, int[] ndof_reduction, double[] mat_rho, [Out] double[] M,
+            [Out] double[] mass_node, IntPtr sums);
+        [DllImport(Lib)] internal static extern int stan_hip_lumped_mass_hex8_dev(
+            IntPtr ctx, long n_nodes, IntPtr d_xyz, IntPtr d_node_dof, long n_elem, IntPtr d_conn, IntPtr d_elem_mat,
+            IntPtr d_elem_type, int n_mat, double[] mat_E_nu, long n_dof, IntPtr d_ndof_reduction, double[] mat_rho,
+            IntPtr d_M, IntPtr d_mass_node, IntPtr sums);
+        [DllImport(Lib)] internal static extern int stan_hip_modes(
+            IntPtr ctx, IntPtr K, double[] M, int n_modes, double tol, int max_outer, double solve_eps, int solve_max_its,
+            [Out] double[] lambda, [Out] double[] phi, [Out] double[] rho, IntPtr rep);
+        [DllImport(Lib)] internal static extern int stan_hip_modes_dev(
+            IntPtr ctx, IntPtr K, IntPtr d_M, int n_modes, double tol, int max_outer, double solve_eps, int solve_max_its,
+            IntPtr d_lambda, IntPtr d_phi, IntPtr d_rho, IntPtr rep);
+        [DllImport(Lib)] internal static extern int stan_hip_block_gram(
+            IntPtr ctx, long N, int q, double[] Z, double[] W, double[] M, [Out] double[] A, [Out] double[] B);
+        [DllImport(Lib)] internal static extern int stan_hip_block_rotate(
+            IntPtr ctx, long N, int q, double[] Z, double[] W, double[] M, double[] Q, double[] lambda, byte[] mask, int in_place,
+            [Out] double[] X, [Out] double[] KX, double[] rhs, [Out] double[] rho2);
 
         // ---- introspection / parity helpers
         [DllImport(Lib)] internal static extern int stan_hip_matrix_info(IntPtr K, out StanMatrixInfo info);

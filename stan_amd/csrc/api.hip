@@ -1,5 +1,5 @@
-// api.hip -- the extern "C" surface of libstan_hip.so declared in include/stan_hip.h, part 1 of 4: a context's life-cycle, options
-// and reports.  (api_solve.hip, api_post.hip, api_loads.hip: the other parts; api_stage.h: what they share.)
+// api.hip -- the extern "C" surface of libstan_hip.so declared in include/stan_hip.h, part 1 of 5: a context's life-cycle, options
+// and reports.  (api_solve.hip, api_post.hip, api_loads.hip, api_modal.hip: the other parts; api_stage.h: what they share.)
 #include <cstring>
 
 #include "internal.h"

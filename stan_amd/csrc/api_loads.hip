@@ -1,4 +1,4 @@
-// api_loads.hip -- the extern "C" surface, part 4 of 4: the load vectors of body forces, face pressures, prescribed displacements
+// api_loads.hip -- the extern "C" surface, part 4 of 5: the load vectors of body forces, face pressures, prescribed displacements
 // and temperature changes, and the thermal stress correction (loads.hip).  One device, one rank (one_device_refused).
 #include "api_stage.h"
 
@@ -132,6 +132,48 @@ int stan_hip_thermal_load_times(stan_ctx *ctx, double ms[3]) {
     STAN_NO_GROUP(ctx, "thermal_load_times");
     for (int k = 0; k < 3; k++) ms[k] = ctx->prof_thermal_ms[k];
     return STAN_OK;
+}
+
+// Lumped mass: the body term with b = rho, per node and at the free DOFs.
+int stan_hip_lumped_mass_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *d_xyz, const int32_t *d_node_dof,
+                                  int64_t n_elem, const int32_t *d_conn, const int32_t *d_elem_mat,
+                                  const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
+                                  const int32_t *d_red, const double *mat_rho, double *d_M, double *d_mass_node, void *sums) {
+    if (!ctx) return STAN_E_ARG;
+    STANCHK(one_device_refused(ctx, "lumped_mass_hex8"));
+    if (!d_xyz || !d_node_dof || !d_red || !mat_E_nu || !mat_rho || (n_elem > 0 && (!d_conn || !d_elem_mat || !d_elem_type))) {
+        ctx->err = "lumped_mass_hex8_dev: null argument";
+        return STAN_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const stan_mesh d{.n_nodes = n_nodes, .n_elem = n_elem, .n_dof = n_dof, .n_mat = n_mat, .xyz = d_xyz,
+                      .node_dof = d_node_dof, .conn = d_conn, .elem_mat = d_elem_mat, .elem_type = d_elem_type, .red = d_red,
+                      .mat_E_nu = mat_E_nu};
+    return stan_lumped_mass_device(ctx, d, mat_rho, d_M, d_mass_node, (stan_mass_sums *)sums);
+}
+
+int stan_hip_lumped_mass_hex8(stan_ctx *ctx, int64_t n_nodes, const double *xyz, const int32_t *node_dof, int64_t n_elem,
+                              const int32_t *conn, const int32_t *elem_mat, const uint8_t *elem_type, int32_t n_mat,
+                              const double *mat_E_nu, int64_t n_dof, const int32_t *red, const double *mat_rho, double *M,
+                              double *mass_node, void *sums) {
+    if (!ctx) return STAN_E_ARG;
+    STANCHK(one_device_refused(ctx, "lumped_mass_hex8"));
+    if (!xyz || !node_dof || !red || !mat_E_nu || !mat_rho || n_nodes <= 0 || n_mat <= 0 || n_elem < 0 || n_dof != n_nodes * 3 ||
+        (n_elem > 0 && (!conn || !elem_mat || !elem_type))) {
+        ctx->err = "lumped_mass_hex8: null or empty argument, or n_dof != 3 n_nodes";
+        return STAN_E_ARG;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const stan_mesh m{.n_nodes = n_nodes, .n_elem = n_elem, .n_dof = n_dof, .n_mat = n_mat, .xyz = xyz, .node_dof = node_dof,
+                      .conn = conn, .elem_mat = elem_mat, .elem_type = elem_type, .red = red, .mat_E_nu = mat_E_nu};
+    // the length of M is fixed by the reduction map alone; every other integer is checked on the device (loads.hip)
+    const size_t N = (size_t)(n_dof - count_fixed(m));
+    host_stage st(ctx);
+    mesh_dbufs bufs; dbuf<double> dM, dn;
+    STANCHK(bufs.upload(st, m));
+    STANCHK(dM.out(st, M, N));
+    STANCHK(dn.out(st, mass_node, (size_t)n_nodes));
+    return st.finish(stan_lumped_mass_device(ctx, bufs.dev, mat_rho, dM.p, dn.p, (stan_mass_sums *)sums), dM, dn);
 }
 
 int stan_hip_thermal_stress_hex8_dev(stan_ctx *ctx, int64_t n_nodes, const double *d_dT, int64_t n_elem, const int32_t *d_conn,

@@ -1,4 +1,4 @@
-// api_post.hip -- the extern "C" surface, part 3 of 4: stress recovery, results kept on the device(s), result scalars, nodal and
+// api_post.hip -- the extern "C" surface, part 3 of 5: stress recovery, results kept on the device(s), result scalars, nodal and
 // internal forces.
 #include "api_stage.h"
 

@@ -1,4 +1,4 @@
-// api_solve.hip -- the extern "C" surface, part 2 of 4: assembly, the CG solves, products and what a matrix tells about itself.
+// api_solve.hip -- the extern "C" surface, part 2 of 5: assembly, the CG solves, products and what a matrix tells about itself.
 #include <cstring>
 
 #include "api_stage.h"

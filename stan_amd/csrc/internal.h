@@ -494,6 +494,32 @@ int stan_thermal_load_device(stan_ctx *ctx, const stan_mesh &d, const double *ma
 // with conn, elem_mat and elem_type (no node array but d_dT); the integers are checked on the device first.  Synchronises
 // the stream.
 int stan_thermal_stress_device(stan_ctx *ctx, const stan_mesh &d, const double *d_dT, const double *mat_alpha, double *d_stress);
+// The row-sum lumped mass (stan_hip_lumped_mass_hex8): the body term of the load vector with b = (rho, 0, 0), its component 0
+// per node; d as above; mat_rho [n_mat] and sums are host memory; d_M [n_red], d_mass_node [n_nodes], either may be null.  The
+// same checks; a free DOF without positive mass is found before any output is stored.
+int stan_lumped_mass_device(stan_ctx *ctx, const stan_mesh &d, const double *mat_rho, double *d_M, double *d_mass_node,
+                            stan_mass_sums *sums);
+
+// ---- modal.hip ------------------------------------------------------------------------------
+// The tall-skinny block kernels of the modal driver (api_modal.hip); a block vector is [q][N], q <= STAN_MODAL_QMAX.  All
+// enqueue on the context's stream; those with host outputs synchronise it.
+constexpr int STAN_MODAL_QMAX = 32;
+// d_rhs [q][N] = M o X0 with X0's column 0 = M and column j > 0 the hash of (row, j); *bad = the first row whose M is not
+// positive and finite (-1: none).  Synchronises.
+int stan_modal_start_device(stan_ctx *ctx, int64_t N, int32_t q, const double *d_M, double *d_rhs, int64_t *bad);
+// A = Z^T W, B = Z^T (M o Z), host arrays [q*q] row-major.  Synchronises.
+int stan_modal_gram_device(stan_ctx *ctx, int64_t N, int32_t q, const double *d_Z, const double *d_W, const double *d_M, double *A,
+                           double *B);
+// X = Z Q, KX = W Q, R = KX - (M o X) diag(lambda), rho2 [q] (host) = sum R^2 / M, d_rhs column j = -R_j / lambda_j where bit j
+// of mask is clear.  Q [q*q] row-major and lambda [q] are host arrays.  d_X / d_KX may be d_Z / d_W.  Synchronises.
+int stan_modal_rotate_device(stan_ctx *ctx, int64_t N, int32_t q, const double *d_Z, const double *d_W, const double *d_M,
+                             const double *Q, const double *lambda, uint32_t mask, double *d_X, double *d_KX, double *d_rhs,
+                             double *rho2);
+// Z_j = X_j / lambda_j + D_dcol[j] (dcol[j] < 0: no correction).  d_Z may be d_X.  Enqueues only.
+int stan_modal_axpy_device(stan_ctx *ctx, int64_t N, int32_t q, const double *d_X, const double *lambda, const int32_t *dcol,
+                           const double *d_D, double *d_Z);
+// d_phi [k][N] = the first k columns of X, each scaled to M-norm 1 with its entry of largest magnitude positive.  Synchronises.
+int stan_modal_normalise_device(stan_ctx *ctx, int64_t N, int32_t k, const double *d_X, const double *d_M, double *d_phi);
 
 // ---- comm.cpp -------------------------------------------------------------------------------
 int stan_comm_allreduce_sum_f64(stan_ctx *ctx, double *d_buf, size_t count);

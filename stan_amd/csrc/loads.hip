@@ -7,6 +7,8 @@
 // No J^-1 is formed for the first two: det J == 0 is no error there.  No counterpart in the reference.
 // The thermal load and the thermal stress of section 3.9 are at the end of the kernels: one more element pass (k_th_elem) in
 // front of the same gather, and one pass over the recovered stress (k_th_stress).
+// The lumped mass of section 3.10 is the body term with b = (rho, 0, 0): k_ld_elem as it stands, and a gather of its own
+// (k_ms_gather) that keeps component 0 of node_gather's sum -- the bits of load_full at the node's first DOF.
 // Faces in CHEXA order:  0 xi=-1 {0,3,4,7}  1 xi=+1 {1,2,5,6}  2 eta=-1 {0,1,4,5}  3 eta=+1 {2,3,6,7}  4 zeta=-1 {0,1,2,3}
 // 5 zeta=+1 {4,5,6,7}; the face list is sorted by face_elem * 6 + face_id, strictly.
 // Phases, all bit-reproducible (no atomics on doubles):
@@ -285,6 +287,71 @@ k_th_stress_check(int64_t n_nodes, int64_t n_elem, int32_t n_mat, const int32_t 
     if (bits) atomicOr((unsigned long long *)&status[SS_ERRBITS], bits);
 }
 
+// ---- lumped mass: the node gather of component 0, checked before anything is stored ---------------
+// mass [n_nodes] (a temporary) = node_gather's l[0] with fe from k_ld_elem under mat_body = (rho, 0, 0); partial [gridDim.x][NMS]
+// = total | free by direction | fixed by direction; *bad_node = the first node with a free DOF whose mass is not positive.
+constexpr int NMS = 7;
+__global__ void __launch_bounds__(256)
+k_ms_gather(int64_t n_nodes, const int64_t *__restrict__ ptr, const int32_t *__restrict__ list, const double *__restrict__ fe,
+            const int32_t *__restrict__ node_dof, const int32_t *__restrict__ red, double *__restrict__ mass,
+            double *__restrict__ partial, long long *bad_node) {
+    __shared__ double sh[4][NMS];
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double s[NMS] = {0, 0, 0, 0, 0, 0, 0};
+    if (n < n_nodes) {
+        double l[3];
+        node_gather(ptr, list, fe, n, l);
+        mass[n] = l[0];
+        s[0] = l[0];
+        const int64_t d0 = node_dof[3 * n];
+        bool any_free = false;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const bool fixed = red[d0 + c] == -1;
+            s[(fixed ? 4 : 1) + c] = l[0];
+            any_free |= !fixed;
+        }
+        if (any_free && !(l[0] > 0.0)) atomicMin(bad_node, (long long)n);
+    }
+    block_sums(s, sh);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < NMS; k++) partial[(int64_t)blockIdx.x * NMS + k] = s[k];
+}
+
+// the stores, behind the check: M at the node's free DOFs in the reduced numbering, mass_node in node order
+__global__ void __launch_bounds__(256)
+k_ms_store(int64_t n_nodes, const double *__restrict__ mass, const int32_t *__restrict__ node_dof, const int32_t *__restrict__ red,
+           int64_t n_red, double *__restrict__ M, double *__restrict__ mass_node) {
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= n_nodes) return;
+    const double m = mass[n];
+    if (mass_node) mass_node[n] = m;
+    if (!M) return;
+    const int64_t d0 = node_dof[3 * n];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const int64_t d = d0 + c;
+        const int32_t r = red[d];
+        if (r != -1 && d - r < n_red) M[d - r] = m;
+    }
+}
+
+// one block: the mass partials in block order, then the element pass's volume
+__global__ void __launch_bounds__(256)
+k_ms_finish(int64_t n_gblocks, const double *__restrict__ gpartial, int64_t n_eblocks, const double *__restrict__ epartial, double *out) {
+    __shared__ double sh[4][NMS + 1];
+    double a[NMS + 1];
+#pragma unroll
+    for (int k = 0; k < NMS + 1; k++) a[k] = 0.0;
+    for (int64_t b = threadIdx.x; b < n_gblocks; b += 256)
+#pragma unroll
+        for (int k = 0; k < NMS; k++) a[k] += gpartial[b * NMS + k];
+    for (int64_t b = threadIdx.x; b < n_eblocks; b += 256) a[NMS] += epartial[b * NES];
+    block_sums(a, sh);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < NMS + 1; k++) out[k] = a[k];
+}
+
 // {beta, alpha} of every material, beta = E alpha / (1 - 2 nu) in fp64 exactly as written
 std::vector<double> thermal_beta(int32_t n_mat, const double *mat_E_nu, const double *mat_alpha) {
     std::vector<double> b(2 * (size_t)n_mat);
@@ -462,6 +529,66 @@ int stan_load_vector_device(stan_ctx *ctx, const stan_mesh &d, const double *mat
         sums->area = out[NGS + 1];
         sums->n_fixed = n_fixed;
         sums->n_faces = n_faces;
+    }
+    return STAN_OK;
+}
+
+int stan_lumped_mass_device(stan_ctx *ctx, const stan_mesh &d, const double *mat_rho, double *d_M, double *d_mass_node,
+                            stan_mass_sums *sums) {
+    const char *who = "lumped_mass_hex8";
+    const int64_t n_nodes = d.n_nodes, n_elem = d.n_elem, n_dof = d.n_dof, n_mat = d.n_mat;
+    auto bad = [&](const std::string &why, int rc) { ctx->err = std::string(who) + ": " + why; return rc; };
+    STANCHK(stan_elem_limits_check(ctx, who, d));
+    if (!d_M && !d_mass_node && !sums) return bad("none of M / mass_node / sums asked for", STAN_E_ARG);
+    std::vector<double> body(3 * (size_t)n_mat, 0.0);   // (rho, 0, 0): the body term's b; outlives the stream's copy
+    for (int64_t m = 0; m < n_mat; m++) {
+        if (!(mat_rho[m] >= 0.0) || !std::isfinite(mat_rho[m])) return bad("density of material " + std::to_string(m) + " is negative or not finite", STAN_E_ARG);
+        body[3 * (size_t)m] = mat_rho[m];
+    }
+    hipStream_t st = ctx->stream;
+    // ---- the checks, before anything is indexed with the caller's integers
+    dev_scope tmp(ctx);
+    int64_t n_fixed;
+    STANCHK(stan_elem_args_check(ctx, tmp, who, d, 0, nullptr, nullptr, &n_fixed));
+    const int64_t n_red = n_dof - n_fixed;
+
+    const int64_t n_gblocks = nblk(n_nodes, 256), n_eblocks = nblk(n_elem, 32);
+    double *d_body, *d_fe, *d_mass, *d_gpartial, *d_epartial, *d_out;
+    STANCHK(tmp.alloc(&d_body, body.size()));
+    STANCHK(tmp.alloc(&d_fe, (size_t)(n_elem > 0 ? n_elem : 1) * 24));
+    STANCHK(tmp.alloc(&d_mass, (size_t)n_nodes));
+    STANCHK(tmp.alloc(&d_gpartial, (size_t)n_gblocks * NMS));
+    STANCHK(tmp.alloc(&d_epartial, (size_t)(n_eblocks > 0 ? n_eblocks : 1) * NES));
+    STANCHK(tmp.alloc(&d_out, (size_t)NMS + 1));
+    HIPCHK(ctx, hipMemcpyAsync(d_body, body.data(), body.size() * 8, hipMemcpyHostToDevice, st));
+    const long long none = 0x7fffffffffffffffLL;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_status + SS_AUX, &none, 8, hipMemcpyHostToDevice, st));
+    if (n_elem > 0)   // the load vector's element pass, no face
+        hipLaunchKernelGGL(k_ld_elem, dim3((unsigned)n_eblocks), dim3(256), 0, st, n_elem, d.xyz, d.conn, d.elem_mat, d_body, (int64_t)0,
+                           nullptr, nullptr, nullptr, d_fe, d_epartial);
+    int64_t *d_ptr;
+    int32_t *d_list;
+    STANCHK(stan_incidence_lists(ctx, tmp, n_nodes, n_elem, d.conn, true, &d_ptr, &d_list));
+    hipLaunchKernelGGL(k_ms_gather, dim3((unsigned)n_gblocks), dim3(256), 0, st, n_nodes, d_ptr, d_list, d_fe, d.node_dof, d.red, d_mass,
+                       d_gpartial, (long long *)(ctx->d_status + SS_AUX));
+    // a free DOF without mass: known before anything is stored into the caller's arrays
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, ctx->d_status + SS_AUX, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (ctx->h_status[SS_AUX] != none)
+        return bad("node " + std::to_string(ctx->h_status[SS_AUX]) + " has a free DOF and no positive mass", STAN_E_ARG);
+    if (d_M || d_mass_node)
+        hipLaunchKernelGGL(k_ms_store, dim3((unsigned)n_gblocks), dim3(256), 0, st, n_nodes, d_mass, d.node_dof, d.red, n_red, d_M, d_mass_node);
+    if (sums) hipLaunchKernelGGL(k_ms_finish, dim3(1), dim3(256), 0, st, n_gblocks, d_gpartial, n_eblocks, d_epartial, d_out);
+    HIPCHK(ctx, hipGetLastError());
+    double out[NMS + 1];
+    if (sums) HIPCHK(ctx, hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));   // the temporaries go back to the context behind the kernels
+    if (sums) {
+        sums->total_mass = out[0];
+        for (int c = 0; c < 3; c++) { sums->free_sum[c] = out[1 + c]; sums->fixed_sum[c] = out[4 + c]; }
+        sums->volume = out[NMS];
+        sums->n_fixed = n_fixed;
     }
     return STAN_OK;
 }

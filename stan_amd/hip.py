@@ -57,6 +57,8 @@ EXPORTS = [
     "stan_hip_load_vector_hex8", "stan_hip_load_vector_hex8_dev", "stan_hip_load_vector_times",
     "stan_hip_thermal_load_hex8", "stan_hip_thermal_load_hex8_dev", "stan_hip_thermal_load_times",
     "stan_hip_thermal_stress_hex8", "stan_hip_thermal_stress_hex8_dev", "stan_hip_results_thermal_stress",
+    "stan_hip_lumped_mass_hex8", "stan_hip_lumped_mass_hex8_dev", "stan_hip_modes", "stan_hip_modes_dev",
+    "stan_hip_block_gram", "stan_hip_block_rotate",
 ]
 # only in the lab build (stan_amd/csrc/lab/stan_hip_lab.h, selected with STAN_HIP_LIB)
 LAB_EXPORTS = ["stan_hip_csr_spmv_bench", "stan_hip_lab_placement_map", "stan_hip_lab_placement_variants", "stan_hip_lab_placement_alloc", "stan_hip_lab_placement_rounds", "stan_hip_lab_placement_cross", "stan_hip_lab_incg_penalty", "stan_hip_lab_placement_vecalloc", "stan_hip_lab_placement_vecshape", "stan_hip_lab_pairing_pmc"]
@@ -113,6 +115,22 @@ class ThermalSums(_Sums):
     """stan_thermal_sums (include/stan_hip.h)"""
     _fields_ = [("load_sum", C.c_double * 3), ("free_sum", C.c_double * 3), ("volume", C.c_double), ("dT_integral", C.c_double),
                 ("n_fixed", C.c_int64)]
+
+
+class MassSums(_Sums):
+    """stan_mass_sums (include/stan_hip.h)"""
+    _fields_ = [("total_mass", C.c_double), ("volume", C.c_double), ("free_sum", C.c_double * 3), ("fixed_sum", C.c_double * 3),
+                ("n_fixed", C.c_int64)]
+
+
+class ModesReport(C.Structure):
+    """stan_modes_report (include/stan_hip.h)"""
+    _fields_ = [("block", C.c_int32), ("outer", C.c_int32), ("converged", C.c_int32), ("cg_worst_type", C.c_int32),
+                ("cg_iterations", C.c_int64), ("max_rho", C.c_double), ("solve_ms", C.c_double), ("product_ms", C.c_double),
+                ("block_ms", C.c_double), ("gram_ms", C.c_double), ("rotate_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class StanHipError(RuntimeError):
@@ -513,6 +531,74 @@ class Context:
         self._chk(self.lib.stan_hip_thermal_load_times(self.h, ms))
         return dict(thermal_elem_ms=ms[0], thermal_list_ms=ms[1], thermal_gather_ms=ms[2])
 
+    # -- modal analysis ---------------------------------------------------------------------------
+    def lumped_mass_hex8(self, xyz, node_dof, conn, elem_mat, elem_type, mat_E_nu, red, mat_rho, M=True, mass_node=True, sums=True):
+        """stan_hip_lumped_mass_hex8 from host arrays: (M [N], mass_node [n_nodes], sums MassSums).  mat_rho [n_mat] (None is
+        passed on as NULL).  An output not asked for is None."""
+        xyz, node_dof, conn, elem_mat, elem_type, mat_E_nu, red = _mesh(
+            xyz=xyz, node_dof=node_dof, conn=conn, elem_mat=elem_mat, elem_type=elem_type, mat_E_nu=mat_E_nu, red=red)
+        n_dof = red.shape[0]
+        N = n_dof - int((red == -1).sum())
+        rho = None if mat_rho is None else np.ascontiguousarray(mat_rho, dtype=np.float64).reshape(-1)
+        if rho is not None and rho.shape[0] != mat_E_nu.shape[0]:
+            raise ValueError("lumped_mass_hex8: mat_rho must be [n_mat]")
+        Mo = np.zeros(N) if M else None
+        mn = np.zeros(xyz.shape[0]) if mass_node else None
+        q = MassSums() if sums else None
+        self._chk(self.lib.stan_hip_lumped_mass_hex8(
+            self.h, C.c_int64(xyz.shape[0]), _ptr(xyz, C.c_double), _ptr(node_dof, C.c_int32), C.c_int64(conn.shape[0]),
+            _ptr(conn, C.c_int32), _ptr(elem_mat, C.c_int32), _ptr(elem_type, C.c_uint8), C.c_int32(mat_E_nu.shape[0]),
+            _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _ptr(red, C.c_int32), _ptr(rho, C.c_double), _ptr(Mo, C.c_double),
+            _ptr(mn, C.c_double), C.byref(q) if sums else None))
+        return Mo, mn, q
+
+    def lumped_mass_hex8_dev(self, n_nodes, d_xyz, d_node_dof, n_elem, d_conn, d_elem_mat, d_elem_type, mat_E_nu, n_dof, d_red,
+                             mat_rho, d_M=None, d_mass_node=None, sums=True):
+        """All d_* are device pointers (ints, e.g. torch tensor.data_ptr()) or None; mat_rho a host array.  Returns the
+        MassSums (None when not asked for)."""
+        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        rho = None if mat_rho is None else np.ascontiguousarray(mat_rho, dtype=np.float64).reshape(-1)
+        q = MassSums() if sums else None
+        self._chk(self.lib.stan_hip_lumped_mass_hex8_dev(
+            self.h, C.c_int64(n_nodes), _dev(d_xyz, C.c_double), _dev(d_node_dof, C.c_int32), C.c_int64(n_elem),
+            _dev(d_conn, C.c_int32), _dev(d_elem_mat, C.c_int32), _dev(d_elem_type, C.c_uint8), C.c_int32(mat_E_nu.shape[0]),
+            _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _dev(d_red, C.c_int32), _ptr(rho, C.c_double), _opt(d_M),
+            _opt(d_mass_node), C.byref(q) if sums else None))
+        return q
+
+    def block_gram(self, Z, W, M):
+        """stan_hip_block_gram: (A, B) [q, q] = Z^T W, Z^T (M o Z) for block vectors Z, W [q, N] and the diagonal M [N]."""
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        M = np.ascontiguousarray(M, dtype=np.float64).reshape(-1)
+        if Z.ndim != 2 or W.shape != Z.shape or M.shape[0] != Z.shape[1]:
+            raise ValueError("block_gram: Z, W must be [q, N] and M [N]")
+        q, N = Z.shape
+        A, B = np.zeros((q, q)), np.zeros((q, q))
+        self._chk(self.lib.stan_hip_block_gram(self.h, C.c_int64(N), C.c_int32(q), _ptr(Z, C.c_double), _ptr(W, C.c_double),
+                                               _ptr(M, C.c_double), _ptr(A, C.c_double), _ptr(B, C.c_double)))
+        return A, B
+
+    def block_rotate(self, Z, W, M, Q, lam, mask=None, in_place=False, rhs=None):
+        """stan_hip_block_rotate: (X, KX, rhs, rho2).  Z, W [q, N], M [N], Q [q, q], lam [q]; mask [q] of 0 / 1 or None; rhs
+        [q, N] the array whose unmasked columns are replaced (a copy is returned; None: zeros)."""
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        M = np.ascontiguousarray(M, dtype=np.float64).reshape(-1)
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(-1)
+        if Z.ndim != 2 or W.shape != Z.shape or M.shape[0] != Z.shape[1] or Q.shape != (Z.shape[0],) * 2 or lam.shape[0] != Z.shape[0]:
+            raise ValueError("block_rotate: Z, W must be [q, N], M [N], Q [q, q], lam [q]")
+        q, N = Z.shape
+        mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+        X, KX, rho2 = np.zeros((q, N)), np.zeros((q, N)), np.zeros(q)
+        R = np.zeros((q, N)) if rhs is None else np.array(rhs, dtype=np.float64).reshape(q, N)
+        self._chk(self.lib.stan_hip_block_rotate(
+            self.h, C.c_int64(N), C.c_int32(q), _ptr(Z, C.c_double), _ptr(W, C.c_double), _ptr(M, C.c_double), _ptr(Q, C.c_double),
+            _ptr(lam, C.c_double), _ptr(mk, C.c_uint8), C.c_int32(int(bool(in_place))), _ptr(X, C.c_double), _ptr(KX, C.c_double),
+            _ptr(R, C.c_double), _ptr(rho2, C.c_double)))
+        return X, KX, R, rho2
+
     def _thermal_stress_args(self, dT, conn, elem_mat, elem_type, mat_E_nu, mat_alpha):
         dT = np.ascontiguousarray(dT, dtype=np.float64).reshape(-1)
         conn, elem_mat, elem_type, mat_E_nu = _mesh(conn=conn, elem_mat=elem_mat, elem_type=elem_type, mat_E_nu=mat_E_nu)
@@ -693,6 +779,29 @@ class Matrix:
             C.c_int32(precision_mode), _dev(d_U, C.c_double), _ptr(term, C.c_int32), _ptr(its, C.c_int32),
             _ptr(rel, C.c_double)))
         return self._multi_reports(term[:m], its[:m], rel[:m])
+
+    def modes(self, M, n_modes, tol=0.0, max_outer=0, solve_eps=0.0, solve_max_its=0):
+        """stan_hip_modes: the n_modes lowest eigenpairs of K phi = lambda M phi, M [N] the diagonal mass.  Returns (lambda
+        [n_modes], phi [n_modes, N], rho [n_modes], report dict of stan_modes_report)."""
+        M = np.ascontiguousarray(M, dtype=np.float64).reshape(-1)
+        N = self.info()["n_reduced"]
+        if M.shape[0] != N:
+            raise ValueError("modes: M must be [N]")
+        k = max(int(n_modes), 1)
+        lam, phi, rho, rep = np.zeros(k), np.zeros((k, N)), np.zeros(k), ModesReport()
+        self.ctx._chk(self.ctx.lib.stan_hip_modes(
+            self.ctx.h, self.k, _ptr(M, C.c_double), C.c_int32(int(n_modes)), C.c_double(tol), C.c_int32(max_outer),
+            C.c_double(solve_eps), C.c_int32(solve_max_its), _ptr(lam, C.c_double), _ptr(phi, C.c_double), _ptr(rho, C.c_double),
+            C.byref(rep)))
+        return lam, phi, rho, rep.as_dict()
+
+    def modes_dev(self, d_M, n_modes, d_lambda, d_phi, d_rho, tol=0.0, max_outer=0, solve_eps=0.0, solve_max_its=0):
+        """d_M [N], d_lambda / d_rho [n_modes], d_phi [n_modes, N]: device pointers (ints).  Returns the report dict."""
+        rep = ModesReport()
+        self.ctx._chk(self.ctx.lib.stan_hip_modes_dev(
+            self.ctx.h, self.k, _opt(d_M), C.c_int32(int(n_modes)), C.c_double(tol), C.c_int32(max_outer), C.c_double(solve_eps),
+            C.c_int32(solve_max_its), _opt(d_lambda), _opt(d_phi), _opt(d_rho), C.byref(rep)))
+        return rep.as_dict()
 
     def to_csr(self, upper_only=True):
         nnz = C.c_int64(0)

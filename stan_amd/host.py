@@ -235,7 +235,7 @@ EXPORTS += [
     "stan_host_db_assign_part", "stan_host_db_add_bc", "stan_host_db_set_analysis",
     "stan_host_db_sizes", "stan_host_db_get_analysis", "stan_host_db_assign_dof",
     "stan_host_db_get_flat", "stan_host_db_get_reduction", "stan_host_db_set_results",
-    "stan_host_db_get_results", "stan_host_db_get_distributed_loads", "stan_host_db_get_thermal_loads",
+    "stan_host_db_get_results", "stan_host_db_get_distributed_loads", "stan_host_db_get_thermal_loads", "stan_host_db_get_density",
 ]
 
 
@@ -408,6 +408,15 @@ class Db:
         self._chk(self.lib.stan_host_db_get_thermal_loads(self.h, cnt, C.c_int32(al.shape[0]), _p(al, C.c_double),
                                                           _p(dT, C.c_double)), "thermal_loads")
         return dict(any=bool(cnt[0]), mat_alpha=al[:nm], dT=dT)
+
+    def density(self):
+        """BuildDensity: dict(any, mat_rho [n_mat]) from the "Density" BCs (material IDs, component 0 = rho; they add up)."""
+        cnt = (C.c_int64 * 2)()
+        self._chk(self.lib.stan_host_db_get_density(self.h, cnt, C.c_int32(0), None), "density")
+        nm = int(cnt[1])
+        rho = np.zeros(max(nm, 1))
+        self._chk(self.lib.stan_host_db_get_density(self.h, cnt, C.c_int32(rho.shape[0]), _p(rho, C.c_double)), "density")
+        return dict(any=bool(cnt[0]), mat_rho=rho[:nm])
 
     def set_results(self, disp, strain=None, stress=None):
         disp = np.ascontiguousarray(disp, dtype=np.float64)

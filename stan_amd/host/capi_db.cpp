@@ -132,7 +132,7 @@ int stan_host_db_add_bc(stan_db *d, int32_t id, const char *name, const char *ty
     bc.Type = type; bc.has_type = true;
     bc.ID = id; bc.ColorID = id % 9;
     for (int64_t i = 0; i < n; i++) {
-        const bool by_material = bc.Type == "BodyForce" || bc.Type == "ThermalExpansion";   // keyed by material IDs
+        const bool by_material = bc.Type == "BodyForce" || bc.Type == "ThermalExpansion" || bc.Type == "Density";   // keyed by material IDs
         if (!by_material && !d->db.NodeLib.ContainsKey(node_ids[i])) continue;  // BoundaryCondition.cs:89
         MatrixST v(3, 1);
         v.M[0] = vals[3 * i]; v.M[1] = vals[3 * i + 1]; v.M[2] = vals[3 * i + 2];
@@ -262,6 +262,22 @@ int stan_host_db_get_thermal_loads(stan_db *d, int64_t counts[2], int32_t cap_ma
         std::copy(tl.mat_alpha.begin(), tl.mat_alpha.end(), mat_alpha);
     }
     if (dT) std::copy(tl.dT.begin(), tl.dT.end(), dT);
+    return STAN_HOST_OK;
+}
+
+int stan_host_db_get_density(stan_db *d, int64_t counts[2], int32_t cap_mat, double *mat_rho) {
+    if (!d || !counts) return STAN_HOST_E_ARG;
+    FlatModel f;
+    int rc = Flatten(d->db, &f, &d->err);
+    if (rc) return rc;
+    MassDensity md;
+    rc = BuildDensity(d->db, f, &md, &d->err);
+    if (rc) return rc;
+    counts[0] = md.any; counts[1] = (int64_t)md.mat_rho.size();
+    if (mat_rho) {
+        if ((int64_t)cap_mat < counts[1]) { d->err = "mat_rho buffer too small"; return STAN_HOST_E_ARG; }
+        std::copy(md.mat_rho.begin(), md.mat_rho.end(), mat_rho);
+    }
     return STAN_HOST_OK;
 }
 

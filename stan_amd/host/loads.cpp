@@ -179,6 +179,37 @@ int BuildThermalLoads(const Database &db, const FlatModel &flat, ThermalLoads *o
     return STAN_HOST_OK;
 }
 
+bool HasDensity(const Database &db) {
+    for (const auto &kv : db.BCLib.Items())
+        if (kv.second.Type == "Density") return true;
+    return false;
+}
+
+int BuildDensity(const Database &db, const FlatModel &flat, MassDensity *out, std::string *err) {
+    auto fail = [&](const std::string &why) { if (err) *err = why; return STAN_HOST_E_ARG; };
+    *out = MassDensity();
+    const size_t nm = flat.mat_E_nu.size() / 2;
+    // the elastic materials in MatLib order are the rows of mat_E_nu (Flatten)
+    std::vector<std::pair<int, int>> mat_row;
+    for (const auto &kv : db.MatLib.Items())
+        if (kv.second.Type.find("Elastic") != std::string::npos) mat_row.emplace_back(kv.first, (int)mat_row.size());
+    if (mat_row.size() != nm) return fail("the flat model does not belong to this database");
+    out->mat_rho.assign(nm, 0.0);
+    for (const auto &kv : db.BCLib.Items()) {
+        const BoundaryCondition &bc = kv.second;
+        if (bc.Type != "Density") continue;
+        out->any = true;
+        for (const auto &nv : bc.NodalValues.Items()) {   // keys are material IDs; several such BCs add up
+            if (nv.second.M.size() < 3) return fail("Density value is not 3x1");
+            int row = -1;
+            for (const auto &mr : mat_row) if (mr.first == nv.first) row = mr.second;
+            if (row < 0) return fail("Density on unknown (or not elastic) material " + std::to_string(nv.first));
+            out->mat_rho[(size_t)row] += nv.second.M[0];
+        }
+    }
+    return STAN_HOST_OK;
+}
+
 }  // namespace stan
 
 extern "C" {

@@ -25,7 +25,12 @@
 // The Types "Temperature" and "ThermalExpansion"  give the thermal load from stan_hip_thermal_load_hex8,
 // added to F in front of the distributed loads: a block "Thermal loads:", the recovered stress less beta dT, the reactions of
 // --reactions as f_int - l, a "thermal" object with --json; one device only.
+// --modes K [--modes-tol T] runs the modal analysis INSTEAD of the static solve and never writes the
+// STdb: the lumped mass from the "Density" BCs (material IDs, component 0 = rho) and the K lowest natural frequencies from
+// stan_hip_modes; a block "Natural frequencies:", with --json a "modes" object, with --vtu PREFIX one PREFIX_mode_NNN.vtu per
+// mode (point arrays "Mode Shape X" / "Y" / "Z" and "Magnitude").  One device only; a file without a "Density" entry is refused.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -64,6 +69,8 @@ int main(int argc, char **argv) {
     std::vector<int> devices;
     std::string vtu_prefix, vtu_results;
     bool vtu = false, vtu_cells = false, reactions = false;
+    int modes = 0;
+    double modes_tol = 0.0;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) {
@@ -89,11 +96,13 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--vtu-results") && i + 1 < argc) vtu_results = argv[++i];
         else if (!strcmp(argv[i], "--vtu-cells")) vtu_cells = true;
         else if (!strcmp(argv[i], "--reactions")) reactions = true;
+        else if (!strcmp(argv[i], "--modes") && i + 1 < argc) modes = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--modes-tol") && i + 1 < argc) modes_tol = atof(argv[++i]);
         else path = argv[i];
     }
     if (path.empty()) {  // Path = path[0] -> IndexOutOfRangeException in the reference
         fprintf(stderr, "usage: stan_solver [--device N | --gpus N | --devices a,b,..] [--p2p] [--mixed|--fixed48] "
-                        "[--no-merit-stop] [--packed] [--object-results] [--json] [--vtu PREFIX [--vtu-results \"name,..\"] [--vtu-cells]] [--reactions] "
+                        "[--no-merit-stop] [--packed] [--object-results] [--json] [--vtu PREFIX [--vtu-results \"name,..\"] [--vtu-cells]] [--reactions] [--modes K [--modes-tol T]] "
                         "<model.STdb>\n");
         return 2;
     }
@@ -116,6 +125,15 @@ int main(int argc, char **argv) {
                         "multi-device handle holds them in chunks (drop --gpus/--devices)\n");
         return 2;
     }
+    if (modes < 0 || modes_tol < 0 || (modes == 0 && modes_tol != 0)) {
+        fprintf(stderr, "stan_solver: --modes K needs K > 0, --modes-tol T needs T >= 0 and --modes\n");
+        return 2;
+    }
+    if (modes && devices.size() > 1) {
+        fprintf(stderr, "stan_solver: --modes works on one device: the lumped mass adds up all elements at a node, and the block "
+                        "solves run on a single-rank context (drop --gpus/--devices)\n");
+        return 2;
+    }
     SolverOptions opt;
     opt.device = device; opt.devices = devices; opt.precision = precision; opt.placement_tries = placement_tries; opt.merit_stop = merit_stop; opt.profile = json;
     opt.p2p = p2p;
@@ -135,6 +153,15 @@ int main(int argc, char **argv) {
     if (!Functions.ProtoDeserialize(path, &DB, &err)) return fail("ProtoDeserialize", err);
     t_read = secs(t0);
     printf("     Done\n");
+    // --modes is checked before anything is computed or written: it needs the densities, and the static analysis it replaces
+    if (modes && !HasDensity(DB)) {
+        fprintf(stderr, "stan_solver: --modes needs a \"Density\" boundary condition (material IDs, component 0 = rho): the file has none\n");
+        return 2;
+    }
+    if (modes && DB.AnalysisLib.Type != "Linear_Statics") {
+        fprintf(stderr, "stan_solver: --modes works on a Linear_Statics file\n");
+        return 2;
+    }
 
     printf("   DoF ordering: ");  // Solver.cs:44-47
     fflush(stdout);
@@ -172,6 +199,48 @@ int main(int argc, char **argv) {
         Functions.ParallelAssembly_K(DB, nDOF_reduction, 1, "Initial", &K);  // Solver.cs:157
         stan_matrix_info minfo;
         stan_hip_matrix_info(K.K, &minfo);
+
+        if (modes) {   // the modal analysis instead of the static solve: nothing of it reaches the STdb
+            MassDensity md;
+            if (BuildDensity(DB, K.flat, &md, &err)) return fail("boundary conditions", err);
+            std::vector<double> lambda, phi, rho;
+            stan_mass_sums msum{};
+            stan_modes_report rep{};
+            Functions.Modes(K, nDOF_reduction, md, modes, modes_tol, &lambda, &phi, &rho, &msum, &rep);
+            const double two_pi = 6.283185307179586476925;
+            printf("   Total mass: %.6e   volume: %.6e\n", msum.total_mass, msum.volume);
+            printf("   Natural frequencies: (block %d, %d outer steps, %lld CG iterations, %s)\n", rep.block, rep.outer,
+                   (long long)rep.cg_iterations, rep.converged ? "converged" : "NOT converged");
+            printf("     mode            lambda    frequency [Hz]           rho\n");
+            for (int j = 0; j < modes; j++)
+                printf("     %4d  %16.8e  %16.8e  %12.3e\n", j + 1, lambda[(size_t)j], std::sqrt(lambda[(size_t)j]) / two_pi, rho[(size_t)j]);
+            if (vtu) {
+                const size_t N = (size_t)minfo.n_reduced;
+                std::vector<double> shape((size_t)n_nodes * 3);
+                for (int j = 0; j < modes; j++) {
+                    const std::vector<double> full = Functions.Include_BC_DOF(
+                        std::vector<double>(phi.begin() + (ptrdiff_t)((size_t)j * N), phi.begin() + (ptrdiff_t)((size_t)(j + 1) * N)), nDOF_reduction);
+                    for (size_t k = 0; k < shape.size(); k++) shape[k] = full[(size_t)K.flat.node_dof[k]];
+                    Functions.Export_Mode_Vtu(K, shape, vtu_prefix, j + 1);
+                }
+                printf("   VTU export: %s_mode_001.vtu ... %s_mode_%03d.vtu\n", vtu_prefix.c_str(), vtu_prefix.c_str(), modes);
+            }
+            printf("\n%s\n  Total CPU time: %.2f s\n%s\n", separator, secs(t_total), separator);
+            if (json) {   // %.17g: the doubles round-trip
+                printf("{\"n_gpus\": 1, \"n_dof\": %d, \"n_reduced\": %lld, \"t_wall_s\": %.3f, \"modes\": {\"n_modes\": %d, \"block\": %d, "
+                       "\"outer\": %d, \"converged\": %d, \"cg_iterations\": %lld, \"total_mass\": %.17g",
+                       DB.nDOF, (long long)minfo.n_reduced, secs(t_wall), modes, rep.block, rep.outer, rep.converged,
+                       (long long)rep.cg_iterations, msum.total_mass);
+                for (int pass = 0; pass < 3; pass++) {
+                    printf(", \"%s\": [", pass == 0 ? "lambda" : pass == 1 ? "frequency_hz" : "rho");
+                    for (int j = 0; j < modes; j++)
+                        printf("%s%.17g", j ? ", " : "", pass == 0 ? lambda[(size_t)j] : pass == 1 ? std::sqrt(lambda[(size_t)j]) / two_pi : rho[(size_t)j]);
+                    printf("]");
+                }
+                printf("}}\n");
+            }
+            return 0;
+        }
 
         // thermal loads, in front of the distributed loads: their F - f_int(u0) then holds this load too
         ThermalLoads thermal_bc;

@@ -345,6 +345,15 @@ struct ThermalLoads {
 };
 bool HasThermalLoads(const Database &db);
 int BuildThermalLoads(const Database &db, const FlatModel &flat, ThermalLoads *out, std::string *err);
+// ---- density (loads.cpp; no counterpart in the reference) ------------------------------------
+// The BoundaryCondition Type "Density" (MATERIAL IDs -> component 0 = rho, resolved exactly like "ThermalExpansion"; several
+// add up) as the array stan_hip_lumped_mass_hex8 takes.
+struct MassDensity {
+    bool any = false;                  // the file holds at least one such BC
+    std::vector<double> mat_rho;       // [n_mat] in the material order of FlatModel (zeros without a "Density")
+};
+bool HasDensity(const Database &db);
+int BuildDensity(const Database &db, const FlatModel &flat, MassDensity *out, std::string *err);
 // faces all of whose corners are in the node set; see stan_host_pressure_faces
 void PressureFaces(int64_t n_elem, const int32_t *conn, const std::vector<uint8_t> &in_set, const std::vector<double> &node_p,
                    std::vector<int32_t> *face_elem, std::vector<uint8_t> *face_id, std::vector<double> *face_p);

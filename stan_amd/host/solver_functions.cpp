@@ -231,6 +231,47 @@ void SolverFunctions::Thermal_Stress(SparseMatrixHandle &K, const ThermalLoads &
     if (rc) throw std::runtime_error(stan_hip_last_error(K.ctx));
 }
 
+void SolverFunctions::Modes(SparseMatrixHandle &K, const std::vector<int32_t> &red, const MassDensity &md, int n_modes, double tol,
+                            std::vector<double> *lambda, std::vector<double> *phi, std::vector<double> *rho, stan_mass_sums *sums,
+                            stan_modes_report *rep) const {
+    const FlatModel &f = K.flat;
+    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
+    size_t n_fixed = 0;
+    for (int32_t r : red) n_fixed += r == -1;
+    const size_t N = red.size() - n_fixed;
+    std::vector<double> M(N > 0 ? N : 1, 0.0);
+    if (stan_hip_lumped_mass_hex8(K.ctx, n_nodes, f.xyz.data(), f.node_dof.data(), n_elem, f.conn.data(), f.elem_mat.data(),
+                                  f.elem_type.data(), (int32_t)(f.mat_E_nu.size() / 2), f.mat_E_nu.data(), (int64_t)red.size(),
+                                  red.data(), md.mat_rho.data(), M.data(), nullptr, sums))
+        throw std::runtime_error(stan_hip_last_error(K.ctx));
+    const size_t k = n_modes > 0 ? (size_t)n_modes : 1;
+    lambda->assign(k, 0.0); rho->assign(k, 0.0); phi->assign(k * (N > 0 ? N : 1), 0.0);
+    if (stan_hip_modes(K.ctx, K.K, M.data(), n_modes, tol, 0, 0.0, 0, lambda->data(), phi->data(), rho->data(), rep))
+        throw std::runtime_error(stan_hip_last_error(K.ctx));
+}
+
+void SolverFunctions::Export_Mode_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &prefix, int mode) const {
+    const FlatModel &f = K.flat;
+    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
+    static const char *const names[4] = {"Mode Shape X", "Mode Shape Y", "Mode Shape Z", "Magnitude"};
+    std::vector<double> point(4 * (size_t)n_nodes);
+    for (int64_t n = 0; n < n_nodes; n++) {
+        double s2 = 0;
+        for (int c = 0; c < 3; c++) {
+            const double v = shape[(size_t)(3 * n + c)];
+            point[(size_t)c * (size_t)n_nodes + (size_t)n] = v;
+            s2 += v * v;
+        }
+        point[3 * (size_t)n_nodes + (size_t)n] = std::sqrt(s2);
+    }
+    char num[16];
+    snprintf(num, sizeof num, "%03d", mode);
+    const std::string path = prefix + "_mode_" + num + ".vtu";
+    if (stan_host_write_vtu(path.c_str(), n_nodes, f.xyz.data(), shape.data(), n_elem, f.conn.data(), 4, names, point.data(), 0, nullptr,
+                            nullptr))
+        throw std::runtime_error("cannot write " + path);
+}
+
 void SolverFunctions::Recovery_Stress_Keep(SparseMatrixHandle &K, const std::vector<double> &dU) const {
     const FlatModel &f = K.flat;
     const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();

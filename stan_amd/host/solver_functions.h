@@ -104,6 +104,15 @@ class SolverFunctions {
     // ... and the recovered stress loses beta dT at every corner: the host array when given, else the results kept on the
     // device (K.results)
     void Thermal_Stress(SparseMatrixHandle &K, const ThermalLoads &tl, std::vector<double> *stress) const;
+    // Modal analysis (stan_hip_lumped_mass_hex8 + stan_hip_modes; no step of the reference): the lumped mass of `md` and the
+    // n_modes lowest eigenpairs of K phi = lambda M phi; lambda / rho [n_modes], phi [n_modes][N] on the free DOFs; *sums and
+    // *rep always filled.  One device only.
+    void Modes(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const MassDensity &md, int n_modes, double tol,
+               std::vector<double> *lambda, std::vector<double> *phi, std::vector<double> *rho, stan_mass_sums *sums,
+               stan_modes_report *rep) const;
+    // <prefix>_mode_NNN.vtu (NNN = 001 ...) for one mode: shape [n_nodes*3] in NodeLib order as the point arrays "Mode Shape X" /
+    // "Y" / "Z" and "Magnitude", through the writer of vtu.cpp (the shape also takes the place of the displacements)
+    void Export_Mode_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &prefix, int mode) const;
     // "name,name,..." of --vtu-results -> indices (stan_host_scalar_name's strings; empty text = all 24); false + *err on an unknown name
     static bool ParseScalarNames(const std::string &text, std::vector<int32_t> *sel, std::string *err);
 
