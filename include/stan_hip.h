@@ -769,6 +769,96 @@ int stan_hip_block_rotate(stan_ctx *ctx, int64_t N, int32_t q, const double *Z, 
                           const double *Q, const double *lambda, const uint8_t *mask, int32_t in_place, double *X,
                           double *KX, double *rhs, double *rho2);
 
+/* ---- transient dynamics: the shifted matrix K + sigma M and implicit Newmark steps ------------- */
+/* No step of the reference.  *out becomes a NEW matrix of this context that holds K + sigma diag(M)
+ * on the free DOFs: M [N] the diagonal mass in the reduced numbering (stan_hip_lumped_mass_hex8), sigma >= 0.  It has K's
+ * layout (its structure arrays are copied) and a value array of its own, placed as an assembled matrix's is; it is unscaled
+ * and carries no derived stream, whatever K's state: every entry that takes a matrix takes it -- stan_hip_cg_solve,
+ * stan_hip_cg_solve_multi, stan_hip_spmv, stan_hip_modes, stan_hip_matrix_to_csr -- and treats it as it treats an assembled K.
+ * It is freed with stan_hip_matrix_free and does not depend on K's lifetime.
+ *   values  an entry not on the diagonal of a free DOF is the value stan_hip_matrix_to_csr exports for K (K's bits while K is
+ *           unscaled, divided by s_row s_col once a solve has left S K S in place); the diagonal entry of free DOF d is
+ *           fma(sigma, M[d - red[d]], v) on that value v; fixed DOFs and padding are copied as they are.
+ * K itself is read only: its values, its scaled flag and its streams are unchanged to the bit.
+ * STAN_E_ARG: a NULL pointer, a K of another context, sigma negative or not finite, an entry of M that is not positive and
+ * finite (found before anything is allocated).  STAN_E_UNSUPPORTED: a multi-device handle, a context with a communicator.
+ * STAN_E_ALLOC: what the call had allocated is given back.  On an error *out is not written. */
+int stan_hip_matrix_shifted(stan_ctx *ctx, stan_matrix *K, double sigma, const double *M, stan_matrix **out);
+/* The same with M in device memory on the context's GPU: read only, ready on the context's stream, naturally aligned. */
+int stan_hip_matrix_shifted_dev(stan_ctx *ctx, stan_matrix *K, double sigma, const double *d_M, stan_matrix **out);
+
+/* M a + C v + K u = g(t) F on the free DOFs by the implicit Newmark method, C = alpha_R M + beta_R K (Rayleigh damping); every
+ * vector is [N] in the reduced numbering.  With
+ *   a0 = 1/(beta_N dt^2), a1 = gamma/(beta_N dt), a2 = 1/(beta_N dt), a3 = 1/(2 beta_N) - 1, a4 = gamma/beta_N - 1,
+ *   a5 = dt (gamma/(2 beta_N) - 1), c_K = 1 + a1 beta_R, sigma = (a0 + a1 alpha_R) / c_K
+ * one step is, in this order of operations:
+ *   p  = a0 u + a2 v + a3 a,  w = a1 u + a4 v + a5 a,  Kw = K w (only when beta_R != 0)
+ *   b  = (g(t_{n+1}) F + M o (p + alpha_R w) + beta_R Kw) / c_K
+ *   (K + sigma M) u' = b        stan_hip_cg_solve_dev's loop on the shifted matrix, fp64, from a zero start, solve_eps and
+ *                               solve_max_its as that entry takes them (both 0 selects 1e-6); the merit stop is off for
+ *                               these solves, as under STAN_OPT_CG_MERIT_STOP 0 (its type 7 would end the run, see below)
+ *   a' = a0 (u' - u) - a2 v - a3 a,  v' = v + dt ((1 - gamma) a + gamma a')
+ * The start is a_0 = (g(0) F - alpha_R M o v0 - beta_R K v0 - K u0) / M; u0 / v0 NULL is zero, and a product is made only where
+ * its vector is given and its coefficient is not zero.  g is the piecewise-linear curve through the n_curve points
+ * (curve_t ascending, curve_g), constant before the first and after the last point, evaluated on the host in fp64; n_curve = 0
+ * is g = 1 (a step load).  beta_N = gamma = 0 selects 1/4 and 1/2; the call requires gamma >= 1/2 and
+ * beta_N >= (gamma + 1/2)^2 / 4 (unconditional stability).
+ * Outputs, each may be NULL except u_end, v_end, a_end:
+ *   probe_u [(n_steps + 1)][n_probe]  u at the reduced DOFs probe_dof [n_probe] at steps 0 .. n_steps
+ *   snaps   [n_snap][3][N]            u, v, a at steps 0, snap_every, 2 snap_every, ... <= n_steps (snap_every > 0)
+ *   energy  [(n_steps + 1)][3]        1/2 v.M v, 1/2 u.K u, g F.u per step (one more product per step, made only on request);
+ *                                     per-workgroup partial sums added in workgroup order: no atomics on doubles
+ *   u_end, v_end, a_end [N]           the state after the last step made (n_steps = 0: the start state and a_0)
+ * rep: a stan_transient_report or NULL (void * as for stan_hip_modes); behind the argument checks it is written on every way
+ * out.  The call builds the shifted matrix (stan_hip_matrix_shifted_dev) and frees it on every way out; K is left as a solve
+ * leaves it.  Two calls give the same bits, and so do the host and the _dev entry.
+ * STAN_E_ARG: dt <= 0 or not finite, negative n_steps, n_curve, n_probe, snap_every, solve_eps or solve_max_its, negative
+ * alpha_R or beta_R, Newmark parameters outside the stable range, a curve with descending t or a value that is not finite, a
+ * probe DOF outside [0, N), NULL where an array is required (snaps with snap_every = 0 is ignored), an entry of M that is not
+ * positive and finite, a K of another context.  STAN_E_UNSUPPORTED: a multi-device handle, a context with a communicator; a
+ * solve that ends with type 5, 7, -5 or -4 stops the run there: the step and the type in the report and in
+ * stan_hip_last_error.  On an error no output but the report has been written. */
+typedef struct stan_transient_report {
+    int32_t steps;            /* steps made                                                                    */
+    int32_t failed_step;      /* the step (1-based) whose solve stopped the run, 0: none                       */
+    int32_t cg_worst_type;    /* the worst termination type a step's solve met: negative < 5 < 7 < 1          */
+    int32_t cg_min_iterations; /* per step                                                                     */
+    int32_t cg_max_iterations;
+    int32_t reserved;
+    int64_t cg_iterations;    /* summed over the steps                                                         */
+    double sigma;             /* the shift of the run's matrix K + sigma M                                     */
+    double shift_ms;          /* stream time of the shift pass, the solves, the products K w / K u and the     */
+    double solve_ms;          /*   step kernels, by events when profiling is on, else zeros                    */
+    double product_ms;
+    double step_ms;
+    double predict_ms;        /* of step_ms: the predict passes,                                               */
+    double correct_ms;        /*   the correct passes with their finishing sums                                */
+} stan_transient_report;
+int stan_hip_transient(stan_ctx *ctx, stan_matrix *K, const double *M, const double *F, const double *u0, const double *v0,
+                       double dt, int32_t n_steps, double beta_N, double gamma, double alpha_R, double beta_R, int32_t n_curve,
+                       const double *curve_t, const double *curve_g, double solve_eps, int32_t solve_max_its, int32_t n_probe,
+                       const int32_t *probe_dof, double *probe_u, int32_t snap_every, double *snaps, double *energy,
+                       double *u_end, double *v_end, double *a_end, void *rep);
+/* The same with every array except the curve in device memory on the context's GPU: inputs read only, ready on the context's
+ * stream, naturally aligned; every entry of every output asked for is stored and nothing beside them; complete on return. */
+int stan_hip_transient_dev(stan_ctx *ctx, stan_matrix *K, const double *d_M, const double *d_F, const double *d_u0,
+                           const double *d_v0, double dt, int32_t n_steps, double beta_N, double gamma, double alpha_R,
+                           double beta_R, int32_t n_curve, const double *curve_t, const double *curve_g, double solve_eps,
+                           int32_t solve_max_its, int32_t n_probe, const int32_t *d_probe_dof, double *d_probe_u,
+                           int32_t snap_every, double *d_snaps, double *d_energy, double *d_u_end, double *d_v_end,
+                           double *d_a_end, void *rep);
+/* The step kernels of stan_hip_transient on host arrays (introspection, as stan_hip_block_gram is); coef [8] = a0, a1, a2, a3,
+ * a4, a5, alpha_R, beta_R.
+ *   predict  w [N] (or NULL) and b [N] of one step from u, v, a, F, M and the scalar gF = g(t_{n+1}); Kw [N] = K w or NULL (then
+ *            the beta_R Kw term is left out); c_K = 1 + coef[1] coef[7] in both forms.
+ *   correct  u, v, a [N] are replaced by u' = u_new, v', a' (coef, dt, gamma).  energy [3] or NULL: 1/2 v'.M v', 1/2 u'.Ku and
+ *            gF F.u' from the same pass (M, F, Ku [N] required then), summed as stan_hip_transient sums them. */
+int stan_hip_newmark_predict(stan_ctx *ctx, int64_t N, const double *u, const double *v, const double *a, const double *F,
+                             const double *M, const double *Kw, const double *coef, double gF, double *w, double *b);
+int stan_hip_newmark_correct(stan_ctx *ctx, int64_t N, const double *u_new, double *u, double *v, double *a, const double *coef,
+                             double dt, double gamma, const double *M, const double *F, const double *Ku, double gF,
+                             double *energy);
+
 /* ---- introspection / parity helpers ------------------------------------------------------- */
 typedef struct stan_matrix_info {
     int64_t n_dof;        /* full DOF count                                      */

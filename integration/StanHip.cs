@@ -142,6 +142,26 @@ namespace STAN_Solver
         public double rotate_ms;
     }
 
+    /// stan_transient_report (include/stan_hip.h); filled through the IntPtr argument of stan_hip_transient
+    [StructLayout(LayoutKind.Sequential)]
+    public struct StanTransientReport
+    {
+        public int steps;
+        public int failed_step;
+        public int cg_worst_type;
+        public int cg_min_iterations;
+        public int cg_max_iterations;
+        public int reserved;
+        public long cg_iterations;
+        public double sigma;
+        public double shift_ms;
+        public double solve_ms;
+        public double product_ms;
+        public double step_ms;
+        public double predict_ms;
+        public double correct_ms;
+    }
+
     internal static class StanHipNative
     {
         // "stan_hip" resolves to libstan_hip.so on Linux (.NET probes lib<name>.so; Mono: <dllmap> or the same probing)
@@ -287,6 +307,30 @@ namespace STAN_Solver
         [DllImport(Lib)] internal static extern int stan_hip_block_rotate(
             IntPtr ctx, long N, int q, double[] Z, double[] W, double[] M, double[] Q, double[] lambda, byte[] mask, int in_place,
             [Out] double[] X, [Out] double[] KX, double[] rhs, [Out] double[] rho2);
+
+        // ---- transient dynamics: M, F, u0, v0 (or null) [N]; curve_t / curve_g [n_curve] or null; probe_dof [n_probe], probe_u
+        //      [(n_steps + 1) * n_probe], snaps [n_snap * 3 * N], energy [(n_steps + 1) * 3] or null; rep -> StanTransientReport or
+        //      IntPtr.Zero.  The step helpers take coef [8]; u, v, a of correct are pinned and updated in place
+        [DllImport(Lib)] internal static extern int stan_hip_matrix_shifted(
+            IntPtr ctx, IntPtr K, double sigma, double[] M, out IntPtr shifted);
+        [DllImport(Lib)] internal static extern int stan_hip_matrix_shifted_dev(
+            IntPtr ctx, IntPtr K, double sigma, IntPtr d_M, out IntPtr shifted);
+        [DllImport(Lib)] internal static extern int stan_hip_transient(
+            IntPtr ctx, IntPtr K, double[] M, double[] F, double[] u0, double[] v0, double dt, int n_steps, double beta_N,
+            double gamma, double alpha_R, double beta_R, int n_curve, double[] curve_t, double[] curve_g, double solve_eps,
+            int solve_max_its, int n_probe, int[] probe_dof, [Out] double[] probe_u, int snap_every, [Out] double[] snaps,
+            [Out] double[] energy, [Out] double[] u_end, [Out] double[] v_end, [Out] double[] a_end, IntPtr rep);
+        [DllImport(Lib)] internal static extern int stan_hip_transient_dev(
+            IntPtr ctx, IntPtr K, IntPtr d_M, IntPtr d_F, IntPtr d_u0, IntPtr d_v0, double dt, int n_steps, double beta_N,
+            double gamma, double alpha_R, double beta_R, int n_curve, double[] curve_t, double[] curve_g, double solve_eps,
+            int solve_max_its, int n_probe, IntPtr d_probe_dof, IntPtr d_probe_u, int snap_every, IntPtr d_snaps,
+            IntPtr d_energy, IntPtr d_u_end, IntPtr d_v_end, IntPtr d_a_end, IntPtr rep);
+        [DllImport(Lib)] internal static extern int stan_hip_newmark_predict(
+            IntPtr ctx, long N, double[] u, double[] v, double[] a, double[] F, double[] M, double[] Kw, double[] coef, double gF,
+            [Out] double[] w, [Out] double[] b);
+        [DllImport(Lib)] internal static extern int stan_hip_newmark_correct(
+            IntPtr ctx, long N, double[] u_new, double[] u, double[] v, double[] a, double[] coef, double dt, double gamma,
+            double[] M, double[] F, double[] Ku, double gF, [Out] double[] energy);
 
         // ---- introspection / parity helpers
         [DllImport(Lib)] internal static extern int stan_hip_matrix_info(IntPtr K, out StanMatrixInfo info);

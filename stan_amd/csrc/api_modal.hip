@@ -88,23 +88,6 @@ bool small_gen_eig(int q, const double *A, const double *B, double *lambda, doub
     return true;
 }
 
-// stream time of the driver's phases, by one event pair around each piece (profiling on; every piece ends synchronised)
-struct piece_timer {
-    stan_ctx *ctx;
-    event_bag evs;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    explicit piece_timer(stan_ctx *c) : ctx(c) {
-        if (ctx->profiling) { e0 = evs.make(); e1 = evs.make(); }
-    }
-    void begin() { if (e0) (void)hipEventRecord(e0, ctx->stream); }
-    void end(double *acc) {
-        if (!e0) return;
-        float t = 0;
-        (void)hipEventRecord(e1, ctx->stream);
-        if (hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&t, e0, e1) == hipSuccess) *acc += t;
-    }
-};
-
 // One device, one rank: the solves are the batched CG's (a single-rank context), the block kernels and their sums run on it
 int modal_refused(stan_ctx *ctx, const char *entry) {
     STAN_NO_GROUP(ctx, std::string(entry) + " (the block solves and the block kernels run on one device)");
@@ -115,16 +98,12 @@ int modal_refused(stan_ctx *ctx, const char *entry) {
     return STAN_OK;
 }
 
-int worse_type(int a, int b) {   // negative < 5 < 7 < 1
-    auto rank = [](int t) { return t < 0 ? 0 : t == 5 ? 1 : t == 7 ? 2 : 3; };
-    if (a == 0) return b;
-    return rank(b) < rank(a) || (rank(b) == rank(a) && b < a) ? b : a;
-}
-
 // the driver on device arrays: d_M [N], d_lambda / d_rho [k], d_phi [k][N]
 int modes_device(stan_ctx *ctx, stan_matrix *K, const double *d_M, int32_t k, double tol, int32_t max_outer, double solve_eps,
                  int32_t solve_max_its, double *d_lambda, double *d_phi, double *d_rho, stan_modes_report *rep) {
     auto bad = [&](const std::string &why, int rc) { ctx->err = "modes: " + why; return rc; };
+    // what every refusal of a K that is not positive definite ends with: the way such a model is analysed
+    const std::string free_hint = "a model without supports?  Analyse the shifted problem K + sigma M: stan_hip_matrix_shifted, stan_solver --modes-shift SIGMA";
     const int64_t N = K->n_red;
     if (k <= 0 || k > N) return bad("n_modes must be in [1, N]", STAN_E_ARG);
     if (!(tol >= 0) || !(solve_eps >= 0) || !std::isfinite(tol) || !std::isfinite(solve_eps) || max_outer < 0 || solve_max_its < 0)
@@ -168,7 +147,7 @@ int modes_device(stan_ctx *ctx, stan_matrix *K, const double *d_M, int32_t k, do
             R.cg_worst_type = worse_type(R.cg_worst_type, term[(size_t)c]);
         }
         if (R.cg_worst_type < 0) {
-            return bad("a CG column ended with termination type " + std::to_string(R.cg_worst_type) + " (K is not positive definite: a model without supports?)",
+            return bad("a CG column ended with termination type " + std::to_string(R.cg_worst_type) + " (K is not positive definite: " + free_hint + ")",
                        STAN_E_UNSUPPORTED);
         }
         return STAN_OK;
@@ -185,9 +164,11 @@ int modes_device(stan_ctx *ctx, stan_matrix *K, const double *d_M, int32_t k, do
         pt.begin();
         STANCHK(stan_modal_gram_device(ctx, N, q, Z, W, d_M, A.data(), B.data()));
         pt.end(&R.gram_ms);
-        if (!small_gen_eig(q, A.data(), B.data(), lam.data(), Qm.data())) return bad("the block lost rank (Z^T M Z is not positive definite)", STAN_E_UNSUPPORTED);
+        if (!small_gen_eig(q, A.data(), B.data(), lam.data(), Qm.data()))
+            return bad("the block lost rank (Z^T M Z is not positive definite: " + free_hint + ")", STAN_E_UNSUPPORTED);
         for (int j = 0; j < q; j++)
-            if (!(lam[(size_t)j] > 0.0)) return bad("Ritz value " + std::to_string(j) + " is not positive (K is not positive definite)", STAN_E_UNSUPPORTED);
+            if (!(lam[(size_t)j] > 0.0))
+                return bad("Ritz value " + std::to_string(j) + " is not positive (K is not positive definite: " + free_hint + ")", STAN_E_UNSUPPORTED);
         const bool last = R.outer >= max_outer;
         pt.begin();   // the last step needs no right-hand side: every column masked
         STANCHK(stan_modal_rotate_device(ctx, N, q, Z, W, d_M, Qm.data(), lam.data(), last ? 0xffffffffu : 0u, Z, W, rhs, rho2.data()));

@@ -291,7 +291,7 @@ int stan_hip_matrix_to_csr(stan_ctx *ctx, stan_matrix *K, int32_t upper_only, in
                         if (pass == 1) {
                             col[q] = (int32_t)(dc - red[dc]);
                             const double a = vals[(slot * 9 + 3 * m + n) * 64 + lane];
-                            val[q] = scaled ? a / (scale[(size_t)d] * scale[(size_t)dc]) : a;
+                            val[q] = scaled ? stan_unscaled_value(a, scale[(size_t)d], scale[(size_t)dc]) : a;
                         }
                         q++;
                     }

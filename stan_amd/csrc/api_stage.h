@@ -116,6 +116,30 @@ inline int one_device_refused(stan_ctx *ctx, const char *entry) {
     return STAN_OK;
 }
 
+// ---- what the drivers over the CG share (api_modal.hip, api_transient.hip) ------------------------------------------------------
+// stream time of a driver's phases, by one event pair around each piece (profiling on; every piece ends synchronised)
+struct piece_timer {
+    stan_ctx *ctx;
+    event_bag evs;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    explicit piece_timer(stan_ctx *c) : ctx(c) {
+        if (ctx->profiling) { e0 = evs.make(); e1 = evs.make(); }
+    }
+    void begin() { if (e0) (void)hipEventRecord(e0, ctx->stream); }
+    void end(double *acc) {
+        if (!e0) return;
+        float t = 0;
+        (void)hipEventRecord(e1, ctx->stream);
+        if (hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&t, e0, e1) == hipSuccess) *acc += t;
+    }
+};
+
+inline int worse_type(int a, int b) {   // negative < 5 < 7 < 1
+    auto rank = [](int t) { return t < 0 ? 0 : t == 5 ? 1 : t == 7 ? 2 : 3; };
+    if (a == 0) return b;
+    return rank(b) < rank(a) || (rank(b) == rank(a) && b < a) ? b : a;
+}
+
 // ---- results kept on the device(s) (stan_hip_recover_hex8_keep, api_post.hip) ------------------------------------------------
 struct stan_results {
     struct part { int device; int64_t e0, e1; double *d_strain, *d_stress; };

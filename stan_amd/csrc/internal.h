@@ -521,6 +521,45 @@ int stan_modal_axpy_device(stan_ctx *ctx, int64_t N, int32_t q, const double *d_
 // d_phi [k][N] = the first k columns of X, each scaled to M-norm 1 with its entry of largest magnitude positive.  Synchronises.
 int stan_modal_normalise_device(stan_ctx *ctx, int64_t N, int32_t k, const double *d_X, const double *d_M, double *d_phi);
 
+// ---- matrix_shift.hip -----------------------------------------------------------------------
+// The value stan_hip_matrix_to_csr exports for an entry a of a matrix that carries S K S, s_row and s_col its two scaling
+// factors: the export and the shift pass share this one expression.
+__host__ __device__ static inline double stan_unscaled_value(double a, double s_row, double s_col) { return a / (s_row * s_col); }
+// *bad = the first index of d_M [N] whose entry is not positive and finite (-1: none).  Synchronises.
+int stan_mass_check_device(stan_ctx *ctx, int64_t N, const double *d_M, int64_t *bad);
+// *out = a new matrix of the context holding K + sigma diag(M) on the free DOFs (stan_hip_matrix_shifted_dev): K's structure
+// arrays copied, its own value array by stan_matrix_alloc_stream, unscaled, nothing derived.  K is read only.  sigma and d_M
+// checked by the caller; shift_ms (may be null) gets the stream time of the value pass when profiling is on.  Synchronises.
+int stan_matrix_shifted_device(stan_ctx *ctx, stan_matrix *K, double sigma, const double *d_M, stan_matrix **out, double *shift_ms = nullptr);
+
+// ---- transient.hip --------------------------------------------------------------------------
+// The Newmark step kernels of the transient driver (api_transient.hip).  Every vector is [N] in
+// memory the caller of these functions owns, 16-byte aligned (the drivers stage a user's arrays); all enqueue on the context's
+// stream and none synchronises.
+struct stan_newmark_coef { double a0, a1, a2, a3, a4, a5, alpha_R, beta_R, c_K, dt, gamma; };
+constexpr int STAN_NM_ROWS = 512;   // entries per workgroup of the step kernels: one pair per lane
+inline int64_t stan_newmark_blocks(int64_t N) { return (N + STAN_NM_ROWS - 1) / STAN_NM_ROWS; }
+// a_0 = (gF F - alpha_R M o v0 - beta_R Kv0 - Ku0) / M; v0, Kv0, Ku0 may be null (the term is left out)
+int stan_newmark_start_device(stan_ctx *ctx, int64_t N, const stan_newmark_coef &c, double gF, const double *F, const double *M,
+                              const double *v0, const double *Kv0, const double *Ku0, double *a);
+// w = a1 u + a4 v + a5 a (the operand of the damping product)
+int stan_newmark_w_device(stan_ctx *ctx, int64_t N, const stan_newmark_coef &c, const double *u, const double *v, const double *a, double *w);
+// b = (gF F + M o (p + alpha_R w) + beta_R Kw) / c_K; Kw null: without the beta_R term
+int stan_newmark_predict_device(stan_ctx *ctx, int64_t N, const stan_newmark_coef &c, double gF, const double *u, const double *v,
+                                const double *a, const double *F, const double *M, const double *Kw, double *b);
+// u, v, a <- u_new, v', a' in place.  d_energy non-null: [3] = 1/2 v'.M v', 1/2 u'.Ku, gF F.u' from the same pass, through
+// d_partial [3][stan_newmark_blocks(N)] and one finishing workgroup per value (workgroup order)
+int stan_newmark_correct_device(stan_ctx *ctx, int64_t N, const stan_newmark_coef &c, const double *u_new, double *u, double *v,
+                                double *a, const double *M, const double *F, const double *Ku, double gF, double *d_partial,
+                                double *d_energy);
+// the same three sums of a state that no step made (step 0)
+int stan_newmark_energy_device(stan_ctx *ctx, int64_t N, const double *u, const double *v, const double *M, const double *F,
+                               const double *Ku, double gF, double *d_partial, double *d_energy);
+// row[j] = u[probe[j]], j < n_probe
+int stan_newmark_probe_device(stan_ctx *ctx, int32_t n_probe, const int32_t *d_probe, const double *u, double *row);
+// *bad = the first j whose probe[j] is outside [0, N) (-1: none).  Synchronises.
+int stan_newmark_probe_check_device(stan_ctx *ctx, int64_t N, int32_t n_probe, const int32_t *d_probe, int64_t *bad);
+
 // ---- comm.cpp -------------------------------------------------------------------------------
 int stan_comm_allreduce_sum_f64(stan_ctx *ctx, double *d_buf, size_t count);
 int stan_comm_info(stan_ctx *ctx, int *version, int *count, int *rank);

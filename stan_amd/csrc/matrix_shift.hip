@@ -1,0 +1,138 @@
+// matrix_shift.hip -- K + sigma diag(M) as a matrix of its own (stan_hip_matrix_shifted): the operator of
+// an implicit time step and of a shifted modal analysis.  The result has K's layout (copies of its structure arrays) and its own
+// value array, unscaled, with nothing derived: the CG, the products, the placement search, the value streams, row folding and
+// the modal driver run on it as on an assembled K.  One device, one rank (the callers refuse the rest).  K is read only.
+#include <cmath>
+
+#include "internal.h"
+
+namespace {
+
+// the first entry of M [N] that is not positive and finite
+__global__ void __launch_bounds__(256)
+k_mass_check(int64_t N, const double *__restrict__ M, long long *bad) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const double m = M[i];
+    if (!(m > 0.0) || m > 1.7976931348623157e308) atomicMin(bad, (long long)i);
+}
+
+// out = the exported values of K with sigma M on the free diagonal: a wavefront per slice, a lane per row, one pass over the
+// slice's slots (k_scale_matrix's walk); s non-null: `vals` carries S K S.  The diagonal block of a row is the first of its
+// own rowlen blocks whose column is the row (k_diag_get's search); fixed DOFs (fixmask), padding rows and padding slots are
+// copied.  M is read one element wide (a caller's pointer); no atomics, nothing of K is written.
+__global__ void __launch_bounds__(256)
+k_shift_matrix(int32_t nslices, int64_t nloc, const int32_t *__restrict__ slot_ptr, const int32_t *__restrict__ rowof,
+               const int32_t *__restrict__ rowlen, const int32_t *__restrict__ cols, const double *__restrict__ vals,
+               const double *__restrict__ s, const int32_t *__restrict__ red, const uint8_t *__restrict__ fixmask, double sigma,
+               const double *__restrict__ M, double *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t slice = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (slice >= nslices) return;
+    const int64_t row = rowof[slice * 64 + lane];
+    const bool live = row < nloc;
+    const int32_t len = live ? rowlen[row] : 0;
+    const int rfix = live ? fixmask[row] : 7;
+    double sr[3] = {1.0, 1.0, 1.0}, sm[3] = {0.0, 0.0, 0.0};
+    if (live) {
+#pragma unroll
+        for (int m = 0; m < 3; m++) {
+            if (s) sr[m] = s[3 * row + m];
+            const int64_t d = 3 * row + m;
+            if (!((rfix >> m) & 1)) sm[m] = M[d - red[d]];
+        }
+    }
+    const int32_t k0 = slot_ptr[slice], k1 = slot_ptr[slice + 1];
+    bool diag_open = true;   // the row's diagonal block has not been met yet
+    for (int32_t k = k0; k < k1; k++) {
+        const int32_t c = cols[(int64_t)k * 64 + lane];
+        const bool own = k - k0 < len;
+        const bool diag = own && diag_open && c == (int32_t)row;
+        if (diag) diag_open = false;
+        const int cfix = own ? fixmask[c] : 7;
+        double sc[3] = {1.0, 1.0, 1.0};
+        if (s && own) { sc[0] = s[3 * (int64_t)c]; sc[1] = s[3 * (int64_t)c + 1]; sc[2] = s[3 * (int64_t)c + 2]; }
+        const double *v = vals + (int64_t)k * 9 * 64 + lane;
+        double *o = out + (int64_t)k * 9 * 64 + lane;
+#pragma unroll
+        for (int m = 0; m < 3; m++)
+#pragma unroll
+            for (int n = 0; n < 3; n++) {
+                double a = v[(3 * m + n) * 64];
+                const bool free_entry = own && !((rfix >> m) & 1) && !((cfix >> n) & 1);
+                if (free_entry) {
+                    if (s) a = stan_unscaled_value(a, sr[m], sc[n]);
+                    if (diag && m == n) a = fma(sigma, sm[m], a);
+                }
+                o[(3 * m + n) * 64] = a;
+            }
+    }
+}
+
+template <typename T>
+int clone_array(stan_ctx *ctx, T **dst, const T *src, size_t n) {
+    STANCHK(stan_dmalloc(ctx, dst, n ? n : 1));
+    if (n && src) HIPCHK(ctx, hipMemcpyAsync(*dst, src, n * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+    return STAN_OK;
+}
+
+}  // namespace
+
+int stan_mass_check_device(stan_ctx *ctx, int64_t N, const double *d_M, int64_t *bad) {
+    hipStream_t st = ctx->stream;
+    const long long none = 0x7fffffffffffffffLL;
+    *bad = -1;
+    if (N <= 0) return STAN_OK;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_status + SS_AUX, &none, 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_mass_check, dim3(nblk(N, 256)), dim3(256), 0, st, N, d_M, (long long *)(ctx->d_status + SS_AUX));
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, ctx->d_status + SS_AUX, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (ctx->h_status[SS_AUX] != none) *bad = ctx->h_status[SS_AUX];
+    return STAN_OK;
+}
+
+int stan_matrix_shifted_device(stan_ctx *ctx, stan_matrix *K, double sigma, const double *d_M, stan_matrix **out, double *shift_ms) {
+    hipStream_t st = ctx->stream;
+    stan_matrix *S = new stan_matrix();
+    S->ctx = ctx;
+    ctx->matrices.push_back(S);
+    struct guard {   // a failed call gives back what it had allocated
+        stan_matrix *k; bool ok = false;
+        ~guard() { if (!ok) stan_hip_matrix_free(k); }
+    } g{S};
+    S->n_dof = K->n_dof; S->n_red = K->n_red; S->nb_glob = K->nb_glob;
+    S->r0 = K->r0; S->r1 = K->r1; S->u0 = K->u0; S->u1 = K->u1;
+    S->nloc = K->nloc; S->nhalo = K->nhalo; S->nslices = K->nslices; S->nslots = K->nslots; S->nblocks = K->nblocks;
+    S->max_row_blocks = K->max_row_blocks; S->n_elem_scanned = K->n_elem_scanned; S->sigma = K->sigma;
+    S->row_starts = K->row_starts;
+    const size_t npad = (size_t)K->nslices * 64;
+    STANCHK(clone_array(ctx, &S->d_slot_ptr, K->d_slot_ptr, (size_t)K->nslices + 1));
+    STANCHK(clone_array(ctx, &S->d_rowlen, K->d_rowlen, npad));
+    STANCHK(clone_array(ctx, &S->d_rowof, K->d_rowof, npad));
+    STANCHK(clone_array(ctx, &S->d_posof, K->d_posof, npad));
+    STANCHK(clone_array(ctx, &S->d_cols, K->d_cols, (size_t)K->nslots * 64));
+    STANCHK(clone_array(ctx, &S->d_red, K->d_red, (size_t)K->n_dof));
+    STANCHK(clone_array(ctx, &S->d_fixmask, K->d_fixmask, (size_t)K->nb_glob));
+    // (behind the columns: the allocation by trial times the product itself -- as in the assembly; the packed column stream
+    // is a function of the columns alone and is built by the first product that wants it, as K's was)
+    STANCHK(stan_matrix_alloc_stream(ctx, S, STAN_PREC_FP64, S->nslots, &S->vs[STAN_PREC_FP64].padded));
+    event_bag evs;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (ctx->profiling && shift_ms) { e0 = evs.make(); e1 = evs.make(); }
+    if (e0) (void)hipEventRecord(e0, st);
+    if (K->nslices > 0)
+        hipLaunchKernelGGL(k_shift_matrix, dim3(nblk(K->nslices, 4)), dim3(256), 0, st, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof,
+                           K->d_rowlen, K->d_cols, K->vals64(), K->scaled ? K->d_scale : (const double *)nullptr, K->d_red,
+                           K->d_fixmask, sigma, d_M, S->vals64());
+    HIPCHK(ctx, hipGetLastError());
+    if (e1) (void)hipEventRecord(e1, st);
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (e1) {
+        float t = 0;
+        if (hipEventElapsedTime(&t, e0, e1) == hipSuccess) *shift_ms += t;
+    }
+    g.ok = true;
+    *out = S;
+    return STAN_OK;
+}

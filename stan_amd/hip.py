@@ -59,6 +59,8 @@ EXPORTS = [
     "stan_hip_thermal_stress_hex8", "stan_hip_thermal_stress_hex8_dev", "stan_hip_results_thermal_stress",
     "stan_hip_lumped_mass_hex8", "stan_hip_lumped_mass_hex8_dev", "stan_hip_modes", "stan_hip_modes_dev",
     "stan_hip_block_gram", "stan_hip_block_rotate",
+    "stan_hip_matrix_shifted", "stan_hip_matrix_shifted_dev", "stan_hip_transient", "stan_hip_transient_dev",
+    "stan_hip_newmark_predict", "stan_hip_newmark_correct",
 ]
 # only in the lab build (stan_amd/csrc/lab/stan_hip_lab.h, selected with STAN_HIP_LIB)
 LAB_EXPORTS = ["stan_hip_csr_spmv_bench", "stan_hip_lab_placement_map", "stan_hip_lab_placement_variants", "stan_hip_lab_placement_alloc", "stan_hip_lab_placement_rounds", "stan_hip_lab_placement_cross", "stan_hip_lab_incg_penalty", "stan_hip_lab_placement_vecalloc", "stan_hip_lab_placement_vecshape", "stan_hip_lab_pairing_pmc"]
@@ -131,6 +133,23 @@ class ModesReport(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TransientReport(C.Structure):
+    """stan_transient_report (include/stan_hip.h)"""
+    _fields_ = [("steps", C.c_int32), ("failed_step", C.c_int32), ("cg_worst_type", C.c_int32), ("cg_min_iterations", C.c_int32),
+                ("cg_max_iterations", C.c_int32), ("reserved", C.c_int32), ("cg_iterations", C.c_int64), ("sigma", C.c_double),
+                ("shift_ms", C.c_double), ("solve_ms", C.c_double), ("product_ms", C.c_double), ("step_ms", C.c_double),
+                ("predict_ms", C.c_double), ("correct_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def newmark_coef(dt, beta_N=0.25, gamma=0.5, alpha_R=0.0, beta_R=0.0):
+    """coef [8] of stan_hip_newmark_predict / _correct: a0 .. a5 in the expressions of include/stan_hip.h, alpha_R, beta_R."""
+    return np.array([1.0 / (beta_N * dt * dt), gamma / (beta_N * dt), 1.0 / (beta_N * dt), 1.0 / (2.0 * beta_N) - 1.0,
+                     gamma / beta_N - 1.0, dt * (gamma / (2.0 * beta_N) - 1.0), alpha_R, beta_R])
 
 
 class StanHipError(RuntimeError):
@@ -599,6 +618,37 @@ class Context:
             _ptr(R, C.c_double), _ptr(rho2, C.c_double)))
         return X, KX, R, rho2
 
+    def newmark_predict(self, u, v, a, F, M, coef, gF, Kw=None, want_w=True):
+        """stan_hip_newmark_predict: (w or None, b) of one Newmark step from the state u, v, a [N]; coef as newmark_coef."""
+        u, v, a, F, M = (np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (u, v, a, F, M))
+        N = u.shape[0]
+        Kw = None if Kw is None else np.ascontiguousarray(Kw, dtype=np.float64).reshape(-1)
+        coef = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+        if any(x.shape[0] != N for x in (v, a, F, M)) or (Kw is not None and Kw.shape[0] != N) or coef.shape[0] != 8:
+            raise ValueError("newmark_predict: u, v, a, F, M, Kw must be [N] and coef [8]")
+        w, b = (np.zeros(N) if want_w else None), np.zeros(N)
+        self._chk(self.lib.stan_hip_newmark_predict(
+            self.h, C.c_int64(N), _ptr(u, C.c_double), _ptr(v, C.c_double), _ptr(a, C.c_double), _ptr(F, C.c_double),
+            _ptr(M, C.c_double), _ptr(Kw, C.c_double), _ptr(coef, C.c_double), C.c_double(gF), _ptr(w, C.c_double),
+            _ptr(b, C.c_double)))
+        return w, b
+
+    def newmark_correct(self, u_new, u, v, a, coef, dt, gamma, M=None, F=None, Ku=None, gF=1.0, energy=False):
+        """stan_hip_newmark_correct: (u', v', a', energy [3] or None); the inputs are left as they are."""
+        u_new = np.ascontiguousarray(u_new, dtype=np.float64).reshape(-1)
+        N = u_new.shape[0]
+        u, v, a = (np.array(x, dtype=np.float64).reshape(-1) for x in (u, v, a))
+        M, F, Ku = (None if x is None else np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (M, F, Ku))
+        coef = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+        if any(x.shape[0] != N for x in (u, v, a)) or any(x is not None and x.shape[0] != N for x in (M, F, Ku)) or coef.shape[0] != 8:
+            raise ValueError("newmark_correct: the vectors must be [N] and coef [8]")
+        e = np.zeros(3) if energy else None
+        self._chk(self.lib.stan_hip_newmark_correct(
+            self.h, C.c_int64(N), _ptr(u_new, C.c_double), _ptr(u, C.c_double), _ptr(v, C.c_double), _ptr(a, C.c_double),
+            _ptr(coef, C.c_double), C.c_double(dt), C.c_double(gamma), _ptr(M, C.c_double), _ptr(F, C.c_double),
+            _ptr(Ku, C.c_double), C.c_double(gF), _ptr(e, C.c_double)))
+        return u, v, a, e
+
     def _thermal_stress_args(self, dT, conn, elem_mat, elem_type, mat_E_nu, mat_alpha):
         dT = np.ascontiguousarray(dT, dtype=np.float64).reshape(-1)
         conn, elem_mat, elem_type, mat_E_nu = _mesh(conn=conn, elem_mat=elem_mat, elem_type=elem_type, mat_E_nu=mat_E_nu)
@@ -801,6 +851,84 @@ class Matrix:
         self.ctx._chk(self.ctx.lib.stan_hip_modes_dev(
             self.ctx.h, self.k, _opt(d_M), C.c_int32(int(n_modes)), C.c_double(tol), C.c_int32(max_outer), C.c_double(solve_eps),
             C.c_int32(solve_max_its), _opt(d_lambda), _opt(d_phi), _opt(d_rho), C.byref(rep)))
+        return rep.as_dict()
+
+    def shifted(self, sigma, M):
+        """stan_hip_matrix_shifted: a new Matrix holding K + sigma diag(M), M [N] the diagonal mass; K is left as it is."""
+        M = np.ascontiguousarray(M, dtype=np.float64).reshape(-1)
+        if M.shape[0] != self.info()["n_reduced"]:
+            raise ValueError("shifted: M must be [N]")
+        k = C.c_void_p()
+        self.ctx._chk(self.ctx.lib.stan_hip_matrix_shifted(self.ctx.h, self.k, C.c_double(sigma), _ptr(M, C.c_double), C.byref(k)))
+        return Matrix(self.ctx, k)
+
+    def shifted_dev(self, sigma, d_M):
+        """d_M [N]: a device pointer (int)."""
+        k = C.c_void_p()
+        self.ctx._chk(self.ctx.lib.stan_hip_matrix_shifted_dev(self.ctx.h, self.k, C.c_double(sigma), _opt(d_M), C.byref(k)))
+        return Matrix(self.ctx, k)
+
+    def modes_shifted(self, M, n_modes, sigma, **kw):
+        """The n_modes lowest eigenpairs of a model that may be free-free, through the shift: stan_hip_modes on K + sigma M
+        gives mu = lambda + sigma.  Returns (lambda = mu - sigma, phi, rho, report); rho and report["max_rho"] are the
+        convergence measures of the SHIFTED problem (relative to mu), report["shift"] = sigma."""
+        S = self.shifted(sigma, M)
+        try:
+            mu, phi, rho, rep = S.modes(M, n_modes, **kw)
+        finally:
+            S.free()
+        rep["shift"] = float(sigma)
+        return mu - sigma, phi, rho, rep
+
+    def transient(self, M, F, dt, n_steps, u0=None, v0=None, beta_N=0.0, gamma=0.0, alpha_R=0.0, beta_R=0.0, curve=None,
+                  solve_eps=0.0, solve_max_its=0, probe_dof=None, snap_every=0, energy=False):
+        """stan_hip_transient: implicit Newmark steps of M a + C v + K u = g(t) F.  curve: [(t, g), ...] or None (g = 1).
+        Returns a dict: u, v, a (the end state), probe_u [n_steps + 1, n_probe], snaps [n_snap, 3, N] or None, energy
+        [n_steps + 1, 3] or None, report (stan_transient_report; written on an error too: StanHipError.report)."""
+        N = self.info()["n_reduced"]
+        M, F = (np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (M, F))
+        u0, v0 = (None if x is None else np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (u0, v0))
+        if any(x is not None and x.shape[0] != N for x in (M, F, u0, v0)):
+            raise ValueError("transient: M, F, u0, v0 must be [N]")
+        ct, cg, nc = None, None, 0
+        if curve is not None:
+            cv = np.ascontiguousarray(curve, dtype=np.float64).reshape(-1, 2)
+            ct, cg, nc = np.ascontiguousarray(cv[:, 0]), np.ascontiguousarray(cv[:, 1]), cv.shape[0]
+        pd = None if probe_dof is None else np.ascontiguousarray(probe_dof, dtype=np.int32).reshape(-1)
+        npr = 0 if pd is None else pd.shape[0]
+        rows = max(int(n_steps), 0) + 1
+        pu = np.zeros((rows, npr)) if npr else None
+        n_snap = (max(int(n_steps), 0) // snap_every + 1) if snap_every > 0 else 0
+        sn = np.zeros((n_snap, 3, N)) if n_snap else None
+        en = np.zeros((rows, 3)) if energy else None
+        ue, ve, ae, rep = np.zeros(N), np.zeros(N), np.zeros(N), TransientReport()
+        rc = self.ctx.lib.stan_hip_transient(
+            self.ctx.h, self.k, _ptr(M, C.c_double), _ptr(F, C.c_double), _ptr(u0, C.c_double), _ptr(v0, C.c_double),
+            C.c_double(dt), C.c_int32(int(n_steps)), C.c_double(beta_N), C.c_double(gamma), C.c_double(alpha_R), C.c_double(beta_R),
+            C.c_int32(nc), _ptr(ct, C.c_double), _ptr(cg, C.c_double), C.c_double(solve_eps), C.c_int32(solve_max_its),
+            C.c_int32(npr), _ptr(pd, C.c_int32), _ptr(pu, C.c_double), C.c_int32(int(snap_every)), _ptr(sn, C.c_double),
+            _ptr(en, C.c_double), _ptr(ue, C.c_double), _ptr(ve, C.c_double), _ptr(ae, C.c_double), C.byref(rep))
+        if rc != 0:
+            e = StanHipError(rc, self.ctx.lib.stan_hip_last_error(self.ctx.h).decode())
+            e.report = rep.as_dict()
+            raise e
+        return dict(u=ue, v=ve, a=ae, probe_u=pu, snaps=sn, energy=en, report=rep.as_dict())
+
+    def transient_dev(self, d_M, d_F, dt, n_steps, d_u_end, d_v_end, d_a_end, d_u0=None, d_v0=None, beta_N=0.0, gamma=0.0,
+                      alpha_R=0.0, beta_R=0.0, curve=None, solve_eps=0.0, solve_max_its=0, n_probe=0, d_probe_dof=None,
+                      d_probe_u=None, snap_every=0, d_snaps=None, d_energy=None):
+        """Every d_* is a device pointer (int) or None; the curve stays on the host.  Returns the report dict."""
+        ct, cg, nc = None, None, 0
+        if curve is not None:
+            cv = np.ascontiguousarray(curve, dtype=np.float64).reshape(-1, 2)
+            ct, cg, nc = np.ascontiguousarray(cv[:, 0]), np.ascontiguousarray(cv[:, 1]), cv.shape[0]
+        rep = TransientReport()
+        self.ctx._chk(self.ctx.lib.stan_hip_transient_dev(
+            self.ctx.h, self.k, _opt(d_M), _opt(d_F), _opt(d_u0), _opt(d_v0), C.c_double(dt), C.c_int32(int(n_steps)),
+            C.c_double(beta_N), C.c_double(gamma), C.c_double(alpha_R), C.c_double(beta_R), C.c_int32(nc), _ptr(ct, C.c_double),
+            _ptr(cg, C.c_double), C.c_double(solve_eps), C.c_int32(solve_max_its), C.c_int32(int(n_probe)),
+            _opt(d_probe_dof, C.c_int32), _opt(d_probe_u), C.c_int32(int(snap_every)), _opt(d_snaps), _opt(d_energy),
+            _opt(d_u_end), _opt(d_v_end), _opt(d_a_end), C.byref(rep)))
         return rep.as_dict()
 
     def to_csr(self, upper_only=True):

@@ -29,6 +29,14 @@
 // STdb: the lumped mass from the "Density" BCs (material IDs, component 0 = rho) and the K lowest natural frequencies from
 // stan_hip_modes; a block "Natural frequencies:", with --json a "modes" object, with --vtu PREFIX one PREFIX_mode_NNN.vtu per
 // mode (point arrays "Mode Shape X" / "Y" / "Z" and "Magnitude").  One device only; a file without a "Density" entry is refused.
+// --modes-shift SIGMA (a model without supports): the modes of K + SIGMA M (stan_hip_matrix_shifted), printed as lambda = mu - SIGMA;
+// rho is then the convergence measure of the shifted problem, "shift" in the JSON object.
+// --transient --dt DT --steps N [--newmark B,G] [--rayleigh A,B] [--load-curve t0,g0,t1,g1,...] [--probe-node ID] [--solve-eps E]
+//  integrates M a + C v + K u = g(t) F from rest by stan_hip_transient INSTEAD of the static solve and never
+// writes the STdb: F is the model's own load (PointLoad, distributed and thermal loads), g = 1 without a curve (a step load), the
+// supports homogeneous (a non-zero "Displacement" is refused); a block "Transient:", with --json a "transient" object, with
+// --vtu PREFIX [--vtu-every K] PREFIX_step_NNNN.vtu every K steps (point arrays "Displacement", "Velocity", "Acceleration" X / Y / Z).
+// One device only; a file without a "Density" entry is refused.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -70,7 +78,26 @@ int main(int argc, char **argv) {
     std::string vtu_prefix, vtu_results;
     bool vtu = false, vtu_cells = false, reactions = false;
     int modes = 0;
-    double modes_tol = 0.0;
+    double modes_tol = 0.0, modes_shift = 0.0;
+    bool transient = false, transient_arg = false, bad_list = false;
+    SolverFunctions::TransientRun run;
+    int probe_node = 0, vtu_every = 1;
+    bool have_probe = false;
+    // "a,b,c" -> doubles; false when an item is not a number
+    auto number_list = [](const char *text, std::vector<double> *out) {
+        out->clear();
+        for (const char *p = text; *p;) {
+            char *end = nullptr;
+            const double x = strtod(p, &end);
+            if (end == p) return false;
+            out->push_back(x);
+            p = end;
+            if (*p == ',') p++;
+            else if (*p) return false;
+        }
+        return true;
+    };
+    std::vector<double> list;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) {
@@ -98,12 +125,34 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--reactions")) reactions = true;
         else if (!strcmp(argv[i], "--modes") && i + 1 < argc) modes = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--modes-tol") && i + 1 < argc) modes_tol = atof(argv[++i]);
+        else if (!strcmp(argv[i], "--modes-shift") && i + 1 < argc) modes_shift = atof(argv[++i]);
+        else if (!strcmp(argv[i], "--transient")) transient = true;
+        else if (!strcmp(argv[i], "--dt") && i + 1 < argc) { transient_arg = true; run.dt = atof(argv[++i]); }
+        else if (!strcmp(argv[i], "--steps") && i + 1 < argc) { transient_arg = true; run.n_steps = atoi(argv[++i]); }
+        else if (!strcmp(argv[i], "--solve-eps") && i + 1 < argc) { transient_arg = true; run.solve_eps = atof(argv[++i]); }
+        else if (!strcmp(argv[i], "--probe-node") && i + 1 < argc) { transient_arg = have_probe = true; probe_node = atoi(argv[++i]); }
+        else if (!strcmp(argv[i], "--vtu-every") && i + 1 < argc) { transient_arg = true; vtu_every = atoi(argv[++i]); }
+        else if (!strcmp(argv[i], "--newmark") && i + 1 < argc) {
+            transient_arg = true;
+            if (number_list(argv[++i], &list) && list.size() == 2) { run.beta_N = list[0]; run.gamma = list[1]; }
+            else bad_list = true;
+        } else if (!strcmp(argv[i], "--rayleigh") && i + 1 < argc) {
+            transient_arg = true;
+            if (number_list(argv[++i], &list) && list.size() == 2) { run.alpha_R = list[0]; run.beta_R = list[1]; }
+            else bad_list = true;
+        } else if (!strcmp(argv[i], "--load-curve") && i + 1 < argc) {
+            transient_arg = true;
+            if (number_list(argv[++i], &list) && !list.empty() && list.size() % 2 == 0)
+                for (size_t k = 0; k < list.size(); k += 2) { run.curve_t.push_back(list[k]); run.curve_g.push_back(list[k + 1]); }
+            else bad_list = true;
+        }
         else path = argv[i];
     }
     if (path.empty()) {  // Path = path[0] -> IndexOutOfRangeException in the reference
         fprintf(stderr, "usage: stan_solver [--device N | --gpus N | --devices a,b,..] [--p2p] [--mixed|--fixed48] "
-                        "[--no-merit-stop] [--packed] [--object-results] [--json] [--vtu PREFIX [--vtu-results \"name,..\"] [--vtu-cells]] [--reactions] [--modes K [--modes-tol T]] "
-                        "<model.STdb>\n");
+                        "[--no-merit-stop] [--packed] [--object-results] [--json] [--vtu PREFIX [--vtu-results \"name,..\"] [--vtu-cells]] [--reactions] [--modes K [--modes-tol T] [--modes-shift SIGMA]] "
+                        "[--transient --dt DT --steps N [--newmark B,G] [--rayleigh A,B] [--load-curve t0,g0,t1,g1,...] [--probe-node ID] "
+                        "[--solve-eps E] [--vtu PREFIX [--vtu-every K]]] <model.STdb>\n");
         return 2;
     }
     // --vtu is checked before anything is read: the input file is overwritten by a run that gets further
@@ -134,6 +183,39 @@ int main(int argc, char **argv) {
                         "solves run on a single-rank context (drop --gpus/--devices)\n");
         return 2;
     }
+    if (modes_shift != 0 && (!modes || !(modes_shift > 0) || !std::isfinite(modes_shift))) {
+        fprintf(stderr, "stan_solver: --modes-shift SIGMA needs SIGMA > 0 and --modes\n");
+        return 2;
+    }
+    // --transient, checked before anything is read as well
+    if (!transient && transient_arg) {
+        fprintf(stderr, "stan_solver: --dt, --steps, --newmark, --rayleigh, --load-curve, --probe-node, --solve-eps and --vtu-every belong to --transient\n");
+        return 2;
+    }
+    if (transient) {
+        const char *why = nullptr;
+        if (modes) why = "--transient and --modes are two analyses: one per run";
+        else if (bad_list) why = "--newmark B,G and --rayleigh A,B take two numbers, --load-curve t0,g0,t1,g1,... an even count of them";
+        else if (!(run.dt > 0) || !std::isfinite(run.dt)) why = "--transient needs --dt DT with DT > 0";
+        else if (run.n_steps < 0) why = "--steps N needs N >= 0";
+        else if (!(run.solve_eps >= 0)) why = "--solve-eps E needs E >= 0";
+        else if (vtu_every < 1) why = "--vtu-every K needs K >= 1";
+        else if (!(run.alpha_R >= 0) || !(run.beta_R >= 0)) why = "--rayleigh A,B needs A >= 0 and B >= 0";
+        else if (!(run.beta_N == 0 && run.gamma == 0) &&
+                 (!(run.gamma >= 0.5) || !(run.beta_N >= (run.gamma + 0.5) * (run.gamma + 0.5) / 4)))
+            why = "--newmark B,G needs G >= 1/2 and B >= (G + 1/2)^2 / 4 (unconditional stability)";
+        for (size_t k = 0; !why && k < run.curve_t.size(); k++)
+            if (!std::isfinite(run.curve_t[k]) || !std::isfinite(run.curve_g[k]) || (k > 0 && run.curve_t[k] < run.curve_t[k - 1]))
+                why = "--load-curve needs finite values and times that do not descend";
+        if (!why && devices.size() > 1)
+            why = "--transient works on one device: the lumped mass adds up all elements at a node, and the shifted matrix and its "
+                  "solves run on a single-rank context (drop --gpus/--devices)";
+        if (why) {
+            fprintf(stderr, "stan_solver: %s\n", why);
+            return 2;
+        }
+        run.snap_every = vtu ? vtu_every : 0;
+    }
     SolverOptions opt;
     opt.device = device; opt.devices = devices; opt.precision = precision; opt.placement_tries = placement_tries; opt.merit_stop = merit_stop; opt.profile = json;
     opt.p2p = p2p;
@@ -160,6 +242,14 @@ int main(int argc, char **argv) {
     }
     if (modes && DB.AnalysisLib.Type != "Linear_Statics") {
         fprintf(stderr, "stan_solver: --modes works on a Linear_Statics file\n");
+        return 2;
+    }
+    if (transient && !HasDensity(DB)) {   // the same, for the same reason
+        fprintf(stderr, "stan_solver: --transient needs a \"Density\" boundary condition (material IDs, component 0 = rho): the file has none\n");
+        return 2;
+    }
+    if (transient && DB.AnalysisLib.Type != "Linear_Statics") {
+        fprintf(stderr, "stan_solver: --transient works on a Linear_Statics file\n");
         return 2;
     }
 
@@ -206,14 +296,19 @@ int main(int argc, char **argv) {
             std::vector<double> lambda, phi, rho;
             stan_mass_sums msum{};
             stan_modes_report rep{};
-            Functions.Modes(K, nDOF_reduction, md, modes, modes_tol, &lambda, &phi, &rho, &msum, &rep);
+            Functions.Modes(K, nDOF_reduction, md, modes, modes_tol, &lambda, &phi, &rho, &msum, &rep, modes_shift);
             const double two_pi = 6.283185307179586476925;
+            // (a rigid-body mode of a shifted run has lambda = 0 up to the tolerance, on either side: its frequency is 0)
+            auto hz = [&](double l) { return l > 0 ? std::sqrt(l) / two_pi : 0.0; };
             printf("   Total mass: %.6e   volume: %.6e\n", msum.total_mass, msum.volume);
             printf("   Natural frequencies: (block %d, %d outer steps, %lld CG iterations, %s)\n", rep.block, rep.outer,
                    (long long)rep.cg_iterations, rep.converged ? "converged" : "NOT converged");
+            if (modes_shift > 0)
+                printf("     shift %.8e: the modes of K + shift M, lambda = mu - shift; rho is the convergence measure of the shifted\n"
+                       "     problem, relative to mu\n", modes_shift);
             printf("     mode            lambda    frequency [Hz]           rho\n");
             for (int j = 0; j < modes; j++)
-                printf("     %4d  %16.8e  %16.8e  %12.3e\n", j + 1, lambda[(size_t)j], std::sqrt(lambda[(size_t)j]) / two_pi, rho[(size_t)j]);
+                printf("     %4d  %16.8e  %16.8e  %12.3e\n", j + 1, lambda[(size_t)j], hz(lambda[(size_t)j]), rho[(size_t)j]);
             if (vtu) {
                 const size_t N = (size_t)minfo.n_reduced;
                 std::vector<double> shape((size_t)n_nodes * 3);
@@ -231,10 +326,11 @@ int main(int argc, char **argv) {
                        "\"outer\": %d, \"converged\": %d, \"cg_iterations\": %lld, \"total_mass\": %.17g",
                        DB.nDOF, (long long)minfo.n_reduced, secs(t_wall), modes, rep.block, rep.outer, rep.converged,
                        (long long)rep.cg_iterations, msum.total_mass);
+                if (modes_shift > 0) printf(", \"shift\": %.17g", modes_shift);   // rho: of the shifted problem
                 for (int pass = 0; pass < 3; pass++) {
                     printf(", \"%s\": [", pass == 0 ? "lambda" : pass == 1 ? "frequency_hz" : "rho");
                     for (int j = 0; j < modes; j++)
-                        printf("%s%.17g", j ? ", " : "", pass == 0 ? lambda[(size_t)j] : pass == 1 ? std::sqrt(lambda[(size_t)j]) / two_pi : rho[(size_t)j]);
+                        printf("%s%.17g", j ? ", " : "", pass == 0 ? lambda[(size_t)j] : pass == 1 ? hz(lambda[(size_t)j]) : rho[(size_t)j]);
                     printf("]");
                 }
                 printf("}}\n");
@@ -278,6 +374,89 @@ int main(int argc, char **argv) {
                    (long long)lsum.n_faces, (long long)dl.n_prescribed);
         }
         const std::vector<double> &F_solve = dist_loads ? F_rhs : F;
+
+        if (transient) {   // the time integration instead of the static solve: nothing of it reaches the STdb
+            for (double x : dl.disp0)
+                if (x != 0.0) {
+                    fprintf(stderr, "stan_solver: --transient takes homogeneous supports only: the file prescribes a non-zero "
+                                    "\"Displacement\"\n");
+                    return 2;
+                }
+            // the probe: the free DOFs of one node, by its ID
+            int probe_dir[3] = {0, 0, 0};
+            if (have_probe) {
+                int64_t node = -1;
+                for (int64_t n = 0; n < n_nodes && node < 0; n++)
+                    if (DB.NodeLib.Items()[(size_t)n].first == probe_node) node = n;
+                if (node < 0) {
+                    fprintf(stderr, "stan_solver: --probe-node %d: the file has no such node\n", probe_node);
+                    return 2;
+                }
+                for (int c = 0; c < 3; c++) {
+                    const int32_t d = K.flat.node_dof[(size_t)(3 * node + c)];
+                    if (nDOF_reduction[(size_t)d] == -1) continue;
+                    probe_dir[run.probe_dof.size()] = c;
+                    run.probe_dof.push_back(d - nDOF_reduction[(size_t)d]);
+                }
+            }
+            MassDensity md;
+            if (BuildDensity(DB, K.flat, &md, &err)) return fail("boundary conditions", err);
+            std::vector<double> probe_u, snaps, energy;
+            stan_mass_sums msum{};
+            stan_transient_report rep{};
+            Functions.Transient(K, nDOF_reduction, md, F_solve, run, &probe_u, &snaps, &energy, &msum, &rep);
+            const size_t np = run.probe_dof.size(), N = (size_t)minfo.n_reduced;
+            const double bN = run.beta_N == 0 && run.gamma == 0 ? 0.25 : run.beta_N, gm = run.beta_N == 0 && run.gamma == 0 ? 0.5 : run.gamma;
+            const double mean_its = rep.steps > 0 ? (double)rep.cg_iterations / rep.steps : 0.0;
+            printf("   Total mass: %.6e   volume: %.6e\n", msum.total_mass, msum.volume);
+            printf("   Transient: (%d steps of dt %.6e, Newmark beta %g gamma %g, Rayleigh alpha %g beta %g)\n", rep.steps, run.dt, bN, gm,
+                   run.alpha_R, run.beta_R);
+            printf("     sigma of K + sigma M: %.8e\n", rep.sigma);
+            printf("     CG iterations per step: min %d  mean %.1f  max %d\n", rep.cg_min_iterations, mean_its, rep.cg_max_iterations);
+            if (np) {
+                printf("     Probe node %d:\n       step                 t", probe_node);
+                for (size_t q = 0; q < np; q++) printf("                u%c", "xyz"[probe_dir[q]]);
+                printf("\n");
+                for (int s = 0; s <= run.n_steps; s++) {
+                    printf("     %6d  %16.8e", s, (double)s * run.dt);
+                    for (size_t q = 0; q < np; q++) printf("  %16.8e", probe_u[(size_t)s * np + q]);
+                    printf("\n");
+                }
+            }
+            const double *ef = &energy[(size_t)run.n_steps * 3];
+            printf("     Final energies: kinetic %.8e  strain %.8e  external %.8e\n", ef[0], ef[1], ef[2]);
+            if (vtu) {
+                int last = 0;
+                for (int s = 0; s <= run.n_steps; s += vtu_every) {
+                    Functions.Export_Step_Vtu(K, nDOF_reduction, &snaps[(size_t)(s / vtu_every) * 3 * N], N, vtu_prefix, s);
+                    last = s;
+                }
+                printf("   VTU export: %s_step_0000.vtu ... %s_step_%04d.vtu\n", vtu_prefix.c_str(), vtu_prefix.c_str(), last);
+            }
+            printf("\n%s\n  Total CPU time: %.2f s\n%s\n", separator, secs(t_total), separator);
+            if (json) {   // %.17g: the doubles round-trip
+                printf("{\"n_gpus\": 1, \"n_dof\": %d, \"n_reduced\": %lld, \"t_wall_s\": %.3f, \"transient\": {\"steps\": %d, \"dt\": %.17g, "
+                       "\"beta_N\": %.17g, \"gamma\": %.17g, \"alpha_R\": %.17g, \"beta_R\": %.17g, \"sigma\": %.17g, \"cg_iterations\": %lld, "
+                       "\"cg_min_iterations\": %d, \"cg_max_iterations\": %d, \"cg_worst_type\": %d, \"total_mass\": %.17g, "
+                       "\"energy_final\": [%.17g, %.17g, %.17g]",
+                       DB.nDOF, (long long)minfo.n_reduced, secs(t_wall), rep.steps, run.dt, bN, gm, run.alpha_R, run.beta_R, rep.sigma,
+                       (long long)rep.cg_iterations, rep.cg_min_iterations, rep.cg_max_iterations, rep.cg_worst_type, msum.total_mass,
+                       ef[0], ef[1], ef[2]);
+                if (np) {
+                    printf(", \"probe_node\": %d, \"probe_direction\": [", probe_node);
+                    for (size_t q = 0; q < np; q++) printf("%s%d", q ? ", " : "", probe_dir[q]);
+                    printf("], \"probe_u\": [");
+                    for (int s = 0; s <= run.n_steps; s++) {
+                        printf("%s[", s ? ", " : "");
+                        for (size_t q = 0; q < np; q++) printf("%s%.17g", q ? ", " : "", probe_u[(size_t)s * np + q]);
+                        printf("]");
+                    }
+                    printf("]");
+                }
+                printf("}}\n");
+            }
+            return 0;
+        }
 
         std::vector<double> U((size_t)(DB.nDOF - n_fixed), 0.0);
         const std::string &ls = DB.AnalysisLib.LinSolver;

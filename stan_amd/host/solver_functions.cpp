@@ -233,21 +233,78 @@ void SolverFunctions::Thermal_Stress(SparseMatrixHandle &K, const ThermalLoads &
 
 void SolverFunctions::Modes(SparseMatrixHandle &K, const std::vector<int32_t> &red, const MassDensity &md, int n_modes, double tol,
                             std::vector<double> *lambda, std::vector<double> *phi, std::vector<double> *rho, stan_mass_sums *sums,
-                            stan_modes_report *rep) const {
+                            stan_modes_report *rep, double shift) const {
+    std::vector<double> M;
+    LumpedMass(K, red, md, &M, sums);
+    const size_t N = M.size();
+    const size_t k = n_modes > 0 ? (size_t)n_modes : 1;
+    lambda->assign(k, 0.0); rho->assign(k, 0.0); phi->assign(k * N, 0.0);
+    stan_matrix *A = K.K, *shifted = nullptr;
+    if (shift > 0) {
+        if (stan_hip_matrix_shifted(K.ctx, K.K, shift, M.data(), &shifted)) throw std::runtime_error(stan_hip_last_error(K.ctx));
+        A = shifted;
+    }
+    const int rc = stan_hip_modes(K.ctx, A, M.data(), n_modes, tol, 0, 0.0, 0, lambda->data(), phi->data(), rho->data(), rep);
+    if (shifted) stan_hip_matrix_free(shifted);
+    if (rc) throw std::runtime_error(stan_hip_last_error(K.ctx));
+    if (shift > 0)
+        for (double &l : *lambda) l -= shift;
+}
+
+void SolverFunctions::LumpedMass(SparseMatrixHandle &K, const std::vector<int32_t> &red, const MassDensity &md, std::vector<double> *M,
+                                 stan_mass_sums *sums) const {
     const FlatModel &f = K.flat;
     const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
     size_t n_fixed = 0;
     for (int32_t r : red) n_fixed += r == -1;
     const size_t N = red.size() - n_fixed;
-    std::vector<double> M(N > 0 ? N : 1, 0.0);
+    M->assign(N > 0 ? N : 1, 0.0);
     if (stan_hip_lumped_mass_hex8(K.ctx, n_nodes, f.xyz.data(), f.node_dof.data(), n_elem, f.conn.data(), f.elem_mat.data(),
                                   f.elem_type.data(), (int32_t)(f.mat_E_nu.size() / 2), f.mat_E_nu.data(), (int64_t)red.size(),
-                                  red.data(), md.mat_rho.data(), M.data(), nullptr, sums))
+                                  red.data(), md.mat_rho.data(), M->data(), nullptr, sums))
         throw std::runtime_error(stan_hip_last_error(K.ctx));
-    const size_t k = n_modes > 0 ? (size_t)n_modes : 1;
-    lambda->assign(k, 0.0); rho->assign(k, 0.0); phi->assign(k * (N > 0 ? N : 1), 0.0);
-    if (stan_hip_modes(K.ctx, K.K, M.data(), n_modes, tol, 0, 0.0, 0, lambda->data(), phi->data(), rho->data(), rep))
+}
+
+void SolverFunctions::Transient(SparseMatrixHandle &K, const std::vector<int32_t> &red, const MassDensity &md, const std::vector<double> &F,
+                                const TransientRun &run, std::vector<double> *probe_u, std::vector<double> *snaps,
+                                std::vector<double> *energy, stan_mass_sums *sums, stan_transient_report *rep) const {
+    std::vector<double> M;
+    LumpedMass(K, red, md, &M, sums);
+    const size_t N = M.size(), rows = (size_t)run.n_steps + 1, np = run.probe_dof.size();
+    const size_t n_snap = run.snap_every > 0 ? (size_t)(run.n_steps / run.snap_every) + 1 : 0;
+    probe_u->assign(rows * np, 0.0);
+    snaps->assign(n_snap * 3 * N, 0.0);
+    energy->assign(rows * 3, 0.0);
+    std::vector<double> u(N), v(N), a(N);
+    if (stan_hip_transient(K.ctx, K.K, M.data(), F.data(), nullptr, nullptr, run.dt, run.n_steps, run.beta_N, run.gamma, run.alpha_R,
+                           run.beta_R, (int32_t)run.curve_t.size(), run.curve_t.data(), run.curve_g.data(), run.solve_eps, 0, (int32_t)np,
+                           np ? run.probe_dof.data() : nullptr, np ? probe_u->data() : nullptr, run.snap_every,
+                           n_snap ? snaps->data() : nullptr, energy->data(), u.data(), v.data(), a.data(), rep))
         throw std::runtime_error(stan_hip_last_error(K.ctx));
+}
+
+void SolverFunctions::Export_Step_Vtu(SparseMatrixHandle &K, const std::vector<int32_t> &red, const double *uva, size_t N,
+                                      const std::string &prefix, int step) const {
+    const FlatModel &f = K.flat;
+    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
+    static const char *const names[9] = {"Displacement X", "Displacement Y", "Displacement Z", "Velocity X", "Velocity Y", "Velocity Z",
+                                         "Acceleration X", "Acceleration Y", "Acceleration Z"};
+    std::vector<double> point(9 * (size_t)n_nodes), disp(3 * (size_t)n_nodes);
+    for (int q = 0; q < 3; q++) {
+        const std::vector<double> full = Include_BC_DOF(std::vector<double>(uva + (size_t)q * N, uva + (size_t)(q + 1) * N), red);
+        for (int64_t n = 0; n < n_nodes; n++)
+            for (int c = 0; c < 3; c++) {
+                const double x = full[(size_t)f.node_dof[(size_t)(3 * n + c)]];
+                point[(size_t)(3 * q + c) * (size_t)n_nodes + (size_t)n] = x;
+                if (q == 0) disp[(size_t)(3 * n + c)] = x;
+            }
+    }
+    char num[16];
+    snprintf(num, sizeof num, "%04d", step);
+    const std::string path = prefix + "_step_" + num + ".vtu";
+    if (stan_host_write_vtu(path.c_str(), n_nodes, f.xyz.data(), disp.data(), n_elem, f.conn.data(), 9, names, point.data(), 0, nullptr,
+                            nullptr))
+        throw std::runtime_error("cannot write " + path);
 }
 
 void SolverFunctions::Export_Mode_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &prefix, int mode) const {

@@ -107,9 +107,31 @@ class SolverFunctions {
     // Modal analysis (stan_hip_lumped_mass_hex8 + stan_hip_modes; no step of the reference): the lumped mass of `md` and the
     // n_modes lowest eigenpairs of K phi = lambda M phi; lambda / rho [n_modes], phi [n_modes][N] on the free DOFs; *sums and
     // *rep always filled.  One device only.
+    // the row-sum lumped mass of `md` on the free DOFs, M [N] (stan_hip_lumped_mass_hex8); *sums always filled
+    void LumpedMass(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const MassDensity &md, std::vector<double> *M,
+                    stan_mass_sums *sums) const;
+    // shift > 0 (a free-free model): stan_hip_modes runs on K + shift M (stan_hip_matrix_shifted) and lambda = mu - shift; rho
+    // and the report are the shifted problem's.
     void Modes(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const MassDensity &md, int n_modes, double tol,
                std::vector<double> *lambda, std::vector<double> *phi, std::vector<double> *rho, stan_mass_sums *sums,
-               stan_modes_report *rep) const;
+               stan_modes_report *rep, double shift = 0.0) const;
+    // Transient dynamics (stan_hip_lumped_mass_hex8 + stan_hip_transient; no step of the reference):
+    // implicit Newmark steps of M a + C v + K u = g(t) F from rest, F the reduced external load.  probe_dof: reduced DOFs;
+    // probe_u [(n_steps + 1)][n_probe]; snaps [n_snap][3][N] when snap_every > 0; energy [(n_steps + 1)][3]; *sums and *rep
+    // always filled.  One device only.
+    struct TransientRun {
+        double dt = 0, beta_N = 0, gamma = 0, alpha_R = 0, beta_R = 0, solve_eps = 0;
+        int n_steps = 0, snap_every = 0;
+        std::vector<double> curve_t, curve_g;
+        std::vector<int32_t> probe_dof;
+    };
+    void Transient(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const MassDensity &md, const std::vector<double> &F,
+                   const TransientRun &run, std::vector<double> *probe_u, std::vector<double> *snaps, std::vector<double> *energy,
+                   stan_mass_sums *sums, stan_transient_report *rep) const;
+    // <prefix>_step_NNNN.vtu for one snapshot: u, v, a [N] on the free DOFs as the point arrays "Displacement X" / "Y" / "Z",
+    // "Velocity ..." and "Acceleration ...", through the writer of vtu.cpp
+    void Export_Step_Vtu(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const double *uva, size_t N,
+                         const std::string &prefix, int step) const;
     // <prefix>_mode_NNN.vtu (NNN = 001 ...) for one mode: shape [n_nodes*3] in NodeLib order as the point arrays "Mode Shape X" /
     // "Y" / "Z" and "Magnitude", through the writer of vtu.cpp (the shape also takes the place of the displacements)
     void Export_Mode_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &prefix, int mode) const;
