@@ -769,6 +769,106 @@ int stan_hip_block_rotate(stan_ctx *ctx, int64_t N, int32_t q, const double *Z, 
                           const double *Q, const double *lambda, const uint8_t *mask, int32_t in_place, double *X,
                           double *KX, double *rhs, double *rho2);
 
+/* ---- linear buckling: the geometric stiffness K_g(U) and critical load factors ------------------ */
+/* No step of the reference.  The element scalars of the geometric (initial-stress) stiffness of n
+ * elements (introspection, as stan_hip_ke_hex8_batch is): with the nodal displacements u8 [n*24] of an element, (E, nu) and the
+ * integration rule of its type (the points and weights of K_e),
+ *   eps_g = B_g u_e,  sigma_g = D eps_g,  s[a][b] = sum_g w_g det J_g (grad N_a)^T Sigma_g grad N_b
+ * Sigma_g the symmetric 3x3 tensor of sigma_g; the element matrix is s (x) I_3.  s36 [n*36]: per element the upper triangle of
+ * the symmetric 8 x 8 s, row-major ((a, b), a <= b, at a*8 - a(a-1)/2 + b - a).  xyz8 [n*24], type [n], host pointers.  The
+ * values are those of the element pass of stan_hip_geometric_stiffness_hex8 (the same kernel).
+ * STAN_E_UNSUPPORTED: a type that is neither HEX8_G1 nor HEX8_G2.  STAN_E_DETJ (element via stan_hip_last_bad_element) when
+ * det J == 0 at a point of an element. */
+int stan_hip_kg_hex8_batch(stan_ctx *ctx, int64_t n, const double *xyz8, const double *u8, double E, double nu,
+                           const uint8_t *type, double *s36);
+/* *out becomes a NEW matrix of this context that holds G = K_g(disp), the geometric stiffness of the stress state of the
+ * displacement field disp [n_nodes][3] (NodeLib order, as stan_hip_internal_forces_hex8 takes it; no thermal part): the mesh
+ * arrays are those K was assembled from.  It has K's layout (its structure arrays are copied) and a value array of its own,
+ * placed as an assembled matrix's is; it is unscaled and carries no derived stream, whatever K's state: stan_hip_spmv,
+ * stan_hip_matrix_to_csr, stan_hip_matrix_info and stan_hip_buckling take it and treat it as they treat an assembled K.  It is
+ * freed with stan_hip_matrix_free and does not depend on K's lifetime.
+ *   values  the block of row node r and column node c holds, on its three diagonal components, the sum of s_e[a][b] over the
+ *           (element e, local node a) incidences of r in ascending element order (then a) and, inside one, over b = 0..7 with
+ *           conn[e][b] = c -- s_e as stan_hip_kg_hex8_batch gives it; the six off-diagonal components are 0.  A fixed DOF is
+ *           stored as the assembly stores it: a zero row and column, 1 on the diagonal.  G is indefinite in general.
+ * Every value is written once, by one lane, in a fixed order, with no atomics on doubles: two calls give the same bits, and so
+ * do the host and the _dev entry.  K itself is read only -- its values are not read at all: its values, its scaled flag and
+ * its streams are unchanged to the bit.
+ * STAN_E_ARG: as stan_hip_internal_forces_hex8 for the arguments and the mesh; a K of another context; a mesh whose node, DOF
+ * or fixed-DOF count is not K's, or one that couples two nodes K's pattern does not.  STAN_E_DOF_LAYOUT and STAN_E_DETJ as
+ * there.  STAN_E_UNSUPPORTED: a multi-device handle, a context with a communicator.  On an error *out is not written and what
+ * the call had allocated is given back. */
+int stan_hip_geometric_stiffness_hex8(stan_ctx *ctx, stan_matrix *K, int64_t n_nodes, const double *xyz, const double *disp,
+                                      const int32_t *node_dof, int64_t n_elem, const int32_t *conn, const int32_t *elem_mat,
+                                      const uint8_t *elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
+                                      const int32_t *ndof_reduction, stan_matrix **out);
+/* The same with every array except mat_E_nu in device memory on the context's GPU: read only, ready on the context's stream,
+ * naturally aligned; complete on return. */
+int stan_hip_geometric_stiffness_hex8_dev(stan_ctx *ctx, stan_matrix *K, int64_t n_nodes, const double *d_xyz,
+                                          const double *d_disp, const int32_t *d_node_dof, int64_t n_elem, const int32_t *d_conn,
+                                          const int32_t *d_elem_mat, const uint8_t *d_elem_type, int32_t n_mat,
+                                          const double *mat_E_nu, int64_t n_dof, const int32_t *d_ndof_reduction,
+                                          stan_matrix **out);
+/* Phase times of the most recent geometric-stiffness call on this context, by HIP events (profiling must be enabled first), as
+ * stan_hip_load_vector_times gives them: ms[0] the element pass, ms[1] the copy of K's layout with the allocation of the value
+ * array, ms[2] the node -> (element, corner) lists and the row maps, ms[3] the row gather. */
+int stan_hip_geometric_stiffness_times(stan_ctx *ctx, double ms[4]);
+
+/* The n_modes lowest positive load factors lambda of (K + lambda G) phi = 0 on the free DOFs: K a matrix of this context (a
+ * supported model: K positive definite), G = K_g(U) of a static solution U on K's layout (stan_hip_geometric_stiffness_hex8).
+ * With H = -G the call finds the n_modes largest positive mu of H x = mu K x (K^-1 H is self-adjoint in the K-inner product)
+ * by block inverse iteration in correction form with a Rayleigh-Ritz step per outer step:
+ *   block   q = min(N, min(2 n_modes, n_modes + 8)) columns, at most 32; column j >= 0 of X0 is the fixed integer hash of
+ *           (row, j) in [-0.5, 0.5) that stan_hip_modes uses for its columns j > 0: no random state;
+ *   first   Y = H X0 by q products on G (the negation is exact), K Z = Y by stan_hip_cg_solve_multi_dev's loop;
+ *   step    W = K Z, Y = H Z (true products); A = Z^T W, B = Z^T Y (a term is one fused multiply-add; per-workgroup sums in a
+ *           fixed order, added in workgroup order); on the host A <- (A + A^T)/2, B <- (B + B^T)/2 and B Q = A Q diag(mu)
+ *           through the Cholesky factor of A and cyclic Jacobi, mu descending (stably); X = Z Q, KX = W Q,
+ *           R_j = sum_l (mu_j W_l - Y_l) Q_lj = mu_j KX_j - HX_j, rho_j = ||R_j||_{D^-1} / (|mu_j| ||KX_j||_{D^-1}), D = diag K;
+ *           stop when mu_j > 0 and rho_j <= tol for every j < n_modes or after max_outer steps; else K D_j = -R_j for the
+ *           columns with rho_j > tol only and Z_j = mu_j X_j + D_j for every column (defined for every sign of mu_j).
+ *   tol = 0 selects 1e-6, max_outer = 0 selects 100, solve_eps = solve_max_its = 0 selects 1e-6 (lincgsetcond).  The solves run
+ *   with the merit stop off, as under STAN_OPT_CG_MERIT_STOP 0; the caller's setting comes back afterwards.
+ * Outputs: factor [n_modes] = 1 / mu_j, ascending; phi [n_modes][N], each scaled so that its entry of largest magnitude is
+ * exactly +1 (the lowest index on a tie); rho [n_modes] as computed on the final vectors.  rep: a stan_buckling_report or NULL
+ * (void * as for stan_hip_modes); behind the argument checks it is written on every way out.  When the final block holds
+ * n_positive < n_modes positive mu the call returns STAN_OK with converged = 0: the first n_positive outputs are filled, the
+ * rest are zeros.  STAN_OK with converged = 0 also when max_outer runs out.
+ * K is left as any solve leaves it; G is unchanged to the bit.  Two calls give the same bits, and so do the host and the _dev
+ * entry; _dev stores all of d_factor, d_phi, d_rho and nothing beside them.
+ * STAN_E_ARG: as stan_hip_modes; a G of another context or one whose layout is not K's.  STAN_E_UNSUPPORTED: a multi-device
+ * handle, a context with a communicator; a CG column that ends with type -5 or -4 (a K that is not positive definite: a model
+ * without supports), the type in the report and in stan_hip_last_error; a block that loses rank. */
+typedef struct stan_buckling_report {
+    int32_t block;            /* q                                                                             */
+    int32_t outer;            /* outer steps made (Rayleigh-Ritz steps)                                        */
+    int32_t converged;        /* 1: mu_j > 0 and rho_j <= tol for every returned mode                          */
+    int32_t n_positive;       /* the mu > 0 in the final block                                                 */
+    int32_t cg_worst_type;    /* the worst termination type a CG column met: negative < 5 < 7 < 1             */
+    int32_t reserved;
+    int64_t cg_iterations;    /* summed over every column of every solve                                       */
+    double lowest_negative_factor; /* 1 / mu of the most negative mu in the final block, 0: none -- the factor under the
+                                      reversed load                                                            */
+    double max_rho;           /* over the first n_modes columns                                                */
+    double solve_ms;          /* stream time in the solves, the products on K and G and the block kernels, by  */
+    double product_ms;        /*   events when profiling is on, else zeros                                     */
+    double block_ms;
+    double gram_ms;           /* of block_ms: the gram passes with their finishing sums,                      */
+    double rotate_ms;         /*   the rotate + residual passes with theirs                                   */
+} stan_buckling_report;
+int stan_hip_buckling(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, int32_t n_modes, double tol, int32_t max_outer,
+                      double solve_eps, int32_t solve_max_its, double *factor, double *phi, double *rho, void *rep);
+int stan_hip_buckling_dev(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, int32_t n_modes, double tol, int32_t max_outer,
+                          double solve_eps, int32_t solve_max_its, double *d_factor, double *d_phi, double *d_rho, void *rep);
+/* The two new block kernels of stan_hip_buckling on host arrays (introspection, as stan_hip_block_rotate is); Z, W, Y [q][N],
+ * D [N] positive, Q [q*q] row-major, mu [q], q <= 32:
+ *   X = Z Q in one launch; KX = W Q and R_j = sum_l (mu_j W_l - Y_l) Q_lj in another, a lane per row, every term one fused
+ *   multiply-add; r2 [q] = sum_i R_ij^2 / D_i and kx2 [q] = sum_i KX_ij^2 / D_i: per-workgroup partial sums in a fixed order,
+ *   added in workgroup order. */
+int stan_hip_buckling_rotate(stan_ctx *ctx, int64_t N, int32_t q, const double *Z, const double *W, const double *Y,
+                             const double *D, const double *Q, const double *mu, double *X, double *KX, double *R, double *r2,
+                             double *kx2);
+
 /* ---- transient dynamics: the shifted matrix K + sigma M and implicit Newmark steps ------------- */
 /* No step of the reference.  *out becomes a NEW matrix of this context that holds K + sigma diag(M)
  * on the free DOFs: M [N] the diagonal mass in the reduced numbering (stan_hip_lumped_mass_hex8), sigma >= 0.  It has K's

@@ -308,6 +308,27 @@ namespace STAN_Solver
             IntPtr ctx, long N, int q, double[] Z, double[] W, double[] M, double[] Q, double[] lambda, byte[] mask, int in_place,
             [Out] double[] X, [Out] double[] KX, double[] rhs, [Out] double[] rho2);
 
+        // ---- linear buckling: G = K_g(disp) on K's layout (freed with stan_hip_matrix_free), then the lowest positive load
+        //      factors; factor / rho [n_modes], phi [n_modes * N]; rep -> a stan_buckling_report or IntPtr.Zero; s36 [n * 36]
+        [DllImport(Lib)] internal static extern int stan_hip_kg_hex8_batch(
+            IntPtr ctx, long n, double[] xyz8, double[] u8, double E, double nu, byte[] type, [Out] double[] s36);
+        [DllImport(Lib)] internal static extern int stan_hip_geometric_stiffness_hex8(
+            IntPtr ctx, IntPtr K, long n_nodes, double[] xyz, double[] disp, int[] node_dof, long n_elem, int[] conn, int[] elem_mat,
+            byte[] elem_type, int n_mat, double[] mat_E_nu, long n_dof, int[] ndof_reduction, out IntPtr G);
+        [DllImport(Lib)] internal static extern int stan_hip_geometric_stiffness_hex8_dev(
+            IntPtr ctx, IntPtr K, long n_nodes, IntPtr d_xyz, IntPtr d_disp, IntPtr d_node_dof, long n_elem, IntPtr d_conn,
+            IntPtr d_elem_mat, IntPtr d_elem_type, int n_mat, double[] mat_E_nu, long n_dof, IntPtr d_ndof_reduction, out IntPtr G);
+        [DllImport(Lib)] internal static extern int stan_hip_geometric_stiffness_times(IntPtr ctx, [Out] double[] ms);
+        [DllImport(Lib)] internal static extern int stan_hip_buckling(
+            IntPtr ctx, IntPtr K, IntPtr G, int n_modes, double tol, int max_outer, double solve_eps, int solve_max_its,
+            [Out] double[] factor, [Out] double[] phi, [Out] double[] rho, IntPtr rep);
+        [DllImport(Lib)] internal static extern int stan_hip_buckling_dev(
+            IntPtr ctx, IntPtr K, IntPtr G, int n_modes, double tol, int max_outer, double solve_eps, int solve_max_its,
+            IntPtr d_factor, IntPtr d_phi, IntPtr d_rho, IntPtr rep);
+        [DllImport(Lib)] internal static extern int stan_hip_buckling_rotate(
+            IntPtr ctx, long N, int q, double[] Z, double[] W, double[] Y, double[] D, double[] Q, double[] mu,
+            [Out] double[] X, [Out] double[] KX, [Out] double[] R, [Out] double[] r2, [Out] double[] kx2);
+
         // ---- transient dynamics: M, F, u0, v0 (or null) [N]; curve_t / curve_g [n_curve] or null; probe_dof [n_probe], probe_u
         //      [(n_steps + 1) * n_probe], snaps [n_snap * 3 * N], energy [(n_steps + 1) * 3] or null; rep -> StanTransientReport or
         //      IntPtr.Zero.  The step helpers take coef [8]; u, v, a of correct are pinned and updated in place

@@ -1,17 +1,16 @@
 // api_modal.hip -- the extern "C" surface, part 5 of 5: the modal analysis.  The driver loop of stan_hip_modes (block inverse iteration in
 // correction form with a Rayleigh-Ritz step) over the solver's batched CG (stan_cg_multi_device), its
 // products (stan_spmv_reduced) and the block kernels of modal.hip; the q x q eigenproblem on the host; the two block helpers.
-// One device, one rank (modal_refused).
+// One device, one rank (block_driver_refused, api_stage.h).
 #include <algorithm>
 #include <cmath>
 
 #include "api_stage.h"
 
-namespace {
-
 // A Q = B Q Lambda for symmetric A and symmetric positive definite B, q x q row-major: B = L L^T, C = L^-1 A L^-T, cyclic
-// Jacobi on C (C = V Theta V^T), Lambda = Theta ascending, Q = L^-T V: Q^T B Q = I.  false: B is not positive definite.
-bool small_gen_eig(int q, const double *A, const double *B, double *lambda, double *Q) {
+// Jacobi on C (C = V Theta V^T), Lambda = Theta ascending (descending: descending; stably either way), Q = L^-T V: Q^T B Q = I.
+// false: B is not positive definite.  Shared with the buckling driver (api_stage.h).
+bool stan_small_gen_eig(int q, const double *A, const double *B, double *lambda, double *Q, bool descending) {
     std::vector<double> L((size_t)q * q, 0.0), Cm((size_t)q * q), V((size_t)q * q, 0.0), T((size_t)q * q);
     auto at = [q](std::vector<double> &m, int i, int j) -> double & { return m[(size_t)i * q + j]; };
     for (int j = 0; j < q; j++) {
@@ -75,7 +74,7 @@ bool small_gen_eig(int q, const double *A, const double *B, double *lambda, doub
     }
     std::vector<int> order((size_t)q);
     for (int i = 0; i < q; i++) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return at(Cm, x, x) < at(Cm, y, y); });
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return descending ? at(Cm, x, x) > at(Cm, y, y) : at(Cm, x, x) < at(Cm, y, y); });
     for (int j = 0; j < q; j++) {
         const int src = order[(size_t)j];
         lambda[j] = at(Cm, src, src);
@@ -88,15 +87,7 @@ bool small_gen_eig(int q, const double *A, const double *B, double *lambda, doub
     return true;
 }
 
-// One device, one rank: the solves are the batched CG's (a single-rank context), the block kernels and their sums run on it
-int modal_refused(stan_ctx *ctx, const char *entry) {
-    STAN_NO_GROUP(ctx, std::string(entry) + " (the block solves and the block kernels run on one device)");
-    if (stan_sharded(ctx)) {
-        ctx->err = std::string(entry) + ": not available on a context with a communicator (the block sums are not reduced over ranks)";
-        return STAN_E_UNSUPPORTED;
-    }
-    return STAN_OK;
-}
+namespace {
 
 // the driver on device arrays: d_M [N], d_lambda / d_rho [k], d_phi [k][N]
 int modes_device(stan_ctx *ctx, stan_matrix *K, const double *d_M, int32_t k, double tol, int32_t max_outer, double solve_eps,
@@ -164,7 +155,7 @@ int modes_device(stan_ctx *ctx, stan_matrix *K, const double *d_M, int32_t k, do
         pt.begin();
         STANCHK(stan_modal_gram_device(ctx, N, q, Z, W, d_M, A.data(), B.data()));
         pt.end(&R.gram_ms);
-        if (!small_gen_eig(q, A.data(), B.data(), lam.data(), Qm.data()))
+        if (!stan_small_gen_eig(q, A.data(), B.data(), lam.data(), Qm.data()))
             return bad("the block lost rank (Z^T M Z is not positive definite: " + free_hint + ")", STAN_E_UNSUPPORTED);
         for (int j = 0; j < q; j++)
             if (!(lam[(size_t)j] > 0.0))
@@ -210,7 +201,7 @@ int modes_device(stan_ctx *ctx, stan_matrix *K, const double *d_M, int32_t k, do
 
 int modes_args(stan_ctx *ctx, stan_matrix *K, const void *M, const void *lambda, const void *phi, const void *rho) {
     if (!ctx) return STAN_E_ARG;
-    STANCHK(modal_refused(ctx, "modes"));
+    STANCHK(block_driver_refused(ctx, "modes"));
     if (!K || !M || !lambda || !phi || !rho) { ctx->err = "modes: null argument"; return STAN_E_ARG; }
     if (K->ctx != ctx) { ctx->err = "modes: K belongs to another context"; return STAN_E_ARG; }
     return STAN_OK;
@@ -245,7 +236,7 @@ int stan_hip_modes(stan_ctx *ctx, stan_matrix *K, const double *M, int32_t n_mod
 
 int stan_hip_block_gram(stan_ctx *ctx, int64_t N, int32_t q, const double *Z, const double *W, const double *M, double *A, double *B) {
     if (!ctx) return STAN_E_ARG;
-    STANCHK(modal_refused(ctx, "block_gram"));
+    STANCHK(block_driver_refused(ctx, "block_gram"));
     if (!Z || !W || !M || !A || !B || N <= 0 || q <= 0 || q > STAN_MODAL_QMAX) { ctx->err = "block_gram: null argument, N <= 0 or q outside [1, 32]"; return STAN_E_ARG; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     host_stage st(ctx);
@@ -260,7 +251,7 @@ int stan_hip_block_rotate(stan_ctx *ctx, int64_t N, int32_t q, const double *Z, 
                           const double *lambda, const uint8_t *mask, int32_t in_place, double *X, double *KX, double *rhs,
                           double *rho2) {
     if (!ctx) return STAN_E_ARG;
-    STANCHK(modal_refused(ctx, "block_rotate"));
+    STANCHK(block_driver_refused(ctx, "block_rotate"));
     if (!Z || !W || !M || !Q || !lambda || !X || !KX || !rhs || !rho2 || N <= 0 || q <= 0 || q > STAN_MODAL_QMAX) {
         ctx->err = "block_rotate: null argument, N <= 0 or q outside [1, 32]";
         return STAN_E_ARG;

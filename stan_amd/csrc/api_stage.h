@@ -134,6 +134,20 @@ struct piece_timer {
     }
 };
 
+// the q x q eigenproblem of the block drivers, on the host (api_modal.hip): A Q = B Q Lambda, B = L L^T, cyclic Jacobi
+bool stan_small_gen_eig(int q, const double *A, const double *B, double *lambda, double *Q, bool descending = false);
+
+// One device, one rank (the modal and the buckling driver and their block helpers): the solves are the batched CG's (a
+// single-rank context), the block kernels and their sums run on it
+inline int block_driver_refused(stan_ctx *ctx, const char *entry) {
+    STAN_NO_GROUP(ctx, std::string(entry) + " (the block solves and the block kernels run on one device)");
+    if (stan_sharded(ctx)) {
+        ctx->err = std::string(entry) + ": not available on a context with a communicator (the block sums are not reduced over ranks)";
+        return STAN_E_UNSUPPORTED;
+    }
+    return STAN_OK;
+}
+
 inline int worse_type(int a, int b) {   // negative < 5 < 7 < 1
     auto rank = [](int t) { return t < 0 ? 0 : t == 5 ? 1 : t == 7 ? 2 : 3; };
     if (a == 0) return b;

@@ -267,6 +267,7 @@ struct stan_ctx {
     stan_profile prof{};
     double prof_loads_ms[3] = {0, 0, 0};   // last load-vector call: element pass | lists | gather (stan_hip_load_vector_times)
     double prof_thermal_ms[3] = {0, 0, 0}; // last thermal-load call, the same phases (stan_hip_thermal_load_times)
+    double prof_kg_ms[4] = {0, 0, 0, 0};   // last geometric-stiffness call: element pass | layout copy | lists and maps | gather (stan_hip_geometric_stiffness_times)
     stan_pool pool;
     stan_cg_ws ws;
     std::vector<stan_matrix *> matrices;  // alive matrices of this context (detached when it is destroyed)
@@ -521,6 +522,24 @@ int stan_modal_axpy_device(stan_ctx *ctx, int64_t N, int32_t q, const double *d_
 // d_phi [k][N] = the first k columns of X, each scaled to M-norm 1 with its entry of largest magnitude positive.  Synchronises.
 int stan_modal_normalise_device(stan_ctx *ctx, int64_t N, int32_t k, const double *d_X, const double *d_M, double *d_phi);
 
+// The block kernels of the buckling driver (api_buckling.hip); block vectors as above.
+// d_X0 [q][N]: column j >= 0 = the hash of (row, j) of stan_modal_start_device's columns j > 0.  Enqueues only.
+int stan_buckling_start_device(stan_ctx *ctx, int64_t N, int32_t q, double *d_X0);
+// y = -y, n entries (exact).  Enqueues only.
+int stan_buckling_negate_device(stan_ctx *ctx, int64_t n, double *d_y);
+// X = Z Q in one launch; KX = W Q, R_j = sum_l (mu_j W_l - Y_l) Q_lj, d_rhs column j = -R_j where bit j of mask is clear,
+// r2 [q] = sum R^2 / D and kx2 [q] = sum KX^2 / D (host) in another.  Q [q*q] row-major and mu [q] are host arrays.  d_X / d_KX
+// may be d_Z / d_W.  Synchronises.
+int stan_buckling_rotate_device(stan_ctx *ctx, int64_t N, int32_t q, const double *d_Z, const double *d_W, const double *d_Y,
+                                const double *d_D, const double *Q, const double *mu, uint32_t mask, double *d_X, double *d_KX,
+                                double *d_rhs, double *r2, double *kx2);
+// Z_j = fma(mu_j, X_j, D_dcol[j]) (dcol[j] < 0: mu_j X_j).  d_Z may be d_X.  Enqueues only.
+int stan_buckling_axpy_device(stan_ctx *ctx, int64_t N, int32_t q, const double *d_X, const double *mu, const int32_t *dcol,
+                              const double *d_D, double *d_Z);
+// d_phi [k][N] = the first k columns of X, each divided by its entry of largest magnitude (the lowest index on a tie): that
+// entry becomes exactly +1.  Synchronises.
+int stan_buckling_normalise_device(stan_ctx *ctx, int64_t N, int32_t k, const double *d_X, double *d_phi);
+
 // ---- matrix_shift.hip -----------------------------------------------------------------------
 // The value stan_hip_matrix_to_csr exports for an entry a of a matrix that carries S K S, s_row and s_col its two scaling
 // factors: the export and the shift pass share this one expression.
@@ -531,6 +550,25 @@ int stan_mass_check_device(stan_ctx *ctx, int64_t N, const double *d_M, int64_t 
 // arrays copied, its own value array by stan_matrix_alloc_stream, unscaled, nothing derived.  K is read only.  sigma and d_M
 // checked by the caller; shift_ms (may be null) gets the stream time of the value pass when profiling is on.  Synchronises.
 int stan_matrix_shifted_device(stan_ctx *ctx, stan_matrix *K, double sigma, const double *d_M, stan_matrix **out, double *shift_ms = nullptr);
+// What the builders of a second matrix on K's layout share (the shifted matrix, the geometric stiffness): *out = a new matrix of
+// the context with copies of K's structure arrays (enqueued on the context's stream), its own value array by
+// stan_matrix_alloc_stream -- not yet filled -- unscaled, nothing derived.  A failure gives back what it had allocated.
+int stan_matrix_clone_layout(stan_ctx *ctx, const stan_matrix *K, stan_matrix **out);
+struct stan_matrix_guard {   // frees a matrix under construction unless the call gets to ok = true
+    stan_matrix *k; bool ok = false;
+    ~stan_matrix_guard() { if (!ok) stan_hip_matrix_free(k); }
+};
+
+// ---- geometric.hip --------------------------------------------------------------------------
+// d_s36 [n][36] = the upper triangle of the element scalars s_e of the geometric stiffness (stan_hip_kg_hex8_batch), by the
+// element pass of stan_geometric_stiffness_device itself; d_xyz8, d_u8 [n][24]; d_type checked by the caller.  Synchronises.
+int stan_kg_batch_device(stan_ctx *ctx, int64_t n, const double *d_xyz8, const double *d_u8, double E, double nu,
+                         const uint8_t *d_type, double *d_s36);
+// *out = a new matrix of the context holding K_g(disp) in K's layout (stan_hip_geometric_stiffness_hex8_dev): K's structure
+// arrays copied, its own value array by stan_matrix_alloc_stream, unscaled, nothing derived.  d: device view with every
+// array, checked on the device before anything is indexed with it.  K is read only (its values are not read at all).
+// Synchronises.
+int stan_geometric_stiffness_device(stan_ctx *ctx, stan_matrix *K, const stan_mesh &d, stan_matrix **out);
 
 // ---- transient.hip --------------------------------------------------------------------------
 // The Newmark step kernels of the transient driver (api_transient.hip).  Every vector is [N] in

@@ -78,29 +78,11 @@ int clone_array(stan_ctx *ctx, T **dst, const T *src, size_t n) {
 
 }  // namespace
 
-int stan_mass_check_device(stan_ctx *ctx, int64_t N, const double *d_M, int64_t *bad) {
-    hipStream_t st = ctx->stream;
-    const long long none = 0x7fffffffffffffffLL;
-    *bad = -1;
-    if (N <= 0) return STAN_OK;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_status + SS_AUX, &none, 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_mass_check, dim3(nblk(N, 256)), dim3(256), 0, st, N, d_M, (long long *)(ctx->d_status + SS_AUX));
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, ctx->d_status + SS_AUX, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (ctx->h_status[SS_AUX] != none) *bad = ctx->h_status[SS_AUX];
-    return STAN_OK;
-}
-
-int stan_matrix_shifted_device(stan_ctx *ctx, stan_matrix *K, double sigma, const double *d_M, stan_matrix **out, double *shift_ms) {
-    hipStream_t st = ctx->stream;
+int stan_matrix_clone_layout(stan_ctx *ctx, const stan_matrix *K, stan_matrix **out) {
     stan_matrix *S = new stan_matrix();
     S->ctx = ctx;
     ctx->matrices.push_back(S);
-    struct guard {   // a failed call gives back what it had allocated
-        stan_matrix *k; bool ok = false;
-        ~guard() { if (!ok) stan_hip_matrix_free(k); }
-    } g{S};
+    stan_matrix_guard g{S};
     S->n_dof = K->n_dof; S->n_red = K->n_red; S->nb_glob = K->nb_glob;
     S->r0 = K->r0; S->r1 = K->r1; S->u0 = K->u0; S->u1 = K->u1;
     S->nloc = K->nloc; S->nhalo = K->nhalo; S->nslices = K->nslices; S->nslots = K->nslots; S->nblocks = K->nblocks;
@@ -117,6 +99,30 @@ int stan_matrix_shifted_device(stan_ctx *ctx, stan_matrix *K, double sigma, cons
     // (behind the columns: the allocation by trial times the product itself -- as in the assembly; the packed column stream
     // is a function of the columns alone and is built by the first product that wants it, as K's was)
     STANCHK(stan_matrix_alloc_stream(ctx, S, STAN_PREC_FP64, S->nslots, &S->vs[STAN_PREC_FP64].padded));
+    g.ok = true;
+    *out = S;
+    return STAN_OK;
+}
+
+int stan_mass_check_device(stan_ctx *ctx, int64_t N, const double *d_M, int64_t *bad) {
+    hipStream_t st = ctx->stream;
+    const long long none = 0x7fffffffffffffffLL;
+    *bad = -1;
+    if (N <= 0) return STAN_OK;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_status + SS_AUX, &none, 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_mass_check, dim3(nblk(N, 256)), dim3(256), 0, st, N, d_M, (long long *)(ctx->d_status + SS_AUX));
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, ctx->d_status + SS_AUX, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (ctx->h_status[SS_AUX] != none) *bad = ctx->h_status[SS_AUX];
+    return STAN_OK;
+}
+
+int stan_matrix_shifted_device(stan_ctx *ctx, stan_matrix *K, double sigma, const double *d_M, stan_matrix **out, double *shift_ms) {
+    hipStream_t st = ctx->stream;
+    stan_matrix *S = nullptr;
+    STANCHK(stan_matrix_clone_layout(ctx, K, &S));
+    stan_matrix_guard g{S};   // a failed call gives back what it had allocated
     event_bag evs;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (ctx->profiling && shift_ms) { e0 = evs.make(); e1 = evs.make(); }

@@ -273,6 +273,145 @@ k_md_scale(int64_t N, const double *__restrict__ X, const double *__restrict__ s
     if (row < N) phi[(int64_t)j * N + row] = X[(int64_t)j * N + row] / scale[j];
 }
 
+// ---- the buckling driver's block kernels (api_buckling.hip) ---------------------------------------
+// the start block: every column j >= 0 is the hash of (row, j)
+__global__ void __launch_bounds__(256)
+k_bk_start(int64_t N, int q, double *__restrict__ X0) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    for (int j = 0; j < q; j++) X0[(int64_t)j * N + i] = start_entry(i, j);
+}
+__global__ void __launch_bounds__(256)
+k_bk_negate(int64_t n, double *__restrict__ y) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = -y[i];
+}
+// X = Z Q: k_md_rotate's shape with one block of operands (Z may be X: a lane has read its whole row before it stores)
+template <int QT>
+__global__ void __launch_bounds__(256)
+k_bk_rotate_x(int64_t N, int q, const double *Z, const double *__restrict__ Qp, double *X) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= N) return;
+    double z[QT];
+#pragma unroll
+    for (int l = 0; l < QT; l++) z[l] = l < q ? Z[(int64_t)l * N + row] : 0.0;
+#pragma unroll
+    for (int j = 0; j < QT; j++) {
+        if (j >= q) continue;   // uniform
+        double x = 0.0;
+#pragma unroll
+        for (int l = 0; l < QT; l++) x = fma(z[l], Qp[l * QT + j], x);
+        X[(int64_t)j * N + row] = x;
+    }
+}
+// KX = W Q, R_j = sum_l (mu_j W_l - Y_l) Q_lj, rhs_j = -R_j where bit j of mask is clear, and per column the workgroup's sums
+// of R^2 / D and KX^2 / D: partial [2 q][gridDim.x], value j of R, q + j of KX.  The two blocks of operands fill the register
+// file, so a column's two sums leave at once: six butterfly stages per wave into LDS, the four waves added in order behind the
+// loop (block_sums' order).  W may be KX.
+template <int QT>
+__global__ void __launch_bounds__(256)
+k_bk_residual(int64_t N, int q, const double *W, const double *__restrict__ Y, const double *__restrict__ D,
+              const double *__restrict__ Qp, const md_cols cols, uint32_t mask, double *KX, double *__restrict__ rhs,
+              double *__restrict__ partial) {
+    __shared__ double sh[4][2 * QT];
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool in = row < N;
+    double w[QT], y[QT];
+#pragma unroll
+    for (int l = 0; l < QT; l++) {
+        w[l] = in && l < q ? W[(int64_t)l * N + row] : 0.0;
+        y[l] = in && l < q ? Y[(int64_t)l * N + row] : 0.0;
+    }
+    const double dinv = in ? 1.0 / D[row] : 0.0;
+#pragma unroll
+    for (int j = 0; j < QT; j++) {
+        if (j >= q) continue;   // uniform
+        const double mu = cols.lambda[j];
+        double kx = 0.0, r = 0.0;
+#pragma unroll
+        for (int l = 0; l < QT; l++) {
+            const double ql = Qp[l * QT + j];
+            kx = fma(w[l], ql, kx);
+            r = fma(fma(mu, w[l], -y[l]), ql, r);
+        }
+        if (in) {
+            KX[(int64_t)j * N + row] = kx;
+            if (!((mask >> j) & 1u)) rhs[(int64_t)j * N + row] = -r;
+        }
+        double s0 = (r * r) * dinv, s1 = (kx * kx) * dinv;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            s0 += __shfl_xor(s0, off, 64);
+            s1 += __shfl_xor(s1, off, 64);
+        }
+        if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6][j] = s0; sh[threadIdx.x >> 6][QT + j] = s1; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * QT) {
+        const int j = threadIdx.x < QT ? threadIdx.x : threadIdx.x - QT;
+        if (j < q) {
+            double s = sh[0][threadIdx.x];
+            for (int wv = 1; wv < 4; wv++) s += sh[wv][threadIdx.x];
+            partial[(int64_t)(threadIdx.x < QT ? j : q + j) * gridDim.x + blockIdx.x] = s;
+        }
+    }
+}
+// Z_j = mu_j X_j + D_dcol[j] (dcol[j] < 0: mu_j X_j); grid (rows / 256, q)
+__global__ void __launch_bounds__(256)
+k_bk_axpy(int64_t N, const double *X, const md_cols cols, const double *__restrict__ D, double *Zo) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int j = blockIdx.y;
+    if (row >= N) return;
+    const double x = X[(int64_t)j * N + row], mu = cols.lambda[j];
+    Zo[(int64_t)j * N + row] = cols.dcol[j] >= 0 ? fma(mu, x, D[(int64_t)cols.dcol[j] * N + row]) : mu * x;
+}
+// per column and workgroup the entry of largest magnitude (lowest index on a tie): pval / pidx [k][gridDim.x]
+__global__ void __launch_bounds__(256)
+k_bk_colmax(int64_t N, const double *__restrict__ X, double *__restrict__ pval, long long *__restrict__ pidx) {
+    __shared__ double shv[4];
+    __shared__ long long shi[4];
+    const int j = blockIdx.y;
+    double bv = 0.0;
+    long long bi = 0x7fffffffffffffffLL;
+    for (int k = 0; k < RT_ROWS / 256; k++) {
+        const int64_t row = (int64_t)blockIdx.x * RT_ROWS + k * 256 + threadIdx.x;
+        if (row < N) amax_merge(bv, bi, X[(int64_t)j * N + row], row);
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double v2 = __shfl_xor(bv, off, 64);
+        const long long i2 = __shfl_xor(bi, off, 64);
+        amax_merge(bv, bi, v2, i2);
+    }
+    if ((threadIdx.x & 63) == 0) { shv[threadIdx.x >> 6] = bv; shi[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) amax_merge(bv, bi, shv[w], shi[w]);
+        const int64_t o = (int64_t)j * gridDim.x + blockIdx.x;
+        pval[o] = bv; pidx[o] = bi;
+    }
+}
+// one workgroup per column: scale[j] = the column's entry of largest magnitude, signed (k_md_scale divides by it)
+__global__ void __launch_bounds__(256)
+k_bk_colmax_finish(int64_t n_blocks, const double *__restrict__ pval, const long long *__restrict__ pidx, double *__restrict__ scale) {
+    __shared__ double shv[4];
+    __shared__ long long shi[4];
+    const int64_t o = (int64_t)blockIdx.x * n_blocks;
+    double bv = 0.0;
+    long long bi = 0x7fffffffffffffffLL;
+    for (int64_t b = threadIdx.x; b < n_blocks; b += 256) amax_merge(bv, bi, pval[o + b], pidx[o + b]);
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double v2 = __shfl_xor(bv, off, 64);
+        const long long i2 = __shfl_xor(bi, off, 64);
+        amax_merge(bv, bi, v2, i2);
+    }
+    if ((threadIdx.x & 63) == 0) { shv[threadIdx.x >> 6] = bv; shi[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) amax_merge(bv, bi, shv[w], shi[w]);
+        scale[blockIdx.x] = bv;
+    }
+}
+
 template <int QT>
 void launch_rotate(hipStream_t st, unsigned nb, int64_t N, int q, const double *Z, const double *W, const double *M, const double *Qp,
                    const md_cols &cols, uint32_t mask, double *X, double *KX, double *rhs, double *partial) {
@@ -378,6 +517,86 @@ int stan_modal_normalise_device(stan_ctx *ctx, int64_t N, int32_t k, const doubl
     STANCHK(tmp.alloc(&d_scale, (size_t)k));
     hipLaunchKernelGGL(k_md_colstats, dim3((unsigned)nb, (unsigned)k), dim3(256), 0, st, N, d_X, d_M, d_psum, d_pval, d_pidx);
     hipLaunchKernelGGL(k_md_colfinish, dim3((unsigned)k), dim3(256), 0, st, nb, d_psum, d_pval, d_pidx, d_scale);
+    hipLaunchKernelGGL(k_md_scale, dim3(nblk(N, 256), (unsigned)k), dim3(256), 0, st, N, d_X, d_scale, d_phi);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipStreamSynchronize(st));   // the temporaries go back to the context behind the kernels
+    return STAN_OK;
+}
+
+// ---- the buckling driver's block kernels ----------------------------------------------------------------------------------
+int stan_buckling_start_device(stan_ctx *ctx, int64_t N, int32_t q, double *d_X0) {
+    STANCHK(block_args_check(ctx, "buckling", N, q));
+    hipLaunchKernelGGL(k_bk_start, dim3(nblk(N, 256)), dim3(256), 0, ctx->stream, N, (int)q, d_X0);
+    HIPCHK(ctx, hipGetLastError());
+    return STAN_OK;
+}
+
+int stan_buckling_negate_device(stan_ctx *ctx, int64_t n, double *d_y) {
+    if (n > 0) hipLaunchKernelGGL(k_bk_negate, dim3(nblk(n, 256)), dim3(256), 0, ctx->stream, n, d_y);
+    HIPCHK(ctx, hipGetLastError());
+    return STAN_OK;
+}
+
+int stan_buckling_rotate_device(stan_ctx *ctx, int64_t N, int32_t q, const double *d_Z, const double *d_W, const double *d_Y,
+                                const double *d_D, const double *Q, const double *mu, uint32_t mask, double *d_X, double *d_KX,
+                                double *d_rhs, double *r2, double *kx2) {
+    STANCHK(block_args_check(ctx, "buckling_rotate", N, q));
+    hipStream_t st = ctx->stream;
+    const int QT = q <= 8 ? 8 : q <= 16 ? 16 : q <= 24 ? 24 : 32;
+    const int64_t nb = nblk(N, 256);
+    std::vector<double> Qp((size_t)QT * QT, 0.0);   // outlives the stream's copy
+    md_cols cols;
+    for (int l = 0; l < QMAX; l++) { cols.lambda[l] = l < q ? mu[l] : 0.0; cols.dcol[l] = -1; }
+    for (int l = 0; l < q; l++)
+        for (int j = 0; j < q; j++) Qp[(size_t)l * QT + j] = Q[l * q + j];
+    dev_scope tmp(ctx);
+    double *d_Qp, *d_partial, *d_out;
+    STANCHK(tmp.alloc(&d_Qp, Qp.size()));
+    STANCHK(tmp.alloc(&d_partial, 2 * (size_t)q * (size_t)nb));
+    STANCHK(tmp.alloc(&d_out, 2 * (size_t)q));
+    HIPCHK(ctx, hipMemcpyAsync(d_Qp, Qp.data(), Qp.size() * 8, hipMemcpyHostToDevice, st));
+    const dim3 g((unsigned)nb), b(256);
+#define STAN_BK_LAUNCH(QTV)                                                                                                      \
+    do {                                                                                                                         \
+        hipLaunchKernelGGL(k_bk_rotate_x<QTV>, g, b, 0, st, N, (int)q, d_Z, d_Qp, d_X);                                          \
+        hipLaunchKernelGGL(k_bk_residual<QTV>, g, b, 0, st, N, (int)q, d_W, d_Y, d_D, d_Qp, cols, mask, d_KX, d_rhs, d_partial); \
+    } while (0)
+    if (QT == 8) STAN_BK_LAUNCH(8);
+    else if (QT == 16) STAN_BK_LAUNCH(16);
+    else if (QT == 24) STAN_BK_LAUNCH(24);
+    else STAN_BK_LAUNCH(32);
+#undef STAN_BK_LAUNCH
+    hipLaunchKernelGGL(k_md_finish, dim3(2 * (unsigned)q), dim3(256), 0, st, nb, d_partial, d_out);
+    HIPCHK(ctx, hipGetLastError());
+    std::vector<double> out(2 * (size_t)q);
+    HIPCHK(ctx, hipMemcpyAsync(out.data(), d_out, out.size() * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    for (int j = 0; j < q; j++) { r2[j] = out[(size_t)j]; kx2[j] = out[(size_t)(q + j)]; }
+    return STAN_OK;
+}
+
+int stan_buckling_axpy_device(stan_ctx *ctx, int64_t N, int32_t q, const double *d_X, const double *mu, const int32_t *dcol,
+                              const double *d_D, double *d_Z) {
+    STANCHK(block_args_check(ctx, "buckling", N, q));
+    md_cols cols;
+    for (int l = 0; l < QMAX; l++) { cols.lambda[l] = l < q ? mu[l] : 0.0; cols.dcol[l] = l < q ? dcol[l] : -1; }
+    hipLaunchKernelGGL(k_bk_axpy, dim3(nblk(N, 256), (unsigned)q), dim3(256), 0, ctx->stream, N, d_X, cols, d_D, d_Z);
+    HIPCHK(ctx, hipGetLastError());
+    return STAN_OK;
+}
+
+int stan_buckling_normalise_device(stan_ctx *ctx, int64_t N, int32_t k, const double *d_X, double *d_phi) {
+    STANCHK(block_args_check(ctx, "buckling", N, k));
+    hipStream_t st = ctx->stream;
+    const int64_t nb = nblk(N, RT_ROWS);
+    dev_scope tmp(ctx);
+    double *d_pval, *d_scale;
+    long long *d_pidx;
+    STANCHK(tmp.alloc(&d_pval, (size_t)k * (size_t)nb));
+    STANCHK(tmp.alloc(&d_pidx, (size_t)k * (size_t)nb));
+    STANCHK(tmp.alloc(&d_scale, (size_t)k));
+    hipLaunchKernelGGL(k_bk_colmax, dim3((unsigned)nb, (unsigned)k), dim3(256), 0, st, N, d_X, d_pval, d_pidx);
+    hipLaunchKernelGGL(k_bk_colmax_finish, dim3((unsigned)k), dim3(256), 0, st, nb, d_pval, d_pidx, d_scale);
     hipLaunchKernelGGL(k_md_scale, dim3(nblk(N, 256), (unsigned)k), dim3(256), 0, st, N, d_X, d_scale, d_phi);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(st));   // the temporaries go back to the context behind the kernels

@@ -61,6 +61,8 @@ EXPORTS = [
     "stan_hip_block_gram", "stan_hip_block_rotate",
     "stan_hip_matrix_shifted", "stan_hip_matrix_shifted_dev", "stan_hip_transient", "stan_hip_transient_dev",
     "stan_hip_newmark_predict", "stan_hip_newmark_correct",
+    "stan_hip_kg_hex8_batch", "stan_hip_geometric_stiffness_hex8", "stan_hip_geometric_stiffness_hex8_dev",
+    "stan_hip_geometric_stiffness_times", "stan_hip_buckling", "stan_hip_buckling_dev", "stan_hip_buckling_rotate",
 ]
 # only in the lab build (stan_amd/csrc/lab/stan_hip_lab.h, selected with STAN_HIP_LIB)
 LAB_EXPORTS = ["stan_hip_csr_spmv_bench", "stan_hip_lab_placement_map", "stan_hip_lab_placement_variants", "stan_hip_lab_placement_alloc", "stan_hip_lab_placement_rounds", "stan_hip_lab_placement_cross", "stan_hip_lab_incg_penalty", "stan_hip_lab_placement_vecalloc", "stan_hip_lab_placement_vecshape", "stan_hip_lab_pairing_pmc"]
@@ -130,6 +132,17 @@ class ModesReport(C.Structure):
     _fields_ = [("block", C.c_int32), ("outer", C.c_int32), ("converged", C.c_int32), ("cg_worst_type", C.c_int32),
                 ("cg_iterations", C.c_int64), ("max_rho", C.c_double), ("solve_ms", C.c_double), ("product_ms", C.c_double),
                 ("block_ms", C.c_double), ("gram_ms", C.c_double), ("rotate_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class BucklingReport(C.Structure):
+    """stan_buckling_report (include/stan_hip.h)"""
+    _fields_ = [("block", C.c_int32), ("outer", C.c_int32), ("converged", C.c_int32), ("n_positive", C.c_int32),
+                ("cg_worst_type", C.c_int32), ("reserved", C.c_int32), ("cg_iterations", C.c_int64),
+                ("lowest_negative_factor", C.c_double), ("max_rho", C.c_double), ("solve_ms", C.c_double),
+                ("product_ms", C.c_double), ("block_ms", C.c_double), ("gram_ms", C.c_double), ("rotate_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -333,6 +346,59 @@ class Context:
                                                   C.c_double(E), C.c_double(nu),
                                                   _ptr(etypes, C.c_uint8), _ptr(out, C.c_double)))
         return out.reshape(n, 24, 24)
+
+    def kg_hex8_batch(self, xyz8, u8, E, nu, etypes):
+        """stan_hip_kg_hex8_batch: s36 [n, 36], the upper triangle of the element scalars of the geometric stiffness."""
+        xyz8 = np.ascontiguousarray(xyz8, dtype=np.float64).reshape(-1, 24)
+        u8 = np.ascontiguousarray(u8, dtype=np.float64).reshape(-1, 24)
+        n = xyz8.shape[0]
+        etypes = np.ascontiguousarray(etypes, dtype=np.uint8).reshape(-1)
+        if u8.shape[0] != n or etypes.shape[0] != n:
+            raise ValueError("kg_hex8_batch: xyz8, u8 must be [n, 24] and etypes [n]")
+        out = np.zeros((n, 36))
+        self._chk(self.lib.stan_hip_kg_hex8_batch(self.h, C.c_int64(n), _ptr(xyz8, C.c_double), _ptr(u8, C.c_double),
+                                                  C.c_double(E), C.c_double(nu), _ptr(etypes, C.c_uint8), _ptr(out, C.c_double)))
+        return out
+
+    def geometric_stiffness_times(self):
+        """dict(kg_elem_ms, kg_layout_ms, kg_list_ms, kg_gather_ms) of the last geometric-stiffness call (profiling enabled)."""
+        ms = (C.c_double * 4)()
+        self._chk(self.lib.stan_hip_geometric_stiffness_times(self.h, ms))
+        return dict(kg_elem_ms=ms[0], kg_layout_ms=ms[1], kg_list_ms=ms[2], kg_gather_ms=ms[3])
+
+    def buckling(self, K, G, n_modes, tol=0.0, max_outer=0, solve_eps=0.0, solve_max_its=0):
+        """stan_hip_buckling: the n_modes lowest positive load factors of (K + lambda G) phi = 0, G = K.geometric_stiffness(...).
+        Returns (factor [n_modes], phi [n_modes, N], rho [n_modes], report dict of stan_buckling_report)."""
+        N = K.info()["n_reduced"]
+        k = max(int(n_modes), 1)
+        fac, phi, rho, rep = np.zeros(k), np.zeros((k, N)), np.zeros(k), BucklingReport()
+        self._chk(self.lib.stan_hip_buckling(
+            self.h, K.k, G.k, C.c_int32(int(n_modes)), C.c_double(tol), C.c_int32(max_outer), C.c_double(solve_eps),
+            C.c_int32(solve_max_its), _ptr(fac, C.c_double), _ptr(phi, C.c_double), _ptr(rho, C.c_double), C.byref(rep)))
+        return fac, phi, rho, rep.as_dict()
+
+    def buckling_dev(self, K, G, n_modes, d_factor, d_phi, d_rho, tol=0.0, max_outer=0, solve_eps=0.0, solve_max_its=0):
+        """d_factor / d_rho [n_modes], d_phi [n_modes, N]: device pointers (ints).  Returns the report dict."""
+        rep = BucklingReport()
+        self._chk(self.lib.stan_hip_buckling_dev(
+            self.h, K.k, G.k, C.c_int32(int(n_modes)), C.c_double(tol), C.c_int32(max_outer), C.c_double(solve_eps),
+            C.c_int32(solve_max_its), _opt(d_factor), _opt(d_phi), _opt(d_rho), C.byref(rep)))
+        return rep.as_dict()
+
+    def buckling_rotate(self, Z, W, Y, D, Q, mu):
+        """stan_hip_buckling_rotate: (X, KX, R, r2, kx2).  Z, W, Y [q, N], D [N], Q [q, q], mu [q]."""
+        Z, W, Y, Q = (np.ascontiguousarray(x, dtype=np.float64) for x in (Z, W, Y, Q))
+        D = np.ascontiguousarray(D, dtype=np.float64).reshape(-1)
+        mu = np.ascontiguousarray(mu, dtype=np.float64).reshape(-1)
+        if Z.ndim != 2 or W.shape != Z.shape or Y.shape != Z.shape or D.shape[0] != Z.shape[1] or Q.shape != (Z.shape[0],) * 2 or mu.shape[0] != Z.shape[0]:
+            raise ValueError("buckling_rotate: Z, W, Y must be [q, N], D [N], Q [q, q], mu [q]")
+        q, N = Z.shape
+        X, KX, R, r2, kx2 = np.zeros((q, N)), np.zeros((q, N)), np.zeros((q, N)), np.zeros(q), np.zeros(q)
+        self._chk(self.lib.stan_hip_buckling_rotate(
+            self.h, C.c_int64(N), C.c_int32(q), _ptr(Z, C.c_double), _ptr(W, C.c_double), _ptr(Y, C.c_double), _ptr(D, C.c_double),
+            _ptr(Q, C.c_double), _ptr(mu, C.c_double), _ptr(X, C.c_double), _ptr(KX, C.c_double), _ptr(R, C.c_double),
+            _ptr(r2, C.c_double), _ptr(kx2, C.c_double)))
+        return X, KX, R, r2, kx2
 
     # -- stress recovery ---------------------------------------------------------------
     def recover_hex8(self, xyz, disp, conn, elem_mat, elem_type, mat_E_nu):
@@ -866,6 +932,31 @@ class Matrix:
         """d_M [N]: a device pointer (int)."""
         k = C.c_void_p()
         self.ctx._chk(self.ctx.lib.stan_hip_matrix_shifted_dev(self.ctx.h, self.k, C.c_double(sigma), _opt(d_M), C.byref(k)))
+        return Matrix(self.ctx, k)
+
+    def geometric_stiffness(self, xyz, disp, node_dof, conn, elem_mat, elem_type, mat_E_nu, red):
+        """stan_hip_geometric_stiffness_hex8: a new Matrix holding G = K_g(disp) in this matrix' layout; disp [n_nodes, 3] in
+        NodeLib order, the mesh arrays those this matrix was assembled from.  This matrix is left as it is."""
+        xyz, disp, node_dof, conn, elem_mat, elem_type, mat_E_nu, red = _mesh(
+            xyz=xyz, disp=disp, node_dof=node_dof, conn=conn, elem_mat=elem_mat, elem_type=elem_type, mat_E_nu=mat_E_nu, red=red)
+        if disp.size != xyz.size:
+            raise ValueError("geometric_stiffness: disp must be [n_nodes, 3]")
+        k = C.c_void_p()
+        self.ctx._chk(self.ctx.lib.stan_hip_geometric_stiffness_hex8(
+            self.ctx.h, self.k, C.c_int64(xyz.shape[0]), _ptr(xyz, C.c_double), _ptr(disp, C.c_double), _ptr(node_dof, C.c_int32),
+            C.c_int64(conn.shape[0]), _ptr(conn, C.c_int32), _ptr(elem_mat, C.c_int32), _ptr(elem_type, C.c_uint8),
+            C.c_int32(mat_E_nu.shape[0]), _ptr(mat_E_nu, C.c_double), C.c_int64(red.shape[0]), _ptr(red, C.c_int32), C.byref(k)))
+        return Matrix(self.ctx, k)
+
+    def geometric_stiffness_dev(self, n_nodes, d_xyz, d_disp, d_node_dof, n_elem, d_conn, d_elem_mat, d_elem_type, mat_E_nu,
+                                n_dof, d_red):
+        """All d_* are device pointers (ints), e.g. torch tensor.data_ptr()."""
+        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        k = C.c_void_p()
+        self.ctx._chk(self.ctx.lib.stan_hip_geometric_stiffness_hex8_dev(
+            self.ctx.h, self.k, C.c_int64(n_nodes), _dev(d_xyz, C.c_double), _dev(d_disp, C.c_double), _dev(d_node_dof, C.c_int32),
+            C.c_int64(n_elem), _dev(d_conn, C.c_int32), _dev(d_elem_mat, C.c_int32), _dev(d_elem_type, C.c_uint8),
+            C.c_int32(mat_E_nu.shape[0]), _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _dev(d_red, C.c_int32), C.byref(k)))
         return Matrix(self.ctx, k)
 
     def modes_shifted(self, M, n_modes, sigma, **kw):

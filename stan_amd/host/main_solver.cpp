@@ -29,6 +29,10 @@
 // STdb: the lumped mass from the "Density" BCs (material IDs, component 0 = rho) and the K lowest natural frequencies from
 // stan_hip_modes; a block "Natural frequencies:", with --json a "modes" object, with --vtu PREFIX one PREFIX_mode_NNN.vtu per
 // mode (point arrays "Mode Shape X" / "Y" / "Z" and "Magnitude").  One device only; a file without a "Density" entry is refused.
+// --buckling K [--buckling-tol T] [--solve-eps E] runs the static solve under the model's own loads, builds
+// G = K_g(U) (stan_hip_geometric_stiffness_hex8) and finds the K lowest positive load factors (stan_hip_buckling): a block
+// "Buckling load factors:", with --json a "buckling" object, with --vtu PREFIX one PREFIX_buckle_NNN.vtu per factor; the STdb is
+// never written.  Refused before anything is computed: several devices, a "Temperature" boundary condition, no supports.
 // --modes-shift SIGMA (a model without supports): the modes of K + SIGMA M (stan_hip_matrix_shifted), printed as lambda = mu - SIGMA;
 // rho is then the convergence measure of the shifted problem, "shift" in the JSON object.
 // --transient --dt DT --steps N [--newmark B,G] [--rayleigh A,B] [--load-curve t0,g0,t1,g1,...] [--probe-node ID] [--solve-eps E]
@@ -79,6 +83,9 @@ int main(int argc, char **argv) {
     bool vtu = false, vtu_cells = false, reactions = false;
     int modes = 0;
     double modes_tol = 0.0, modes_shift = 0.0;
+    int buckling = 0;
+    double buckling_tol = 0.0, solve_eps = 0.0;
+    bool buckling_arg = false, have_solve_eps = false;
     bool transient = false, transient_arg = false, bad_list = false;
     SolverFunctions::TransientRun run;
     int probe_node = 0, vtu_every = 1;
@@ -129,7 +136,9 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--transient")) transient = true;
         else if (!strcmp(argv[i], "--dt") && i + 1 < argc) { transient_arg = true; run.dt = atof(argv[++i]); }
         else if (!strcmp(argv[i], "--steps") && i + 1 < argc) { transient_arg = true; run.n_steps = atoi(argv[++i]); }
-        else if (!strcmp(argv[i], "--solve-eps") && i + 1 < argc) { transient_arg = true; run.solve_eps = atof(argv[++i]); }
+        else if (!strcmp(argv[i], "--buckling") && i + 1 < argc) { buckling_arg = true; buckling = atoi(argv[++i]); }
+        else if (!strcmp(argv[i], "--buckling-tol") && i + 1 < argc) { buckling_arg = true; buckling_tol = atof(argv[++i]); }
+        else if (!strcmp(argv[i], "--solve-eps") && i + 1 < argc) { have_solve_eps = true; solve_eps = run.solve_eps = atof(argv[++i]); }
         else if (!strcmp(argv[i], "--probe-node") && i + 1 < argc) { transient_arg = have_probe = true; probe_node = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "--vtu-every") && i + 1 < argc) { transient_arg = true; vtu_every = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "--newmark") && i + 1 < argc) {
@@ -151,6 +160,7 @@ int main(int argc, char **argv) {
     if (path.empty()) {  // Path = path[0] -> IndexOutOfRangeException in the reference
         fprintf(stderr, "usage: stan_solver [--device N | --gpus N | --devices a,b,..] [--p2p] [--mixed|--fixed48] "
                         "[--no-merit-stop] [--packed] [--object-results] [--json] [--vtu PREFIX [--vtu-results \"name,..\"] [--vtu-cells]] [--reactions] [--modes K [--modes-tol T] [--modes-shift SIGMA]] "
+                        "[--buckling K [--buckling-tol T] [--solve-eps E] [--vtu PREFIX]] "
                         "[--transient --dt DT --steps N [--newmark B,G] [--rayleigh A,B] [--load-curve t0,g0,t1,g1,...] [--probe-node ID] "
                         "[--solve-eps E] [--vtu PREFIX [--vtu-every K]]] <model.STdb>\n");
         return 2;
@@ -187,6 +197,21 @@ int main(int argc, char **argv) {
         fprintf(stderr, "stan_solver: --modes-shift SIGMA needs SIGMA > 0 and --modes\n");
         return 2;
     }
+    // --buckling, checked before anything is read as well
+    if (buckling_arg) {
+        const char *why = nullptr;
+        if (buckling <= 0 || !(buckling_tol >= 0)) why = "--buckling K needs K > 0, --buckling-tol T needs T >= 0 and --buckling";
+        else if (modes || transient) why = "--buckling, --modes and --transient are three analyses: one per run";
+        else if (!(solve_eps >= 0)) why = "--solve-eps E needs E >= 0";
+        else if (devices.size() > 1)
+            why = "--buckling works on one device: the geometric stiffness adds up all elements at a node, and the block solves run "
+                  "on a single-rank context (drop --gpus/--devices)";
+        if (why) {
+            fprintf(stderr, "stan_solver: %s\n", why);
+            return 2;
+        }
+    }
+    if (have_solve_eps && !buckling) transient_arg = true;
     // --transient, checked before anything is read as well
     if (!transient && transient_arg) {
         fprintf(stderr, "stan_solver: --dt, --steps, --newmark, --rayleigh, --load-curve, --probe-node, --solve-eps and --vtu-every belong to --transient\n");
@@ -253,6 +278,18 @@ int main(int argc, char **argv) {
         return 2;
     }
 
+    if (buckling && DB.AnalysisLib.Type != "Linear_Statics") {
+        fprintf(stderr, "stan_solver: --buckling works on a Linear_Statics file\n");
+        return 2;
+    }
+    if (buckling)   // the stress state is sigma = D B u: a thermal part is out of scope
+        for (const auto &kv : DB.BCLib.Items())
+            if (kv.second.Type == "Temperature") {
+                fprintf(stderr, "stan_solver: --buckling takes mechanical loads only: the file has a \"Temperature\" boundary condition "
+                                "(thermal pre-stress is out of scope)\n");
+                return 2;
+            }
+
     printf("   DoF ordering: ");  // Solver.cs:44-47
     fflush(stdout);
     t0 = clk::now();
@@ -283,6 +320,10 @@ int main(int argc, char **argv) {
                                                "elements at a node, and a multi-device handle holds them in chunks (drop --gpus/--devices)");
         t_bc = secs(t0);
         const int64_t n_nodes = (int64_t)DB.NodeLib.Count();
+        if (buckling && n_fixed == 0) {   // before anything is assembled: K of a model without supports is not positive definite
+            fprintf(stderr, "stan_solver: --buckling needs a supported model: the file fixes no DOF\n");
+            return 2;
+        }
 
         t0 = clk::now();
         SparseMatrixHandle K;
@@ -451,6 +492,53 @@ int main(int argc, char **argv) {
                         for (size_t q = 0; q < np; q++) printf("%s%.17g", q ? ", " : "", probe_u[(size_t)s * np + q]);
                         printf("]");
                     }
+                    printf("]");
+                }
+                printf("}}\n");
+            }
+            return 0;
+        }
+
+        if (buckling) {   // the static solve under the model's own loads, G from that U, then the load factors: nothing reaches the STdb
+            const std::vector<double> Ub = Functions.LinearSolver_CG(K, F_solve, DB.AnalysisLib);
+            printf("   CG iterations: %d, scaled relative residual %.3e\n", Functions.last_iterations, Functions.last_rel_residual);
+            const std::vector<double> Ubf = Functions.Include_BC_DOF(Ub, nDOF_reduction);
+            std::vector<double> dispb((size_t)n_nodes * 3);
+            for (size_t k = 0; k < dispb.size(); k++) dispb[k] = Ubf[(size_t)K.flat.node_dof[k]];
+            if (dist_loads && !dl.disp0.empty())   // the solved field is U on top of the prescribed u0
+                for (size_t k = 0; k < dispb.size(); k++) dispb[k] += dl.disp0[k];
+            std::vector<double> factor, phi, rho;
+            stan_buckling_report rep{};
+            Functions.Buckling(K, nDOF_reduction, dispb, buckling, buckling_tol, solve_eps, &factor, &phi, &rho, &rep);
+            const int found = rep.n_positive < buckling ? rep.n_positive : buckling;
+            printf("   Buckling load factors: (block %d, %d outer steps, %lld CG iterations, %s)\n", rep.block, rep.outer,
+                   (long long)rep.cg_iterations, rep.converged ? "converged" : "NOT converged");
+            printf("     mode            factor           rho\n");
+            for (int j = 0; j < found; j++) printf("     %4d  %16.8e  %12.3e\n", j + 1, factor[(size_t)j], rho[(size_t)j]);
+            if (found < buckling) printf("     only %d positive factors in the block of %d\n", rep.n_positive, rep.block);
+            if (rep.lowest_negative_factor != 0)
+                printf("     lowest negative factor (the load reversed): %.8e\n", rep.lowest_negative_factor);
+            if (vtu) {
+                const size_t N = (size_t)minfo.n_reduced;
+                std::vector<double> shape((size_t)n_nodes * 3);
+                for (int j = 0; j < found; j++) {
+                    const std::vector<double> full = Functions.Include_BC_DOF(
+                        std::vector<double>(phi.begin() + (ptrdiff_t)((size_t)j * N), phi.begin() + (ptrdiff_t)((size_t)(j + 1) * N)), nDOF_reduction);
+                    for (size_t k = 0; k < shape.size(); k++) shape[k] = full[(size_t)K.flat.node_dof[k]];
+                    Functions.Export_Buckle_Vtu(K, shape, vtu_prefix, j + 1);
+                }
+                if (found > 0) printf("   VTU export: %s_buckle_001.vtu ... %s_buckle_%03d.vtu\n", vtu_prefix.c_str(), vtu_prefix.c_str(), found);
+            }
+            printf("\n%s\n  Total CPU time: %.2f s\n%s\n", separator, secs(t_total), separator);
+            if (json) {   // %.17g: the doubles round-trip
+                printf("{\"n_gpus\": 1, \"n_dof\": %d, \"n_reduced\": %lld, \"t_wall_s\": %.3f, \"buckling\": {\"n_modes\": %d, \"block\": %d, "
+                       "\"outer\": %d, \"converged\": %d, \"n_positive\": %d, \"cg_iterations\": %lld, \"static_cg_iterations\": %d, "
+                       "\"lowest_negative_factor\": %.17g",
+                       DB.nDOF, (long long)minfo.n_reduced, secs(t_wall), buckling, rep.block, rep.outer, rep.converged, rep.n_positive,
+                       (long long)rep.cg_iterations, Functions.last_iterations, rep.lowest_negative_factor);
+                for (int pass = 0; pass < 2; pass++) {
+                    printf(", \"%s\": [", pass == 0 ? "factor" : "rho");
+                    for (int j = 0; j < found; j++) printf("%s%.17g", j ? ", " : "", pass == 0 ? factor[(size_t)j] : rho[(size_t)j]);
                     printf("]");
                 }
                 printf("}}\n");

@@ -307,10 +307,39 @@ void SolverFunctions::Export_Step_Vtu(SparseMatrixHandle &K, const std::vector<i
         throw std::runtime_error("cannot write " + path);
 }
 
-void SolverFunctions::Export_Mode_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &prefix, int mode) const {
+void SolverFunctions::Buckling(SparseMatrixHandle &K, const std::vector<int32_t> &red, const std::vector<double> &dU, int n_modes, double tol,
+                               double solve_eps, std::vector<double> *factor, std::vector<double> *phi, std::vector<double> *rho,
+                               stan_buckling_report *rep) const {
     const FlatModel &f = K.flat;
     const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
+    size_t n_fixed = 0;
+    for (int32_t r : red) n_fixed += r == -1;
+    const size_t N = red.size() - n_fixed, k = n_modes > 0 ? (size_t)n_modes : 1;
+    factor->assign(k, 0.0); rho->assign(k, 0.0); phi->assign(k * N, 0.0);
+    stan_matrix *G = nullptr;
+    if (stan_hip_geometric_stiffness_hex8(K.ctx, K.K, n_nodes, f.xyz.data(), dU.data(), f.node_dof.data(), n_elem, f.conn.data(),
+                                          f.elem_mat.data(), f.elem_type.data(), (int32_t)(f.mat_E_nu.size() / 2), f.mat_E_nu.data(),
+                                          (int64_t)red.size(), red.data(), &G))
+        throw std::runtime_error(stan_hip_last_error(K.ctx));
+    const int rc = stan_hip_buckling(K.ctx, K.K, G, n_modes, tol, 0, solve_eps, 0, factor->data(), phi->data(), rho->data(), rep);
+    stan_hip_matrix_free(G);
+    if (rc) throw std::runtime_error(stan_hip_last_error(K.ctx));
+}
+
+void SolverFunctions::Export_Mode_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &prefix, int mode) const {
     static const char *const names[4] = {"Mode Shape X", "Mode Shape Y", "Mode Shape Z", "Magnitude"};
+    Export_Shape_Vtu(K, shape, prefix + "_mode_", names, mode);
+}
+
+void SolverFunctions::Export_Buckle_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &prefix, int mode) const {
+    static const char *const names[4] = {"Buckling Shape X", "Buckling Shape Y", "Buckling Shape Z", "Magnitude"};
+    Export_Shape_Vtu(K, shape, prefix + "_buckle_", names, mode);
+}
+
+void SolverFunctions::Export_Shape_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &stem,
+                                       const char *const names[4], int mode) const {
+    const FlatModel &f = K.flat;
+    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
     std::vector<double> point(4 * (size_t)n_nodes);
     for (int64_t n = 0; n < n_nodes; n++) {
         double s2 = 0;
@@ -323,7 +352,7 @@ void SolverFunctions::Export_Mode_Vtu(SparseMatrixHandle &K, const std::vector<d
     }
     char num[16];
     snprintf(num, sizeof num, "%03d", mode);
-    const std::string path = prefix + "_mode_" + num + ".vtu";
+    const std::string path = stem + num + ".vtu";
     if (stan_host_write_vtu(path.c_str(), n_nodes, f.xyz.data(), shape.data(), n_elem, f.conn.data(), 4, names, point.data(), 0, nullptr,
                             nullptr))
         throw std::runtime_error("cannot write " + path);

@@ -135,6 +135,18 @@ class SolverFunctions {
     // <prefix>_mode_NNN.vtu (NNN = 001 ...) for one mode: shape [n_nodes*3] in NodeLib order as the point arrays "Mode Shape X" /
     // "Y" / "Z" and "Magnitude", through the writer of vtu.cpp (the shape also takes the place of the displacements)
     void Export_Mode_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &prefix, int mode) const;
+    // Linear buckling (stan_hip_geometric_stiffness_hex8 + stan_hip_buckling; no step of the reference):
+    // G = K_g of the static solution nodal_dU [n_nodes*3] (NodeLib order), then the n_modes lowest positive load factors of
+    // (K + lambda G) phi = 0; factor / rho [n_modes], phi [n_modes][N] on the free DOFs; *rep always filled.  One device only.
+    void Buckling(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const std::vector<double> &nodal_dU, int n_modes,
+                  double tol, double solve_eps, std::vector<double> *factor, std::vector<double> *phi, std::vector<double> *rho,
+                  stan_buckling_report *rep) const;
+    // <prefix>_buckle_NNN.vtu (NNN = 001 ...) for one buckling shape: as Export_Mode_Vtu with the point arrays "Buckling Shape X" /
+    // "Y" / "Z" and "Magnitude"
+    void Export_Buckle_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &prefix, int mode) const;
+    // what the two share: <stem>NNN.vtu with the four point arrays `names`
+    void Export_Shape_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &stem, const char *const names[4],
+                          int mode) const;
     // "name,name,..." of --vtu-results -> indices (stan_host_scalar_name's strings; empty text = all 24); false + *err on an unknown name
     static bool ParseScalarNames(const std::string &text, std::vector<int32_t> *sel, std::string *err);
 
