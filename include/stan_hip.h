@@ -122,6 +122,8 @@ int stan_hip_set_stream(stan_ctx *ctx, void *hip_stream);
  *   20 STAN_OPT_CG_REFINE            1     reduced-precision streams: 0 fp64 check only, 1 + refinement passes, 2 + fp64 refresh
  *   21 STAN_OPT_CG_LAZY_SCALING      1     the loop's first product brings K into its Jacobi-scaled form (no pass of its own)
  *   22 STAN_OPT_VALUE_STREAM_60      -1    fp64 solves stream the scaled values as lossless 60-bit words (auto)
+ *   23 STAN_OPT_CG_X_RING            -1    merit stop off: x formed once per refresh window from a ring of directions (auto)
+ *   24 STAN_OPT_CG_REFRESH_60        -1    the fused refresh passes read the 60-bit stream where the plain products do (auto)
  * The descriptions follow in the order the options were added.
  *   STAN_OPT_CG_MERIT_STOP  1 (default): stop with type 7 when the merit function x'Ax-2b'x
  *                           no longer decreases (rounding floor, ~1e-7 relative residual on
@@ -297,6 +299,28 @@ int stan_hip_set_stream(stan_ctx *ctx, void *hip_stream);
                            pool budget).  stan_profile.value_stream (STAN_VALUE_STREAM_60) and spmv_bytes tell what
                            ran; placement_candidates / _ms_best / _ms_worst then describe the search for THIS block (the
                            one the plain products stream), which never moves the solver's vectors. */
+#define STAN_OPT_CG_X_RING 23 /* -1 (default) / 0 / 1.  Where STAN_OPT_CG_DEFER_X forms x' = x + alpha p next to p' -- the merit
+                           stop off -- nothing reads the iterate between two residual refreshes.  The loop then keeps the
+                           directions of a window in a ring of W + 1 vectors (W = STAN_OPT_CG_RUPDATE when that is 2 ... 16,
+                           otherwise 10), the step kernel writes p' into the next slot and leaves x alone, and one pass in
+                           front of every refresh (and one behind the loop) adds the pending terms to x in iteration
+                           order, one fused multiply-add per term: the same operations in the same order, the same bits,
+                           8 fewer vector passes per window of 10.  Applies to STAN_PREC_FP64 on one rank in the classic
+                           loop with STAN_OPT_CG_FUSED_REFRESH 1 and a refresh period other than 1; anything else runs
+                           the loop as it is without this option.  1: wherever it applies; -1: there, and only above
+                           150 000 block rows; 0: never.  The ring is taken per solve ((W + 1) gather-length vectors,
+                           148^3: 11 x 79 MB) and only when there is room for it: a parked block that fits, or the block
+                           and as much again (a sixteenth of the device at least) free; no room: the loop as it is.
+                           stan_hip_cg_loop_info tells what the last solve did; the flush launches are part of
+                           stan_profile.loop_kernel_launches. */
+#define STAN_OPT_CG_REFRESH_60 24 /* -1 (default) / 0 / 1.  In a solve whose plain products read the lossless 60-bit stream
+                           (STAN_OPT_VALUE_STREAM_60) the fused refresh passes -- A x and A p in one matrix pass, every
+                           STAN_OPT_CG_RUPDATE iterations -- read it too: the same doubles bit for bit, 68 B per block
+                           instead of 72, and no product inside the loop reads the fp64 block any more.  The sums are
+                           formed as the fp64 pass forms them: the results do not depend on this option.  The first
+                           product, the encoding pass, the fp64 check, exports and stan_hip_spmv keep the fp64 values,
+                           which stay resident.  1: wherever the solve has the stream; -1: there, and only above 150 000
+                           block rows; 0: never.  stan_hip_cg_loop_info tells which stream the refresh passes read. */
 #define STAN_OPT_SPMV_VARIANT 3 /* SpMV kernel variant (cg.hip): -1 = auto (default: 9 for fp64/fp32 streams,
                            12 for FIXED-48), 0 = plain loads + identity mapping, 9 = non-temporal matrix
                            stream + XCD-chunked workgroup mapping, 12 = 9 unrolled by 4: these three add a row's
@@ -308,6 +332,13 @@ int stan_hip_set_stream(stan_ctx *ctx, void *hip_stream);
 int stan_hip_set_option(stan_ctx *ctx, int32_t option, int64_t value);
 /* What STAN_OPT_POOL currently keeps: bytes and number of parked device blocks (either may be NULL). */
 int stan_hip_pool_info(stan_ctx *ctx, int64_t *bytes_parked, int64_t *blocks_parked);
+
+/* What STAN_OPT_CG_X_RING and STAN_OPT_CG_REFRESH_60 did in the most recent solve of this context (a call of its own:
+ * stan_profile is ABI and keeps its fields; no profiling needed).  *x_ring_window: the ring's window W, 0 when the loop
+ * formed x every iteration (the option off, the loop not of the form it applies to, or no room for the ring);
+ * *x_ring_flushes: the flush launches the loop enqueued, the closing one included; *refresh_stream: the value stream the
+ * fused refresh passes read (STAN_PREC_*, or STAN_VALUE_STREAM_60), -1 when the solve made none.  Any pointer may be NULL. */
+int stan_hip_cg_loop_info(stan_ctx *ctx, int32_t *x_ring_window, int64_t *x_ring_flushes, int32_t *refresh_stream);
 
 /* ---- multi-GPU (RCCL over xGMI) -------------------------------------------------------- */
 /* Rank 0 creates the 128-byte id, the host distributes it (torch.distributed broadcast,
@@ -398,7 +429,7 @@ int stan_hip_cg_solve_dev(stan_ctx *ctx, stan_matrix *K, const double *d_F, doub
  * NULL F / U, a K of another context.
  * The options that only pick between equivalent forms of the single solve (STAN_OPT_SPMV_VARIANT, STAN_OPT_SPMV_SMALL,
  * STAN_OPT_ROW_FOLDING, STAN_OPT_CG_FUSED_REFRESH, STAN_OPT_CG_LAZY_SCALING, STAN_OPT_CG_DEFER_X, STAN_OPT_VEC_STORE_NT,
- * STAN_OPT_CG_FOLD_REDUCE) select nothing here.  The batched loop has ONE form: the padded BSELL streams (packed
+ * STAN_OPT_CG_FOLD_REDUCE, STAN_OPT_CG_X_RING, STAN_OPT_CG_REFRESH_60) select nothing here.  The batched loop has ONE form: the padded BSELL streams (packed
  * columns when the context has them), one wavefront per slice with the non-temporal matrix stream and the XCD-chunked
  * mapping, the matrix scaled before the loop, reductions folded into their producers, the residual refresh as
  * alglib's literal second product A(x + a p).  With STAN_OPT_SPMV_SMALL = 0, STAN_OPT_CG_FUSED_REFRESH = 0 and

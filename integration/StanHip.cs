@@ -180,7 +180,7 @@ namespace STAN_Solver
                            STAN_OPT_PACKED_COLUMNS = 13, STAN_OPT_CG_DEFER_X = 14, STAN_OPT_SPMV_SMALL = 15,
                            STAN_OPT_PLACEMENT_MAX_BYTES = 16, STAN_OPT_SELL_SIGMA = 17, STAN_OPT_COMM_P2P = 18,
                            STAN_OPT_ROW_FOLDING = 19, STAN_OPT_CG_REFINE = 20, STAN_OPT_CG_LAZY_SCALING = 21,
-                           STAN_OPT_VALUE_STREAM_60 = 22;
+                           STAN_OPT_VALUE_STREAM_60 = 22, STAN_OPT_CG_X_RING = 23, STAN_OPT_CG_REFRESH_60 = 24;
 
         // ---- context
         [DllImport(Lib)] internal static extern int stan_hip_init(int device, out IntPtr ctx);
@@ -191,6 +191,7 @@ namespace STAN_Solver
         [DllImport(Lib)] internal static extern int stan_hip_set_stream(IntPtr ctx, IntPtr hip_stream);
         [DllImport(Lib)] internal static extern int stan_hip_set_option(IntPtr ctx, int option, long value);
         [DllImport(Lib)] internal static extern int stan_hip_pool_info(IntPtr ctx, out long bytes_parked, out long blocks_parked);
+        [DllImport(Lib)] internal static extern int stan_hip_cg_loop_info(IntPtr ctx, out int x_ring_window, out long x_ring_flushes, out int refresh_stream);
 
         // ---- several processes, one per GPU (a .NET host normally uses stan_hip_init_multi instead)
         [DllImport(Lib)] internal static extern int stan_hip_comm_unique_id([Out] byte[] id);

@@ -137,6 +137,8 @@ int stan_hip_set_option(stan_ctx *ctx, int32_t option, int64_t value) {
         }
     }
     else if (option == STAN_OPT_VALUE_STREAM_60 && value >= -1 && value <= 1) ctx->value_stream_60 = (int)value;
+    else if (option == STAN_OPT_CG_X_RING && value >= -1 && value <= 1) ctx->cg_x_ring = (int)value;
+    else if (option == STAN_OPT_CG_REFRESH_60 && value >= -1 && value <= 1) ctx->cg_refresh_60 = (int)value;
     else if (option == STAN_OPT_OVERLAP_HALO) ctx->overlap_halo = value != 0;
     else if (option == STAN_OPT_SELL_SIGMA && value >= 1 && value <= 32) ctx->sell_sigma = (int)value;
     else if (option == STAN_OPT_PLACEMENT_TRIES && value >= 1 && value <= 64) ctx->placement_tries = (int)value;
@@ -153,6 +155,15 @@ int stan_hip_pool_info(stan_ctx *ctx, int64_t *bytes_parked, int64_t *blocks_par
     if (ctx->group) ctx = stan_group_rank0(ctx);
     if (bytes_parked) *bytes_parked = (int64_t)ctx->pool.bytes_avail;
     if (blocks_parked) *blocks_parked = (int64_t)ctx->pool.avail.size();
+    return STAN_OK;
+}
+
+int stan_hip_cg_loop_info(stan_ctx *ctx, int32_t *x_ring_window, int64_t *x_ring_flushes, int32_t *refresh_stream) {
+    if (!ctx) return STAN_E_ARG;
+    if (ctx->group) ctx = stan_group_rank0(ctx);
+    if (x_ring_window) *x_ring_window = ctx->prof_x_ring_window;
+    if (x_ring_flushes) *x_ring_flushes = ctx->prof_x_ring_flushes;
+    if (refresh_stream) *refresh_stream = ctx->prof_refresh_stream;
     return STAN_OK;
 }
 

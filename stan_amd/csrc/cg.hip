@@ -28,6 +28,7 @@
 
 #include "internal.h"
 #include "s60.h"
+#include "x_ring.h"
 #include "p2p_device.h"
 #include "fx48.h"
 
@@ -243,8 +244,13 @@ unsigned launch_product(stan_ctx *ctx, stan_matrix *K, const product_plan &P, co
     fold.nblocks = grid;
     fold.np = (int)grid + poff;
     const colstream cs = colstream_of(ctx, K->pk, K->nslots);
-    if (s60) {   // one plain product with its p.Ap sum: k_spmv<s60_t, 1, 9 | 12>, nothing else is instantiated for this stream
+    if (s60) {   // one plain product with its p.Ap sum: k_spmv<s60_t, 1, 9 | 12>, or the fused refresh pass: k_spmv2<s60_t>; nothing else is instantiated for this stream
         const s60_t *vals = (const s60_t *)(a.vals ? a.vals : K->vs[a.kind].padded);
+        if (a.x2) {
+            hipLaunchKernelGGL((k_spmv2<s60_t>), dim3(grid), dim3(256), 0, stream, K->nslices, K->nloc, K->d_slot_ptr, K->d_rowof, K->d_cols,
+                               vals, a.x, a.x2, a.y, a.y2, a.partial, a.st, a.k, slist, nlist, poff, fold, cs);
+            return grid;
+        }
         auto launch = [&](auto var) {
             hipLaunchKernelGGL((k_spmv<s60_t, 1, decltype(var)::value>), dim3(grid), dim3(256), 0, stream, K->nslices, K->nloc, K->d_slot_ptr,
                                K->d_rowof, K->d_cols, vals, a.x, a.y, a.partial, a.st, a.k, slist, nlist, poff, fold, cs);
@@ -433,7 +439,15 @@ struct cg_run {
     bool reduced = false;             // the caller asked for a reduced-precision stream: fp64 check + refinement (every rank alike)
     uint32_t *pend60 = nullptr;       // the block of plan.stream60, allocated in setup() (the placement search needs the vectors idle); encoded -- and
                                       // handed to K -- in front of the first product that finds the values scaled (product())
-    int64_t n60 = 0;                  // products enqueued on it
+    int64_t n60 = 0;                  // plain products enqueued on it
+    bool refresh60 = false;           // STAN_OPT_CG_REFRESH_60: where the plain products read that stream the fused refresh passes do too (k_spmv2<s60_t>)
+    int refresh_stream = -1;          // the stream the last fused refresh pass read (-1: none ran)
+    // STAN_OPT_CG_X_RING (x_ring.h): W + 1 gather-length slots for the directions p_k (slot k mod (W + 1)) and as many doubles for
+    // the alphas, taken per solve in setup(); ring_w = 0: the loop as ever (x' formed by k_update every iteration)
+    int ring_w = 0;
+    double *ring = nullptr, *ring_alpha = nullptr;
+    int64_t ring_flushed = 0, n_flush = 0;   // the last term the enqueued flushes cover; flush launches
+    double *ring_slot(int64_t j) const { return ring + (int64_t)xring_slot(j, ring_w) * ng; }
     ~cg_run() { if (pend60) stan_dfree(ctx, pend60); }
     int refine = 0;                   // STAN_OPT_CG_REFINE, reduced-precision modes only
     int64_t n3 = 0, npad = 0, ng = 0, dof0 = 0;
@@ -516,8 +530,10 @@ struct cg_run {
             if (!K->vs[STAN_VALUE_STREAM_60].padded) plan.stream60_unavailable();
             STANCHK(rc);
         }
-        const bool s60 = plan.stream60 && !pend60 && !x2 && dot == 1 && !extra && !lazy_scale && kind == STAN_PREC_FP64;
-        if (s60) { kind = STAN_VALUE_STREAM_60; n60++; }
+        // the plain products, and -- STAN_OPT_CG_REFRESH_60 -- the fused refresh passes too: then no product inside the loop reads the fp64 block
+        const bool s60 = plan.stream60 && !pend60 && (!x2 || refresh60) && dot == 1 && !extra && !lazy_scale && kind == STAN_PREC_FP64;
+        if (s60) { kind = STAN_VALUE_STREAM_60; if (!x2) n60++; }
+        if (x2) refresh_stream = kind;
         span.begin(st_, k);
         auto go = [&](int which, hipStream_t s, bool last) -> unsigned {
             n_launch++;
@@ -556,6 +572,8 @@ struct cg_run {
     }
 
     int setup();
+    int setup_x_ring();
+    void flush_x_ring(int64_t k, int64_t last_enqueued);
     int begin_pass(bool from_F, double eps_pass, bool *done);
     int iterate(double eps_pass, int32_t max_its_pass);
     int pass(bool from_F, double eps_pass, int32_t max_its_pass);
@@ -602,6 +620,7 @@ int cg_run::setup() {
         STANCHK(folded_copy(STAN_PREC_FP64, true));   // (decides K->fold_state, touches no value)
         plan.fold_planned(K);
     }
+    refresh60 = ctx->cg_refresh_60 > 0 || (ctx->cg_refresh_60 < 0 && K->nb_glob > STREAM60_AUTO_ROWS);
     lazy_scale = plan.may_lazy_scale;
     if (lazy_scale) STANCHK(ensure_scale_vector(ctx, K));
     else STANCHK(ensure_scaled(ctx, K));
@@ -644,6 +663,7 @@ int cg_run::setup() {
     p2p_tab = p2p ? stan_p2p_table(ctx) : nullptr;
     vg = vec_grid(n3);
     its_before_restart = K->n_red > 0 ? K->n_red : 1;   // lincgcreate: ItsBeforeRestart = N (global reduced size)
+    STANCHK(setup_x_ring());
     // Sharded SpMV with the halo exchange hidden behind the interior slices: the slices whose
     // rows reference no halo column run on a side stream while the main stream packs, sends
     // and receives; the boundary slices follow on the main stream.  RCCL only ever sees the
@@ -660,6 +680,52 @@ int cg_run::setup() {
     return STAN_OK;
 }
 
+// The ring of directions (STAN_OPT_CG_X_RING): where the iteration defers x today -- the classic fp64 loop of one rank, merit
+// stop off, fused refresh, a refresh period other than 1 -- and, under -1, only above STREAM60_AUTO_ROWS block rows (a smaller
+// system's vectors live in the caches).  The ring is an extra of the solve, W + 1 vectors beside its eight: whether there is
+// room is decided before anything is allocated (a parked block that fits, or the block and as much again -- a sixteenth of
+// the device at least -- free), a block that cannot be had flushes no parked one, and without it the loop runs as ever.
+// ctx->ws is not touched: the products write v and w where the placement search left them.
+int cg_run::setup_x_ring() {
+    ring_w = 0;
+    ctx->prof_x_ring_window = 0;
+    ctx->prof_x_ring_flushes = 0;
+    const bool applies = precision_mode == STAN_PREC_FP64 && !dist && !sr && ctx->cg_defer_x && !ctx->cg_merit_stop &&
+                         ctx->cg_fused_refresh && ctx->cg_rupdate != 1 && n3 > 0;
+    if (!applies || ctx->cg_x_ring == 0 || (ctx->cg_x_ring < 0 && K->nb_glob <= STREAM60_AUTO_ROWS)) return STAN_OK;
+    const int W = xring_window(ctx->cg_rupdate);
+    const size_t bytes = (size_t)(W + 1) * (size_t)ng * 8;
+    const stan_pool &pool = ctx->pool;
+    bool room = false;
+    if (pool.enabled && bytes >= stan_pool::MIN_BYTES)
+        for (const stan_pool::blk &b : pool.avail) room = room || (b.cap >= bytes && b.cap <= bytes + bytes / 2);
+    if (!room) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return STAN_OK; }
+        room = free_b >= bytes + (bytes > total_b / 16 ? bytes : total_b / 16);
+    }
+    if (!room) return STAN_OK;
+    void *blk = nullptr;
+    if (stan_dmalloc_bytes(ctx, &blk, bytes, false) != STAN_OK) { ctx->err.clear(); return STAN_OK; }   // (fragmentation: room by the figures, no block)
+    bufs.p.push_back(blk);
+    ring = (double *)blk;
+    STANCHK(bufs.alloc(&ring_alpha, (size_t)(W + 1)));
+    ring_w = W;
+    // the pad behind the owned rows is gathered like everything else: zero, as p's
+    for (int s = 0; s <= W && ng > n3; s++) HIPCHK(ctx, hipMemsetAsync(ring + (int64_t)s * ng + n3, 0, (size_t)(ng - n3) * 8, st_));
+    return STAN_OK;
+}
+// k > 0: the flush in front of iteration k, covering the terms up to k - 1; k == 0: the closing flush behind the loop
+void cg_run::flush_x_ring(int64_t k, int64_t last_enqueued) {
+    xring_args a;
+    a.n3 = n3; a.ng = ng; a.k = k;
+    a.first = ring_flushed + 1; a.last = k - 1; a.last_enqueued = last_enqueued;
+    a.W = ring_w; a.ring = ring; a.alpha = ring_alpha; a.x = xb[0]; a.st = stt;
+    hipLaunchKernelGGL(k_xring_flush, dim3(vg), dim3(VEC_T), 0, st_, a);
+    n_launch++; n_flush++;
+    if (k > 0) ring_flushed = k - 1;
+}
+
 // ---- one pass of the loop ------------------------------------------------------------------------------------
 // Right-hand side, x0 = 0, r0 = p0 = b^, ||b^||, first residual test.  from_F: b^ = S F (the caller's load vector);
 // otherwise b^ = the vector in r (a refinement pass: the fp64 residual fp64_check left there).
@@ -668,7 +734,7 @@ int cg_run::begin_pass(bool from_F, double eps_pass, bool *done) {
         const fold_args f = vec_fold(sc + S_VMV, p2p_to(0, true));
         if (from_F)
             hipLaunchKernelGGL(k_init, dim3(vg), dim3(VEC_T), 0, st_, n3, dof0, K->d_red, d_F, K->d_scale,
-                               bh, xb[0], r, p, partial, f);
+                               bh, xb[0], r, ring_w ? ring_slot(1) : p, partial, f);
         else
             hipLaunchKernelGGL(k_init_b, dim3(vg), dim3(VEC_T), 0, st_, n3, (const double *)r, bh, xb[0], r, p, partial, f);
         reduce_if_unfolded((int)vg, 1, sc + S_VMV, p2p_to(0, true));
@@ -708,6 +774,10 @@ int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
     }
     // a sharded loop polls more often: what runs ahead of the stop are exchanges nobody can cut short
     const int chunk = dist ? CHUNK_DIST : CHUNK;
+    if (ring_w) {   // (setup_x_ring: one pass, the classic loop, every refresh a fused one)
+        ring_flushed = 0;
+        HIPCHK(ctx, hipMemsetAsync(stt + T_FLUSHED, 0, 8, st_));
+    }
     while (!done && rc == STAN_OK) {
         // enqueue one chunk of iterations
         for (int c = 0; c < chunk && k < chunk_poll::hard_cap; c++, k++) {
@@ -740,7 +810,11 @@ int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
                 continue;
             }
             const bool fused = refresh && ctx->cg_fused_refresh && !refresh64;
-            rc = product(p, fused ? xb[(k - 1) & 1] : nullptr, v, 1, sc + S_VMV, k, p2p_to(0, true), plan.vs);
+            // the ring: p_k sits in its slot, x in xb[0], brought up to x_{k-1} in front of the product that multiplies it
+            double *const pk = ring_w ? ring_slot(k) : p;
+            double *const xprev = ring_w ? xb[0] : xb[(k - 1) & 1];
+            if (ring_w && xring_flush_due(k, ring_flushed, ring_w, refresh)) flush_x_ring(k, 0);
+            rc = product(pk, fused ? xprev : nullptr, v, 1, sc + S_VMV, k, p2p_to(0, true), plan.vs);
             if (rc) break;
             rc = exchange_sums(sc + S_VMV, 1, &rs_vmv);
             if (rc) break;
@@ -749,7 +823,7 @@ int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
             a.rs_vmv = rs_vmv;
             a.n3 = n3; a.k = k; a.sc = sc; a.st = stt;
             a.xcur = xb[(k - 1) & 1]; a.xnext = xb[k & 1];
-            a.r = r; a.p = p; a.v = v; a.w = w; a.bh = bh; a.partial = partial;
+            a.r = r; a.p = pk; a.v = v; a.w = w; a.bh = bh; a.partial = partial;
             a.refresh = refresh ? (fused ? 2 : 1) : 0;
             a.merit = ctx->cg_merit_stop ? 1 : 0;
             // x' = x + a p moves into k_update (p is read once for both updates: -79 MB of 714 per
@@ -771,8 +845,14 @@ int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
             if (rc) break;
             const double *ux = a.defer_x ? a.xcur : nullptr;
             double *uxn = a.defer_x ? a.xnext : nullptr;
-            hipLaunchKernelGGL((ctx->vec_store_nt & 1) ? k_update<true> : k_update<false>, dim3(vg), dim3(VEC_T), 0, st_, n3, k, sc, stt,
-                               eps_pass, (int64_t)max_its_pass, its_before_restart, ctx->cg_merit_stop ? 1 : 0, r, p, ux, uxn, rs_r2, rs_vmv);
+            if (ring_w)   // p_{k+1} into the next slot, alpha_k next to the ring; x waits for the flush
+                hipLaunchKernelGGL(((ctx->vec_store_nt & 1) ? k_update<true, true> : k_update<false, true>), dim3(vg), dim3(VEC_T), 0, st_, n3, k, sc, stt,
+                                   eps_pass, (int64_t)max_its_pass, its_before_restart, 0, r, pk, (const double *)nullptr, (double *)nullptr,
+                                   rs_r2, rs_vmv, ring_slot(k + 1), ring_alpha + xring_slot(k, ring_w));
+            else
+                hipLaunchKernelGGL(((ctx->vec_store_nt & 1) ? k_update<true, false> : k_update<false, false>), dim3(vg), dim3(VEC_T), 0, st_, n3, k, sc, stt,
+                                   eps_pass, (int64_t)max_its_pass, its_before_restart, ctx->cg_merit_stop ? 1 : 0, r, p, ux, uxn, rs_r2, rs_vmv,
+                                   (double *)nullptr, (double *)nullptr);
             n_launch++;
         }
         if (rc) break;
@@ -792,13 +872,14 @@ int cg_run::iterate(double eps_pass, int32_t max_its_pass) {
     hipError_t e = hipStreamSynchronize(st_);
     if (rc) return rc;
     if (e != hipSuccess) { ctx->err = std::string("cg: ") + hipGetErrorString(e); return STAN_E_HIP; }
+    if (ring_w) flush_x_ring(0, k - 1);   // the closing flush: x in xb[0] becomes the iterate T_XSEL / T_ITERS name
     HIPCHK(ctx, hipMemcpyAsync(h_st, stt, T_NSTAT * 8, hipMemcpyDeviceToHost, st_));
     HIPCHK(ctx, hipMemcpyAsync(h_sc, sc, S_NSCAL * 8, hipMemcpyDeviceToHost, st_));
     HIPCHK(ctx, hipStreamSynchronize(st_));
     pass_type = (int)h_st[T_TYPE];
     pass_its = h_st[T_ITERS];
     if (pass_type == 0) { pass_type = 5; pass_its = k - 1; h_st[T_XSEL] = (k - 1) & 1; }  // hard cap
-    xfin = xb[h_st[T_XSEL] & 1];
+    xfin = ring_w ? xb[0] : xb[h_st[T_XSEL] & 1];
     return STAN_OK;
 }
 
@@ -868,6 +949,9 @@ int cg_run::finish(const double *x_result, int type, int64_t its, double rel_rec
     if (ctx->profiling) hipEventRecord(ev1, st_);
     HIPCHK(ctx, hipStreamSynchronize(st_));
 
+    ctx->prof_x_ring_window = ring_w;
+    ctx->prof_x_ring_flushes = n_flush;
+    ctx->prof_refresh_stream = refresh_stream;
     if (term_out) *term_out = type;
     if (iters_out) *iters_out = (int32_t)(its > chunk_poll::hard_cap ? chunk_poll::hard_cap : its);
     if (rel_res_out) *rel_res_out = rel64 >= 0 ? rel64 : rel_rec;
@@ -902,6 +986,8 @@ int cg_run::finish(const double *x_result, int type, int64_t its, double rel_rec
     // vector passes of one classic iteration: k_step reads r, v (+ p, x unless deferred; + b^ for the
     // merit sum) and writes r (+ x); k_update reads r, p (+ x when deferred) and writes p (+ x)
     pf.cg_iteration_vector_bytes = 3 * K->nloc * 8 * ((ctx->cg_defer_x && !ctx->cg_merit_stop ? 8 : 9) + (ctx->cg_merit_stop ? 1 : 0));
+    // the ring: k_update reads r, p and writes p (6 passes with k_step's 3), a flush per window reads W directions and x and writes x
+    if (ring_w) pf.cg_iteration_vector_bytes = 3 * K->nloc * 8 * (7 * (int64_t)ring_w + 2) / ring_w;
     pf.loop_kernel_launches = n_launch;
     pf.loop_collectives = n_coll;
     pf.loop_stream_waits = n_wait;

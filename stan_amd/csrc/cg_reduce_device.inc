@@ -15,7 +15,9 @@ enum { S_BNORM = 0, S_VMV = 1, S_R2NEW = 2, S_MERIT = 3, S_RHO0 = 4, S_RHO1 = 5,
        // fp64 check of a reduced-precision solve: ||b - A64 x||^2 and the merit sum of the same pass
        S_CHK_R2 = 16, S_CHK_MF = 17, S_NSCAL = 24 };
 // device status slots (int64)
-enum { T_ITER_A = 0, T_ITER_B = 1, T_TYPE = 2, T_ITERS = 3, T_XSEL = 4, T_NSTAT = 8 };
+enum { T_ITER_A = 0, T_ITER_B = 1, T_TYPE = 2, T_ITERS = 3, T_XSEL = 4,
+       T_FLUSHED = 5,   // STAN_OPT_CG_X_RING: the last term alpha_j p_j the iterate holds (k_xring_flush)
+       T_NSTAT = 8 };
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

@@ -118,12 +118,14 @@ k_refresh(int64_t n3, int64_t k, const int64_t *st, const double *bh, const doub
 }
 
 // decisions of the iteration + p = r + beta p
-template <bool PNT>
+// RING (STAN_OPT_CG_X_RING, x_ring.h): p is p_k in its slot of the ring and stays; p_{k+1} goes to `pnext`, the next slot, and
+// alpha_k to `alpha_out`, its place next to the ring.  x is not touched: k_xring_flush forms it once per window.
+template <bool PNT, bool RING>
 __global__ void __launch_bounds__(VEC_T)
 k_update(int64_t n3, int64_t k, double *sc, int64_t *st, double epsf, int64_t maxits,
          int64_t its_before_restart, int merit_stop, const double *r, double *p,
          const double *xcur, double *xnext /* non-null: the deferred x' = x + a p of this iteration */,
-         red_src rs_r2, red_src rs_vmv) {
+         red_src rs_r2, red_src rs_vmv, double *pnext, double *alpha_out) {
     __shared__ double sh[4];
     if (st[T_ITER_A] < k || st[T_ITER_B] <= k) return;
     double t2[2];
@@ -157,10 +159,22 @@ k_update(int64_t n3, int64_t k, double *sc, int64_t *st, double epsf, int64_t ma
     const int64_t stride = (int64_t)gridDim.x * VEC_T;
     // alpha of this iteration, as k_step formed it (same operands, same bits)
     double alpha = 0.0;
-    if (xnext) {   // block-uniform
+    if (RING || xnext) {   // block-uniform
         double v1[1];
         red_get<1>(sc + S_VMV, rs_vmv, v1, sh);
         alpha = rho / v1[0];
+    }
+    if constexpr (RING) {
+        // the term alpha_k p_k is pending from here on, whether the iteration stops (types 1, 5, -4 select x_k) or not
+        if (blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha;
+        if (type) return;
+        for (int64_t i = (int64_t)blockIdx.x * VEC_T + threadIdx.x; i < n3; i += stride) {
+            const double po = PNT ? vld_rmw(p + i) : p[i];
+            const double pn = (PNT ? vld_ro(r + i) : r[i]) + beta * po;
+            if (PNT) __builtin_nontemporal_store(pn, pnext + i);
+            else pnext[i] = pn;
+        }
+        return;
     }
     if (type) {
         // the iteration that stops (types 1, 5, -4 select x' = buffer k & 1) still owes its x'
@@ -180,6 +194,63 @@ k_update(int64_t n3, int64_t k, double *sc, int64_t *st, double epsf, int64_t ma
         else p[i] = pn;
         if (xnext) __builtin_nontemporal_store(vld_ro(xcur + i) + alpha * po, xnext + i);
     }
+}
+
+// ---- the iterate from the ring of directions (STAN_OPT_CG_X_RING, x_ring.h) ------------------------
+// x += the pending terms alpha_j p_j, j = first ... last, in iteration order: one fused multiply-add per term, as k_update
+// forms x' = x + alpha p one iteration at a time.  In front of a refresh iteration k (k > 0): the terms are the host's
+// (everything before k ran unless the solve has stopped: then nothing is done), and T_FLUSHED records the last one.
+// Closing (k == 0, behind the loop): the terms between T_FLUSHED and the iterate the status words name.
+struct xring_args {
+    int64_t n3, ng;         // owned length; length of a slot
+    int64_t k;              // the iteration this flush stands in front of; 0: the closing flush
+    int64_t first, last;    // k > 0: the terms
+    int64_t last_enqueued;  // k == 0: the last iteration of the loop (the hard cap's iterate)
+    int W;
+    const double *ring;     // [W + 1][ng]
+    const double *alpha;    // [W + 1]
+    double *x;
+    int64_t *st;
+};
+template <int N>
+__device__ __forceinline__ void xring_sum(const xring_args &a, int64_t first) {
+    const double *q[N];
+    double al[N];
+#pragma unroll
+    for (int m = 0; m < N; m++) {
+        const int s = xring_slot(first + m, a.W);
+        q[m] = a.ring + (int64_t)s * a.ng;
+        al[m] = a.alpha[s];
+    }
+    const int64_t stride = (int64_t)gridDim.x * VEC_T;
+    for (int64_t i = (int64_t)blockIdx.x * VEC_T + threadIdx.x; i < a.n3; i += stride) {
+        double pv[N];
+#pragma unroll
+        for (int m = 0; m < N; m++) pv[m] = __builtin_nontemporal_load(q[m] + i);
+        double x = __builtin_nontemporal_load(a.x + i);
+#pragma unroll
+        for (int m = 0; m < N; m++) x = __builtin_fma(al[m], pv[m], x);
+        __builtin_nontemporal_store(x, a.x + i);
+    }
+}
+__global__ void __launch_bounds__(VEC_T) k_xring_flush(xring_args a) {
+    int64_t first = a.first, last = a.last;
+    if (a.k > 0) {
+        if (stopped(a.st, a.k)) return;
+    } else {
+        first = a.st[T_FLUSHED] + 1;
+        last = xring_final_iterate(a.st[T_TYPE], a.st[T_ITERS], a.st[T_XSEL], a.last_enqueued);
+    }
+    const int64_t n = last - first + 1;   // <= W <= XRING_MAX_W (xring_flush_due)
+    if (n <= 0 || n > XRING_MAX_W) return;
+    switch ((int)n) {
+#define XRING_CASE(N) case N: xring_sum<N>(a, first); break;
+        XRING_CASE(1) XRING_CASE(2) XRING_CASE(3) XRING_CASE(4) XRING_CASE(5) XRING_CASE(6) XRING_CASE(7) XRING_CASE(8)
+        XRING_CASE(9) XRING_CASE(10) XRING_CASE(11) XRING_CASE(12) XRING_CASE(13) XRING_CASE(14) XRING_CASE(15) XRING_CASE(16)
+#undef XRING_CASE
+    }
+    // (read by the closing flush only: a later kernel)
+    if (a.k > 0 && blockIdx.x == 0 && threadIdx.x == 0) a.st[T_FLUSHED] = last;
 }
 
 // ---- single-reduction CG (Chronopoulos-Gear), STAN_OPT_CG_SINGLE_REDUCE --------------------------

@@ -262,6 +262,11 @@ struct stan_ctx {
     int prof_colours = 0;
     int spmv_variant = -1; // -1 = auto (plan_products picks per value stream); >= 0: A/B lab
     int value_stream_60 = -1;  // STAN_OPT_VALUE_STREAM_60: -1 = the fp64 loop of a large system on one rank streams the 60-bit values; 1 always where k_spmv runs; 0 never
+    int cg_x_ring = -1;        // STAN_OPT_CG_X_RING: where k_update defers x, x is formed once per refresh window from a ring of directions (x_ring.h); -1 = above 150 000 block rows; 1 always there; 0 never
+    int prof_x_ring_window = 0;        // last solve: the ring's window W (0: the loop formed x every iteration) ...
+    int64_t prof_x_ring_flushes = 0;   // ... and the flush launches it enqueued (stan_hip_cg_loop_info)
+    int cg_refresh_60 = -1;    // STAN_OPT_CG_REFRESH_60: where the plain products of a solve read the 60-bit stream its fused refresh passes do too; -1 = above 150 000 block rows; 1 always there; 0 never
+    int prof_refresh_stream = -1;      // last solve: the value stream its fused refresh passes read (-1: none ran)
     // profiling
     bool profiling = false;
     stan_profile prof{};

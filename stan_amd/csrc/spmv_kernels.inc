@@ -454,6 +454,10 @@ k_spmv_small(int32_t nslices, int64_t nloc, const int32_t *__restrict__ slot_ptr
 // refresh needs A x next to the A p every iteration needs -- one matrix stream instead of two.
 // 128-VGPR budget (4 waves per SIMD): with the default target the four gathers of a trip (x and x2 of two slots) were
 // issued one by one, each behind a wait for earlier data
+// VT = s60_t (STAN_OPT_CG_REFRESH_60): the same pass on the lossless 60-bit stream.  In the gfx950 code of k_spmv2<double>
+// every one of its row sums -- six per block, in each of the walk's block bodies (two per packed trip and the odd slot, two
+// per int32-column trip and its remainder) -- keeps a1 x1 (a1 u1) as the rounded multiplication and fuses a0 x0, then
+// a2 x2, onto it, as k_spmv does: s60_row spells exactly that out, for every position alike.
 template <typename VT>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 4)))
 k_spmv2(int32_t nslices, int64_t nloc, const int32_t *__restrict__ slot_ptr, const int32_t *__restrict__ rowof,
@@ -482,12 +486,21 @@ k_spmv2(int32_t nslices, int64_t nloc, const int32_t *__restrict__ slot_ptr, con
             x0 *= FX48_INV; x1 *= FX48_INV; xx2 *= FX48_INV;                          \
             u0 *= FX48_INV; u1 *= FX48_INV; u2 *= FX48_INV;                           \
         }                                                                             \
-        y0 += a[0] * x0 + a[1] * x1 + a[2] * xx2;                                     \
-        y1 += a[3] * x0 + a[4] * x1 + a[5] * xx2;                                     \
-        yy2 += a[6] * x0 + a[7] * x1 + a[8] * xx2;                                    \
-        z0 += a[0] * u0 + a[1] * u1 + a[2] * u2;                                      \
-        z1 += a[3] * u0 + a[4] * u1 + a[5] * u2;                                      \
-        z2 += a[6] * u0 + a[7] * u1 + a[8] * u2;                                      \
+        if constexpr (vstream<VT>::P60) {                                             \
+            y0 = s60_row(a[0], a[1], a[2], x0, x1, xx2, y0);                          \
+            y1 = s60_row(a[3], a[4], a[5], x0, x1, xx2, y1);                          \
+            yy2 = s60_row(a[6], a[7], a[8], x0, x1, xx2, yy2);                        \
+            z0 = s60_row(a[0], a[1], a[2], u0, u1, u2, z0);                           \
+            z1 = s60_row(a[3], a[4], a[5], u0, u1, u2, z1);                           \
+            z2 = s60_row(a[6], a[7], a[8], u0, u1, u2, z2);                           \
+        } else {                                                                      \
+            y0 += a[0] * x0 + a[1] * x1 + a[2] * xx2;                                 \
+            y1 += a[3] * x0 + a[4] * x1 + a[5] * xx2;                                 \
+            yy2 += a[6] * x0 + a[7] * x1 + a[8] * xx2;                                \
+            z0 += a[0] * u0 + a[1] * u1 + a[2] * u2;                                  \
+            z1 += a[3] * u0 + a[4] * u1 + a[5] * u2;                                  \
+            z2 += a[6] * u0 + a[7] * u1 + a[8] * u2;                                  \
+        }                                                                             \
     }
         walk_slots<true, 2, vstream<VT>::STRIDE>(cs, cols, slice, lane, k0, k0, k1, vals,
                                                  [&](int64_t c, const VT *vp) { STAN_SPMV2_BLOCK(c, vp) });

@@ -36,6 +36,8 @@ OPT_ROW_FOLDING = 19
 OPT_CG_REFINE = 20
 OPT_CG_LAZY_SCALING = 21
 OPT_VALUE_STREAM_60 = 22
+OPT_CG_X_RING = 23
+OPT_CG_REFRESH_60 = 24
 VALUE_STREAM_60 = 3   # Profile.value_stream of an fp64 solve whose plain products read the lossless 60-bit stream
 E_HIP, E_ARG, E_ALLOC, E_DETJ, E_DOF_LAYOUT, E_VALENCE, E_COMM, E_UNSUPPORTED = (
     -1, -2, -3, -4, -5, -6, -7, -8)
@@ -48,7 +50,7 @@ EXPORTS = [
     "stan_hip_ke_hex8_batch", "stan_hip_matrix_to_csr", "stan_hip_spmv", "stan_hip_spmv_bench", "stan_hip_stream_bench",
     "stan_hip_stream60_roundtrip",
     "stan_hip_set_profiling", "stan_hip_get_profile", "stan_hip_set_option", "stan_hip_recover_hex8", "stan_hip_recover_hex8_dev",
-    "stan_hip_nodal_forces_hex8", "stan_hip_pool_info",
+    "stan_hip_nodal_forces_hex8", "stan_hip_pool_info", "stan_hip_cg_loop_info",
     "stan_hip_matrix_plan", "stan_hip_spmv_local", "stan_hip_comm_info", "stan_hip_comm_library",
     "stan_hip_matrix_part_info", "stan_hip_get_profile_rank", "stan_hip_device_info", "stan_hip_matrix_diagonal",
     "stan_hip_recover_hex8_keep", "stan_hip_results_map", "stan_hip_results_free",
@@ -302,6 +304,17 @@ class Context:
         b, n = C.c_int64(0), C.c_int64(0)
         self._chk(self.lib.stan_hip_pool_info(self.h, C.byref(b), C.byref(n)))
         return b.value, n.value
+
+    def cg_loop_info(self):
+        """(window W, flush launches, refresh stream) of the last solve: W of OPT_CG_X_RING, 0 when the loop formed x every
+        iteration; the value stream its fused refresh passes read (OPT_CG_REFRESH_60), -1 when there were none."""
+        w, n, s = C.c_int32(0), C.c_int64(0), C.c_int32(-1)
+        self._chk(self.lib.stan_hip_cg_loop_info(self.h, C.byref(w), C.byref(n), C.byref(s)))
+        return w.value, n.value, s.value
+
+    def cg_x_ring_info(self):
+        """(window W, flush launches) of OPT_CG_X_RING in the last solve; W = 0: the loop formed x every iteration."""
+        return self.cg_loop_info()[:2]
 
     # -- multi-GPU -----------------------------------------------------------------
     def unique_id(self):
