@@ -924,7 +924,9 @@ int cg_run::fp64_check(double *xg, const double *b, double *r2_out) {
     HIPCHK(ctx, hipMemcpyAsync(h_sc, sc, S_NSCAL * 8, hipMemcpyDeviceToHost, st_));
     STANCHK(cg_wait(ctx, p2p, st_, nullptr));
     *r2_out = h_sc[S_CHK_R2];
-    spmv64_sp.drain(chunk_poll::hard_cap, &prof_spmv64_ms, &prof_spmv64_n);   // (every one: they carry the iteration of a refresh, or 0)
+    // the check itself (it carries iteration 0) and the refreshes of the pass behind it that did work: the host enqueues up to two
+    // chunks past the stop, and a refresh out there returns at once -- counted, it made fp64_products depend on the chunk size
+    spmv64_sp.drain(pass_its, &prof_spmv64_ms, &prof_spmv64_n);
     return STAN_OK;
 }
 

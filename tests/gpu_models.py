@@ -1,5 +1,6 @@
 """What the device tests of the products and of the CG loop share (tests/test_gpu_product_precision.py,
-tests/test_gpu_sharded_precision.py): the library's default options, a fresh assembly of a model of tests/product_ref.py on a
+tests/test_gpu_sharded_precision.py, tests/test_gpu_reduced_forms.py, tests/test_gpu_refinement_passes.py,
+tests/test_gpu_cg_restart.py): the library's default options and the block that sets some and puts them back, a fresh assembly of a model of tests/product_ref.py on a
 one-device context, the matrix it exports with its probes, and the long-double CG on that matrix -- each computed once per
 pytest run (product_ref.cached) and left unchanged."""
 from stan_amd import hip
@@ -7,7 +8,29 @@ from tests import product_ref as P
 
 DEFAULTS = {hip.OPT_CG_MERIT_STOP: 1, hip.OPT_SPMV_VARIANT: -1, hip.OPT_SPMV_SMALL: 1, hip.OPT_PACKED_COLUMNS: 1, hip.OPT_SELL_SIGMA: 1,
             hip.OPT_ROW_FOLDING: -1, hip.OPT_VALUE_STREAM_60: -1, hip.OPT_CG_FOLD_REDUCE: 1, hip.OPT_CG_FUSED_REFRESH: 1,
-            hip.OPT_CG_DEFER_X: 1, hip.OPT_CG_SINGLE_REDUCE: 0, hip.OPT_CG_REFINE: 1, hip.OPT_OVERLAP_HALO: 1, hip.OPT_COMM_P2P: 0}
+            hip.OPT_CG_DEFER_X: 1, hip.OPT_CG_SINGLE_REDUCE: 0, hip.OPT_CG_REFINE: 1, hip.OPT_OVERLAP_HALO: 1, hip.OPT_COMM_P2P: 0,
+            hip.OPT_CG_RUPDATE: 10, hip.OPT_CG_X_RING: -1}
+LARGE = {hip.OPT_SPMV_SMALL: 0}
+PADDED = {**LARGE, hip.OPT_ROW_FOLDING: 0}            # the padded streams: left to itself (-1) the library folds where that saves slots
+
+
+class options:
+    """Options set for a block, every one restored to its default behind it -- also when the block fails; profiling on inside."""
+
+    def __init__(self, ctx, opts):
+        self.ctx, self.opts = ctx, opts
+
+    def __enter__(self):
+        self.ctx.set_profiling(True)
+        for k, v in self.opts.items():
+            self.ctx.set_option(k, v)
+
+    def __exit__(self, *exc):
+        try:
+            for k in self.opts:
+                self.ctx.set_option(k, DEFAULTS[k])
+        finally:
+            self.ctx.set_profiling(False)
 
 
 def assemble(ctx, name, sigma=1):

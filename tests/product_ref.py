@@ -1,4 +1,4 @@
-"""Two instruments for the products (stan_amd/csrc/spmv_kernels.inc) and the CG loop (cg_vector_kernels.inc,
+"""Four instruments for the products (stan_amd/csrc/spmv_kernels.inc) and the CG loop (cg_vector_kernels.inc,
 cg_reduce_device.inc), and the yardsticks the device is held to.  Everything is observed through Matrix.spmv / to_csr /
 diagonal / scaled_residual and cg_solve / cg_solve_multi with max_its = k; nothing here asks the library for more.
 
@@ -19,6 +19,13 @@ diagonal / scaled_residual and cg_solve / cg_solve_multi with max_its = k; nothi
    rank_dot is the sum of a solve on several ranks (per-rank partials added in rank order), and cg_iterates /
    cg_single_reduce_f64 take it for every sum of the loop (dot=): the float64 loop as a sharded solve orders it, which
    tests/test_product_ref.py holds inside the one-rank bounds -- and the mutants of a halo exchange outside them.
+
+4. FROM THE DEVICE'S OWN ITERATE.  What happens late in a loop -- the restart every n_red iterations, the refinement pass behind
+   a converged first one -- is out of a replay's reach (a converged recurrence, or float64 and long double orders apart by
+   then).  one_step and refinement_pass take the iterate the device returned at max_its = k as exact data and predict in long
+   double what it must add next; the float64 restatement of the same construction is the yardstick, one rounding of the
+   iterate the floor (step_units, step_floor).  refine_driver_f64 restates the passes of stan_cg_device in float64: how many
+   there are and how far every stop decision is from its threshold.
 
 Row sums (row_units) are counted in units of 2^-53 sum_j |a_ij| |x_j|, the rounding scale of the row itself: a wrong entry
 in a row far below max|y| cannot hide there.  A row of m stored entries summed in ANY order, with or without fused
@@ -69,6 +76,29 @@ DEVICE_CG_FACTOR = 4
 KMAX_REDUCED = 12
 REDUCED_CG_UNITS_MEASURED = {("fixed48", "cube6"): (127.8, 65.4), ("fixed48", "perforated12"): (71.0, 39.0),
                              ("mixed", "cube6"): (8.2, 6.3), ("mixed", "perforated12"): (6.1, 1.8)}
+# The same pair for STAN_OPT_CG_SINGLE_REDUCE on a reduced stream: cg_single_reduce_f64(quantise=) against the same reference.
+REDUCED_SR_CG_UNITS_MEASURED = {("fixed48", "cube6"): (106.9, 66.4), ("fixed48", "perforated12"): (70.5, 10.2),
+                                ("mixed", "cube6"): (18.5, 32.7), ("mixed", "perforated12"): (32.5, 4.2)}
+# STAN_OPT_CG_REFINE 2 on the float32 stream, k = 48 .. 52: the float64 loop that refreshes on the fp64 values at iteration 50
+# (and never before) against the same loop in long double.  (U units, recurrence-residual units) per model.
+REFINE2_KS = (48, 49, 50, 51, 52)
+REFINE2_UNITS_MEASURED = {"cube6": (4590.0, 9.66e4), "perforated12": (7.9e4, 50.4)}
+# The second refinement pass of a float32 solve to REFINE_EPS, iterates 1 .. 12 behind the first pass's U_1 (refinement_pass in
+# float64 through added_f64, against long double), worst over k in units of 2^-53 max|S d_k|; and the iterations of the first
+# pass of the float64 stand-in.
+REFINE_EPS = 1e-10
+REFINE_KMAX = 12
+SECOND_PASS_UNITS_MEASURED = {"cube6": 2.16e8, "perforated12": 9.85e7}
+FIRST_PASS_ITS_MEASURED = {"cube6": 112, "perforated12": 322}
+# FIXED-48: the eps_f at which the float64 restatement of the driver (refine_driver_f64) takes exactly two passes on both
+# models with every stop decision a factor 1.01 from its threshold; (iterations of pass 1, of pass 2) on the oracle's matrix.
+REFINE_EPS_FIXED48 = 1e-12
+FIXED48_PASSES_MEASURED = {"cube6": (124, 2), "perforated12": (356, 60)}
+# The step behind the restart (one_step), float64 against long double through added_f64: (model, k) -> (yardstick, floor) in
+# units of 2^-53 max|d_ref|, STAN_OPT_CG_RUPDATE 6, the job's own load vector, the fp64 values.
+RESTART_RUPDATE = 6
+RESTART_CASES = (("cube1s", 1), ("cube2s", 1), ("cube2s", 2))        # (model, k / n_red)
+RESTART_STEP_UNITS_MEASURED = {("cube1s", 1): (1.89e5, 5.93e5), ("cube2s", 1): (1.94e5, 8.38e4), ("cube2s", 2): (1.58e7, 1.25e7)}
 
 # Roundings between a stored a_ij and the entry rebuilt from a product of the SCALED matrix, K x = S^-1 (A^ (S^-1 x))
 # (stan_spmv_reduced, cg_entries.inc), counted from the code: s_i s_j (1) and a_ij times it (2) in k_scale_matrix /
@@ -89,10 +119,19 @@ def star_job(k, layers=3, rings=2):
     return problem.make_job(xyz, conn, z0, np.ones((len(z0), 3)), top, np.tile([0.0, 10.0, 5.0], (len(top), 1)))
 
 
+def stretched_cube_job(n):
+    """problem.cube_job(n, jitter=0.1) with the coordinates stretched by (30, 1, 1/30): elements of aspect 900, a matrix on
+    which the loop is nowhere near converged after n_red iterations (12 for n = 1, 54 for n = 2) -- the models of the restart."""
+    j = problem.cube_job(n, jitter=0.1)
+    j.xyz = np.ascontiguousarray(j.xyz * np.array([30.0, 1.0, 1.0 / 30.0]))
+    return j
+
+
 # name -> (builder, cube size n or None).  The smallest models that reach each branch of the products: one slice of fewer than
 # 64 rows / a pair-kernel workgroup without a second slice (cube1, cube2); 17 slices with a ragged last one (cube6); packed
 # column modes 1 and 2 (cube20); mixed row lengths and odd slot counts (perforated12); rows of 75 blocks (star12); 1 077
-# slices, one full 256-workgroup window of the XCD-chunked mapping plus its ragged tail (cube40).
+# slices, one full 256-workgroup window of the XCD-chunked mapping plus its ragged tail (cube40); 12 and 54 equations on
+# which the restart of the loop every n_red iterations acts on an unconverged recurrence (cube1s, cube2s).
 _BUILDERS = {
     "cube1": (lambda: problem.cube_job(1), 1),
     "cube2": (lambda: problem.cube_job(2), 2),
@@ -101,6 +140,8 @@ _BUILDERS = {
     "perforated12": (lambda: problem.perforated_job(12, 0.4), None),
     "star12": (lambda: star_job(12, rings=1), None),
     "cube40": (lambda: problem.cube_job(40), 40),
+    "cube1s": (lambda: stretched_cube_job(1), 1),
+    "cube2s": (lambda: stretched_cube_job(2), 2),
 }
 _jobs = {}
 
@@ -320,14 +361,19 @@ def _dot(a, b):
     return (a * b).sum()
 
 
-def cg_iterates(A, F, kmax, rupdate=10, pap=None, late_beta=False, mv=None, dot=_dot):
+def cg_iterates(A, F, kmax, rupdate=10, pap=None, late_beta=False, mv=None, dot=_dot, refresh_with=None, restart=0, b=None, stop=None):
     """The classic loop of stan_oracle_cg_opt (merit stop off) on the Scaled matrix A in A's number type:
     [(U_k, sqrt(r_k . r_k) / ||b^||) for k = 1 .. kmax].  dot(a, b): every sum of the loop (rho, r . r, ||b^||^2, p . A p) --
     rank_dot() for the order of a sharded solve; pap(p, v): the sum p . A p alone (default: dot); late_beta: beta from the rho
-    of one iteration earlier; mv: another product -- the hooks of the mutants."""
+    of one iteration earlier; mv: another product -- the hooks of the mutants.  refresh_with(x): the product of the refresh
+    iterations alone (STAN_OPT_CG_REFINE 2: the fp64 values behind a loop on a reduced stream); restart: beta = 0 behind
+    every restart-th iteration (lincg's ItsBeforeRestart = n_red; 0: never, which is the loop of every model whose compared
+    iterates end before n_red); b: the scaled right-hand side itself instead of S F (a refinement pass iterates on r_t); stop:
+    the loop ends behind the first iterate with sqrt(r . r) <= stop ||b^|| (the driver's stand-in)."""
     mv = A.mv if mv is None else mv
     pap = dot if pap is None else pap
-    b = A.rhs(F)
+    refresh_with = mv if refresh_with is None else refresh_with
+    b = A.rhs(F) if b is None else b
     x, r = np.zeros_like(b), b.copy()
     p = r.copy()
     rho = dot(r, r)
@@ -338,10 +384,14 @@ def cg_iterates(A, F, kmax, rupdate=10, pap=None, late_beta=False, mv=None, dot=
         v = mv(p)
         alpha = rho / pap(p, v)
         x = x + alpha * p
-        r = b - mv(x) if rupdate and k % rupdate == 0 else r - alpha * v
+        r = b - refresh_with(x) if rupdate and k % rupdate == 0 else r - alpha * v
         r2 = dot(r, r)
         out.append((A.s * x, np.sqrt(r2) / bnorm))
+        if stop is not None and out[-1][1] <= stop:
+            break
         beta = r2 / (rho_before if late_beta else rho)
+        if restart and k % restart == 0:
+            beta = beta * 0
         rho_before, rho = rho, r2
         p = r + beta * p
     return out
@@ -353,14 +403,15 @@ def cg_reference(csr, F, kmax, rupdate=10, quantise=None):
     return [u for u, _r in its], [r for _u, r in its]
 
 
-def cg_single_reduce_f64(csr, F, kmax, rupdate=10, dot=_dot):
+def cg_single_reduce_f64(csr, F, kmax, rupdate=10, dot=_dot, quantise=None, restart=0):
     """The Chronopoulos-Gear recurrences as the comment block of cg_vector_kernels.inc states them, in plain float64 numpy:
       w_k = A r_k, gamma_k = r_k . r_k, delta_k = r_k . w_k
       beta_k = gamma_k / gamma_{k-1}, p_k . A p_k = delta_k - beta_k gamma_k / alpha_{k-1}, alpha_k = gamma_k / p_k . A p_k
       p = r + beta p, s = w + beta s, x' = x + alpha p, r' = r - alpha s      (refresh iterations: r' = b^ - A x')
     Returns [(U_k, sqrt(gamma_k) / ||b^||)] with gamma_k the sum the product behind iteration k forms.  dot(a, b): every sum
-    (||b^||^2, gamma, delta), as in cg_iterates."""
-    A = Scaled(*csr, T=np.float64)
+    (||b^||^2, gamma, delta), as in cg_iterates; quantise: the reduced-precision stream the products read (Scaled); restart:
+    beta = 0 -- p = r, s = w, alpha = gamma / delta -- in the iteration behind every restart-th one, as k_vec_sr has it."""
+    A = Scaled(*csr, T=np.float64, quantise=quantise)
     b = A.rhs(F)
     x, r, p, s = np.zeros_like(b), b.copy(), np.zeros_like(b), np.zeros_like(b)
     bnorm = np.sqrt(dot(b, b))
@@ -371,7 +422,7 @@ def cg_single_reduce_f64(csr, F, kmax, rupdate=10, dot=_dot):
         gamma, delta = dot(r, r), dot(r, w)
         if k > 1:
             out.append((A.s * x, np.sqrt(gamma) / bnorm))
-        if k == 1:
+        if k == 1 or (restart and (k - 1) % restart == 0):
             beta, pap = 0.0, delta
         else:
             beta = gamma / gamma_prev
@@ -383,6 +434,102 @@ def cg_single_reduce_f64(csr, F, kmax, rupdate=10, dot=_dot):
         r = b - A.mv(x) if rupdate and k % rupdate == 0 else r - alpha * s
         gamma_prev, alpha_prev = gamma, alpha
     return out
+
+
+# ---- instruments that start from an iterate the DEVICE returned ------------------------------------------------------------------
+# A replay of the whole loop cannot test what happens late in it: by then the recurrence has converged, or float64 and long
+# double have drifted apart by orders.  These take the iterate U the device returned at max_its = k as exact data and predict,
+# in long double, what the device must add to it next; the float64 restatement of the same construction is the yardstick.
+# A difference d of two returned iterates is counted in units of 2^-53 max|d_ref| (step_units) and cannot be resolved below
+# the rounding of the iterates themselves: step_floor = max|U| / max|d_ref| units.
+
+def one_step(csr, F, U, quantise=None, T=LD):
+    """S (alpha r) with x = U / s, r = b^ - A^ x, alpha = r.r / r.A^ r: the whole step of the iteration behind a restart
+    (beta = 0: p = r) that is also a refresh iteration (r = b^ - A^ x).  (step, ||r|| / ||b^||)."""
+    A = Scaled(*csr, T=T, quantise=quantise)
+    b = A.rhs(F)
+    r = b - A.mv(np.asarray(U, dtype=np.float64).astype(T) / A.s)
+    rr = _dot(r, r)
+    return A.s * (rr / _dot(r, A.mv(r)) * r), np.sqrt(rr / _dot(b, b))
+
+
+def added_f64(U, step):
+    """fl(U + step) - U in float64: what two returned iterates can show of a step (the yardsticks go through it)."""
+    U = np.asarray(U, dtype=np.float64)
+    return (U + np.asarray(step, dtype=np.float64)) - U
+
+
+def step_units(d, d_ref):
+    """max|d - d_ref| in units of 2^-53 max|d_ref|."""
+    d = np.asarray(d, dtype=np.float64)
+    assert np.isfinite(d).all() and d.shape == d_ref.shape
+    return float(abs(d.astype(LD) - d_ref).max() / abs(d_ref).max() / U53)
+
+
+def step_floor(U, d_ref):
+    """max|U| / max|d_ref|: one rounding of the iterate in the units of step_units."""
+    return float(abs(np.asarray(U, dtype=np.float64)).max() / abs(d_ref).max())
+
+
+def refinement_pass(csr, F, U1, kmax, quantise, T=LD, rhs_quantise=None, loop_quantise="same", rupdate=10):
+    """The pass of iterative refinement behind the iterate U1 (stan_cg_device): r_t = b^ - A^64 (U1 / s) with the fp64 values,
+    then the loop from x = 0 on the right-hand side r_t with the reduced stream's values: [S d_k for k = 1 .. kmax], and
+    ||r_t|| / ||b^||.  The hooks of the mutants: rhs_quantise -- r_t formed with those values instead of the fp64 ones;
+    loop_quantise -- the loop's values (None: the fp64 matrix), "same": quantise."""
+    A64 = Scaled(*csr, T=T, quantise=rhs_quantise)
+    Aq = Scaled(*csr, T=T, quantise=quantise if loop_quantise == "same" else loop_quantise)
+    b0 = A64.rhs(F)
+    rt = b0 - A64.mv(np.asarray(U1, dtype=np.float64).astype(T) / A64.s)
+    its = cg_iterates(Aq, None, kmax, rupdate, b=rt)
+    return [u for u, _r in its], np.sqrt(_dot(rt, rt) / _dot(b0, b0))
+
+
+def first_pass_f64(csr, F, eps, quantise, cap=2000, rupdate=10):
+    """The float64 stand-in of the first pass of a reduced-precision solve: the loop on the quantised matrix until
+    sqrt(r.r) <= eps ||b^||.  (n1, [rel_k for k = 1 .. n1], U_n1)."""
+    A = Scaled(*csr, T=np.float64, quantise=quantise)
+    its = cg_iterates(A, F, cap, rupdate, stop=eps)
+    assert its[-1][1] <= eps
+    return len(its), [float(r) for _u, r in its], its[-1][0]
+
+
+def refine_driver_f64(csr, F, eps_f, quantise, max_passes=8, cap=5000, rupdate=10):
+    """stan_cg_device's passes (STAN_OPT_CG_REFINE 1, no iteration limit) restated in float64: the loop on the quantised matrix
+    until sqrt(r.r) <= eps_pass ||b_pass||, the fp64 check rel64 = ||b^ - A^64 x|| / ||b^||, x the sum of the passes' iterates,
+    the next pass on r_t with eps_pass = eps_f / rel64; it ends when rel64 <= eps_f, when rel64 has not halved, or after
+    max_passes.  One dict per pass: its, the loop's residual at its stop and one iteration earlier over eps_pass (stop, before:
+    how far both decisions of the loop are from their threshold), rel64 / eps_f behind it (check), U = S x."""
+    A64, Aq = Scaled(*csr, T=np.float64), Scaled(*csr, T=np.float64, quantise=quantise)
+    b0 = A64.rhs(F)
+    bn0 = np.sqrt(_dot(b0, b0))
+    x, b, eps_pass, prev, out = np.zeros_like(b0), b0, eps_f, None, []
+    while True:
+        its = cg_iterates(Aq, None, cap, rupdate, b=b, stop=eps_pass)
+        assert its[-1][1] <= eps_pass
+        x = x + its[-1][0] / Aq.s
+        rt = b0 - A64.mv(x)
+        rel64 = float(np.sqrt(_dot(rt, rt)) / bn0)
+        out.append(dict(its=len(its), stop=float(its[-1][1] / eps_pass), before=float(its[-2][1] / eps_pass) if len(its) > 1 else np.inf,
+                        check=rel64 / eps_f, U=A64.s * x))
+        if rel64 <= eps_f or len(out) >= max_passes or (prev is not None and not rel64 < 0.5 * prev):
+            return out
+        prev, b, eps_pass = rel64, rt, eps_f / rel64
+
+
+def two_passes_clear_of_thresholds(passes, factor=1.01):
+    """Exactly two passes of refine_driver_f64, every decision `factor` away from its threshold: each loop stops below
+    eps_pass / factor having stood above factor eps_pass one iteration earlier; rel64 misses eps_f by the factor behind the
+    first pass and meets it by the factor behind the second."""
+    return (len(passes) == 2 and all(p["stop"] <= 1 / factor and p["before"] >= factor for p in passes) and
+            passes[0]["check"] >= factor and passes[1]["check"] <= 1 / factor)
+
+
+def rel64_of(csr, F, U, T=LD):
+    """||b^ - A^64 (U / s)|| / ||b^||, the residual the fp64 check of a reduced-precision solve reports."""
+    A = Scaled(*csr, T=T)
+    b = A.rhs(F)
+    r = b - A.mv(np.asarray(U, dtype=np.float64).astype(T) / A.s)
+    return float(np.sqrt(_dot(r, r) / _dot(b, b)))
 
 
 # ---- the sharded loop -----------------------------------------------------------------------------------------------------------

@@ -22,12 +22,10 @@ import pytest
 
 from stan_amd import hip
 from tests import product_ref as P
-from tests.gpu_models import DEFAULTS, assemble as _assemble, model as _model, reduced_reference, reference as _reference
+from tests.gpu_models import LARGE, PADDED, assemble as _assemble, model as _model, options as _options, reduced_reference, reference as _reference
 
 pytestmark = pytest.mark.gpu
 
-LARGE = {hip.OPT_SPMV_SMALL: 0}
-PADDED = {**LARGE, hip.OPT_ROW_FOLDING: 0}            # the padded streams: left to itself (-1) the library folds where that saves slots
 # form -> options: what launch_product (cg.hip) routes a plain fp64 product to
 FORMS = {
     "small": {},                                                    # k_spmv_small<double, 0>
@@ -42,25 +40,6 @@ FRESH_CASES = ([(m, f, 1) for m in P.SPMV_MODELS for f in FRESH_FORMS] + [("cube
                [("perforated12", "small", 32), ("perforated12", "v9", 32)])        # sigma 32: the SELL-C-sigma permutation (rowof)
 SCALED_CASES = [(m, f) for m in P.SPMV_MODELS for f in FRESH_FORMS] + [("perforated12", "fold"), ("star12", "fold")]
 R = P.SCALED_PATH_ROUNDINGS
-
-
-class _options:
-    """Options set for a block, every one restored to its default behind it; profiling on inside."""
-
-    def __init__(self, ctx, opts):
-        self.ctx, self.opts = ctx, opts
-
-    def __enter__(self):
-        self.ctx.set_profiling(True)
-        for k, v in self.opts.items():
-            self.ctx.set_option(k, v)
-
-    def __exit__(self, *exc):
-        try:
-            for k in self.opts:
-                self.ctx.set_option(k, DEFAULTS[k])
-        finally:
-            self.ctx.set_profiling(False)
 
 
 def _same_export(K, csr):

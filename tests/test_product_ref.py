@@ -441,3 +441,168 @@ def test_sharded_mutants_exceed_the_bounds(oracle, built_libs, name, nranks):
         assert first == k_stated and stays, label
     print("%s on %d ranks, (d) under load case 0: first caught at k = %s" % (name, nranks, late))
     assert all(k is not None for k in late) and max(late) > 1
+
+
+# ---- the reduced streams in the single-reduction loop, REFINE 2, the refinement passes, the restart ----------------------------------
+# (tests/test_gpu_reduced_forms.py, tests/test_gpu_refinement_passes.py, tests/test_gpu_cg_restart.py)
+
+def _one_of_nine(csr):
+    mask = (P.rows_of(csr[0]) % 3 == 0) & (csr[1] % 3 == 1)
+    assert mask.sum() * 9 == csr[2].shape[0]
+    return mask
+
+
+@pytest.mark.parametrize("name", P.CG_MODELS)
+@pytest.mark.parametrize("stream", list(P.QUANTISE))
+def test_reduced_single_reduction_yardstick_and_the_decode_mutant(oracle, name, stream):
+    """The Chronopoulos-Gear restatement on the quantised matrix (cg_single_reduce_f64(quantise=)) against the long-double CG on
+    the matrix quantised from long-double entries: within a factor of two of the recorded constant both ways, and with one
+    entry of nine off by 2^-30 over 4 x it in U and in the residual by k = 3."""
+    j, _A, csr = _model(oracle, name)
+    q = P.QUANTISE[stream]
+    Us, rels = P.cg_reference(csr, j.F, P.KMAX_REDUCED, quantise=q)
+    wu, wr = _worst(P.cg_single_reduce_f64(csr, j.F, P.KMAX_REDUCED, quantise=q), Us, rels)
+    ru, rr = P.REDUCED_SR_CG_UNITS_MEASURED[stream, name]
+    print("%s %s: single-reduction float64 loop U %.1f / residual %.1f units (recorded %.1f / %.1f)" % (name, stream, wu, wr, ru, rr))
+    assert _within_a_factor_of_two(wu, ru) and _within_a_factor_of_two(wr, rr)
+    bump = np.where(_one_of_nine(csr), 2.0 ** -30, 0.0)
+    its = P.cg_single_reduce_f64(csr, j.F, 3, quantise=lambda a: q(a) + bump)
+    u, r = P.u_units(its[2][0], Us[2]), P.res_units(its[2][1], rels[2])
+    print("%s %s: one entry of nine off by 2^-30: U %.3g / residual %.3g units at k = 3" % (name, stream, u, r))
+    assert u > P.DEVICE_CG_FACTOR * ru and r > P.DEVICE_CG_FACTOR * rr
+
+
+@pytest.mark.parametrize("name", P.CG_MODELS)
+def test_refine2_yardstick_and_the_refresh_on_the_reduced_values(oracle, name):
+    """STAN_OPT_CG_REFINE 2 on the float32 stream: the loop that refreshes at iteration 50 and not before, with b^ - A^64 x there.
+    The float64 restatement against long double at k = 48 .. 52 stays within a factor of two of its recorded figures; no
+    compared iterate sits on a converged recurrence; and the mutant -- the refresh at 50 formed with the REDUCED values, what
+    REFINE 1 does -- is the same bits up to 49 and exceeds 4 x the yardstick at k = 51 and 52 in U, and from k = 50 in the
+    recurrence residual, which is why the device test asserts both.  FIXED-48: the two references themselves are closer than
+    the yardstick in U (printed), so no iterate comparison can tell the two refreshes apart; the device test counts products."""
+    j, _A, csr = _model(oracle, name)
+    for stream in ("mixed", "fixed48"):
+        q = P.QUANTISE[stream]
+        AqL, A64L = P.Scaled(*csr, T=P.LD, quantise=q), P.Scaled(*csr, T=P.LD)
+        Aq, A64 = P.Scaled(*csr, T=np.float64, quantise=q), P.Scaled(*csr, T=np.float64)
+        ref = P.cg_iterates(AqL, j.F, 52, rupdate=50, refresh_with=A64L.mv)
+        other = P.cg_iterates(AqL, j.F, 52, rupdate=50)
+        yard = P.cg_iterates(Aq, j.F, 52, rupdate=50, refresh_with=A64.mv)
+        mutant = P.cg_iterates(Aq, j.F, 52, rupdate=50)
+        ks = [k - 1 for k in P.REFINE2_KS]
+        yu, yr = max(P.u_units(yard[k][0], ref[k][0]) for k in ks), max(P.res_units(yard[k][1], ref[k][1]) for k in ks)
+        mu = {k + 1: P.u_units(mutant[k][0], ref[k][0]) for k in ks}
+        mr = {k + 1: P.res_units(mutant[k][1], ref[k][1]) for k in ks}
+        apart = {k + 1: P.u_units(np.asarray(other[k][0], dtype=np.float64), ref[k][0]) for k in (50, 51)}
+        print("%s %s: REFINE 2 yardstick U %.3g / residual %.3g units; refresh on the reduced values: U %s, residual %s; the two "
+              "references apart by %s; residual at k = 52: %.2e" % (name, stream, yu, yr, {k: "%.3g" % v for k, v in mu.items()},
+                                                                    {k: "%.3g" % v for k, v in mr.items()}, {k: "%.3g" % v for k, v in apart.items()}, float(ref[51][1])))
+        assert float(min(r for _u, r in ref)) > 1e-6
+        if stream == "fixed48":
+            assert max(apart.values()) < yu                      # nothing to tell apart
+            continue
+        ru, rr = P.REFINE2_UNITS_MEASURED[name]
+        assert _within_a_factor_of_two(yu, ru) and _within_a_factor_of_two(yr, rr)
+        assert all(np.array_equal(mutant[k][0], yard[k][0]) for k in range(49))
+        assert mu[51] > P.DEVICE_CG_FACTOR * yu and mu[52] > P.DEVICE_CG_FACTOR * yu
+        assert all(mr[k] > P.DEVICE_CG_FACTOR * yr for k in (50, 51, 52))
+
+
+@pytest.mark.parametrize("name", P.CG_MODELS)
+def test_second_pass_yardstick_its_condition_and_mutants(oracle, name):
+    """The refinement passes of a float32 solve to 1e-10.  CONDITION: at the first pass's stop n1 and one iteration earlier the
+    float64 stand-in's residual is at least 1 % from eps (measured: 3 % on perforated12, 15 % on cube6).  That makes n1 the
+    device's on cube6, where no order of the sums moves the third digit; on perforated12, 322 iterations in, the order of the
+    sums alone moves the residual at the stop between 0.93 and 0.98 eps and long double stops at 320: the device may read 322
+    or 323, and its test takes n1 from the device.  The second
+    pass from the stand-in's U_1: the float64 restatement (r_t and the loop in float64, fl(U_1 + S d_k) - U_1) against long
+    double stays within a factor of two of its recorded figure, and at 4 x it
+      r_t formed with the reduced values (the pass would iterate on its own recurrence's residual) is over at every k,
+      a pass that iterates on the fp64 matrix is over at k = 10 and 12 (it starts out inside: one step barely tells),
+      a dropped k_accumulate (U = S d_k alone) is over at every k."""
+    j, _A, csr = _model(oracle, name)
+    q = P.QUANTISE["mixed"]
+    n1, rels, U1 = P.first_pass_f64(csr, j.F, P.REFINE_EPS, q)
+    margins = [abs(r / P.REFINE_EPS - 1) for r in rels[-2:]]
+    rel64 = P.rel64_of(csr, j.F, U1)
+    print("%s: first pass %d iterations, |rel / eps - 1| before / at the stop %.3f / %.3f, rel64 %.3e" % (name, n1, margins[0], margins[1], rel64))
+    assert n1 == P.FIRST_PASS_ITS_MEASURED[name] and min(margins) >= 0.01 and rel64 > 1.01 * P.REFINE_EPS
+    # what that margin is worth: the same loop with its sums formed in 64 and in 256 chunks, and in long double
+    Aq = P.Scaled(*csr, T=np.float64, quantise=q)
+    chunked = {c: P.cg_iterates(Aq, j.F, 2 * n1, stop=P.REFINE_EPS, dot=P.rank_dot(np.arange(j.n_red) * c // j.n_red, c)) for c in (64, 256)}
+    n1_ld = len(P.cg_iterates(P.Scaled(*csr, T=P.LD, quantise=q), j.F, 2 * n1, stop=P.REFINE_EPS))
+    print("%s: residual over eps at the stop with the sums in 64 / 256 chunks: %s; long double stops at %d" %
+          (name, ", ".join("%.3f at %d" % (its[-1][1] / P.REFINE_EPS, len(its)) for its in chunked.values()), n1_ld))
+    assert all(abs(len(its) - n1) <= 1 for its in chunked.values()) and abs(n1_ld - n1) <= 2
+    ref, _rt = P.refinement_pass(csr, j.F, U1, P.REFINE_KMAX, q)
+    units = lambda ds: [P.step_units(P.added_f64(U1, d), ref[k]) for k, d in enumerate(ds)]      # noqa: E731
+    yard = units(P.refinement_pass(csr, j.F, U1, P.REFINE_KMAX, q, T=np.float64)[0])
+    reduced_rt = units(P.refinement_pass(csr, j.F, U1, P.REFINE_KMAX, q, T=np.float64, rhs_quantise=q)[0])
+    fp64_loop = units(P.refinement_pass(csr, j.F, U1, P.REFINE_KMAX, q, T=np.float64, loop_quantise=None)[0])
+    dropped = [P.step_units(d - U1, ref[k]) for k, d in enumerate(P.refinement_pass(csr, j.F, U1, P.REFINE_KMAX, q, T=np.float64)[0])]
+    bound = P.DEVICE_CG_FACTOR * max(yard)
+    print("%s: second pass yardstick %.3g units (recorded %.3g); r_t from the reduced values %.3g .. %.3g, fp64 loop %.3g .. %.3g, "
+          "dropped accumulate %.3g .. %.3g; max|S d_k| / max|U_1| %.2e .. %.2e" %
+          (name, max(yard), P.SECOND_PASS_UNITS_MEASURED[name], min(reduced_rt), max(reduced_rt), min(fp64_loop), max(fp64_loop),
+           min(dropped), max(dropped), float(abs(ref[0]).max() / abs(U1).max()), float(abs(ref[-1]).max() / abs(U1).max())))
+    assert _within_a_factor_of_two(max(yard), P.SECOND_PASS_UNITS_MEASURED[name])
+    assert min(reduced_rt) > bound and min(dropped) > bound
+    assert fp64_loop[9] > bound and fp64_loop[11] > bound
+
+
+@pytest.mark.parametrize("name", P.CG_MODELS)
+def test_fixed48_driver_takes_two_passes_away_from_every_threshold(oracle, name):
+    """FIXED-48 at eps_f = REFINE_EPS_FIXED48: the float64 restatement of the driver takes exactly two passes, and every stop
+    decision -- the loop's residual at each pass's stop and one iteration earlier against eps_pass, the fp64 check behind each
+    pass against eps_f -- is a factor 1.01 from its threshold.  (The iterates of the second pass are not compared on the
+    device: rel64 behind pass 1 is 2e-12 and max|S d| / max|U_1| 4e-14, a few hundred units of 2^-53 of U_1 -- rounding noise.)"""
+    j, _A, csr = _model(oracle, name)
+    passes = P.refine_driver_f64(csr, j.F, P.REFINE_EPS_FIXED48, P.QUANTISE["fixed48"])
+    print("%s: %s" % (name, [(p["its"], round(p["stop"], 3), round(p["before"], 3), round(p["check"], 3)) for p in passes]))
+    assert tuple(p["its"] for p in passes) == P.FIXED48_PASSES_MEASURED[name]
+    assert P.two_passes_clear_of_thresholds(passes)
+
+
+@pytest.mark.parametrize("name,mult", P.RESTART_CASES)
+def test_one_step_instrument_sees_a_loop_without_the_restart(oracle, name, mult):
+    """The restart every n_red iterations (k_update: beta stays 0 when k % its_before_restart == 0), on the stretched cubes
+    under STAN_OPT_CG_RUPDATE 6, where k = n_red is a refresh iteration too: the step behind it is S (alpha r) with r = b^ - A^
+    x_k, whatever came before (P.one_step, from the loop's own U_k).  CONDITION: the true residual at U_k is above 1e-4 (on
+    cube1 / cube2 the recurrence has converged by n_red and the step is below rounding).  The float64 loop WITH the restart
+    stays inside 4 x max(yardstick, floor) -- on the fp64 values, both reduced streams, the three load vectors and in the
+    single-reduction recurrences (k_vec_sr restarts in the iteration behind, (k - 1) % n_red == 0) -- and the loop WITHOUT it
+    (k = n_red only: by 2 n_red that loop has converged) exceeds the bound by a factor of 1e6 and more (measured: 1e10)."""
+    j, _A, csr = _model(oracle, name)
+    n, ru = j.n_red, P.RESTART_RUPDATE
+    k = mult * n
+    assert n % ru == 0 and n == {"cube1s": 12, "cube2s": 54}[name]
+
+    def figures(U_k, U_next, F, q):
+        d_ref, true_res = P.one_step(csr, F, U_k, quantise=q)
+        yard = P.step_units(P.added_f64(U_k, P.one_step(csr, F, U_k, quantise=q, T=np.float64)[0]), d_ref)
+        return P.step_units(U_next - U_k, d_ref), yard, P.step_floor(U_k, d_ref), float(true_res)
+
+    for stream, q in [("fp64", None)] + list(P.QUANTISE.items()):
+        A = P.Scaled(*csr, T=np.float64, quantise=q)
+        for lc, F in enumerate(P.load_cases(name) if q is None else [j.F]):
+            its = P.cg_iterates(A, F, k + 1, rupdate=ru, restart=n)
+            got, yard, floor, true_res = figures(its[k - 1][0], its[k][0], F, q)
+            print("%s %s load case %d, k = %d: the float64 loop reads %.3g units (yardstick %.3g, floor %.3g), true residual %.2e" %
+                  (name, stream, lc, k, got, yard, floor, true_res))
+            assert true_res > 1e-4 and got <= P.DEVICE_CG_FACTOR * max(yard, floor)
+            if q is None and lc == 0:
+                ry, rf = P.RESTART_STEP_UNITS_MEASURED[name, mult]
+                assert _within_a_factor_of_two(yard, ry) and _within_a_factor_of_two(floor, rf)
+            if mult == 1:
+                its = P.cg_iterates(A, F, k + 1, rupdate=ru)
+                got, yard, floor, _res = figures(its[k - 1][0], its[k][0], F, q)
+                print("    without the restart: %.3g units, %.1e x the bound" % (got, got / (P.DEVICE_CG_FACTOR * max(yard, floor))))
+                assert got > 1e6 * P.DEVICE_CG_FACTOR * max(yard, floor)
+    for restart in (n, 0):
+        its = P.cg_single_reduce_f64(csr, j.F, k + 1, rupdate=ru, restart=restart)
+        got, yard, floor, _res = figures(its[k - 1][0], its[k][0], j.F, None)
+        print("%s single reduction, restart %d, k = %d: %.3g units (yardstick %.3g, floor %.3g)" % (name, restart, k, got, yard, floor))
+        if restart:
+            assert got <= P.DEVICE_CG_FACTOR * max(yard, floor)
+        elif mult == 1:
+            assert got > 1e6 * P.DEVICE_CG_FACTOR * max(yard, floor)
