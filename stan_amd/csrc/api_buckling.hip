@@ -1,7 +1,8 @@
 // api_buckling.hip -- the extern "C" surface of linear buckling: the element scalars of the geometric
 // stiffness on a batch (introspection), the assembled matrix G = K_g(U) in K's layout (geometric.hip), and the driver loop of
 // stan_hip_buckling over the solver's batched CG (stan_cg_multi_device), its products (stan_spmv_reduced) on K and on G, the
-// block kernels of modal.hip and the q x q eigenproblem of api_modal.hip on the host.  One device, one rank.
+// block kernels of modal.hip and the q x q eigenproblem of api_modal.hip on the host; the stages it has in common with the modal
+// driver are block_run's (api_stage.h).  One device, one rank.
 #include <algorithm>
 #include <cmath>
 
@@ -21,31 +22,15 @@ int kg_args(stan_ctx *ctx, const char *who, stan_matrix *K, stan_matrix **out, b
 // block inverse iteration in correction form with a Rayleigh-Ritz step; factor = 1 / mu.
 int buckling_device(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, int32_t k, double tol, int32_t max_outer, double solve_eps,
                     int32_t solve_max_its, double *d_factor, double *d_phi, double *d_rho, stan_buckling_report *rep) {
-    auto bad = [&](const std::string &why, int rc) { ctx->err = "buckling: " + why; return rc; };
-    const int64_t N = K->n_red;
-    if (k <= 0 || k > N) return bad("n_modes must be in [1, N]", STAN_E_ARG);
-    if (!(tol >= 0) || !(solve_eps >= 0) || !std::isfinite(tol) || !std::isfinite(solve_eps) || max_outer < 0 || solve_max_its < 0)
-        return bad("tol, solve_eps, max_outer and solve_max_its must be >= 0", STAN_E_ARG);
-    const int64_t q64 = std::min<int64_t>(N, std::min<int64_t>(2 * (int64_t)k, (int64_t)k + 8));
-    if (q64 > STAN_MODAL_QMAX) return bad("the block of min(2 n_modes, n_modes + 8) columns exceeds 32", STAN_E_ARG);
-    const int q = (int)q64;
-    if (tol == 0) tol = 1e-6;
-    if (max_outer == 0) max_outer = 100;
-    if (solve_eps == 0 && solve_max_its == 0) solve_eps = 1e-6;   // lincgsetcond
-    stan_buckling_report R{};
-    struct report_out {   // the report as far as the call got, on every way out
-        stan_buckling_report *to; const stan_buckling_report &from;
-        ~report_out() { if (to) *to = from; }
-    } report{rep, R};
-    R.block = q;
-    piece_timer pt(ctx);
+    block_run<stan_buckling_report> run(ctx, K, "buckling", k, tol, max_outer, solve_eps, solve_max_its);
+    STANCHK(run.begin(rep));
+    stan_buckling_report &R = run.R;
+    piece_timer &pt = run.pt;
+    const int64_t N = run.N;
+    const int q = run.q;
     hipStream_t st = ctx->stream;
     // the solves run with the merit stop off, as the transient driver's do (its type 7 would leave a correction unfinished)
-    struct merit_off {   // the caller's setting comes back on every way out
-        stan_ctx *c; bool was;
-        explicit merit_off(stan_ctx *x) : c(x), was(x->cg_merit_stop) { c->cg_merit_stop = false; }
-        ~merit_off() { c->cg_merit_stop = was; }
-    } merit(ctx);
+    merit_off merit(ctx);
 
     dev_scope tmp(ctx);
     double *Z, *W, *Y, *rhs, *D, *dg;   // [q][N] each (dg: [N], diag K); X lives in Z, K X in W
@@ -57,44 +42,22 @@ int buckling_device(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, int32_t k, do
     STANCHK(tmp.alloc(&D, qn));
     STANCHK(tmp.alloc(&dg, (size_t)N));
 
-    std::vector<int32_t> term((size_t)q), its((size_t)q);
-    // n columns of `F` -> `U` through the batched CG; a column that ends with -5 / -4 ends the call
-    auto solve = [&](int n, const double *F, double *U) -> int {
-        pt.begin();
-        STANCHK(stan_cg_multi_device(ctx, K, n, F, solve_eps, solve_max_its, STAN_PREC_FP64, U, term.data(), its.data(), nullptr));
-        pt.end(&R.solve_ms);
-        for (int c = 0; c < n; c++) {
-            R.cg_iterations += its[(size_t)c];
-            R.cg_worst_type = worse_type(R.cg_worst_type, term[(size_t)c]);
-        }
-        if (R.cg_worst_type < 0)
-            return bad("a CG column ended with termination type " + std::to_string(R.cg_worst_type) +
-                           " (K is not positive definite: a model without supports?)", STAN_E_UNSUPPORTED);
-        return STAN_OK;
-    };
     // out_j = H in_j = -(G in_j), q true products; the negation is exact
     auto h_products = [&](const double *in, double *out) -> int {
-        pt.begin();
-        for (int j = 0; j < q; j++) STANCHK(stan_spmv_reduced(ctx, G, in + (size_t)j * N, out + (size_t)j * N));
-        STANCHK(stan_buckling_negate_device(ctx, (int64_t)qn, out));
-        pt.end(&R.product_ms);
-        return STAN_OK;
+        return run.products(G, in, out, [&] { return stan_buckling_negate_device(ctx, (int64_t)qn, out); });
     };
     pt.begin();
     STANCHK(stan_buckling_start_device(ctx, N, q, Z));
     pt.end(&R.block_ms);
     STANCHK(h_products(Z, rhs));
-    STANCHK(solve(q, rhs, Z));
+    STANCHK(run.solve(q, rhs, Z, "a model without supports?"));
     STANCHK(stan_matrix_diagonal(ctx, K, dg));   // (behind the first solve: K is in the state every later step finds it in)
 
     std::vector<double> A((size_t)q * q), B((size_t)q * q), unused((size_t)q * q), Qm((size_t)q * q), mu((size_t)q), r2((size_t)q),
         kx2((size_t)q), rho((size_t)q);
-    std::vector<int32_t> dcol((size_t)q);
     for (;;) {
         R.outer++;
-        pt.begin();
-        for (int j = 0; j < q; j++) STANCHK(stan_spmv_reduced(ctx, K, Z + (size_t)j * N, W + (size_t)j * N));
-        pt.end(&R.product_ms);
+        STANCHK(run.products(K, Z, W));
         STANCHK(h_products(Z, Y));
         pt.begin();   // A = Z^T W, B = Z^T Y: the modal gram pass twice (its second output, Z^T (dg o Z), is not used)
         STANCHK(stan_modal_gram_device(ctx, N, q, Z, W, dg, A.data(), unused.data()));
@@ -107,8 +70,8 @@ int buckling_device(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, int32_t k, do
             }
         // B Q = A Q diag(mu) through the Cholesky factor of A = Z^T K Z, mu descending
         if (!stan_small_gen_eig(q, B.data(), A.data(), mu.data(), Qm.data(), true))
-            return bad("the block lost rank (Z^T K Z is not positive definite)", STAN_E_UNSUPPORTED);
-        const bool last = R.outer >= max_outer;
+            return run.bad("the block lost rank (Z^T K Z is not positive definite)", STAN_E_UNSUPPORTED);
+        const bool last = R.outer >= run.max_outer;
         pt.begin();   // the last step needs no right-hand side: every column masked
         STANCHK(stan_buckling_rotate_device(ctx, N, q, Z, W, Y, dg, Qm.data(), mu.data(), last ? 0xffffffffu : 0u, Z, W, rhs, r2.data(),
                                             kx2.data()));
@@ -120,25 +83,20 @@ int buckling_device(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, int32_t k, do
             rho[(size_t)j] = std::sqrt(r2[(size_t)j]) / (std::fabs(mu[(size_t)j]) * std::sqrt(kx2[(size_t)j]));
             if (mu[(size_t)j] > 0.0) R.n_positive++;
             if (j < k) {
-                done = done && mu[(size_t)j] > 0.0 && rho[(size_t)j] <= tol;
+                done = done && mu[(size_t)j] > 0.0 && rho[(size_t)j] <= run.tol;
                 R.max_rho = std::max(R.max_rho, rho[(size_t)j]);
             }
         }
         R.lowest_negative_factor = mu[(size_t)q - 1] < 0.0 ? 1.0 / mu[(size_t)q - 1] : 0.0;   // mu descends
         R.converged = done ? 1 : 0;
         if (done || last) break;
-        // K D = -R for the columns that have not converged, packed side by side (a column's CG does not depend on its
-        // neighbours), then Z = X diag(mu) + D: defined for every sign of mu
-        int n = 0;
-        for (int j = 0; j < q; j++) {
-            dcol[(size_t)j] = -1;
-            if (!(rho[(size_t)j] > tol)) continue;
-            if (n != j) HIPCHK(ctx, hipMemcpyAsync(rhs + (size_t)n * N, rhs + (size_t)j * N, (size_t)N * 8, hipMemcpyDeviceToDevice, st));
-            dcol[(size_t)j] = n++;
-        }
-        if (n > 0) STANCHK(solve(n, rhs, D));
+        // K D = -R for the columns that have not converged (a column is solved again where rho > tol), then
+        // Z = X diag(mu) + D: defined for every sign of mu
+        int n;
+        STANCHK(run.pack(rhs, [&](int j) { return rho[(size_t)j] > run.tol; }, &n));
+        if (n > 0) STANCHK(run.solve(n, rhs, D, "a model without supports?"));
         pt.begin();
-        STANCHK(stan_buckling_axpy_device(ctx, N, q, Z, mu.data(), dcol.data(), D, Z));
+        STANCHK(stan_buckling_axpy_device(ctx, N, q, Z, mu.data(), run.dcol.data(), D, Z));
         pt.end(&R.block_ms);
     }
     // the first min(k, n_positive) pairs; the rest of the outputs are zeros
@@ -149,11 +107,7 @@ int buckling_device(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, int32_t k, do
     pt.begin();
     if (kk > 0) STANCHK(stan_buckling_normalise_device(ctx, N, kk, Z, d_phi));
     pt.end(&R.block_ms);
-    R.block_ms += R.gram_ms + R.rotate_ms;
-    HIPCHK(ctx, hipMemcpyAsync(d_factor, fac.data(), (size_t)k * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(d_rho, rh.data(), (size_t)k * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return STAN_OK;
+    return run.finish(fac.data(), rh.data(), d_factor, d_rho);
 }
 
 int buckling_args(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, const void *factor, const void *phi, const void *rho) {

@@ -1,7 +1,8 @@
 // api_modal.hip -- the extern "C" surface, part 5 of 5: the modal analysis.  The driver loop of stan_hip_modes (block inverse iteration in
 // correction form with a Rayleigh-Ritz step) over the solver's batched CG (stan_cg_multi_device), its
 // products (stan_spmv_reduced) and the block kernels of modal.hip; the q x q eigenproblem on the host; the two block helpers.
-// One device, one rank (block_driver_refused, api_stage.h).
+// One device, one rank (block_driver_refused, api_stage.h).  What the loop shares with the buckling driver's (the checks and
+// defaults, the solves, the products, the packing, the tail) is block_run of api_stage.h.
 #include <algorithm>
 #include <cmath>
 
@@ -92,27 +93,14 @@ namespace {
 // the driver on device arrays: d_M [N], d_lambda / d_rho [k], d_phi [k][N]
 int modes_device(stan_ctx *ctx, stan_matrix *K, const double *d_M, int32_t k, double tol, int32_t max_outer, double solve_eps,
                  int32_t solve_max_its, double *d_lambda, double *d_phi, double *d_rho, stan_modes_report *rep) {
-    auto bad = [&](const std::string &why, int rc) { ctx->err = "modes: " + why; return rc; };
     // what every refusal of a K that is not positive definite ends with: the way such a model is analysed
     const std::string free_hint = "a model without supports?  Analyse the shifted problem K + sigma M: stan_hip_matrix_shifted, stan_solver --modes-shift SIGMA";
-    const int64_t N = K->n_red;
-    if (k <= 0 || k > N) return bad("n_modes must be in [1, N]", STAN_E_ARG);
-    if (!(tol >= 0) || !(solve_eps >= 0) || !std::isfinite(tol) || !std::isfinite(solve_eps) || max_outer < 0 || solve_max_its < 0)
-        return bad("tol, solve_eps, max_outer and solve_max_its must be >= 0", STAN_E_ARG);
-    const int64_t q64 = std::min<int64_t>(N, std::min<int64_t>(2 * (int64_t)k, (int64_t)k + 8));
-    if (q64 > STAN_MODAL_QMAX) return bad("the block of min(2 n_modes, n_modes + 8) columns exceeds 32", STAN_E_ARG);
-    const int q = (int)q64;
-    if (tol == 0) tol = 1e-6;
-    if (max_outer == 0) max_outer = 100;
-    if (solve_eps == 0 && solve_max_its == 0) solve_eps = 1e-6;   // lincgsetcond
-    stan_modes_report R{};
-    struct report_out {   // the report as far as the call got, on every way out
-        stan_modes_report *to; const stan_modes_report &from;
-        ~report_out() { if (to) *to = from; }
-    } report{rep, R};
-    R.block = q;
-    piece_timer pt(ctx);
-    hipStream_t st = ctx->stream;
+    block_run<stan_modes_report> run(ctx, K, "modes", k, tol, max_outer, solve_eps, solve_max_its);
+    STANCHK(run.begin(rep));
+    stan_modes_report &R = run.R;
+    piece_timer &pt = run.pt;
+    const int64_t N = run.N;
+    const int q = run.q;
 
     dev_scope tmp(ctx);
     double *Z, *W, *rhs, *D;   // [q][N] each; X lives in Z, K X in W
@@ -125,42 +113,22 @@ int modes_device(stan_ctx *ctx, stan_matrix *K, const double *d_M, int32_t k, do
     pt.begin();
     STANCHK(stan_modal_start_device(ctx, N, q, d_M, rhs, &bad_row));
     pt.end(&R.block_ms);
-    if (bad_row >= 0) return bad("M[" + std::to_string(bad_row) + "] is not positive and finite", STAN_E_ARG);
-
-    std::vector<int32_t> term((size_t)q), its((size_t)q);
-    // n columns of `F` -> `U` through the batched CG; a column that ends with -5 / -4 ends the call
-    auto solve = [&](int n, const double *F, double *U) -> int {
-        pt.begin();
-        STANCHK(stan_cg_multi_device(ctx, K, n, F, solve_eps, solve_max_its, STAN_PREC_FP64, U, term.data(), its.data(), nullptr));
-        pt.end(&R.solve_ms);
-        for (int c = 0; c < n; c++) {
-            R.cg_iterations += its[(size_t)c];
-            R.cg_worst_type = worse_type(R.cg_worst_type, term[(size_t)c]);
-        }
-        if (R.cg_worst_type < 0) {
-            return bad("a CG column ended with termination type " + std::to_string(R.cg_worst_type) + " (K is not positive definite: " + free_hint + ")",
-                       STAN_E_UNSUPPORTED);
-        }
-        return STAN_OK;
-    };
-    STANCHK(solve(q, rhs, Z));
+    if (bad_row >= 0) return run.bad("M[" + std::to_string(bad_row) + "] is not positive and finite", STAN_E_ARG);
+    STANCHK(run.solve(q, rhs, Z, free_hint));
 
     std::vector<double> A((size_t)q * q), B((size_t)q * q), Qm((size_t)q * q), lam((size_t)q), rho2((size_t)q), rho((size_t)q);
-    std::vector<int32_t> dcol((size_t)q);
     for (;;) {
         R.outer++;
-        pt.begin();
-        for (int j = 0; j < q; j++) STANCHK(stan_spmv_reduced(ctx, K, Z + (size_t)j * N, W + (size_t)j * N));
-        pt.end(&R.product_ms);
+        STANCHK(run.products(K, Z, W));
         pt.begin();
         STANCHK(stan_modal_gram_device(ctx, N, q, Z, W, d_M, A.data(), B.data()));
         pt.end(&R.gram_ms);
         if (!stan_small_gen_eig(q, A.data(), B.data(), lam.data(), Qm.data()))
-            return bad("the block lost rank (Z^T M Z is not positive definite: " + free_hint + ")", STAN_E_UNSUPPORTED);
+            return run.bad("the block lost rank (Z^T M Z is not positive definite: " + free_hint + ")", STAN_E_UNSUPPORTED);
         for (int j = 0; j < q; j++)
             if (!(lam[(size_t)j] > 0.0))
-                return bad("Ritz value " + std::to_string(j) + " is not positive (K is not positive definite: " + free_hint + ")", STAN_E_UNSUPPORTED);
-        const bool last = R.outer >= max_outer;
+                return run.bad("Ritz value " + std::to_string(j) + " is not positive (K is not positive definite: " + free_hint + ")", STAN_E_UNSUPPORTED);
+        const bool last = R.outer >= run.max_outer;
         pt.begin();   // the last step needs no right-hand side: every column masked
         STANCHK(stan_modal_rotate_device(ctx, N, q, Z, W, d_M, Qm.data(), lam.data(), last ? 0xffffffffu : 0u, Z, W, rhs, rho2.data()));
         pt.end(&R.rotate_ms);
@@ -169,34 +137,25 @@ int modes_device(stan_ctx *ctx, stan_matrix *K, const double *d_M, int32_t k, do
         for (int j = 0; j < q; j++) {
             rho[(size_t)j] = std::sqrt(rho2[(size_t)j]) / lam[(size_t)j];
             if (j < k) {
-                done = done && rho[(size_t)j] <= tol;
+                done = done && rho[(size_t)j] <= run.tol;
                 R.max_rho = std::max(R.max_rho, rho[(size_t)j]);
             }
         }
         R.converged = done ? 1 : 0;
         if (done || last) break;
-        // K D = -R Lambda^-1 for the columns that have not converged, packed side by side (a column's CG does not depend on
-        // its neighbours), then Z = X Lambda^-1 + D
-        int n = 0;
-        for (int j = 0; j < q; j++) {
-            dcol[(size_t)j] = -1;
-            if (rho[(size_t)j] <= tol) continue;
-            if (n != j) HIPCHK(ctx, hipMemcpyAsync(rhs + (size_t)n * N, rhs + (size_t)j * N, (size_t)N * 8, hipMemcpyDeviceToDevice, st));
-            dcol[(size_t)j] = n++;
-        }
-        STANCHK(solve(n, rhs, D));
+        // K D = -R Lambda^-1 for the columns that have not converged (a column is left out where rho <= tol), then
+        // Z = X Lambda^-1 + D
+        int n;
+        STANCHK(run.pack(rhs, [&](int j) { return !(rho[(size_t)j] <= run.tol); }, &n));
+        STANCHK(run.solve(n, rhs, D, free_hint));
         pt.begin();
-        STANCHK(stan_modal_axpy_device(ctx, N, q, Z, lam.data(), dcol.data(), D, Z));
+        STANCHK(stan_modal_axpy_device(ctx, N, q, Z, lam.data(), run.dcol.data(), D, Z));
         pt.end(&R.block_ms);
     }
     pt.begin();
     STANCHK(stan_modal_normalise_device(ctx, N, k, Z, d_M, d_phi));
     pt.end(&R.block_ms);
-    R.block_ms += R.gram_ms + R.rotate_ms;
-    HIPCHK(ctx, hipMemcpyAsync(d_lambda, lam.data(), (size_t)k * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(d_rho, rho.data(), (size_t)k * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return STAN_OK;
+    return run.finish(lam.data(), rho.data(), d_lambda, d_rho);
 }
 
 int modes_args(stan_ctx *ctx, stan_matrix *K, const void *M, const void *lambda, const void *phi, const void *rho) {

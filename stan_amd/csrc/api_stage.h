@@ -2,6 +2,9 @@
 // checks of a host view, the refusals several entries repeat, and the kept results.  Not part of the C ABI.
 #pragma once
 
+#include <algorithm>
+#include <cmath>
+
 #include "internal.h"
 
 // The stream side of one host entry.  Declared before the entry's device buffers (and behind any host memory of the entry's
@@ -116,7 +119,22 @@ inline int one_device_refused(stan_ctx *ctx, const char *entry) {
     return STAN_OK;
 }
 
-// ---- what the drivers over the CG share (api_modal.hip, api_transient.hip) ------------------------------------------------------
+// ---- what the drivers over the CG share (api_modal.hip, api_transient.hip, api_buckling.hip) ------------------------------------
+// the report as far as the call got, on every way out (to == null: nobody asked, or not yet)
+template <typename Rep>
+struct report_out {
+    Rep *to; const Rep &from;
+    ~report_out() { if (to) *to = from; }
+};
+
+// A driver's solves run with ALGLIB's merit stop off (its type 7 would leave a step or a correction unfinished); the caller's
+// setting comes back on every way out
+struct merit_off {
+    stan_ctx *c; bool was;
+    explicit merit_off(stan_ctx *x) : c(x), was(x->cg_merit_stop) { c->cg_merit_stop = false; }
+    ~merit_off() { c->cg_merit_stop = was; }
+};
+
 // stream time of a driver's phases, by one event pair around each piece (profiling on; every piece ends synchronised)
 struct piece_timer {
     stan_ctx *ctx;
@@ -153,6 +171,93 @@ inline int worse_type(int a, int b) {   // negative < 5 < 7 < 1
     if (a == 0) return b;
     return rank(b) < rank(a) || (rank(b) == rank(a) && b < a) ? b : a;
 }
+
+// What a run of a block driver carries (modes_device, buckling_device; Rep is stan_modes_report or stan_buckling_report, which
+// name the shared fields alike) and the stages that are the same in both.  The loops themselves are the drivers': they differ
+// in every line that matters (the pencil, the norm, the order, the stop test).
+template <typename Rep>
+struct block_run {
+    stan_ctx *ctx; stan_matrix *K;
+    const char *who;                  // the driver's name: the prefix of its error texts
+    int64_t N; int32_t k; int q = 0;  // rows, pairs asked for, columns of the block
+    double tol, solve_eps; int32_t max_outer, solve_max_its;
+    Rep R{};
+    report_out<Rep> report{nullptr, R};
+    piece_timer pt;
+    std::vector<int32_t> term, its, dcol;   // [q]: of the last solve; a column's place among the packed right-hand sides
+
+    block_run(stan_ctx *c, stan_matrix *Km, const char *name, int32_t n_modes, double tol_, int32_t max_outer_, double solve_eps_,
+              int32_t solve_max_its_)
+        : ctx(c), K(Km), who(name), N(Km->n_red), k(n_modes), tol(tol_), solve_eps(solve_eps_), max_outer(max_outer_),
+          solve_max_its(solve_max_its_), pt(c) {}
+    int bad(const std::string &why, int rc) { ctx->err = std::string(who) + ": " + why; return rc; }
+    // the argument checks, the block size and the defaults; from here on `rep` gets the report on every way out
+    int begin(Rep *rep) {
+        if (k <= 0 || k > N) return bad("n_modes must be in [1, N]", STAN_E_ARG);
+        if (!(tol >= 0) || !(solve_eps >= 0) || !std::isfinite(tol) || !std::isfinite(solve_eps) || max_outer < 0 || solve_max_its < 0)
+            return bad("tol, solve_eps, max_outer and solve_max_its must be >= 0", STAN_E_ARG);
+        const int64_t q64 = std::min<int64_t>(N, std::min<int64_t>(2 * (int64_t)k, (int64_t)k + 8));
+        if (q64 > STAN_MODAL_QMAX) return bad("the block of min(2 n_modes, n_modes + 8) columns exceeds 32", STAN_E_ARG);
+        q = (int)q64;
+        if (tol == 0) tol = 1e-6;
+        if (max_outer == 0) max_outer = 100;
+        if (solve_eps == 0 && solve_max_its == 0) solve_eps = 1e-6;   // lincgsetcond
+        report.to = rep;
+        R.block = q;
+        term.resize((size_t)q); its.resize((size_t)q); dcol.resize((size_t)q);
+        return STAN_OK;
+    }
+    // n columns of `F` -> `U` through the batched CG; a column that ends with -5 / -4 ends the call (hint: what the driver
+    // says about a K that is not positive definite)
+    int solve(int n, const double *F, double *U, const std::string &hint) {
+        pt.begin();
+        STANCHK(stan_cg_multi_device(ctx, K, n, F, solve_eps, solve_max_its, STAN_PREC_FP64, U, term.data(), its.data(), nullptr));
+        pt.end(&R.solve_ms);
+        for (int c = 0; c < n; c++) {
+            R.cg_iterations += its[(size_t)c];
+            R.cg_worst_type = worse_type(R.cg_worst_type, term[(size_t)c]);
+        }
+        if (R.cg_worst_type < 0)
+            return bad("a CG column ended with termination type " + std::to_string(R.cg_worst_type) + " (K is not positive definite: " + hint + ")",
+                       STAN_E_UNSUPPORTED);
+        return STAN_OK;
+    }
+    // out_j = A in_j, q true products, and what `then` enqueues behind them, as one piece of product_ms
+    template <typename Then>
+    int products(stan_matrix *A, const double *in, double *out, Then &&then) {
+        pt.begin();
+        for (int j = 0; j < q; j++) STANCHK(stan_spmv_reduced(ctx, A, in + (size_t)j * N, out + (size_t)j * N));
+        STANCHK(then());
+        pt.end(&R.product_ms);
+        return STAN_OK;
+    }
+    int products(stan_matrix *A, const double *in, double *out) {
+        return products(A, in, out, [] { return (int)STAN_OK; });
+    }
+    // the right-hand sides of the columns j with again(j) packed side by side (a column's CG does not depend on its
+    // neighbours): dcol[j] = the column's place, -1 for the others; *n = how many
+    template <typename Again>
+    int pack(double *rhs, Again &&again, int *n_out) {
+        int n = 0;
+        for (int j = 0; j < q; j++) {
+            dcol[(size_t)j] = -1;
+            if (!again(j)) continue;
+            if (n != j) HIPCHK(ctx, hipMemcpyAsync(rhs + (size_t)n * N, rhs + (size_t)j * N, (size_t)N * 8, hipMemcpyDeviceToDevice, ctx->stream));
+            dcol[(size_t)j] = n++;
+        }
+        *n_out = n;
+        return STAN_OK;
+    }
+    // the tail: the block pieces' times folded, the two k-vectors out
+    int finish(const double *values, const double *rho, double *d_values, double *d_rho) {
+        hipStream_t st = ctx->stream;
+        R.block_ms += R.gram_ms + R.rotate_ms;
+        HIPCHK(ctx, hipMemcpyAsync(d_values, values, (size_t)k * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(d_rho, rho, (size_t)k * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        return STAN_OK;
+    }
+};
 
 // ---- results kept on the device(s) (stan_hip_recover_hex8_keep, api_post.hip) ------------------------------------------------
 struct stan_results {

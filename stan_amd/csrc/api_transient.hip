@@ -94,10 +94,7 @@ int transient_device(stan_ctx *ctx, stan_matrix *K, const double *d_Min, const d
     if (N <= 0) return bad("the matrix has no free DOF", STAN_E_ARG);
     const size_t n = (size_t)N, nb = n * 8;
     stan_transient_report R{};
-    struct report_out {   // the report as far as the call got, on every way out
-        stan_transient_report *to; const stan_transient_report &from;
-        ~report_out() { if (to) *to = from; }
-    } report{rep, R};
+    report_out<stan_transient_report> report{rep, R};
     const stan_newmark_coef c = make_coef(P.dt, P.beta_N, P.gamma, P.alpha_R, P.beta_R);
     R.sigma = (c.a0 + c.a1 * P.alpha_R) / c.c_K;
     if (!std::isfinite(R.sigma) || !std::isfinite(c.a0)) return bad("dt is too small: 1 / (beta_N dt^2) is not finite", STAN_E_ARG);
@@ -136,11 +133,7 @@ int transient_device(stan_ctx *ctx, stan_matrix *K, const double *d_Min, const d
     // The steps' solves run with ALGLIB's merit stop off, as under STAN_OPT_CG_MERIT_STOP 0: that stop is there for the static
     // solve's parity with the reference, which has no transient analysis; its type 7 ("no further progress": near 1e-7 on
     // these systems, and now and then above 1e-6 on a stiffness-dominated step) would end a run that the loop can finish.
-    struct merit_off {   // the caller's setting comes back on every way out
-        stan_ctx *c; bool was;
-        explicit merit_off(stan_ctx *x) : c(x), was(x->cg_merit_stop) { c->cg_merit_stop = false; }
-        ~merit_off() { c->cg_merit_stop = was; }
-    } merit(ctx);
+    merit_off merit(ctx);
     stan_matrix *S = nullptr;
     struct shifted_guard {   // freed on every way out
         stan_matrix *&s;

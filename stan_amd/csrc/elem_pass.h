@@ -1,5 +1,6 @@
 // elem_pass.h -- the skeleton shared by the element passes after the solve: k_recover (recovery.hip), k_if_elem
 // (internal_forces.hip) and k_ld_elem (loads.hip), with the block reduction and the node gather of their second phases.
+// block_sums and the kernel that finishes a two-pass sum (k_finish_sums) also serve modal.hip and transient.hip.
 //
 // Layout (round 5): a workgroup of 256 lanes = 4 waves, a wave = 8 elements, an element = 8 lanes.
 // Lane g of an element is its Gauss point g AND its local node g: it loads node g only (3 coordinates, 3 displacements: 7
@@ -154,6 +155,20 @@ __device__ __forceinline__ void block_sums(double (&s)[N], double (*sh)[W]) {   
         for (int w = 1; w < 4; w++)
 #pragma unroll
             for (int k = 0; k < N; k++) s[k] += sh[w][k];
+}
+// The second pass of a two-pass sum (modal.hip, transient.hip): out[v] = the sum of partial[v][0 .. n_blocks) in block order.
+// One workgroup of T lanes per value: thread t adds blocks t, t + T, ... in ascending order, then the workgroup's fixed order.
+// A kernel defined in a header is emitted only in the translation units that instantiate it.
+template <int T>
+__global__ void __launch_bounds__(T)
+k_finish_sums(int64_t n_blocks, const double *__restrict__ partial, double *__restrict__ out) {
+    static_assert(T == 256, "block_sums adds the four waves of 256 lanes");
+    __shared__ double sh[4][1];
+    double s[1] = {0.0};
+    const double *p = partial + (int64_t)blockIdx.x * n_blocks;
+    for (int64_t b = threadIdx.x; b < n_blocks; b += T) s[0] += p[b];
+    block_sums(s, sh);
+    if (threadIdx.x == 0) out[blockIdx.x] = s[0];
 }
 
 // node gather: f = the sum of fe[3t .. 3t + 2] over node n's list entries t = element * 8 + corner, in list order

@@ -507,8 +507,9 @@ int stan_lumped_mass_device(stan_ctx *ctx, const stan_mesh &d, const double *mat
                             stan_mass_sums *sums);
 
 // ---- modal.hip ------------------------------------------------------------------------------
-// The tall-skinny block kernels of the modal driver (api_modal.hip); a block vector is [q][N], q <= STAN_MODAL_QMAX.  All
-// enqueue on the context's stream; those with host outputs synchronise it.
+// The tall-skinny block kernels of the modal driver (api_modal.hip) and, below, of the buckling driver; a block vector is
+// [q][N], q <= STAN_MODAL_QMAX.  All enqueue on the context's stream; those with host outputs synchronise it.  The two sets
+// differ in their kernels; the host halves of the rotate, axpy and normalise entries are one routine each inside modal.hip.
 constexpr int STAN_MODAL_QMAX = 32;
 // d_rhs [q][N] = M o X0 with X0's column 0 = M and column j > 0 the hash of (row, j); *bad = the first row whose M is not
 // positive and finite (-1: none).  Synchronises.
@@ -735,6 +736,21 @@ static inline int stan_detj_check(stan_ctx *ctx, const char *why) {
     return STAN_E_DETJ;
 }
 static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }   // blocks of t threads over n items
+// The round trip of a check on the device: the slot d_status[SS_AUX] starts at "none", `enqueue(slot)` launches on the context's
+// stream the kernel that takes atomicMin(slot, index) at every index it refuses, the slot comes back; *first = the lowest such
+// index (-1: none).  Synchronises.
+template <typename F>
+static inline int stan_first_offender(stan_ctx *ctx, int64_t *first, F &&enqueue) {
+    hipStream_t st = ctx->stream;
+    const long long none = 0x7fffffffffffffffLL;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_status + SS_AUX, &none, 8, hipMemcpyHostToDevice, st));
+    enqueue((long long *)(ctx->d_status + SS_AUX));
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, ctx->d_status + SS_AUX, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    *first = ctx->h_status[SS_AUX] == none ? -1 : ctx->h_status[SS_AUX];
+    return STAN_OK;
+}
 
 // ---- multi.hip: fan-out of the public entry points for a group handle ------------------------
 void stan_set_global_error(const std::string &msg);   // api.hip: errors raised before a context exists

@@ -105,17 +105,11 @@ int stan_matrix_clone_layout(stan_ctx *ctx, const stan_matrix *K, stan_matrix **
 }
 
 int stan_mass_check_device(stan_ctx *ctx, int64_t N, const double *d_M, int64_t *bad) {
-    hipStream_t st = ctx->stream;
-    const long long none = 0x7fffffffffffffffLL;
     *bad = -1;
     if (N <= 0) return STAN_OK;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_status + SS_AUX, &none, 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_mass_check, dim3(nblk(N, 256)), dim3(256), 0, st, N, d_M, (long long *)(ctx->d_status + SS_AUX));
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, ctx->d_status + SS_AUX, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (ctx->h_status[SS_AUX] != none) *bad = ctx->h_status[SS_AUX];
-    return STAN_OK;
+    return stan_first_offender(ctx, bad, [&](long long *slot) {
+        hipLaunchKernelGGL(k_mass_check, dim3(nblk(N, 256)), dim3(256), 0, ctx->stream, N, d_M, slot);
+    });
 }
 
 int stan_matrix_shifted_device(stan_ctx *ctx, stan_matrix *K, double sigma, const double *d_M, stan_matrix **out, double *shift_ms) {

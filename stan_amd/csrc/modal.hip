@@ -8,9 +8,13 @@
 //             row: the row of Z and of W in registers, Q and Lambda uniform operands;
 //   axpy      Z_j = X_j / lambda_j + D_j;
 //   normalise column sums of M x^2 and the entry of largest magnitude (lowest index on a tie), then the scaling.
+// Behind them the buckling driver's kernels (api_buckling.hip, section 3.12) where its algorithm differs.  What the two sets
+// share is written once: block_amax, k_finish_sums (elem_pass.h), k_md_scale and the host halves of the entries.
 // All bit-reproducible: no atomics on doubles; a workgroup's sum has a fixed order (rows ascending per wave, the four waves in
-// order / block_sums), the workgroups' partial sums are added in workgroup order by one workgroup per value (k_md_finish).
-#include "elem_pass.h"   // block_sums
+// order / block_sums), the workgroups' partial sums are added in workgroup order by one workgroup per value (k_finish_sums).
+#include <type_traits>
+
+#include "elem_pass.h"   // block_sums, k_finish_sums
 
 namespace {
 
@@ -132,18 +136,6 @@ k_md_gram(int64_t N, int q, const double *__restrict__ Z, const double *__restri
     }
 }
 
-// out[v] = the sum of partial[v][0 .. n_blocks) in block order: one workgroup per value, thread t adds blocks t, t + 256, ...
-// in ascending order, then the workgroup's fixed order
-__global__ void __launch_bounds__(256)
-k_md_finish(int64_t n_blocks, const double *__restrict__ partial, double *__restrict__ out) {
-    __shared__ double sh[4][1];
-    double s[1] = {0.0};
-    const double *p = partial + (int64_t)blockIdx.x * n_blocks;
-    for (int64_t b = threadIdx.x; b < n_blocks; b += 256) s[0] += p[b];
-    block_sums(s, sh);
-    if (threadIdx.x == 0) out[blockIdx.x] = s[0];
-}
-
 // ---- rotate + residual ---------------------------------------------------------------------------------------------------
 // Q and lambda padded with zeros to QT (QT x QT row-major, QT): a column beyond q multiplies zeros.  partial [q][gridDim.x].
 // Z / W may be X / KX: a lane has read its whole row before it stores any of it, and rows are independent.
@@ -210,6 +202,22 @@ __device__ __forceinline__ void amax_merge(double &v, long long &i, double v2, l
     const double f = fabs(v), f2 = fabs(v2);
     if (f2 > f || (f2 == f && i2 < i)) { v = v2; i = i2; }
 }
+constexpr long long NO_INDEX = 0x7fffffffffffffffLL;   // the index of "no entry yet": every row's is lower
+// The workgroup's (value, index) on thread 0 from the 256 lanes': a 64-lane butterfly, the waves' results handed over through
+// shv / shi, the four merged by thread 0.  `barrier` runs between the stores to shv / shi and thread 0's reads and holds the
+// workgroup barrier that orders them: __syncthreads(), or block_sums where the kernel sums too.
+template <typename Barrier>
+__device__ __forceinline__ void block_amax(double &bv, long long &bi, double *shv, long long *shi, Barrier &&barrier) {
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double v2 = __shfl_xor(bv, off, 64);
+        const long long i2 = __shfl_xor(bi, off, 64);
+        amax_merge(bv, bi, v2, i2);
+    }
+    if ((threadIdx.x & 63) == 0) { shv[threadIdx.x >> 6] = bv; shi[threadIdx.x >> 6] = bi; }
+    barrier();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < 4; w++) amax_merge(bv, bi, shv[w], shi[w]);
+}
 __global__ void __launch_bounds__(256)
 k_md_colstats(int64_t N, const double *__restrict__ X, const double *__restrict__ M, double *__restrict__ psum,
               double *__restrict__ pval, long long *__restrict__ pidx) {
@@ -218,7 +226,7 @@ k_md_colstats(int64_t N, const double *__restrict__ X, const double *__restrict_
     __shared__ long long shi[4];
     const int j = blockIdx.y;
     double s[1] = {0.0}, bv = 0.0;
-    long long bi = 0x7fffffffffffffffLL;
+    long long bi = NO_INDEX;
     for (int k = 0; k < RT_ROWS / 256; k++) {
         const int64_t row = (int64_t)blockIdx.x * RT_ROWS + k * 256 + threadIdx.x;
         if (row >= N) continue;
@@ -226,15 +234,8 @@ k_md_colstats(int64_t N, const double *__restrict__ X, const double *__restrict_
         s[0] = fma(M[row] * x, x, s[0]);
         amax_merge(bv, bi, x, row);
     }
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double v2 = __shfl_xor(bv, off, 64);
-        const long long i2 = __shfl_xor(bi, off, 64);
-        amax_merge(bv, bi, v2, i2);
-    }
-    if ((threadIdx.x & 63) == 0) { shv[threadIdx.x >> 6] = bv; shi[threadIdx.x >> 6] = bi; }
-    block_sums(s, sh);   // (its barrier orders shv / shi too)
+    block_amax(bv, bi, shv, shi, [&] { block_sums(s, sh); });   // (its barrier orders shv / shi too)
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) amax_merge(bv, bi, shv[w], shi[w]);
         const int64_t o = (int64_t)j * gridDim.x + blockIdx.x;
         psum[o] = s[0]; pval[o] = bv; pidx[o] = bi;
     }
@@ -248,20 +249,13 @@ k_md_colfinish(int64_t n_blocks, const double *__restrict__ psum, const double *
     __shared__ long long shi[4];
     const int64_t o = (int64_t)blockIdx.x * n_blocks;
     double s[1] = {0.0}, bv = 0.0;
-    long long bi = 0x7fffffffffffffffLL;
+    long long bi = NO_INDEX;
     for (int64_t b = threadIdx.x; b < n_blocks; b += 256) {
         s[0] += psum[o + b];
         amax_merge(bv, bi, pval[o + b], pidx[o + b]);
     }
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double v2 = __shfl_xor(bv, off, 64);
-        const long long i2 = __shfl_xor(bi, off, 64);
-        amax_merge(bv, bi, v2, i2);
-    }
-    if ((threadIdx.x & 63) == 0) { shv[threadIdx.x >> 6] = bv; shi[threadIdx.x >> 6] = bi; }
-    block_sums(s, sh);
+    block_amax(bv, bi, shv, shi, [&] { block_sums(s, sh); });   // (its barrier orders shv / shi too)
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) amax_merge(bv, bi, shv[w], shi[w]);
         const double nrm = sqrt(s[0]);
         scale[blockIdx.x] = bv < 0.0 ? -nrm : nrm;
     }
@@ -372,20 +366,13 @@ k_bk_colmax(int64_t N, const double *__restrict__ X, double *__restrict__ pval, 
     __shared__ long long shi[4];
     const int j = blockIdx.y;
     double bv = 0.0;
-    long long bi = 0x7fffffffffffffffLL;
+    long long bi = NO_INDEX;
     for (int k = 0; k < RT_ROWS / 256; k++) {
         const int64_t row = (int64_t)blockIdx.x * RT_ROWS + k * 256 + threadIdx.x;
         if (row < N) amax_merge(bv, bi, X[(int64_t)j * N + row], row);
     }
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double v2 = __shfl_xor(bv, off, 64);
-        const long long i2 = __shfl_xor(bi, off, 64);
-        amax_merge(bv, bi, v2, i2);
-    }
-    if ((threadIdx.x & 63) == 0) { shv[threadIdx.x >> 6] = bv; shi[threadIdx.x >> 6] = bi; }
-    __syncthreads();
+    block_amax(bv, bi, shv, shi, [] { __syncthreads(); });
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) amax_merge(bv, bi, shv[w], shi[w]);
         const int64_t o = (int64_t)j * gridDim.x + blockIdx.x;
         pval[o] = bv; pidx[o] = bi;
     }
@@ -397,27 +384,13 @@ k_bk_colmax_finish(int64_t n_blocks, const double *__restrict__ pval, const long
     __shared__ long long shi[4];
     const int64_t o = (int64_t)blockIdx.x * n_blocks;
     double bv = 0.0;
-    long long bi = 0x7fffffffffffffffLL;
+    long long bi = NO_INDEX;
     for (int64_t b = threadIdx.x; b < n_blocks; b += 256) amax_merge(bv, bi, pval[o + b], pidx[o + b]);
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double v2 = __shfl_xor(bv, off, 64);
-        const long long i2 = __shfl_xor(bi, off, 64);
-        amax_merge(bv, bi, v2, i2);
-    }
-    if ((threadIdx.x & 63) == 0) { shv[threadIdx.x >> 6] = bv; shi[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) amax_merge(bv, bi, shv[w], shi[w]);
-        scale[blockIdx.x] = bv;
-    }
+    block_amax(bv, bi, shv, shi, [] { __syncthreads(); });
+    if (threadIdx.x == 0) scale[blockIdx.x] = bv;
 }
 
-template <int QT>
-void launch_rotate(hipStream_t st, unsigned nb, int64_t N, int q, const double *Z, const double *W, const double *M, const double *Qp,
-                   const md_cols &cols, uint32_t mask, double *X, double *KX, double *rhs, double *partial) {
-    hipLaunchKernelGGL(k_md_rotate<QT>, dim3(nb), dim3(256), 0, st, N, q, Z, W, M, Qp, cols, mask, X, KX, rhs, partial);
-}
-
+// ---- the host halves of the entries: what the two drivers' entries share ---------------------------------------------------
 int block_args_check(stan_ctx *ctx, const char *who, int64_t N, int32_t q) {
     if (N <= 0 || q <= 0 || q > QMAX || N > ((int64_t)1 << 31) - 1) {
         ctx->err = std::string(who) + ": N must be in [1, 2^31) and q in [1, 32]";
@@ -426,19 +399,96 @@ int block_args_check(stan_ctx *ctx, const char *who, int64_t N, int32_t q) {
     return STAN_OK;
 }
 
+// the columns' scalars and corrections as a kernel argument; beyond q no kernel reads them (zeros and "no correction")
+void fill_cols(md_cols &cols, int q, const double *scalar, const int32_t *dcol) {
+    for (int l = 0; l < QMAX; l++) { cols.lambda[l] = l < q ? scalar[l] : 0.0; cols.dcol[l] = dcol && l < q ? dcol[l] : -1; }
+}
+
+// f(std::integral_constant<int, QT>): the one dispatch over the widths the rotate kernels are instantiated for
+template <typename F>
+void with_qt(int QT, F &&f) {
+    if (QT == 8) f(std::integral_constant<int, 8>{});
+    else if (QT == 16) f(std::integral_constant<int, 16>{});
+    else if (QT == 24) f(std::integral_constant<int, 24>{});
+    else f(std::integral_constant<int, 32>{});
+}
+
+// What a rotate call sets up: the width QT of its kernels, Q padded with zeros to QT x QT (the host copy outlives the
+// stream's), the columns' scalars, and the temporaries of the sums: n_sums values per workgroup of 256 rows.
+struct rotate_call {
+    int QT = 0; int64_t nb = 0;   // the kernels' width, workgroups of 256 rows
+    std::vector<double> Qp;
+    md_cols cols;
+    dev_scope tmp;
+    double *d_Qp = nullptr, *d_partial = nullptr, *d_out = nullptr;
+    explicit rotate_call(stan_ctx *ctx) : tmp(ctx) {}
+    int prepare(int64_t N, int q, const double *Q, const double *scalar, size_t n_sums) {
+        QT = q <= 8 ? 8 : q <= 16 ? 16 : q <= 24 ? 24 : 32;
+        nb = nblk(N, 256);
+        Qp.assign((size_t)QT * QT, 0.0);
+        fill_cols(cols, q, scalar, nullptr);
+        for (int l = 0; l < q; l++)
+            for (int j = 0; j < q; j++) Qp[(size_t)l * QT + j] = Q[l * q + j];
+        STANCHK(tmp.alloc(&d_Qp, Qp.size()));
+        STANCHK(tmp.alloc(&d_partial, n_sums * (size_t)nb));
+        STANCHK(tmp.alloc(&d_out, n_sums));
+        HIPCHK(tmp.ctx, hipMemcpyAsync(d_Qp, Qp.data(), Qp.size() * 8, hipMemcpyHostToDevice, tmp.ctx->stream));
+        return STAN_OK;
+    }
+};
+
+// the tail of the entries with sums: out [n] (host) = the nb workgroups' partials of each value added in workgroup order.
+// Synchronises.
+int finish_sums(stan_ctx *ctx, int64_t nb, size_t n, const double *d_partial, double *d_out, double *out) {
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL(k_finish_sums<256>, dim3((unsigned)n), dim3(256), 0, st, nb, d_partial, d_out);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out, d_out, n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return STAN_OK;
+}
+
+// Z_j = X_j combined with its scalar and its correction by `kernel` (k_md_axpy or k_bk_axpy).  Enqueues only.
+int block_axpy(stan_ctx *ctx, const char *who, decltype(&k_md_axpy) kernel, int64_t N, int32_t q, const double *d_X,
+               const double *scalar, const int32_t *dcol, const double *d_D, double *d_Z) {
+    STANCHK(block_args_check(ctx, who, N, q));
+    md_cols cols;
+    fill_cols(cols, q, scalar, dcol);
+    hipLaunchKernelGGL(kernel, dim3(nblk(N, 256), (unsigned)q), dim3(256), 0, ctx->stream, N, d_X, cols, d_D, d_Z);
+    HIPCHK(ctx, hipGetLastError());
+    return STAN_OK;
+}
+
+// d_phi = the first k columns of X, column j divided by scale[j].  `enqueue(st, rows, cols, nb, t)` launches the pass over the
+// rows (grid `rows`: partials per column and workgroup of RT_ROWS rows) and the one workgroup per column (grid `cols`) that
+// leaves scale[j].  with_sums: the modal norm's partial sums are allocated too, in front as ever.  Synchronises.
+struct normalise_tmp { double *psum = nullptr, *pval = nullptr, *scale = nullptr; long long *pidx = nullptr; };
+template <typename Enqueue>
+int block_normalise(stan_ctx *ctx, const char *who, int64_t N, int32_t k, const double *d_X, double *d_phi, bool with_sums,
+                    Enqueue &&enqueue) {
+    STANCHK(block_args_check(ctx, who, N, k));
+    hipStream_t st = ctx->stream;
+    const int64_t nb = nblk(N, RT_ROWS);
+    dev_scope tmp(ctx);
+    normalise_tmp t;
+    if (with_sums) STANCHK(tmp.alloc(&t.psum, (size_t)k * (size_t)nb));
+    STANCHK(tmp.alloc(&t.pval, (size_t)k * (size_t)nb));
+    STANCHK(tmp.alloc(&t.pidx, (size_t)k * (size_t)nb));
+    STANCHK(tmp.alloc(&t.scale, (size_t)k));
+    enqueue(st, dim3((unsigned)nb, (unsigned)k), dim3((unsigned)k), nb, t);
+    hipLaunchKernelGGL(k_md_scale, dim3(nblk(N, 256), (unsigned)k), dim3(256), 0, st, N, d_X, t.scale, d_phi);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipStreamSynchronize(st));   // the temporaries go back to the context behind the kernels
+    return STAN_OK;
+}
+
 }  // namespace
 
 int stan_modal_start_device(stan_ctx *ctx, int64_t N, int32_t q, const double *d_M, double *d_rhs, int64_t *bad) {
     STANCHK(block_args_check(ctx, "modes", N, q));
-    hipStream_t st = ctx->stream;
-    const long long none = 0x7fffffffffffffffLL;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_status + SS_AUX, &none, 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_md_start, dim3(nblk(N, 256)), dim3(256), 0, st, N, (int)q, d_M, d_rhs, (long long *)(ctx->d_status + SS_AUX));
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, ctx->d_status + SS_AUX, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    *bad = ctx->h_status[SS_AUX] == none ? -1 : ctx->h_status[SS_AUX];
-    return STAN_OK;
+    return stan_first_offender(ctx, bad, [&](long long *slot) {
+        hipLaunchKernelGGL(k_md_start, dim3(nblk(N, 256)), dim3(256), 0, ctx->stream, N, (int)q, d_M, d_rhs, slot);
+    });
 }
 
 int stan_modal_gram_device(stan_ctx *ctx, int64_t N, int32_t q, const double *d_Z, const double *d_W, const double *d_M, double *A,
@@ -455,11 +505,8 @@ int stan_modal_gram_device(stan_ctx *ctx, int64_t N, int32_t q, const double *d_
         hipLaunchKernelGGL((k_md_gram<1, 4>), dim3((unsigned)nb), dim3(256), 0, st, N, (int)q, d_Z, d_W, d_M, d_partial);
     else
         hipLaunchKernelGGL((k_md_gram<4, 8>), dim3((unsigned)nb), dim3(256), 0, st, N, (int)q, d_Z, d_W, d_M, d_partial);
-    hipLaunchKernelGGL(k_md_finish, dim3((unsigned)nv), dim3(256), 0, st, nb, d_partial, d_out);
-    HIPCHK(ctx, hipGetLastError());
     std::vector<double> out((size_t)nv);
-    HIPCHK(ctx, hipMemcpyAsync(out.data(), d_out, (size_t)nv * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    STANCHK(finish_sums(ctx, nb, out.size(), d_partial, d_out, out.data()));
     for (int k = 0; k < q * q; k++) { A[k] = out[(size_t)k]; B[k] = out[(size_t)(q * q + k)]; }
     return STAN_OK;
 }
@@ -469,58 +516,25 @@ int stan_modal_rotate_device(stan_ctx *ctx, int64_t N, int32_t q, const double *
                              double *rho2) {
     STANCHK(block_args_check(ctx, "block_rotate", N, q));
     hipStream_t st = ctx->stream;
-    const int QT = q <= 8 ? 8 : q <= 16 ? 16 : q <= 24 ? 24 : 32;
-    const int64_t nb = nblk(N, 256);
-    std::vector<double> Qp((size_t)QT * QT, 0.0);   // outlives the stream's copy
-    md_cols cols;
-    for (int l = 0; l < QMAX; l++) { cols.lambda[l] = l < q ? lambda[l] : 0.0; cols.dcol[l] = -1; }
-    for (int l = 0; l < q; l++)
-        for (int j = 0; j < q; j++) Qp[(size_t)l * QT + j] = Q[l * q + j];
-    dev_scope tmp(ctx);
-    double *d_Qp, *d_partial, *d_out;
-    STANCHK(tmp.alloc(&d_Qp, Qp.size()));
-    STANCHK(tmp.alloc(&d_partial, (size_t)q * (size_t)nb));
-    STANCHK(tmp.alloc(&d_out, (size_t)q));
-    HIPCHK(ctx, hipMemcpyAsync(d_Qp, Qp.data(), Qp.size() * 8, hipMemcpyHostToDevice, st));
-    const unsigned g = (unsigned)nb;
-    if (QT == 8) launch_rotate<8>(st, g, N, q, d_Z, d_W, d_M, d_Qp, cols, mask, d_X, d_KX, d_rhs, d_partial);
-    else if (QT == 16) launch_rotate<16>(st, g, N, q, d_Z, d_W, d_M, d_Qp, cols, mask, d_X, d_KX, d_rhs, d_partial);
-    else if (QT == 24) launch_rotate<24>(st, g, N, q, d_Z, d_W, d_M, d_Qp, cols, mask, d_X, d_KX, d_rhs, d_partial);
-    else launch_rotate<32>(st, g, N, q, d_Z, d_W, d_M, d_Qp, cols, mask, d_X, d_KX, d_rhs, d_partial);
-    hipLaunchKernelGGL(k_md_finish, dim3((unsigned)q), dim3(256), 0, st, nb, d_partial, d_out);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(rho2, d_out, (size_t)q * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return STAN_OK;
+    rotate_call c(ctx);
+    STANCHK(c.prepare(N, q, Q, lambda, (size_t)q));
+    with_qt(c.QT, [&](auto qt) {
+        hipLaunchKernelGGL(k_md_rotate<decltype(qt)::value>, dim3((unsigned)c.nb), dim3(256), 0, st, N, (int)q, d_Z, d_W, d_M, c.d_Qp,
+                           c.cols, mask, d_X, d_KX, d_rhs, c.d_partial);
+    });
+    return finish_sums(ctx, c.nb, (size_t)q, c.d_partial, c.d_out, rho2);
 }
 
 int stan_modal_axpy_device(stan_ctx *ctx, int64_t N, int32_t q, const double *d_X, const double *lambda, const int32_t *dcol,
                            const double *d_D, double *d_Z) {
-    STANCHK(block_args_check(ctx, "modes", N, q));
-    md_cols cols;
-    for (int l = 0; l < QMAX; l++) { cols.lambda[l] = l < q ? lambda[l] : 1.0; cols.dcol[l] = l < q ? dcol[l] : -1; }
-    hipLaunchKernelGGL(k_md_axpy, dim3(nblk(N, 256), (unsigned)q), dim3(256), 0, ctx->stream, N, d_X, cols, d_D, d_Z);
-    HIPCHK(ctx, hipGetLastError());
-    return STAN_OK;
+    return block_axpy(ctx, "modes", k_md_axpy, N, q, d_X, lambda, dcol, d_D, d_Z);
 }
 
 int stan_modal_normalise_device(stan_ctx *ctx, int64_t N, int32_t k, const double *d_X, const double *d_M, double *d_phi) {
-    STANCHK(block_args_check(ctx, "modes", N, k));
-    hipStream_t st = ctx->stream;
-    const int64_t nb = nblk(N, RT_ROWS);
-    dev_scope tmp(ctx);
-    double *d_psum, *d_pval, *d_scale;
-    long long *d_pidx;
-    STANCHK(tmp.alloc(&d_psum, (size_t)k * (size_t)nb));
-    STANCHK(tmp.alloc(&d_pval, (size_t)k * (size_t)nb));
-    STANCHK(tmp.alloc(&d_pidx, (size_t)k * (size_t)nb));
-    STANCHK(tmp.alloc(&d_scale, (size_t)k));
-    hipLaunchKernelGGL(k_md_colstats, dim3((unsigned)nb, (unsigned)k), dim3(256), 0, st, N, d_X, d_M, d_psum, d_pval, d_pidx);
-    hipLaunchKernelGGL(k_md_colfinish, dim3((unsigned)k), dim3(256), 0, st, nb, d_psum, d_pval, d_pidx, d_scale);
-    hipLaunchKernelGGL(k_md_scale, dim3(nblk(N, 256), (unsigned)k), dim3(256), 0, st, N, d_X, d_scale, d_phi);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipStreamSynchronize(st));   // the temporaries go back to the context behind the kernels
-    return STAN_OK;
+    return block_normalise(ctx, "modes", N, k, d_X, d_phi, true, [&](hipStream_t st, dim3 rows, dim3 cols, int64_t nb, const normalise_tmp &t) {
+        hipLaunchKernelGGL(k_md_colstats, rows, dim3(256), 0, st, N, d_X, d_M, t.psum, t.pval, t.pidx);
+        hipLaunchKernelGGL(k_md_colfinish, cols, dim3(256), 0, st, nb, t.psum, t.pval, t.pidx, t.scale);
+    });
 }
 
 // ---- the buckling driver's block kernels ----------------------------------------------------------------------------------
@@ -542,63 +556,28 @@ int stan_buckling_rotate_device(stan_ctx *ctx, int64_t N, int32_t q, const doubl
                                 double *d_rhs, double *r2, double *kx2) {
     STANCHK(block_args_check(ctx, "buckling_rotate", N, q));
     hipStream_t st = ctx->stream;
-    const int QT = q <= 8 ? 8 : q <= 16 ? 16 : q <= 24 ? 24 : 32;
-    const int64_t nb = nblk(N, 256);
-    std::vector<double> Qp((size_t)QT * QT, 0.0);   // outlives the stream's copy
-    md_cols cols;
-    for (int l = 0; l < QMAX; l++) { cols.lambda[l] = l < q ? mu[l] : 0.0; cols.dcol[l] = -1; }
-    for (int l = 0; l < q; l++)
-        for (int j = 0; j < q; j++) Qp[(size_t)l * QT + j] = Q[l * q + j];
-    dev_scope tmp(ctx);
-    double *d_Qp, *d_partial, *d_out;
-    STANCHK(tmp.alloc(&d_Qp, Qp.size()));
-    STANCHK(tmp.alloc(&d_partial, 2 * (size_t)q * (size_t)nb));
-    STANCHK(tmp.alloc(&d_out, 2 * (size_t)q));
-    HIPCHK(ctx, hipMemcpyAsync(d_Qp, Qp.data(), Qp.size() * 8, hipMemcpyHostToDevice, st));
-    const dim3 g((unsigned)nb), b(256);
-#define STAN_BK_LAUNCH(QTV)                                                                                                      \
-    do {                                                                                                                         \
-        hipLaunchKernelGGL(k_bk_rotate_x<QTV>, g, b, 0, st, N, (int)q, d_Z, d_Qp, d_X);                                          \
-        hipLaunchKernelGGL(k_bk_residual<QTV>, g, b, 0, st, N, (int)q, d_W, d_Y, d_D, d_Qp, cols, mask, d_KX, d_rhs, d_partial); \
-    } while (0)
-    if (QT == 8) STAN_BK_LAUNCH(8);
-    else if (QT == 16) STAN_BK_LAUNCH(16);
-    else if (QT == 24) STAN_BK_LAUNCH(24);
-    else STAN_BK_LAUNCH(32);
-#undef STAN_BK_LAUNCH
-    hipLaunchKernelGGL(k_md_finish, dim3(2 * (unsigned)q), dim3(256), 0, st, nb, d_partial, d_out);
-    HIPCHK(ctx, hipGetLastError());
+    rotate_call c(ctx);
+    STANCHK(c.prepare(N, q, Q, mu, 2 * (size_t)q));
+    with_qt(c.QT, [&](auto qt) {
+        constexpr int QT = decltype(qt)::value;
+        const dim3 g((unsigned)c.nb), b(256);
+        hipLaunchKernelGGL(k_bk_rotate_x<QT>, g, b, 0, st, N, (int)q, d_Z, c.d_Qp, d_X);
+        hipLaunchKernelGGL(k_bk_residual<QT>, g, b, 0, st, N, (int)q, d_W, d_Y, d_D, c.d_Qp, c.cols, mask, d_KX, d_rhs, c.d_partial);
+    });
     std::vector<double> out(2 * (size_t)q);
-    HIPCHK(ctx, hipMemcpyAsync(out.data(), d_out, out.size() * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    STANCHK(finish_sums(ctx, c.nb, out.size(), c.d_partial, c.d_out, out.data()));
     for (int j = 0; j < q; j++) { r2[j] = out[(size_t)j]; kx2[j] = out[(size_t)(q + j)]; }
     return STAN_OK;
 }
 
 int stan_buckling_axpy_device(stan_ctx *ctx, int64_t N, int32_t q, const double *d_X, const double *mu, const int32_t *dcol,
                               const double *d_D, double *d_Z) {
-    STANCHK(block_args_check(ctx, "buckling", N, q));
-    md_cols cols;
-    for (int l = 0; l < QMAX; l++) { cols.lambda[l] = l < q ? mu[l] : 0.0; cols.dcol[l] = l < q ? dcol[l] : -1; }
-    hipLaunchKernelGGL(k_bk_axpy, dim3(nblk(N, 256), (unsigned)q), dim3(256), 0, ctx->stream, N, d_X, cols, d_D, d_Z);
-    HIPCHK(ctx, hipGetLastError());
-    return STAN_OK;
+    return block_axpy(ctx, "buckling", k_bk_axpy, N, q, d_X, mu, dcol, d_D, d_Z);
 }
 
 int stan_buckling_normalise_device(stan_ctx *ctx, int64_t N, int32_t k, const double *d_X, double *d_phi) {
-    STANCHK(block_args_check(ctx, "buckling", N, k));
-    hipStream_t st = ctx->stream;
-    const int64_t nb = nblk(N, RT_ROWS);
-    dev_scope tmp(ctx);
-    double *d_pval, *d_scale;
-    long long *d_pidx;
-    STANCHK(tmp.alloc(&d_pval, (size_t)k * (size_t)nb));
-    STANCHK(tmp.alloc(&d_pidx, (size_t)k * (size_t)nb));
-    STANCHK(tmp.alloc(&d_scale, (size_t)k));
-    hipLaunchKernelGGL(k_bk_colmax, dim3((unsigned)nb, (unsigned)k), dim3(256), 0, st, N, d_X, d_pval, d_pidx);
-    hipLaunchKernelGGL(k_bk_colmax_finish, dim3((unsigned)k), dim3(256), 0, st, nb, d_pval, d_pidx, d_scale);
-    hipLaunchKernelGGL(k_md_scale, dim3(nblk(N, 256), (unsigned)k), dim3(256), 0, st, N, d_X, d_scale, d_phi);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipStreamSynchronize(st));   // the temporaries go back to the context behind the kernels
-    return STAN_OK;
+    return block_normalise(ctx, "buckling", N, k, d_X, d_phi, false, [&](hipStream_t st, dim3 rows, dim3 cols, int64_t nb, const normalise_tmp &t) {
+        hipLaunchKernelGGL(k_bk_colmax, rows, dim3(256), 0, st, N, d_X, t.pval, t.pidx);
+        hipLaunchKernelGGL(k_bk_colmax_finish, cols, dim3(256), 0, st, nb, t.pval, t.pidx, t.scale);
+    });
 }

@@ -9,8 +9,8 @@
 //            the workgroup's sums of 1/2 v' M v', 1/2 u' (K u'), g F u' from the same pass
 //   probe    row[j] = u[probe[j]]
 // Bit-reproducible: no atomics on doubles; a workgroup's sum has a fixed order (block_sums), the workgroups' partial sums are
-// added in workgroup order by one workgroup per value (k_nm_finish, as k_md_finish of modal.hip).
-#include "elem_pass.h"   // block_sums
+// added in workgroup order by one workgroup per value (k_finish_sums of elem_pass.h, which modal.hip uses too).
+#include "elem_pass.h"   // block_sums, k_finish_sums
 
 namespace {
 
@@ -121,17 +121,6 @@ k_nm_energy(int64_t N, const double *__restrict__ u, const double *__restrict__ 
     nm_energy_out(s, partial);
 }
 
-// out[v] = the sum of partial[v][0 .. n_blocks) in block order: one workgroup per value
-__global__ void __launch_bounds__(NM_T)
-k_nm_finish(int64_t n_blocks, const double *__restrict__ partial, double *__restrict__ out) {
-    __shared__ double sh[4][1];
-    double s[1] = {0.0};
-    const double *p = partial + (int64_t)blockIdx.x * n_blocks;
-    for (int64_t b = threadIdx.x; b < n_blocks; b += NM_T) s[0] += p[b];
-    block_sums(s, sh);
-    if (threadIdx.x == 0) out[blockIdx.x] = s[0];
-}
-
 __global__ void __launch_bounds__(64)
 k_nm_probe(int32_t n_probe, const int32_t *__restrict__ probe, const double *__restrict__ u, double *__restrict__ row) {
     const int32_t j = blockIdx.x * 64 + threadIdx.x;
@@ -195,7 +184,7 @@ int stan_newmark_correct_device(stan_ctx *ctx, int64_t N, const stan_newmark_coe
     const unsigned g = nm_grid(N);
     if (d_energy) {
         hipLaunchKernelGGL(k_nm_correct<true>, dim3(g), dim3(NM_T), 0, ctx->stream, N, c, u_new, u, v, a, M, F, Ku, gF, d_partial);
-        hipLaunchKernelGGL(k_nm_finish, dim3(3), dim3(NM_T), 0, ctx->stream, (int64_t)g, d_partial, d_energy);
+        hipLaunchKernelGGL(k_finish_sums<NM_T>, dim3(3), dim3(NM_T), 0, ctx->stream, (int64_t)g, d_partial, d_energy);
     } else
         hipLaunchKernelGGL(k_nm_correct<false>, dim3(g), dim3(NM_T), 0, ctx->stream, N, c, u_new, u, v, a, M, F, Ku, gF, d_partial);
     HIPCHK(ctx, hipGetLastError());
@@ -207,7 +196,7 @@ int stan_newmark_energy_device(stan_ctx *ctx, int64_t N, const double *u, const 
     STANCHK(nm_args(ctx, N));
     const unsigned g = nm_grid(N);
     hipLaunchKernelGGL(k_nm_energy, dim3(g), dim3(NM_T), 0, ctx->stream, N, u, v, M, F, Ku, gF, d_partial);
-    hipLaunchKernelGGL(k_nm_finish, dim3(3), dim3(NM_T), 0, ctx->stream, (int64_t)g, d_partial, d_energy);
+    hipLaunchKernelGGL(k_finish_sums<NM_T>, dim3(3), dim3(NM_T), 0, ctx->stream, (int64_t)g, d_partial, d_energy);
     HIPCHK(ctx, hipGetLastError());
     return STAN_OK;
 }
@@ -220,15 +209,9 @@ int stan_newmark_probe_device(stan_ctx *ctx, int32_t n_probe, const int32_t *d_p
 }
 
 int stan_newmark_probe_check_device(stan_ctx *ctx, int64_t N, int32_t n_probe, const int32_t *d_probe, int64_t *bad) {
-    hipStream_t st = ctx->stream;
-    const long long none = 0x7fffffffffffffffLL;
     *bad = -1;
     if (n_probe <= 0) return STAN_OK;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_status + SS_AUX, &none, 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_nm_probe_check, dim3(nblk(n_probe, 64)), dim3(64), 0, st, N, n_probe, d_probe, (long long *)(ctx->d_status + SS_AUX));
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_AUX, ctx->d_status + SS_AUX, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (ctx->h_status[SS_AUX] != none) *bad = ctx->h_status[SS_AUX];
-    return STAN_OK;
+    return stan_first_offender(ctx, bad, [&](long long *slot) {
+        hipLaunchKernelGGL(k_nm_probe_check, dim3(nblk(n_probe, 64)), dim3(64), 0, ctx->stream, N, n_probe, d_probe, slot);
+    });
 }
