@@ -900,6 +900,84 @@ int stan_hip_buckling_rotate(stan_ctx *ctx, int64_t N, int32_t q, const double *
                              const double *D, const double *Q, const double *mu, double *X, double *KX, double *R, double *r2,
                              double *kx2);
 
+/* ---- consistent mass: M_c on K's layout, A + sigma B, modes on the pencil ------------------------ */
+/* No step of the reference.  The element scalars of the consistent mass of n HEX8 elements
+ * (introspection, as stan_hip_kg_hex8_batch is):
+ *   m[a][b] = rho sum_g N_a(q_g) N_b(q_g) det J_g w_g
+ * over the 2 x 2 x 2 Gauss rule for both element types (the rule of the lumped mass, stan_hip_lumped_mass_hex8: a one-point rule
+ * would leave the matrix singular); the element matrix is m (x) I_3.  m36 [n*36]: per element the upper triangle of the
+ * symmetric 8 x 8 m, row-major ((a, b), a <= b, at a*8 - a(a-1)/2 + b - a).  xyz8 [n*24], host pointers.  The values are those
+ * of the element pass of stan_hip_consistent_mass_hex8 (the same kernel); two calls give the same bits.
+ * STAN_E_ARG: a rho that is not positive and finite.  STAN_E_DETJ (element via stan_hip_last_bad_element) when det J == 0 at a
+ * point of an element. */
+int stan_hip_mass_hex8_batch(stan_ctx *ctx, int64_t n, const double *xyz8, double rho, double *m36);
+/* *out becomes a NEW matrix of this context that holds the consistent mass M_c of the mesh K was assembled from, mat_rho [n_mat]
+ * the densities (host memory in both entries, as mat_E_nu is).  It has K's layout (its structure arrays are copied) and a value
+ * array of its own, placed as an assembled matrix's is; it is unscaled and carries no derived stream, whatever K's state:
+ * stan_hip_spmv, stan_hip_cg_solve, stan_hip_matrix_to_csr, stan_hip_matrix_info, stan_hip_matrix_axpy and stan_hip_modes_pencil
+ * take it and treat it as they treat an assembled K.  It is freed with stan_hip_matrix_free and does not depend on K's lifetime.
+ *   values  as stan_hip_geometric_stiffness_hex8 stores G, by the same row gather: the block of row node r and column node c
+ *           holds, on its three diagonal components, the sum of m_e[a][b] over the (element e, local node a) incidences of r in
+ *           ascending element order (then a) and, inside one, over b = 0..7 with conn[e][b] = c -- m_e as
+ *           stan_hip_mass_hex8_batch gives it; the six off-diagonal components are 0.  A fixed DOF is stored as the assembly
+ *           stores it: a zero row and column, 1 on the diagonal.
+ * Every value is written once, by one lane, in a fixed order, with no atomics on doubles: two calls give the same bits, and so
+ * do the host and the _dev entry.  K itself is read only -- its values are not read at all: its values, its scaled flag and
+ * its streams are unchanged to the bit.
+ * STAN_E_ARG: as stan_hip_geometric_stiffness_hex8; an element whose material's density is not positive and finite (found
+ * before the element scalars or the matrix are allocated; a material no element uses is not looked at).  STAN_E_DOF_LAYOUT,
+ * STAN_E_DETJ and STAN_E_UNSUPPORTED as there.  On an error *out is not written and what the call had allocated is given back. */
+int stan_hip_consistent_mass_hex8(stan_ctx *ctx, stan_matrix *K, int64_t n_nodes, const double *xyz, const double *mat_rho,
+                                  const int32_t *node_dof, int64_t n_elem, const int32_t *conn, const int32_t *elem_mat,
+                                  const uint8_t *elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
+                                  const int32_t *ndof_reduction, stan_matrix **out);
+/* The same with every array except mat_rho and mat_E_nu in device memory on the context's GPU: read only, ready on the context's
+ * stream, naturally aligned; complete on return. */
+int stan_hip_consistent_mass_hex8_dev(stan_ctx *ctx, stan_matrix *K, int64_t n_nodes, const double *d_xyz, const double *mat_rho,
+                                      const int32_t *d_node_dof, int64_t n_elem, const int32_t *d_conn, const int32_t *d_elem_mat,
+                                      const uint8_t *d_elem_type, int32_t n_mat, const double *mat_E_nu, int64_t n_dof,
+                                      const int32_t *d_ndof_reduction, stan_matrix **out);
+/* Phase times of the most recent consistent-mass call on this context, by HIP events (profiling must be enabled first), as
+ * stan_hip_geometric_stiffness_times gives them: ms[0] the element pass, ms[1] the copy of K's layout with the allocation of the
+ * value array, ms[2] the node -> (element, corner) lists and the row maps, ms[3] the row gather; ms[4] the value pass of the
+ * most recent stan_hip_matrix_axpy. */
+int stan_hip_consistent_mass_times(stan_ctx *ctx, double ms[5]);
+/* *out becomes a NEW matrix of this context that holds A + sigma B, A and B two matrices of this context on ONE layout (an
+ * assembled K and what stan_hip_consistent_mass_hex8, stan_hip_geometric_stiffness_hex8, stan_hip_matrix_shifted or this entry
+ * made on it); sigma any finite value (a negative one may give an indefinite matrix: the CG reports that as it does for any).
+ * It has the common layout (A's structure arrays are copied) and a value array of its own, placed as an assembled matrix's is;
+ * it is unscaled and carries no derived stream: every entry that takes a matrix takes it.
+ *   values  a free entry is fma(sigma, b, a), a and b the values stan_hip_matrix_to_csr exports for A and for B (a matrix'
+ *           bits while it is unscaled, divided by its own s_row s_col once a solve has left S K S in place): one rounding on
+ *           top of the exports; fixed DOFs and padding are copied from A as they are.
+ * "One layout" is checked, not assumed: the sizes on the host, the slice pointers, row lengths, row order, columns, fixed-DOF
+ * masks and reduction maps by a comparison on the device, before anything is allocated.  A and B are read only: their values,
+ * scaled flags and streams are unchanged to the bit.  No atomics on doubles: two calls give the same bits.
+ * STAN_E_ARG: a NULL pointer, a matrix of another context, sigma not finite, two layouts that differ.  STAN_E_UNSUPPORTED: a
+ * multi-device handle, a context with a communicator.  STAN_E_ALLOC: what the call had allocated is given back.  On an error
+ * *out is not written. */
+int stan_hip_matrix_axpy(stan_ctx *ctx, stan_matrix *A, double sigma, stan_matrix *B, stan_matrix **out);
+/* The n_modes lowest eigenpairs of K phi = lambda Mmat phi on the free DOFs: K a matrix of this context (positive definite: a
+ * supported model, or K + sigma M_c by stan_hip_matrix_axpy for a free-free one, whose values are lambda + sigma), Mmat a mass
+ * matrix on K's layout (stan_hip_consistent_mass_hex8).  The loop is that of stan_hip_buckling with H = +Mmat and no negation:
+ * the n_modes largest positive mu of Mmat x = mu K x with the same block size, start block, products, sums, host eigenproblem,
+ * correction solves (merit stop off) and stop test, rho_j = ||mu_j K x_j - Mmat x_j||_{D^-1} / (mu_j ||K x_j||_{D^-1}), D = diag K.
+ * tol, max_outer, solve_eps and solve_max_its and their zeros as there.
+ * Outputs: lambda [n_modes] = 1 / mu_j, ascending; phi [n_modes][N], each scaled so that phi_j^T Mmat phi_j = 1 -- the scale
+ * from one true product Mmat x_j at the end, a term of the sum one fused multiply-add, per-workgroup sums in a fixed order added
+ * in workgroup order -- with its entry of largest magnitude positive (the lowest index on a tie); rho [n_modes] as computed on
+ * the final vectors.  rep: a stan_buckling_report or NULL (void * as for stan_hip_modes): n_positive counts the mu > 0 of the
+ * final block, lowest_negative_factor is 1 / mu of the most negative one (0: none; a mass that is positive definite has none).
+ * When the final block holds n_positive < n_modes positive mu (a mass that is not positive definite) the call returns STAN_OK
+ * with converged = 0: the first n_positive outputs are filled, the rest are zeros.  STAN_OK with converged = 0 also when
+ * max_outer runs out.  K is left as any solve leaves it; Mmat is unchanged to the bit.  Two calls give the same bits, and so do
+ * the host and the _dev entry; _dev stores all of d_lambda, d_phi, d_rho and nothing beside them.
+ * Errors as stan_hip_buckling, with Mmat in G's place. */
+int stan_hip_modes_pencil(stan_ctx *ctx, stan_matrix *K, stan_matrix *Mmat, int32_t n_modes, double tol, int32_t max_outer,
+                          double solve_eps, int32_t solve_max_its, double *lambda, double *phi, double *rho, void *rep);
+int stan_hip_modes_pencil_dev(stan_ctx *ctx, stan_matrix *K, stan_matrix *Mmat, int32_t n_modes, double tol, int32_t max_outer,
+                              double solve_eps, int32_t solve_max_its, double *d_lambda, double *d_phi, double *d_rho, void *rep);
+
 /* ---- transient dynamics: the shifted matrix K + sigma M and implicit Newmark steps ------------- */
 /* No step of the reference.  *out becomes a NEW matrix of this context that holds K + sigma diag(M)
  * on the free DOFs: M [N] the diagonal mass in the reduced numbering (stan_hip_lumped_mass_hex8), sigma >= 0.  It has K's

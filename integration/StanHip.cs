@@ -330,6 +330,27 @@ namespace STAN_Solver
             IntPtr ctx, long N, int q, double[] Z, double[] W, double[] Y, double[] D, double[] Q, double[] mu,
             [Out] double[] X, [Out] double[] KX, [Out] double[] R, [Out] double[] r2, [Out] double[] kx2);
 
+        // ---- consistent mass: m36 [n * 36]; Mc = the mass on K's layout and sum = A + sigma B (both freed with
+        //      stan_hip_matrix_free); mat_rho [n_mat] host memory in both entries; ms [5]; lambda / rho [n_modes], phi
+        //      [n_modes * N]; rep -> a stan_buckling_report or IntPtr.Zero
+        [DllImport(Lib)] internal static extern int stan_hip_mass_hex8_batch(
+            IntPtr ctx, long n, double[] xyz8, double rho, [Out] double[] m36);
+        [DllImport(Lib)] internal static extern int stan_hip_consistent_mass_hex8(
+            IntPtr ctx, IntPtr K, long n_nodes, double[] xyz, double[] mat_rho, int[] node_dof, long n_elem, int[] conn, int[] elem_mat,
+            byte[] elem_type, int n_mat, double[] mat_E_nu, long n_dof, int[] ndof_reduction, out IntPtr Mc);
+        [DllImport(Lib)] internal static extern int stan_hip_consistent_mass_hex8_dev(
+            IntPtr ctx, IntPtr K, long n_nodes, IntPtr d_xyz, double[] mat_rho, IntPtr d_node_dof, long n_elem, IntPtr d_conn,
+            IntPtr d_elem_mat, IntPtr d_elem_type, int n_mat, double[] mat_E_nu, long n_dof, IntPtr d_ndof_reduction, out IntPtr Mc);
+        [DllImport(Lib)] internal static extern int stan_hip_consistent_mass_times(IntPtr ctx, [Out] double[] ms);
+        [DllImport(Lib)] internal static extern int stan_hip_matrix_axpy(
+            IntPtr ctx, IntPtr A, double sigma, IntPtr B, out IntPtr sum);
+        [DllImport(Lib)] internal static extern int stan_hip_modes_pencil(
+            IntPtr ctx, IntPtr K, IntPtr Mmat, int n_modes, double tol, int max_outer, double solve_eps, int solve_max_its,
+            [Out] double[] lambda, [Out] double[] phi, [Out] double[] rho, IntPtr rep);
+        [DllImport(Lib)] internal static extern int stan_hip_modes_pencil_dev(
+            IntPtr ctx, IntPtr K, IntPtr Mmat, int n_modes, double tol, int max_outer, double solve_eps, int solve_max_its,
+            IntPtr d_lambda, IntPtr d_phi, IntPtr d_rho, IntPtr rep);
+
         // ---- transient dynamics: M, F, u0, v0 (or null) [N]; curve_t / curve_g [n_curve] or null; probe_dof [n_probe], probe_u
         //      [(n_steps + 1) * n_probe], snaps [n_snap * 3 * N], energy [(n_steps + 1) * 3] or null; rep -> StanTransientReport or
         //      IntPtr.Zero.  The step helpers take coef [8]; u, v, a of correct are pinned and updated in place

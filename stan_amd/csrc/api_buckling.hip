@@ -20,9 +20,11 @@ int kg_args(stan_ctx *ctx, const char *who, stan_matrix *K, stan_matrix **out, b
 
 // The driver on device arrays: d_factor / d_rho [k], d_phi [k][N].  With H = -G the k largest positive mu of H x = mu K x by
 // block inverse iteration in correction form with a Rayleigh-Ritz step; factor = 1 / mu.
-int buckling_device(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, int32_t k, double tol, int32_t max_outer, double solve_eps,
+// pencil (stan_hip_modes_pencil, section 3.13): the same loop with H = +G, G a mass matrix, so that 1 / mu are the eigenvalues of
+// K phi = lambda G phi, and the vectors scaled to phi^T G phi = 1 by one true product at the end.
+int buckling_device(stan_ctx *ctx, bool pencil, stan_matrix *K, stan_matrix *G, int32_t k, double tol, int32_t max_outer, double solve_eps,
                     int32_t solve_max_its, double *d_factor, double *d_phi, double *d_rho, stan_buckling_report *rep) {
-    block_run<stan_buckling_report> run(ctx, K, "buckling", k, tol, max_outer, solve_eps, solve_max_its);
+    block_run<stan_buckling_report> run(ctx, K, pencil ? "modes_pencil" : "buckling", k, tol, max_outer, solve_eps, solve_max_its);
     STANCHK(run.begin(rep));
     stan_buckling_report &R = run.R;
     piece_timer &pt = run.pt;
@@ -42,8 +44,9 @@ int buckling_device(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, int32_t k, do
     STANCHK(tmp.alloc(&D, qn));
     STANCHK(tmp.alloc(&dg, (size_t)N));
 
-    // out_j = H in_j = -(G in_j), q true products; the negation is exact
+    // out_j = H in_j = -(G in_j), q true products; the negation is exact (pencil: H = G, no negation)
     auto h_products = [&](const double *in, double *out) -> int {
+        if (pencil) return run.products(G, in, out);
         return run.products(G, in, out, [&] { return stan_buckling_negate_device(ctx, (int64_t)qn, out); });
     };
     pt.begin();
@@ -104,20 +107,28 @@ int buckling_device(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, int32_t k, do
     std::vector<double> fac((size_t)k, 0.0), rh((size_t)k, 0.0);
     for (int j = 0; j < kk; j++) { fac[(size_t)j] = 1.0 / mu[(size_t)j]; rh[(size_t)j] = rho[(size_t)j]; }
     HIPCHK(ctx, hipMemsetAsync(d_phi, 0, (size_t)k * (size_t)N * 8, st));
+    if (pencil && kk > 0) {   // phi_j^T G phi_j = 1: the scale from kk true products
+        pt.begin();
+        for (int j = 0; j < kk; j++) STANCHK(stan_spmv_reduced(ctx, G, Z + (size_t)j * N, Y + (size_t)j * N));
+        pt.end(&R.product_ms);
+    }
     pt.begin();
-    if (kk > 0) STANCHK(stan_buckling_normalise_device(ctx, N, kk, Z, d_phi));
+    if (kk > 0) STANCHK(pencil ? stan_pencil_normalise_device(ctx, N, kk, Z, Y, d_phi) : stan_buckling_normalise_device(ctx, N, kk, Z, d_phi));
     pt.end(&R.block_ms);
     return run.finish(fac.data(), rh.data(), d_factor, d_rho);
 }
 
-int buckling_args(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, const void *factor, const void *phi, const void *rho) {
+int buckling_args(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, const void *factor, const void *phi, const void *rho,
+                  bool pencil = false) {
     if (!ctx) return STAN_E_ARG;
-    STANCHK(block_driver_refused(ctx, "buckling"));
-    if (!K || !G || !factor || !phi || !rho) { ctx->err = "buckling: null argument"; return STAN_E_ARG; }
-    if (K->ctx != ctx || G->ctx != ctx) { ctx->err = "buckling: K or G belongs to another context"; return STAN_E_ARG; }
+    const std::string who = pencil ? "modes_pencil" : "buckling", G_name = pencil ? "Mmat" : "G";
+    STANCHK(block_driver_refused(ctx, who.c_str()));
+    if (!K || !G || !factor || !phi || !rho) { ctx->err = who + ": null argument"; return STAN_E_ARG; }
+    if (K->ctx != ctx || G->ctx != ctx) { ctx->err = who + ": K or " + G_name + " belongs to another context"; return STAN_E_ARG; }
     if (G->n_dof != K->n_dof || G->n_red != K->n_red || G->nb_glob != K->nb_glob || G->nloc != K->nloc || G->nslices != K->nslices ||
         G->nslots != K->nslots || G->nblocks != K->nblocks || G->sigma != K->sigma) {
-        ctx->err = "buckling: G does not have K's layout (build it with stan_hip_geometric_stiffness_hex8 on this K)";
+        ctx->err = who + ": " + G_name + " does not have K's layout (build it with " +
+                   (pencil ? "stan_hip_consistent_mass_hex8" : "stan_hip_geometric_stiffness_hex8") + " on this K)";
         return STAN_E_ARG;
     }
     return STAN_OK;
@@ -131,7 +142,7 @@ int stan_hip_buckling_dev(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, int32_t
                           double solve_eps, int32_t solve_max_its, double *d_factor, double *d_phi, double *d_rho, void *rep) {
     STANCHK(buckling_args(ctx, K, G, d_factor, d_phi, d_rho));
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    return buckling_device(ctx, K, G, n_modes, tol, max_outer, solve_eps, solve_max_its, d_factor, d_phi, d_rho, (stan_buckling_report *)rep);
+    return buckling_device(ctx, false, K, G, n_modes, tol, max_outer, solve_eps, solve_max_its, d_factor, d_phi, d_rho, (stan_buckling_report *)rep);
 }
 
 int stan_hip_buckling(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, int32_t n_modes, double tol, int32_t max_outer, double solve_eps,
@@ -145,8 +156,32 @@ int stan_hip_buckling(stan_ctx *ctx, stan_matrix *K, stan_matrix *G, int32_t n_m
     STANCHK(df.alloc(st, k, factor));
     STANCHK(dp.alloc(st, k * N, phi));
     STANCHK(dr.alloc(st, k, rho));
-    const int rc = buckling_device(ctx, K, G, n_modes, tol, max_outer, solve_eps, solve_max_its, df.p, dp.p, dr.p, (stan_buckling_report *)rep);
+    const int rc = buckling_device(ctx, false, K, G, n_modes, tol, max_outer, solve_eps, solve_max_its, df.p, dp.p, dr.p, (stan_buckling_report *)rep);
     return st.finish(rc, df, dp, dr);
+}
+
+int stan_hip_modes_pencil_dev(stan_ctx *ctx, stan_matrix *K, stan_matrix *Mmat, int32_t n_modes, double tol, int32_t max_outer,
+                              double solve_eps, int32_t solve_max_its, double *d_lambda, double *d_phi, double *d_rho, void *rep) {
+    STANCHK(buckling_args(ctx, K, Mmat, d_lambda, d_phi, d_rho, true));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    return buckling_device(ctx, true, K, Mmat, n_modes, tol, max_outer, solve_eps, solve_max_its, d_lambda, d_phi, d_rho,
+                           (stan_buckling_report *)rep);
+}
+
+int stan_hip_modes_pencil(stan_ctx *ctx, stan_matrix *K, stan_matrix *Mmat, int32_t n_modes, double tol, int32_t max_outer,
+                          double solve_eps, int32_t solve_max_its, double *lambda, double *phi, double *rho, void *rep) {
+    STANCHK(buckling_args(ctx, K, Mmat, lambda, phi, rho, true));
+    if (n_modes <= 0 || n_modes > K->n_red) { ctx->err = "modes_pencil: n_modes must be in [1, N]"; return STAN_E_ARG; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t N = (size_t)K->n_red, k = (size_t)n_modes;
+    host_stage st(ctx);
+    dbuf<double> dl, dp, dr;
+    STANCHK(dl.alloc(st, k, lambda));
+    STANCHK(dp.alloc(st, k * N, phi));
+    STANCHK(dr.alloc(st, k, rho));
+    const int rc = buckling_device(ctx, true, K, Mmat, n_modes, tol, max_outer, solve_eps, solve_max_its, dl.p, dp.p, dr.p,
+                                   (stan_buckling_report *)rep);
+    return st.finish(rc, dl, dp, dr);
 }
 
 int stan_hip_buckling_rotate(stan_ctx *ctx, int64_t N, int32_t q, const double *Z, const double *W, const double *Y, const double *D,

@@ -20,6 +20,13 @@
 // reads pair up into ds_read_b128.
 constexpr int ELEM_REC = 50;
 
+// The element scalars of geometric.hip and mass.hip, one per node pair: the upper triangle of the symmetric 8 x 8, row-major:
+// (a, b), a <= b, at a * 8 - a (a - 1) / 2 + b - a
+constexpr int KG_N = 36;
+__host__ __device__ constexpr int kg_index(int a, int b) {
+    return (a <= b ? a * 8 - a * (a - 1) / 2 + (b - a) : b * 8 - b * (b - 1) / 2 + (a - b));
+}
+
 // wave-local exchange through LDS: the LDS executes one wave's instructions in order (as in k_spmv_fold), so a wave-level
 // fence is all that the lanes of one wave need between a write and another lane's read
 __device__ __forceinline__ void wave_sync() {

@@ -12,16 +12,13 @@
 //                 components of the block, the essential BCs are applied as k_numeric applies them, and every value of
 //                 the array -- padding included -- is stored exactly once.
 // stan_hip_kg_hex8_batch runs k_kg_elem itself on the batch (its elements' corners numbered 0 .. 8n - 1).
+// The row gather with its maps, its host half and the batch numbering serve every matrix of element scalars s_e (x) I_3: the
+// consistent mass of mass.hip is built by stan_elem_scalars_matrix too.
 #include "elem_pass.h"
 
 namespace {
 
 constexpr long long NONE = 0x7fffffffffffffffLL;
-constexpr int KG_N = 36;   // the upper triangle of the 8 x 8 scalars, row-major: (a, b), a <= b, at a * 8 - a (a - 1) / 2 + b - a
-
-__host__ __device__ constexpr int kg_index(int a, int b) {
-    return (a <= b ? a * 8 - a * (a - 1) / 2 + (b - a) : b * 8 - b * (b - 1) / 2 + (a - b));
-}
 
 // ---- element pass: s36 [n_elem][36] --------------------------------------------------------------------------------------
 // Lane mapping, record load and Gauss point are elem_pass.h's; strain and stress are hex8_strain / hex8_stress.  Lane g holds
@@ -87,6 +84,26 @@ k_kg_elem(int64_t n_elem, const double *__restrict__ xyz, const double *__restri
     }
 }
 
+// the element pass on a device view whose integers have been checked; d_s36 [n_elem][36]; pt (may be null): marks 0 and 1
+// around the kernel
+int kg_elem_pass(stan_ctx *ctx, dev_scope &tmp, const stan_mesh &d, double *d_s36, phase_timer *pt = nullptr) {
+    lamG_buf lamG;
+    STANCHK(lamG.alloc(tmp, d.n_mat, d.mat_E_nu));
+    HIPCHK(ctx, lamG.upload(ctx->stream));
+    if (pt) STANCHK(pt->mark(0));
+    if (d.n_elem > 0)   // 8 lanes per element, 8 elements per wave, 32 per workgroup
+        hipLaunchKernelGGL(k_kg_elem, dim3(nblk(d.n_elem, 32)), dim3(256), 0, ctx->stream, d.n_elem, d.xyz, d.disp, d.conn, d.elem_mat,
+                           d.elem_type, lamG.d, d_s36, (long long *)(ctx->d_status + SS_BAD_ELEM));
+    if (pt) STANCHK(pt->mark(1));
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_BAD_ELEM, ctx->d_status + SS_BAD_ELEM, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // lamG's host copy goes with this call
+    return stan_detj_check(ctx, " (geometric stiffness)");
+}
+
+}  // namespace
+
+// ---- what every matrix of element scalars s_e (x) I_3 shares (G here, the consistent mass of mass.hip) ---------------------------
 // the corners of a batch: element e's corner a is "node" 8 e + a, one material
 __global__ void __launch_bounds__(256)
 k_kg_iota(int64_t n8, int32_t *__restrict__ conn, int32_t *__restrict__ elem_mat) {
@@ -166,64 +183,18 @@ k_kg_gather(int32_t nslices, int64_t nloc, const int32_t *__restrict__ slot_ptr,
     if (matched != (p1 - p0) * 8) atomicOr((unsigned long long *)&status[SS_ERRBITS], 1ull);
 }
 
-// the element pass on a device view whose integers have been checked; d_s36 [n_elem][36]; pt (may be null): marks 0 and 1
-// around the kernel
-int kg_elem_pass(stan_ctx *ctx, dev_scope &tmp, const stan_mesh &d, double *d_s36, phase_timer *pt = nullptr) {
-    lamG_buf lamG;
-    STANCHK(lamG.alloc(tmp, d.n_mat, d.mat_E_nu));
-    HIPCHK(ctx, lamG.upload(ctx->stream));
-    if (pt) STANCHK(pt->mark(0));
-    if (d.n_elem > 0)   // 8 lanes per element, 8 elements per wave, 32 per workgroup
-        hipLaunchKernelGGL(k_kg_elem, dim3(nblk(d.n_elem, 32)), dim3(256), 0, ctx->stream, d.n_elem, d.xyz, d.disp, d.conn, d.elem_mat,
-                           d.elem_type, lamG.d, d_s36, (long long *)(ctx->d_status + SS_BAD_ELEM));
-    if (pt) STANCHK(pt->mark(1));
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_BAD_ELEM, ctx->d_status + SS_BAD_ELEM, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // lamG's host copy goes with this call
-    return stan_detj_check(ctx, " (geometric stiffness)");
-}
-
-}  // namespace
-
-int stan_kg_batch_device(stan_ctx *ctx, int64_t n, const double *d_xyz8, const double *d_u8, double E, double nu,
-                         const uint8_t *d_type, double *d_s36) {
-    if (n <= 0) return STAN_OK;
-    if (n >= (int64_t)1 << 28) { ctx->err = "kg_hex8_batch: more than 2^28 elements"; return STAN_E_ARG; }
-    hipStream_t st = ctx->stream;
-    dev_scope tmp(ctx);
-    int32_t *d_conn, *d_mat;
-    STANCHK(tmp.alloc(&d_conn, (size_t)n * 8));
-    STANCHK(tmp.alloc(&d_mat, (size_t)n));
-    hipLaunchKernelGGL(k_kg_iota, dim3(nblk(n * 8, 256)), dim3(256), 0, st, n * 8, d_conn, d_mat);
+int stan_elem_batch_iota(stan_ctx *ctx, int64_t n, int32_t *d_conn, int32_t *d_mat) {
+    hipLaunchKernelGGL(k_kg_iota, dim3(nblk(n * 8, 256)), dim3(256), 0, ctx->stream, n * 8, d_conn, d_mat);
     const long long none = NONE;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_status + SS_BAD_ELEM, &none, 8, hipMemcpyHostToDevice, st));
-    const double E_nu[2] = {E, nu};
-    const stan_mesh d{.n_nodes = n * 8, .n_elem = n, .n_mat = 1, .xyz = d_xyz8, .disp = d_u8, .conn = d_conn, .elem_mat = d_mat,
-                      .elem_type = d_type, .mat_E_nu = E_nu};
-    return kg_elem_pass(ctx, tmp, d, d_s36);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_status + SS_BAD_ELEM, &none, 8, hipMemcpyHostToDevice, ctx->stream));
+    return STAN_OK;
 }
 
-int stan_geometric_stiffness_device(stan_ctx *ctx, stan_matrix *K, const stan_mesh &d, stan_matrix **out) {
-    const char *who = "geometric_stiffness_hex8";
-    auto bad = [&](const char *why, int rc) { ctx->err = std::string(who) + ": " + why; return rc; };
-    STANCHK(stan_elem_limits_check(ctx, who, d));
-    if (K->nhalo != 0 || K->r0 != 0 || K->nloc != K->nb_glob) return bad("K is a shard of a larger matrix", STAN_E_UNSUPPORTED);
-    if (d.n_nodes != K->nb_glob || d.n_dof != K->n_dof) return bad("the mesh does not have K's block rows", STAN_E_ARG);
+int stan_elem_scalars_matrix(stan_ctx *ctx, dev_scope &tmp, const char *who, stan_matrix *K, const stan_mesh &d, const double *d_s36,
+                             stan_matrix **out, double ms[3]) {
     hipStream_t st = ctx->stream;
-    dev_scope tmp(ctx);
-    int64_t n_fixed;
-    STANCHK(stan_elem_args_check(ctx, tmp, who, d, 0, nullptr, nullptr, &n_fixed));
-    if (d.n_dof - n_fixed != K->n_red) return bad("the mesh does not have K's fixed DOFs", STAN_E_ARG);
-
-    // ---- the element scalars (the largest temporary: given back with `tmp`)
     const int64_t n_inc = d.n_elem * 8;
-    double *d_s36;
-    STANCHK(tmp.alloc(&d_s36, (size_t)(d.n_elem > 0 ? d.n_elem : 1) * KG_N));
-    for (double &ms : ctx->prof_kg_ms) ms = 0;
-    phase_timer pt(ctx, 2), pt2(ctx, 4);   // element pass | layout copy, lists and maps, gather
-    STANCHK(kg_elem_pass(ctx, tmp, d, d_s36, &pt));
-    STANCHK(pt.read(0, 1, &ctx->prof_kg_ms[0]));
-
+    phase_timer pt2(ctx, 4);   // layout copy, lists and maps, gather
     // ---- the new matrix: K's structure, its own values, nothing derived (stan_matrix_clone_layout)
     stan_matrix *G = nullptr;
     STANCHK(pt2.mark(0));
@@ -248,9 +219,53 @@ int stan_geometric_stiffness_device(stan_ctx *ctx, stan_matrix *K, const stan_me
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_status + SS_ERRBITS, ctx->d_status + SS_ERRBITS, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));   // the temporaries go back to the context behind the kernels
-    for (int k = 0; k < 3; k++) STANCHK(pt2.read(k, k + 1, &ctx->prof_kg_ms[k + 1]));
-    if (ctx->h_status[SS_ERRBITS]) return bad("an element couples two nodes that K's pattern does not (another mesh)", STAN_E_ARG);
+    for (int k = 0; k < 3; k++) STANCHK(pt2.read(k, k + 1, &ms[k]));
+    if (ctx->h_status[SS_ERRBITS]) {
+        ctx->err = std::string(who) + ": an element couples two nodes that K's pattern does not (another mesh)";
+        return STAN_E_ARG;
+    }
     g.ok = true;
     *out = G;
     return STAN_OK;
+}
+
+int stan_elem_scalars_matrix_args(stan_ctx *ctx, dev_scope &tmp, const char *who, stan_matrix *K, const stan_mesh &d) {
+    auto bad = [&](const char *why, int rc) { ctx->err = std::string(who) + ": " + why; return rc; };
+    STANCHK(stan_elem_limits_check(ctx, who, d));
+    if (K->nhalo != 0 || K->r0 != 0 || K->nloc != K->nb_glob) return bad("K is a shard of a larger matrix", STAN_E_UNSUPPORTED);
+    if (d.n_nodes != K->nb_glob || d.n_dof != K->n_dof) return bad("the mesh does not have K's block rows", STAN_E_ARG);
+    int64_t n_fixed;
+    STANCHK(stan_elem_args_check(ctx, tmp, who, d, 0, nullptr, nullptr, &n_fixed));
+    if (d.n_dof - n_fixed != K->n_red) return bad("the mesh does not have K's fixed DOFs", STAN_E_ARG);
+    return STAN_OK;
+}
+
+int stan_kg_batch_device(stan_ctx *ctx, int64_t n, const double *d_xyz8, const double *d_u8, double E, double nu,
+                         const uint8_t *d_type, double *d_s36) {
+    if (n <= 0) return STAN_OK;
+    if (n >= (int64_t)1 << 28) { ctx->err = "kg_hex8_batch: more than 2^28 elements"; return STAN_E_ARG; }
+    dev_scope tmp(ctx);
+    int32_t *d_conn, *d_mat;
+    STANCHK(tmp.alloc(&d_conn, (size_t)n * 8));
+    STANCHK(tmp.alloc(&d_mat, (size_t)n));
+    STANCHK(stan_elem_batch_iota(ctx, n, d_conn, d_mat));
+    const double E_nu[2] = {E, nu};
+    const stan_mesh d{.n_nodes = n * 8, .n_elem = n, .n_mat = 1, .xyz = d_xyz8, .disp = d_u8, .conn = d_conn, .elem_mat = d_mat,
+                      .elem_type = d_type, .mat_E_nu = E_nu};
+    return kg_elem_pass(ctx, tmp, d, d_s36);
+}
+
+int stan_geometric_stiffness_device(stan_ctx *ctx, stan_matrix *K, const stan_mesh &d, stan_matrix **out) {
+    const char *who = "geometric_stiffness_hex8";
+    dev_scope tmp(ctx);
+    STANCHK(stan_elem_scalars_matrix_args(ctx, tmp, who, K, d));
+
+    // ---- the element scalars (the largest temporary: given back with `tmp`)
+    double *d_s36;
+    STANCHK(tmp.alloc(&d_s36, (size_t)(d.n_elem > 0 ? d.n_elem : 1) * KG_N));
+    for (double &ms : ctx->prof_kg_ms) ms = 0;
+    phase_timer pt(ctx, 2);   // element pass | layout copy, lists and maps, gather: stan_elem_scalars_matrix
+    STANCHK(kg_elem_pass(ctx, tmp, d, d_s36, &pt));
+    STANCHK(pt.read(0, 1, &ctx->prof_kg_ms[0]));
+    return stan_elem_scalars_matrix(ctx, tmp, who, K, d, d_s36, out, ctx->prof_kg_ms + 1);
 }

@@ -272,6 +272,8 @@ struct stan_ctx {
     stan_profile prof{};
     double prof_loads_ms[3] = {0, 0, 0};   // last load-vector call: element pass | lists | gather (stan_hip_load_vector_times)
     double prof_thermal_ms[3] = {0, 0, 0}; // last thermal-load call, the same phases (stan_hip_thermal_load_times)
+    double prof_cm_ms[4] = {0, 0, 0, 0};   // last consistent-mass call, the same four phases (stan_hip_consistent_mass_times)
+    double prof_axpy_ms = 0;               // last stan_hip_matrix_axpy: the value pass
     double prof_kg_ms[4] = {0, 0, 0, 0};   // last geometric-stiffness call: element pass | layout copy | lists and maps | gather (stan_hip_geometric_stiffness_times)
     stan_pool pool;
     stan_cg_ws ws;
@@ -545,6 +547,9 @@ int stan_buckling_axpy_device(stan_ctx *ctx, int64_t N, int32_t q, const double 
 // d_phi [k][N] = the first k columns of X, each divided by its entry of largest magnitude (the lowest index on a tie): that
 // entry becomes exactly +1.  Synchronises.
 int stan_buckling_normalise_device(stan_ctx *ctx, int64_t N, int32_t k, const double *d_X, double *d_phi);
+// The pencil driver's (stan_hip_modes_pencil): d_phi [k][N] = the first k columns of X, each divided by sqrt(X_j . MX_j), d_MX
+// [k][N] = Mmat X by true products, with its entry of largest magnitude positive (the lowest index on a tie).  Synchronises.
+int stan_pencil_normalise_device(stan_ctx *ctx, int64_t N, int32_t k, const double *d_X, const double *d_MX, double *d_phi);
 
 // ---- matrix_shift.hip -----------------------------------------------------------------------
 // The value stan_hip_matrix_to_csr exports for an entry a of a matrix that carries S K S, s_row and s_col its two scaling
@@ -575,6 +580,32 @@ int stan_kg_batch_device(stan_ctx *ctx, int64_t n, const double *d_xyz8, const d
 // array, checked on the device before anything is indexed with it.  K is read only (its values are not read at all).
 // Synchronises.
 int stan_geometric_stiffness_device(stan_ctx *ctx, stan_matrix *K, const stan_mesh &d, stan_matrix **out);
+// What the matrices of element scalars s_e (x) I_3 on K's layout share (G above, the consistent mass of mass.hip).
+// The checks before anything is indexed: the limits, K whole on this device, the mesh's counts against K's, the integers on the
+// device (stan_elem_args_check with a claim array out of `tmp`), the fixed DOFs against K's; "<who>: <what>".
+int stan_elem_scalars_matrix_args(stan_ctx *ctx, dev_scope &tmp, const char *who, stan_matrix *K, const stan_mesh &d);
+// *out = a new matrix by stan_matrix_clone_layout whose values are the ordered row gather of d_s36 [n_elem][36] (the upper
+// triangles, kg_index's order): the node -> (element, corner) lists, the row maps, k_kg_gather, the status check (a mesh that
+// couples two nodes K's pattern does not: STAN_E_ARG, the matrix given back).  ms [3] (profiling on): layout copy | lists and
+// maps | gather.  The lists and maps are temporaries of `tmp`.  Synchronises.
+int stan_elem_scalars_matrix(stan_ctx *ctx, dev_scope &tmp, const char *who, stan_matrix *K, const stan_mesh &d, const double *d_s36,
+                             stan_matrix **out, double ms[3]);
+// the connectivity of a batch (element e's corner a is "node" 8 e + a, material 0; d_conn [8 n], d_mat [n]) and the reset of the
+// det J word.  Enqueues only.
+int stan_elem_batch_iota(stan_ctx *ctx, int64_t n, int32_t *d_conn, int32_t *d_mat);
+
+// ---- mass.hip -------------------------------------------------------------------------------
+// d_m36 [n][36] = the upper triangle of the element scalars m_e of the consistent mass (stan_hip_mass_hex8_batch), by the element
+// pass of stan_consistent_mass_device itself; d_xyz8 [n][24]; rho checked by the caller.  Synchronises.
+int stan_mass_batch_device(stan_ctx *ctx, int64_t n, const double *d_xyz8, double rho, double *d_m36);
+// *out = a new matrix of the context holding the consistent mass M_c in K's layout (stan_hip_consistent_mass_hex8_dev), built as
+// stan_geometric_stiffness_device builds G.  d: device view with every array but disp; mat_rho [n_mat] is host memory.  K is
+// read only (its values are not read at all).  Synchronises.
+int stan_consistent_mass_device(stan_ctx *ctx, stan_matrix *K, const stan_mesh &d, const double *mat_rho, stan_matrix **out);
+// *out = a new matrix of the context holding A + sigma B (stan_hip_matrix_axpy, matrix_shift.hip): A and B whole matrices of this
+// context on one layout, compared on the host (the scalars) and on the device (the structure arrays) before anything is
+// allocated; axpy_ms (may be null) gets the stream time of the value pass when profiling is on.  Synchronises.
+int stan_matrix_axpy_device(stan_ctx *ctx, stan_matrix *A, double sigma, stan_matrix *B, stan_matrix **out, double *axpy_ms = nullptr);
 
 // ---- transient.hip --------------------------------------------------------------------------
 // The Newmark step kernels of the transient driver (api_transient.hip).  Every vector is [N] in

@@ -240,6 +240,29 @@ k_md_colstats(int64_t N, const double *__restrict__ X, const double *__restrict_
         psum[o] = s[0]; pval[o] = bv; pidx[o] = bi;
     }
 }
+// the same for a matrix mass (stan_hip_modes_pencil): Y = Mmat X by true products, the sum is x . y, a term one fused multiply-add
+__global__ void __launch_bounds__(256)
+k_pc_colstats(int64_t N, const double *__restrict__ X, const double *__restrict__ Y, double *__restrict__ psum,
+              double *__restrict__ pval, long long *__restrict__ pidx) {
+    __shared__ double sh[4][1];
+    __shared__ double shv[4];
+    __shared__ long long shi[4];
+    const int j = blockIdx.y;
+    double s[1] = {0.0}, bv = 0.0;
+    long long bi = NO_INDEX;
+    for (int k = 0; k < RT_ROWS / 256; k++) {
+        const int64_t row = (int64_t)blockIdx.x * RT_ROWS + k * 256 + threadIdx.x;
+        if (row >= N) continue;
+        const double x = X[(int64_t)j * N + row];
+        s[0] = fma(Y[(int64_t)j * N + row], x, s[0]);
+        amax_merge(bv, bi, x, row);
+    }
+    block_amax(bv, bi, shv, shi, [&] { block_sums(s, sh); });   // (its barrier orders shv / shi too)
+    if (threadIdx.x == 0) {
+        const int64_t o = (int64_t)j * gridDim.x + blockIdx.x;
+        psum[o] = s[0]; pval[o] = bv; pidx[o] = bi;
+    }
+}
 // one workgroup per column: the partials in block order; scale[j] = +-sqrt(sum M x^2), negative where the largest entry is
 __global__ void __launch_bounds__(256)
 k_md_colfinish(int64_t n_blocks, const double *__restrict__ psum, const double *__restrict__ pval, const long long *__restrict__ pidx,
@@ -538,6 +561,13 @@ int stan_modal_normalise_device(stan_ctx *ctx, int64_t N, int32_t k, const doubl
 }
 
 // ---- the buckling driver's block kernels ----------------------------------------------------------------------------------
+int stan_pencil_normalise_device(stan_ctx *ctx, int64_t N, int32_t k, const double *d_X, const double *d_MX, double *d_phi) {
+    return block_normalise(ctx, "modes_pencil", N, k, d_X, d_phi, true, [&](hipStream_t st, dim3 rows, dim3 cols, int64_t nb, const normalise_tmp &t) {
+        hipLaunchKernelGGL(k_pc_colstats, rows, dim3(256), 0, st, N, d_X, d_MX, t.psum, t.pval, t.pidx);
+        hipLaunchKernelGGL(k_md_colfinish, cols, dim3(256), 0, st, nb, t.psum, t.pval, t.pidx, t.scale);
+    });
+}
+
 int stan_buckling_start_device(stan_ctx *ctx, int64_t N, int32_t q, double *d_X0) {
     STANCHK(block_args_check(ctx, "buckling", N, q));
     hipLaunchKernelGGL(k_bk_start, dim3(nblk(N, 256)), dim3(256), 0, ctx->stream, N, (int)q, d_X0);

@@ -65,6 +65,8 @@ EXPORTS = [
     "stan_hip_newmark_predict", "stan_hip_newmark_correct",
     "stan_hip_kg_hex8_batch", "stan_hip_geometric_stiffness_hex8", "stan_hip_geometric_stiffness_hex8_dev",
     "stan_hip_geometric_stiffness_times", "stan_hip_buckling", "stan_hip_buckling_dev", "stan_hip_buckling_rotate",
+    "stan_hip_mass_hex8_batch", "stan_hip_consistent_mass_hex8", "stan_hip_consistent_mass_hex8_dev",
+    "stan_hip_consistent_mass_times", "stan_hip_matrix_axpy", "stan_hip_modes_pencil", "stan_hip_modes_pencil_dev",
 ]
 # only in the lab build (stan_amd/csrc/lab/stan_hip_lab.h, selected with STAN_HIP_LIB)
 LAB_EXPORTS = ["stan_hip_csr_spmv_bench", "stan_hip_lab_placement_map", "stan_hip_lab_placement_variants", "stan_hip_lab_placement_alloc", "stan_hip_lab_placement_rounds", "stan_hip_lab_placement_cross", "stan_hip_lab_incg_penalty", "stan_hip_lab_placement_vecalloc", "stan_hip_lab_placement_vecshape", "stan_hip_lab_pairing_pmc"]
@@ -396,6 +398,40 @@ class Context:
         self._chk(self.lib.stan_hip_buckling_dev(
             self.h, K.k, G.k, C.c_int32(int(n_modes)), C.c_double(tol), C.c_int32(max_outer), C.c_double(solve_eps),
             C.c_int32(solve_max_its), _opt(d_factor), _opt(d_phi), _opt(d_rho), C.byref(rep)))
+        return rep.as_dict()
+
+    def mass_hex8_batch(self, xyz8, rho):
+        """stan_hip_mass_hex8_batch: m36 [n, 36], the upper triangle of the element scalars of the consistent mass."""
+        xyz8 = np.ascontiguousarray(xyz8, dtype=np.float64).reshape(-1, 24)
+        n = xyz8.shape[0]
+        out = np.zeros((n, 36))
+        self._chk(self.lib.stan_hip_mass_hex8_batch(self.h, C.c_int64(n), _ptr(xyz8, C.c_double), C.c_double(rho), _ptr(out, C.c_double)))
+        return out
+
+    def consistent_mass_times(self):
+        """dict(cm_elem_ms, cm_layout_ms, cm_list_ms, cm_gather_ms) of the last consistent-mass call and axpy_ms of the last
+        Matrix.axpy (profiling enabled)."""
+        ms = (C.c_double * 5)()
+        self._chk(self.lib.stan_hip_consistent_mass_times(self.h, ms))
+        return dict(cm_elem_ms=ms[0], cm_layout_ms=ms[1], cm_list_ms=ms[2], cm_gather_ms=ms[3], axpy_ms=ms[4])
+
+    def modes_pencil(self, K, Mmat, n_modes, tol=0.0, max_outer=0, solve_eps=0.0, solve_max_its=0):
+        """stan_hip_modes_pencil: the n_modes lowest eigenpairs of K phi = lambda Mmat phi, Mmat = K.consistent_mass(...).
+        Returns (lambda [n_modes], phi [n_modes, N], rho [n_modes], report dict of stan_buckling_report)."""
+        N = K.info()["n_reduced"]
+        k = max(int(n_modes), 1)
+        lam, phi, rho, rep = np.zeros(k), np.zeros((k, N)), np.zeros(k), BucklingReport()
+        self._chk(self.lib.stan_hip_modes_pencil(
+            self.h, K.k, Mmat.k, C.c_int32(int(n_modes)), C.c_double(tol), C.c_int32(max_outer), C.c_double(solve_eps),
+            C.c_int32(solve_max_its), _ptr(lam, C.c_double), _ptr(phi, C.c_double), _ptr(rho, C.c_double), C.byref(rep)))
+        return lam, phi, rho, rep.as_dict()
+
+    def modes_pencil_dev(self, K, Mmat, n_modes, d_lambda, d_phi, d_rho, tol=0.0, max_outer=0, solve_eps=0.0, solve_max_its=0):
+        """d_lambda / d_rho [n_modes], d_phi [n_modes, N]: device pointers (ints).  Returns the report dict."""
+        rep = BucklingReport()
+        self._chk(self.lib.stan_hip_modes_pencil_dev(
+            self.h, K.k, Mmat.k, C.c_int32(int(n_modes)), C.c_double(tol), C.c_int32(max_outer), C.c_double(solve_eps),
+            C.c_int32(solve_max_its), _opt(d_lambda), _opt(d_phi), _opt(d_rho), C.byref(rep)))
         return rep.as_dict()
 
     def buckling_rotate(self, Z, W, Y, D, Q, mu):
@@ -970,6 +1006,40 @@ class Matrix:
             self.ctx.h, self.k, C.c_int64(n_nodes), _dev(d_xyz, C.c_double), _dev(d_disp, C.c_double), _dev(d_node_dof, C.c_int32),
             C.c_int64(n_elem), _dev(d_conn, C.c_int32), _dev(d_elem_mat, C.c_int32), _dev(d_elem_type, C.c_uint8),
             C.c_int32(mat_E_nu.shape[0]), _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _dev(d_red, C.c_int32), C.byref(k)))
+        return Matrix(self.ctx, k)
+
+    def consistent_mass(self, xyz, node_dof, conn, elem_mat, elem_type, mat_E_nu, red, mat_rho):
+        """stan_hip_consistent_mass_hex8: a new Matrix holding the consistent mass M_c in this matrix' layout; mat_rho [n_mat],
+        the mesh arrays those this matrix was assembled from.  This matrix is left as it is."""
+        xyz, node_dof, conn, elem_mat, elem_type, mat_E_nu, red = _mesh(
+            xyz=xyz, node_dof=node_dof, conn=conn, elem_mat=elem_mat, elem_type=elem_type, mat_E_nu=mat_E_nu, red=red)
+        rho = None if mat_rho is None else np.ascontiguousarray(mat_rho, dtype=np.float64).reshape(-1)
+        if rho is not None and rho.shape[0] != mat_E_nu.shape[0]:
+            raise ValueError("consistent_mass: mat_rho must be [n_mat]")
+        k = C.c_void_p()
+        self.ctx._chk(self.ctx.lib.stan_hip_consistent_mass_hex8(
+            self.ctx.h, self.k, C.c_int64(xyz.shape[0]), _ptr(xyz, C.c_double), _ptr(rho, C.c_double), _ptr(node_dof, C.c_int32),
+            C.c_int64(conn.shape[0]), _ptr(conn, C.c_int32), _ptr(elem_mat, C.c_int32), _ptr(elem_type, C.c_uint8),
+            C.c_int32(mat_E_nu.shape[0]), _ptr(mat_E_nu, C.c_double), C.c_int64(red.shape[0]), _ptr(red, C.c_int32), C.byref(k)))
+        return Matrix(self.ctx, k)
+
+    def consistent_mass_dev(self, n_nodes, d_xyz, mat_rho, d_node_dof, n_elem, d_conn, d_elem_mat, d_elem_type, mat_E_nu, n_dof,
+                            d_red):
+        """All d_* are device pointers (ints), e.g. torch tensor.data_ptr(); mat_rho and mat_E_nu host arrays."""
+        mat_E_nu = np.ascontiguousarray(mat_E_nu, dtype=np.float64).reshape(-1, 2)
+        rho = np.ascontiguousarray(mat_rho, dtype=np.float64).reshape(-1)
+        k = C.c_void_p()
+        self.ctx._chk(self.ctx.lib.stan_hip_consistent_mass_hex8_dev(
+            self.ctx.h, self.k, C.c_int64(n_nodes), _dev(d_xyz, C.c_double), _ptr(rho, C.c_double), _dev(d_node_dof, C.c_int32),
+            C.c_int64(n_elem), _dev(d_conn, C.c_int32), _dev(d_elem_mat, C.c_int32), _dev(d_elem_type, C.c_uint8),
+            C.c_int32(mat_E_nu.shape[0]), _ptr(mat_E_nu, C.c_double), C.c_int64(n_dof), _dev(d_red, C.c_int32), C.byref(k)))
+        return Matrix(self.ctx, k)
+
+    def axpy(self, sigma, B):
+        """stan_hip_matrix_axpy: a new Matrix holding this matrix + sigma B, B a Matrix on this matrix' layout; both are left
+        as they are."""
+        k = C.c_void_p()
+        self.ctx._chk(self.ctx.lib.stan_hip_matrix_axpy(self.ctx.h, self.k, C.c_double(sigma), None if B is None else B.k, C.byref(k)))
         return Matrix(self.ctx, k)
 
     def modes_shifted(self, M, n_modes, sigma, **kw):

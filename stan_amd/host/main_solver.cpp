@@ -35,6 +35,9 @@
 // never written.  Refused before anything is computed: several devices, a "Temperature" boundary condition, no supports.
 // --modes-shift SIGMA (a model without supports): the modes of K + SIGMA M (stan_hip_matrix_shifted), printed as lambda = mu - SIGMA;
 // rho is then the convergence measure of the shifted problem, "shift" in the JSON object.
+// --mass consistent (with --modes; default lumped, the path above) runs on the consistent mass M_c:
+// stan_hip_consistent_mass_hex8 on K's layout and stan_hip_modes_pencil, under --modes-shift on stan_hip_matrix_axpy(K, SIGMA, M_c); the
+// block "Natural frequencies:" names the mass and the "modes" object carries "mass": "consistent".
 // --transient --dt DT --steps N [--newmark B,G] [--rayleigh A,B] [--load-curve t0,g0,t1,g1,...] [--probe-node ID] [--solve-eps E]
 //  integrates M a + C v + K u = g(t) F from rest by stan_hip_transient INSTEAD of the static solve and never
 // writes the STdb: F is the model's own load (PointLoad, distributed and thermal loads), g = 1 without a curve (a step load), the
@@ -83,6 +86,7 @@ int main(int argc, char **argv) {
     bool vtu = false, vtu_cells = false, reactions = false;
     int modes = 0;
     double modes_tol = 0.0, modes_shift = 0.0;
+    std::string mass_kind = "lumped";
     int buckling = 0;
     double buckling_tol = 0.0, solve_eps = 0.0;
     bool buckling_arg = false, have_solve_eps = false;
@@ -133,6 +137,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--modes") && i + 1 < argc) modes = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--modes-tol") && i + 1 < argc) modes_tol = atof(argv[++i]);
         else if (!strcmp(argv[i], "--modes-shift") && i + 1 < argc) modes_shift = atof(argv[++i]);
+        else if (!strcmp(argv[i], "--mass") && i + 1 < argc) mass_kind = argv[++i];
         else if (!strcmp(argv[i], "--transient")) transient = true;
         else if (!strcmp(argv[i], "--dt") && i + 1 < argc) { transient_arg = true; run.dt = atof(argv[++i]); }
         else if (!strcmp(argv[i], "--steps") && i + 1 < argc) { transient_arg = true; run.n_steps = atoi(argv[++i]); }
@@ -159,7 +164,7 @@ int main(int argc, char **argv) {
     }
     if (path.empty()) {  // Path = path[0] -> IndexOutOfRangeException in the reference
         fprintf(stderr, "usage: stan_solver [--device N | --gpus N | --devices a,b,..] [--p2p] [--mixed|--fixed48] "
-                        "[--no-merit-stop] [--packed] [--object-results] [--json] [--vtu PREFIX [--vtu-results \"name,..\"] [--vtu-cells]] [--reactions] [--modes K [--modes-tol T] [--modes-shift SIGMA]] "
+                        "[--no-merit-stop] [--packed] [--object-results] [--json] [--vtu PREFIX [--vtu-results \"name,..\"] [--vtu-cells]] [--reactions] [--modes K [--modes-tol T] [--modes-shift SIGMA] [--mass lumped|consistent]] "
                         "[--buckling K [--buckling-tol T] [--solve-eps E] [--vtu PREFIX]] "
                         "[--transient --dt DT --steps N [--newmark B,G] [--rayleigh A,B] [--load-curve t0,g0,t1,g1,...] [--probe-node ID] "
                         "[--solve-eps E] [--vtu PREFIX [--vtu-every K]]] <model.STdb>\n");
@@ -195,6 +200,14 @@ int main(int argc, char **argv) {
     }
     if (modes_shift != 0 && (!modes || !(modes_shift > 0) || !std::isfinite(modes_shift))) {
         fprintf(stderr, "stan_solver: --modes-shift SIGMA needs SIGMA > 0 and --modes\n");
+        return 2;
+    }
+    if (mass_kind != "lumped" && mass_kind != "consistent") {
+        fprintf(stderr, "stan_solver: --mass takes lumped or consistent, not \"%s\"\n", mass_kind.c_str());
+        return 2;
+    }
+    if (mass_kind == "consistent" && !modes) {
+        fprintf(stderr, "stan_solver: --mass consistent needs --modes\n");
         return 2;
     }
     // --buckling, checked before anything is read as well
@@ -337,13 +350,15 @@ int main(int argc, char **argv) {
             std::vector<double> lambda, phi, rho;
             stan_mass_sums msum{};
             stan_modes_report rep{};
-            Functions.Modes(K, nDOF_reduction, md, modes, modes_tol, &lambda, &phi, &rho, &msum, &rep, modes_shift);
+            const bool consistent = mass_kind == "consistent";
+            if (consistent) Functions.ModesConsistent(K, nDOF_reduction, md, modes, modes_tol, &lambda, &phi, &rho, &msum, &rep, modes_shift);
+            else Functions.Modes(K, nDOF_reduction, md, modes, modes_tol, &lambda, &phi, &rho, &msum, &rep, modes_shift);
             const double two_pi = 6.283185307179586476925;
             // (a rigid-body mode of a shifted run has lambda = 0 up to the tolerance, on either side: its frequency is 0)
             auto hz = [&](double l) { return l > 0 ? std::sqrt(l) / two_pi : 0.0; };
             printf("   Total mass: %.6e   volume: %.6e\n", msum.total_mass, msum.volume);
-            printf("   Natural frequencies: (block %d, %d outer steps, %lld CG iterations, %s)\n", rep.block, rep.outer,
-                   (long long)rep.cg_iterations, rep.converged ? "converged" : "NOT converged");
+            printf("   Natural frequencies: (%sblock %d, %d outer steps, %lld CG iterations, %s)\n", consistent ? "consistent mass, " : "",
+                   rep.block, rep.outer, (long long)rep.cg_iterations, rep.converged ? "converged" : "NOT converged");
             if (modes_shift > 0)
                 printf("     shift %.8e: the modes of K + shift M, lambda = mu - shift; rho is the convergence measure of the shifted\n"
                        "     problem, relative to mu\n", modes_shift);
@@ -367,6 +382,7 @@ int main(int argc, char **argv) {
                        "\"outer\": %d, \"converged\": %d, \"cg_iterations\": %lld, \"total_mass\": %.17g",
                        DB.nDOF, (long long)minfo.n_reduced, secs(t_wall), modes, rep.block, rep.outer, rep.converged,
                        (long long)rep.cg_iterations, msum.total_mass);
+                if (consistent) printf(", \"mass\": \"consistent\"");
                 if (modes_shift > 0) printf(", \"shift\": %.17g", modes_shift);   // rho: of the shifted problem
                 for (int pass = 0; pass < 3; pass++) {
                     printf(", \"%s\": [", pass == 0 ? "lambda" : pass == 1 ? "frequency_hz" : "rho");

@@ -251,6 +251,41 @@ void SolverFunctions::Modes(SparseMatrixHandle &K, const std::vector<int32_t> &r
         for (double &l : *lambda) l -= shift;
 }
 
+void SolverFunctions::ModesConsistent(SparseMatrixHandle &K, const std::vector<int32_t> &red, const MassDensity &md, int n_modes, double tol,
+                                      std::vector<double> *lambda, std::vector<double> *phi, std::vector<double> *rho,
+                                      stan_mass_sums *sums, stan_modes_report *rep, double shift) const {
+    std::vector<double> M;
+    LumpedMass(K, red, md, &M, sums);   // the sums (total mass, volume) and the refusal of a free DOF without mass, as for --modes
+    const FlatModel &f = K.flat;
+    const size_t N = M.size();
+    const size_t k = n_modes > 0 ? (size_t)n_modes : 1;
+    lambda->assign(k, 0.0); rho->assign(k, 0.0); phi->assign(k * N, 0.0);
+    stan_matrix *Mc = nullptr, *shifted = nullptr;
+    if (stan_hip_consistent_mass_hex8(K.ctx, K.K, (int64_t)(f.xyz.size() / 3), f.xyz.data(), md.mat_rho.data(), f.node_dof.data(),
+                                      (int64_t)f.elem_mat.size(), f.conn.data(), f.elem_mat.data(), f.elem_type.data(),
+                                      (int32_t)(f.mat_E_nu.size() / 2), f.mat_E_nu.data(), (int64_t)red.size(), red.data(), &Mc))
+        throw std::runtime_error(stan_hip_last_error(K.ctx));
+    stan_matrix *A = K.K;
+    if (shift > 0) {
+        if (stan_hip_matrix_axpy(K.ctx, K.K, shift, Mc, &shifted)) {
+            stan_hip_matrix_free(Mc);
+            throw std::runtime_error(stan_hip_last_error(K.ctx));
+        }
+        A = shifted;
+    }
+    stan_buckling_report br{};
+    const int rc = stan_hip_modes_pencil(K.ctx, A, Mc, n_modes, tol, 0, 0.0, 0, lambda->data(), phi->data(), rho->data(), &br);
+    if (shifted) stan_hip_matrix_free(shifted);
+    stan_hip_matrix_free(Mc);
+    if (rc) throw std::runtime_error(stan_hip_last_error(K.ctx));
+    *rep = stan_modes_report{};
+    rep->block = br.block; rep->outer = br.outer; rep->converged = br.converged; rep->cg_worst_type = br.cg_worst_type;
+    rep->cg_iterations = br.cg_iterations; rep->max_rho = br.max_rho; rep->solve_ms = br.solve_ms; rep->product_ms = br.product_ms;
+    rep->block_ms = br.block_ms; rep->gram_ms = br.gram_ms; rep->rotate_ms = br.rotate_ms;
+    if (shift > 0)
+        for (double &l : *lambda) l -= shift;
+}
+
 void SolverFunctions::LumpedMass(SparseMatrixHandle &K, const std::vector<int32_t> &red, const MassDensity &md, std::vector<double> *M,
                                  stan_mass_sums *sums) const {
     const FlatModel &f = K.flat;

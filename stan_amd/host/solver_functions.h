@@ -115,6 +115,12 @@ class SolverFunctions {
     void Modes(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const MassDensity &md, int n_modes, double tol,
                std::vector<double> *lambda, std::vector<double> *phi, std::vector<double> *rho, stan_mass_sums *sums,
                stan_modes_report *rep, double shift = 0.0) const;
+    // The same on the consistent mass: M_c on K's layout (stan_hip_consistent_mass_hex8) and
+    // stan_hip_modes_pencil; shift > 0: on stan_hip_matrix_axpy(K, shift, M_c).  phi is scaled to phi^T M_c phi = 1; *rep holds the
+    // fields the two reports share.
+    void ModesConsistent(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const MassDensity &md, int n_modes, double tol,
+                         std::vector<double> *lambda, std::vector<double> *phi, std::vector<double> *rho, stan_mass_sums *sums,
+                         stan_modes_report *rep, double shift = 0.0) const;
     // Transient dynamics (stan_hip_lumped_mass_hex8 + stan_hip_transient; no step of the reference):
     // implicit Newmark steps of M a + C v + K u = g(t) F from rest, F the reduced external load.  probe_dof: reduced DOFs;
     // probe_u [(n_steps + 1)][n_probe]; snaps [n_snap][3][N] when snap_every > 0; energy [(n_steps + 1)][3]; *sums and *rep
