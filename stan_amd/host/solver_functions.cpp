@@ -13,6 +13,36 @@ namespace stan {
 using clk = std::chrono::steady_clock;
 static double secs(clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); }
 
+namespace {
+
+// the mesh arguments of a stan_hip_*_hex8 call: sizes and pointers of the flat model
+struct MeshView {
+    explicit MeshView(const FlatModel &f)
+        : n_nodes((int64_t)(f.xyz.size() / 3)), n_elem((int64_t)f.elem_mat.size()), n_mat((int32_t)(f.mat_E_nu.size() / 2)),
+          xyz(f.xyz.data()), mat_E_nu(f.mat_E_nu.data()), node_dof(f.node_dof.data()), conn(f.conn.data()),
+          elem_mat(f.elem_mat.data()), elem_type(f.elem_type.data()) {}
+    int64_t n_nodes, n_elem;
+    int32_t n_mat;
+    const double *xyz, *mat_E_nu;
+    const int32_t *node_dof, *conn, *elem_mat;
+    const uint8_t *elem_type;
+};
+
+// the free DOFs of a reduction map (-1 marks a fixed one)
+size_t n_reduced(const std::vector<int32_t> &red) {
+    size_t n_fixed = 0;
+    for (int32_t r : red) n_fixed += r == -1;
+    return red.size() - n_fixed;
+}
+
+// the fields that the reports of stan_hip_modes and stan_hip_modes_pencil share
+stan_modes_report shared_fields(const stan_buckling_report &b) {
+    return {b.block, b.outer, b.converged, b.cg_worst_type, b.cg_iterations, b.max_rho, b.solve_ms, b.product_ms, b.block_ms, b.gram_ms,
+            b.rotate_ms};
+}
+
+}  // namespace
+
 struct SolverFunctions::Warm {
     std::thread th;
     stan_ctx *ctx = nullptr;
@@ -80,11 +110,9 @@ void SolverFunctions::ParallelAssembly_K(const Database &DB, const std::vector<i
     stan_hip_set_option(K->ctx, STAN_OPT_PLACEMENT_TRIES, opt_.placement_tries < 1 ? 1 : opt_.placement_tries);
     if (opt_.p2p && stan_hip_set_option(K->ctx, STAN_OPT_COMM_P2P, 1)) throw std::runtime_error(stan_hip_last_error(K->ctx));
     if (opt_.profile) stan_hip_set_profiling(K->ctx, 1);
-    const FlatModel &f = K->flat;
-    const int rc = stan_hip_assemble_hex8(K->ctx, (int64_t)DB.NodeLib.Count(), f.xyz.data(), f.node_dof.data(),
-                                          (int64_t)DB.ElemLib.Count(), f.conn.data(), f.elem_mat.data(),
-                                          f.elem_type.data(), (int32_t)(f.mat_E_nu.size() / 2),
-                                          f.mat_E_nu.data(), DB.nDOF, red.data(), &K->K);
+    const MeshView v(K->flat);
+    const int rc = stan_hip_assemble_hex8(K->ctx, v.n_nodes, v.xyz, v.node_dof, v.n_elem, v.conn, v.elem_mat, v.elem_type, v.n_mat,
+                                          v.mat_E_nu, DB.nDOF, red.data(), &K->K);
     if (rc) throw std::runtime_error(stan_hip_last_error(K->ctx));  // det J == 0: MatrixST.cs:315-318 throws
     const_cast<SolverFunctions *>(this)->last_assembly_s = secs(t0);
     printf("          Done in %.2fs\n", last_assembly_s);  // SolverFunctions.cs:177
@@ -171,12 +199,10 @@ std::vector<double> SolverFunctions::LinearSolver_LU(SparseMatrixHandle &K, cons
 
 void SolverFunctions::Recovery_Stress(SparseMatrixHandle &K, const std::vector<double> &dU,
                                       std::vector<double> *strain, std::vector<double> *stress) const {
-    const FlatModel &f = K.flat;
-    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
-    strain->assign((size_t)n_elem * 48, 0.0);
-    stress->assign((size_t)n_elem * 48, 0.0);
-    if (stan_hip_recover_hex8(K.ctx, n_nodes, f.xyz.data(), dU.data(), n_elem, f.conn.data(), f.elem_mat.data(),
-                              f.elem_type.data(), (int32_t)(f.mat_E_nu.size() / 2), f.mat_E_nu.data(),
+    const MeshView v(K.flat);
+    strain->assign((size_t)v.n_elem * 48, 0.0);
+    stress->assign((size_t)v.n_elem * 48, 0.0);
+    if (stan_hip_recover_hex8(K.ctx, v.n_nodes, v.xyz, dU.data(), v.n_elem, v.conn, v.elem_mat, v.elem_type, v.n_mat, v.mat_E_nu,
                               strain->data(), stress->data()))
         throw std::runtime_error(stan_hip_last_error(K.ctx));  // HEX8_G1: the reference throws too (Element.cs:242)
 }
@@ -184,25 +210,21 @@ void SolverFunctions::Recovery_Stress(SparseMatrixHandle &K, const std::vector<d
 void SolverFunctions::Equilibrium(SparseMatrixHandle &K, const std::vector<double> &dU, const std::vector<double> &F,
                                   const std::vector<int32_t> &red, std::vector<double> *f_int, std::vector<double> *reaction,
                                   stan_equilibrium *eq) const {
-    const FlatModel &f = K.flat;
-    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
+    const MeshView v(K.flat);
     if (f_int) f_int->assign(red.size(), 0.0);
     if (reaction) reaction->assign(red.size(), 0.0);
-    if (stan_hip_internal_forces_hex8(K.ctx, n_nodes, f.xyz.data(), dU.data(), f.node_dof.data(), n_elem, f.conn.data(),
-                                      f.elem_mat.data(), f.elem_type.data(), (int32_t)(f.mat_E_nu.size() / 2), f.mat_E_nu.data(),
-                                      (int64_t)red.size(), red.data(), F.empty() ? nullptr : F.data(),
+    if (stan_hip_internal_forces_hex8(K.ctx, v.n_nodes, v.xyz, dU.data(), v.node_dof, v.n_elem, v.conn, v.elem_mat, v.elem_type, v.n_mat,
+                                      v.mat_E_nu, (int64_t)red.size(), red.data(), F.empty() ? nullptr : F.data(),
                                       f_int ? f_int->data() : nullptr, reaction ? reaction->data() : nullptr, eq))
         throw std::runtime_error(stan_hip_last_error(K.ctx));
 }
 
 void SolverFunctions::Load_Vector(SparseMatrixHandle &K, const std::vector<int32_t> &red, const DistributedLoads &dl,
                                   std::vector<double> *F, std::vector<double> *F_solve, stan_load_sums *sums) const {
-    const FlatModel &f = K.flat;
-    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
+    const MeshView v(K.flat);
     F_solve->assign(F->size(), 0.0);
-    if (stan_hip_load_vector_hex8(K.ctx, n_nodes, f.xyz.data(), f.node_dof.data(), n_elem, f.conn.data(), f.elem_mat.data(),
-                                  f.elem_type.data(), (int32_t)(f.mat_E_nu.size() / 2), f.mat_E_nu.data(), (int64_t)red.size(),
-                                  red.data(), dl.mat_body.empty() ? nullptr : dl.mat_body.data(), (int64_t)dl.face_elem.size(),
+    if (stan_hip_load_vector_hex8(K.ctx, v.n_nodes, v.xyz, v.node_dof, v.n_elem, v.conn, v.elem_mat, v.elem_type, v.n_mat, v.mat_E_nu,
+                                  (int64_t)red.size(), red.data(), dl.mat_body.empty() ? nullptr : dl.mat_body.data(), (int64_t)dl.face_elem.size(),
                                   dl.face_elem.data(), dl.face_id.data(), dl.face_p.data(),
                                   dl.disp0.empty() ? nullptr : dl.disp0.data(), F->data(), F_solve->data(), nullptr, sums))
         throw std::runtime_error(stan_hip_last_error(K.ctx));
@@ -210,93 +232,61 @@ void SolverFunctions::Load_Vector(SparseMatrixHandle &K, const std::vector<int32
 
 void SolverFunctions::Thermal_Load(SparseMatrixHandle &K, const std::vector<int32_t> &red, const ThermalLoads &tl,
                                    std::vector<double> *F, std::vector<double> *load_full, stan_thermal_sums *sums) const {
-    const FlatModel &f = K.flat;
-    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
+    const MeshView v(K.flat);
     load_full->assign(red.size(), 0.0);
-    if (stan_hip_thermal_load_hex8(K.ctx, n_nodes, f.xyz.data(), f.node_dof.data(), n_elem, f.conn.data(), f.elem_mat.data(),
-                                   f.elem_type.data(), (int32_t)(f.mat_E_nu.size() / 2), f.mat_E_nu.data(), (int64_t)red.size(),
-                                   red.data(), tl.mat_alpha.data(), tl.dT.data(), F->data(), load_full->data(), sums))
+    if (stan_hip_thermal_load_hex8(K.ctx, v.n_nodes, v.xyz, v.node_dof, v.n_elem, v.conn, v.elem_mat, v.elem_type, v.n_mat, v.mat_E_nu,
+                                   (int64_t)red.size(), red.data(), tl.mat_alpha.data(), tl.dT.data(), F->data(), load_full->data(), sums))
         throw std::runtime_error(stan_hip_last_error(K.ctx));
 }
 
 void SolverFunctions::Thermal_Stress(SparseMatrixHandle &K, const ThermalLoads &tl, std::vector<double> *stress) const {
-    const FlatModel &f = K.flat;
-    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
-    const int32_t n_mat = (int32_t)(f.mat_E_nu.size() / 2);
-    const int rc = stress ? stan_hip_thermal_stress_hex8(K.ctx, n_nodes, tl.dT.data(), n_elem, f.conn.data(), f.elem_mat.data(),
-                                                         f.elem_type.data(), n_mat, f.mat_E_nu.data(), tl.mat_alpha.data(),
-                                                         stress->data())
-                          : stan_hip_results_thermal_stress(K.ctx, K.results, n_nodes, tl.dT.data(), f.conn.data(), f.elem_mat.data(),
-                                                            f.elem_type.data(), n_mat, f.mat_E_nu.data(), tl.mat_alpha.data());
+    const MeshView v(K.flat);
+    const int rc = stress ? stan_hip_thermal_stress_hex8(K.ctx, v.n_nodes, tl.dT.data(), v.n_elem, v.conn, v.elem_mat, v.elem_type, v.n_mat,
+                                                         v.mat_E_nu, tl.mat_alpha.data(), stress->data())
+                          : stan_hip_results_thermal_stress(K.ctx, K.results, v.n_nodes, tl.dT.data(), v.conn, v.elem_mat, v.elem_type,
+                                                            v.n_mat, v.mat_E_nu, tl.mat_alpha.data());
     if (rc) throw std::runtime_error(stan_hip_last_error(K.ctx));
 }
 
-void SolverFunctions::Modes(SparseMatrixHandle &K, const std::vector<int32_t> &red, const MassDensity &md, int n_modes, double tol,
-                            std::vector<double> *lambda, std::vector<double> *phi, std::vector<double> *rho, stan_mass_sums *sums,
-                            stan_modes_report *rep, double shift) const {
+void SolverFunctions::Modes(SparseMatrixHandle &K, const std::vector<int32_t> &red, const MassDensity &md, MassKind mass, int n_modes,
+                            double tol, std::vector<double> *lambda, std::vector<double> *phi, std::vector<double> *rho,
+                            stan_mass_sums *sums, stan_modes_report *rep, double shift) const {
     std::vector<double> M;
-    LumpedMass(K, red, md, &M, sums);
+    LumpedMass(K, red, md, &M, sums);   // under the consistent mass too: the sums (total mass, volume) and the refusal of a free DOF without mass
     const size_t N = M.size();
     const size_t k = n_modes > 0 ? (size_t)n_modes : 1;
     lambda->assign(k, 0.0); rho->assign(k, 0.0); phi->assign(k * N, 0.0);
-    stan_matrix *A = K.K, *shifted = nullptr;
-    if (shift > 0) {
-        if (stan_hip_matrix_shifted(K.ctx, K.K, shift, M.data(), &shifted)) throw std::runtime_error(stan_hip_last_error(K.ctx));
-        A = shifted;
-    }
-    const int rc = stan_hip_modes(K.ctx, A, M.data(), n_modes, tol, 0, 0.0, 0, lambda->data(), phi->data(), rho->data(), rep);
-    if (shifted) stan_hip_matrix_free(shifted);
-    if (rc) throw std::runtime_error(stan_hip_last_error(K.ctx));
-    if (shift > 0)
-        for (double &l : *lambda) l -= shift;
-}
-
-void SolverFunctions::ModesConsistent(SparseMatrixHandle &K, const std::vector<int32_t> &red, const MassDensity &md, int n_modes, double tol,
-                                      std::vector<double> *lambda, std::vector<double> *phi, std::vector<double> *rho,
-                                      stan_mass_sums *sums, stan_modes_report *rep, double shift) const {
-    std::vector<double> M;
-    LumpedMass(K, red, md, &M, sums);   // the sums (total mass, volume) and the refusal of a free DOF without mass, as for --modes
-    const FlatModel &f = K.flat;
-    const size_t N = M.size();
-    const size_t k = n_modes > 0 ? (size_t)n_modes : 1;
-    lambda->assign(k, 0.0); rho->assign(k, 0.0); phi->assign(k * N, 0.0);
-    stan_matrix *Mc = nullptr, *shifted = nullptr;
-    if (stan_hip_consistent_mass_hex8(K.ctx, K.K, (int64_t)(f.xyz.size() / 3), f.xyz.data(), md.mat_rho.data(), f.node_dof.data(),
-                                      (int64_t)f.elem_mat.size(), f.conn.data(), f.elem_mat.data(), f.elem_type.data(),
-                                      (int32_t)(f.mat_E_nu.size() / 2), f.mat_E_nu.data(), (int64_t)red.size(), red.data(), &Mc))
-        throw std::runtime_error(stan_hip_last_error(K.ctx));
-    stan_matrix *A = K.K;
-    if (shift > 0) {
-        if (stan_hip_matrix_axpy(K.ctx, K.K, shift, Mc, &shifted)) {
-            stan_hip_matrix_free(Mc);
+    OwnedMatrix Mc, shifted;   // the mass and the operator, by kind
+    stan_matrix *made = nullptr;
+    if (mass == MASS_CONSISTENT) {
+        const MeshView v(K.flat);
+        if (stan_hip_consistent_mass_hex8(K.ctx, K.K, v.n_nodes, v.xyz, md.mat_rho.data(), v.node_dof, v.n_elem, v.conn, v.elem_mat,
+                                          v.elem_type, v.n_mat, v.mat_E_nu, (int64_t)red.size(), red.data(), &made))
             throw std::runtime_error(stan_hip_last_error(K.ctx));
-        }
-        A = shifted;
+        Mc.reset(made);
     }
-    stan_buckling_report br{};
-    const int rc = stan_hip_modes_pencil(K.ctx, A, Mc, n_modes, tol, 0, 0.0, 0, lambda->data(), phi->data(), rho->data(), &br);
-    if (shifted) stan_hip_matrix_free(shifted);
-    stan_hip_matrix_free(Mc);
-    if (rc) throw std::runtime_error(stan_hip_last_error(K.ctx));
-    *rep = stan_modes_report{};
-    rep->block = br.block; rep->outer = br.outer; rep->converged = br.converged; rep->cg_worst_type = br.cg_worst_type;
-    rep->cg_iterations = br.cg_iterations; rep->max_rho = br.max_rho; rep->solve_ms = br.solve_ms; rep->product_ms = br.product_ms;
-    rep->block_ms = br.block_ms; rep->gram_ms = br.gram_ms; rep->rotate_ms = br.rotate_ms;
+    if (shift > 0) {
+        if (Mc ? stan_hip_matrix_axpy(K.ctx, K.K, shift, Mc.get(), &made) : stan_hip_matrix_shifted(K.ctx, K.K, shift, M.data(), &made))
+            throw std::runtime_error(stan_hip_last_error(K.ctx));
+        shifted.reset(made);
+    }
+    stan_matrix *A = shifted ? shifted.get() : K.K;
+    stan_buckling_report pencil{};
+    if (Mc ? stan_hip_modes_pencil(K.ctx, A, Mc.get(), n_modes, tol, 0, 0.0, 0, lambda->data(), phi->data(), rho->data(), &pencil)
+           : stan_hip_modes(K.ctx, A, M.data(), n_modes, tol, 0, 0.0, 0, lambda->data(), phi->data(), rho->data(), rep))
+        throw std::runtime_error(stan_hip_last_error(K.ctx));
+    if (Mc) *rep = shared_fields(pencil);
     if (shift > 0)
         for (double &l : *lambda) l -= shift;
 }
 
 void SolverFunctions::LumpedMass(SparseMatrixHandle &K, const std::vector<int32_t> &red, const MassDensity &md, std::vector<double> *M,
                                  stan_mass_sums *sums) const {
-    const FlatModel &f = K.flat;
-    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
-    size_t n_fixed = 0;
-    for (int32_t r : red) n_fixed += r == -1;
-    const size_t N = red.size() - n_fixed;
+    const MeshView v(K.flat);
+    const size_t N = n_reduced(red);
     M->assign(N > 0 ? N : 1, 0.0);
-    if (stan_hip_lumped_mass_hex8(K.ctx, n_nodes, f.xyz.data(), f.node_dof.data(), n_elem, f.conn.data(), f.elem_mat.data(),
-                                  f.elem_type.data(), (int32_t)(f.mat_E_nu.size() / 2), f.mat_E_nu.data(), (int64_t)red.size(),
-                                  red.data(), md.mat_rho.data(), M->data(), nullptr, sums))
+    if (stan_hip_lumped_mass_hex8(K.ctx, v.n_nodes, v.xyz, v.node_dof, v.n_elem, v.conn, v.elem_mat, v.elem_type, v.n_mat, v.mat_E_nu,
+                                  (int64_t)red.size(), red.data(), md.mat_rho.data(), M->data(), nullptr, sums))
         throw std::runtime_error(stan_hip_last_error(K.ctx));
 }
 
@@ -320,85 +310,67 @@ void SolverFunctions::Transient(SparseMatrixHandle &K, const std::vector<int32_t
 
 void SolverFunctions::Export_Step_Vtu(SparseMatrixHandle &K, const std::vector<int32_t> &red, const double *uva, size_t N,
                                       const std::string &prefix, int step) const {
-    const FlatModel &f = K.flat;
-    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
+    const MeshView v(K.flat);
     static const char *const names[9] = {"Displacement X", "Displacement Y", "Displacement Z", "Velocity X", "Velocity Y", "Velocity Z",
                                          "Acceleration X", "Acceleration Y", "Acceleration Z"};
-    std::vector<double> point(9 * (size_t)n_nodes), disp(3 * (size_t)n_nodes);
+    std::vector<double> point(9 * (size_t)v.n_nodes), disp;
     for (int q = 0; q < 3; q++) {
-        const std::vector<double> full = Include_BC_DOF(std::vector<double>(uva + (size_t)q * N, uva + (size_t)(q + 1) * N), red);
-        for (int64_t n = 0; n < n_nodes; n++)
-            for (int c = 0; c < 3; c++) {
-                const double x = full[(size_t)f.node_dof[(size_t)(3 * n + c)]];
-                point[(size_t)(3 * q + c) * (size_t)n_nodes + (size_t)n] = x;
-                if (q == 0) disp[(size_t)(3 * n + c)] = x;
-            }
+        std::vector<double> nodal = Nodal_Vector(K, uva + (size_t)q * N, red);
+        for (int64_t n = 0; n < v.n_nodes; n++)
+            for (int c = 0; c < 3; c++) point[(size_t)(3 * q + c) * (size_t)v.n_nodes + (size_t)n] = nodal[(size_t)(3 * n + c)];
+        if (q == 0) disp.swap(nodal);
     }
     char num[16];
     snprintf(num, sizeof num, "%04d", step);
     const std::string path = prefix + "_step_" + num + ".vtu";
-    if (stan_host_write_vtu(path.c_str(), n_nodes, f.xyz.data(), disp.data(), n_elem, f.conn.data(), 9, names, point.data(), 0, nullptr,
-                            nullptr))
+    if (stan_host_write_vtu(path.c_str(), v.n_nodes, v.xyz, disp.data(), v.n_elem, v.conn, 9, names, point.data(), 0, nullptr, nullptr))
         throw std::runtime_error("cannot write " + path);
 }
 
 void SolverFunctions::Buckling(SparseMatrixHandle &K, const std::vector<int32_t> &red, const std::vector<double> &dU, int n_modes, double tol,
                                double solve_eps, std::vector<double> *factor, std::vector<double> *phi, std::vector<double> *rho,
                                stan_buckling_report *rep) const {
-    const FlatModel &f = K.flat;
-    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
-    size_t n_fixed = 0;
-    for (int32_t r : red) n_fixed += r == -1;
-    const size_t N = red.size() - n_fixed, k = n_modes > 0 ? (size_t)n_modes : 1;
+    const MeshView v(K.flat);
+    const size_t N = n_reduced(red), k = n_modes > 0 ? (size_t)n_modes : 1;
     factor->assign(k, 0.0); rho->assign(k, 0.0); phi->assign(k * N, 0.0);
-    stan_matrix *G = nullptr;
-    if (stan_hip_geometric_stiffness_hex8(K.ctx, K.K, n_nodes, f.xyz.data(), dU.data(), f.node_dof.data(), n_elem, f.conn.data(),
-                                          f.elem_mat.data(), f.elem_type.data(), (int32_t)(f.mat_E_nu.size() / 2), f.mat_E_nu.data(),
-                                          (int64_t)red.size(), red.data(), &G))
+    stan_matrix *made = nullptr;
+    if (stan_hip_geometric_stiffness_hex8(K.ctx, K.K, v.n_nodes, v.xyz, dU.data(), v.node_dof, v.n_elem, v.conn, v.elem_mat, v.elem_type,
+                                          v.n_mat, v.mat_E_nu, (int64_t)red.size(), red.data(), &made))
         throw std::runtime_error(stan_hip_last_error(K.ctx));
-    const int rc = stan_hip_buckling(K.ctx, K.K, G, n_modes, tol, 0, solve_eps, 0, factor->data(), phi->data(), rho->data(), rep);
-    stan_hip_matrix_free(G);
-    if (rc) throw std::runtime_error(stan_hip_last_error(K.ctx));
+    const OwnedMatrix G(made);
+    if (stan_hip_buckling(K.ctx, K.K, G.get(), n_modes, tol, 0, solve_eps, 0, factor->data(), phi->data(), rho->data(), rep))
+        throw std::runtime_error(stan_hip_last_error(K.ctx));
 }
 
-void SolverFunctions::Export_Mode_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &prefix, int mode) const {
-    static const char *const names[4] = {"Mode Shape X", "Mode Shape Y", "Mode Shape Z", "Magnitude"};
-    Export_Shape_Vtu(K, shape, prefix + "_mode_", names, mode);
-}
+const SolverFunctions::ShapeKind SolverFunctions::MODE_SHAPE = {"mode", {"Mode Shape X", "Mode Shape Y", "Mode Shape Z", "Magnitude"}};
+const SolverFunctions::ShapeKind SolverFunctions::BUCKLING_SHAPE = {"buckle",
+                                                                    {"Buckling Shape X", "Buckling Shape Y", "Buckling Shape Z", "Magnitude"}};
 
-void SolverFunctions::Export_Buckle_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &prefix, int mode) const {
-    static const char *const names[4] = {"Buckling Shape X", "Buckling Shape Y", "Buckling Shape Z", "Magnitude"};
-    Export_Shape_Vtu(K, shape, prefix + "_buckle_", names, mode);
-}
-
-void SolverFunctions::Export_Shape_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &stem,
-                                       const char *const names[4], int mode) const {
-    const FlatModel &f = K.flat;
-    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
-    std::vector<double> point(4 * (size_t)n_nodes);
-    for (int64_t n = 0; n < n_nodes; n++) {
+void SolverFunctions::Export_Shape_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &prefix,
+                                       const ShapeKind &kind, int number) const {
+    const MeshView v(K.flat);
+    std::vector<double> point(4 * (size_t)v.n_nodes);
+    for (int64_t n = 0; n < v.n_nodes; n++) {
         double s2 = 0;
         for (int c = 0; c < 3; c++) {
-            const double v = shape[(size_t)(3 * n + c)];
-            point[(size_t)c * (size_t)n_nodes + (size_t)n] = v;
-            s2 += v * v;
+            const double x = shape[(size_t)(3 * n + c)];
+            point[(size_t)c * (size_t)v.n_nodes + (size_t)n] = x;
+            s2 += x * x;
         }
-        point[3 * (size_t)n_nodes + (size_t)n] = std::sqrt(s2);
+        point[3 * (size_t)v.n_nodes + (size_t)n] = std::sqrt(s2);
     }
     char num[16];
-    snprintf(num, sizeof num, "%03d", mode);
-    const std::string path = stem + num + ".vtu";
-    if (stan_host_write_vtu(path.c_str(), n_nodes, f.xyz.data(), shape.data(), n_elem, f.conn.data(), 4, names, point.data(), 0, nullptr,
-                            nullptr))
+    snprintf(num, sizeof num, "%03d", number);
+    const std::string path = prefix + "_" + kind.stem + "_" + num + ".vtu";
+    if (stan_host_write_vtu(path.c_str(), v.n_nodes, v.xyz, shape.data(), v.n_elem, v.conn, 4, kind.names, point.data(), 0, nullptr, nullptr))
         throw std::runtime_error("cannot write " + path);
 }
 
 void SolverFunctions::Recovery_Stress_Keep(SparseMatrixHandle &K, const std::vector<double> &dU) const {
-    const FlatModel &f = K.flat;
-    const int64_t n_nodes = (int64_t)(f.xyz.size() / 3), n_elem = (int64_t)f.elem_mat.size();
+    const MeshView v(K.flat);
     if (K.results) { stan_hip_results_free(K.results); K.results = nullptr; }
-    if (stan_hip_recover_hex8_keep(K.ctx, n_nodes, f.xyz.data(), dU.data(), n_elem, f.conn.data(), f.elem_mat.data(),
-                                   f.elem_type.data(), (int32_t)(f.mat_E_nu.size() / 2), f.mat_E_nu.data(), &K.results))
+    if (stan_hip_recover_hex8_keep(K.ctx, v.n_nodes, v.xyz, dU.data(), v.n_elem, v.conn, v.elem_mat, v.elem_type, v.n_mat, v.mat_E_nu,
+                                   &K.results))
         throw std::runtime_error(stan_hip_last_error(K.ctx));  // HEX8_G1: the reference throws too (Element.cs:242)
 }
 
@@ -468,15 +440,24 @@ void SolverFunctions::Export_Vtu(SparseMatrixHandle &K, const std::vector<double
     *t_write = secs(t0);
 }
 
+std::vector<double> SolverFunctions::Nodal_Vector(const SparseMatrixHandle &K, const double *reduced, const std::vector<int32_t> &red) const {
+    const std::vector<int32_t> &node_dof = K.flat.node_dof;
+    std::vector<double> nodal(node_dof.size());
+    ParallelRanges(nodal.size(), [&](size_t a, size_t b) {
+        for (size_t k = a; k < b; k++) {
+            const size_t d = (size_t)node_dof[k];
+            nodal[k] = red[d] == -1 ? 0.0 : reduced[d - (size_t)red[d]];   // Include_BC_DOF's entry d
+        }
+    });
+    return nodal;
+}
 std::vector<double> SolverFunctions::Include_BC_DOF(const std::vector<double> &A, const std::vector<int32_t> &red) const {
     std::vector<double> full(red.size(), 0.0);  // SolverFunctions.cs:520-538
     for (size_t i = 0; i < red.size(); i++) full[i] = red[i] == -1 ? 0.0 : A[i - (size_t)red[i]];
     return full;
 }
 std::vector<double> SolverFunctions::Exclude_BC_DOF(const std::vector<double> &A, const std::vector<int32_t> &red) const {
-    size_t nfix = 0;  // SolverFunctions.cs:540-555
-    for (int32_t r : red) nfix += r == -1;
-    std::vector<double> out(red.size() - nfix, 0.0);
+    std::vector<double> out(n_reduced(red), 0.0);  // SolverFunctions.cs:540-555
     for (size_t i = 0; i < red.size(); i++)
         if (red[i] != -1) out[i - (size_t)red[i]] = A[i];
     return out;

@@ -12,8 +12,10 @@
 // returned regardless (SolverFunctions.cs:323-329).
 #pragma once
 
+#include <memory>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/stan_hip.h"
@@ -33,6 +35,22 @@ class SparseMatrixHandle {
     stan_matrix *K = nullptr;
     FlatModel flat;  // kept for Recovery_Stress (the reference caches J/BL on the elements)
 };
+
+// a stan_matrix that this side made (K + sigma M, M_c, K_g) and frees on every way out
+struct MatrixFree {
+    void operator()(stan_matrix *m) const { stan_hip_matrix_free(m); }
+};
+using OwnedMatrix = std::unique_ptr<stan_matrix, MatrixFree>;
+
+// fn(i0, i1) over [0, n) on the host threads of libstan_host (STAN_HOST_THREADS)
+template <typename F>
+void ParallelRanges(size_t n, F fn) {
+    const size_t nt = (size_t)HostThreads();
+    if (nt <= 1 || n < 4096) { fn((size_t)0, n); return; }
+    std::vector<std::thread> th;
+    for (size_t t = 0; t < nt; t++) th.emplace_back([=] { fn(n * t / nt, n * (t + 1) / nt); });
+    for (std::thread &x : th) x.join();
+}
 
 struct SolverOptions {  // extras of the native driver, never stored in the STdb
     int device = 0;
@@ -104,23 +122,20 @@ class SolverFunctions {
     // ... and the recovered stress loses beta dT at every corner: the host array when given, else the results kept on the
     // device (K.results)
     void Thermal_Stress(SparseMatrixHandle &K, const ThermalLoads &tl, std::vector<double> *stress) const;
-    // Modal analysis (stan_hip_lumped_mass_hex8 + stan_hip_modes; no step of the reference): the lumped mass of `md` and the
-    // n_modes lowest eigenpairs of K phi = lambda M phi; lambda / rho [n_modes], phi [n_modes][N] on the free DOFs; *sums and
-    // *rep always filled.  One device only.
     // the row-sum lumped mass of `md` on the free DOFs, M [N] (stan_hip_lumped_mass_hex8); *sums always filled
     void LumpedMass(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const MassDensity &md, std::vector<double> *M,
                     stan_mass_sums *sums) const;
-    // shift > 0 (a free-free model): stan_hip_modes runs on K + shift M (stan_hip_matrix_shifted) and lambda = mu - shift; rho
-    // and the report are the shifted problem's.
-    void Modes(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const MassDensity &md, int n_modes, double tol,
-               std::vector<double> *lambda, std::vector<double> *phi, std::vector<double> *rho, stan_mass_sums *sums,
-               stan_modes_report *rep, double shift = 0.0) const;
-    // The same on the consistent mass: M_c on K's layout (stan_hip_consistent_mass_hex8) and
+    // Modal analysis (stan_hip_lumped_mass_hex8 + stan_hip_modes; no step of the reference): the lumped mass of `md` and the
+    // n_modes lowest eigenpairs of K phi = lambda M phi; lambda / rho [n_modes], phi [n_modes][N] on the free DOFs; *sums and
+    // *rep always filled.  One device only.  shift > 0 (a free-free model): on K + shift M (stan_hip_matrix_shifted) and
+    // lambda = mu - shift; rho and the report are the shifted problem's.
+    // MASS_CONSISTENT: the same on M_c on K's layout (stan_hip_consistent_mass_hex8) and
     // stan_hip_modes_pencil; shift > 0: on stan_hip_matrix_axpy(K, shift, M_c).  phi is scaled to phi^T M_c phi = 1; *rep holds the
-    // fields the two reports share.
-    void ModesConsistent(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const MassDensity &md, int n_modes, double tol,
-                         std::vector<double> *lambda, std::vector<double> *phi, std::vector<double> *rho, stan_mass_sums *sums,
-                         stan_modes_report *rep, double shift = 0.0) const;
+    // fields the two entries' reports share.
+    enum MassKind { MASS_LUMPED, MASS_CONSISTENT };
+    void Modes(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const MassDensity &md, MassKind mass, int n_modes,
+               double tol, std::vector<double> *lambda, std::vector<double> *phi, std::vector<double> *rho, stan_mass_sums *sums,
+               stan_modes_report *rep, double shift = 0.0) const;
     // Transient dynamics (stan_hip_lumped_mass_hex8 + stan_hip_transient; no step of the reference):
     // implicit Newmark steps of M a + C v + K u = g(t) F from rest, F the reduced external load.  probe_dof: reduced DOFs;
     // probe_u [(n_steps + 1)][n_probe]; snaps [n_snap][3][N] when snap_every > 0; energy [(n_steps + 1)][3]; *sums and *rep
@@ -138,24 +153,27 @@ class SolverFunctions {
     // "Velocity ..." and "Acceleration ...", through the writer of vtu.cpp
     void Export_Step_Vtu(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const double *uva, size_t N,
                          const std::string &prefix, int step) const;
-    // <prefix>_mode_NNN.vtu (NNN = 001 ...) for one mode: shape [n_nodes*3] in NodeLib order as the point arrays "Mode Shape X" /
-    // "Y" / "Z" and "Magnitude", through the writer of vtu.cpp (the shape also takes the place of the displacements)
-    void Export_Mode_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &prefix, int mode) const;
     // Linear buckling (stan_hip_geometric_stiffness_hex8 + stan_hip_buckling; no step of the reference):
     // G = K_g of the static solution nodal_dU [n_nodes*3] (NodeLib order), then the n_modes lowest positive load factors of
     // (K + lambda G) phi = 0; factor / rho [n_modes], phi [n_modes][N] on the free DOFs; *rep always filled.  One device only.
     void Buckling(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const std::vector<double> &nodal_dU, int n_modes,
                   double tol, double solve_eps, std::vector<double> *factor, std::vector<double> *phi, std::vector<double> *rho,
                   stan_buckling_report *rep) const;
-    // <prefix>_buckle_NNN.vtu (NNN = 001 ...) for one buckling shape: as Export_Mode_Vtu with the point arrays "Buckling Shape X" /
-    // "Y" / "Z" and "Magnitude"
-    void Export_Buckle_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &prefix, int mode) const;
-    // what the two share: <stem>NNN.vtu with the four point arrays `names`
-    void Export_Shape_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &stem, const char *const names[4],
-                          int mode) const;
+    // <prefix>_mode_NNN.vtu / <prefix>_buckle_NNN.vtu (NNN = 001 ...) for one mode or buckling shape: shape [n_nodes*3] in NodeLib
+    // order as the point arrays "Mode Shape X" / "Y" / "Z" ("Buckling Shape ...") and "Magnitude", through the writer of vtu.cpp
+    // (the shape also takes the place of the displacements)
+    struct ShapeKind {
+        const char *stem, *names[4];
+    };
+    static const ShapeKind MODE_SHAPE, BUCKLING_SHAPE;
+    void Export_Shape_Vtu(SparseMatrixHandle &K, const std::vector<double> &shape, const std::string &prefix, const ShapeKind &kind,
+                          int number) const;
     // "name,name,..." of --vtu-results -> indices (stan_host_scalar_name's strings; empty text = all 24); false + *err on an unknown name
     static bool ParseScalarNames(const std::string &text, std::vector<int32_t> *sel, std::string *err);
 
+    // a reduced vector [N] in NodeLib order, [n_nodes*3]: U = Include_BC_DOF(U, nDOF_reduction) and node.dU_buffer[d] = U[DOF[d]]
+    // (Solver.cs:168-178) in one pass over the nodes, without the vector over all DOFs in between; 0 at the fixed DOFs
+    std::vector<double> Nodal_Vector(const SparseMatrixHandle &K, const double *reduced, const std::vector<int32_t> &nDOF_reduction) const;
     std::vector<double> Include_BC_DOF(const std::vector<double> &A, const std::vector<int32_t> &nDOF_reduction) const;
     std::vector<double> Exclude_BC_DOF(const std::vector<double> &A, const std::vector<int32_t> &nDOF_reduction) const;
     double Vector_Norm(const std::vector<double> &v) const;
