@@ -1068,6 +1068,85 @@ int stan_hip_newmark_correct(stan_ctx *ctx, int64_t N, const double *u_new, doub
                              double dt, double gamma, const double *M, const double *F, const double *Ku, double gF,
                              double *energy);
 
+/* ---- explicit dynamics: central-difference steps and the stable step ---------------------------- */
+/* No step of the reference.  Two numbers that bracket lambda_max(M^-1 K), M [N] the diagonal mass in the
+ * reduced numbering; the central-difference scheme below is stable for dt <= 2 / sqrt(lambda_max), with or without mass damping.
+ *   lambda_upper  max over the free DOFs d of (sum_j |K_dj|) / M_d, K_dj the values stan_hip_matrix_to_csr exports (a
+ *                 Gershgorin bound): lambda_upper >= lambda_max, so *dt_stable = 2 / sqrt(lambda_upper) is stable by proof.  One
+ *                 pass over K's values; the maximum is order-free: two calls give the same bits.
+ *   lambda_power  n_power > 0: the Rayleigh quotient x.Kx / x.Mx after n_power iterations x <- (K x / M) / sqrt(Kx.Kx / M) from
+ *                 x_0[i] = the integer hash of (i, 0) that starts stan_hip_buckling's block (a fixed vector), n_power + 1
+ *                 products, sums in a fixed order (the quotient's two carried as pairs hi + lo): lambda_power <= lambda_max up to rounding, so a dt above
+ *                 2 / sqrt(lambda_power) is unstable by proof.  n_power = 0: skipped, *lambda_power = 0.
+ * K is read only, scaled or not.  STAN_E_ARG: a NULL pointer, a K of another context or without a free DOF, a negative n_power,
+ * an entry of M that is not positive and finite.  STAN_E_UNSUPPORTED: a multi-device handle, a context with a communicator. */
+int stan_hip_stable_step(stan_ctx *ctx, stan_matrix *K, const double *M, int32_t n_power, double *lambda_upper, double *lambda_power,
+                         double *dt_stable);
+/* The same with M in device memory on the context's GPU (read only, ready on the context's stream); the three results are host
+ * scalars. */
+int stan_hip_stable_step_dev(stan_ctx *ctx, stan_matrix *K, const double *d_M, int32_t n_power, double *lambda_upper,
+                             double *lambda_power, double *dt_stable);
+
+/* M a + alpha_R M v + K u = g(t) F on the free DOFs by explicit central differences: no solve, one product of K and one vector
+ * pass per step, stable for dt <= 2 / sqrt(lambda_max(M^-1 K)).  Every vector is [N] in the reduced numbering.  With dt2 = dt dt,
+ * h = alpha_R dt / 2, om = 1 - h, op = 1 + h one step is, in this order of operations (every product that feeds a sum is
+ * fused with it: fma(g F, -K u), fma(-om u_{n-1}, 2 u_n), fma(dt2 q, .), one rounding each):
+ *   u_{n+1} = ((2 u_n - om u_{n-1}) + dt2 ((g(t_n) F - K u_n) / M)) / op
+ *   v_n     = (u_{n+1} - u_{n-1}) / (2 dt),   a_n = ((u_{n+1} - 2 u_n) + u_{n-1}) / dt2          for n >= 1
+ * and the start is a_0 = ((g(0) F - K u0) - alpha_R (M o v0)) / M, u_{-1} = (u0 - dt v0) + (dt2 / 2) a_0; step 0 reports u0, v0 and
+ * this a_0 (the central differences of step 0 equal them up to rounding); u0 / v0 NULL is zero.  The outputs at step n are
+ * (u_n, v_n, a_n), n = 0 .. n_steps: the loop makes one update more than n_steps, which closes v and a of the last step.  g is
+ * the load curve of stan_hip_transient, evaluated on the host in fp64 at t_n = n dt.  There is no beta_R: stiffness-proportional
+ * damping in an explicit step is a different, lagged scheme.
+ * Outputs, each may be NULL except u_end, v_end, a_end:
+ *   probe_u [(n_steps + 1)][n_probe]  u at the reduced DOFs probe_dof [n_probe] at steps 0 .. n_steps
+ *   snaps   [n_snap][3][N]            u, v, a at steps 0, snap_every, 2 snap_every, ... <= n_steps (snap_every > 0)
+ *   energy  [n_en][3]                 1/2 v.M v, 1/2 u.K u, g F.u at steps 0, energy_every, 2 energy_every, ... <= n_steps
+ *                                     (energy_every > 0; required then); K u is the product the step makes anyway; v is the
+ *                                     central difference at every step, step 0 included; per-workgroup partial sums added in
+ *                                     workgroup order: no atomics on doubles
+ *   u_end, v_end, a_end [N]           the state at step n_steps (n_steps = 0: u0, v0 and a_0)
+ * The stable step: lambda_upper is always computed, and with n_power > 0 lambda_power (stan_hip_stable_step); a dt above
+ * 2 / sqrt(lambda_power) is refused before a step is made.  The loop watches u_{n+1} for entries that are not finite.
+ * rep: a stan_explicit_report or NULL; behind the argument checks it is written on every way out.  K is read only.  Two calls
+ * give the same bits, and so do the host and the _dev entry.
+ * STAN_E_ARG: dt <= 0 or not finite, negative n_steps, n_curve, n_probe, snap_every, energy_every or n_power, alpha_R negative or
+ * not finite, a curve with descending t or a value that is not finite, a probe DOF outside [0, N), NULL where an array is required
+ * (snaps with snap_every = 0 and energy with energy_every = 0 are ignored), an entry of M that is not positive and finite, a K of
+ * another context; n_power > 0 and dt > 2 / sqrt(lambda_power): the message names both numbers and says unstable.
+ * STAN_E_UNSUPPORTED: a multi-device handle, a context with a communicator; an entry of some u_{n+1} that is not finite (an
+ * arithmetic overflow): the step in the report and in stan_hip_last_error.  On an error no output but the report is written. */
+typedef struct stan_explicit_report {
+    int32_t steps;                /* steps made                                                                */
+    int32_t first_nonfinite_step; /* the lowest step n + 1 whose u_{n+1} has an entry that is not finite, 0: none */
+    double lambda_upper;          /* the two brackets of lambda_max(M^-1 K) (lambda_power 0 when n_power = 0)  */
+    double lambda_power;
+    double dt_stable;             /* 2 / sqrt(lambda_upper)                                                    */
+    double product_ms;            /* stream time of the products, the update passes with their finishing sums, */
+    double update_ms;             /*   the row bound and the power iteration, by events when profiling is on,  */
+    double bound_ms;              /*   else zeros                                                              */
+    double power_ms;
+} stan_explicit_report;
+int stan_hip_explicit(stan_ctx *ctx, stan_matrix *K, const double *M, const double *F, const double *u0, const double *v0, double dt,
+                      int32_t n_steps, double alpha_R, int32_t n_curve, const double *curve_t, const double *curve_g, int32_t n_probe,
+                      const int32_t *probe_dof, double *probe_u, int32_t snap_every, double *snaps, int32_t energy_every, double *energy,
+                      double *u_end, double *v_end, double *a_end, int32_t n_power, void *rep);
+/* The same with every array except the curve in device memory on the context's GPU: inputs read only, ready on the context's
+ * stream, naturally aligned; every entry of every output asked for is stored and nothing beside them; complete on return. */
+int stan_hip_explicit_dev(stan_ctx *ctx, stan_matrix *K, const double *d_M, const double *d_F, const double *d_u0, const double *d_v0,
+                          double dt, int32_t n_steps, double alpha_R, int32_t n_curve, const double *curve_t, const double *curve_g,
+                          int32_t n_probe, const int32_t *d_probe_dof, double *d_probe_u, int32_t snap_every, double *d_snaps,
+                          int32_t energy_every, double *d_energy, double *d_u_end, double *d_v_end, double *d_a_end, int32_t n_power,
+                          void *rep);
+/* The update kernel of stan_hip_explicit on host arrays [N] with all of its outputs (introspection, as stan_hip_newmark_correct
+ * is).  y: the step's product, K u (s NULL) or A^ (u / s) of a matrix that carries S K S (s [N] given: K u = y / s in registers,
+ * and u_next_scaled [N] = u_next / s is required).  u_next [N] = u_{n+1} from u = u_n, u_prev = u_{n-1}, M, F, gF = g(t_n).  v, a
+ * [N] (both or neither): v_n, a_n.  energy [3] or NULL: 1/2 v_n.M v_n, 1/2 u_n.K u_n, gF F.u_n, summed as the driver sums them.
+ * *first_nonfinite (may be NULL): `step` if an entry of u_next is not finite, else 0. */
+int stan_hip_central_update(stan_ctx *ctx, int64_t N, const double *y, const double *s, const double *u, const double *u_prev,
+                            const double *M, const double *F, double dt, double alpha_R, double gF, int64_t step, double *u_next,
+                            double *u_next_scaled, double *v, double *a, double *energy, int64_t *first_nonfinite);
+
 /* ---- introspection / parity helpers ------------------------------------------------------- */
 typedef struct stan_matrix_info {
     int64_t n_dof;        /* full DOF count                                      */

@@ -162,6 +162,21 @@ namespace STAN_Solver
         public double correct_ms;
     }
 
+    /// stan_explicit_report (include/stan_hip.h); filled through the IntPtr argument of stan_hip_explicit
+    [StructLayout(LayoutKind.Sequential)]
+    public struct StanExplicitReport
+    {
+        public int steps;
+        public int first_nonfinite_step;
+        public double lambda_upper;
+        public double lambda_power;
+        public double dt_stable;
+        public double product_ms;
+        public double update_ms;
+        public double bound_ms;
+        public double power_ms;
+    }
+
     internal static class StanHipNative
     {
         // "stan_hip" resolves to libstan_hip.so on Linux (.NET probes lib<name>.so; Mono: <dllmap> or the same probing)
@@ -374,6 +389,27 @@ namespace STAN_Solver
         [DllImport(Lib)] internal static extern int stan_hip_newmark_correct(
             IntPtr ctx, long N, double[] u_new, double[] u, double[] v, double[] a, double[] coef, double dt, double gamma,
             double[] M, double[] F, double[] Ku, double gF, [Out] double[] energy);
+
+        // ---- explicit dynamics: the arrays as for stan_hip_transient; energy [(n_steps / energy_every + 1) * 3] or null; rep ->
+        //      StanExplicitReport or IntPtr.Zero.  The update helper: s and u_next_scaled together or both null, v and a likewise
+        [DllImport(Lib)] internal static extern int stan_hip_stable_step(
+            IntPtr ctx, IntPtr K, double[] M, int n_power, out double lambda_upper, out double lambda_power, out double dt_stable);
+        [DllImport(Lib)] internal static extern int stan_hip_stable_step_dev(
+            IntPtr ctx, IntPtr K, IntPtr d_M, int n_power, out double lambda_upper, out double lambda_power, out double dt_stable);
+        [DllImport(Lib)] internal static extern int stan_hip_explicit(
+            IntPtr ctx, IntPtr K, double[] M, double[] F, double[] u0, double[] v0, double dt, int n_steps, double alpha_R,
+            int n_curve, double[] curve_t, double[] curve_g, int n_probe, int[] probe_dof, [Out] double[] probe_u, int snap_every,
+            [Out] double[] snaps, int energy_every, [Out] double[] energy, [Out] double[] u_end, [Out] double[] v_end,
+            [Out] double[] a_end, int n_power, IntPtr rep);
+        [DllImport(Lib)] internal static extern int stan_hip_explicit_dev(
+            IntPtr ctx, IntPtr K, IntPtr d_M, IntPtr d_F, IntPtr d_u0, IntPtr d_v0, double dt, int n_steps, double alpha_R,
+            int n_curve, double[] curve_t, double[] curve_g, int n_probe, IntPtr d_probe_dof, IntPtr d_probe_u, int snap_every,
+            IntPtr d_snaps, int energy_every, IntPtr d_energy, IntPtr d_u_end, IntPtr d_v_end, IntPtr d_a_end, int n_power,
+            IntPtr rep);
+        [DllImport(Lib)] internal static extern int stan_hip_central_update(
+            IntPtr ctx, long N, double[] y, double[] s, double[] u, double[] u_prev, double[] M, double[] F, double dt,
+            double alpha_R, double gF, long step, [Out] double[] u_next, [Out] double[] u_next_scaled, [Out] double[] v,
+            [Out] double[] a, [Out] double[] energy, out long first_nonfinite);
 
         // ---- introspection / parity helpers
         [DllImport(Lib)] internal static extern int stan_hip_matrix_info(IntPtr K, out StanMatrixInfo info);

@@ -135,6 +135,17 @@ struct merit_off {
     ~merit_off() { c->cg_merit_stop = was; }
 };
 
+// The load curve of the time integrators at x: piecewise linear through the n points (t ascending, g), constant before the first
+// and after the last point; the segment is that of the LAST point with t <= x (a repeated t is a jump); no point: 1.  The
+// expression of api_transient.hip's curve_at, which the explicit driver shares through this copy.
+inline double stan_curve_at(int n, const double *t, const double *g, double x) {
+    if (n == 0) return 1.0;
+    if (x <= t[0]) return g[0];
+    if (x >= t[n - 1]) return g[n - 1];
+    const int i = (int)(std::upper_bound(t, t + n, x) - t) - 1;
+    return g[i] + (g[i + 1] - g[i]) * ((x - t[i]) / (t[i + 1] - t[i]));
+}
+
 // stream time of a driver's phases, by one event pair around each piece (profiling on; every piece ends synchronised)
 struct piece_timer {
     stan_ctx *ctx;

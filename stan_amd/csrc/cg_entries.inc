@@ -229,3 +229,17 @@ int stan_spmv_probe(stan_ctx *ctx, stan_matrix *K, const void *vals, size_t byte
     // one launch to warm up, then two groups of three launches, the faster group counts
     return timed_launches(ctx, 1, 2, 3, [&]() { launch_product(ctx, K, P, pa); }, ms_out);
 }
+
+// ---- the product of a loop that keeps its vectors resident (api_explicit.hip) ---------------------------------------------------
+// the never-stopped status words such a loop hands to every product it enqueues: a temporary of `tmp`, filled on the stream
+int stan_product_status(stan_ctx *ctx, dev_scope &tmp, int64_t **stt) { return alloc_never_stopped(ctx, tmp, stt, ctx->stream); }
+
+// yf = A^ xf: ONE plain fp64 product on the caller's vectors in the padded full numbering (3 * nslices * 64 doubles each, what
+// launch_plain_product takes; A^ = S K S once K->scaled), by the plan a solve under the same options gets.  Rows of padding
+// are not stored.  Enqueues only: no allocation, no copy, no synchronisation.  Single rank.
+int stan_product_full(stan_ctx *ctx, stan_matrix *K, const double *xf, double *yf, const int64_t *stt) {
+    if (ctx->nranks != 1) { ctx->err = "product: single-rank contexts only"; return STAN_E_UNSUPPORTED; }
+    launch_plain_product(ctx, K, xf, yf, stt);
+    HIPCHK(ctx, hipGetLastError());
+    return STAN_OK;
+}

@@ -419,6 +419,12 @@ int stan_cg_device(stan_ctx *ctx, stan_matrix *K, const double *d_F, double eps_
 int stan_cg_multi_device(stan_ctx *ctx, stan_matrix *K, int32_t n_rhs, const double *d_F, double eps_f, int32_t max_its,
                          int32_t precision_mode, double *d_U, int32_t *term, int32_t *iters, double *rel_res);
 int stan_spmv_reduced(stan_ctx *ctx, stan_matrix *K, const double *d_x, double *d_y);
+// The product of a loop that keeps its vectors resident (cg_entries.inc): yf = A^ xf on caller-held vectors in the padded full
+// numbering (3 * nslices * 64 doubles; index 3 * row + m; A^ = S K S once K->scaled), ONE plain fp64 product by the plan a
+// solve gets; rows of padding are not stored.  Enqueues only.  stt: the status words of stan_product_status (a temporary of
+// `tmp`, filled on the stream), made once per loop.  Single rank.
+int stan_product_status(stan_ctx *ctx, dev_scope &tmp, int64_t **stt);
+int stan_product_full(stan_ctx *ctx, stan_matrix *K, const double *xf, double *yf, const int64_t *stt);
 int stan_matrix_diagonal(stan_ctx *ctx, stan_matrix *K, double *d_diag);
 int stan_spmv_bench_device(stan_ctx *ctx, stan_matrix *K, int32_t precision_mode, int32_t reps,
                            double *avg_ms);
@@ -634,6 +640,48 @@ int stan_newmark_energy_device(stan_ctx *ctx, int64_t N, const double *u, const 
 int stan_newmark_probe_device(stan_ctx *ctx, int32_t n_probe, const int32_t *d_probe, const double *u, double *row);
 // *bad = the first j whose probe[j] is outside [0, N) (-1: none).  Synchronises.
 int stan_newmark_probe_check_device(stan_ctx *ctx, int64_t N, int32_t n_probe, const int32_t *d_probe, int64_t *bad);
+
+// ---- explicit.hip ---------------------------------------------------------------------------
+// The kernels of the explicit driver (api_explicit.hip): the central-difference update, the maps
+// between the reduced numbering and the padded full one the driver keeps its vectors in, the row bound and the power sums of
+// the stable step.  Vectors are 16-byte aligned memory of the caller of these functions; all enqueue on the context's stream
+// and, unless said otherwise, none synchronises.
+struct stan_cd_coef { double dt, dt2, two_dt, om, op, alpha_R; };   // dt, dt dt, 2 dt, 1 - h, 1 + h with h = alpha_R dt / 2
+inline stan_cd_coef stan_cd_make_coef(double dt, double alpha_R) {
+    const double h = alpha_R * dt / 2.0;
+    return stan_cd_coef{dt, dt * dt, 2.0 * dt, 1.0 - h, 1.0 + h, alpha_R};
+}
+constexpr int STAN_CD_ROWS = 512;   // entries per workgroup of the vector kernels: one pair per lane
+inline int64_t stan_cd_blocks(int64_t n) { return (n + STAN_CD_ROWS - 1) / STAN_CD_ROWS; }
+// out[d] = `fill` at a fixed DOF (red[d] == -1) and in the padding n_dof <= d < n_pad, else in[d - red[d]] (in null: 0), divided
+// by div[d] where div is given: k_expand's mapping
+int stan_cd_expand_device(stan_ctx *ctx, int64_t n_dof, int64_t n_pad, const int32_t *d_red, const double *in, const double *div,
+                          double fill, double *out);
+// out[d - red[d]] = full[d] on the free DOFs; full_of[d - red[d]] = d
+int stan_cd_compress_device(stan_ctx *ctx, int64_t n_dof, const int32_t *d_red, const double *full, double *out);
+int stan_cd_index_device(stan_ctx *ctx, int64_t n_dof, const int32_t *d_red, int32_t *full_of);
+// a = (gF F - Ku - alpha_R (M v)) / M and up = (u - dt v) + (dt2 / 2) a, Ku = y (s null) or y / s
+int stan_cd_start_device(stan_ctx *ctx, int64_t n, const stan_cd_coef &c, double gF, const double *y, const double *s, const double *u,
+                         const double *v, const double *M, const double *F, double *a, double *up);
+// One central-difference update (the expressions: explicit.hip's header).  y: the product of the step (K u_n, or A^ (u_n / s)
+// with s given); up holds u_{n-1} and receives u_{n+1}; xh (s given) receives u_{n+1} / s; v, a non-null: v_n and a_n are
+// stored; d_energy non-null: [3] = 1/2 v_n.M v_n, 1/2 u_n.K u_n, gF F.u_n through d_partial [3][stan_cd_blocks(n)]; flag: the
+// lowest `step` at which an entry of u_{n+1} is not finite (atomicMin on an integer)
+int stan_cd_update_device(stan_ctx *ctx, int64_t n, const stan_cd_coef &c, double gF, long long step, const double *y, const double *s,
+                          const double *un, double *up, const double *M, const double *F, double *xh, double *v, double *a,
+                          double *d_partial, double *d_energy, long long *flag);
+// row[j] = u[full_of[probe[j]]]
+int stan_cd_probe_device(stan_ctx *ctx, int32_t n_probe, const int32_t *d_probe, const int32_t *full_of, const double *u, double *row);
+// *bound (host) = max over the free DOFs d of (sum_j |K_dj|) / Mf[d], K_dj the exported values over the free columns; Mf in
+// the full numbering.  K is read only.  Synchronises.
+int stan_row_bound_device(stan_ctx *ctx, stan_matrix *K, const double *Mf, double *bound);
+// the sums of one power step: d_sums [5] = x.Kx as hi, lo; x.(M x) as hi, lo (unevaluated pairs: error-free products and sums);
+// Kx.Kx / M, with Kx = y or y / s, through d_partial [5][stan_cd_blocks(n)]
+int stan_power_sums_device(stan_ctx *ctx, int64_t n, const double *y, const double *s, const double *x, const double *M,
+                           double *d_partial, double *d_sums);
+// x = (Kx / M) / sqrt(d_sums[4]), xh (s given) = x / s
+int stan_power_next_device(stan_ctx *ctx, int64_t n, const double *y, const double *s, const double *M, const double *d_sums, double *x,
+                           double *xh);
 
 // ---- comm.cpp -------------------------------------------------------------------------------
 int stan_comm_allreduce_sum_f64(stan_ctx *ctx, double *d_buf, size_t count);

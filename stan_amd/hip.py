@@ -63,6 +63,7 @@ EXPORTS = [
     "stan_hip_block_gram", "stan_hip_block_rotate",
     "stan_hip_matrix_shifted", "stan_hip_matrix_shifted_dev", "stan_hip_transient", "stan_hip_transient_dev",
     "stan_hip_newmark_predict", "stan_hip_newmark_correct",
+    "stan_hip_stable_step", "stan_hip_stable_step_dev", "stan_hip_explicit", "stan_hip_explicit_dev", "stan_hip_central_update",
     "stan_hip_kg_hex8_batch", "stan_hip_geometric_stiffness_hex8", "stan_hip_geometric_stiffness_hex8_dev",
     "stan_hip_geometric_stiffness_times", "stan_hip_buckling", "stan_hip_buckling_dev", "stan_hip_buckling_rotate",
     "stan_hip_mass_hex8_batch", "stan_hip_consistent_mass_hex8", "stan_hip_consistent_mass_hex8_dev",
@@ -158,6 +159,16 @@ class TransientReport(C.Structure):
                 ("cg_max_iterations", C.c_int32), ("reserved", C.c_int32), ("cg_iterations", C.c_int64), ("sigma", C.c_double),
                 ("shift_ms", C.c_double), ("solve_ms", C.c_double), ("product_ms", C.c_double), ("step_ms", C.c_double),
                 ("predict_ms", C.c_double), ("correct_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ExplicitReport(C.Structure):
+    """stan_explicit_report (include/stan_hip.h)"""
+    _fields_ = [("steps", C.c_int32), ("first_nonfinite_step", C.c_int32), ("lambda_upper", C.c_double), ("lambda_power", C.c_double),
+                ("dt_stable", C.c_double), ("product_ms", C.c_double), ("update_ms", C.c_double), ("bound_ms", C.c_double),
+                ("power_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -764,6 +775,23 @@ class Context:
             _ptr(Ku, C.c_double), C.c_double(gF), _ptr(e, C.c_double)))
         return u, v, a, e
 
+    def central_update(self, y, u, u_prev, M, F, dt, alpha_R=0.0, gF=1.0, step=1, s=None, state=True, energy=False):
+        """stan_hip_central_update: dict(u_next, u_next_scaled or None, v, a (or None), energy [3] or None, first_nonfinite) of
+        one central-difference update on host arrays [N]; y = K u, or A^ (u / s) with s given."""
+        y, u, u_prev, M, F = (np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (y, u, u_prev, M, F))
+        N = y.shape[0]
+        s = None if s is None else np.ascontiguousarray(s, dtype=np.float64).reshape(-1)
+        if any(x.shape[0] != N for x in (u, u_prev, M, F)) or (s is not None and s.shape[0] != N):
+            raise ValueError("central_update: the vectors must be [N]")
+        un, uh = np.zeros(N), (None if s is None else np.zeros(N))
+        v, a = (np.zeros(N), np.zeros(N)) if state else (None, None)
+        e, bad = (np.zeros(3) if energy else None), C.c_int64(0)
+        self._chk(self.lib.stan_hip_central_update(
+            self.h, C.c_int64(N), _ptr(y, C.c_double), _ptr(s, C.c_double), _ptr(u, C.c_double), _ptr(u_prev, C.c_double),
+            _ptr(M, C.c_double), _ptr(F, C.c_double), C.c_double(dt), C.c_double(alpha_R), C.c_double(gF), C.c_int64(step),
+            _ptr(un, C.c_double), _ptr(uh, C.c_double), _ptr(v, C.c_double), _ptr(a, C.c_double), _ptr(e, C.c_double), C.byref(bad)))
+        return dict(u_next=un, u_next_scaled=uh, v=v, a=a, energy=e, first_nonfinite=bad.value)
+
     def _thermal_stress_args(self, dT, conn, elem_mat, elem_type, mat_E_nu, mat_alpha):
         dT = np.ascontiguousarray(dT, dtype=np.float64).reshape(-1)
         conn, elem_mat, elem_type, mat_E_nu = _mesh(conn=conn, elem_mat=elem_mat, elem_type=elem_type, mat_E_nu=mat_E_nu)
@@ -1103,6 +1131,76 @@ class Matrix:
             _ptr(cg, C.c_double), C.c_double(solve_eps), C.c_int32(solve_max_its), C.c_int32(int(n_probe)),
             _opt(d_probe_dof, C.c_int32), _opt(d_probe_u), C.c_int32(int(snap_every)), _opt(d_snaps), _opt(d_energy),
             _opt(d_u_end), _opt(d_v_end), _opt(d_a_end), C.byref(rep)))
+        return rep.as_dict()
+
+    def stable_step(self, M, n_power=0):
+        """stan_hip_stable_step: (lambda_upper, lambda_power, dt_stable) of M^-1 K, M [N] the lumped mass."""
+        M = np.ascontiguousarray(M, dtype=np.float64).reshape(-1)
+        if M.shape[0] != self.info()["n_reduced"]:
+            raise ValueError("stable_step: M must be [N]")
+        lu, lp, dts = C.c_double(0), C.c_double(0), C.c_double(0)
+        self.ctx._chk(self.ctx.lib.stan_hip_stable_step(self.ctx.h, self.k, _ptr(M, C.c_double), C.c_int32(int(n_power)),
+                                                        C.byref(lu), C.byref(lp), C.byref(dts)))
+        return lu.value, lp.value, dts.value
+
+    def stable_step_dev(self, d_M, n_power=0):
+        """d_M: a device pointer (int)."""
+        lu, lp, dts = C.c_double(0), C.c_double(0), C.c_double(0)
+        self.ctx._chk(self.ctx.lib.stan_hip_stable_step_dev(self.ctx.h, self.k, _opt(d_M), C.c_int32(int(n_power)),
+                                                            C.byref(lu), C.byref(lp), C.byref(dts)))
+        return lu.value, lp.value, dts.value
+
+    @staticmethod
+    def _curve(curve):
+        if curve is None:
+            return None, None, 0
+        cv = np.ascontiguousarray(curve, dtype=np.float64).reshape(-1, 2)
+        return np.ascontiguousarray(cv[:, 0]), np.ascontiguousarray(cv[:, 1]), cv.shape[0]
+
+    def explicit(self, M, F, dt, n_steps, u0=None, v0=None, alpha_R=0.0, curve=None, probe_dof=None, snap_every=0, energy_every=0,
+                 n_power=0, out=None):
+        """stan_hip_explicit: central-difference steps of M a + alpha_R M v + K u = g(t) F.  curve: [(t, g), ...] or None (g = 1).
+        Returns a dict: u, v, a (the state at step n_steps), probe_u [n_steps + 1, n_probe], snaps [n_snap, 3, N] or None, energy
+        [n_en, 3] or None, report (stan_explicit_report; written on an error too: StanHipError.report).  out: a dict of
+        preallocated arrays under the same names, used instead of fresh ones (a refused call must leave them untouched)."""
+        N = self.info()["n_reduced"]
+        M, F = (np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (M, F))
+        u0, v0 = (None if x is None else np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (u0, v0))
+        if any(x is not None and x.shape[0] != N for x in (M, F, u0, v0)):
+            raise ValueError("explicit: M, F, u0, v0 must be [N]")
+        ct, cg, nc = self._curve(curve)
+        pd = None if probe_dof is None else np.ascontiguousarray(probe_dof, dtype=np.int32).reshape(-1)
+        npr = 0 if pd is None else pd.shape[0]
+        steps = max(int(n_steps), 0)
+        o = dict(out or {})
+        pu = o.get("probe_u", np.zeros((steps + 1, npr)) if npr else None)
+        sn = o.get("snaps", np.zeros((steps // snap_every + 1, 3, N)) if snap_every > 0 else None)
+        en = o.get("energy", np.zeros((steps // energy_every + 1, 3)) if energy_every > 0 else None)
+        ue, ve, ae = (o.get(k, None) for k in ("u", "v", "a"))
+        ue, ve, ae = (np.zeros(N) if x is None else x for x in (ue, ve, ae))
+        rep = ExplicitReport()
+        rc = self.ctx.lib.stan_hip_explicit(
+            self.ctx.h, self.k, _ptr(M, C.c_double), _ptr(F, C.c_double), _ptr(u0, C.c_double), _ptr(v0, C.c_double),
+            C.c_double(dt), C.c_int32(int(n_steps)), C.c_double(alpha_R), C.c_int32(nc), _ptr(ct, C.c_double), _ptr(cg, C.c_double),
+            C.c_int32(npr), _ptr(pd, C.c_int32), _ptr(pu, C.c_double), C.c_int32(int(snap_every)), _ptr(sn, C.c_double),
+            C.c_int32(int(energy_every)), _ptr(en, C.c_double), _ptr(ue, C.c_double), _ptr(ve, C.c_double), _ptr(ae, C.c_double),
+            C.c_int32(int(n_power)), C.byref(rep))
+        if rc != 0:
+            e = StanHipError(rc, self.ctx.lib.stan_hip_last_error(self.ctx.h).decode())
+            e.report = rep.as_dict()
+            raise e
+        return dict(u=ue, v=ve, a=ae, probe_u=pu, snaps=sn, energy=en, report=rep.as_dict())
+
+    def explicit_dev(self, d_M, d_F, dt, n_steps, d_u_end, d_v_end, d_a_end, d_u0=None, d_v0=None, alpha_R=0.0, curve=None, n_probe=0,
+                     d_probe_dof=None, d_probe_u=None, snap_every=0, d_snaps=None, energy_every=0, d_energy=None, n_power=0):
+        """Every d_* is a device pointer (int) or None; the curve stays on the host.  Returns the report dict."""
+        ct, cg, nc = self._curve(curve)
+        rep = ExplicitReport()
+        self.ctx._chk(self.ctx.lib.stan_hip_explicit_dev(
+            self.ctx.h, self.k, _opt(d_M), _opt(d_F), _opt(d_u0), _opt(d_v0), C.c_double(dt), C.c_int32(int(n_steps)),
+            C.c_double(alpha_R), C.c_int32(nc), _ptr(ct, C.c_double), _ptr(cg, C.c_double), C.c_int32(int(n_probe)),
+            _opt(d_probe_dof, C.c_int32), _opt(d_probe_u), C.c_int32(int(snap_every)), _opt(d_snaps), C.c_int32(int(energy_every)),
+            _opt(d_energy), _opt(d_u_end), _opt(d_v_end), _opt(d_a_end), C.c_int32(int(n_power)), C.byref(rep)))
         return rep.as_dict()
 
     def to_csr(self, upper_only=True):

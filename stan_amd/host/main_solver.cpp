@@ -46,13 +46,21 @@ static const char *const kUsage =
     "[--transient --dt DT --steps N [--newmark B,G] [--rayleigh A,B] [--load-curve t0,g0,t1,g1,...] [--probe-node ID] "
     "[--solve-eps E] [--vtu PREFIX [--vtu-every K]]] <model.STdb>\n";
 
+// what --help prints behind kUsage (kUsage itself is pinned text: tests/golden/console_refusals.json)
+static const char *const kExplicitUsage =
+    "       stan_solver --explicit --steps N [--dt DT | --dt auto] [--dt-scale S] [--rayleigh A,0] [--load-curve t0,g0,t1,g1,...] "
+    "[--probe-node ID] [--json] [--vtu PREFIX [--vtu-every K]] <model.STdb>\n"
+    "         --dt auto     dt = S * 2 / sqrt(lambda_upper), lambda_upper the Gershgorin row bound of M^-1 K: stable by proof\n"
+    "         --dt-scale S  default 0.9: the usual convention of explicit codes, not a measured value\n";
+
 // ---- options ------------------------------------------------------------------------------------------------------------------
 // --device N, --gpus N (devices 0..N-1) or --devices a,b,c (several GPUs from this ONE process: stan_hip_init_multi, rows of K
 // sharded, RCCL inside the CG), --mixed, --fixed48, --no-merit-stop, --packed, --placement-tries N (default 16; 1 = plain
 // allocation), --p2p (several GPUs: the CG exchanges peer to peer instead of over RCCL, STAN_OPT_COMM_P2P), --object-results
 // (store the results in the Node / Element objects before the export, as the reference does, instead of encoding them from the
 // flat arrays: same bytes), --json (one JSON line with sizes, iterations, device and host phase times and the SpMV's HBM rate);
-// --vtu, --reactions: RunStatics; --modes, --modes-shift, --mass: RunModes; --buckling: RunBuckling; --transient: RunTransient.
+// --vtu, --reactions: RunStatics; --modes, --modes-shift, --mass: RunModes; --buckling: RunBuckling; --transient: RunTransient;
+// --explicit (with --dt auto, --dt-scale): RunExplicit; --help: the usage lines.
 struct CliOptions {
     std::string path;
     int device = 0, precision = STAN_PREC_FP64, placement_tries = 16;
@@ -71,6 +79,8 @@ struct CliOptions {
     SolverFunctions::TransientRun run;
     int probe_node = 0, vtu_every = 1;
     bool have_probe = false;
+    bool explicit_run = false, explicit_arg = false, dt_auto = false, help = false;   // --explicit; --dt auto / --dt-scale seen
+    double dt_scale = 0.9;
     bool several_devices() const { return devices.size() > 1; }
 };
 
@@ -133,6 +143,10 @@ static CliOptions ParseArgs(int argc, char **argv) {
         else if (value("--modes-shift")) o.modes_shift = atof(argv[++i]);
         else if (value("--mass")) o.mass_kind = argv[++i];
         else if (flag("--transient")) o.transient = true;
+        else if (flag("--help")) o.help = true;
+        else if (flag("--explicit")) o.explicit_run = true;
+        else if (value("--dt-scale")) { o.transient_arg = o.explicit_arg = true; o.dt_scale = atof(argv[++i]); }
+        else if (value("--dt") && !strcmp(argv[i + 1], "auto")) { o.transient_arg = o.explicit_arg = o.dt_auto = true; i++; }
         else if (value("--dt")) { o.transient_arg = true; run.dt = atof(argv[++i]); }
         else if (value("--steps")) { o.transient_arg = true; run.n_steps = atoi(argv[++i]); }
         else if (value("--buckling")) { o.buckling_arg = true; o.buckling = atoi(argv[++i]); }
@@ -188,6 +202,27 @@ static std::string Refusal(const CliOptions &o) {
             return OneDevice("--buckling works",
                              "the geometric stiffness adds up all elements at a node, and the block solves run on a single-rank context");
     }
+    if (o.explicit_arg && !o.explicit_run) return "--dt auto and --dt-scale belong to --explicit";
+    if (o.explicit_run) {
+        if (o.modes || o.transient || o.buckling_arg) return "--explicit, --transient, --modes and --buckling are four analyses: one per run";
+        if (o.bad_list) return "--rayleigh A,0 takes two numbers, --load-curve t0,g0,t1,g1,... an even count of them";
+        if (!o.dt_auto && (!(run.dt > 0) || !std::isfinite(run.dt))) return "--explicit needs --dt DT with DT > 0, or --dt auto";
+        if (o.dt_auto && run.dt != 0) return "--dt DT and --dt auto are two steps: one per run";
+        if (!(o.dt_scale > 0) || !std::isfinite(o.dt_scale)) return "--dt-scale S needs S > 0";
+        if (run.n_steps < 0) return "--steps N needs N >= 0";
+        if (o.vtu_every < 1) return "--vtu-every K needs K >= 1";
+        if (run.beta_N != 0 || run.gamma != 0 || o.have_solve_eps) return "--newmark and --solve-eps belong to --transient: an explicit step has no solve";
+        if (run.beta_R != 0)
+            return "--explicit takes --rayleigh A,0 only: beta_R, the stiffness-proportional damping, is a different, lagged scheme in an explicit step";
+        if (!(run.alpha_R >= 0) || !std::isfinite(run.alpha_R)) return "--rayleigh A,0 needs A >= 0";
+        for (size_t k = 0; k < run.curve_t.size(); k++)
+            if (!std::isfinite(run.curve_t[k]) || !std::isfinite(run.curve_g[k]) || (k > 0 && run.curve_t[k] < run.curve_t[k - 1]))
+                return "--load-curve needs finite values and times that do not descend";
+        if (several)
+            return OneDevice("--explicit works", "the lumped mass adds up all elements at a node, and the resident product and the step sums run "
+                                                 "on a single-rank context");
+        return "";
+    }
     if (!o.transient && o.transient_arg)
         return "--dt, --steps, --newmark, --rayleigh, --load-curve, --probe-node, --solve-eps and --vtu-every belong to --transient";
     if (o.transient) {
@@ -213,7 +248,7 @@ static std::string Refusal(const CliOptions &o) {
 // ... and what is wrong with the file for the analysis that was asked for: --modes and --transient need the densities, all three
 // the static analysis they replace or start from; the stress state of --buckling is sigma = D B u, a thermal part is out of scope
 static std::string FileRefusal(const CliOptions &o, const Database &DB) {
-    const std::string analysis = o.modes ? "--modes" : o.transient ? "--transient" : o.buckling ? "--buckling" : "";
+    const std::string analysis = o.modes ? "--modes" : o.transient ? "--transient" : o.explicit_run ? "--explicit" : o.buckling ? "--buckling" : "";
     if (analysis.empty()) return "";
     if (!o.buckling && !HasDensity(DB))
         return analysis + " needs a \"Density\" boundary condition (material IDs, component 0 = rho): the file has none";
@@ -508,6 +543,77 @@ static int RunTransient(const SolverFunctions &Functions, const CliOptions &o, P
     return 0;
 }
 
+// --explicit --steps N [--dt DT | --dt auto] [--dt-scale S] [--rayleigh A,0] [--load-curve ...] [--probe-node ID] (DESIGN.md section
+// 3.14) integrates M a + alpha_R M v + K u = g(t) F from rest by stan_hip_explicit INSTEAD of the static solve and never writes the
+// STdb: the load, the curve, the supports, the probe and the .vtu files as for --transient; --dt auto is S * 2 / sqrt(lambda_upper), S
+// = 0.9 unless --dt-scale gives it.  A block "Explicit:", with --json an "explicit" object.  One device only; a file without a
+// "Density" entry is refused.
+static int RunExplicit(const SolverFunctions &Functions, const CliOptions &o, Prepared &m) {
+    for (double x : m.dl.disp0)
+        if (x != 0.0) return refuse("--explicit takes homogeneous supports only: the file prescribes a non-zero \"Displacement\"");
+    SolverFunctions::ExplicitRun run;
+    run.dt_auto = o.dt_auto; run.dt = o.run.dt; run.dt_scale = o.dt_scale; run.alpha_R = o.run.alpha_R; run.n_steps = o.run.n_steps;
+    run.snap_every = o.run.snap_every; run.curve_t = o.run.curve_t; run.curve_g = o.run.curve_g;
+    int probe_dir[3] = {0, 0, 0};
+    if (o.have_probe && !ProbeDofs(o, m, &run.probe_dof, probe_dir))
+        return refuse("--probe-node " + std::to_string(o.probe_node) + ": the file has no such node");
+    std::string err;
+    MassDensity md;
+    if (BuildDensity(m.DB, m.K.flat, &md, &err)) return fail("boundary conditions", err);
+    std::vector<double> probe_u, snaps, energy;
+    stan_mass_sums msum{};
+    stan_explicit_report rep{};
+    Functions.Explicit(m.K, m.nDOF_reduction, md, m.F_solve(), &run, &probe_u, &snaps, &energy, &msum, &rep);
+    const size_t np = run.probe_dof.size(), N = (size_t)m.minfo.n_reduced;
+    printf("   Total mass: %.6e   volume: %.6e\n", msum.total_mass, msum.volume);
+    printf("   Explicit: (%d steps of dt %.6e%s, central differences, Rayleigh alpha %g)\n", rep.steps, run.dt,
+           run.dt_auto ? " = dt-scale x dt_stable" : "", run.alpha_R);
+    printf("     dt_stable = 2 / sqrt(lambda_upper): %.8e\n", rep.dt_stable);
+    printf("     lambda_upper (row bound): %.8e   lambda_power (%d iterations, a lower bound): %.8e\n", rep.lambda_upper, run.n_power,
+           rep.lambda_power);
+    if (np) {
+        printf("     Probe node %d:\n       step                 t", o.probe_node);
+        for (size_t q = 0; q < np; q++) printf("                u%c", "xyz"[probe_dir[q]]);
+        printf("\n");
+        for (int s = 0; s <= run.n_steps; s++) {
+            printf("     %6d  %16.8e", s, (double)s * run.dt);
+            for (size_t q = 0; q < np; q++) printf("  %16.8e", probe_u[(size_t)s * np + q]);
+            printf("\n");
+        }
+    }
+    const double *ef = &energy[energy.size() - 3];
+    printf("     Final energies: kinetic %.8e  strain %.8e  external %.8e\n", ef[0], ef[1], ef[2]);
+    if (o.vtu) {
+        int last = 0;
+        for (int s = 0; s <= run.n_steps; s += o.vtu_every) {
+            Functions.Export_Step_Vtu(m.K, m.nDOF_reduction, &snaps[(size_t)(s / o.vtu_every) * 3 * N], N, o.vtu_prefix, s);
+            last = s;
+        }
+        printf("   VTU export: %s_step_0000.vtu ... %s_step_%04d.vtu\n", o.vtu_prefix.c_str(), o.vtu_prefix.c_str(), last);
+    }
+    ClosingBanner(m);
+    if (o.json) {
+        JsonHead(m, "explicit");
+        printf("\"steps\": %d, \"dt\": %.17g, \"dt_auto\": %d, \"dt_scale\": %.17g, \"dt_stable\": %.17g, \"lambda_upper\": %.17g, "
+               "\"lambda_power\": %.17g, \"n_power\": %d, \"alpha_R\": %.17g, \"first_nonfinite_step\": %d, \"total_mass\": %.17g",
+               rep.steps, run.dt, run.dt_auto ? 1 : 0, run.dt_scale, rep.dt_stable, rep.lambda_upper, rep.lambda_power, run.n_power,
+               run.alpha_R, rep.first_nonfinite_step, msum.total_mass);
+        JsonArray("energy_final", ef, 3);
+        if (np) {
+            printf(", \"probe_node\": %d, \"probe_direction\": [", o.probe_node);
+            for (size_t q = 0; q < np; q++) printf("%s%d", q ? ", " : "", probe_dir[q]);
+            printf("], \"probe_u\": [");
+            for (int s = 0; s <= run.n_steps; s++) {
+                printf("%s", s ? ", " : "");
+                JsonNumbers(&probe_u[(size_t)s * np], np);
+            }
+            printf("]");
+        }
+        printf("}}\n");
+    }
+    return 0;
+}
+
 // --buckling K [--buckling-tol T] [--solve-eps E] runs the static solve under the model's own loads, builds
 // G = K_g(U) (stan_hip_geometric_stiffness_hex8) and finds the K lowest positive load factors (stan_hip_buckling): a block
 // "Buckling load factors:", with --json a "buckling" object, with --vtu PREFIX one PREFIX_buckle_NNN.vtu per factor; the STdb is
@@ -717,6 +823,11 @@ static int RunStatics(SolverFunctions &Functions, const CliOptions &o, Prepared 
 
 int main(int argc, char **argv) {
     const CliOptions o = ParseArgs(argc, argv);
+    if (o.help) {
+        fputs(kUsage, stdout);
+        fputs(kExplicitUsage, stdout);
+        return 0;
+    }
     if (o.path.empty()) {  // Path = path[0] -> IndexOutOfRangeException in the reference
         fputs(kUsage, stderr);
         return 2;
@@ -743,6 +854,7 @@ int main(int argc, char **argv) {
         if (o.modes) return RunModes(Functions, o, m);   // before the loads are built
         if (int rc = BuildLoads(Functions, &m)) return rc;
         if (o.transient) return RunTransient(Functions, o, m);
+        if (o.explicit_run) return RunExplicit(Functions, o, m);
         if (o.buckling) return RunBuckling(Functions, o, m);
         return RunStatics(Functions, o, m);
     } catch (const std::exception &e) {  // the C# lets these escape Main as unhandled exceptions

@@ -308,6 +308,30 @@ void SolverFunctions::Transient(SparseMatrixHandle &K, const std::vector<int32_t
         throw std::runtime_error(stan_hip_last_error(K.ctx));
 }
 
+void SolverFunctions::Explicit(SparseMatrixHandle &K, const std::vector<int32_t> &red, const MassDensity &md, const std::vector<double> &F,
+                               ExplicitRun *run, std::vector<double> *probe_u, std::vector<double> *snaps, std::vector<double> *energy,
+                               stan_mass_sums *sums, stan_explicit_report *rep) const {
+    std::vector<double> M;
+    LumpedMass(K, red, md, &M, sums);
+    if (run->dt_auto) {
+        double upper = 0, power = 0, dt_stable = 0;
+        if (stan_hip_stable_step(K.ctx, K.K, M.data(), 0, &upper, &power, &dt_stable)) throw std::runtime_error(stan_hip_last_error(K.ctx));
+        run->dt = run->dt_scale * dt_stable;
+    }
+    const size_t N = M.size(), rows = (size_t)run->n_steps + 1, np = run->probe_dof.size();
+    const size_t n_snap = run->snap_every > 0 ? (size_t)(run->n_steps / run->snap_every) + 1 : 0;
+    const int energy_every = run->n_steps > 0 ? run->n_steps : 1;   // steps 0 and n_steps: a long run does not pay the sums each step
+    probe_u->assign(rows * np, 0.0);
+    snaps->assign(n_snap * 3 * N, 0.0);
+    energy->assign((size_t)(run->n_steps / energy_every + 1) * 3, 0.0);
+    std::vector<double> u(N), v(N), a(N);
+    if (stan_hip_explicit(K.ctx, K.K, M.data(), F.data(), nullptr, nullptr, run->dt, run->n_steps, run->alpha_R, (int32_t)run->curve_t.size(),
+                          run->curve_t.data(), run->curve_g.data(), (int32_t)np, np ? run->probe_dof.data() : nullptr,
+                          np ? probe_u->data() : nullptr, run->snap_every, n_snap ? snaps->data() : nullptr, energy_every, energy->data(),
+                          u.data(), v.data(), a.data(), run->n_power, rep))
+        throw std::runtime_error(stan_hip_last_error(K.ctx));
+}
+
 void SolverFunctions::Export_Step_Vtu(SparseMatrixHandle &K, const std::vector<int32_t> &red, const double *uva, size_t N,
                                       const std::string &prefix, int step) const {
     const MeshView v(K.flat);

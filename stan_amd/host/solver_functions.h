@@ -149,6 +149,21 @@ class SolverFunctions {
     void Transient(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const MassDensity &md, const std::vector<double> &F,
                    const TransientRun &run, std::vector<double> *probe_u, std::vector<double> *snaps, std::vector<double> *energy,
                    stan_mass_sums *sums, stan_transient_report *rep) const;
+    // Explicit dynamics (stan_hip_lumped_mass_hex8 + stan_hip_stable_step + stan_hip_explicit; no step of the reference, DESIGN.md
+    // section 3.14): central-difference steps of M a + alpha_R M v + K u = g(t) F from rest.  dt_auto: run->dt becomes dt_scale *
+    // 2 / sqrt(lambda_upper) (the row bound, before the run).  n_power iterations give the report's lambda_power; a dt it proves
+    // unstable is the library's refusal.  probe_u [(n_steps + 1)][n_probe]; snaps [n_snap][3][N] when snap_every > 0; energy [2][3]
+    // (n_steps = 0: [1][3]): steps 0 and n_steps; *sums and *rep always filled.  One device only.
+    struct ExplicitRun {
+        bool dt_auto = false;
+        double dt = 0, dt_scale = 0.9, alpha_R = 0;
+        int n_steps = 0, snap_every = 0, n_power = 30;
+        std::vector<double> curve_t, curve_g;
+        std::vector<int32_t> probe_dof;
+    };
+    void Explicit(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const MassDensity &md, const std::vector<double> &F,
+                  ExplicitRun *run, std::vector<double> *probe_u, std::vector<double> *snaps, std::vector<double> *energy,
+                  stan_mass_sums *sums, stan_explicit_report *rep) const;
     // <prefix>_step_NNNN.vtu for one snapshot: u, v, a [N] on the free DOFs as the point arrays "Displacement X" / "Y" / "Z",
     // "Velocity ..." and "Acceleration ...", through the writer of vtu.cpp
     void Export_Step_Vtu(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const double *uva, size_t N,
