@@ -1147,6 +1147,63 @@ int stan_hip_central_update(stan_ctx *ctx, int64_t N, const double *y, const dou
                             const double *M, const double *F, double dt, double alpha_R, double gF, int64_t step, double *u_next,
                             double *u_next_scaled, double *v, double *a, double *energy, int64_t *first_nonfinite);
 
+/* ---- frequency response: modal superposition with a static correction ------------------------- */
+/* No step of the reference.  The steady-state response u(t) = Re(x e^{i w t}) of
+ * M a + C v + K u = Re(F e^{i w t}) at n_freq circular frequencies omega [n_freq] (rad/s) from n_modes <= 32 M-orthonormal
+ * eigenpairs (lambda [n_modes], phi [n_modes][N], as stan_hip_modes or stan_hip_modes_pencil deliver them: Phi^T M Phi = I, so
+ * neither K nor M is needed), every vector [N] in the reduced numbering.  Mode j is damped by
+ *   c_j = alpha_R + beta_R lambda_j + 2 zeta_j sqrt(lambda_j)          (zeta [n_modes] or NULL: zeros)
+ * and the response is
+ *   x_f = r + sum_j phi_j (a_jf + i b_jf),   p_j = phi_j . F,   r = u_static - sum_j phi_j (p_j / lambda_j)   (u_static NULL: r = 0)
+ * u_static = K^-1 F (stan_hip_cg_solve) makes r the static response of the modes that were left out: the static correction; it is
+ * not damped.  In this order of operations (every product that feeds a sum is fused with it, one rounding):
+ *   p_j   a term fma(phi_jd, F_d, .), rows ascending per lane, a fixed order inside a workgroup, the workgroups' partial sums
+ *         added in workgroup order: no atomics on doubles
+ *   r_d   u_static_d, then fma(-phi_jd, p_j / lambda_j, .) for j ascending
+ *   table on the host in fp64:  c_j = fma(2 zeta_j, sqrt(lambda_j), fma(beta_R, lambda_j, alpha_R));  d = fma(-w, w, lambda_j);
+ *         e = w c_j;  D = fma(d, d, e e);  a_jf = p_j (d / D);  b_jf = -(p_j (e / D))
+ *   re    r_d, then fma(phi_jd, a_jf, .) for j ascending;   im: 0, then fma(phi_jd, b_jf, .) for j ascending
+ *   peak  amp2 = fma(re, re, im im); peak [N] = sqrt of the largest amp2 over the frequencies, peak_idx [N] the lowest frequency
+ *         index that attains it; the sweep is one fused pass: Phi is read once, the n_freq responses of a DOF never leave the
+ *         registers
+ * Outputs, each may be NULL except p; peak and peak_idx go together:
+ *   probe [n_freq][n_probe][2]   (re, im) at the reduced DOFs probe_dof [n_probe] for every frequency
+ *   snaps [n_snap][2][N]         re and im at the frequency indices snap_freq [n_snap]: the bits the sweep computed there, and
+ *                                the bits of the probes at the same DOFs
+ *   p [n_modes]                  the modal loads
+ * rep: a stan_harmonic_report or NULL; behind the argument checks it is written on every way out.  Inputs are read only.  The
+ * call orders itself on the context's stream (stan_hip_set_stream).  Two calls give the same bits, and so do the host and the _dev
+ * entry.
+ * STAN_E_ARG: N <= 0, n_modes <= 0 or > 32, n_freq <= 0 or > 65536, negative n_probe or n_snap, a NULL required pointer, peak
+ * without peak_idx, a lambda_j that is not positive and finite, a negative or non-finite alpha_R, beta_R, zeta_j or omega_f, a probe
+ * DOF outside [0, N), a snap_freq outside [0, n_freq), a frequency with D == 0 or D not finite for a mode (an undamped load exactly
+ * on a resonance): stan_hip_last_error names the index of the frequency and of the mode.  STAN_E_UNSUPPORTED: a multi-device handle,
+ * a context with a communicator.  Every one of them is found before anything is launched: on an error no output but the report is
+ * written. */
+typedef struct stan_harmonic_report {
+    int32_t n_modes;
+    int32_t n_freq;
+    int64_t peak_dof;            /* the DOF of the largest entry of peak (the lowest on a tie); -1 without peak, */
+    double peak;                 /*   and when no entry of peak is a number (phi or F not finite): peak is NaN   */
+    int32_t peak_freq;           /* its frequency index, -1 where peak_dof is                                    */
+    int32_t static_correction;   /* 1: u_static was given                                                        */
+    double project_ms;           /* stream time of the projection (p and r), the sweep with its reduction, the   */
+    double sweep_ms;             /*   snapshots and the probes, by events when profiling is on, else zeros       */
+    double snap_ms;
+    double probe_ms;
+} stan_harmonic_report;
+int stan_hip_harmonic(stan_ctx *ctx, int64_t N, int32_t n_modes, const double *lambda, const double *phi, const double *F,
+                      const double *u_static, double alpha_R, double beta_R, const double *zeta, int32_t n_freq, const double *omega,
+                      int32_t n_probe, const int32_t *probe_dof, double *probe, int32_t n_snap, const int32_t *snap_freq, double *snaps,
+                      double *p, double *peak, int32_t *peak_idx, void *rep);
+/* The same with every array except omega, zeta and snap_freq in device memory on the context's GPU: inputs read only, ready on the
+ * context's stream, naturally aligned; every entry of every output asked for is stored and nothing beside them; complete on
+ * return. */
+int stan_hip_harmonic_dev(stan_ctx *ctx, int64_t N, int32_t n_modes, const double *d_lambda, const double *d_phi, const double *d_F,
+                          const double *d_u_static, double alpha_R, double beta_R, const double *zeta, int32_t n_freq, const double *omega,
+                          int32_t n_probe, const int32_t *d_probe_dof, double *d_probe, int32_t n_snap, const int32_t *snap_freq,
+                          double *d_snaps, double *d_p, double *d_peak, int32_t *d_peak_idx, void *rep);
+
 /* ---- introspection / parity helpers ------------------------------------------------------- */
 typedef struct stan_matrix_info {
     int64_t n_dof;        /* full DOF count                                      */

@@ -115,6 +115,13 @@ const char *stan_host_scalar_name(int32_t s);
 int stan_host_write_vtu(const char *path, int64_t n_nodes, const double *xyz, const double *disp, int64_t n_elem,
                         const int32_t *conn, int32_t n_point_arrays, const char *const *names, const double *point_values,
                         int32_t n_cell_arrays, const char *const *cell_names, const double *cell_values);
+/* The same with point arrays of several components (no step of the reference): point_components [n_point_arrays] >= 1 (NULL: 1
+ * each, the call above), array k is [n_nodes][point_components[k]], node by node, the arrays one after the other in point_values;
+ * an array of more than one component carries NumberOfComponents. */
+int stan_host_write_vtu_components(const char *path, int64_t n_nodes, const double *xyz, const double *disp, int64_t n_elem,
+                                   const int32_t *conn, int32_t n_point_arrays, const char *const *names, const int32_t *point_components,
+                                   const double *point_values, int32_t n_cell_arrays, const char *const *cell_names,
+                                   const double *cell_values);
 
 /* ---- STAN_Database object model + STdb codec (stan_amd/host/model.h) -----------------------
  * stan_db wraps a Database (Database.cs:10-21).  Text comes back through

@@ -177,6 +177,22 @@ namespace STAN_Solver
         public double power_ms;
     }
 
+    /// stan_harmonic_report (include/stan_hip.h); filled through the IntPtr argument of stan_hip_harmonic
+    [StructLayout(LayoutKind.Sequential)]
+    public struct StanHarmonicReport
+    {
+        public int n_modes;
+        public int n_freq;
+        public long peak_dof;
+        public double peak;
+        public int peak_freq;
+        public int static_correction;
+        public double project_ms;
+        public double sweep_ms;
+        public double snap_ms;
+        public double probe_ms;
+    }
+
     internal static class StanHipNative
     {
         // "stan_hip" resolves to libstan_hip.so on Linux (.NET probes lib<name>.so; Mono: <dllmap> or the same probing)
@@ -410,6 +426,18 @@ namespace STAN_Solver
             IntPtr ctx, long N, double[] y, double[] s, double[] u, double[] u_prev, double[] M, double[] F, double dt,
             double alpha_R, double gF, long step, [Out] double[] u_next, [Out] double[] u_next_scaled, [Out] double[] v,
             [Out] double[] a, [Out] double[] energy, out long first_nonfinite);
+
+        // ---- frequency response: lambda [n_modes], phi [n_modes * N], omega [n_freq] in rad/s; u_static, zeta, probe, snaps, peak and
+        //      peak_idx may be null (peak and peak_idx together); probe [n_freq * n_probe * 2], snaps [n_snap * 2 * N]; rep ->
+        //      StanHarmonicReport or IntPtr.Zero
+        [DllImport(Lib)] internal static extern int stan_hip_harmonic(
+            IntPtr ctx, long N, int n_modes, double[] lambda, double[] phi, double[] F, double[] u_static, double alpha_R,
+            double beta_R, double[] zeta, int n_freq, double[] omega, int n_probe, int[] probe_dof, [Out] double[] probe, int n_snap,
+            int[] snap_freq, [Out] double[] snaps, [Out] double[] p, [Out] double[] peak, [Out] int[] peak_idx, IntPtr rep);
+        [DllImport(Lib)] internal static extern int stan_hip_harmonic_dev(
+            IntPtr ctx, long N, int n_modes, IntPtr d_lambda, IntPtr d_phi, IntPtr d_F, IntPtr d_u_static, double alpha_R,
+            double beta_R, double[] zeta, int n_freq, double[] omega, int n_probe, IntPtr d_probe_dof, IntPtr d_probe, int n_snap,
+            int[] snap_freq, IntPtr d_snaps, IntPtr d_p, IntPtr d_peak, IntPtr d_peak_idx, IntPtr rep);
 
         // ---- introspection / parity helpers
         [DllImport(Lib)] internal static extern int stan_hip_matrix_info(IntPtr K, out StanMatrixInfo info);

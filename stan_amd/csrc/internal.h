@@ -683,6 +683,30 @@ int stan_power_sums_device(stan_ctx *ctx, int64_t n, const double *y, const doub
 int stan_power_next_device(stan_ctx *ctx, int64_t n, const double *y, const double *s, const double *M, const double *d_sums, double *x,
                            double *xh);
 
+// ---- harmonic.hip ---------------------------------------------------------------------------
+// The kernels of the frequency response (api_harmonic.hip); the expressions: harmonic.hip's header.  Phi is
+// [k][N], the table d_tab [n_freq][stan_harmonic_width(k)] pairs (a, b) with zeros beyond k, d_r [N] or null (then r = 0).  All
+// enqueue on the context's stream and none synchronises.
+constexpr int STAN_HM_ROWS = 1024;   // rows per workgroup of the projection and of the peak reduction
+inline int64_t stan_harmonic_blocks(int64_t N) { return (N + STAN_HM_ROWS - 1) / STAN_HM_ROWS; }
+inline int stan_harmonic_width(int k) { return (k + 3) & ~3; }   // the table's pairs per frequency: k rounded up to a multiple of 4
+// d_p [k] = Phi^T F through d_partial [k][stan_harmonic_blocks(N)]
+int stan_harmonic_dots_device(stan_ctx *ctx, int64_t N, int32_t k, const double *d_phi, const double *d_F, double *d_partial, double *d_p);
+// d_r = d_us - sum_j phi_j c[j], c [k] host
+int stan_harmonic_residual_device(stan_ctx *ctx, int64_t N, int32_t k, const double *d_phi, const double *d_us, const double *c, double *d_r);
+int stan_harmonic_sweep_device(stan_ctx *ctx, int64_t N, int32_t k, int32_t n_freq, const double *d_phi, const double *d_r,
+                               const double *d_tab, double *d_peak, int32_t *d_peak_idx);
+// d_snaps [n_snap][2][N] at the table rows d_snap_freq [n_snap]
+int stan_harmonic_snap_device(stan_ctx *ctx, int64_t N, int32_t k, int32_t n_snap, const int32_t *d_snap_freq, const double *d_phi,
+                              const double *d_r, const double *d_tab, double *d_snaps);
+// d_probe [n_freq][n_probe][2]
+int stan_harmonic_probe_device(stan_ctx *ctx, int64_t N, int32_t k, int32_t n_freq, int32_t n_probe, const int32_t *d_probe_dof,
+                               const double *d_phi, const double *d_r, const double *d_tab, double *d_probe);
+// d_out[0] = the largest entry of d_peak, d_out_idx[0] = its row (the lowest on a tie), d_out_idx[1] = d_peak_idx of that row;
+// d_pval / d_pidx [stan_harmonic_blocks(N)]
+int stan_harmonic_peakmax_device(stan_ctx *ctx, int64_t N, const double *d_peak, const int32_t *d_peak_idx, double *d_pval, long long *d_pidx,
+                                 double *d_out, long long *d_out_idx);
+
 // ---- comm.cpp -------------------------------------------------------------------------------
 int stan_comm_allreduce_sum_f64(stan_ctx *ctx, double *d_buf, size_t count);
 int stan_comm_info(stan_ctx *ctx, int *version, int *count, int *rank);

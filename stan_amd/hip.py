@@ -64,6 +64,7 @@ EXPORTS = [
     "stan_hip_matrix_shifted", "stan_hip_matrix_shifted_dev", "stan_hip_transient", "stan_hip_transient_dev",
     "stan_hip_newmark_predict", "stan_hip_newmark_correct",
     "stan_hip_stable_step", "stan_hip_stable_step_dev", "stan_hip_explicit", "stan_hip_explicit_dev", "stan_hip_central_update",
+    "stan_hip_harmonic", "stan_hip_harmonic_dev",
     "stan_hip_kg_hex8_batch", "stan_hip_geometric_stiffness_hex8", "stan_hip_geometric_stiffness_hex8_dev",
     "stan_hip_geometric_stiffness_times", "stan_hip_buckling", "stan_hip_buckling_dev", "stan_hip_buckling_rotate",
     "stan_hip_mass_hex8_batch", "stan_hip_consistent_mass_hex8", "stan_hip_consistent_mass_hex8_dev",
@@ -169,6 +170,16 @@ class ExplicitReport(C.Structure):
     _fields_ = [("steps", C.c_int32), ("first_nonfinite_step", C.c_int32), ("lambda_upper", C.c_double), ("lambda_power", C.c_double),
                 ("dt_stable", C.c_double), ("product_ms", C.c_double), ("update_ms", C.c_double), ("bound_ms", C.c_double),
                 ("power_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class HarmonicReport(C.Structure):
+    """stan_harmonic_report (include/stan_hip.h)"""
+    _fields_ = [("n_modes", C.c_int32), ("n_freq", C.c_int32), ("peak_dof", C.c_int64), ("peak", C.c_double), ("peak_freq", C.c_int32),
+                ("static_correction", C.c_int32), ("project_ms", C.c_double), ("sweep_ms", C.c_double), ("snap_ms", C.c_double),
+                ("probe_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -743,6 +754,57 @@ class Context:
             _ptr(lam, C.c_double), _ptr(mk, C.c_uint8), C.c_int32(int(bool(in_place))), _ptr(X, C.c_double), _ptr(KX, C.c_double),
             _ptr(R, C.c_double), _ptr(rho2, C.c_double)))
         return X, KX, R, rho2
+
+    def harmonic(self, lam, phi, F, omega, u_static=None, alpha_R=0.0, beta_R=0.0, zeta=None, probe_dof=None, snap_freq=None,
+                 peak=True, out=None):
+        """stan_hip_harmonic: the steady-state response to F e^{i w t} at the circular frequencies omega [n_freq] from the
+        M-orthonormal modes lam [k], phi [k, N], with the static correction when u_static = K^-1 F is given.  Returns a dict: p
+        [k], probe [n_freq, n_probe, 2] or None, snaps [n_snap, 2, N] or None, peak [N] and peak_idx [N] (int32) or None, report
+        (stan_harmonic_report; written on an error too: StanHipError.report).  out: a dict of preallocated arrays under the
+        same names, used instead of fresh ones (a refused call must leave them untouched)."""
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        if phi.ndim != 2:
+            raise ValueError("harmonic: phi must be [k, N]")
+        k, N = phi.shape
+        lam, F, omega = (np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (lam, F, omega))
+        us, zt = (None if x is None else np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in (u_static, zeta))
+        if lam.shape[0] != k or F.shape[0] != N or (us is not None and us.shape[0] != N) or (zt is not None and zt.shape[0] != k):
+            raise ValueError("harmonic: lam, zeta must be [k] and F, u_static [N]")
+        pd = None if probe_dof is None else np.ascontiguousarray(probe_dof, dtype=np.int32).reshape(-1)
+        sf = None if snap_freq is None else np.ascontiguousarray(snap_freq, dtype=np.int32).reshape(-1)
+        npr, nsn, nf = (0 if pd is None else pd.shape[0]), (0 if sf is None else sf.shape[0]), omega.shape[0]
+        o = dict(out or {})
+        pr = o.get("probe", np.zeros((nf, npr, 2)) if npr else None)
+        sn = o.get("snaps", np.zeros((nsn, 2, N)) if nsn else None)
+        p = o.get("p", None)
+        p = np.zeros(k) if p is None else p
+        pk = o.get("peak", np.zeros(N) if peak else None)
+        pi = o.get("peak_idx", np.zeros(N, dtype=np.int32) if peak else None)
+        rep = HarmonicReport()
+        rc = self.lib.stan_hip_harmonic(
+            self.h, C.c_int64(N), C.c_int32(k), _ptr(lam, C.c_double), _ptr(phi, C.c_double), _ptr(F, C.c_double), _ptr(us, C.c_double),
+            C.c_double(alpha_R), C.c_double(beta_R), _ptr(zt, C.c_double), C.c_int32(nf), _ptr(omega, C.c_double), C.c_int32(npr),
+            _ptr(pd, C.c_int32), _ptr(pr, C.c_double), C.c_int32(nsn), _ptr(sf, C.c_int32), _ptr(sn, C.c_double), _ptr(p, C.c_double),
+            _ptr(pk, C.c_double), _ptr(pi, C.c_int32), C.byref(rep))
+        if rc != 0:
+            e = StanHipError(rc, self.lib.stan_hip_last_error(self.h).decode())
+            e.report = rep.as_dict()
+            raise e
+        return dict(p=p, probe=pr, snaps=sn, peak=pk, peak_idx=pi, report=rep.as_dict())
+
+    def harmonic_dev(self, N, n_modes, d_lambda, d_phi, d_F, omega, d_p, d_u_static=None, alpha_R=0.0, beta_R=0.0, zeta=None, n_probe=0,
+                     d_probe_dof=None, d_probe=None, snap_freq=None, d_snaps=None, d_peak=None, d_peak_idx=None):
+        """Every d_* is a device pointer (int) or None; omega, zeta and snap_freq stay on the host.  Returns the report dict."""
+        omega = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
+        zt = None if zeta is None else np.ascontiguousarray(zeta, dtype=np.float64).reshape(-1)
+        sf = None if snap_freq is None else np.ascontiguousarray(snap_freq, dtype=np.int32).reshape(-1)
+        rep = HarmonicReport()
+        self._chk(self.lib.stan_hip_harmonic_dev(
+            self.h, C.c_int64(N), C.c_int32(int(n_modes)), _opt(d_lambda), _opt(d_phi), _opt(d_F), _opt(d_u_static), C.c_double(alpha_R),
+            C.c_double(beta_R), _ptr(zt, C.c_double), C.c_int32(omega.shape[0]), _ptr(omega, C.c_double), C.c_int32(int(n_probe)),
+            _opt(d_probe_dof, C.c_int32), _opt(d_probe), C.c_int32(0 if sf is None else sf.shape[0]), _ptr(sf, C.c_int32), _opt(d_snaps),
+            _opt(d_p), _opt(d_peak), _opt(d_peak_idx, C.c_int32), C.byref(rep)))
+        return rep.as_dict()
 
     def newmark_predict(self, u, v, a, F, M, coef, gF, Kw=None, want_w=True):
         """stan_hip_newmark_predict: (w or None, b) of one Newmark step from the state u, v, a [N]; coef as newmark_coef."""

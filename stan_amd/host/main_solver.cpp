@@ -10,7 +10,7 @@
 //
 // In the order of a run: CliOptions (all that argv sets: ParseArgs, then Refusal before anything is read -- a run that gets further
 // overwrites its input), Prepared (what every analysis starts from: ReadModel, BuildTables, Assemble, BuildLoads), RunModes /
-// RunTransient / RunBuckling / RunStatics, main().  The extra switches (never stored in the STdb) are described where they are carried out.
+// RunTransient / RunExplicit / RunHarmonic / RunBuckling / RunStatics, main().  The extra switches (never stored in the STdb) are described where they are carried out.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -53,6 +53,13 @@ static const char *const kExplicitUsage =
     "         --dt auto     dt = S * 2 / sqrt(lambda_upper), lambda_upper the Gershgorin row bound of M^-1 K: stable by proof\n"
     "         --dt-scale S  default 0.9: the usual convention of explicit codes, not a measured value\n";
 
+static const char *const kHarmonicUsage =
+    "       stan_solver --harmonic F0,F1,NF --modes K [--mass consistent] [--modes-tol T] [--rayleigh A,B] [--modal-damping Z] "
+    "[--probe-node ID] [--json] [--vtu PREFIX [--vtu-every E]] <model.STdb>\n"
+    "         --harmonic F0,F1,NF  the steady-state response to the file's loads times e^{i w t} at NF frequencies, linearly spaced\n"
+    "                              from F0 to F1 in Hz (NF = 1: F0), by superposition of the K lowest modes with a static correction\n"
+    "         --modal-damping Z    the damping ratio of every mode, on top of --rayleigh A,B\n";
+
 // ---- options ------------------------------------------------------------------------------------------------------------------
 // --device N, --gpus N (devices 0..N-1) or --devices a,b,c (several GPUs from this ONE process: stan_hip_init_multi, rows of K
 // sharded, RCCL inside the CG), --mixed, --fixed48, --no-merit-stop, --packed, --placement-tries N (default 16; 1 = plain
@@ -60,7 +67,7 @@ static const char *const kExplicitUsage =
 // (store the results in the Node / Element objects before the export, as the reference does, instead of encoding them from the
 // flat arrays: same bytes), --json (one JSON line with sizes, iterations, device and host phase times and the SpMV's HBM rate);
 // --vtu, --reactions: RunStatics; --modes, --modes-shift, --mass: RunModes; --buckling: RunBuckling; --transient: RunTransient;
-// --explicit (with --dt auto, --dt-scale): RunExplicit; --help: the usage lines.
+// --explicit (with --dt auto, --dt-scale): RunExplicit; --harmonic (with --modal-damping): RunHarmonic; --help: the usage lines.
 struct CliOptions {
     std::string path;
     int device = 0, precision = STAN_PREC_FP64, placement_tries = 16;
@@ -81,6 +88,8 @@ struct CliOptions {
     bool have_probe = false;
     bool explicit_run = false, explicit_arg = false, dt_auto = false, help = false;   // --explicit; --dt auto / --dt-scale seen
     double dt_scale = 0.9;
+    bool harmonic = false, harmonic_bad = false, have_modal_damping = false, time_arg = false;   // --harmonic; an option of the time integrators seen
+    double f0 = 0, f1 = 0, n_freq = 0, modal_damping = -1;                                        // (n_freq as given: checked in Refusal)
     bool several_devices() const { return devices.size() > 1; }
 };
 
@@ -145,25 +154,32 @@ static CliOptions ParseArgs(int argc, char **argv) {
         else if (flag("--transient")) o.transient = true;
         else if (flag("--help")) o.help = true;
         else if (flag("--explicit")) o.explicit_run = true;
-        else if (value("--dt-scale")) { o.transient_arg = o.explicit_arg = true; o.dt_scale = atof(argv[++i]); }
-        else if (value("--dt") && !strcmp(argv[i + 1], "auto")) { o.transient_arg = o.explicit_arg = o.dt_auto = true; i++; }
-        else if (value("--dt")) { o.transient_arg = true; run.dt = atof(argv[++i]); }
-        else if (value("--steps")) { o.transient_arg = true; run.n_steps = atoi(argv[++i]); }
+        else if (value("--harmonic")) {
+            o.harmonic = true;
+            if (NumberList(argv[++i], &list) && list.size() == 3) { o.f0 = list[0]; o.f1 = list[1]; o.n_freq = list[2]; }
+            else o.harmonic_bad = true;
+        }
+        else if (value("--modal-damping")) { o.have_modal_damping = true; o.modal_damping = atof(argv[++i]); }
+        else if (value("--dt-scale")) { o.transient_arg = o.explicit_arg = o.time_arg = true; o.dt_scale = atof(argv[++i]); }
+        else if (value("--dt") && !strcmp(argv[i + 1], "auto")) { o.transient_arg = o.explicit_arg = o.dt_auto = o.time_arg = true; i++; }
+        else if (value("--dt")) { o.transient_arg = o.time_arg = true; run.dt = atof(argv[++i]); }
+        else if (value("--steps")) { o.transient_arg = o.time_arg = true; run.n_steps = atoi(argv[++i]); }
         else if (value("--buckling")) { o.buckling_arg = true; o.buckling = atoi(argv[++i]); }
         else if (value("--buckling-tol")) { o.buckling_arg = true; o.buckling_tol = atof(argv[++i]); }
         else if (value("--solve-eps")) { o.have_solve_eps = true; o.solve_eps = run.solve_eps = atof(argv[++i]); }
         else if (value("--probe-node")) { o.transient_arg = o.have_probe = true; o.probe_node = atoi(argv[++i]); }
         else if (value("--vtu-every")) { o.transient_arg = true; o.vtu_every = atoi(argv[++i]); }
-        else if (value("--newmark")) { if (numbers(2)) { run.beta_N = list[0]; run.gamma = list[1]; } }
+        else if (value("--newmark")) { o.time_arg = true; if (numbers(2)) { run.beta_N = list[0]; run.gamma = list[1]; } }
         else if (value("--rayleigh")) { if (numbers(2)) { run.alpha_R = list[0]; run.beta_R = list[1]; } }
         else if (value("--load-curve")) {
+            o.time_arg = true;
             if (numbers(0))
                 for (size_t k = 0; k < list.size(); k += 2) { run.curve_t.push_back(list[k]); run.curve_g.push_back(list[k + 1]); }
         }
         else o.path = argv[i];
     }
     if (o.vtu) SolverFunctions::ParseScalarNames(o.vtu_results, &o.vtu_sel, &o.vtu_results_why);
-    if (o.have_solve_eps && !o.buckling) o.transient_arg = true;   // --solve-eps belongs to --buckling, else to --transient
+    if (o.have_solve_eps && !o.buckling) o.transient_arg = o.time_arg = true;   // --solve-eps belongs to --buckling, else to --transient
     run.snap_every = o.vtu ? o.vtu_every : 0;
     return o;
 }
@@ -180,6 +196,25 @@ static std::string OneDevice(const char *what, const char *reason, const char *o
 static std::string Refusal(const CliOptions &o) {
     const SolverFunctions::TransientRun &run = o.run;
     const bool several = o.several_devices();
+    if (o.have_modal_damping && !o.harmonic) return "--modal-damping Z belongs to --harmonic";
+    if (o.harmonic) {   // first: each of these has a text of its own, whatever else the line holds
+        if (o.harmonic_bad) return "--harmonic F0,F1,NF takes three numbers: the first and the last frequency in Hz and how many";
+        if (!(o.n_freq >= 1) || o.n_freq != std::floor(o.n_freq) || !(o.f0 >= 0) || !(o.f1 >= o.f0) || !std::isfinite(o.f1))
+            return "--harmonic F0,F1,NF needs NF >= 1, F0 >= 0 and F1 >= F0";
+        if (o.n_freq > 65536) return "--harmonic F0,F1,NF takes at most 65536 frequencies";
+        if (o.transient || o.explicit_run || o.buckling_arg) return "--harmonic, --transient, --explicit and --buckling are four analyses: one per run";
+        if (o.modes == 0 && o.modes_tol == 0) return "--harmonic needs --modes K: the response is the superposition of the K lowest modes";
+        if (o.modes_shift != 0)
+            return "--harmonic needs a supported model: --modes-shift is for a model without supports, which has no static solution to correct with";
+        if (o.bad_list) return "--rayleigh A,B takes two numbers";
+        if (o.time_arg) return "--dt, --steps, --newmark, --load-curve and --solve-eps belong to the time integrators: a frequency response has no steps";
+        if (!(run.alpha_R >= 0) || !(run.beta_R >= 0) || !std::isfinite(run.alpha_R) || !std::isfinite(run.beta_R))
+            return "--rayleigh A,B needs A >= 0 and B >= 0";
+        if (o.have_modal_damping && (!(o.modal_damping >= 0) || !std::isfinite(o.modal_damping))) return "--modal-damping Z needs Z >= 0";
+        if (o.vtu_every < 1) return "--vtu-every E needs E >= 1";
+        if (several)
+            return OneDevice("--harmonic works", "the modes, the static solution and the sweep over them live on a single-rank context");
+    }
     if (o.vtu && several)
         return OneDevice("--vtu works", "the result scalars average over all elements at a node, and a multi-device handle holds them in chunks",
                          ", or export in a second run");
@@ -223,7 +258,7 @@ static std::string Refusal(const CliOptions &o) {
                                                  "on a single-rank context");
         return "";
     }
-    if (!o.transient && o.transient_arg)
+    if (!o.transient && !o.harmonic && o.transient_arg)
         return "--dt, --steps, --newmark, --rayleigh, --load-curve, --probe-node, --solve-eps and --vtu-every belong to --transient";
     if (o.transient) {
         if (o.modes) return "--transient and --modes are two analyses: one per run";
@@ -248,7 +283,7 @@ static std::string Refusal(const CliOptions &o) {
 // ... and what is wrong with the file for the analysis that was asked for: --modes and --transient need the densities, all three
 // the static analysis they replace or start from; the stress state of --buckling is sigma = D B u, a thermal part is out of scope
 static std::string FileRefusal(const CliOptions &o, const Database &DB) {
-    const std::string analysis = o.modes ? "--modes" : o.transient ? "--transient" : o.explicit_run ? "--explicit" : o.buckling ? "--buckling" : "";
+    const std::string analysis = o.harmonic ? "--harmonic" : o.modes ? "--modes" : o.transient ? "--transient" : o.explicit_run ? "--explicit" : o.buckling ? "--buckling" : "";
     if (analysis.empty()) return "";
     if (!o.buckling && !HasDensity(DB))
         return analysis + " needs a \"Density\" boundary condition (material IDs, component 0 = rho): the file has none";
@@ -614,6 +649,125 @@ static int RunExplicit(const SolverFunctions &Functions, const CliOptions &o, Pr
     return 0;
 }
 
+// --harmonic F0,F1,NF --modes K [--mass consistent] [--modes-tol T] [--rayleigh A,B] [--modal-damping Z] [--probe-node ID] (DESIGN.md
+// section 3.15) finds the steady-state response to the file's loads times e^{i w t} at NF frequencies from F0 to F1 Hz and never writes
+// the STdb: the modes exactly as --modes finds them (on the assembled K, before any solve has scaled it), the static solve of the
+// file's loads for the static correction, then stan_hip_harmonic_dev on what stayed in device memory (SolverFunctions::HarmonicResident).  A block "Frequency response:", with --json a "harmonic" object,
+// with --vtu PREFIX PREFIX_peak.vtu ("Peak Amplitude", "Peak Frequency") and PREFIX_freq_NNNN.vtu ("Displacement Re" / "Im") for every
+// E-th frequency.  One device only; a file without a "Density" entry is refused.
+static int RunHarmonic(SolverFunctions &Functions, const CliOptions &o, Prepared &m) {
+    for (double x : m.dl.disp0)
+        if (x != 0.0) return refuse("--harmonic takes homogeneous supports only: the file prescribes a non-zero \"Displacement\"");
+    SolverFunctions::HarmonicRun run;
+    run.alpha_R = o.run.alpha_R; run.beta_R = o.run.beta_R; run.zeta = o.have_modal_damping ? o.modal_damping : -1.0;
+    run.snap_every = o.vtu ? o.vtu_every : 0;
+    int probe_dir[3] = {0, 0, 0};
+    if (o.have_probe && !ProbeDofs(o, m, &run.probe_dof, probe_dir))
+        return refuse("--probe-node " + std::to_string(o.probe_node) + ": the file has no such node");
+    const double two_pi = 6.283185307179586476925;
+    const int nf = (int)o.n_freq;
+    std::vector<double> hz((size_t)nf);
+    for (int f = 0; f < nf; f++) hz[(size_t)f] = nf == 1 ? o.f0 : o.f0 + (o.f1 - o.f0) * ((double)f / (double)(nf - 1));
+    for (double x : hz) run.omega.push_back(two_pi * x);
+    std::string err;
+    MassDensity md;
+    if (BuildDensity(m.DB, m.K.flat, &md, &err)) return fail("boundary conditions", err);
+
+    std::vector<double> lambda, p, probe, snaps, peak;
+    std::vector<int32_t> peak_idx;
+    stan_mass_sums msum{};
+    stan_modes_report mrep{};
+    stan_harmonic_report rep{};
+    const bool consistent = o.mass_kind == "consistent";
+    Functions.HarmonicResident(m.K, m.nDOF_reduction, md, consistent ? SolverFunctions::MASS_CONSISTENT : SolverFunctions::MASS_LUMPED,
+                               o.modes, o.modes_tol, m.F_solve(), m.DB.AnalysisLib, run, &lambda, &p, &probe, &snaps, &peak, &peak_idx, &msum,
+                               &mrep, &rep);
+    printf("   CG iterations: %d, scaled relative residual %.3e\n", Functions.last_iterations, Functions.last_rel_residual);
+
+    const size_t k = (size_t)o.modes, np = run.probe_dof.size(), N = (size_t)m.minfo.n_reduced;
+    std::vector<double> mode_hz(k), ratio(k);   // the damping ratio of mode j: c_j / (2 sqrt(lambda_j))
+    for (size_t j = 0; j < k; j++) {
+        const double w = std::sqrt(lambda[j]);
+        mode_hz[j] = w / two_pi;
+        ratio[j] = (run.alpha_R + run.beta_R * lambda[j]) / (2.0 * w) + (run.zeta >= 0 ? run.zeta : 0.0);
+    }
+    // the largest amplitude: its reduced DOF as node ID and direction
+    int peak_node = 0, peak_dir = 0;
+    for (int64_t n = 0; n < m.n_nodes && rep.peak_dof >= 0; n++)
+        for (int c = 0; c < 3; c++) {
+            const int32_t d = m.K.flat.node_dof[(size_t)(3 * n + c)];
+            if (m.nDOF_reduction[(size_t)d] != -1 && d - m.nDOF_reduction[(size_t)d] == rep.peak_dof) {
+                peak_node = m.DB.NodeLib.Items()[(size_t)n].first;
+                peak_dir = c;
+            }
+        }
+    const double peak_hz = rep.peak_freq >= 0 ? hz[(size_t)rep.peak_freq] : 0.0;
+    const double deg = 360.0 / two_pi;
+    printf("   Total mass: %.6e   volume: %.6e\n", msum.total_mass, msum.volume);
+    printf("   Frequency response: (%d frequencies from %.6e to %.6e Hz, %d modes%s, static correction)\n", nf, hz.front(), hz.back(),
+           o.modes, consistent ? ", consistent mass" : "");
+    printf("     modes: block %d, %d outer steps, %lld CG iterations, %s\n", mrep.block, mrep.outer, (long long)mrep.cg_iterations,
+           mrep.converged ? "converged" : "NOT converged");
+    printf("     damping: Rayleigh alpha %g beta %g, modal ratio %g\n", run.alpha_R, run.beta_R, run.zeta >= 0 ? run.zeta : 0.0);
+    printf("     mode    frequency [Hz]      modal load p   damping ratio\n");
+    for (size_t j = 0; j < k; j++) printf("     %4d  %16.8e  %16.8e  %14.6e\n", (int)j + 1, mode_hz[j], p[j], ratio[j]);
+    printf("     Largest amplitude: %.8e at node %d, direction %c, at %.8e Hz\n", rep.peak, peak_node, "XYZ"[peak_dir], peak_hz);
+    if (np) {
+        printf("     Probe node %d:\n      index    frequency [Hz]", o.probe_node);
+        for (size_t q = 0; q < np; q++) printf("              |u%c|    phase(u%c) [deg]", "xyz"[probe_dir[q]], "xyz"[probe_dir[q]]);
+        printf("\n");
+        for (int f = 0; f < nf; f++) {
+            printf("     %6d  %16.8e", f, hz[(size_t)f]);
+            for (size_t q = 0; q < np; q++) {
+                const double re = probe[((size_t)f * np + q) * 2], im = probe[((size_t)f * np + q) * 2 + 1];
+                printf("  %16.8e  %16.8e", std::hypot(re, im), std::atan2(im, re) * deg);
+            }
+            printf("\n");
+        }
+    }
+    if (o.vtu) {
+        Functions.Export_Peak_Vtu(m.K, m.nDOF_reduction, peak.data(), peak_idx.data(), hz, o.vtu_prefix);
+        int last = 0;
+        for (int f = 0; f < nf; f += o.vtu_every) {
+            Functions.Export_Freq_Vtu(m.K, m.nDOF_reduction, &snaps[(size_t)(f / o.vtu_every) * 2 * N], N, o.vtu_prefix, f);
+            last = f;
+        }
+        printf("   VTU export: %s_peak.vtu, %s_freq_0000.vtu ... %s_freq_%04d.vtu\n", o.vtu_prefix.c_str(), o.vtu_prefix.c_str(),
+               o.vtu_prefix.c_str(), last);
+    }
+    ClosingBanner(m);
+    if (o.json) {
+        JsonHead(m, "harmonic");
+        printf("\"n_modes\": %d, \"n_freq\": %d, \"f0_hz\": %.17g, \"f1_hz\": %.17g, \"alpha_R\": %.17g, \"beta_R\": %.17g, \"modal_damping\": %.17g, "
+               "\"static_cg_iterations\": %d, \"modes_converged\": %d, \"total_mass\": %.17g, \"peak\": %.17g, \"peak_node\": %d, "
+               "\"peak_direction\": %d, \"peak_frequency_hz\": %.17g, \"peak_frequency_index\": %d",
+               o.modes, nf, o.f0, o.f1, run.alpha_R, run.beta_R, run.zeta >= 0 ? run.zeta : 0.0, Functions.last_iterations, mrep.converged,
+               msum.total_mass, rep.peak, peak_node, peak_dir, peak_hz, rep.peak_freq);
+        if (consistent) printf(", \"mass\": \"consistent\"");
+        JsonArray("lambda", lambda.data(), k);
+        JsonArray("mode_frequency_hz", mode_hz.data(), k);
+        JsonArray("modal_load", p.data(), k);
+        JsonArray("damping_ratio", ratio.data(), k);
+        JsonArray("frequency_hz", hz.data(), (size_t)nf);
+        if (np) {
+            printf(", \"probe_node\": %d, \"probe_direction\": [", o.probe_node);
+            for (size_t q = 0; q < np; q++) printf("%s%d", q ? ", " : "", probe_dir[q]);
+            printf("], \"probe_re_im\": [");   // [n_freq][n_probe][2]
+            for (int f = 0; f < nf; f++) {
+                printf("%s[", f ? ", " : "");
+                for (size_t q = 0; q < np; q++) {
+                    printf("%s", q ? ", " : "");
+                    JsonNumbers(&probe[((size_t)f * np + q) * 2], 2);
+                }
+                printf("]");
+            }
+            printf("]");
+        }
+        printf("}}\n");
+    }
+    return 0;
+}
+
 // --buckling K [--buckling-tol T] [--solve-eps E] runs the static solve under the model's own loads, builds
 // G = K_g(U) (stan_hip_geometric_stiffness_hex8) and finds the K lowest positive load factors (stan_hip_buckling): a block
 // "Buckling load factors:", with --json a "buckling" object, with --vtu PREFIX one PREFIX_buckle_NNN.vtu per factor; the STdb is
@@ -826,6 +980,7 @@ int main(int argc, char **argv) {
     if (o.help) {
         fputs(kUsage, stdout);
         fputs(kExplicitUsage, stdout);
+        fputs(kHarmonicUsage, stdout);
         return 0;
     }
     if (o.path.empty()) {  // Path = path[0] -> IndexOutOfRangeException in the reference
@@ -851,6 +1006,10 @@ int main(int argc, char **argv) {
         printf("\n%s\n        LINEAR STATIC ANALYSIS \n%s\n", kSeparator, kSeparator);
         if (int rc = BuildTables(o, &m)) return rc;
         Assemble(Functions, &m);
+        if (o.harmonic) {   // (--modes K belongs to it)
+            if (int rc = BuildLoads(Functions, &m)) return rc;
+            return RunHarmonic(Functions, o, m);
+        }
         if (o.modes) return RunModes(Functions, o, m);   // before the loads are built
         if (int rc = BuildLoads(Functions, &m)) return rc;
         if (o.transient) return RunTransient(Functions, o, m);

@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <dlfcn.h>
 #include <thread>
 
 namespace stan {
@@ -330,6 +331,154 @@ void SolverFunctions::Explicit(SparseMatrixHandle &K, const std::vector<int32_t>
                           np ? probe_u->data() : nullptr, run->snap_every, n_snap ? snaps->data() : nullptr, energy_every, energy->data(),
                           u.data(), v.data(), a.data(), run->n_power, rep))
         throw std::runtime_error(stan_hip_last_error(K.ctx));
+}
+
+namespace {
+
+// Device memory of this process for the run that keeps its arrays resident (HarmonicResident).  The HIP runtime is in the process
+// already, as libstan_hip.so's own dependency: its four entries are looked up by name, so that this side needs neither HIP's
+// headers nor a link line of its own.  Copies are the synchronous ones: an array is ready on every stream when upload() returns.
+struct DeviceRuntime {
+    int (*set_device)(int) = nullptr;
+    int (*malloc_)(void **, size_t) = nullptr;
+    int (*free_)(void *) = nullptr;
+    int (*memcpy_)(void *, const void *, size_t, int) = nullptr;   // kind 1: host to device, 2: device to host
+    DeviceRuntime() {
+        set_device = (int (*)(int))dlsym(RTLD_DEFAULT, "hipSetDevice");
+        malloc_ = (int (*)(void **, size_t))dlsym(RTLD_DEFAULT, "hipMalloc");
+        free_ = (int (*)(void *))dlsym(RTLD_DEFAULT, "hipFree");
+        memcpy_ = (int (*)(void *, const void *, size_t, int))dlsym(RTLD_DEFAULT, "hipMemcpy");
+        if (!set_device || !malloc_ || !free_ || !memcpy_) throw std::runtime_error("the HIP runtime's entries are not in this process");
+    }
+};
+
+template <typename T>
+struct DeviceArray {   // n entries on the device, given back on every way out
+    const DeviceRuntime &rt;
+    T *p = nullptr;
+    size_t n;
+    DeviceArray(const DeviceRuntime &r, size_t count) : rt(r), n(count) {
+        if (rt.malloc_((void **)&p, (n ? n : 1) * sizeof(T))) throw std::runtime_error("hipMalloc of " + std::to_string(n * sizeof(T)) + " bytes failed");
+    }
+    DeviceArray(const DeviceRuntime &r, const std::vector<T> &host) : DeviceArray(r, host.size()) {
+        if (n && rt.memcpy_(p, host.data(), n * sizeof(T), 1)) throw std::runtime_error("copy to the device failed");
+    }
+    DeviceArray(const DeviceArray &) = delete; DeviceArray &operator=(const DeviceArray &) = delete;
+    ~DeviceArray() { rt.free_(p); }
+    void fetch(std::vector<T> *host) const {
+        host->resize(n);
+        if (n && rt.memcpy_(host->data(), p, n * sizeof(T), 2)) throw std::runtime_error("copy from the device failed");
+    }
+};
+
+}  // namespace
+
+void SolverFunctions::HarmonicResident(SparseMatrixHandle &K, const std::vector<int32_t> &red, const MassDensity &md, MassKind mass,
+                                       int n_modes, double tol, const std::vector<double> &F, const Analysis &A, const HarmonicRun &run,
+                                       std::vector<double> *lambda, std::vector<double> *p, std::vector<double> *probe,
+                                       std::vector<double> *snaps, std::vector<double> *peak, std::vector<int32_t> *peak_idx,
+                                       stan_mass_sums *sums, stan_modes_report *mrep, stan_harmonic_report *rep) const {
+    std::vector<double> M;
+    LumpedMass(K, red, md, &M, sums);   // as Modes(): under the consistent mass too
+    const size_t N = M.size(), k = n_modes > 0 ? (size_t)n_modes : 1, nf = run.omega.size(), np = run.probe_dof.size();
+    const DeviceRuntime rt;
+    if (rt.set_device(opt_.device)) throw std::runtime_error("hipSetDevice failed");
+    // the modes, exactly as Modes() asks for them, into device memory
+    DeviceArray<double> d_lambda(rt, k), d_phi(rt, k * N), d_rho(rt, k);
+    if (mass == MASS_CONSISTENT) {
+        const MeshView v(K.flat);
+        stan_matrix *made = nullptr;
+        if (stan_hip_consistent_mass_hex8(K.ctx, K.K, v.n_nodes, v.xyz, md.mat_rho.data(), v.node_dof, v.n_elem, v.conn, v.elem_mat,
+                                          v.elem_type, v.n_mat, v.mat_E_nu, (int64_t)red.size(), red.data(), &made))
+            throw std::runtime_error(stan_hip_last_error(K.ctx));
+        const OwnedMatrix Mc(made);
+        stan_buckling_report pencil{};
+        if (stan_hip_modes_pencil_dev(K.ctx, K.K, Mc.get(), n_modes, tol, 0, 0.0, 0, d_lambda.p, d_phi.p, d_rho.p, &pencil))
+            throw std::runtime_error(stan_hip_last_error(K.ctx));
+        *mrep = shared_fields(pencil);
+    } else {
+        const DeviceArray<double> d_M(rt, M);
+        if (stan_hip_modes_dev(K.ctx, K.K, d_M.p, n_modes, tol, 0, 0.0, 0, d_lambda.p, d_phi.p, d_rho.p, mrep))
+            throw std::runtime_error(stan_hip_last_error(K.ctx));
+    }
+    d_lambda.fetch(lambda);
+    // the static solution, with LinearSolver_CG's lines
+    const auto t0 = clk::now();
+    printf("   Solving linear system...   ");
+    fflush(stdout);
+    const DeviceArray<double> d_F(rt, F);
+    DeviceArray<double> d_U(rt, N);
+    int32_t type = 0, its = 0;
+    double rel = 0;
+    if (stan_hip_cg_solve_dev(K.ctx, K.K, d_F.p, A.LinSolverTolerance, A.LinSolverIterMax, opt_.precision, d_U.p, &type, &its, &rel))
+        throw std::runtime_error(stan_hip_last_error(K.ctx));
+    SolverFunctions *self = const_cast<SolverFunctions *>(this);
+    self->last_termination_type = type; self->last_iterations = its; self->last_rel_residual = rel;
+    self->last_cg_s = secs(t0);
+    printf(type == 1 || type == 7 ? "  NORMAL " : "  ERROR ");
+    printf(" (type %d) in %.2fs\n", type, last_cg_s);
+    // the response on what stayed in device memory
+    std::vector<int32_t> snap_freq;
+    for (size_t f = 0; run.snap_every > 0 && f < nf; f += (size_t)run.snap_every) snap_freq.push_back((int32_t)f);
+    const std::vector<double> zeta(k, run.zeta);
+    const DeviceArray<int32_t> d_probe_dof(rt, run.probe_dof);
+    DeviceArray<double> d_p(rt, k), d_probe(rt, nf * np * 2), d_snaps(rt, snap_freq.size() * 2 * N), d_peak(rt, N);
+    DeviceArray<int32_t> d_peak_idx(rt, N);
+    if (stan_hip_harmonic_dev(K.ctx, (int64_t)N, (int32_t)k, d_lambda.p, d_phi.p, d_F.p, d_U.p, run.alpha_R, run.beta_R,
+                              run.zeta >= 0 ? zeta.data() : nullptr, (int32_t)nf, run.omega.data(), (int32_t)np,
+                              np ? d_probe_dof.p : nullptr, np ? d_probe.p : nullptr, (int32_t)snap_freq.size(),
+                              snap_freq.empty() ? nullptr : snap_freq.data(), snap_freq.empty() ? nullptr : d_snaps.p, d_p.p, d_peak.p,
+                              d_peak_idx.p, rep))
+        throw std::runtime_error(stan_hip_last_error(K.ctx));
+    d_p.fetch(p); d_probe.fetch(probe); d_snaps.fetch(snaps); d_peak.fetch(peak); d_peak_idx.fetch(peak_idx);
+}
+
+// a reduced vector [N] as [n_nodes][3] in NodeLib order (0 at the fixed DOFs), appended to *point
+static void AppendNodal(const SolverFunctions &fn, SparseMatrixHandle &K, const double *reduced, const std::vector<int32_t> &red,
+                        std::vector<double> *point) {
+    const std::vector<double> nodal = fn.Nodal_Vector(K, reduced, red);
+    point->insert(point->end(), nodal.begin(), nodal.end());
+}
+
+void SolverFunctions::Export_Peak_Vtu(SparseMatrixHandle &K, const std::vector<int32_t> &red, const double *peak, const int32_t *peak_idx,
+                                      const std::vector<double> &hz, const std::string &prefix) const {
+    const MeshView v(K.flat);
+    static const char *const names[2] = {"Peak Amplitude", "Peak Frequency"};
+    static const int32_t comps[2] = {3, 1};
+    std::vector<double> point;
+    AppendNodal(*this, K, peak, red, &point);
+    // the frequency at which the node's largest component peaks (a node without a free DOF: 0)
+    const std::vector<int32_t> &node_dof = K.flat.node_dof;
+    for (int64_t n = 0; n < v.n_nodes; n++) {
+        double best = -1.0, at = 0.0;
+        for (int c = 0; c < 3; c++) {
+            const size_t d = (size_t)node_dof[(size_t)(3 * n + c)];
+            if (red[d] == -1) continue;
+            const size_t r = d - (size_t)red[d];
+            if (peak[r] > best) { best = peak[r]; at = hz[(size_t)peak_idx[r]]; }
+        }
+        point.push_back(at);
+    }
+    const std::string path = prefix + "_peak.vtu";
+    if (stan_host_write_vtu_components(path.c_str(), v.n_nodes, v.xyz, nullptr, v.n_elem, v.conn, 2, names, comps, point.data(), 0, nullptr,
+                                       nullptr))
+        throw std::runtime_error("cannot write " + path);
+}
+
+void SolverFunctions::Export_Freq_Vtu(SparseMatrixHandle &K, const std::vector<int32_t> &red, const double *re_im, size_t N,
+                                      const std::string &prefix, int index) const {
+    const MeshView v(K.flat);
+    static const char *const names[2] = {"Displacement Re", "Displacement Im"};
+    static const int32_t comps[2] = {3, 3};
+    std::vector<double> point;
+    AppendNodal(*this, K, re_im, red, &point);
+    AppendNodal(*this, K, re_im + N, red, &point);
+    char num[16];
+    snprintf(num, sizeof num, "%04d", index);
+    const std::string path = prefix + "_freq_" + num + ".vtu";
+    if (stan_host_write_vtu_components(path.c_str(), v.n_nodes, v.xyz, nullptr, v.n_elem, v.conn, 2, names, comps, point.data(), 0, nullptr,
+                                       nullptr))
+        throw std::runtime_error("cannot write " + path);
 }
 
 void SolverFunctions::Export_Step_Vtu(SparseMatrixHandle &K, const std::vector<int32_t> &red, const double *uva, size_t N,

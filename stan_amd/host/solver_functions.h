@@ -164,6 +164,31 @@ class SolverFunctions {
     void Explicit(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const MassDensity &md, const std::vector<double> &F,
                   ExplicitRun *run, std::vector<double> *probe_u, std::vector<double> *snaps, std::vector<double> *energy,
                   stan_mass_sums *sums, stan_explicit_report *rep) const;
+    // Frequency response (no step of the reference): the steady-state response of M a + C v + K u = F e^{i w t}
+    // at run.omega (rad/s) from the n_modes lowest modes, with the static correction of K^-1 F.  The modes are asked for exactly as
+    // Modes() asks (stan_hip_modes_dev, or stan_hip_modes_pencil_dev on the consistent mass: the host entries' bits), the static solve
+    // is stan_hip_cg_solve_dev with LinearSolver_CG's console lines and report fields, and stan_hip_harmonic_dev runs on what stayed in
+    // device memory: Phi, F and the static solution never come to the host.  zeta < 0: no modal damping.  lambda, p [n_modes]; probe
+    // [n_freq][n_probe][2]; snaps [n_snap][2][N] at the frequency indices 0, snap_every, ... (snap_every > 0); peak / peak_idx [N];
+    // *sums, *mrep and *rep always filled.  One device only.
+    struct HarmonicRun {
+        double alpha_R = 0, beta_R = 0, zeta = -1;
+        int snap_every = 0;
+        std::vector<double> omega;
+        std::vector<int32_t> probe_dof;
+    };
+    void HarmonicResident(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const MassDensity &md, MassKind mass,
+                          int n_modes, double tol, const std::vector<double> &F, const Analysis &AnalysisLib, const HarmonicRun &run,
+                          std::vector<double> *lambda, std::vector<double> *p, std::vector<double> *probe, std::vector<double> *snaps,
+                          std::vector<double> *peak, std::vector<int32_t> *peak_idx, stan_mass_sums *sums, stan_modes_report *mrep,
+                          stan_harmonic_report *rep) const;
+    // <prefix>_peak.vtu: peak / peak_idx [N] on the free DOFs as the point arrays "Peak Amplitude" (3 components) and "Peak Frequency"
+    // (the frequency in Hz at which the node's largest component peaks); <prefix>_freq_NNNN.vtu: re, im [N] as "Displacement Re" and
+    // "Displacement Im" (3 components each), through the writer of vtu.cpp
+    void Export_Peak_Vtu(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const double *peak, const int32_t *peak_idx,
+                         const std::vector<double> &hz, const std::string &prefix) const;
+    void Export_Freq_Vtu(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const double *re_im, size_t N,
+                         const std::string &prefix, int index) const;
     // <prefix>_step_NNNN.vtu for one snapshot: u, v, a [N] on the free DOFs as the point arrays "Displacement X" / "Y" / "Z",
     // "Velocity ..." and "Acceleration ...", through the writer of vtu.cpp
     void Export_Step_Vtu(SparseMatrixHandle &K, const std::vector<int32_t> &nDOF_reduction, const double *uva, size_t N,

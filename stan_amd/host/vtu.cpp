@@ -62,6 +62,17 @@ const char *stan_host_scalar_name(int32_t s) { return s >= 0 && s < 24 ? SCALAR_
 int stan_host_write_vtu(const char *path, int64_t n_nodes, const double *xyz, const double *disp, int64_t n_elem,
                         const int32_t *conn, int32_t n_point_arrays, const char *const *names, const double *point_values,
                         int32_t n_cell_arrays, const char *const *cell_names, const double *cell_values) {
+    return stan_host_write_vtu_components(path, n_nodes, xyz, disp, n_elem, conn, n_point_arrays, names, nullptr, point_values, n_cell_arrays,
+                                          cell_names, cell_values);
+}
+
+int stan_host_write_vtu_components(const char *path, int64_t n_nodes, const double *xyz, const double *disp, int64_t n_elem,
+                                   const int32_t *conn, int32_t n_point_arrays, const char *const *names, const int32_t *point_components,
+                                   const double *point_values, int32_t n_cell_arrays, const char *const *cell_names,
+                                   const double *cell_values) {
+    auto comps = [&](int32_t k) { return point_components ? point_components[k] : 1; };
+    for (int32_t k = 0; point_components && k < n_point_arrays; k++)
+        if (point_components[k] < 1) return STAN_HOST_E_ARG;
     if (!path || n_nodes <= 0 || !xyz || n_elem < 0 || (n_elem > 0 && !conn) || n_point_arrays < 0 || n_cell_arrays < 0 ||
         (n_point_arrays > 0 && (!names || !point_values)) || (n_cell_arrays > 0 && (!cell_names || !cell_values)))
         return STAN_HOST_E_ARG;
@@ -86,7 +97,7 @@ int stan_host_write_vtu(const char *path, int64_t n_nodes, const double *xyz, co
     array("Int64", "offsets", 1, ne * 8);
     array("UInt8", "types", 1, ne);
     head += "      </Cells>\n      <PointData>\n";
-    for (int32_t k = 0; k < n_point_arrays; k++) array("Float32", xml_escape(names[k]), 1, nn * 4);
+    for (int32_t k = 0; k < n_point_arrays; k++) array("Float32", xml_escape(names[k]), comps(k), nn * 4 * (uint64_t)comps(k));
     head += "      </PointData>\n      <CellData>\n";
     for (int32_t k = 0; k < n_cell_arrays; k++) array("Float32", xml_escape(cell_names[k]), 1, ne * 4);
     head += "      </CellData>\n    </Piece>\n  </UnstructuredGrid>\n  <AppendedData encoding=\"raw\">\n   _";
@@ -100,9 +111,11 @@ int stan_host_write_vtu(const char *path, int64_t n_nodes, const double *xyz, co
     ok = ok && put_array<int64_t>(f, ne * 8, [&](uint64_t i) { return (int64_t)conn[i]; });
     ok = ok && put_array<int64_t>(f, ne, [&](uint64_t i) { return (int64_t)(8 * (i + 1)); });
     ok = ok && put_array<uint8_t>(f, ne, [&](uint64_t) { return (uint8_t)12; });   // VTK_HEXAHEDRON
+    const double *pv = point_values;   // array k: [n_nodes][comps(k)]
     for (int32_t k = 0; ok && k < n_point_arrays; k++) {
-        const double *v = point_values + (uint64_t)k * nn;
-        ok = put_array<float>(f, nn, [&](uint64_t i) { return (float)v[i]; });
+        const uint64_t n = nn * (uint64_t)comps(k);
+        ok = put_array<float>(f, n, [&](uint64_t i) { return (float)pv[i]; });
+        pv += n;
     }
     for (int32_t k = 0; ok && k < n_cell_arrays; k++) {
         const double *v = cell_values + (uint64_t)k * ne;
